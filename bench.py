@@ -19,6 +19,9 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
   cpu_baseline : the CPU oracle (oracle/wm_oracle.c, kind "port") timed on this box's host cores on a
                  bounded sample of the same frames (rank 0, N=1 only)
   parity       : GPU vs oracle on those sample frames (max |d corr|, max rel |d a|)
+
+--dump-outputs DIR writes the outputs of the last timed step as .npy files (see dump_outputs) so that two builds can be
+compared output for output: the inputs depend on the arguments only.
 """
 import argparse
 import ctypes as C
@@ -398,6 +401,39 @@ def plumbing_only(args, torch, dist, rank, world):
     return 0 if ok and ranks_seen == world else 1
 
 
+# --dump-outputs: the watermarked planes of one step are 48 x 3840 x 2160 values at the default workload (1.6 GB in f32), so
+# they are kept as per-frame float64 sums (every pixel counts) plus this many pixels at fixed seeded positions (32 MB in f32)
+DUMP_Y_SAMPLE = 8 << 20
+DUMP_SEED = 20240611
+
+
+def dump_outputs(out_dir, np, torch, ys, a_out, corr_out, F):
+    """what the last timed step handed its caller, frame k = slot * F + f: makeWatermark's strength a and output plane y, and
+    detectWatermark's correlation.  Called after the barrier that closed the timed region (every slot collected), before any
+    later leg reuses the buffers.  Same arguments -> same inputs -> files two builds can be compared on."""
+    os.makedirs(out_dir, exist_ok=True)
+    S = len(ys)
+    a = np.array([a_out[sl][f] for sl in range(S) for f in range(F)], dtype=np.float32)
+    corr = np.array([corr_out[sl][f] for sl in range(S) for f in range(F)], dtype=np.float32)
+    y_sum = torch.cat([y.reshape(F, -1).sum(dim=1, dtype=torch.float64) for y in ys]).cpu().numpy()
+    per_slot = ys[0].numel()
+    total = S * per_slot
+    if total <= DUMP_Y_SAMPLE:
+        y_sample = torch.cat([y.reshape(-1) for y in ys]).to(torch.float32).cpu().numpy()
+    else:
+        # positions in the flat [S*F, rows, cols] stack of the step's outputs, sorted, duplicates dropped
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, total, DUMP_Y_SAMPLE, dtype=np.int64))
+        parts = []
+        for sl in range(S):
+            lo, hi = np.searchsorted(idx, [sl * per_slot, (sl + 1) * per_slot])
+            if hi > lo:
+                sel = torch.from_numpy(idx[lo:hi] - sl * per_slot).to(ys[sl].device)
+                parts.append(ys[sl].reshape(-1).index_select(0, sel).to(torch.float32).cpu())
+        y_sample = torch.cat(parts).numpy()
+    for name, arr in (("strength", a), ("correlation", corr), ("y_frame_sum", y_sum), ("y_sample", y_sample)):
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -423,7 +459,12 @@ def main():
     ap.add_argument("--sustain-seconds", type=float, default=1.0, help="span of the sustained repeat of the timed loop (0 = skip)")
     ap.add_argument("--stream-seconds", type=float, default=1.0, help="timed span of every part of the stream leg")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU work budget of the cpu_baseline sample")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step "
+                    "returned (rank 0's frames) as DIR/<name>.npy: per-frame strength and correlation, per-frame float64 sums of the "
+                    "watermarked planes and a fixed seeded sample of their pixels (at most 8 Mi values, 32 MB)")
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher around us: be the launcher (before torch is imported, let alone the GPU touched)
@@ -571,6 +612,8 @@ def main():
     # every frame of the timed steps must have been solvable: a run over passthrough frames would time nothing
     for sl in range(S):
         assert all(v == 0 for v in st_e[sl]) and all(v == 0 for v in st_d[sl]), "unsolvable frames in the timed region"
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, np, torch, ys, a_out, corr_out, F)
 
     # ---- per-kernel durations with hipEvents on the launch stream: a separate pass, every launch on slot 0's stream and
     # bracketed by its own pair of events (with several slots in flight kernels of different streams overlap and an event pair
