@@ -5,11 +5,14 @@
  * include/) may call, link or load this file.  Allowed users: tests/,
  * __graft_entry__.smoke() and bench.py's cpu_baseline leg, as the checker.
  *
- * PARITY UNPINNED: the reference (kar-dim/Watermarking-GPU @ 2025-05-23) holds no
- * tests, golden vectors or expected values for this path, and its own
- * implementation cannot be built here (ArrayFire + OpenCL + MSVC).
- * This file restates the published algorithm from the reference sources cited
- * per function below; it is cross-checked against an independent numpy
+ * The reference (kar-dim/Watermarking-GPU @ 2025-05-23) holds no tests, golden
+ * vectors or expected values for this path, and its host program cannot be built
+ * here (ArrayFire + OpenCL + MSVC).  This file restates the published
+ * algorithm from the reference sources cited per function below.  The parts that
+ * restate the three OpenCL kernels (wmo_nvf_mask, wmo_scaled_neighbors,
+ * wmo_gram_ref_partials) are held bit-exact to those kernels compiled from the
+ * reference source with its build options (oracle/build_ref.py,
+ * tests/test_ref_kernels.py); the rest is cross-checked against an independent numpy
  * restatement (tests/np_restatement.py) on the reference's sample image/W pair.
  *
  * Conventions: planes are row-major f32, x(r,c) = buf[r*cols + c];
@@ -184,12 +187,12 @@ static float tree_sum_f32(const float* v, size_t n, size_t stride)
  * (me_p3.hpp:61-67,76-82; threads beyond the image width contribute the zeros of the table's initialisation), and
  * af::sum folds the per-work-group partials (Watermark.cpp:148-149).
  */
-static int gram_ref_arith(const float* x, int rows, int cols, double Rx[64], double rx[8])
+/* the per-work-group partials of gram_ref_arith: part[(r * ngroups + g) * 44 + k], k = the 36 upper-triangle Rx sums
+ * (row-major) then the 8 rx sums; ngroups = ceil(cols / 64) */
+int wmo_gram_ref_partials(const float* x, int rows, int cols, float* part)
 {
+    if (!x || !part || rows < 1 || cols < 1) return WMO_BAD_ARG;
     const int ng = (cols + 63) / 64;
-    const size_t np = (size_t)rows * ng;
-    float* part = (float*)malloc(np * 44 * sizeof(float));
-    if (!part) return WMO_BAD_ARG;
 #pragma omp parallel for schedule(static)
     for (int r = 0; r < rows; r++) {
         const float* up = x + (size_t)clampi(r - 1, 0, rows - 1) * cols;
@@ -215,16 +218,33 @@ static int gram_ref_arith(const float* x, int rows, int cols, double Rx[64], dou
             memcpy(part + ((size_t)r * ng + g) * 44, acc, sizeof(acc));
         }
     }
+    return WMO_OK;
+}
+
+/* gram_ref_arith's fold of np work-group partials (af::sum stand-in: pairwise f32 tree) into the symmetric Rx and rx */
+int wmo_gram_ref_fold(const float* part, long long np, double Rx[64], double rx[8])
+{
+    if (!part || np < 1) return WMO_BAD_ARG;
     int k = 0;
     for (int i = 0; i < 8; i++)
         for (int j = i; j < 8; j++, k++) {
-            const double v = (double)tree_sum_f32(part + k, np, 44);
+            const double v = (double)tree_sum_f32(part + k, (size_t)np, 44);
             Rx[i * 8 + j] = v;
             Rx[j * 8 + i] = v;
         }
-    for (int i = 0; i < 8; i++) rx[i] = (double)tree_sum_f32(part + 36 + i, np, 44);
-    free(part);
+    for (int i = 0; i < 8; i++) rx[i] = (double)tree_sum_f32(part + 36 + i, (size_t)np, 44);
     return WMO_OK;
+}
+
+static int gram_ref_arith(const float* x, int rows, int cols, double Rx[64], double rx[8])
+{
+    const size_t np = (size_t)rows * ((cols + 63) / 64);
+    float* part = (float*)malloc(np * 44 * sizeof(float));
+    if (!part) return WMO_BAD_ARG;
+    int st = wmo_gram_ref_partials(x, rows, cols, part);
+    if (st == WMO_OK) st = wmo_gram_ref_fold(part, (long long)np, Rx, rx);
+    free(part);
+    return st;
 }
 
 /* af::solve (Watermark.cpp:203) in f32: LU with partial pivoting, same unsolvable rule as wmo_solve */
@@ -355,8 +375,9 @@ void wmo_error_sequence(const float* x, int rows, int cols, const float c[8], fl
 
 /*
  * NVF mask (nvf.hpp:37-50): p x p replicate-padded window, row-major tap order,
- * sum += v; sumSq = fma(v, v, sumSq) (-cl-mad-enable, main.cpp:106); mean = sum / p^2;
- * variance = sumSq / p^2 - mean * mean (two roundings, not fused); out = variance / (1 + variance).
+ * sum += v; sumSq = fma(v, v, sumSq); mean = sum / p^2; variance = fma(-mean, mean, sumSq / p^2);
+ * out = variance / (1 + variance).  Both fused operations are the contractions clang makes in nvf.hpp:44,48 under the
+ * reference's -cl-mad-enable (main.cpp:106): pinned bit-exact to the reference kernel by tests/test_ref_kernels.py.
  */
 int wmo_nvf_mask(const float* x, int rows, int cols, int p, float* m)
 {
@@ -376,7 +397,7 @@ int wmo_nvf_mask(const float* x, int rows, int cols, int p, float* m)
                 }
             }
             const float mean = sum / psq;
-            const float var = (sumsq / psq) - (mean * mean);
+            const float var = fmaf(-mean, mean, sumsq / psq);
             m[(size_t)r * cols + c] = var / (1.0f + var);
         }
     }

@@ -181,7 +181,9 @@ def main():
     out["_meta"] = {
         "psnr": 40.0, "p": 3,
         "generator": "tests/golden/make_golden.py (oracle/wm_oracle.c, exact-sum policy; cross-checked vs tests/np_restatement.py)",
-        "note": "expected values are NOT produced by the reference binary (unbuildable here); parity unpinned",
+        "note": "expected values are NOT produced by the reference binary (its host program is unbuildable here); the oracle's "
+                "nvf / scaled_neighbors_p3 / me arithmetic is pinned bit-exact to the reference's own kernels "
+                "(tests/test_ref_kernels.py), af::sum order and af::solve stay bracketed",
     }
     with open(f"{HERE}/golden.json", "w") as f:
         json.dump(out, f, indent=1, sort_keys=True)

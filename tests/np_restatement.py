@@ -56,7 +56,8 @@ def nvf_mask(x, p=3):
             ss = (v.astype(np.float64) * v.astype(np.float64) + ss.astype(np.float64)).astype(np.float32)
     psq = np.float32(p * p)
     mean = (s / psq).astype(np.float32)
-    var = ((ss / psq).astype(np.float32) - (mean * mean).astype(np.float32)).astype(np.float32)
+    # fma(-mean, mean, sumSq / p^2): mean^2 is exact in f64, one rounding to f32 (nvf.hpp:48 under -cl-mad-enable)
+    var = ((ss / psq).astype(np.float32).astype(np.float64) - mean.astype(np.float64) ** 2).astype(np.float32)
     return (var / (np.float32(1) + var)).astype(np.float32)
 
 

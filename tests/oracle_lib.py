@@ -39,6 +39,8 @@ def lib():
         L.wmo_strength_factor.restype = C.c_float
         L.wmo_strength_factor.argtypes = [C.c_float]
         L.wmo_gram.argtypes = [fp, C.c_int, C.c_int, dp, dp, op]
+        L.wmo_gram_ref_partials.argtypes = [fp, C.c_int, C.c_int, fp]
+        L.wmo_gram_ref_fold.argtypes = [fp, C.c_longlong, dp, dp]
         L.wmo_solve.argtypes = [dp, dp, fp]
         L.wmo_solve_f32.argtypes = [dp, dp, fp]
         L.wmo_scaled_neighbors.argtypes = [fp, C.c_int, C.c_int, fp, fp]
@@ -90,6 +92,23 @@ def gram(x, **kw):
     rx = np.zeros(8, np.float64)
     st = lib().wmo_gram(_f(x), x.shape[0], x.shape[1], _d(Rx), _d(rx), _opts(**kw))
     assert st == 0
+    return Rx, rx
+
+
+def gram_ref_partials(x):
+    """ref_arith's per-work-group sums [rows * ceil(cols / 64), 44]: the 36 upper-triangle Rx sums (row-major), the 8 rx"""
+    x = _c32(x)
+    part = np.empty((x.shape[0] * ((x.shape[1] + 63) // 64), 44), np.float32)
+    assert lib().wmo_gram_ref_partials(_f(x), x.shape[0], x.shape[1], _f(part)) == 0
+    return part
+
+
+def gram_ref_fold(part):
+    """ref_arith's f32 fold of work-group partials into (Rx 8x8, rx 8)"""
+    part = _c32(part)
+    Rx = np.zeros((8, 8), np.float64)
+    rx = np.zeros(8, np.float64)
+    assert lib().wmo_gram_ref_fold(_f(part), part.shape[0], _d(Rx), _d(rx)) == 0
     return Rx, rx
 
 

@@ -8,8 +8,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-# variance = sumSq / p^2 - mean^2 of pixels in [0, 255]: at most 255^2 = 65025 < 2^17; rounding can take it below zero by
-# far less than 0.5 (a constant region: |error| <~ 0.1)
+# variance = fma(-mean, mean, sumSq / p^2) of pixels in [0, 255]: at most 255^2 = 65025 < 2^17; rounding can take it below
+# zero by far less than 0.5 (a constant region of fractional grey: down to about -0.23 at p = 9)
 # (-0.0 itself is excluded: q - mean^2 is never -0 under round-to-nearest, and the sequence returns +0 for it)
 RANGES = [(0x00000000, 0x48000000), (0x80000001, 0xBF000000)]
 

@@ -166,7 +166,8 @@ def test_golden_fixtures(wm, torch_cuda, golden, tag):
         assert eng.detectWatermark(dev(torch, gray), mt) == pytest.approx(g[name]["corr_unmarked"], abs=TOL_CORR)
 
 
-def test_golden_crop_per_pixel(wm, torch_cuda, golden, pair_crop):
+def test_golden_crop_per_pixel_pinned_nvf(wm, torch_cuda, golden, pair_crop):
+    """per-pixel records of the crop; m_nvf / y_nvf follow nvf.hpp's fused variance (test_ref_kernels.py)"""
     import os
     from conftest import GOLDEN
     torch = torch_cuda

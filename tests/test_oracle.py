@@ -15,8 +15,17 @@ def test_strength_factor():
     assert abs(O.strength_factor(40.0) - float(NP.strength_factor(40.0))) < 1e-6
 
 
-@pytest.mark.parametrize("tag", ["512", "720p_crop"])
+@pytest.mark.parametrize("tag", ["512"])
 def test_golden_scalars(golden, tag):
+    check_golden_scalars(golden, tag)
+
+
+def test_golden_scalars_720p_crop_pinned_nvf(golden):
+    """the crop's NVF records, regenerated when the NVF variance was pinned to nvf.hpp's fused form (test_ref_kernels.py)"""
+    check_golden_scalars(golden, "720p_crop")
+
+
+def check_golden_scalars(golden, tag):
     from conftest import load_pair
     rgb, W = load_pair(golden, tag)
     gray = O.rgb2gray(rgb)
@@ -46,12 +55,13 @@ def test_golden_512_survey_values(golden):
                                                    -0.1014981, 0.4773920, -0.1693899], atol=2e-7)
     assert g["ME"]["a"] == pytest.approx(34.902996, rel=1e-6)
     assert g["ME"]["corr_rgb_harness"] == pytest.approx(0.7375435, abs=1e-6)
-    assert g["NVF"]["a"] == pytest.approx(2.852794, rel=1e-6)
+    assert g["NVF"]["a"] == pytest.approx(2.8527939, rel=1e-6)
     assert g["NVF"]["corr_rgb_harness"] == pytest.approx(0.5858539, abs=1e-6)
     assert g["max_abs_e"] == pytest.approx(57.679, abs=1e-3)
 
 
-def test_golden_crop_per_pixel(golden, pair_crop):
+def test_golden_crop_per_pixel_pinned_nvf(golden, pair_crop):
+    """per-pixel records of the crop; m_nvf / y_nvf follow nvf.hpp's fused variance (test_ref_kernels.py)"""
     import os
     from conftest import GOLDEN
     rgb, W = pair_crop
@@ -67,7 +77,8 @@ def test_golden_crop_per_pixel(golden, pair_crop):
 
 
 @pytest.mark.parametrize("shape", [(64, 64), (70, 131), (96, 200)])
-def test_oracle_vs_numpy_restatement(shape):
+def test_oracle_vs_numpy_restatement_pinned_nvf(shape):
+    """np_restatement.nvf_mask forms the variance as nvf.hpp does under -cl-mad-enable: fma(-mean, mean, sumSq / p^2)"""
     x = synth_frame(shape[0], shape[1], frame=3)
     W = synth_watermark(shape[0], shape[1])
     Rx, rx = O.gram(x)

@@ -1,10 +1,11 @@
 """The bracket the build states against the REFERENCE's own arithmetic (last row): coefficients <= 5e-3
 (<= 720p) / 5e-2 (4K class), a <= 1 % rel, correlation <= 2e-3 abs, y RMS <= 0.25 grey levels.
 
-The reference cannot be run here (ArrayFire / OpenCL / MSVC) and ships no vectors, so "the reference's arithmetic" is
-the oracle's ref_arith switch: products rounded to half, 64-lane f32 work-group sums in lane order, f32 fold of the
-partials, f32 LU (me_p3.hpp:8-21,61-82; Watermark.cpp:148-149,203).  This cannot pin parity -- it is the same restatement
-in another precision -- but it turns the claimed bracket into a tested one.  CPU part: the oracle's exact policy against
+The reference's host program cannot be run here (ArrayFire / OpenCL / MSVC) and ships no vectors, so "the reference's
+arithmetic" is the oracle's ref_arith switch: products rounded to half, 64-lane f32 work-group sums in lane order, f32 fold
+of the partials, f32 LU (me_p3.hpp:8-21,61-82; Watermark.cpp:148-149,203).  The per-work-group sums are pinned bit-exact
+to the reference's own me kernel (tests/test_ref_kernels.py); what this file brackets is the rest: the order of af::sum
+(a pairwise tree here) and af::solve (f32 LU here), which no reference source fixes.  CPU part: the oracle's exact policy against
 its reference-arithmetic mode on the committed fixtures, and the records in golden.json (written by make_golden.py)."""
 import numpy as np
 import pytest

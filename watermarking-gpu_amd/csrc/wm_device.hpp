@@ -159,7 +159,7 @@ __device__ __forceinline__ float div_inrange(float n, float d)
 // var / (1 + var) of the NVF mask (nvf.hpp:50) with d = 1 + var already formed: hardware reciprocal, product, ONE residual
 // correction -- 4 operations instead of the 11 of the IEEE division sequence (8 in div_inrange).  No error bound of v_rcp_f32
 // proves that in general; it does not have to: the divisor is a function of the dividend, so the inputs are a ONE-parameter
-// family, and the mask can only produce var = sumSq/p^2 - mean^2 of pixels in [0, 255], i.e. values in [-0.5, 2^17) with
+// family, and the mask can only produce var = fma(-mean, mean, sumSq/p^2) of pixels in [0, 255], i.e. values in [-0.5, 2^17) with
 // room to spare -- 2.2e9 floats.  Every one of them is checked on the device against the compiler's correctly rounded
 // division (wm_selftest_nvf_quotient, wm.h; tests/test_gpu_nvf_quotient.py, every round, on the hardware the kernels run on):
 // 0 differing results for this sequence on gfx950.  VARIANT selects what the self-test compares: 0 = div_inrange (8

@@ -159,7 +159,8 @@ constexpr int PFW = WM_PFW;  // rows of W / base prefetched per wave
 
 // =================================================================================================
 // NVF value of pixel k from a window of 2*PAD+1 rows (nvf.hpp:37-50): row-major taps,
-// sum += v; sumSq = fma(v, v, sumSq); mean = sum / p^2; var = sumSq / p^2 - mean*mean; var / (1 + var)
+// sum += v; sumSq = fma(v, v, sumSq); mean = sum / p^2; var = fma(-mean, mean, sumSq / p^2); var / (1 + var)
+// (both fmas are the contractions the reference's -cl-mad-enable build makes, main.cpp:106; tests/test_ref_kernels.py)
 // =================================================================================================
 template <int PAD>
 __device__ __forceinline__ float nvf_from_sums(float sum, float sumsq)
@@ -169,7 +170,7 @@ __device__ __forceinline__ float nvf_from_sums(float sum, float sumsq)
     constexpr float psq = (float)((2 * PAD + 1) * (2 * PAD + 1));
     constexpr float rpsq = 1.0f / psq;
     const float mean = div_by(sum, psq, rpsq);
-    const float var = div_by(sumsq, psq, rpsq) - (mean * mean);
+    const float var = fmaf(-mean, mean, div_by(sumsq, psq, rpsq));
     return nvf_quot(var, 1.0f + var);
 }
 
