@@ -118,6 +118,42 @@ private:
 
 }  // namespace wm
 
+// A bank of watermark keys on one device (wm.h wm_keys_*): what Watermark::detectWatermarkKeys scores one image against.
+// Owns its device planes; movable, not copyable.  Errors throw std::runtime_error like the Watermark methods.
+class WatermarkKeys {
+public:
+    WatermarkKeys(const dim_t rows, const dim_t cols, const int nkeys, const int device = 0)
+    {
+        wm_keys* k = nullptr;
+        check(wm_keys_create(&k, device, (int)rows, (int)cols, nkeys), "WatermarkKeys");
+        keys = k;
+    }
+    WatermarkKeys(const WatermarkKeys&) = delete;
+    WatermarkKeys& operator=(const WatermarkKeys&) = delete;
+    WatermarkKeys(WatermarkKeys&& other) noexcept : keys(other.keys) { other.keys = nullptr; }
+    WatermarkKeys& operator=(WatermarkKeys&& other) noexcept
+    {
+        if (this != &other) { wm_keys_destroy(keys); keys = other.keys; other.keys = nullptr; }
+        return *this;
+    }
+    ~WatermarkKeys() { wm_keys_destroy(keys); }
+
+    // key k := host floats [rows * cols], a W file (loadRandomMatrix's checks), or the W generated from a seed
+    void set(int k, const float* host_w) { check(wm_keys_set(keys, k, host_w, WM_MEM_HOST), "WatermarkKeys::set"); }
+    void load(int k, const std::string& randomMatrixPath) { check(wm_keys_load_file(keys, k, randomMatrixPath.c_str()), "WatermarkKeys::load"); }
+    void generate(int k, uint32_t seed) { check(wm_keys_generate(keys, k, seed), "WatermarkKeys::generate"); }
+    int count() const { return wm_keys_count(keys); }
+    dim2 size() const { return {wm_keys_rows(keys), wm_keys_cols(keys)}; }
+    const wm_keys* handle() const { return keys; }
+
+private:
+    wm_keys* keys = nullptr;
+    static void check(int rc, const char* where)
+    {
+        if (rc != WM_OK) throw std::runtime_error(std::string("ERROR in ") + where + ": " + wm_strerror(rc) + " Error code: " + std::to_string(rc) + "\n");
+    }
+};
+
 /*!
  *  \brief  Functions for watermark computation and detection (MI355X-native engine behind the reference's surface)
  */
@@ -178,6 +214,16 @@ public:
         float corr = 0.0f;
         const int rc = wm_detect(ctx, (int)maskType, &pimg, &corr, nullptr, WM_SLOT_SYNC);
         if (rc < 0) fail(rc, "detectWatermark");
+        return corr;
+    }
+    // detectWatermark of one grey image against every key of `keys` in one call (wm.h wm_detect_keys): score k is what
+    // detectWatermark returns with key k as W (0.0f for every key when the prediction system is not solvable)
+    std::vector<float> detectWatermarkKeys(const wm::Image& watermarkedImage, const WatermarkKeys& keys, MASK_TYPE maskType) const
+    {
+        const wm_plane pimg = watermarkedImage.plane();
+        std::vector<float> corr((size_t)keys.count(), 0.0f);
+        const int rc = wm_detect_keys(ctx, (int)maskType, &pimg, keys.handle(), corr.data(), nullptr, WM_SLOT_SYNC);
+        if (rc < 0) fail(rc, "detectWatermarkKeys");
         return corr;
     }
     // makeWatermark, then detectWatermark on its result (the pair testForImage runs per image, main.cpp:165-220), as ONE call:

@@ -175,6 +175,42 @@ int wm_detect(wm_ctx* ctx, int mask, const wm_plane* img, float* corr_out, int* 
 int wm_embed_detect(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* base, const wm_plane* out, float* a_out,
                     float* corr_out, int* status_out, int slot);
 
+/* ---- Key identification: one image against a bank of watermark keys ------------------------------------------------------
+ * A bank holds K watermark planes (the W of wm_create) of one rows x cols shape on one device, stacked as ONE device allocation
+ * [K][rows][cols] f32, row-major (each plane in the W file's layout, Watermark.cpp:62-75).  The bank always owns a copy of its
+ * planes; every fill call completes before it returns.  Argument errors (nkeys < 1 or > WM_KEYS_MAX, k out of range, rows or
+ * cols outside 1..32768, null pointers) return WM_ERR_BAD_ARG before any device is touched; WM_ERR_ALLOC when the bank does
+ * not fit.  A new bank's planes are zero. */
+#define WM_KEYS_MAX 4096
+typedef struct wm_keys wm_keys;
+int wm_keys_create(wm_keys** out, int device, int rows, int cols, int nkeys);
+void wm_keys_destroy(wm_keys* keys);
+int wm_keys_count(const wm_keys* keys);
+int wm_keys_rows(const wm_keys* keys);
+int wm_keys_cols(const wm_keys* keys);
+const float* wm_keys_device_ptr(const wm_keys* keys, int k);  /* device plane of key k (NULL if out of range) */
+/* key k := rows*cols floats at `w`, a host (WM_MEM_HOST) or device (WM_MEM_DEVICE) array */
+int wm_keys_set(wm_keys* keys, int k, const float* w, int mem);
+/* key k := a W file (loadRandomMatrix, Watermark.cpp:62-75): WM_ERR_W_OPEN / WM_ERR_W_SIZE as wm_create_from_file */
+int wm_keys_load_file(wm_keys* keys, int k, const char* path);
+/* key k := the W of wm_create_generated(..., seed), bit for bit (the same device generator) */
+int wm_keys_generate(wm_keys* keys, int k, uint32_t seed);
+
+/* detectWatermark (Watermark.cpp:234-250) of every frame of `img` against EVERY key of the bank: whose key is in this copy?
+ * corr_out[frames][nkeys] (row-major), status_out[frames] (may be NULL).  Takes every input wm_detect takes (f32 / u8, any
+ * pitch and width, WM_MEM_HOST, WM_MEM_SLOT_OUT, batches up to max_frames, ME with p = 3, NVF with p = 3..9); the context
+ * supplies shape, p and device -- its own W is not used -- and a bank of another shape or device is WM_ERR_BAD_ARG.  The image
+ * side runs once for all keys (wm_detect's Gram sweep, hand-over included, and solve); one sweep then reads the image once per
+ * group of keys and every key plane once (k_detect_keys).  Key k's score is wm_detect's with key k as W on the batched sweeps, bit
+ * for bit.  An unsolvable frame has status WM_UNSOLVABLE and 0.0f for every key (Watermark.cpp:246-247).
+ * An ENQUEUE on the slot like wm_detect (WM_SLOT_SYNC: slot 0, waits); it may share a slot with embeds and detects in any order.
+ * frames * nkeys results count against the slot's capacity of 4096 un-synced results (shared with the other calls' one result per
+ * frame); beyond it the call returns WM_ERR_BUSY.  Never takes the fused single-launch kernels.
+ *
+ * HAZARD.  The kernels read the bank when the stream reaches them: the bank must stay ALIVE and UNMODIFIED (no wm_keys_set /
+ * _load_file / _generate / _destroy on it) until wm_sync of this slot has returned.  The library does not check this. */
+int wm_detect_keys(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* keys, float* corr_out, int* status_out, int slot);
+
 /* Building blocks exposed for parity tests (the reference keeps them private):
  * computeCustomMask / computePredictionErrorMask (Watermark.cpp:96-114,176-218).
  * mask_out / e_out: f32 device planes [rows,cols] (e_out may be NULL; ignored for NVF).

@@ -23,6 +23,7 @@ WM_ERR_BAD_ARG, WM_ERR_NO_DEVICE, WM_ERR_ALLOC, WM_ERR_PSNR, WM_ERR_BUSY = -5, -
 WM_SLOT_SYNC = -1
 WM_F32, WM_U8 = 0, 1
 WM_MEM_DEVICE, WM_MEM_HOST, WM_MEM_SLOT_OUT = 0, 1, 2
+WM_KEYS_MAX = 4096
 
 
 class MASK_TYPE(enum.IntEnum):
@@ -60,6 +61,16 @@ ABI = [
     ("wm_embed", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), _P(wm_plane), _P(wm_plane), _P(C.c_float), _P(C.c_int), C.c_int]),
     ("wm_detect", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), _P(C.c_float), _P(C.c_int), C.c_int]),
     ("wm_embed_detect", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), _P(wm_plane), _P(wm_plane), _P(C.c_float), _P(C.c_float), _P(C.c_int), C.c_int]),
+    ("wm_keys_create", C.c_int, [_P(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("wm_keys_destroy", None, [C.c_void_p]),
+    ("wm_keys_count", C.c_int, [C.c_void_p]),
+    ("wm_keys_rows", C.c_int, [C.c_void_p]),
+    ("wm_keys_cols", C.c_int, [C.c_void_p]),
+    ("wm_keys_device_ptr", C.c_void_p, [C.c_void_p, C.c_int]),
+    ("wm_keys_set", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    ("wm_keys_load_file", C.c_int, [C.c_void_p, C.c_int, C.c_char_p]),
+    ("wm_keys_generate", C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
+    ("wm_detect_keys", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), C.c_void_p, _P(C.c_float), _P(C.c_int), C.c_int]),
     ("wm_compute_mask", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), _P(wm_plane), _P(wm_plane), _P(C.c_float), _P(C.c_int), C.c_int]),
     ("wm_gram", C.c_int, [_ctx_p, _P(wm_plane), _P(C.c_double), C.c_int]),
     ("wm_band_configure", C.c_int, [_ctx_p, C.c_int, C.c_int, C.c_longlong]),
@@ -166,6 +177,100 @@ def plane_of(t, channels=1, batched=None):
         raise RuntimeError("channel dimension mismatch")
     return wm_plane(t.data_ptr(), t.shape[-2], t.shape[-1], channels, dt, WM_MEM_DEVICE, frames, t.stride(-2), cstride,
                     fstride)
+
+
+class KeySet:
+    """A bank of watermark keys on one device (wm.h wm_keys_*): K planes [rows, cols] f32 that Watermark.detectKeys scores an
+    image against in one call.  The bank owns copies of its planes."""
+
+    def __init__(self, rows, cols, nkeys, device=0):
+        self._keys = C.c_void_p()
+        rc = lib().wm_keys_create(C.byref(self._keys), device, rows, cols, nkeys)
+        if rc != WM_OK:
+            self._keys = C.c_void_p()
+            _raise(rc)
+
+    @classmethod
+    def from_seeds(cls, rows, cols, seeds, device=0):
+        """key k = the W of Watermark.generated(rows, cols, seeds[k], ...) (wm_keys_generate)"""
+        seeds = list(seeds)
+        self = cls(rows, cols, len(seeds), device)
+        for k, sd in enumerate(seeds):
+            self._chk(lib().wm_keys_generate(self._keys, k, int(sd) & 0xFFFFFFFF))
+        return self
+
+    @classmethod
+    def from_files(cls, paths, rows, cols, device=0):
+        """key k = the raw f32 W file paths[k] (wm_keys_load_file)"""
+        paths = list(paths)
+        self = cls(rows, cols, len(paths), device)
+        for k, p in enumerate(paths):
+            self._chk(lib().wm_keys_load_file(self._keys, k, os.fsencode(p)))
+        return self
+
+    def _chk(self, rc):
+        if rc != WM_OK:
+            self.close()
+            _raise(rc)
+
+    def set(self, k, w):
+        """key k := a [rows, cols] float32 torch tensor (on the GPU or not) or numpy array"""
+        if isinstance(w, np.ndarray):
+            a = np.ascontiguousarray(w, dtype=np.float32)
+            if a.size != self.rows * self.cols:
+                _raise(WM_ERR_BAD_ARG)
+            rc = lib().wm_keys_set(self._keys, k, a.ctypes.data_as(C.c_void_p), WM_MEM_HOST)
+        else:
+            import torch
+            t = w.detach().to(torch.float32).contiguous()
+            if t.numel() != self.rows * self.cols:
+                _raise(WM_ERR_BAD_ARG)
+            if t.is_cuda:
+                torch.cuda.current_stream().synchronize()
+            rc = lib().wm_keys_set(self._keys, k, C.c_void_p(t.data_ptr()), WM_MEM_DEVICE if t.is_cuda else WM_MEM_HOST)
+        if rc != WM_OK:
+            _raise(rc)
+
+    def plane(self, k):
+        """key k as a numpy array [rows, cols] (downloaded)"""
+        w = np.empty((self.rows, self.cols), np.float32)
+        p = lib().wm_keys_device_ptr(self._keys, k)
+        if not p:
+            _raise(WM_ERR_BAD_ARG)
+        rc = lib().wm_memcpy_d2h(w.ctypes.data_as(C.c_void_p), p, w.nbytes)
+        if rc != WM_OK:
+            _raise(rc)
+        return w
+
+    @property
+    def handle(self):
+        return self._keys
+
+    @property
+    def count(self):
+        return lib().wm_keys_count(self._keys)
+
+    def __len__(self):
+        return self.count
+
+    @property
+    def rows(self):
+        return lib().wm_keys_rows(self._keys)
+
+    @property
+    def cols(self):
+        return lib().wm_keys_cols(self._keys)
+
+    def close(self):
+        if getattr(self, "_keys", None):
+            lib().wm_keys_destroy(self._keys)
+            self._keys = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Watermark:
@@ -325,6 +430,20 @@ class Watermark:
             return corr[0]
         return list(corr)
 
+    def detectKeys(self, image, keys, maskType):
+        """detectWatermark of `image` against every key of the KeySet `keys` in one call (wm.h wm_detect_keys): a float32 numpy
+        array [frames, K] ([K] for one grey frame); 0.0 for every key of an unsolvable frame"""
+        import torch
+        pimg = plane_of(image, 1)
+        frames, K = pimg.frames, keys.count
+        corr = np.zeros((frames, K), np.float32)
+        torch.cuda.current_stream().synchronize()
+        rc = lib().wm_detect_keys(self._ctx, int(maskType), C.byref(pimg), keys.handle, corr.ctypes.data_as(_P(C.c_float)), None,
+                                  WM_SLOT_SYNC)
+        if rc < 0:
+            _raise(rc, self._ctx)
+        return corr[0] if image.dim() == 2 else corr
+
     def makeAndDetect(self, inputImage, outputImage, maskType, out=None):
         """makeWatermark followed by detectWatermark on its result (testForImage's pair, main.cpp:165-220) as one call
         (wm.h wm_embed_detect; grey output).  Returns (watermarked, strength or None, correlation)."""
@@ -371,6 +490,21 @@ class Watermark:
     def detect_async(self, image, maskType, slot, corr_out=None, status_out=None):
         pimg = self._as_plane(image, 1)
         rc = lib().wm_detect(self._ctx, int(maskType), C.byref(pimg), corr_out, status_out, slot)
+        if rc < 0:
+            _raise(rc, self._ctx)
+
+    def detect_keys_async(self, image, keys, maskType, slot, corr_out, status_out=None):
+        """wm_detect_keys enqueued on `slot`: corr_out (frames * K floats: a ctypes array or a C-contiguous float32 numpy array)
+        and status_out (frames ints, may be None) are written by sync(slot); `keys` must stay alive and unmodified until then"""
+        pimg = self._as_plane(image, 1)
+        if isinstance(corr_out, np.ndarray):
+            assert corr_out.dtype == np.float32 and corr_out.flags.c_contiguous
+            corr_out = corr_out.ctypes.data_as(_P(C.c_float))
+        if isinstance(status_out, np.ndarray):
+            assert status_out.dtype == np.int32 and status_out.flags.c_contiguous
+            status_out = status_out.ctypes.data_as(_P(C.c_int))
+        rc = lib().wm_detect_keys(self._ctx, int(maskType), C.byref(pimg), keys.handle if isinstance(keys, KeySet) else keys,
+                                  corr_out, status_out, slot)
         if rc < 0:
             _raise(rc, self._ctx)
 

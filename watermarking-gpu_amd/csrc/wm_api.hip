@@ -5,6 +5,7 @@
 #include "../../include/wm.h"
 #include "wm_kernels.hpp"
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -35,8 +36,9 @@ constexpr int TARGET_WAVES_ME = 1280;
 constexpr int TARGET_WAVES_NVF = 2048;
 
 // the fold steps (solve, embed scalars, correlation) are tails of k_gram / k_*_stats / k_detect: no kernels of their own
-enum KernelId { K_GRAM = 0, K_ME_STATS, K_NVF_STATS, K_EMBED, K_DETECT, K_MASK, K_FUSED_EMBED, K_FUSED_DETECT, K_GRAM_HO, K_FUSED_PAIR, K_COUNT };
-const char* const kKernelNames[K_COUNT] = {"k_gram", "k_me_stats", "k_nvf_stats", "k_embed", "k_detect", "k_mask", "k_fused_embed", "k_fused_detect", "k_gram_ho", "k_fused_pair"};
+enum KernelId { K_GRAM = 0, K_ME_STATS, K_NVF_STATS, K_EMBED, K_DETECT, K_MASK, K_FUSED_EMBED, K_FUSED_DETECT, K_GRAM_HO, K_FUSED_PAIR, K_DETECT_KEYS, K_COUNT };
+const char* const kKernelNames[K_COUNT] = {"k_gram", "k_me_stats", "k_nvf_stats", "k_embed", "k_detect", "k_mask", "k_fused_embed", "k_fused_detect", "k_gram_ho", "k_fused_pair",
+                                           "k_detect_keys"};
 
 // fused single-frame launches use every CU and wait for each other inside the launch: two of them in flight on one device
 // could each hold a part of the CUs and starve the other (their spins are bounded, so that would be a slow fallback, not a
@@ -82,6 +84,7 @@ struct Pending {
     int* status_out;
     float* coef_out;  // host destination for 8*frames coefficients (mask-only ops)
     int coef_off;
+    int nkeys = 0;    // wm_detect_keys: frames * nkeys records, value_out [frames][nkeys], status_out [frames]
 };
 
 struct Slot {
@@ -133,6 +136,8 @@ struct Slot {
     void* st_in = nullptr; size_t st_in_bytes = 0;
     void* st_base = nullptr; size_t st_base_bytes = 0;
     void* st_out = nullptr; size_t st_out_bytes = 0;
+    // wm_detect_keys: per-(frame, key) partial records of k_detect_keys (grown on demand)
+    void* keys_part = nullptr; size_t keys_part_bytes = 0;
 };
 
 struct ProfRec { int kid; hipEvent_t a, b; bool first; };  // first: the sweep's first launch (counts the call)
@@ -175,6 +180,14 @@ struct wm_ctx {
     uint64_t prof_n[K_COUNT] = {0};
     double prof_ms[K_COUNT] = {0};
     ~wm_ctx();  // releases streams, scratch and events (also on the error paths of wm_create / wm_clone)
+};
+
+// a bank of watermark keys (wm_keys_*): K planes of one shape on one device, one allocation [K][rows][cols]
+struct wm_keys {
+    int device = 0;
+    int rows = 0, cols = 0, nkeys = 0;
+    float* d = nullptr;
+    ~wm_keys() { if (d) { (void)hipSetDevice(device); (void)hipFree(d); } }
 };
 
 namespace {
@@ -318,6 +331,7 @@ void free_slot(Slot& s)
     if (s.h_res) (void)hipHostFree(s.h_res);
     if (s.h_coefres) (void)hipHostFree(s.h_coefres);
     (void)hipFree(s.st_in); (void)hipFree(s.st_base); (void)hipFree(s.st_out); (void)hipFree(s.fz_block); (void)hipFree(s.d_ho); (void)hipFree(s.d_hoseam);
+    (void)hipFree(s.keys_part);
     s = Slot();
 }
 
@@ -743,6 +757,16 @@ int deliver(Slot& s)
 {
     int rc = WM_OK;
     for (auto& pd : s.pending) {
+        if (pd.nkeys > 0) {
+            // wm_detect_keys: record f * nkeys + k; every key of a frame carries the frame's status
+            for (int f = 0; f < pd.frames; ++f) {
+                const int st = s.h_res[pd.res_off + f * pd.nkeys].status;
+                if (pd.status_out) pd.status_out[f] = st;
+                if (st != 0) rc = WM_UNSOLVABLE;
+                for (int k = 0; k < pd.nkeys; ++k) pd.value_out[f * pd.nkeys + k] = s.h_res[pd.res_off + f * pd.nkeys + k].value;
+            }
+            continue;
+        }
         for (int f = 0; f < pd.frames; ++f) {
             const OpResult& r = s.h_res[pd.res_off + f];
             if (pd.status_out) pd.status_out[f] = r.status;
@@ -1335,6 +1359,113 @@ int wm_embed_detect(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_pla
     const int rd = wm_detect(ctx, mask, &slot_plane, corr_out, nullptr, WM_SLOT_SYNC);
     if (rd < 0 && !s.pending.empty()) (void)do_sync(ctx, s);  // (never leave the embed's result queued behind a failed call)
     return rd;
+}
+
+// ---- key banks (wm_keys_*) and the multi-key detector ------------------------------------------------------------------
+int wm_keys_create(wm_keys** out, int device, int rows, int cols, int nkeys)
+{
+    if (!out) return WM_ERR_BAD_ARG;
+    *out = nullptr;
+    if (rows < 1 || cols < 1 || rows > 32768 || cols > 32768 || nkeys < 1 || nkeys > WM_KEYS_MAX) return WM_ERR_BAD_ARG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return WM_ERR_NO_DEVICE;
+    if (device < 0 || device >= ndev) device = 0;  // (wm_create's rule, main.cpp:73-78)
+    if (hipSetDevice(device) != hipSuccess) return WM_ERR_NO_DEVICE;
+    std::unique_ptr<wm_keys> k(new wm_keys);
+    k->device = device; k->rows = rows; k->cols = cols; k->nkeys = nkeys;
+    const size_t bytes = (size_t)nkeys * rows * cols * sizeof(float);
+    if (hipMalloc((void**)&k->d, bytes) != hipSuccess) { (void)hipGetLastError(); k->d = nullptr; return WM_ERR_ALLOC; }
+    if (hipMemset(k->d, 0, bytes) != hipSuccess) return WM_ERR_RUNTIME;
+    *out = k.release();
+    return WM_OK;
+}
+
+void wm_keys_destroy(wm_keys* keys) { delete keys; }
+
+int wm_keys_count(const wm_keys* keys) { return keys ? keys->nkeys : 0; }
+int wm_keys_rows(const wm_keys* keys) { return keys ? keys->rows : 0; }
+int wm_keys_cols(const wm_keys* keys) { return keys ? keys->cols : 0; }
+const float* wm_keys_device_ptr(const wm_keys* keys, int k)
+{
+    if (!keys || k < 0 || k >= keys->nkeys) return nullptr;
+    return keys->d + (size_t)k * keys->rows * keys->cols;
+}
+
+int wm_keys_set(wm_keys* keys, int k, const float* w, int mem)
+{
+    if (!keys || !w || k < 0 || k >= keys->nkeys || (mem != WM_MEM_DEVICE && mem != WM_MEM_HOST)) return WM_ERR_BAD_ARG;
+    if (hipSetDevice(keys->device) != hipSuccess) return WM_ERR_RUNTIME;
+    const size_t n = (size_t)keys->rows * keys->cols;
+    if (hipMemcpy(keys->d + (size_t)k * n, w, n * sizeof(float), mem == WM_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice) != hipSuccess ||
+        hipDeviceSynchronize() != hipSuccess)
+        return WM_ERR_RUNTIME;
+    return WM_OK;
+}
+
+int wm_keys_load_file(wm_keys* keys, int k, const char* path)
+{
+    if (!keys || !path || k < 0 || k >= keys->nkeys) return WM_ERR_BAD_ARG;
+    std::vector<float> w;
+    const int rc = read_w_file(nullptr, path, keys->rows, keys->cols, w);  // (loadRandomMatrix's checks: WM_ERR_W_OPEN, WM_ERR_W_SIZE)
+    if (rc != WM_OK) return rc;
+    return wm_keys_set(keys, k, w.data(), WM_MEM_HOST);
+}
+
+int wm_keys_generate(wm_keys* keys, int k, uint32_t seed)
+{
+    if (!keys || k < 0 || k >= keys->nkeys) return WM_ERR_BAD_ARG;
+    if (hipSetDevice(keys->device) != hipSuccess) return WM_ERR_RUNTIME;
+    // wm_create_generated's launch: the same kernel and grid, so the plane is that context's W bit for bit
+    launch_gen_w(nullptr, keys->d + (size_t)k * keys->rows * keys->cols, keys->rows, keys->cols, seed);
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return WM_ERR_RUNTIME;
+    return WM_OK;
+}
+
+int wm_detect_keys(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* keys, float* corr_out, int* status_out, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    if (mask != WM_MASK_ME && mask != WM_MASK_NVF) return fail(ctx, WM_ERR_BAD_ARG, "bad mask type");
+    if (ctx->p != 3 && mask == WM_MASK_ME) return fail(ctx, WM_ERR_BAD_P, "ME mask needs p == 3 (main.cpp:89)");
+    if (!keys || !corr_out) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_keys: null keys or corr_out");
+    if (keys->device != ctx->device || keys->rows != ctx->rows || keys->cols != ctx->cols)
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_keys: the key bank is " + std::to_string(keys->rows) + "x" + std::to_string(keys->cols) + " on device " +
+                                             std::to_string(keys->device) + ", the engine " + std::to_string(ctx->rows) + "x" + std::to_string(ctx->cols) +
+                                             " on device " + std::to_string(ctx->device));
+    if (ctx->band_hi > 0) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_keys: not in band mode");
+    Slot* sp; bool sync_after;
+    int rc = get_slot(ctx, slot, &sp, &sync_after);
+    if (rc != WM_OK) return rc;
+    Slot& s = *sp;
+    if ((rc = check_plane(ctx, img, 0, false, "image", true)) != WM_OK) return rc;
+    const int frames = img->frames;
+    const int nkeys = keys->nkeys;
+    if ((long long)s.res_used + (long long)frames * nkeys > RES_CAP)
+        return fail(ctx, WM_ERR_BUSY, "too many un-synced results on this slot (frames x keys count against " + std::to_string(RES_CAP) + ")");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    PlaneDesc xd;
+    if ((rc = prep_input(ctx, s, img, &xd)) != WM_OK) return rc;
+    LaunchGeom lg;
+    if ((rc = geom_checked(ctx, frames, mask, &lg)) != WM_OK) return rc;
+    // partial records: [frames][nkeys][rstride][2] + [frames][rstride]
+    const int rstride = std::max(ctx->max_nblk, ctx->max_nrec);
+    const size_t need = (size_t)frames * (2 * (size_t)nkeys + 1) * rstride * sizeof(double);
+    if ((rc = ensure(ctx, &s.keys_part, &s.keys_part_bytes, need)) != WM_OK) return rc;
+    const int aligned_w = fits_32bit(ctx->rows, ctx->cols, WM_F32) ? 1 : 0;
+    const long long kstride = (long long)ctx->rows * ctx->cols;
+    OpResult* res = s.d_res + s.res_used;
+    // the image side is wm_detect's: the Gram sweep (or the hand-over of the slot's last embed) and the solve
+    if ((rc = gram_sweep(ctx, s, lg, frames, xd, img)) != WM_OK) return rc;
+    {
+        ProfScope ps(ctx, K_DETECT_KEYS, s.stream);
+        if (launch_detect_keys(s.stream, lg, frames, mask, ctx->p / 2, xd, keys->d, kstride, nkeys, aligned_w, s.d_coef, s.d_status,
+                               (double*)s.keys_part, rstride, res) != 0)
+            return fail(ctx, WM_ERR_RUNTIME, "wm_detect_keys: geometry exceeds the record arrays");
+    }
+    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
+    if ((rc = push_pending(ctx, s, frames * nkeys, corr_out, status_out, nullptr)) != WM_OK) return rc;
+    s.pending.back().frames = frames;
+    s.pending.back().nkeys = nkeys;
+    return sync_after ? do_sync(ctx, s) : WM_OK;
 }
 
 int wm_compute_mask(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* mask_out, const wm_plane* e_out,

@@ -1,0 +1,413 @@
+// wm_k_detect_keys.hip -- k_detect_keys: the detector of ONE image against a bank of K watermark keys (wm_detect_keys, wm.h)
+// with its fold kernel k_keys_fold.
+//
+// Everything on the image side of the detector is independent of the key (Watermark.cpp:221-250): the coefficients c (one
+// Gram sweep + solve, wm_api.hip gram_sweep), e_w = x - c.nbrs(x), the mask m (ME: |e_w|, NVF: nvf(x)) and ||e_w||^2.  Only
+// u_k = m W_k, e_u_k = u_k - c.nbrs(u_k), <e_u_k, e_w> and ||e_u_k||^2 change with the key.  k_detect_keys is k_detect's strip
+// march (wm_k_detect.hip detect_march) with a compile-time group of KG keys inside every row step: x, e_w and m are formed
+// once per row, then every key of the group loads its W row, forms its rolling u window and runs its residual4 chain.  K > KG
+// is a grid axis over key groups (x is marched again per group; the groups of one tile run back to back on one XCD, so those
+// re-reads are L2 hits).  Per key the per-pixel operations, their order and the partial-sum grouping are k_detect's: a key's
+// score is bit-identical to wm_detect's with that key as W (tests/test_gpu_keys.py).
+#include "wm_march.hpp"
+
+#ifndef WM_KEYS_G
+#define WM_KEYS_G 2   // keys per group (registers vs. x re-reads)
+#endif
+#ifndef WM_PFW_KEYS
+#define WM_PFW_KEYS 2  // W rows in flight per key (must divide UNROLL): 2 keys x 2 rows keep as many W loads in flight per wave as
+                       // k_detect's 3 rows, and with 3 rows the f32 ME instance spills at 3 waves per SIMD
+#endif
+
+namespace wmk {
+
+constexpr int KG = WM_KEYS_G;
+constexpr int PFK = WM_PFW_KEYS;
+static_assert(UNROLL % PFK == 0, "the W prefetch ring must divide the march group");
+
+struct KeysArgs {
+    const float* W;     // the bank [nkeys][rows][cols]
+    long long kstride;  // elements between key planes
+    int nkeys;
+    int ngroups;        // key groups = grid blocks per tile
+    int rstride;        // partial records per (frame, key): >= the sweep's blocks (nblk_total) and wave records (nrec)
+    double* part;       // [frames][nkeys][rstride][2]  {<e_u,e_w>, ||e_u||^2}
+    double* partw;      // [frames][rstride]            ||e_w||^2 (written by key group 0)
+};
+
+// the march of detect_march (wm_k_detect.hip) with the key-dependent half repeated for the KG keys of the group
+template <typename T, int MASK, int PAD, int HC, bool VEC, bool EDGE>
+__device__ __forceinline__ void keys_march(const T* __restrict__ xf, long long pitch, const float* const (&Wk)[KG],
+                                           const Geom& g, const WaveJob& j, float* lds_x, float* lds_u,
+                                           const float (&c)[8], float (&dot)[KG], float (&nu)[KG], float& nw)
+{
+    constexpr int HRX = MASK == 0 ? 1 : PAD;
+    constexpr int NR = 2 * HRX + 1;
+    constexpr int O = 4 * HC;
+    constexpr int MID = HRX;
+    const int R = g.rows, C = g.cols;
+    float nc[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) nc[k] = -c[k];
+    const int t0 = j.rs > 0 ? j.rs - 1 : 0;
+    const int t1 = j.re < R ? j.re : R - 1;
+    const int nu_rows = t1 - t0 + 1;
+    const int n = nu_rows + 2 * HRX;
+    constexpr bool HALO1 = VEC && HC == 1 && (MASK == 0 || PAD <= 3);
+    XMarch<T, HC, HALO1 ? HRX : HRX + 1, NR, VEC, PFX, EDGE, HALO1, UNROLL> xm;
+    PMarch<float, VEC, PFK> wm_[KG];
+    const int c0 = j.c0s + 4 * j.lane;
+    const bool left_edge = EDGE && j.c0s == 0;
+    const bool has_right = !EDGE || j.c0s + STRIP <= C - 1;
+    xm.start(xf, pitch, g, j, lds_x, t0 - HRX, n);
+#pragma unroll
+    for (int q = 0; q < KG; ++q) wm_[q].start(Wk[q], C, C, j, t0, nu_rows);
+    const int wh_col = j.lane == WAVE - 1 ? (j.c0s + STRIP < C ? j.c0s + STRIP : C - 1) : (j.c0s > 0 ? j.c0s - 1 : 0);
+    const unsigned wh_off = (unsigned)wh_col * 4u;
+    auto load_wh = [&](int q, int r) -> float {
+        if constexpr (HALO1) return 0.0f;
+        else if constexpr (VEC) return buf_load<float>(wm_[q].ps.rs, wh_off, (unsigned)r * wm_[q].ps.pitch_b);
+        else return Wk[q][wh_col + (long long)r * C];
+    };
+    float whpre[KG][PFK];
+#pragma unroll
+    for (int q = 0; q < KG; ++q)
+#pragma unroll
+        for (int s = 0; s < PFK; ++s) whpre[q][s] = load_wh(q, min(t0 + s, t1));
+    float uw[KG][3][6];
+    float eww[3][4];
+#pragma unroll
+    for (int q = 0; q < KG; ++q)
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int b = 0; b < 6; ++b) uw[q][a][b] = 0.f;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) eww[a][b] = 0.f;
+    const int last_col_local = C - 1 - j.c0s;
+    const bool own = HALO1 || !EDGE || 4 * j.lane >= j.dup;
+    march_n<2 * HRX, UNROLL>(n, [&](int i, auto qc, auto emit) {
+        constexpr int Q = decltype(qc)::value;
+        xm.template step<Q>(i);
+        if (decltype(emit)::value) {
+            const int o = i - 2 * HRX;
+            const int t = t0 + o;
+            constexpr int SLOT = (Q + 2 * UNROLL - 2 * HRX) % PFK;
+            const float* xup = xm.template row<Q>(MID - 1);
+            const float* xmid = xm.template row<Q>(MID);
+            const float* xdn = xm.template row<Q>(MID + 1);
+            // ---- the image side, once per row: e_w and the mask of the 4 own pixels (and, LDS path, of the strip's halo columns)
+            float* ew = eww[Q % 3];
+            float ewn[4], m[4];
+            residual4<O>(xup, xmid, xdn, nc, ewn);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                ew[k] = ewn[k];
+                m[k] = MASK == 0 ? fabsf(ew[k]) : nvf_value<PAD, O, Q>(xm, k);
+            }
+            float mh = 0.0f;  // (LDS path) lane 0: the mask at column c0s - 1, lane 63: at column c0s + STRIP
+            if constexpr (!HALO1) {
+                if (j.lane == 0 && !left_edge) {
+                    const float eh = residual1<O>(xup, xmid, xdn, -1, nc);
+                    mh = MASK == 0 ? fabsf(eh) : nvf_value<PAD, O, Q>(xm, -1);
+                }
+                if (j.lane == WAVE - 1 && has_right) {
+                    const float eh = residual1<O>(xup, xmid, xdn, 4, nc);
+                    mh = MASK == 0 ? fabsf(eh) : nvf_value<PAD, O, Q>(xm, 4);
+                }
+            }
+            const int r = t - 1;
+            const bool emit_r = r >= j.rs && r < j.re;
+            const bool last_row = j.re == R && t == R - 1;
+            // ---- the key side: k_detect's operations for every key of the group
+#pragma unroll
+            for (int q = 0; q < KG; ++q) {
+                const float4 w = wm_[q].template take<SLOT>();
+                const float wh = HALO1 ? 0.0f : pinned(whpre[q][SLOT]);
+                float uu[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) uu[k] = m[k] * f4get(w, k);
+                float* un = uw[q][Q % 3];
+                if constexpr (HALO1) {
+                    if constexpr (EDGE) {
+                        un[0] = dpp_from_prev(uu[3], uu[0]);
+                        const float nx = dpp_from_next(uu[0], uu[3]);
+                        un[5] = xm.xs.rsel ? uu[3] : nx;
+                    } else {
+                        un[0] = dpp_from_prev_any(uu[3]);
+                        un[5] = dpp_from_next_any(uu[0]);
+                    }
+                } else {
+#pragma unroll
+                    for (int k = 1; k < 4; ++k)
+                        if (c0 + k >= C) uu[k] = uu[k - 1];
+                    float* urow = lds_u + (2 * q + (Q & 1)) * RowBuf<1>::N;
+                    reinterpret_cast<float4*>(urow)[1 + j.lane] = make_float4(uu[0], uu[1], uu[2], uu[3]);
+                    if (j.lane == 0) urow[3] = left_edge ? uu[0] : mh * wh;
+                    if (j.lane == WAVE - 1 && has_right) urow[4 + STRIP] = mh * wh;
+                    if (!has_right) {
+                        const int lk = last_col_local - 4 * j.lane;
+                        if (lk >= 0 && lk < 4) urow[4 + last_col_local + 1] = uu[lk];
+                    }
+                    wave_lds_fence();
+                    un[0] = urow[3 + 4 * j.lane];
+                    un[5] = urow[8 + 4 * j.lane];
+                }
+                un[1] = uu[0]; un[2] = uu[1]; un[3] = uu[2]; un[4] = uu[3];
+                if (o == 0 && j.rs == 0) {
+#pragma unroll
+                    for (int b = 0; b < 6; ++b) uw[q][(Q + 2) % 3][b] = un[b];
+                }
+                if (emit_r) {
+                    const float* um = uw[q][(Q + 1) % 3];
+                    const float* u0 = uw[q][(Q + 2) % 3];
+                    const float* ewp = eww[(Q + 2) % 3];
+                    float eun[4];
+                    residual4<1>(um, u0, un, nc, eun);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        if (VEC ? own : (c0 + k < C && c0 + k >= j.own_c0)) {
+                            const float eu = eun[k];
+                            dot[q] = fmaf(eu, ewp[k], dot[q]);
+                            nu[q] = fmaf(eu, eu, nu[q]);
+                            if (q == 0) nw = fmaf(ewp[k], ewp[k], nw);
+                        }
+                    }
+                }
+                if (last_row) {
+                    const float* u0 = uw[q][(Q + 2) % 3];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        if (VEC ? own : (c0 + k < C && c0 + k >= j.own_c0)) {
+                            const float eu = residual1<1>(u0, un, un, k, nc);
+                            dot[q] = fmaf(eu, ew[k], dot[q]);
+                            nu[q] = fmaf(eu, eu, nu[q]);
+                            if (q == 0) nw = fmaf(ew[k], ew[k], nw);
+                        }
+                    }
+                }
+                wm_[q].template refill<SLOT>(o);
+                if constexpr (!HALO1) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    whpre[q][SLOT] = load_wh(q, min(t + PFK, t1));
+                    asm volatile("" ::: "memory");
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        }
+    });
+    if constexpr (HALO1) {
+        const bool mine = j.lane >= j.lo && j.lane <= j.hi;
+#pragma unroll
+        for (int q = 0; q < KG; ++q) { dot[q] = mine ? dot[q] : 0.0f; nu[q] = mine ? nu[q] : 0.0f; }
+        nw = mine ? nw : 0.0f;
+    }
+}
+
+// inverse of xcd_remap (wm_device.hpp): the hardware block id whose logical index is L
+__device__ __forceinline__ int xcd_unmap(int L, int nblk)
+{
+    const int per = nblk >> 3, rem = nblk & 7;
+    const int big = rem * (per + 1);
+    int x, i;
+    if (L < big) { x = L / (per + 1); i = L - x * (per + 1); }
+    else { x = rem + (L - big) / per; i = L - big - (x - rem) * per; }
+    return i * 8 + x;
+}
+
+// occupancy floor: the aligned 3x3 instances hold two keys' u windows and W rings besides k_detect's registers -- 4 waves per
+// SIMD for u8 planes (122 / 124 VGPRs), 3 for f32 ones (at 4 they spill 17 VGPRs); the generic instances 2 (LDS re-lay, halo
+// predictions of their own)
+template <typename T, int MASK, int PAD, int HC, bool VEC>
+__global__ __launch_bounds__(BLOCK, (PAD == 1 && HC == 1 ? (VEC ? (sizeof(T) == 1 ? 4 : 3) : 2) : 1)) void k_detect_keys(
+    const T* __restrict__ x, long long pitch, long long fstride, KeysArgs ka, Geom g, const float* __restrict__ coef,
+    const int* __restrict__ status)
+{
+    __shared__ __attribute__((aligned(16))) float s_row[WPB][2 * RowBuf<HC>::N];
+    __shared__ __attribute__((aligned(16))) float s_u[WPB][2 * KG * RowBuf<1>::N];
+    __shared__ double s_red[WPB][2 * KG + 1];
+    // block order: the key groups of one (tile, frame) block are consecutive logical indices of one XCD (xcd_remap), so the
+    // tile of x is read from memory once and from that XCD's L2 for the other groups; inside a group the order is k_detect's
+    const int nb = (int)gridDim.x / ka.ngroups;
+    const int pidx = xcd_remap((int)blockIdx.x, (int)gridDim.x);
+    const int grp = pidx % ka.ngroups;
+    const WaveJob j = make_job(g, xcd_unmap(pidx / ka.ngroups, nb));
+    const int frame = j.frame;
+    const int k0 = grp * KG;
+    float dot[KG], nu[KG], nw = 0.0f;
+#pragma unroll
+    for (int q = 0; q < KG; ++q) { dot[q] = 0.0f; nu[q] = 0.0f; }
+    if (j.valid && status[frame] == 0) {
+        float c[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) c[k] = coef[frame * 8 + k];
+        const T* xf = x + (long long)frame * fstride;
+        // keys beyond the bank (a short last group) repeat its last key; their sums are not stored
+        const float* Wk[KG];
+#pragma unroll
+        for (int q = 0; q < KG; ++q) Wk[q] = ka.W + (long long)min(k0 + q, ka.nkeys - 1) * ka.kstride;
+        constexpr bool V = VEC && HC == 1;
+        if (MASK != 0 || strip_on_edge<V>(g, j)) keys_march<T, MASK, PAD, HC, V, true>(xf, pitch, Wk, g, j, s_row[j.wave], s_u[j.wave], c, dot, nu, nw);
+        else keys_march<T, MASK, PAD, HC, V, (MASK != 0)>(xf, pitch, Wk, g, j, s_row[j.wave], s_u[j.wave], c, dot, nu, nw);
+    }
+    double d[2 * KG + 1];
+#pragma unroll
+    for (int q = 0; q < KG; ++q) { d[2 * q] = wave_sum((double)dot[q]); d[2 * q + 1] = wave_sum((double)nu[q]); }
+    d[2 * KG] = wave_sum((double)nw);
+    if (g.quad) {
+        // the waves of this block are 4 frames: one record per wave (k_detect's corr_fold order, folded by k_keys_fold)
+        if (!j.valid || j.lane != 0) return;
+#pragma unroll
+        for (int q = 0; q < KG; ++q) {
+            if (k0 + q >= ka.nkeys) break;
+            double* p = ka.part + (((long long)frame * ka.nkeys + k0 + q) * ka.rstride + j.rec) * 2;
+            p[0] = d[2 * q]; p[1] = d[2 * q + 1];
+        }
+        if (grp == 0) ka.partw[(long long)frame * ka.rstride + j.rec] = d[2 * KG];
+        return;
+    }
+    // the waves of this block are 4 segments of one frame: one record per block, k_detect's ((w0 + w1) + w2) + w3
+    if (j.lane == 0) {
+#pragma unroll
+        for (int v = 0; v < 2 * KG + 1; ++v) s_red[j.wave][v] = d[v];
+    }
+    __syncthreads();
+    const int v = threadIdx.x;
+    if (v < 2 * KG + 1) {
+        const double s = ((s_red[0][v] + s_red[1][v]) + s_red[2][v]) + s_red[3][v];
+        const long long blk = g.pb0 + j.tile;
+        if (v == 2 * KG) { if (grp == 0) ka.partw[(long long)frame * ka.rstride + blk] = s; }
+        else if (k0 + v / 2 < ka.nkeys) ka.part[(((long long)frame * ka.nkeys + k0 + v / 2) * ka.rstride + blk) * 2 + (v & 1)] = s;
+    }
+}
+
+// one block per (frame, key): the records folded in k_detect's order -- corr_finalize_frame's over the blocks, or (quad)
+// corr_fold's over the segments of each strip, then over the strips -- into corr = (float)dot / (float)(||e_w|| * ||e_u||)
+// (Watermark.cpp:230); unsolvable => 0.0f (:246-247)
+constexpr int KEYS_MAX_STRIPS = 256;
+__global__ __launch_bounds__(BLOCK) void k_keys_fold(const double* __restrict__ part, const double* __restrict__ partw, int rstride,
+                                                     int nkeys, int quad, int nblk, int nsegs, int nstrips,
+                                                     const int* __restrict__ status, OpResult* __restrict__ res)
+{
+    __shared__ double s[3][BLOCK];
+    const int frame = blockIdx.x / nkeys, key = blockIdx.x - frame * nkeys;
+    const double* pk = part + ((long long)frame * nkeys + key) * rstride * 2;
+    const double* pw = partw + (long long)frame * rstride;
+    const int t = threadIdx.x;
+    double r0 = 0.0, r1 = 0.0, r2 = 0.0;
+    if (!quad) {
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+        for (int b0 = t; b0 < nblk; b0 += 2 * BLOCK) {
+            double v[2][3];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int b = min(b0 + u * BLOCK, nblk - 1);
+                v[u][0] = pk[2 * b]; v[u][1] = pk[2 * b + 1]; v[u][2] = pw[b];
+            }
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const bool in = b0 + u * BLOCK < nblk;
+                a0 += in ? v[u][0] : 0.0; a1 += in ? v[u][1] : 0.0; a2 += in ? v[u][2] : 0.0;
+            }
+        }
+        s[0][t] = a0; s[1][t] = a1; s[2][t] = a2;
+        __syncthreads();
+        for (int o = BLOCK / 2; o > 0; o >>= 1) {
+            if (t < o) { s[0][t] += s[0][t + o]; s[1][t] += s[1][t + o]; s[2][t] += s[2][t + o]; }
+            __syncthreads();
+        }
+        r0 = s[0][0]; r1 = s[1][0]; r2 = s[2][0];
+    } else {
+        __shared__ double ss[3][KEYS_MAX_STRIPS];
+        const int lane = t & (WAVE - 1), wave = t / WAVE;
+        for (int st = wave; st < nstrips; st += WPB) {
+            double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+            for (int s0 = lane; s0 < nsegs; s0 += 2 * WAVE) {
+                double v[2][3];
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const int rec = min(s0 + u * WAVE, nsegs - 1) * nstrips + st;
+                    v[u][0] = pk[2 * rec]; v[u][1] = pk[2 * rec + 1]; v[u][2] = pw[rec];
+                }
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const bool in = s0 + u * WAVE < nsegs;
+                    a0 += in ? v[u][0] : 0.0; a1 += in ? v[u][1] : 0.0; a2 += in ? v[u][2] : 0.0;
+                }
+            }
+            a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2);
+            if (lane == 0) { ss[0][st] = a0; ss[1][st] = a1; ss[2][st] = a2; }
+        }
+        __syncthreads();
+        if (wave == 0) {
+            double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+            for (int s0 = lane; s0 < nstrips; s0 += WAVE) { a0 += ss[0][s0]; a1 += ss[1][s0]; a2 += ss[2][s0]; }
+            r0 = wave_sum(a0); r1 = wave_sum(a1); r2 = wave_sum(a2);
+        }
+    }
+    if (t == 0) {
+        const int st = status[frame];
+        float corr = 0.0f;
+        if (st == 0) corr = (float)r0 / (float)(sqrt(r2) * sqrt(r1));
+        OpResult o;
+        o.status = st; o.value = corr;
+        res[blockIdx.x] = o;
+    }
+}
+
+template <typename T>
+static void launch_detect_keys_t(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x,
+                                 int aligned_w, const KeysArgs& ka, const float* coef, const int* status, bool split)
+{
+    // k_detect's launch plan (launch_detect_t), every grid times the key groups
+#define KEYS_GO(KER, SP)                                                                                                   \
+    do {                                                                                                                   \
+        const SweepPart sp_ = (SP);                                                                                        \
+        if (sp_.run) WM_KLAUNCH(KER, dim3(sp_.grid.x * (unsigned)ka.ngroups), dim3(BLOCK), 0, s, (const T*)x.p, x.pitch,   \
+                                x.fstride, ka, sp_.g, coef, status);                                                       \
+    } while (0)
+#define KEYS3P(MASK, P)                                                                                                    \
+    do {                                                                                                                   \
+        if (align_mode(lg, x.aligned && aligned_w) == 2) {                                                                 \
+            KEYS_GO((k_detect_keys<T, MASK, P, 1, true>), sweep_part_overlap(lg, frames, 1));                               \
+        } else if (split) {                                                                                                \
+            KEYS_GO((k_detect_keys<T, MASK, P, 1, true>), sweep_part_split_overlap(lg, frames, 1));                         \
+            KEYS_GO((k_detect_keys<T, MASK, P, 1, false>), sweep_part_split_generic(lg, frames, 1));                        \
+        } else {                                                                                                           \
+            KEYS_GO((k_detect_keys<T, MASK, P, 1, false>), sweep_part(lg, frames, false, 0, 1));                            \
+        }                                                                                                                  \
+    } while (0)
+    if (mask == 0) { KEYS3P(0, 1); }
+    else if (pad == 1) { KEYS3P(1, 1); }
+    else if (pad == 2) { KEYS3P(1, 2); }
+    else if (pad == 3) { KEYS3P(1, 3); }
+    else { KEYS_GO((k_detect_keys<T, 1, 4, 2, false>), sweep_part(lg, frames, false, 0, 1)); }
+#undef KEYS3P
+#undef KEYS_GO
+}
+
+int detect_keys_group(void) { return KG; }
+
+int launch_detect_keys(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x,
+                       const float* Wbank, long long kstride, int nkeys, int aligned_w, const float* coef, const int* status,
+                       double* part, int rstride, OpResult* res)
+{
+    // the geometry k_detect takes for this plane (launch_detect): overlapped strips, overlapped strips + one generic strip,
+    // or the plain strips
+    const bool overlap = (mask == 0 || pad <= 3) && align_mode(lg, x.aligned && aligned_w) == 2;
+    const bool split = (mask == 0 || pad == 1) && !overlap && x.aligned && aligned_w && split_applies(lg.cols);
+    const LaunchGeom ld = overlap ? overlap_geom(lg) : (split ? split_geom(lg) : lg);
+    const bool quad = frames >= 4;
+    if (ld.nblk > rstride || ld.nstrips * ld.nsegs > rstride || ld.nstrips > KEYS_MAX_STRIPS) return -1;
+    KeysArgs ka;
+    ka.W = Wbank; ka.kstride = kstride; ka.nkeys = nkeys; ka.ngroups = (nkeys + KG - 1) / KG; ka.rstride = rstride;
+    ka.part = part; ka.partw = part + (size_t)frames * nkeys * rstride * 2;
+    WM_DISPATCH_T(x.dtype, launch_detect_keys_t<T>(s, ld, frames, mask, pad, x, aligned_w, ka, coef, status, split));
+    WM_KLAUNCH(k_keys_fold, dim3((unsigned)(frames * nkeys)), dim3(BLOCK), 0, s, (const double*)ka.part, (const double*)ka.partw,
+               rstride, nkeys, quad ? 1 : 0, ld.nblk, ld.nsegs, ld.nstrips, status, res);
+    return 0;
+}
+
+}  // namespace wmk

@@ -178,6 +178,13 @@ void launch_mask(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int 
 void launch_detect(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* W,
                    int aligned_w, const float* coef, const int* status, double* pcorr, unsigned* ticket, unsigned* ticket_strip,
                    double* scorr, OpResult* res, RawSums* raw);
+// one image against a bank of keys (wm_detect_keys, wm_k_detect_keys.hip): k_detect's sweep for every key of the bank, key
+// groups as a grid axis, then one fold block per (frame, key) into res[frame * nkeys + key].  part: [frames][2 nkeys + 1][rstride]
+// doubles of scratch.  Returns -1 when the sweep's records exceed rstride (nothing is launched)
+int launch_detect_keys(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x,
+                       const float* Wbank, long long kstride, int nkeys, int aligned_w, const float* coef, const int* status,
+                       double* part, int rstride, OpResult* res);
+int detect_keys_group(void);  // keys per group of k_detect_keys (compile-time KG)
 // band mode: solve the 8x8 system from all-reduced Gram totals [frames][44]; writes coef / status like k_gram's tail
 void launch_solve_totals(hipStream_t s, int frames, const double* totals, float* coef, int* status);
 // band mode, device-resident exchange (wm_band_*_dev): glue kernels between the sweeps and the caller's collectives
