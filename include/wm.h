@@ -160,8 +160,22 @@ int wm_set_rows_per_segment(wm_ctx* ctx, int rows_per_segment);
  * a_out[frames], status_out[frames] (either may be NULL) are written by wm_sync. */
 int wm_embed(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* base, const wm_plane* out, float* a_out,
              int* status_out, int slot);
-/* Watermark::detectWatermark(watermarkedImage, maskType)  (Watermark.cpp:234-250) */
+/* Watermark::detectWatermark(watermarkedImage, maskType)  (Watermark.cpp:234-250).
+ * The caller promises nothing about `img`.  When it is the device plane the same slot's last wm_embed wrote (same pointer,
+ * pitch, frame stride, frames and dtype), that embed handed its Gram sums over (ME mask, grey f32 planes on the aligned path,
+ * p = 3, two frames or more, no band) and no detector has used them yet, the call takes the CHECKED hand-over: the Gram
+ * matrix comes from the embed's sums (k_gram_ho, no Gram sweep over img), and the detector's own sweep sums a 64-bit digest
+ * of the pixels it reads that any change of a single pixel alters.  A frame whose digest equals the one the embed left
+ * keeps its score; any other frame is redone on the device from the plane as it is (k_gram_redo + k_detect_redo, launched
+ * after every checked detect, empty when nothing changed) -- the result is then the ordinary path's.  Scores agree with the
+ * ordinary path to the rounding of the Gram sums' grouping (<= 1.2e-7).  wm_set_checked_handover switches this off. */
 int wm_detect(wm_ctx* ctx, int mask, const wm_plane* img, float* corr_out, int* status_out, int slot);
+/* the checked hand-over of wm_detect: 1 (default; environment WM_CHECKED_HANDOVER=0 changes the default) on, 0 off -- every
+ * wm_detect then takes the ordinary Gram sweep and wm_embed leaves sums behind only under wm_set_handover, as before */
+int wm_set_checked_handover(wm_ctx* ctx, int on);
+/* frames the checked hand-over trusted (digest equal) and redid (digest different) since the context was configured, over
+ * all slots; waits for every slot's queued work.  Either pointer may be NULL */
+int wm_checked_handover_counts(wm_ctx* ctx, unsigned long long* trusted, unsigned long long* redone);
 
 /* makeWatermark followed by detectWatermark on its result -- the pair the reference's sample protocol runs per image
  * (testForImage, main.cpp:165-220) -- as ONE call: the results of wm_embed(...) then wm_detect(out, ...), delivered

@@ -52,6 +52,8 @@ ABI = [
     ("wm_configure", C.c_int, [_ctx_p, C.c_int, C.c_int]),
     ("wm_set_fused", C.c_int, [_ctx_p, C.c_int]),
     ("wm_set_handover", C.c_int, [_ctx_p, C.c_int]),
+    ("wm_set_checked_handover", C.c_int, [_ctx_p, C.c_int]),
+    ("wm_checked_handover_counts", C.c_int, [_ctx_p, _P(C.c_ulonglong), _P(C.c_ulonglong)]),
     ("wm_fused_info", C.c_int, [_ctx_p, _P(C.c_int), _P(C.c_int), _P(C.c_ulonglong)]),
     ("wm_fused_lock_skips", C.c_ulonglong, [_ctx_p]),
     ("wm_fused_stamps", C.c_int, [_ctx_p, _P(C.c_ulonglong), C.c_int]),
@@ -367,6 +369,20 @@ class Watermark:
         rc = lib().wm_set_handover(self._ctx, 1 if on else 0)
         if rc != WM_OK:
             _raise(rc, self._ctx)
+
+    def set_checked_handover(self, on):
+        """wm_detect of the plane the slot's last embed wrote, checked by a digest of it (wm.h wm_set_checked_handover); on by default"""
+        rc = lib().wm_set_checked_handover(self._ctx, 1 if on else 0)
+        if rc != WM_OK:
+            _raise(rc, self._ctx)
+
+    def checked_handover_counts(self):
+        """(trusted, redone): frames of checked hand-overs since the context was configured (wm.h wm_checked_handover_counts)"""
+        t, r = C.c_ulonglong(0), C.c_ulonglong(0)
+        rc = lib().wm_checked_handover_counts(self._ctx, C.byref(t), C.byref(r))
+        if rc != WM_OK:
+            _raise(rc, self._ctx)
+        return t.value, r.value
 
     def fused_info(self):
         """(active, workgroups, tile_rows, fallbacks)"""

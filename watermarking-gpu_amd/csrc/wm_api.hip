@@ -36,9 +36,12 @@ constexpr int TARGET_WAVES_ME = 1280;
 constexpr int TARGET_WAVES_NVF = 2048;
 
 // the fold steps (solve, embed scalars, correlation) are tails of k_gram / k_*_stats / k_detect: no kernels of their own
-enum KernelId { K_GRAM = 0, K_ME_STATS, K_NVF_STATS, K_EMBED, K_DETECT, K_MASK, K_FUSED_EMBED, K_FUSED_DETECT, K_GRAM_HO, K_FUSED_PAIR, K_DETECT_KEYS, K_COUNT };
+// (the checked hand-over of wm_detect: its k_gram_ho launch and the predicated redo launches behind it are counted apart from
+// the opt-in hand-over's k_gram_ho and from the Gram sweeps)
+enum KernelId { K_GRAM = 0, K_ME_STATS, K_NVF_STATS, K_EMBED, K_DETECT, K_MASK, K_FUSED_EMBED, K_FUSED_DETECT, K_GRAM_HO, K_FUSED_PAIR, K_DETECT_KEYS,
+                K_GRAM_HO_CHECKED, K_GRAM_REDO, K_DETECT_REDO, K_COUNT };
 const char* const kKernelNames[K_COUNT] = {"k_gram", "k_me_stats", "k_nvf_stats", "k_embed", "k_detect", "k_mask", "k_fused_embed", "k_fused_detect", "k_gram_ho", "k_fused_pair",
-                                           "k_detect_keys"};
+                                           "k_detect_keys", "k_gram_ho_checked", "k_gram_redo", "k_detect_redo"};
 
 // fused single-frame launches use every CU and wait for each other inside the launch: two of them in flight on one device
 // could each hold a part of the CUs and starve the other (their spins are bounded, so that would be a slow fallback, not a
@@ -99,6 +102,10 @@ struct Slot {
     float* d_pmax = nullptr;
     double* d_pss = nullptr;
     double* d_pcorr = nullptr;
+    unsigned long long* d_pdig = nullptr;   // [frames][nrec] digest records of a checking k_detect (DigCheck)
+    unsigned long long* d_sdig = nullptr;   // [frames][nstrips] its strip records
+    int* d_redo = nullptr;                  // [frames] frames a checking k_detect left to the redo launches
+    unsigned long long* d_hocnt = nullptr;  // [2] frames trusted / redone by checked hand-overs
     EmbedScalars* d_scal = nullptr;
     float* d_smax = nullptr;       // [max_frames][nstrips] strip records of the stats sweep
     double* d_sss = nullptr;
@@ -123,9 +130,12 @@ struct Slot {
     unsigned fz_epoch = 0;
     // Gram hand-over (wm_set_handover): wave + seam records [max_frames][ho_stride_max][13]; ho.valid: the last embed on this
     // slot left the tile-internal lag sums of its output (= last_out) there, for the geometry ho.lg
+    // promised: the embed ran under wm_set_handover / wm_embed_detect (a WM_MEM_SLOT_OUT detector may trust the sums); else only
+    // the checked hand-over of wm_detect takes them, once (used: a detector or wm_gram has taken them)
     double* d_ho = nullptr;
     float* d_hoseam = nullptr;   // [max_frames][strips - 1][rows][4]: the columns at the strip boundaries (HandOver::seam)
-    struct HoInfo { bool valid = false; LaunchGeom lg{}; int frames = 0; int stride = 0; } ho;
+    unsigned long long* d_hodig = nullptr;  // [max_frames][ho_stride_max] digest records, then [max_frames] frame digests (HandOver::dig / fdig)
+    struct HoInfo { bool valid = false; bool promised = false; bool used = false; LaunchGeom lg{}; int frames = 0; int stride = 0; } ho;
     // wm_embed_detect: a fused embed whose wait was deferred to the detector's record (the two launches go out back to back)
     struct PairEmbed {
         bool armed = false; int res_index = 0; bool host_out = false; bool out_overlaps_inputs = false;
@@ -166,6 +176,7 @@ struct wm_ctx {
     int handover = 0;        // wm_set_handover
     int handover_verify = (getenv("WM_HANDOVER_VERIFY") && getenv("WM_HANDOVER_VERIFY")[0] == '1') ? 1 : 0;  // debug: re-check every hand-over
     int pair_handover = 0;   // 1 inside wm_embed_detect: its detector reads the embed's output by construction
+    int checked_handover = (getenv("WM_CHECKED_HANDOVER") && getenv("WM_CHECKED_HANDOVER")[0] == '0') ? 0 : 1;  // wm_set_checked_handover
     int pair_mode = 0;       // 1 inside wm_embed_detect: the fused embed does not wait (and the caller holds the FusedGuard)
     int fused_lock_fd = -1;  // per-device lock file shared with other processes (FusedGuard), -1: none
     int max_nblk = 0, max_nrec = 0;  // per-frame capacity of the slots' partial-record arrays (alloc_slots)
@@ -331,7 +342,7 @@ void free_slot(Slot& s)
     if (s.h_res) (void)hipHostFree(s.h_res);
     if (s.h_coefres) (void)hipHostFree(s.h_coefres);
     (void)hipFree(s.st_in); (void)hipFree(s.st_base); (void)hipFree(s.st_out); (void)hipFree(s.fz_block); (void)hipFree(s.d_ho); (void)hipFree(s.d_hoseam);
-    (void)hipFree(s.keys_part);
+    (void)hipFree(s.d_hodig); (void)hipFree(s.keys_part);
     s = Slot();
 }
 
@@ -358,26 +369,39 @@ int worst_nrec(int rows, int cols, int rps_override) { return strips_alloc(cols)
 
 // Gram hand-over: records per frame of a slot's hand-over array = the wave records + the seam-block records of the largest geometry
 int ho_stride_max(const wm_ctx* ctx) { return ctx->max_nrec + 2 * ((ctx->max_nrec + 3) / 4) + 2; }
-// both arrays of a slot or neither: a slot with records but no seam array would send k_embed<HO>'s edge lanes to address 0
+// all arrays of a slot or none: a slot with records but no seam array would send k_embed<HO>'s edge lanes to address 0
+bool ho_ready(const Slot& s) { return s.d_ho && s.d_hoseam && s.d_hodig; }
+int ho_alloc_slot(wm_ctx* ctx, Slot& s)
+{
+    if (ho_ready(s)) return WM_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    s.ho.valid = false;
+    (void)hipFree(s.d_ho); (void)hipFree(s.d_hoseam); (void)hipFree(s.d_hodig);
+    s.d_ho = nullptr; s.d_hoseam = nullptr; s.d_hodig = nullptr;
+    void* rec = nullptr; void* seam = nullptr; void* dig = nullptr;
+    hipError_t e = hipMalloc(&rec, (size_t)ctx->max_frames * ho_stride_max(ctx) * 13 * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&seam, (size_t)ctx->max_frames * ceil_div(ctx->cols, 256) * ctx->rows * 4 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(&dig, (size_t)ctx->max_frames * (ho_stride_max(ctx) + 1) * sizeof(unsigned long long));
+    if (e != hipSuccess) {
+        (void)hipFree(rec); (void)hipFree(seam); (void)hipFree(dig);
+        (void)hipGetLastError();
+        return fail(ctx, WM_ERR_ALLOC, std::string("hand-over arrays: ") + hipGetErrorString(e));
+    }
+    s.d_ho = (double*)rec; s.d_hoseam = (float*)seam; s.d_hodig = (unsigned long long*)dig;
+    return WM_OK;
+}
 int ho_alloc(wm_ctx* ctx)
 {
-    HIPCHK(ctx, hipSetDevice(ctx->device));
     for (auto& s : ctx->slots) {
         s.ho.valid = false;
-        if (s.d_ho && s.d_hoseam) continue;
-        (void)hipFree(s.d_ho); (void)hipFree(s.d_hoseam);
-        s.d_ho = nullptr; s.d_hoseam = nullptr;
-        void* rec = nullptr; void* seam = nullptr;
-        hipError_t e = hipMalloc(&rec, (size_t)ctx->max_frames * ho_stride_max(ctx) * 13 * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc(&seam, (size_t)ctx->max_frames * ceil_div(ctx->cols, 256) * ctx->rows * 4 * sizeof(float));
-        if (e != hipSuccess) {
-            (void)hipFree(rec); (void)hipFree(seam);
-            (void)hipGetLastError();
-            return fail(ctx, WM_ERR_ALLOC, std::string("hand-over arrays: ") + hipGetErrorString(e));
-        }
-        s.d_ho = (double*)rec; s.d_hoseam = (float*)seam;
+        const int rc = ho_alloc_slot(ctx, s);
+        if (rc != WM_OK) return rc;
     }
     return WM_OK;
+}
+HandOver handover_of(const wm_ctx* ctx, const Slot& s, int stride)
+{
+    return HandOver{s.d_ho, stride, s.d_hoseam, s.d_hodig, s.d_hodig + (size_t)ctx->max_frames * ho_stride_max(ctx)};
 }
 
 int alloc_slots(wm_ctx* ctx, int nslots, int max_frames)
@@ -425,6 +449,10 @@ int alloc_slots(wm_ctx* ctx, int nslots, int max_frames)
             {(void**)&s.d_pmax, nr * sizeof(float)},
             {(void**)&s.d_pss, nr * sizeof(double)},
             {(void**)&s.d_pcorr, nr * 3 * sizeof(double)},
+            {(void**)&s.d_pdig, nr * sizeof(unsigned long long)},
+            {(void**)&s.d_sdig, nsr * sizeof(unsigned long long)},
+            {(void**)&s.d_redo, (size_t)max_frames * sizeof(int)},
+            {(void**)&s.d_hocnt, 2 * sizeof(unsigned long long)},
             {(void**)&s.d_scal, (size_t)max_frames * sizeof(EmbedScalars)},
             {(void**)&s.d_smax, nsr * sizeof(float)},
             {(void**)&s.d_sss, nsr * sizeof(double)},
@@ -935,6 +963,31 @@ int wm_set_handover(wm_ctx* ctx, int on)
     return WM_OK;
 }
 
+int wm_set_checked_handover(wm_ctx* ctx, int on)
+{
+    if (!ctx || on < 0 || on > 1) return fail(ctx, WM_ERR_BAD_ARG, "wm_set_checked_handover: 0 or 1");
+    for (auto& s : ctx->slots)
+        if (!s.ho.promised) s.ho.valid = false;
+    ctx->checked_handover = on;
+    return WM_OK;
+}
+
+int wm_checked_handover_counts(wm_ctx* ctx, unsigned long long* trusted, unsigned long long* redone)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    unsigned long long t = 0, r = 0;
+    for (auto& s : ctx->slots) {
+        unsigned long long c[2] = {0, 0};
+        HIPCHK(ctx, hipMemcpyAsync(c, s.d_hocnt, sizeof c, hipMemcpyDeviceToHost, s.stream));
+        HIPCHK(ctx, hipStreamSynchronize(s.stream));
+        t += c[0]; r += c[1];
+    }
+    if (trusted) *trusted = t;
+    if (redone) *redone = r;
+    return WM_OK;
+}
+
 int wm_fused_info(const wm_ctx* ctx, int* workgroups, int* tile_rows, unsigned long long* fallbacks)
 {
     if (!ctx) return 0;
@@ -1158,9 +1211,13 @@ int wm_embed(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* bas
     // Gram hand-over (wm_set_handover): k_embed also leaves the tile-internal lag sums of y for a detector that reads this
     // output as WM_MEM_SLOT_OUT (grey f32 planes on the aligned path; launch_embed says whether it applied)
     // (its tiles reach two rows behind their segment: not when the output overwrites the base those rows are read from)
-    if (ctx->pair_handover && !(s.d_ho && s.d_hoseam) && ho_alloc(ctx) != WM_OK) { (void)hipGetLastError(); ctx->last_error.clear(); }  // (no memory: no hand-over)
-    const HandOver ho{s.d_ho, lg.nstrips * lg.nsegs + handover_seam_blocks(lg), s.d_hoseam};
-    const HandOver* hop = (ctx->handover || ctx->pair_handover) && s.d_ho && s.d_hoseam && out->channels == 1 && ho.stride <= ho_stride_max(ctx) &&
+    // ... and, with the checked hand-over on, for ANY later wm_detect of this output on this slot (ME embeds: the detector's
+    // digest check decides whether the sums are used, wm.h wm_detect)
+    const bool promised = ctx->handover || ctx->pair_handover;
+    const bool want_ho = promised || (ctx->checked_handover && mask == WM_MASK_ME);
+    if (want_ho && !ho_ready(s) && ho_alloc_slot(ctx, s) != WM_OK) { (void)hipGetLastError(); ctx->last_error.clear(); }  // (no memory: no hand-over)
+    const HandOver ho = handover_of(ctx, s, lg.nstrips * lg.nsegs + handover_seam_blocks(lg));
+    const HandOver* hop = want_ho && ho_ready(s) && out->channels == 1 && ho.stride <= ho_stride_max(ctx) &&
                                   !descs_overlap(bd, od, ctx->rows, ctx->cols, frames) ? &ho : nullptr;
     bool handed = false;
     if (mask == WM_MASK_ME) {
@@ -1171,7 +1228,7 @@ int wm_embed(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* bas
         { ProfScope ps(ctx, K_NVF_STATS, s.stream); launch_nvf_stats(s.stream, lg, frames, xd, W, aligned_w, pad, s.d_pss, s.d_ticket + ctx->max_frames * TKS, strip_tickets(ctx, s, 0), s.d_sss, ctx->sF, sqrt_n(ctx), s.d_scal, res, s.d_raw); }
         { ProfScope ps(ctx, K_EMBED, s.stream); handed = launch_embed(s.stream, lg, frames, 1, pad, xd, W, aligned_w, bd, od, nullptr, nullptr, s.d_scal, hop); }
     }
-    if (handed) { s.ho.valid = true; s.ho.lg = lg; s.ho.frames = frames; s.ho.stride = ho.stride; }
+    if (handed) { s.ho.valid = true; s.ho.promised = promised; s.ho.used = false; s.ho.lg = lg; s.ho.frames = frames; s.ho.stride = ho.stride; }
     if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
     if (out->mem == WM_MEM_HOST && (rc = stage_out(ctx, s, out, s.st_out, st_out_l)) != WM_OK) return rc;
     s.last_out = od; s.last_out_frames = frames; s.last_out_dtype = out->dtype;
@@ -1180,18 +1237,32 @@ int wm_embed(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* bas
     return sync_after && !ctx->pair_mode ? do_sync(ctx, s) : WM_OK;  // (wm_embed_detect: the detector's wait covers the embed)
 }
 
+// k_gram_ho over the sums the slot's last embed left (the border blocks are this short launch's longest: as many of them as the
+// record array holds, not the batched sweep's 16)
+static void gram_from_handover(wm_ctx* ctx, Slot& s, int frames, const PlaneDesc& xd)
+{
+    LaunchGeom l2 = s.ho.lg;
+    l2.nbb = border_blocks(ctx->rows, ctx->cols);
+    launch_gram_ho(s.stream, l2, frames, xd, handover_of(ctx, s, s.ho.stride), s.d_gramb, s.d_ticket, s.d_coef, s.d_status, s.d_gramtot);
+}
+
+// does this detector input take the checked hand-over (wm.h wm_detect)?  The plane the slot's last embed wrote -- the same
+// descriptor --, sums nobody has used yet, and the checking detector's path (f32, ME, overlapped aligned strips)
+static bool checked_handover_applies(const wm_ctx* ctx, const Slot& s, const LaunchGeom& lg, int frames, int mask, const PlaneDesc& xd, int aligned_w)
+{
+    const PlaneDesc& o = s.last_out;
+    return ctx->checked_handover && s.ho.valid && !s.ho.used && ho_ready(s) && ctx->band_hi == 0 && s.ho.frames == frames &&
+           s.last_out_frames == frames && xd.p == o.p && xd.pitch == o.pitch && xd.fstride == o.fstride && xd.dtype == o.dtype &&
+           s.last_out_dtype == WM_F32 && xd.channels == 1 && detect_checkable(lg, mask, ctx->p / 2, xd, aligned_w);
+}
+
 // the Gram sweep of a detector-side call: k_gram over the plane -- or, when the plane is the slot's last embed output and that
 // embed left its tile-internal lag sums (wm_set_handover), only the seams, the border frame and the solve (k_gram_ho)
 static int gram_sweep(wm_ctx* ctx, Slot& s, const LaunchGeom& lg, int frames, const PlaneDesc& xd, const wm_plane* img)
 {
-    if (img->mem == WM_MEM_SLOT_OUT && s.ho.valid && s.ho.frames == frames && s.d_ho && s.d_hoseam && ctx->band_hi == 0) {
-        {
-            ProfScope ps(ctx, K_GRAM_HO, s.stream);
-            // (the border blocks are this short launch's longest: as many of them as the record array holds, not the batched sweep's 16)
-            LaunchGeom l2 = s.ho.lg;
-            l2.nbb = border_blocks(ctx->rows, ctx->cols);
-            launch_gram_ho(s.stream, l2, frames, xd, HandOver{s.d_ho, s.ho.stride, s.d_hoseam}, s.d_gramb, s.d_ticket, s.d_coef, s.d_status, s.d_gramtot);
-        }
+    if (img->mem == WM_MEM_SLOT_OUT && s.ho.valid && s.ho.promised && s.ho.frames == frames && ho_ready(s) && ctx->band_hi == 0) {
+        s.ho.used = true;
+        { ProfScope ps(ctx, K_GRAM_HO, s.stream); gram_from_handover(ctx, s, frames, xd); }
         if (!ctx->handover_verify) return WM_OK;
         // WM_HANDOVER_VERIFY=1 (a debug mode, it synchronises): the hand-over rests on the caller's promise that the plane
         // behind WM_MEM_SLOT_OUT is still what the embed wrote.  Run the ordinary Gram sweep over the plane as it is NOW and
@@ -1296,8 +1367,21 @@ int wm_detect(wm_ctx* ctx, int mask, const wm_plane* img, float* corr_out, int* 
     const float* W = ctx->w->d_w;
     const int aligned_w = fits_32bit(ctx->rows, ctx->cols, WM_F32) ? 1 : 0  /* (W is a dense f32 plane: 4-byte aligned rows suffice, vec_ok) */;
     OpResult* res = s.d_res + s.res_used;
-    if ((rc = gram_sweep(ctx, s, lg, frames, xd, img)) != WM_OK) return rc;
-    { ProfScope ps(ctx, K_DETECT, s.stream); launch_detect(s.stream, lg, frames, mask, ctx->p / 2, xd, W, aligned_w, s.d_coef, s.d_status, s.d_pcorr, s.d_ticket + 2 * ctx->max_frames * TKS, strip_tickets(ctx, s, 1), s.d_scorr, res, s.d_raw + ctx->max_frames); }
+    unsigned* dticket = s.d_ticket + 2 * ctx->max_frames * TKS;
+    // (a WM_MEM_SLOT_OUT plane under wm_set_handover keeps the promised hand-over of gram_sweep)
+    if (!(img->mem == WM_MEM_SLOT_OUT && s.ho.promised) && checked_handover_applies(ctx, s, lg, frames, mask, xd, aligned_w)) {
+        // checked hand-over: the Gram matrix from the embed's sums, the detector checks the plane against the embed's digest, and
+        // the frames it does not trust are redone by the ordinary sweeps (predicated on the device: empty launches otherwise)
+        s.ho.used = true;
+        const DigCheck dc{s.d_pdig, s.d_sdig, handover_of(ctx, s, s.ho.stride).fdig, s.d_redo, s.d_hocnt};
+        { ProfScope ps(ctx, K_GRAM_HO_CHECKED, s.stream); gram_from_handover(ctx, s, frames, xd); }
+        { ProfScope ps(ctx, K_DETECT, s.stream); launch_detect(s.stream, lg, frames, mask, ctx->p / 2, xd, W, aligned_w, s.d_coef, s.d_status, s.d_pcorr, dticket, strip_tickets(ctx, s, 1), s.d_scorr, res, s.d_raw + ctx->max_frames, &dc, 1); }
+        { ProfScope ps(ctx, K_GRAM_REDO, s.stream); launch_gram(s.stream, lg, frames, xd, s.d_gram, s.d_gramb, s.d_ticket, s.d_coef, s.d_status, s.d_gramtot, s.d_redo); }
+        { ProfScope ps(ctx, K_DETECT_REDO, s.stream); launch_detect(s.stream, lg, frames, mask, ctx->p / 2, xd, W, aligned_w, s.d_coef, s.d_status, s.d_pcorr, dticket, strip_tickets(ctx, s, 1), s.d_scorr, res, s.d_raw + ctx->max_frames, &dc, 2); }
+    } else {
+        if ((rc = gram_sweep(ctx, s, lg, frames, xd, img)) != WM_OK) return rc;
+        { ProfScope ps(ctx, K_DETECT, s.stream); launch_detect(s.stream, lg, frames, mask, ctx->p / 2, xd, W, aligned_w, s.d_coef, s.d_status, s.d_pcorr, dticket, strip_tickets(ctx, s, 1), s.d_scorr, res, s.d_raw + ctx->max_frames); }
+    }
     if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
     if ((rc = push_pending(ctx, s, frames, corr_out, status_out, nullptr)) != WM_OK) return rc;
     return sync_after ? do_sync(ctx, s) : WM_OK;

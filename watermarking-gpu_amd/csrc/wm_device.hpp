@@ -668,6 +668,54 @@ __device__ __forceinline__ double wave_sum(double v)
     const int hi = __builtin_amdgcn_readlane((int)(b >> 32), 63);
     return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
+// wrap-around integer sum over the wave (the digest of the checked hand-over): exact, so its order does not matter
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ unsigned long long dpp_mov0_u64(unsigned long long v)
+{
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)v, CTRL, ROW_MASK, 0xF, false);
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(v >> 32), CTRL, ROW_MASK, 0xF, false);
+    return ((unsigned long long)hi << 32) | lo;
+}
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
+{
+    v += dpp_mov0_u64<0x111, 0xF>(v);  // row_shr:1
+    v += dpp_mov0_u64<0x112, 0xF>(v);  // row_shr:2
+    v += dpp_mov0_u64<0x114, 0xF>(v);  // row_shr:4
+    v += dpp_mov0_u64<0x118, 0xF>(v);  // row_shr:8
+    v += dpp_mov0_u64<0x142, 0xA>(v);  // row_bcast15 into rows 1 and 3
+    v += dpp_mov0_u64<0x143, 0xC>(v);  // row_bcast31 into rows 2 and 3
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 63);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 63);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+// ---- digest of an f32 plane (checked Gram hand-over, wm_k_embed.hip / wm_k_detect.hip) ------------------------------------
+// D = sum over the pixels of v^2 (64-bit, wrap-around), v = (bits(y) ^ K_col(c)) + K_row(r) (32-bit, wrap-around), with hashed
+// keys.  For a fixed position v is a bijection of the pixel's bits and v -> v^2 is injective on [0, 2^32) with |v'^2 - v^2| <
+// 2^64, so ANY change of one pixel changes D.  The square and the xor make it nonlinear in the bits: zero-sum patterns such as
+// (+d, -2d, +d) along a row, or two swapped pixels (the keys differ by position), change it too, but for collisions of
+// probability ~2^-64.  Integer sums are exact: D does not depend on how waves, blocks or strips partition the plane, so the
+// embed and the detector can each sum it their own way.  K_col(c) = h(c & ~3) ^ (c & 3) * 0x9E3779B9: one key register per
+// lane of 4 pixels (a lane's first column is a multiple of 4 in both kernels).
+__device__ __forceinline__ uint32_t dig_mix(uint32_t h)
+{
+    h ^= h >> 16; h *= 0x7FEB352Du; h ^= h >> 15; h *= 0x846CA68Bu; h ^= h >> 16;
+    return h;
+}
+__device__ __forceinline__ uint32_t dig_row_key(int r) { return dig_mix((uint32_t)r * 0x9E3779B1u + 0x3C6EF372u); }
+__device__ __forceinline__ uint32_t dig_col_key4(int c0) { return dig_mix((uint32_t)c0 ^ 0xA54FF53Au); }  // c0: a multiple of 4
+// the 4 pixels of a lane at columns c0 .. c0+3 of row r: rk = dig_row_key(r), cb = dig_col_key4(c0)
+__device__ __forceinline__ void dig_add4(unsigned long long& acc, float y0, float y1, float y2, float y3, uint32_t rk, uint32_t cb)
+{
+    cb = pinned(cb);  // (keeps the 4 per-pixel keys from being hoisted out of the row loop into 4 registers)
+    const float y[4] = {y0, y1, y2, y3};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t v = (__float_as_uint(y[k]) ^ cb ^ ((uint32_t)k * 0x9E3779B9u)) + rk;
+        acc += (unsigned long long)v * v;
+    }
+}
+
 __device__ __forceinline__ float wave_max(float v)  // for values >= 0 (0 is the identity here)
 {
     v = fmaxf(v, dpp_mov0<0x111, 0xF>(v));

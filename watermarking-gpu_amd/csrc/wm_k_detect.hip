@@ -27,10 +27,12 @@ constexpr int PFWD = WM_PFW_DET;  // rows of W (and of W's halo column) prefetch
 //   correlation; NVF: m = nvf(x));  e_u = u - c.nbrs(u)  with u replicate-padded;
 //   per block: <e_u,e_w>, ||e_u||^2, ||e_w||^2          (Watermark.cpp:221-250)
 // =================================================================================================
-template <typename T, int MASK, int PAD, int HC, bool VEC, bool EDGE>
+// DIG (the checking instance, f32 on the overlapped aligned path): also the digest of the pixels this wave owns (dig_add,
+// wm_device.hpp) -- x rows rs .. re-1, lanes lo .. hi, as loaded
+template <typename T, int MASK, int PAD, int HC, bool VEC, bool EDGE, bool DIG = false>
 __device__ __forceinline__ void detect_march(const T* __restrict__ xf, long long pitch, const float* __restrict__ W,
                                              const Geom& g, const WaveJob& j, float* lds_x, float* lds_u,
-                                             const float (&c)[8], float& dot, float& nu, float& nw)
+                                             const float (&c)[8], float& dot, float& nu, float& nw, unsigned long long& dig)
 {
     constexpr int HRX = MASK == 0 ? 1 : PAD;  // x rows needed above/below a u row
     constexpr int NR = 2 * HRX + 1;
@@ -90,6 +92,8 @@ __device__ __forceinline__ void detect_march(const T* __restrict__ xf, long long
     // lanes that own their 4 columns: not the duplicate lanes of a shifted last strip (their sums belong to the previous strip),
     // and with overlapped strips (HALO1) only lanes lo .. hi -- those sum everything and are masked once, at the end
     const bool own = HALO1 || !EDGE || 4 * j.lane >= j.dup;
+    static_assert(!DIG || (HALO1 && std::is_same<T, float>::value), "digest: f32 planes on the overlapped aligned path");
+    const uint32_t dcb = DIG ? dig_col_key4(c0) : 0u;
     march_n<2 * HRX, DR>(n, [&](int i, auto qc, auto emit) {
         constexpr int Q = decltype(qc)::value;
         xm.template step<Q>(i);
@@ -116,6 +120,9 @@ __device__ __forceinline__ void detect_march(const T* __restrict__ xf, long long
                 ew[k] = ewn[k];
                 const float m = MASK == 0 ? fabsf(ew[k]) : nvf_value<PAD, O, Q>(xm, k);
                 uu[k] = m * f4get(w, k);
+            }
+            if constexpr (DIG) {
+                if (t >= j.rs && t < j.re) dig_add4(dig, xmid[O], xmid[O + 1], xmid[O + 2], xmid[O + 3], dig_row_key(t), dcb);
             }
             float* un = uw[Q % 3];
             if constexpr (HALO1) {
@@ -216,17 +223,47 @@ __device__ __forceinline__ void detect_march(const T* __restrict__ xf, long long
         // the provider lanes (and the lanes beyond the image's last column) summed pixels other lanes own: drop their sums
         const bool mine = j.lane >= j.lo && j.lane <= j.hi;
         dot = mine ? dot : 0.0f; nu = mine ? nu : 0.0f; nw = mine ? nw : 0.0f;
+        if constexpr (DIG) dig = mine ? dig : 0ull;
     }
 }
 
 // corr_fold (tail of k_detect; take_ticket, wm_device.hpp): the last wave of a strip folds the strip's records, the last
 // strip's wave folds the frame:
 // corr = (float)dot / (float)(||e_w|| * ||e_u||)   (Watermark.cpp:230); unsolvable => 0.0f (:246-247)
+// publish a frame's score -- or, in the checking instance (CK = 1), only when the digest of the plane this sweep read equals the
+// one the embed left (DigCheck); else flag the frame for the redo launches
+template <int CK>
+__device__ __forceinline__ void corr_publish(int frame, double a0, double a1, double a2, unsigned long long dg,
+                                             const int* __restrict__ status, OpResult* res, RawSums* raw, const DigCheck& dc)
+{
+    if constexpr (CK == 1) {
+        const bool ok = dg == dc.want[frame];
+        dc.redo[frame] = ok ? 0 : 1;
+        atomicAdd(dc.count + (ok ? 0 : 1), 1ull);
+        if (!ok) return;
+    }
+    const int st = status[frame];
+    float corr = 0.0f;
+    if (st == 0) corr = (float)a0 / (float)(sqrt(a2) * sqrt(a1));
+    res[frame].status = st;
+    res[frame].value = corr;
+    RawSums rw;
+    rw.v[0] = a0; rw.v[1] = a1; rw.v[2] = a2; rw.v[3] = 0.0;
+    raw[frame] = rw;
+}
+
+template <int CK>
 __device__ __forceinline__ void corr_fold(int frame, const WaveJob& j, const double* pcorr, int nrec,
-                                          const int* __restrict__ status, const CorrTail& tl)
+                                          const int* __restrict__ status, const CorrTail& tl, const DigCheck& dc)
 {
     const int lane = j.lane;
     if (!take_ticket(tl.ticket_strip + (frame * tl.nstrips + j.strip) * TKS, (unsigned)tl.nsegs, lane)) return;
+    unsigned long long dg = 0;
+    if constexpr (CK == 1) {
+        for (int s0 = lane; s0 < tl.nsegs; s0 += WAVE) dg += ld_agent(dc.pdig + (long long)frame * nrec + (long long)s0 * tl.nstrips + j.strip);
+        dg = wave_sum_u64(dg);
+        if (lane == 0) st_agent(dc.sdig + (long long)frame * tl.nstrips + j.strip, dg);
+    }
     // all loads of a batch are issued before the first is used (index clamped, surplus terms dropped): agent-scope loads
     // come from the memory side, a dependent chain of them costs a memory latency per term
     double a0 = 0.0, a1 = 0.0, a2 = 0.0;
@@ -250,31 +287,33 @@ __device__ __forceinline__ void corr_fold(int frame, const WaveJob& j, const dou
     }
     if (!take_ticket(tl.ticket + frame * TKS, (unsigned)tl.nstrips, lane)) return;
     a0 = 0.0; a1 = 0.0; a2 = 0.0;
+    dg = 0;
     for (int s0 = lane; s0 < tl.nstrips; s0 += WAVE) {
         const double* q = tl.scorr + ((long long)frame * tl.nstrips + s0) * 3;
         const double v0 = ld_agent(q), v1 = ld_agent(q + 1), v2 = ld_agent(q + 2);
         a0 += v0; a1 += v1; a2 += v2;
+        if constexpr (CK == 1) dg += ld_agent(dc.sdig + (long long)frame * tl.nstrips + s0);
     }
     a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2);
-    if (lane == 0) {
-        const int st = status[frame];
-        float corr = 0.0f;
-        if (st == 0) corr = (float)a0 / (float)(sqrt(a2) * sqrt(a1));
-        tl.res[frame].status = st;
-        tl.res[frame].value = corr;
-        RawSums rw;
-        rw.v[0] = a0; rw.v[1] = a1; rw.v[2] = a2; rw.v[3] = 0.0;
-        tl.raw[frame] = rw;
-    }
+    if constexpr (CK == 1) dg = wave_sum_u64(dg);
+    if (lane == 0) corr_publish<CK>(frame, a0, a1, a2, dg, status, tl.res, tl.raw, dc);
 }
 
 // corr_finalize_frame (tail of k_detect, run by the frame's last block):
 // corr = (float)dot / (float)(||e_w|| * ||e_u||)   (Watermark.cpp:230); unsolvable => 0.0f (:246-247)
+template <int CK>
 __device__ __forceinline__ void corr_finalize_frame(int frame, const double* pcorr, int nblk, const int* __restrict__ status,
-                                                    OpResult* __restrict__ res, RawSums* __restrict__ raw)
+                                                    OpResult* __restrict__ res, RawSums* __restrict__ raw, const DigCheck& dc)
 {
     __shared__ double s[3][BLOCK];
     const int t = threadIdx.x;
+    unsigned long long dg = 0;
+    if constexpr (CK == 1) {
+        if (t < WAVE) {
+            for (int b = t; b < nblk; b += WAVE) dg += ld_agent(dc.pdig + (long long)frame * nblk + b);
+            dg = wave_sum_u64(dg);
+        }
+    }
     double a0 = 0.0, a1 = 0.0, a2 = 0.0;
     // 2 x 3 partials in flight per thread (index clamped, surplus terms dropped), see solve_frame
     for (int b0 = t; b0 < nblk; b0 += 2 * BLOCK) {
@@ -296,63 +335,89 @@ __device__ __forceinline__ void corr_finalize_frame(int frame, const double* pco
         if (t < o) { s[0][t] += s[0][t + o]; s[1][t] += s[1][t + o]; s[2][t] += s[2][t + o]; }
         __syncthreads();
     }
-    if (t == 0) {
-        const int st = status[frame];
-        float corr = 0.0f;
-        if (st == 0) corr = (float)s[0][0] / (float)(sqrt(s[2][0]) * sqrt(s[1][0]));
-        res[frame].status = st;
-        res[frame].value = corr;
-        RawSums rw;
-        rw.v[0] = s[0][0]; rw.v[1] = s[1][0]; rw.v[2] = s[2][0]; rw.v[3] = 0.0;
-        raw[frame] = rw;
-    }
+    if (t == 0) corr_publish<CK>(frame, s[0][0], s[1][0], s[2][0], dg, status, res, raw, dc);
 }
 
-template <typename T, int MASK, int PAD, int HC, bool VEC>
-// occupancy floor: 4 waves per SIMD for the aligned 3x3 instances (105 / 106 / 91 VGPRs); the generic instances (LDS re-lay,
-// halo predictions of their own) need ~150 registers -- bound to 4 they spilled 48-70 VGPRs to scratch, at 3 they do not
-__global__ __launch_bounds__(BLOCK, (PAD == 1 && HC == 1 ? (VEC ? WM_DET_WAVES : 3) : 1)) void k_detect(const T* __restrict__ x, long long pitch, long long fstride,
-                                                  const float* __restrict__ W, Geom g,
-                                                  const float* __restrict__ coef, const int* __restrict__ status,
-                                                  double* pcorr, CorrTail tail)
+// CK: 0 = the ordinary sweep; 1 = the checking instance of a checked hand-over (DigCheck, wm_kernels.hpp: every frame's march
+// runs -- an unsolvable one too, its sums dropped -- for the digest); 2 = k_detect_redo (frames with dc.redo[f] == 0 leave first)
+template <typename T, int MASK, int PAD, int HC, bool VEC, int CK>
+__device__ __forceinline__ void detect_body(const T* __restrict__ x, long long pitch, long long fstride, const float* __restrict__ W,
+                                            const Geom& g, const float* __restrict__ coef, const int* __restrict__ status,
+                                            double* pcorr, const CorrTail& tail, const DigCheck& dc)
 {
     __shared__ __attribute__((aligned(16))) float s_row[WPB][2 * RowBuf<HC>::N];
     __shared__ __attribute__((aligned(16))) float s_u[WPB][2 * RowBuf<1>::N];
     __shared__ double s_red[WPB][3];
+    __shared__ unsigned long long s_dig[WPB];
     const WaveJob j = make_job(g);
     const int frame = j.frame;
+    if constexpr (CK == 2) {
+        // quad: the waves of a block are different frames (surplus waves of a short last quad have none) -- a wave-uniform exit, no
+        // barrier on that path; else the block is one frame (its waves past the last segment still take part in the barrier)
+        if (g.quad ? (!j.valid || dc.redo[frame] == 0) : dc.redo[frame] == 0) return;
+    }
     float dot = 0.0f, nu = 0.0f, nw = 0.0f;
-    if (j.valid && status[frame] == 0) {
+    unsigned long long dig = 0;
+    const int st = j.valid ? status[frame] : 1;
+    if (j.valid && (CK == 1 || st == 0)) {
         float c[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) c[k] = coef[frame * 8 + k];
         const T* xf = x + (long long)frame * fstride;
         constexpr bool DPP_OK = HC == 1;  // the halo of p = 9 (HC = 2) exceeds one neighbour chunk: LDS path only
         constexpr bool V = VEC && DPP_OK;
-        if (MASK != 0 || strip_on_edge<V>(g, j)) detect_march<T, MASK, PAD, HC, V, true>(xf, pitch, W, g, j, s_row[j.wave], s_u[j.wave], c, dot, nu, nw);
-        else detect_march<T, MASK, PAD, HC, V, (MASK != 0)>(xf, pitch, W, g, j, s_row[j.wave], s_u[j.wave], c, dot, nu, nw);
+        constexpr bool D = CK == 1;
+        if (MASK != 0 || strip_on_edge<V>(g, j)) detect_march<T, MASK, PAD, HC, V, true, D>(xf, pitch, W, g, j, s_row[j.wave], s_u[j.wave], c, dot, nu, nw, dig);
+        else detect_march<T, MASK, PAD, HC, V, (MASK != 0), D>(xf, pitch, W, g, j, s_row[j.wave], s_u[j.wave], c, dot, nu, nw, dig);
+        if (CK == 1 && st != 0) { dot = 0.0f; nu = 0.0f; nw = 0.0f; }  // (what the ordinary sweep sums for an unsolvable frame)
     }
     const double d0 = wave_sum((double)dot), d1 = wave_sum((double)nu), d2 = wave_sum((double)nw);
+    if constexpr (CK == 1) dig = wave_sum_u64(dig);
     if (g.quad) {
         // the waves of this block are 4 frames: one record per wave, folded per strip and then per frame (corr_fold)
         if (!j.valid) return;  // surplus wave of a short last quad (wave-uniform; no barrier below)
         if (j.lane == 0) {
             double* p = pcorr + ((long long)frame * g.nrec + j.rec) * 3;
             st_agent(p, d0); st_agent(p + 1, d1); st_agent(p + 2, d2);
+            if constexpr (CK == 1) st_agent(dc.pdig + (long long)frame * g.nrec + j.rec, dig);
         }
-        corr_fold(frame, j, pcorr, g.nrec, status, tail);
+        corr_fold<CK>(frame, j, pcorr, g.nrec, status, tail, dc);
         return;
     }
     // the waves of this block are 4 segments of one frame: one record per block, folded by the frame's last block
-    if (j.lane == 0) { s_red[j.wave][0] = d0; s_red[j.wave][1] = d1; s_red[j.wave][2] = d2; }
+    if (j.lane == 0) { s_red[j.wave][0] = d0; s_red[j.wave][1] = d1; s_red[j.wave][2] = d2; s_dig[j.wave] = dig; }
     __syncthreads();
     if (threadIdx.x < 3) {
         const int k = threadIdx.x;
         st_agent(pcorr + ((long long)frame * g.nblk_total + g.pb0 + j.tile) * 3 + k, ((s_red[0][k] + s_red[1][k]) + s_red[2][k]) + s_red[3][k]);
     }
+    if (CK == 1 && threadIdx.x == 3)
+        st_agent(dc.pdig + (long long)frame * g.nblk_total + g.pb0 + j.tile, s_dig[0] + s_dig[1] + s_dig[2] + s_dig[3]);
     if (last_block_of_frame(tail.ticket + frame * TKS, (unsigned)tail.expected))
-        corr_finalize_frame(frame, pcorr, g.nblk_total, status, tail.res, tail.raw);
+        corr_finalize_frame<CK>(frame, pcorr, g.nblk_total, status, tail.res, tail.raw, dc);
 }
+
+// occupancy floor: 4 waves per SIMD for the aligned 3x3 instances (105 / 106 / 91 VGPRs); the generic instances (LDS re-lay,
+// halo predictions of their own) need ~150 registers -- bound to 4 they spilled 48-70 VGPRs to scratch, at 3 they do not
+#define WM_DET_BOUNDS (PAD == 1 && HC == 1 ? (VEC ? WM_DET_WAVES : 3) : 1)
+template <typename T, int MASK, int PAD, int HC, bool VEC, int CK = 0>
+__global__ __launch_bounds__(BLOCK, WM_DET_BOUNDS) void k_detect(const T* __restrict__ x, long long pitch, long long fstride,
+                                                                 const float* __restrict__ W, Geom g,
+                                                                 const float* __restrict__ coef, const int* __restrict__ status,
+                                                                 double* pcorr, CorrTail tail, DigCheck dc)
+{
+    detect_body<T, MASK, PAD, HC, VEC, CK>(x, pitch, fstride, W, g, coef, status, pcorr, tail, dc);
+}
+// the fallback of a checked hand-over: k_detect over the frames whose digest did not match (a kernel of its own for profiles)
+template <typename T, int MASK, int PAD, int HC, bool VEC>
+__global__ __launch_bounds__(BLOCK, WM_DET_BOUNDS) void k_detect_redo(const T* __restrict__ x, long long pitch, long long fstride,
+                                                                      const float* __restrict__ W, Geom g,
+                                                                      const float* __restrict__ coef, const int* __restrict__ status,
+                                                                      double* pcorr, CorrTail tail, DigCheck dc)
+{
+    detect_body<T, MASK, PAD, HC, VEC, 2>(x, pitch, fstride, W, g, coef, status, pcorr, tail, dc);
+}
+#undef WM_DET_BOUNDS
 
 // results of a mask-only op: status + coefficients
 __global__ void k_mask_result(const int* __restrict__ status, const float* __restrict__ coef, OpResult* __restrict__ res,
@@ -367,11 +432,11 @@ __global__ void k_mask_result(const int* __restrict__ status, const float* __res
 template <typename T>
 static void launch_detect_t(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x,
                             const float* W, int aligned_w, const float* coef, const int* status, double* pcorr,
-                            const CorrTail& tail, bool split)
+                            const CorrTail& tail, bool split, const DigCheck& dc)
 {
 #define DET(MASK, P, HC)                                                                                                      \
     WM_LAUNCH_SWEEP_Q(s, lg, frames, align_mode(lg, x.aligned && aligned_w && HC == 1), (k_detect<T, MASK, P, HC, true>), (k_detect<T, MASK, P, HC, false>), \
-                    (const T*)x.p, x.pitch, x.fstride, W, g, coef, status, pcorr, tail)
+                    (const T*)x.p, x.pitch, x.fstride, W, g, coef, status, pcorr, tail, dc)
     // 3x3 masks: the aligned instantiation works on overlapped strips (every strip, when all planes allow vector access and
     // the width is a multiple of 4); otherwise the whole image takes the generic instantiation
 #define DET3P(MASK, P)                                                                                                          \
@@ -379,16 +444,16 @@ static void launch_detect_t(hipStream_t s, const LaunchGeom& lg, int frames, int
         if (align_mode(lg, x.aligned && aligned_w) == 2) {                                                                    \
             const SweepPart pv_ = sweep_part_overlap(lg, frames, 1);                                                          \
             const Geom g = pv_.g;                                                                                             \
-            WM_KLAUNCH((k_detect<T, MASK, P, 1, true>), pv_.grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, W, g, coef, status, pcorr, tail); \
+            WM_KLAUNCH((k_detect<T, MASK, P, 1, true>), pv_.grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, W, g, coef, status, pcorr, tail, dc); \
         } else if (split) {                                                                                                   \
             /* a width that is not a multiple of 4: overlapped strips below column B + one generic strip (wm_march.hpp) */     \
             { const SweepPart pv_ = sweep_part_split_overlap(lg, frames, 1); const Geom g = pv_.g;                              \
-              WM_KLAUNCH((k_detect<T, MASK, P, 1, true>), pv_.grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, W, g, coef, status, pcorr, tail); } \
+              WM_KLAUNCH((k_detect<T, MASK, P, 1, true>), pv_.grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, W, g, coef, status, pcorr, tail, dc); } \
             { const SweepPart pg_ = sweep_part_split_generic(lg, frames, 1); const Geom g = pg_.g;                              \
-              WM_KLAUNCH((k_detect<T, MASK, P, 1, false>), pg_.grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, W, g, coef, status, pcorr, tail); } \
+              WM_KLAUNCH((k_detect<T, MASK, P, 1, false>), pg_.grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, W, g, coef, status, pcorr, tail, dc); } \
         } else {                                                                                                              \
             WM_LAUNCH_SWEEP_Q(s, lg, frames, 0, (k_detect<T, MASK, P, 1, true>), (k_detect<T, MASK, P, 1, false>),           \
-                              (const T*)x.p, x.pitch, x.fstride, W, g, coef, status, pcorr, tail);                            \
+                              (const T*)x.p, x.pitch, x.fstride, W, g, coef, status, pcorr, tail, dc);                            \
         }                                                                                                                     \
     } while (0)
     if (mask == 0) { DET3P(0, 1); return; }
@@ -401,10 +466,24 @@ static void launch_detect_t(hipStream_t s, const LaunchGeom& lg, int frames, int
 #undef DET
 #undef DET3P
 }
+bool detect_checkable(const LaunchGeom& lg, int mask, int pad, const PlaneDesc& x, int aligned_w)
+{
+    return x.dtype == 0 && mask == 0 && pad == 1 && align_mode(lg, x.aligned && aligned_w) == 2;
+}
 void launch_detect(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* W,
                    int aligned_w, const float* coef, const int* status, double* pcorr, unsigned* ticket, unsigned* ticket_strip,
-                   double* scorr, OpResult* res, RawSums* raw)
+                   double* scorr, OpResult* res, RawSums* raw, const DigCheck* dc, int mode)
 {
+    if (mode != 0) {
+        // the checking instance and its redo launch: f32, ME, overlapped strips (detect_checkable, checked by the caller)
+        const LaunchGeom ld = overlap_geom(lg);
+        const CorrTail tail{ticket, ticket_strip, ld.nblk, ld.nsegs, ld.nstrips, scorr, res, raw};
+        const SweepPart pv = sweep_part_overlap(ld, frames, 1);
+        if (mode == 1) WM_KLAUNCH((k_detect<float, 0, 1, 1, true, 1>), pv.grid, dim3(BLOCK), 0, s, (const float*)x.p, x.pitch, x.fstride, W, pv.g, coef, status, pcorr, tail, *dc);
+        else WM_KLAUNCH((k_detect_redo<float, 0, 1, 1, true>), pv.grid, dim3(BLOCK), 0, s, (const float*)x.p, x.pitch, x.fstride, W, pv.g, coef, status, pcorr, tail, *dc);
+        return;
+    }
+    const DigCheck none{nullptr, nullptr, nullptr, nullptr, nullptr};
     // the aligned 3x3 path runs on overlapped strips: more, narrower strips than the other sweeps of the call (overlap_geom);
     // the records, the strip tickets and the fold follow that strip count
     const bool overlap = (mask == 0 || pad <= 3) && align_mode(lg, x.aligned && aligned_w) == 2;
@@ -412,7 +491,7 @@ void launch_detect(hipStream_t s, const LaunchGeom& lg, int frames, int mask, in
     const bool split = (mask == 0 || pad == 1) && !overlap && x.aligned && aligned_w && split_applies(lg.cols);
     const LaunchGeom ld = overlap ? overlap_geom(lg) : (split ? split_geom(lg) : lg);
     const CorrTail tail{ticket, ticket_strip, ld.nblk, ld.nsegs, ld.nstrips, scorr, res, raw};
-    WM_DISPATCH_T(x.dtype, launch_detect_t<T>(s, ld, frames, mask, pad, x, W, aligned_w, coef, status, pcorr, tail, split));
+    WM_DISPATCH_T(x.dtype, launch_detect_t<T>(s, ld, frames, mask, pad, x, W, aligned_w, coef, status, pcorr, tail, split, none));
 }
 
 // ---- W on the device: the counter-based N(0,1) generator of csrc/app/wm_genw.cpp (the replacement of the reference's

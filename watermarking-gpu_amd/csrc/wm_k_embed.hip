@@ -324,7 +324,7 @@ __device__ __forceinline__ void embed_march(const TX* __restrict__ xf, long long
                                             const TB* __restrict__ bptr, TB* __restrict__ optr, const PlaneDesc& base,
                                             const PlaneDesc& out, const Geom& g, const WaveJob& j, float* lds, float* obuf,
                                             const float (&c)[8], float a, float maxe, bool pass = false, double* horec = nullptr,
-                                            float* hoseam = nullptr)
+                                            float* hoseam = nullptr, unsigned long long* hodig = nullptr)
 {
     static_assert(!HO || (VEC && NCH == 1 && sizeof(TB) == 4), "hand-over: grey f32 planes on the aligned path");
     constexpr int NR = MASK == 0 ? 3 : 2 * PAD + 1;
@@ -360,6 +360,9 @@ __device__ __forceinline__ void embed_march(const TX* __restrict__ xf, long long
 #pragma unroll
         for (int k = 0; k < 4; ++k) ho.cv[k] = !EDGE || (c0 + k >= 2 && c0 + k <= g.cols - 3 && 4 * j.lane >= j.dup);
     }
+    // digest of the stored y (dig_add, wm_device.hpp): the pixels this lane stores, as stored
+    unsigned long long dig = 0;
+    const uint32_t dcb = HO ? dig_col_key4(c0) : 0u;
     // this lane's entry of the seam array, or null: lane 63 holds columns S-2, S-1 of the boundary behind its strip, the first
     // lane that owns pixels (lane 0, or dup / 4 in a shifted last strip) holds columns S, S+1 of the boundary in front of it
     float* seamp = nullptr;
@@ -411,6 +414,8 @@ __device__ __forceinline__ void embed_march(const TX* __restrict__ xf, long long
                     ho_row<Q % 3>(ho, y, o >= 2 && rq >= 1 && rq < g.rows - 2);
                     if (seamp && o < nout)
                         *reinterpret_cast<float2*>(seamp + (long long)(j.rs + o) * 4) = seam_right ? make_float2(y.z, y.w) : make_float2(y.x, y.y);
+                    if (o < nout && (!EDGE || 4 * j.lane >= j.dup))  // (duplicate lanes of a shifted last strip store nothing)
+                        dig_add4(dig, y.x, y.y, y.z, y.w, dig_row_key(j.rs + o), dcb);
                 }
                 if constexpr (VEC) {
                     if ((!EDGE || 4 * j.lane >= j.dup) && (!HO || o < nout))  // duplicate lanes of a shifted last strip: the previous strip stores these pixels
@@ -427,6 +432,8 @@ __device__ __forceinline__ void embed_march(const TX* __restrict__ xf, long long
         int idx;
         const double t = wave_sum_multi<13>(ho.acc, j.lane, idx);
         if (idx < 13) horec[idx] = t;
+        const unsigned long long dw = wave_sum_u64(dig);
+        if (j.lane == 0) *hodig = dw;
     }
 }
 
@@ -473,11 +480,12 @@ __global__ __launch_bounds__(BLOCK, HO ? WM_HO_BLOCKS : 1) void k_embed(const TX
     const bool pass = HO && st != 0;
     double* horec = HO ? ho.rec + ((long long)frame * ho.stride + j.rec) * 13 : nullptr;
     float* hoseam = HO ? ho.seam : nullptr;
+    unsigned long long* hodig = HO ? ho.dig + (long long)frame * ho.stride + j.rec : nullptr;
     // NVF windows (PAD > 1) keep the single instance: their halo fix-up is a small share of the step
     if (MASK != 0 || strip_on_edge<VEC>(g, j))
-        embed_march<TX, TB, NCH, MASK, PAD, VEC, BX, true, HO>(xf, pitch, W, bptr, optr, base, out, g, j, s_row[j.wave], s_out[VEC ? 0 : j.wave], c, a, maxe, pass, horec, hoseam);
+        embed_march<TX, TB, NCH, MASK, PAD, VEC, BX, true, HO>(xf, pitch, W, bptr, optr, base, out, g, j, s_row[j.wave], s_out[VEC ? 0 : j.wave], c, a, maxe, pass, horec, hoseam, hodig);
     else
-        embed_march<TX, TB, NCH, MASK, PAD, VEC, BX, (MASK != 0), HO>(xf, pitch, W, bptr, optr, base, out, g, j, s_row[j.wave], s_out[VEC ? 0 : j.wave], c, a, maxe, pass, horec, hoseam);
+        embed_march<TX, TB, NCH, MASK, PAD, VEC, BX, (MASK != 0), HO>(xf, pitch, W, bptr, optr, base, out, g, j, s_row[j.wave], s_out[VEC ? 0 : j.wave], c, a, maxe, pass, horec, hoseam, hodig);
 }
 
 // =================================================================================================
@@ -583,12 +591,12 @@ static bool launch_embed_tt(hipStream_t s, const LaunchGeom& lg, int frames, int
     const int al = align_mode(lg, x.aligned && aligned_w && base.aligned && out.aligned);
     // the base is the grey input itself (same plane, same layout): k_embed then takes it from its stencil window
     const bool bx = NCH == 1 && std::is_same<TX, TB>::value && base.p == x.p && base.pitch == x.pitch && base.fstride == x.fstride;
-    const HandOver none{nullptr, 0, nullptr};
+    const HandOver none{nullptr, 0, nullptr, nullptr, nullptr};
     if constexpr (NCH == 1 && std::is_same<TX, float>::value && std::is_same<TB, float>::value) {
         // Gram hand-over: every strip on the aligned path (one launch), 3x3 windows, a core, segments of two rows or more; two
         // frames or more (measured at 4K: one frame -3 %, two +2 %, four +6..9 %, eight and more +9..11 % -- a one-frame launch of
         // k_gram_ho is as latency-bound as the k_gram it replaces)
-        if (ho && ho->rec && frames >= 2 && al == 2 && lg.nfull > 0 && pad == 1 && lg.rps >= 2 && lg.rows >= 4 && lg.cols >= 5 && lg.row_lo == 0 && lg.row_hi == lg.rows) {
+        if (ho && ho->rec && ho->dig && frames >= 2 && al == 2 && lg.nfull > 0 && pad == 1 && lg.rps >= 2 && lg.rows >= 4 && lg.cols >= 5 && lg.row_lo == 0 && lg.row_hi == lg.rows) {
             const SweepPart pv_ = sweep_part(lg, frames, true, al, 1);
             const Geom g = pv_.g;
 #define EMB_HO(MASK)                                                                                                            \

@@ -327,13 +327,15 @@ __device__ __forceinline__ void solve_frame(int frame, const double* pmain, int 
 // march blocks: 13 lag sums over the core, one partial record per block
 // With nbb > 0 the first nbb blocks of the grid evaluate the border frame (they are few and latency-bound, so they
 // should start first and overlap the march instead of costing a launch of their own); the march blocks follow.
+// redo (k_gram_redo): the blocks of frames with redo[f] == 0 leave before they touch a record or a ticket
 template <typename T, bool VEC>
-__global__ __launch_bounds__(BLOCK, WM_GRAM_WAVES) void k_gram(const T* __restrict__ x, long long pitch, long long fstride, Geom g, int nbb,
-                                                double* pmain, double* pborder, SolveTail tail)
+__device__ __forceinline__ void gram_body(const T* __restrict__ x, long long pitch, long long fstride, const Geom& g, int nbb,
+                                          double* pmain, double* pborder, const SolveTail& tail, const int* __restrict__ redo)
 {
     const int nlead = nbb * g.frames;  // leading border blocks: nbb per frame
     if ((int)blockIdx.x < nlead) {
         const int bfr = (int)blockIdx.x / nbb;
+        if (redo && redo[bfr] == 0) return;
         gram_border_block<T, VEC>(x, pitch, fstride, g.rows, g.cols, nbb, (int)blockIdx.x - bfr * nbb, bfr, pborder, g.row_lo, g.row_hi);
         if (last_block_of_frame(tail.ticket + bfr * TKS, (unsigned)tail.expected))
             solve_frame(bfr, pmain, g.nblk_total, pborder, tail.nbb_total, tail.coef, tail.status, tail.gram_tot);
@@ -345,6 +347,7 @@ __global__ __launch_bounds__(BLOCK, WM_GRAM_WAVES) void k_gram(const T* __restri
     const bool core_empty = R < 4 || C < 5;
     const WaveJob j = make_job(g, (int)blockIdx.x - nlead);
     const int frame = j.frame;
+    if (redo && redo[frame] == 0) return;  // (block-uniform: the 4 waves of a k_gram block are segments of one frame)
     const T* xf = x + (long long)frame * fstride;
     double acc[13];
 #pragma unroll
@@ -365,6 +368,31 @@ __global__ __launch_bounds__(BLOCK, WM_GRAM_WAVES) void k_gram(const T* __restri
     if (last_block_of_frame(tail.ticket + frame * TKS, (unsigned)tail.expected))
         solve_frame(frame, pmain, g.nblk_total, pborder, tail.nbb_total, tail.coef, tail.status, tail.gram_tot);
 }
+template <typename T, bool VEC>
+__global__ __launch_bounds__(BLOCK, WM_GRAM_WAVES) void k_gram(const T* __restrict__ x, long long pitch, long long fstride, Geom g, int nbb,
+                                                double* pmain, double* pborder, SolveTail tail)
+{
+    gram_body<T, VEC>(x, pitch, fstride, g, nbb, pmain, pborder, tail, nullptr);
+}
+// the fallback of a checked hand-over (DigCheck, wm_kernels.hpp): k_gram over the frames whose digest did not match -- a kernel
+// of its own so that profiles tell its (normally empty) launches from the Gram sweeps
+template <typename T, bool VEC>
+__global__ __launch_bounds__(BLOCK, WM_GRAM_WAVES) void k_gram_redo(const T* __restrict__ x, long long pitch, long long fstride, Geom g, int nbb,
+                                                     double* pmain, double* pborder, SolveTail tail, const int* __restrict__ redo)
+{
+    gram_body<T, VEC>(x, pitch, fstride, g, nbb, pmain, pborder, tail, redo);
+}
+
+// the frame's digest of y (HandOver::fdig): the seam blocks' shares of the embed's digest records, folded by the frame's last
+// block (wrap-around integer sums: exact in any order).  One wave, 64 records per round
+__device__ __forceinline__ void ho_digest_frame(int frame, const HandOver& ho, int nrec, int nsb)
+{
+    if (threadIdx.x >= WAVE) return;
+    unsigned long long d = 0;
+    for (int b = (int)threadIdx.x; b < nsb; b += WAVE) d += ld_agent(ho.dig + (long long)frame * ho.stride + nrec + b);
+    d = wave_sum_u64(d);
+    if (threadIdx.x == 0) ho.fdig[frame] = d;
+}
 
 // =================================================================================================
 // k_gram_ho: the detector's Gram matrix of a plane y whose tile-internal lag sums the embed left behind (HandOver).  Blocks
@@ -378,8 +406,10 @@ __global__ __launch_bounds__(BLOCK) void k_gram_ho(const float* __restrict__ y, 
     if ((int)blockIdx.x < nlead) {
         const int bfr = (int)blockIdx.x / nbb;
         gram_border_block<float, true>(y, pitch, fstride, g.rows, g.cols, nbb, (int)blockIdx.x - bfr * nbb, bfr, pborder, g.row_lo, g.row_hi);
-        if (last_block_of_frame(tail.ticket + bfr * TKS, (unsigned)tail.expected))
+        if (last_block_of_frame(tail.ticket + bfr * TKS, (unsigned)tail.expected)) {
+            ho_digest_frame(bfr, ho, g.nrec, nsb);
             solve_frame(bfr, ho.rec + (long long)g.nrec * 13, nsb, pborder, tail.nbb_total, tail.coef, tail.status, tail.gram_tot, ho.stride);
+        }
         return;
     }
     __shared__ double s_red[WPB][13];
@@ -419,12 +449,21 @@ __global__ __launch_bounds__(BLOCK) void k_gram_ho(const float* __restrict__ y, 
             for (int u = 0; u < 4; ++u) wsum += r0 + u * nsb < g.nrec ? v[u] : 0.0;
         }
     }
+    if (threadIdx.x == WAVE) {
+        // ... and of their digest records (a lane of the second wave)
+        const unsigned long long* wd = ho.dig + (long long)frame * ho.stride;
+        unsigned long long d = 0;
+        for (int r0 = t; r0 < g.nrec; r0 += nsb) d += wd[r0];
+        st_agent(ho.dig + (long long)frame * ho.stride + g.nrec + t, d);
+    }
     __syncthreads();
     if (threadIdx.x < 13)
         st_agent(ho.rec + ((long long)frame * ho.stride + g.nrec + t) * 13 + threadIdx.x,
                  (((s_red[0][threadIdx.x] + s_red[1][threadIdx.x]) + s_red[2][threadIdx.x]) + s_red[3][threadIdx.x]) + wsum);
-    if (last_block_of_frame(tail.ticket + frame * TKS, (unsigned)tail.expected))
+    if (last_block_of_frame(tail.ticket + frame * TKS, (unsigned)tail.expected)) {
+        ho_digest_frame(frame, ho, g.nrec, nsb);
         solve_frame(frame, ho.rec + (long long)g.nrec * 13, nsb, pborder, tail.nbb_total, tail.coef, tail.status, tail.gram_tot, ho.stride);
+    }
 }
 
 // band mode (intra-frame sharding): the Gram totals of a frame were all-reduced over the ranks; solve from them
@@ -513,7 +552,7 @@ void launch_gram_ho(hipStream_t s, const LaunchGeom& lg, int frames, const Plane
 }
 
 void launch_gram(hipStream_t s, const LaunchGeom& lg, int frames, const PlaneDesc& x, double* pmain, double* pborder,
-                 unsigned* ticket, float* coef, int* status, double* gram_tot)
+                 unsigned* ticket, float* coef, int* status, double* gram_tot, const int* redo)
 {
     // the border blocks ride in the first launch of the sweep (the aligned-path one when it exists)
     const int al = align_mode(lg, x.aligned != 0);
@@ -527,15 +566,19 @@ void launch_gram(hipStream_t s, const LaunchGeom& lg, int frames, const PlaneDes
         Geom g = pv.g;
         g.frame_fastest = 0;  // the Gram sweep reads no W: keep a frame's tiles together (halo rows stay in L2)
         const dim3 grid(pv.grid.x + nbb_v * frames, 1, 1);
-        WM_DISPATCH_T(x.dtype, WM_KLAUNCH((k_gram<T, true>), grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, g, nbb_v,
-                                                   pmain, pborder, tail));
+        if (redo) WM_DISPATCH_T(x.dtype, WM_KLAUNCH((k_gram_redo<T, true>), grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, g, nbb_v,
+                                                             pmain, pborder, tail, redo));
+        else WM_DISPATCH_T(x.dtype, WM_KLAUNCH((k_gram<T, true>), grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, g, nbb_v,
+                                                        pmain, pborder, tail));
     }
     if (pg.run) {
         Geom g = pg.g;
         g.frame_fastest = 0;
         const dim3 grid(pg.grid.x + nbb_g * frames, 1, 1);
-        WM_DISPATCH_T(x.dtype, WM_KLAUNCH((k_gram<T, false>), grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, g, nbb_g,
-                                                   pmain, pborder, tail));
+        if (redo) WM_DISPATCH_T(x.dtype, WM_KLAUNCH((k_gram_redo<T, false>), grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, g, nbb_g,
+                                                             pmain, pborder, tail, redo));
+        else WM_DISPATCH_T(x.dtype, WM_KLAUNCH((k_gram<T, false>), grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, g, nbb_g,
+                                                        pmain, pborder, tail));
     }
 }
 

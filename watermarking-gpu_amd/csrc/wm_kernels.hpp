@@ -145,8 +145,9 @@ int launch_fused_embed(hipStream_t s, const FusedGeom& fg, const FusedScratch& s
 int launch_fused_detect(hipStream_t s, const FusedGeom& fg, const FusedScratch& sc, unsigned epoch, int mask, const PlaneDesc& x,
                         const float* W, OpResult* res);
 
+// redo: frames with redo[f] == 0 are skipped (k_gram_redo, the fallback of a checked hand-over), null: every frame (k_gram)
 void launch_gram(hipStream_t s, const LaunchGeom& lg, int frames, const PlaneDesc& x, double* pmain, double* pborder,
-                 unsigned* ticket, float* coef, int* status, double* gram_tot);
+                 unsigned* ticket, float* coef, int* status, double* gram_tot, const int* redo = nullptr);
 void launch_me_stats(hipStream_t s, const LaunchGeom& lg, int frames, const PlaneDesc& x, const float* W, int aligned_w,
                      const float* coef, const int* status, float* pmax, double* pss, unsigned* ticket, unsigned* ticket_strip,
                      float* smax, double* sss, float sF, double sqrt_n, EmbedScalars* scal, OpResult* res, RawSums* raw);
@@ -160,10 +161,26 @@ void launch_nvf_stats(hipStream_t s, const LaunchGeom& lg, int frames, const Pla
 // border frame and the solve -- the detector's Gram sweep over y is not run.
 //   rec:  [frames][stride][13]            wave records at [0, nstrips * nsegs), k_gram_ho's seam-block records behind them
 //   seam: [frames][nstrips - 1][rows][4]  y at columns S-2, S-1, S, S+1 of the boundary S in front of strip k (k = 1 ..)
+//   dig:  [frames][stride]                digest records of y (dig_add, wm_device.hpp): one per wave of k_embed, k_gram_ho's
+//                                         seam-block shares of them behind
+//   fdig: [frames]                        the digest of each frame of y, folded by k_gram_ho's last block
 struct HandOver {
     double* rec;
     int stride;
     float* seam;
+    unsigned long long* dig;
+    unsigned long long* fdig;
+};
+// Checked hand-over (wm_detect on the plane a slot's last embed wrote): k_detect's checking instance sums the digest of the
+// plane it reads and holds it against HandOver::fdig -- equal: the score stands; different: nothing is published, redo[f] = 1,
+// and the predicated k_gram_redo / k_detect_redo that follow redo that frame from the plane as it is (their blocks of frames
+// with redo[f] = 0 leave at once, before any ticket)
+struct DigCheck {
+    unsigned long long* pdig;        // [frames][records] digest records of this sweep
+    unsigned long long* sdig;        // [frames][nstrips] strip records (Geom::quad)
+    const unsigned long long* want;  // [frames] HandOver::fdig
+    int* redo;                       // [frames] written by the checking instance, read by the redo launches
+    unsigned long long* count;       // [2] frames trusted / redone (cumulative)
 };
 int handover_seam_blocks(const LaunchGeom& lg);   // seam blocks per frame of k_gram_ho for this geometry
 // returns true when the hand-over instantiation ran (f32 grey planes on the aligned path, p = 3, segments of >= 2 rows)
@@ -175,9 +192,12 @@ void launch_gram_ho(hipStream_t s, const LaunchGeom& lg, int frames, const Plane
                     unsigned* ticket, float* coef, int* status, double* gram_tot);
 void launch_mask(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* coef,
                  const int* status, const EmbedScalars* scal, const PlaneDesc& mo, const PlaneDesc& eo);
+// dc / mode: 0 = the ordinary sweep (dc unused); 1 = the checking instance (f32 planes on the overlapped aligned 3x3 path:
+// detect_checkable); 2 = k_detect_redo, the frames with dc->redo[f] != 0 only
 void launch_detect(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* W,
                    int aligned_w, const float* coef, const int* status, double* pcorr, unsigned* ticket, unsigned* ticket_strip,
-                   double* scorr, OpResult* res, RawSums* raw);
+                   double* scorr, OpResult* res, RawSums* raw, const DigCheck* dc = nullptr, int mode = 0);
+bool detect_checkable(const LaunchGeom& lg, int mask, int pad, const PlaneDesc& x, int aligned_w);
 // one image against a bank of keys (wm_detect_keys, wm_k_detect_keys.hip): k_detect's sweep for every key of the bank, key
 // groups as a grid axis, then one fold block per (frame, key) into res[frame * nkeys + key].  part: [frames][2 nkeys + 1][rstride]
 // doubles of scratch.  Returns -1 when the sweep's records exceed rstride (nothing is launched)
