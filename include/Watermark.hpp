@@ -55,6 +55,20 @@ public:
         if (!p) throw std::runtime_error("wm::Image: device allocation failed (no usable HIP device?)\n");
         buf_ = std::shared_ptr<void>(p, [device, nb](void* q) { pool_give(device, nb, q); });
     }
+    // n images of one shape in ONE device buffer, image i at i * elements() (each shares the buffer; what a batched plane
+    // with frame stride elements() addresses)
+    static std::vector<Image> stack(int n, dim_t rows, dim_t cols, int channels = 1, dtype t = dtype::f32, int device = 0)
+    {
+        Image all(rows * n, cols, channels, t, device);
+        const size_t each = all.bytes() / (size_t)n;
+        std::vector<Image> v((size_t)n);
+        for (int i = 0; i < n; ++i) {
+            Image& im = v[(size_t)i];
+            im.rows_ = rows; im.cols_ = cols; im.channels_ = channels; im.type_ = t; im.device_ = device;
+            im.buf_ = std::shared_ptr<void>(all.buf_, static_cast<char*>(all.buf_.get()) + (size_t)i * each);
+        }
+        return v;
+    }
     static Image fromHost(const float* data, dim_t rows, dim_t cols, int channels = 1, int device = 0)
     {
         Image im(rows, cols, channels, dtype::f32, device);
@@ -225,6 +239,26 @@ public:
         const int rc = wm_detect_keys(ctx, (int)maskType, &pimg, keys.handle(), corr.data(), nullptr, WM_SLOT_SYNC);
         if (rc < 0) fail(rc, "detectWatermarkKeys");
         return corr;
+    }
+    // makeWatermark of one grey image with every key of `keys` as W in one call (wm.h wm_embed_keys): copy k is what
+    // makeWatermark returns with key k as W, strengths[k] its strength.  Not solvable: every copy is `outputImage` itself and
+    // `strengths` is left untouched (Watermark.cpp:164-165)
+    std::vector<wm::Image> makeWatermarkKeys(const wm::Image& inputImage, const wm::Image& outputImage, const WatermarkKeys& keys,
+                                             std::vector<float>& strengths, MASK_TYPE maskType) const
+    {
+        const int K = keys.count();
+        std::vector<wm::Image> copies = wm::Image::stack(K, outputImage.rows(), outputImage.cols(), outputImage.channels(), outputImage.type(), device);
+        const wm_plane pin = inputImage.plane(), pbase = outputImage.plane();
+        wm_plane pout = copies[0].plane();
+        pout.frames = K;
+        pout.frame_stride = (int64_t)outputImage.elements();
+        std::vector<float> a((size_t)K, 0.0f);
+        int st = 0;
+        const int rc = wm_embed_keys(ctx, (int)maskType, &pin, &pbase, keys.handle(), &pout, a.data(), &st, WM_SLOT_SYNC);
+        if (rc < 0) fail(rc, "makeWatermarkKeys");
+        if (st != 0) return std::vector<wm::Image>((size_t)K, outputImage);
+        strengths = a;
+        return copies;
     }
     // makeWatermark, then detectWatermark on its result (the pair testForImage runs per image, main.cpp:165-220), as ONE call:
     // same results, one wait (wm.h wm_embed_detect; grey output images)

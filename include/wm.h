@@ -225,6 +225,30 @@ int wm_keys_generate(wm_keys* keys, int k, uint32_t seed);
  * _load_file / _generate / _destroy on it) until wm_sync of this slot has returned.  The library does not check this. */
 int wm_detect_keys(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* keys, float* corr_out, int* status_out, int slot);
 
+/* makeWatermark (Watermark.cpp:156-172) of every frame of `in_gray` once with EVERY key of the bank as W: one marked copy per
+ * recipient.  Copy (f, k) -- frame f marked with key k -- is frame f * nkeys + k of `out`, so out->frames must be
+ * in_gray->frames * nkeys; `out` is a WM_MEM_DEVICE plane with the channels and dtype of `base` (any pitch and frame stride; it
+ * may hold more frames than max_frames).  a_out[frames][nkeys] (row-major) and status_out[frames] (either may be NULL) are
+ * written by wm_sync.  in_gray and base take everything wm_embed takes (f32 / u8, grey or planar RGB base, a base that is
+ * in_gray itself, any pitch and width, WM_MEM_HOST, WM_MEM_SLOT_OUT for in_gray, batches up to max_frames, ME with p = 3 --
+ * WM_ERR_BAD_P otherwise, as wm_embed --, NVF with p = 3..9); the context supplies shape, p, psnr and device -- its own W is not
+ * used.  WM_ERR_BAD_ARG for a host `out`, an `out` that overlaps in_gray or base, a wrong out->frames, a bank of another shape
+ * or device, and in band mode.  Copy (f, k) and a[f][k] equal, bit for bit, what wm_embed on the batched sweeps
+ * (wm_set_fused(0)) gives with key k as W.  The image side -- the Gram sweep, the solve, the mask and max|e| -- runs once for all
+ * keys; one sweep (k_stats_keys) then sums every key's ||u|| reading the image once per group of keys and every key plane once,
+ * and one more (k_embed_keys) writes the copies.  For a grey base it also reads the image once per group and every key plane
+ * once; for a planar-RGB base it runs once per channel, so the image is read three times per group and every key plane three
+ * times.  An unsolvable frame has status WM_UNSOLVABLE: all its copies equal
+ * base bit for bit and its K strengths are left untouched (Watermark.cpp:164-165).
+ * An ENQUEUE on the slot like wm_embed (WM_SLOT_SYNC: slot 0, waits); never takes the fused single-launch kernels.  frames * nkeys
+ * results count against the slot's capacity of 4096 un-synced results; beyond it the call returns WM_ERR_BUSY.  It leaves no
+ * Gram hand-over behind and does not change what WM_MEM_SLOT_OUT names (still the slot's last wm_embed output); like every
+ * library write it ends a hand-over whose plane its copies overwrite.
+ *
+ * HAZARD.  As for wm_detect_keys: the bank must stay ALIVE and UNMODIFIED until wm_sync of this slot has returned. */
+int wm_embed_keys(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* base, const wm_keys* keys, const wm_plane* out,
+                  float* a_out, int* status_out, int slot);
+
 /* Building blocks exposed for parity tests (the reference keeps them private):
  * computeCustomMask / computePredictionErrorMask (Watermark.cpp:96-114,176-218).
  * mask_out / e_out: f32 device planes [rows,cols] (e_out may be NULL; ignored for NVF).

@@ -73,6 +73,7 @@ ABI = [
     ("wm_keys_load_file", C.c_int, [C.c_void_p, C.c_int, C.c_char_p]),
     ("wm_keys_generate", C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
     ("wm_detect_keys", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), C.c_void_p, _P(C.c_float), _P(C.c_int), C.c_int]),
+    ("wm_embed_keys", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), _P(wm_plane), C.c_void_p, _P(wm_plane), _P(C.c_float), _P(C.c_int), C.c_int]),
     ("wm_compute_mask", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), _P(wm_plane), _P(wm_plane), _P(C.c_float), _P(C.c_int), C.c_int]),
     ("wm_gram", C.c_int, [_ctx_p, _P(wm_plane), _P(C.c_double), C.c_int]),
     ("wm_band_configure", C.c_int, [_ctx_p, C.c_int, C.c_int, C.c_longlong]),
@@ -460,6 +461,33 @@ class Watermark:
             _raise(rc, self._ctx)
         return corr[0] if image.dim() == 2 else corr
 
+    def makeWatermarkKeys(self, inputImage, outputImage, keys, maskType, out=None):
+        """makeWatermark of `inputImage` with every key of the KeySet `keys` as W in one call (wm.h wm_embed_keys).  Returns
+        (copies, strengths): copies [K, ...] for one frame ([F, K, ...] for a batch [F, R, C]), copy k marked with key k, each
+        shaped like one frame of `outputImage`; strengths a float32 numpy array [K] ([F, K]), NaN for every key of an unsolvable
+        frame (whose copies equal outputImage).  `out`, if given, is a tensor of the copies' shape on the GPU."""
+        import torch
+        rgb = outputImage.dim() - inputImage.dim() == 1
+        ch = 3 if rgb else 1
+        pin = plane_of(inputImage, 1)
+        pbase = plane_of(outputImage, ch)
+        frames, K = pin.frames, keys.count
+        batched = inputImage.dim() == 3
+        per = tuple(outputImage.shape[1:] if batched else outputImage.shape)
+        shape = ((frames,) if batched else ()) + (K,) + per
+        if out is None:
+            out = torch.empty(shape, dtype=outputImage.dtype, device=outputImage.device)
+        elif tuple(out.shape) != shape or out.dtype != outputImage.dtype:
+            raise RuntimeError(f"out must be {outputImage.dtype} of shape {shape}, got {out.dtype} {tuple(out.shape)}")
+        pout = plane_of(out.view((frames * K,) + per), ch)
+        a = np.full((frames, K), np.nan, np.float32)
+        torch.cuda.current_stream().synchronize()
+        rc = lib().wm_embed_keys(self._ctx, int(maskType), C.byref(pin), C.byref(pbase), keys.handle, C.byref(pout),
+                                 a.ctypes.data_as(_P(C.c_float)), None, WM_SLOT_SYNC)
+        if rc < 0:
+            _raise(rc, self._ctx)
+        return out, (a if batched else a[0])
+
     def makeAndDetect(self, inputImage, outputImage, maskType, out=None):
         """makeWatermark followed by detectWatermark on its result (testForImage's pair, main.cpp:165-220) as one call
         (wm.h wm_embed_detect; grey output).  Returns (watermarked, strength or None, correlation)."""
@@ -521,6 +549,31 @@ class Watermark:
             status_out = status_out.ctypes.data_as(_P(C.c_int))
         rc = lib().wm_detect_keys(self._ctx, int(maskType), C.byref(pimg), keys.handle if isinstance(keys, KeySet) else keys,
                                   corr_out, status_out, slot)
+        if rc < 0:
+            _raise(rc, self._ctx)
+
+    def embed_keys_async(self, inputImage, outputImage, out, keys, maskType, slot, a_out=None, status_out=None):
+        """wm_embed_keys enqueued on `slot`: `out` holds frames * K copies (a tensor [frames * K, ...] or a wm_plane; copy (f, k) is
+        frame f * K + k); a_out (frames * K floats) and status_out (frames ints) -- ctypes arrays or C-contiguous numpy arrays, may
+        be None -- are written by sync(slot); `keys` must stay alive and unmodified until then.  With a wm_plane inputImage,
+        outputImage is a wm_plane as well (its channels cannot be told from a tensor's rank then)"""
+        if isinstance(outputImage, wm_plane):
+            ch = outputImage.channels
+        elif isinstance(inputImage, wm_plane):
+            raise RuntimeError("embed_keys_async: with a wm_plane inputImage, pass outputImage as a wm_plane too")
+        else:
+            ch = 3 if outputImage.dim() - inputImage.dim() == 1 else 1
+        pin = self._as_plane(inputImage, 1)
+        pbase = self._as_plane(outputImage, ch)
+        pout = self._as_plane(out, ch)
+        if isinstance(a_out, np.ndarray):
+            assert a_out.dtype == np.float32 and a_out.flags.c_contiguous
+            a_out = a_out.ctypes.data_as(_P(C.c_float))
+        if isinstance(status_out, np.ndarray):
+            assert status_out.dtype == np.int32 and status_out.flags.c_contiguous
+            status_out = status_out.ctypes.data_as(_P(C.c_int))
+        rc = lib().wm_embed_keys(self._ctx, int(maskType), C.byref(pin), C.byref(pbase), keys.handle if isinstance(keys, KeySet) else keys,
+                                 C.byref(pout), a_out, status_out, slot)
         if rc < 0:
             _raise(rc, self._ctx)
 

@@ -39,9 +39,10 @@ constexpr int TARGET_WAVES_NVF = 2048;
 // (the checked hand-over of wm_detect: its k_gram_ho launch and the predicated redo launches behind it are counted apart from
 // the opt-in hand-over's k_gram_ho and from the Gram sweeps)
 enum KernelId { K_GRAM = 0, K_ME_STATS, K_NVF_STATS, K_EMBED, K_DETECT, K_MASK, K_FUSED_EMBED, K_FUSED_DETECT, K_GRAM_HO, K_FUSED_PAIR, K_DETECT_KEYS,
-                K_GRAM_HO_CHECKED, K_GRAM_REDO, K_DETECT_REDO, K_COUNT };
+                K_GRAM_HO_CHECKED, K_GRAM_REDO, K_DETECT_REDO, K_STATS_KEYS, K_EMBED_KEYS_FOLD, K_EMBED_KEYS, K_COUNT };
 const char* const kKernelNames[K_COUNT] = {"k_gram", "k_me_stats", "k_nvf_stats", "k_embed", "k_detect", "k_mask", "k_fused_embed", "k_fused_detect", "k_gram_ho", "k_fused_pair",
-                                           "k_detect_keys", "k_gram_ho_checked", "k_gram_redo", "k_detect_redo"};
+                                           "k_detect_keys", "k_gram_ho_checked", "k_gram_redo", "k_detect_redo", "k_stats_keys",
+                                           "k_embed_keys_fold", "k_embed_keys"};
 
 // fused single-frame launches use every CU and wait for each other inside the launch: two of them in flight on one device
 // could each hold a part of the CUs and starve the other (their spins are bounded, so that would be a slow fallback, not a
@@ -87,7 +88,7 @@ struct Pending {
     int* status_out;
     float* coef_out;  // host destination for 8*frames coefficients (mask-only ops)
     int coef_off;
-    int nkeys = 0;    // wm_detect_keys: frames * nkeys records, value_out [frames][nkeys], status_out [frames]
+    int nkeys = 0;    // wm_detect_keys / wm_embed_keys: frames * nkeys records, value_out [frames][nkeys], status_out [frames]
 };
 
 struct Slot {
@@ -148,6 +149,8 @@ struct Slot {
     void* st_out = nullptr; size_t st_out_bytes = 0;
     // wm_detect_keys: per-(frame, key) partial records of k_detect_keys (grown on demand)
     void* keys_part = nullptr; size_t keys_part_bytes = 0;
+    // wm_embed_keys: per-(frame, key) stats records and strengths of k_stats_keys (grown on demand)
+    void* ekeys_part = nullptr; size_t ekeys_part_bytes = 0;
 };
 
 struct ProfRec { int kid; hipEvent_t a, b; bool first; };  // first: the sweep's first launch (counts the call)
@@ -342,7 +345,7 @@ void free_slot(Slot& s)
     if (s.h_res) (void)hipHostFree(s.h_res);
     if (s.h_coefres) (void)hipHostFree(s.h_coefres);
     (void)hipFree(s.st_in); (void)hipFree(s.st_base); (void)hipFree(s.st_out); (void)hipFree(s.fz_block); (void)hipFree(s.d_ho); (void)hipFree(s.d_hoseam);
-    (void)hipFree(s.d_hodig); (void)hipFree(s.keys_part);
+    (void)hipFree(s.d_hodig); (void)hipFree(s.keys_part); (void)hipFree(s.ekeys_part);
     s = Slot();
 }
 
@@ -675,17 +678,17 @@ bool planes_overlap(const wm_plane* a, const wm_plane* b)
 }
 
 // the same question for RESOLVED planes (what the kernels will address: a WM_MEM_SLOT_OUT input is the slot's last output,
-// host planes are their staging buffers)
-bool descs_overlap(const PlaneDesc& a, const PlaneDesc& b, int rows, int cols, int frames)
+// host planes are their staging buffers); frames_b > 0: `b` has that many frames (wm_embed_keys' K copies per input frame)
+bool descs_overlap(const PlaneDesc& a, const PlaneDesc& b, int rows, int cols, int frames, int frames_b = 0)
 {
-    auto extent = [&](const PlaneDesc& d) {
+    auto extent = [&](const PlaneDesc& d, int f) {
         size_t n = (size_t)(rows - 1) * d.pitch + cols;
         if (d.channels > 1) n += (size_t)(d.channels - 1) * d.cstride;
-        if (frames > 1) n += (size_t)(frames - 1) * d.fstride;
+        if (f > 1) n += (size_t)(f - 1) * d.fstride;
         return n * (d.dtype == WM_F32 ? 4 : 1);
     };
-    const char* a0 = (const char*)a.p; const char* a1 = a0 + extent(a);
-    const char* b0 = (const char*)b.p; const char* b1 = b0 + extent(b);
+    const char* a0 = (const char*)a.p; const char* a1 = a0 + extent(a, frames);
+    const char* b0 = (const char*)b.p; const char* b1 = b0 + extent(b, frames_b > 0 ? frames_b : frames);
     return a0 < b1 && b0 < a1;
 }
 
@@ -786,11 +789,12 @@ int deliver(Slot& s)
     int rc = WM_OK;
     for (auto& pd : s.pending) {
         if (pd.nkeys > 0) {
-            // wm_detect_keys: record f * nkeys + k; every key of a frame carries the frame's status
+            // wm_detect_keys / wm_embed_keys: record f * nkeys + k; every key of a frame carries the frame's status
             for (int f = 0; f < pd.frames; ++f) {
                 const int st = s.h_res[pd.res_off + f * pd.nkeys].status;
                 if (pd.status_out) pd.status_out[f] = st;
                 if (st != 0) rc = WM_UNSOLVABLE;
+                if (!pd.value_out || (st != 0 && pd.keep_value_when_unsolvable)) continue;
                 for (int k = 0; k < pd.nkeys; ++k) pd.value_out[f * pd.nkeys + k] = s.h_res[pd.res_off + f * pd.nkeys + k].value;
             }
             continue;
@@ -1549,6 +1553,91 @@ int wm_detect_keys(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* ke
     if ((rc = push_pending(ctx, s, frames * nkeys, corr_out, status_out, nullptr)) != WM_OK) return rc;
     s.pending.back().frames = frames;
     s.pending.back().nkeys = nkeys;
+    return sync_after ? do_sync(ctx, s) : WM_OK;
+}
+
+// makeWatermark of every frame with every key of the bank: wm_embed's input handling, wm_detect_keys' bank and result handling
+int wm_embed_keys(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* base, const wm_keys* keys, const wm_plane* out,
+                  float* a_out, int* status_out, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    if (mask != WM_MASK_ME && mask != WM_MASK_NVF) return fail(ctx, WM_ERR_BAD_ARG, "bad mask type");
+    if (mask == WM_MASK_ME && ctx->p != 3) return fail(ctx, WM_ERR_BAD_P, "ME mask needs p == 3 (main.cpp:89)");
+    if (!keys || !out) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_keys: null keys or out");
+    if (keys->device != ctx->device || keys->rows != ctx->rows || keys->cols != ctx->cols)
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_keys: the key bank is " + std::to_string(keys->rows) + "x" + std::to_string(keys->cols) + " on device " +
+                                             std::to_string(keys->device) + ", the engine " + std::to_string(ctx->rows) + "x" + std::to_string(ctx->cols) +
+                                             " on device " + std::to_string(ctx->device));
+    if (ctx->band_hi > 0) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_keys: not in band mode");
+    Slot* sp; bool sync_after;
+    int rc = get_slot(ctx, slot, &sp, &sync_after);
+    if (rc != WM_OK) return rc;
+    Slot& s = *sp;
+    if ((rc = check_plane(ctx, in_gray, 0, false, "in_gray", true)) != WM_OK) return rc;
+    const int frames = in_gray->frames;
+    const int nkeys = keys->nkeys;
+    if ((rc = check_plane(ctx, base, frames, true, "base")) != WM_OK) return rc;
+    // out: frames * nkeys device planes (more than max_frames is fine: the sweeps' scratch is per input frame)
+    if (out->mem != WM_MEM_DEVICE) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_keys: out must be a WM_MEM_DEVICE plane");
+    if ((long long)out->frames != (long long)frames * nkeys)
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_keys: out->frames must be in_gray->frames * nkeys = " + std::to_string((long long)frames * nkeys));
+    {
+        wm_plane one = *out;
+        one.frames = 1;
+        if ((rc = check_plane(ctx, &one, 1, true, "out")) != WM_OK) return rc;
+        if (out->frames > 1 && out->frame_stride < (int64_t)(out->channels - 1) * (out->channels > 1 ? out->channel_stride : 0) + (int64_t)out->rows * out->pitch)
+            return fail(ctx, WM_ERR_BAD_ARG, "out: frame_stride too small (frames overlap)");
+    }
+    if (out->channels != base->channels || out->dtype != base->dtype) return fail(ctx, WM_ERR_BAD_ARG, "out must have the shape and dtype of base");
+    if (in_gray->dtype != base->dtype) return fail(ctx, WM_ERR_BAD_ARG, "in_gray and base must have the same dtype (the reference converts whole frames, main.cpp:355-357)");
+    if ((long long)s.res_used + (long long)frames * nkeys > RES_CAP)
+        return fail(ctx, WM_ERR_BUSY, "too many un-synced results on this slot (frames x keys count against " + std::to_string(RES_CAP) + ")");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+
+    PlaneDesc xd, bd;
+    if ((rc = prep_input(ctx, s, in_gray, &xd)) != WM_OK) return rc;
+    const bool base_is_in = base->data == in_gray->data && base->mem == in_gray->mem && base->mem != WM_MEM_SLOT_OUT && base->channels == 1 &&
+                            base->dtype == in_gray->dtype && base->pitch == in_gray->pitch;
+    if (base->mem == WM_MEM_HOST) {
+        if (base_is_in) { bd = xd; }
+        else {
+            Staged st = staged_layout(base);
+            if ((rc = ensure(ctx, &s.st_base, &s.st_base_bytes, st.bytes)) != WM_OK) return rc;
+            if ((rc = stage_in(ctx, s, base, s.st_base, st)) != WM_OK) return rc;
+            bd = st.d; bd.p = s.st_base;
+        }
+    } else bd = desc_device(base);
+    const PlaneDesc od = desc_device(out);
+    // K outputs of one input: an in-place call has no meaning (judged on the RESOLVED planes, as wm_embed judges them)
+    if (descs_overlap(xd, od, ctx->rows, ctx->cols, frames, frames * nkeys) || descs_overlap(bd, od, ctx->rows, ctx->cols, frames, frames * nkeys))
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_keys: out overlaps in_gray or base");
+    // no hand-over of its own, and WM_MEM_SLOT_OUT keeps naming the last wm_embed output; a hand-over whose plane the copies
+    // overwrite ends here
+    invalidate_handovers(ctx, od, frames * nkeys);
+
+    LaunchGeom lg;
+    if ((rc = geom_checked(ctx, frames, mask, &lg)) != WM_OK) return rc;
+    const int rstride = std::max(ctx->max_nblk, ctx->max_nrec);
+    if ((rc = ensure(ctx, &s.ekeys_part, &s.ekeys_part_bytes, embed_keys_scratch_bytes(frames, nkeys, rstride))) != WM_OK) return rc;
+    const int aligned_w = fits_32bit(ctx->rows, ctx->cols, WM_F32) ? 1 : 0  /* (W is a dense f32 plane: 4-byte aligned rows suffice, vec_ok) */;
+    const long long kstride = (long long)ctx->rows * ctx->cols;
+    const int pad = ctx->p / 2;
+    OpResult* res = s.d_res + s.res_used;
+    const int* status = mask == WM_MASK_ME ? s.d_status : nullptr;
+    // the image side is wm_embed's: the Gram sweep and solve (ME)
+    if (mask == WM_MASK_ME) { ProfScope ps(ctx, K_GRAM, s.stream); launch_gram(s.stream, lg, frames, xd, s.d_gram, s.d_gramb, s.d_ticket, s.d_coef, s.d_status, s.d_gramtot); }
+    {
+        ProfScope ps(ctx, K_STATS_KEYS, s.stream);
+        if (launch_stats_keys(s.stream, lg, frames, mask, pad, xd, keys->d, kstride, nkeys, aligned_w, s.d_coef, status, s.ekeys_part, rstride) != 0)
+            return fail(ctx, WM_ERR_RUNTIME, "wm_embed_keys: geometry exceeds the record arrays");
+    }
+    { ProfScope ps(ctx, K_EMBED_KEYS_FOLD, s.stream); launch_embed_keys_fold(s.stream, lg, frames, mask, nkeys, status, s.ekeys_part, rstride, ctx->sF, sqrt_n(ctx), res); }
+    { ProfScope ps(ctx, K_EMBED_KEYS, s.stream); launch_embed_keys(s.stream, lg, frames, mask, pad, xd, keys->d, kstride, nkeys, aligned_w, bd, od, s.d_coef, status, s.ekeys_part, rstride); }
+    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
+    if ((rc = push_pending(ctx, s, frames * nkeys, a_out, status_out, nullptr)) != WM_OK) return rc;
+    s.pending.back().frames = frames;
+    s.pending.back().nkeys = nkeys;
+    s.pending.back().keep_value_when_unsolvable = true;  // (wm_embed's rule: an unsolvable frame leaves its K strengths untouched)
     return sync_after ? do_sync(ctx, s) : WM_OK;
 }
 

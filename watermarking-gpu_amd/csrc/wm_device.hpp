@@ -288,6 +288,17 @@ __device__ __forceinline__ int xcd_remap(int b, int nblk)
     const int x = b & 7, i = b >> 3;
     return x * per + (x < rem ? x : rem) + i;
 }
+// its inverse: the hardware block id whose logical index is L (grids with an extra axis inside the logical index: the key
+// groups of k_detect_keys / k_stats_keys / k_embed_keys)
+__device__ __forceinline__ int xcd_unmap(int L, int nblk)
+{
+    const int per = nblk >> 3, rem = nblk & 7;
+    const int big = rem * (per + 1);
+    int x, i;
+    if (L < big) { x = L / (per + 1); i = L - x * (per + 1); }
+    else { x = rem + (L - big) / per; i = L - big - (x - rem) * per; }
+    return i * 8 + x;
+}
 
 // block_id: 0 .. ntiles*frames-1 (callers subtract any leading extra blocks first)
 __device__ __forceinline__ WaveJob make_job(const Geom& g, int block_id)

@@ -206,17 +206,6 @@ __device__ __forceinline__ void keys_march(const T* __restrict__ xf, long long p
     }
 }
 
-// inverse of xcd_remap (wm_device.hpp): the hardware block id whose logical index is L
-__device__ __forceinline__ int xcd_unmap(int L, int nblk)
-{
-    const int per = nblk >> 3, rem = nblk & 7;
-    const int big = rem * (per + 1);
-    int x, i;
-    if (L < big) { x = L / (per + 1); i = L - x * (per + 1); }
-    else { x = rem + (L - big) / per; i = L - big - (x - rem) * per; }
-    return i * 8 + x;
-}
-
 // occupancy floor: the aligned 3x3 instances hold two keys' u windows and W rings besides k_detect's registers -- 4 waves per
 // SIMD for u8 planes (122 / 124 VGPRs), 3 for f32 ones (at 4 they spill 17 VGPRs); the generic instances 2 (LDS re-lay, halo
 // predictions of their own)

@@ -205,6 +205,20 @@ int launch_detect_keys(hipStream_t s, const LaunchGeom& lg, int frames, int mask
                        const float* Wbank, long long kstride, int nkeys, int aligned_w, const float* coef, const int* status,
                        double* part, int rstride, OpResult* res);
 int detect_keys_group(void);  // keys per group of k_detect_keys (compile-time KG)
+// one image embedded with every key of a bank (wm_embed_keys, wm_k_embed_keys.hip).  The image side is wm_embed's (launch_gram:
+// coef / status); then k_stats_keys (k_me_stats' / k_nvf_stats' sweep for every key, key groups as a grid axis), one fold block
+// per (frame, key) into res[frame * nkeys + key] and the scalars k_embed_keys reads, and k_embed_keys (k_embed's sweep for every
+// key: copy (frame, key) is frame frame * nkeys + key of `out`).  scratch: embed_keys_scratch_bytes of device memory, the same
+// for the three launches.  launch_stats_keys returns -1 when the sweep's records exceed rstride (nothing is launched)
+size_t embed_keys_scratch_bytes(int frames, int nkeys, int rstride);
+int launch_stats_keys(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* Wbank,
+                      long long kstride, int nkeys, int aligned_w, const float* coef, const int* status, void* scratch, int rstride);
+void launch_embed_keys_fold(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int nkeys, const int* status, void* scratch,
+                            int rstride, float sF, double sqrt_n, OpResult* res);
+void launch_embed_keys(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* Wbank,
+                       long long kstride, int nkeys, int aligned_w, const PlaneDesc& base, const PlaneDesc& out, const float* coef,
+                       const int* status, void* scratch, int rstride);
+int embed_keys_group(void);  // keys per group of k_stats_keys / k_embed_keys (compile-time EKG)
 // band mode: solve the 8x8 system from all-reduced Gram totals [frames][44]; writes coef / status like k_gram's tail
 void launch_solve_totals(hipStream_t s, int frames, const double* totals, float* coef, int* status);
 // band mode, device-resident exchange (wm_band_*_dev): glue kernels between the sweeps and the caller's collectives
