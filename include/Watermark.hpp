@@ -218,6 +218,7 @@ public:
         const int rc = wm_embed(ctx, (int)maskType, &pin, &pbase, &pout, &a, &st, WM_SLOT_SYNC);
         if (rc < 0) fail(rc, "makeWatermark");
         if (st != 0) return outputImage;  // not solvable: output image without modification, strength untouched
+        // ||m W|| = 0 (integer-flat image under NVF, zero W): strength +inf, out == outputImage bit for bit (wm.h wm_embed)
         watermarkStrength = a;
         return out;
     }

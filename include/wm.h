@@ -157,7 +157,11 @@ int wm_set_rows_per_segment(wm_ctx* ctx, int rows_per_segment);
  * in_gray: the mask source ([rows,cols], 1 channel); base: what the watermark is added to (1 or 3
  * channels, same rows/cols/dtype family); out: same shape as base, may alias base.  If out also overlaps
  * in_gray (in-place video frames, main.cpp:356,380) the library snapshots in_gray first (one extra copy).
- * a_out[frames], status_out[frames] (either may be NULL) are written by wm_sync. */
+ * a_out[frames], status_out[frames] (either may be NULL) are written by wm_sync.
+ * Zero-energy frames: when u = m W vanishes (an integer-flat frame under NVF, a zero W), ||u|| = 0 and the strength is
+ * a = sF / 0 = +inf, reported as such with status WM_OK; the watermark term is then taken as 0, so out == base bit for bit
+ * (the reference's result is undefined there: af::clamp of NaN, Watermark.cpp:170-171).  wm_detect with a zero W scores
+ * 0 / 0 = NaN with status WM_OK. */
 int wm_embed(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* base, const wm_plane* out, float* a_out,
              int* status_out, int slot);
 /* Watermark::detectWatermark(watermarkedImage, maskType)  (Watermark.cpp:234-250).
@@ -239,7 +243,9 @@ int wm_detect_keys(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* ke
  * and one more (k_embed_keys) writes the copies.  For a grey base it also reads the image once per group and every key plane
  * once; for a planar-RGB base it runs once per channel, so the image is read three times per group and every key plane three
  * times.  An unsolvable frame has status WM_UNSOLVABLE: all its copies equal
- * base bit for bit and its K strengths are left untouched (Watermark.cpp:164-165).
+ * base bit for bit and its K strengths are left untouched (Watermark.cpp:164-165).  A zero key (a bank's planes start at
+ * zero) follows wm_embed's zero-energy rule on its own: its copies equal base bit for bit, its strength is +inf, and the
+ * other keys' copies are unaffected; wm_detect_keys scores it NaN.
  * An ENQUEUE on the slot like wm_embed (WM_SLOT_SYNC: slot 0, waits); never takes the fused single-launch kernels.  frames * nkeys
  * results count against the slot's capacity of 4096 un-synced results; beyond it the call returns WM_ERR_BUSY.  It leaves no
  * Gram hand-over behind and does not change what WM_MEM_SLOT_OUT names (still the slot's last wm_embed output); like every

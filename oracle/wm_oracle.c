@@ -474,7 +474,7 @@ static double dot_rows(const float* a, const float* b, int rows, int cols)
  * out: same shape as base.  out may alias base.  On WMO_UNSOLVABLE out = base bit-exact and
  * *a is left untouched (Watermark.cpp:164-165).
  * u = mask * W; a = sF / (float)(norm(u) / sqrt(N)); out = clamp(base + u * a, 0, 255) with
- * the multiply-add fused (pinned choice, see header).
+ * the multiply-add fused (pinned choice, see header).  a = +inf (norm(u) = 0): out = base, see below.
  */
 int wmo_embed(const float* gray, const float* base, int channels, const float* W, int rows, int cols, int p,
               float psnr, int mask, float* out, float* a_out, float* mask_out, const wmo_opts* opt)
@@ -503,12 +503,16 @@ int wmo_embed(const float* gray, const float* base, int channels, const float* W
     const double nrm = norm2_rows(m, rows, cols);
     const float a = wmo_strength_factor(psnr) / (float)(nrm / sqrt((double)n));
     if (a_out) *a_out = a;
+    /* ||u|| = 0 (an integer-flat frame under NVF, a zero W): a = sF / 0 = +inf and u * a = 0 * inf = NaN.  The reference's
+     * result is undefined there (af::clamp of NaN, Watermark.cpp:170-171).  The build's rule: a stays +inf as reported, the
+     * watermark term is taken as 0, so out = clamp(base) = base. */
+    const float aw = isinf(a) ? 0.0f : a;
     for (int ch = 0; ch < channels; ch++) {
         const float* b = base + (size_t)ch * n;
         float* o = out + (size_t)ch * n;
 #pragma omp parallel for schedule(static)
         for (size_t i = 0; i < n; i++) {
-            float y = fmaf(m[i], a, b[i]);
+            float y = fmaf(m[i], aw, b[i]);
             y = y < 0.0f ? 0.0f : y;
             y = y > 255.0f ? 255.0f : y;
             o[i] = y;

@@ -77,8 +77,11 @@ def embed(gray, base, W, p=3, psnr=40.0, mask="ME"):
         m = nvf_mask(gray, p)
     u = (m * W.astype(np.float32)).astype(np.float32)
     nrm = np.sqrt(np.sum(u.astype(np.float64) ** 2))
-    a = np.float32(strength_factor(psnr) / np.float32(nrm / np.sqrt(float(gray.size))))
-    y = (u.astype(np.float64) * np.float64(a) + base.astype(np.float64)).astype(np.float32)
+    with np.errstate(divide="ignore"):  # ||u|| = 0: a = +inf
+        a = np.float32(strength_factor(psnr) / np.float32(nrm / np.sqrt(float(gray.size))))
+    # ||u|| = 0 gives a = +inf: the watermark term is taken as 0 (y = base), the strength reported stays +inf
+    aw = np.float64(0.0) if np.isinf(a) else np.float64(a)
+    y = (u.astype(np.float64) * aw + base.astype(np.float64)).astype(np.float32)
     return np.clip(y, 0, 255).astype(np.float32), float(a)
 
 

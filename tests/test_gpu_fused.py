@@ -464,10 +464,11 @@ def test_one_call_pair_equals_the_two_calls(wm, tc, shape, mask, dtype, one_laun
         cb = ef.detectWatermark(yb, mk)
         y1, a1b, c1b = ef.makeAndDetect(xd, base, mk)
         assert a1b == ab and c1b == cb and torch.equal(y1, yb)
-        if mask == "ME":
-            flat = torch.full_like(xd, 7)
-            yf_, af_, cf_ = ef.makeAndDetect(flat, base, mk)
-            assert af_ is None and torch.equal(yf_, base) and cf_ == ef.detectWatermark(base, mk)
+        # a flat frame: unsolvable under ME; under NVF its mask is 0, so ||u|| = 0 and a = +inf with y == base (wm.h wm_embed)
+        flat = torch.full_like(xd, 7)
+        yf_, af_, cf_ = ef.makeAndDetect(flat, base, mk)
+        assert (af_ is None) if mask == "ME" else (af_ == float("inf"))
+        assert torch.equal(yf_, base) and cf_ == ef.detectWatermark(base, mk)
         y1, a1, c1 = ef.makeAndDetect(xd, xd, mk)
     if dtype == "f32" and R * Cc <= 1080 * 1920:
         so, yo, ao = O.embed(x, x, W, mask=omk)

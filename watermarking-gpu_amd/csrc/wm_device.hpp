@@ -141,6 +141,11 @@ __device__ __forceinline__ float div_by(float a, float b, float rb)
     return fmaf(r, rb, q0);
 }
 
+// The strength as y = clamp(base + a u) consumes it.  ||u|| = 0 (u = m W vanishes: an integer-flat frame under NVF, a zero
+// W or bank key) gives a = sF / 0 = +inf, and fmaf(0, inf, b) = NaN, which fminf/fmaxf would turn into 0 (a black frame).
+// The watermark term is then taken as 0, so y = base; the strength reported stays +inf.  Per frame, not per pixel.
+__device__ __forceinline__ float applied_strength(float a) { return a == __builtin_huge_valf() ? 0.0f : a; }
+
 // n / d for a finite |d| well inside the f32 range: the arithmetic of the IEEE division sequence the compiler emits
 // (reciprocal, one refinement, quotient, two residual corrections) without its range scaling and special-case
 // fix-up -- 8 operations instead of 11, the same correctly rounded quotient

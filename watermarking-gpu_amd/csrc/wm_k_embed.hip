@@ -473,7 +473,7 @@ __global__ __launch_bounds__(BLOCK, HO ? WM_HO_BLOCKS : 1) void k_embed(const TX
 #pragma unroll
         for (int k = 0; k < 8; ++k) c[k] = coef[frame * 8 + k];
     }
-    const float a = scal[frame].a;
+    const float a = applied_strength(scal[frame].a);
     const float maxe = scal[frame].maxe;
     const TX* xf = x + (long long)frame * fstride;
     // hand-over: an unsolvable frame runs the march too (y = base, selected per row) -- its lag sums are the detector's

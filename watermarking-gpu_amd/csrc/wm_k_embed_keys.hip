@@ -409,7 +409,7 @@ __global__ __launch_bounds__(BLOCK) void k_embed_keys(const T* __restrict__ x, l
 #pragma unroll
     for (int q = 0; q < EKG; ++q) {
         Wk[q] = ka.W + (long long)kq[q] * ka.kstride;
-        a[q] = ka.scal[(long long)frame * ka.nkeys + kq[q]].a;
+        a[q] = applied_strength(ka.scal[(long long)frame * ka.nkeys + kq[q]].a);  // (per key: a zero key leaves its copy = base)
     }
     const float maxe = ka.scal[(long long)frame * ka.nkeys + k0].maxe;  // (the same for every key of the frame)
     const T* xf = x + (long long)frame * fstride;

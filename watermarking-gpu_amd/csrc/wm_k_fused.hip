@@ -928,6 +928,7 @@ __device__ __forceinline__ bool fused_embed_body(const T* __restrict__ x, long l
     if (!fetch_granules(a.gran + 16, 2, a.epoch, vals, L.flags + 1)) return false;
     FSTAMP(a, 6);
     const float sa = __uint_as_float(vals[0]);
+    const float ay = applied_strength(sa);  // (the strength reported stays sa)
     const float maxe = __uint_as_float(vals[1]);
     const float inv_maxe = 1.0f / maxe;
     // ---- y = clamp(base + a * m * W, 0, 255)   (Watermark.cpp:169-171)
@@ -946,10 +947,10 @@ __device__ __forceinline__ bool fused_embed_body(const T* __restrict__ x, long l
                 u[k] = mk * f4get(w[i], k);
             }
             float4 y;
-            y.x = fminf(fmaxf(fmaf(u[0], sa, b.x), 0.0f), 255.0f);
-            y.y = fminf(fmaxf(fmaf(u[1], sa, b.y), 0.0f), 255.0f);
-            y.z = fminf(fmaxf(fmaf(u[2], sa, b.z), 0.0f), 255.0f);
-            y.w = fminf(fmaxf(fmaf(u[3], sa, b.w), 0.0f), 255.0f);
+            y.x = fminf(fmaxf(fmaf(u[0], ay, b.x), 0.0f), 255.0f);
+            y.y = fminf(fmaxf(fmaf(u[1], ay, b.y), 0.0f), 255.0f);
+            y.z = fminf(fmaxf(fmaf(u[2], ay, b.z), 0.0f), 255.0f);
+            y.w = fminf(fmaxf(fmaf(u[3], ay, b.w), 0.0f), 255.0f);
             if (j.own && i < j.nv) store4_through<TB>(optr + (long long)ch * out.cstride + (long long)(j.rs + i) * out.pitch + j.c0, y);
             if constexpr (PAIR) {
                 // (the row's base was read above; every lane -- duplicate lanes hold the same pixels -- keeps its y in the tile)
