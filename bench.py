@@ -12,13 +12,17 @@ before the timed region.  Workload at N=1: BASELINE.json configs[2] (3840x2160, 
 Frames are independent units, so N GPUs shard the stream frame-parallel (weak scaling: every rank gets
 its own batch); the only collective is the RCCL gather of the per-frame detector scores (4 B/frame).
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run does what the headline figure needs and nothing else: set up, warm up, time the K
+steps, write --dump-outputs, print the contract fields with the run's record (config, ranks, placement, path bytes).  Every other
+measurement or check takes runs of its own and waits behind --full, which adds to the same line
   roofline     : dominant kernel, algorithmic bytes per launch / average launch duration measured with
                  hipEvents on the launch stream (wm_prof_*), against the 8 TB/s HBM peak
   kernels      : the same figure for every kernel of the path
   cpu_baseline : the CPU oracle (oracle/wm_oracle.c, kind "port") timed on this box's host cores on a
                  bounded sample of the same frames (rank 0, N=1 only)
   parity       : GPU vs oracle on those sample frames (max |d corr|, max rel |d a|)
+and the sustained repeat of the timed loop, the Gram hand-over leg, the memory yardstick, the video-stream leg, the
+one-image-per-call leg and the record of the box (the --no-* options drop single legs of a --full run).
 
 --dump-outputs DIR writes the outputs of the last timed step as .npy files (see dump_outputs) so that two builds can be
 compared output for output: the inputs depend on the arguments only.
@@ -446,11 +450,14 @@ def main():
                     "configs[1] / [4]'s other mask: four sweeps per frame instead of five)")
     ap.add_argument("--frames-per-slot", type=int, default=16)
     ap.add_argument("--slots", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-single-call", action="store_true", help="skip the one-image-per-call leg (wm_single)")
-    ap.add_argument("--no-stream", action="store_true", help="skip the video-stream leg (BASELINE.json configs[3])")
-    ap.add_argument("--no-slot-out", action="store_true", help="skip the Gram hand-over leg (path_slot_out)")
-    ap.add_argument("--no-membench", action="store_true", help="skip the pure store / copy / read yardstick (membench)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run every other leg (per-kernel durations and roofline, "
+                    "sustained repeat, Gram hand-over, memory yardstick, video stream, one image per call, CPU baseline and parity) and "
+                    "add their figures to the line; off by default: a plain run measures the headline figure only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle's baseline and the parity check")
+    ap.add_argument("--no-single-call", action="store_true", help="with --full: skip the one-image-per-call leg (wm_single)")
+    ap.add_argument("--no-stream", action="store_true", help="with --full: skip the video-stream leg (BASELINE.json configs[3])")
+    ap.add_argument("--no-slot-out", action="store_true", help="with --full: skip the Gram hand-over leg (path_slot_out)")
+    ap.add_argument("--no-membench", action="store_true", help="with --full: skip the pure store / copy / read yardstick (membench)")
     ap.add_argument("--stream-batch", type=int, default=8, help="frames per call of the stream leg")
     ap.add_argument("--stream-slots", type=int, default=4, help="slots (calls in flight) of the stream leg")
     ap.add_argument("--stream-frames", type=int, default=512, help="distinct u8 Y planes in the stream leg's ring, per NODE (shared out over the ranks)")
@@ -615,6 +622,69 @@ def main():
     if args.dump_outputs is not None and rank == 0:
         dump_outputs(args.dump_outputs, np, torch, ys, a_out, corr_out, F)
 
+    placements = [placement]
+    if world > 1 or force_dist:
+        # every rank's record as a fixed-size byte tensor through the same collective the rates use (all_gather_into_tensor on
+        # the communicator's device): nothing here that the score gather has not exercised already
+        PLEN = 1024
+        raw = json.dumps(placement).encode()[:PLEN]
+        buf = torch.zeros(PLEN, dtype=torch.uint8)
+        buf[:len(raw)] = torch.tensor(list(raw), dtype=torch.uint8)
+        every_b = torch.empty(world * PLEN, dtype=torch.uint8, device=coll_dev)
+        dist.all_gather_into_tensor(every_b, buf.to(coll_dev))
+        placements = []
+        for r in range(world):
+            chunk = bytes(every_b[r * PLEN:(r + 1) * PLEN].cpu().tolist()).rstrip(b"\0")
+            try:
+                placements.append(json.loads(chunk.decode()))
+            except Exception:
+                placements.append({"numa_node": None, "note": "record of this rank did not fit / parse"})
+    # whole metric frame: embed-ME 3 sweeps {x};{x,W};{x,W->y} + detect-ME 2 sweeps {y};{y,W}
+    # (NVF: no Gram sweep on the embed side -- embed 2 sweeps {x,W};{x,W->y} + detect 2 sweeps {y};{y,W}: SURVEY.md 8d)
+    nsweep_x = 3 if args.mask == "ME" else 2  # sweeps of the embed
+    frame_bytes = (((es) if args.mask == "ME" else 0) + (es + 4) + (es + 4 + es) + (es) + (es + 4)) * N
+    path_gbs = fps / world * frame_bytes / 1e9
+    # bytes that have to come from / go to HBM per frame: W is ONE plane shared by the F frames of a launch (the block
+    # order lets L2 serve the other F-1 uses), so it counts 1/F per sweep that reads it
+    frame_bytes_hbm = ((6 if args.mask == "ME" else 5) * es + 3 * 4.0 / F) * N
+    path_hbm_gbs = fps / world * frame_bytes_hbm / 1e9
+
+    out = {
+        "metric": f"frames/sec embed+detect ({args.mask} mask) at {Cc}x{R}",
+        "value": round(fps, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(1e3 * dt / args.steps, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": args.dtype, "data": "synthetic",
+        "config": {"workload": f"{Cc}x{R} {args.dtype} luminance frames, {args.mask} mask p=3 psnr=40, makeWatermark+detectWatermark per frame, "
+                               f"frames resident in HBM" + (" (BASELINE.json configs[2])" if (R, Cc, args.mask, args.dtype) == (2160, 3840, "ME", "f32") else ""),
+                   "frames_per_step_per_gpu": B, "slots": S, "frames_per_launch": F, "parallelism": f"frame-parallel x{world}"},
+        # multi-GPU record: ranks the communicator counted (all-reduce of ones), every rank's own rate over the timed steps
+        "ranks_seen": ranks_seen, "backend": (backend if (world > 1 or force_dist) else None),
+        "per_rank_frames_per_s": [round(v, 1) for v in per_rank_fps],
+        # host placement of every rank (NUMA node of its GPU, the CPUs it pinned itself to before allocating anything pinned;
+        # watermarking-gpu_amd/placement.py).  A one-rank run is described, not pinned
+        "placement": placements,
+        "path": {"hbm_bytes_per_frame": int(frame_bytes_hbm), "achieved_GBs_per_gpu": round(path_hbm_gbs, 1),
+                 "frac_of_hbm_peak": round(path_hbm_gbs / HBM_PEAK_GBS, 4),
+                 "definition": f"{nsweep_x + 2} sweeps per frame, every frame plane once per sweep, W once per launch of F frames",
+                 # SURVEY.md 8d's unit counts W in every sweep of every frame (36 N bytes at f32): L2 serves most of it,
+                 # so this figure can exceed what HBM delivers and is NOT a roofline fraction
+                 "survey_unit": {"bytes_per_frame": frame_bytes, "GBs_per_gpu": round(path_gbs, 1)},
+                 "x_realtime_30fps": round(fps / 30.0, 1),
+                 # SURVEY.md 8d: the compulsory floor, every plane once per op (embed {x,W->y}, detect {y,W}); only a
+                 # persistent single-launch design with grid barriers could approach it
+                 "compulsory_bytes_per_frame": ((es + 4 + es) + (es + 4)) * N,
+                 "frac_of_hbm_peak_compulsory": round(fps / world * ((es + 4 + es) + (es + 4)) * N / 1e9 / HBM_PEAK_GBS, 4)},
+    }
+    # ---- a plain run ends here: set up, warmed up, timed, dumped, one line.  Everything below measures or checks something
+    # else than the headline figure and runs with --full only
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        eng.close()
+        if world > 1 or force_dist:
+            dist.destroy_process_group()
+        return 0
+
     # ---- per-kernel durations with hipEvents on the launch stream: a separate pass, every launch on slot 0's stream and
     # bracketed by its own pair of events (with several slots in flight kernels of different streams overlap and an event pair
     # would time the overlap, not the kernel).  The steps are enqueued back to back and synchronised ONCE at the end: with a
@@ -777,23 +847,6 @@ def main():
         if "k_embed" in kernels and membench["store"]["GBs"]:
             # k_embed's algorithmic bytes against what the same box does with a pure copy of as many bytes: the kernel's share
             membench["k_embed_vs_copy"] = round(kernels["k_embed"]["achieved_GBs"] / membench["copy"]["GBs"], 4) if membench["copy"]["GBs"] else None
-    placements = [placement]
-    if world > 1 or force_dist:
-        # every rank's record as a fixed-size byte tensor through the same collective the rates use (all_gather_into_tensor on
-        # the communicator's device): nothing here that the score gather has not exercised already
-        PLEN = 1024
-        raw = json.dumps(placement).encode()[:PLEN]
-        buf = torch.zeros(PLEN, dtype=torch.uint8)
-        buf[:len(raw)] = torch.tensor(list(raw), dtype=torch.uint8)
-        every_b = torch.empty(world * PLEN, dtype=torch.uint8, device=coll_dev)
-        dist.all_gather_into_tensor(every_b, buf.to(coll_dev))
-        placements = []
-        for r in range(world):
-            chunk = bytes(every_b[r * PLEN:(r + 1) * PLEN].cpu().tolist()).rstrip(b"\0")
-            try:
-                placements.append(json.loads(chunk.decode()))
-            except Exception:
-                placements.append({"numa_node": None, "note": "record of this rank did not fit / parse"})
     dom = max((k for k in kernels if "achieved_GBs" in kernels[k]), key=lambda k: kernels[k]["avg_us"] * kernels[k]["launches"])
     # HBM bytes per launch from the PMC passes (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in runs of their own,
     # tools/run_pmc.sh): a RECORDED figure read from profiles/pmc_traffic.json, not a measurement of this run
@@ -821,46 +874,12 @@ def main():
                "k_detect": "HBM (reads y; W from L2); vector issue close behind (~89 instructions per 4-pixel row and lane)",
                "k_nvf_stats": "vector issue beside HBM (the pinned NVF arithmetic: 17 sums + 3 correctly rounded quotients per pixel)"}
     roofline["limiter"] = LIMITER.get(dom, "HBM")
-    # whole metric frame: embed-ME 3 sweeps {x};{x,W};{x,W->y} + detect-ME 2 sweeps {y};{y,W}
-    # (NVF: no Gram sweep on the embed side -- embed 2 sweeps {x,W};{x,W->y} + detect 2 sweeps {y};{y,W}: SURVEY.md 8d)
-    nsweep_x = 3 if args.mask == "ME" else 2  # sweeps of the embed
-    frame_bytes = (((es) if args.mask == "ME" else 0) + (es + 4) + (es + 4 + es) + (es) + (es + 4)) * N
-    path_gbs = fps / world * frame_bytes / 1e9
-    # bytes that have to come from / go to HBM per frame: W is ONE plane shared by the F frames of a launch (the block
-    # order lets L2 serve the other F-1 uses), so it counts 1/F per sweep that reads it
-    frame_bytes_hbm = ((6 if args.mask == "ME" else 5) * es + 3 * 4.0 / F) * N
-    path_hbm_gbs = fps / world * frame_bytes_hbm / 1e9
-
-    out = {
-        "metric": f"frames/sec embed+detect ({args.mask} mask) at {Cc}x{R}",
-        "value": round(fps, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(1e3 * dt / args.steps, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": args.dtype, "data": "synthetic",
-        "config": {"workload": f"{Cc}x{R} {args.dtype} luminance frames, {args.mask} mask p=3 psnr=40, makeWatermark+detectWatermark per frame, "
-                               f"frames resident in HBM" + (" (BASELINE.json configs[2])" if (R, Cc, args.mask, args.dtype) == (2160, 3840, "ME", "f32") else ""),
-                   "frames_per_step_per_gpu": B, "slots": S, "frames_per_launch": F, "parallelism": f"frame-parallel x{world}"},
-        # multi-GPU record: ranks the communicator counted (all-reduce of ones), every rank's own rate over the timed steps
-        "ranks_seen": ranks_seen, "backend": (backend if (world > 1 or force_dist) else None),
-        "per_rank_frames_per_s": [round(v, 1) for v in per_rank_fps],
-        # host placement of every rank (NUMA node of its GPU, the CPUs it pinned itself to before allocating anything pinned;
-        # watermarking-gpu_amd/placement.py).  A one-rank run is described, not pinned
-        "placement": placements,
+    out.update({
         "sustained": sustained,
         "box": box_record(pci) if rank == 0 else None,
         "membench": membench,
         "path_slot_out": slot_out,
         "roofline": roofline,
-        "path": {"hbm_bytes_per_frame": int(frame_bytes_hbm), "achieved_GBs_per_gpu": round(path_hbm_gbs, 1),
-                 "frac_of_hbm_peak": round(path_hbm_gbs / HBM_PEAK_GBS, 4),
-                 "definition": f"{nsweep_x + 2} sweeps per frame, every frame plane once per sweep, W once per launch of F frames",
-                 # SURVEY.md 8d's unit counts W in every sweep of every frame (36 N bytes at f32): L2 serves most of it,
-                 # so this figure can exceed what HBM delivers and is NOT a roofline fraction
-                 "survey_unit": {"bytes_per_frame": frame_bytes, "GBs_per_gpu": round(path_gbs, 1)},
-                 "x_realtime_30fps": round(fps / 30.0, 1),
-                 # SURVEY.md 8d: the compulsory floor, every plane once per op (embed {x,W->y}, detect {y,W}); only a
-                 # persistent single-launch design with grid barriers could approach it
-                 "compulsory_bytes_per_frame": ((es + 4 + es) + (es + 4)) * N,
-                 "frac_of_hbm_peak_compulsory": round(fps / world * ((es + 4 + es) + (es + 4)) * N / 1e9 / HBM_PEAK_GBS, 4)},
         "kernels": kernels,
         # cross-check of the per-kernel durations: the same serial steps timed on the host (enqueue of all steps -> one
         # synchronisation) against the sum of the five launches' event durations.  The events are attached to the dispatches
@@ -871,7 +890,7 @@ def main():
         "kernels_after_sustained_load": kernels_after,
         "serial_step_check": {"wall_us_per_step": round(serial_step_us, 1),
                               "sum_of_kernel_event_us": round(sum(v["avg_us"] * v["launches"] for v in kernels.values()) / prof_steps, 1)},
-    }
+    })
 
     # ---- the video-stream configuration (BASELINE.json configs[3]): every rank runs its shard of the stream
     if not args.no_stream and (R, Cc) == (2160, 3840) and args.mask == "ME":

@@ -1,5 +1,5 @@
 """The bench line's contract, checked on the committed line of the last profile run (profiles/r04_bench_n1.json is what
-`python bench.py` printed on the GPU box): the keys the driver parses, the roofline / cpu_baseline objects, and the
+a run with every leg, today `python bench.py --full`, printed on the GPU box): the keys the driver parses, the roofline / cpu_baseline objects, and the
 arithmetic that ties them together.  No GPU needed."""
 import json
 import os
@@ -145,3 +145,12 @@ def test_launcher_form_still_works_under_torchrun_env():
     """with RANK / WORLD_SIZE in the environment (the driver's torch.distributed.run form) bench.py does not spawn"""
     p = _bench("--gpus", "1", "--plumbing-only", env={"RANK": "0", "LOCAL_RANK": "0", "WORLD_SIZE": "1"})
     assert p.returncode == 0 and json.loads(p.stdout.strip().splitlines()[-1])["n_gpus"] == 1
+
+
+def test_full_is_an_accepted_option():
+    """`--full` (every leg beside the headline figure) is accepted, also where there is nothing for it to add"""
+    p = _bench("--help")
+    assert p.returncode == 0 and "--full" in p.stdout
+    p = _bench("--gpus", "1", "--plumbing-only", "--full")
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert json.loads(p.stdout.strip().splitlines()[-1])["n_gpus"] == 1

@@ -78,13 +78,13 @@ def test_rccl_world1_after_engine_load():
 
 
 def test_bench_two_ranks_without_a_launcher_on_one_gpu():
-    """`python bench.py --gpus 2` with NO launcher around it: bench.py starts the two ranks itself (before touching the GPU),
+    """`python bench.py --gpus 2 --full` with NO launcher around it: bench.py starts the two ranks itself (before touching the GPU),
     both share this box's one GPU (WM_BENCH_ALL_ON_DEVICE0, gloo instead of RCCL: two RCCL ranks cannot share a device), and
     rank 0's single JSON line comes back with n_gpus 2, both ranks counted and a rate per rank"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(WM_BENCH_ALL_ON_DEVICE0="1", WM_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--rows", "1080", "--cols", "1920",
-                        "--frames-per-slot", "4", "--slots", "2", "--sustain-seconds", "0.2"], env=env, capture_output=True, text=True, timeout=600)
+                        "--frames-per-slot", "4", "--slots", "2", "--sustain-seconds", "0.2", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-1000:] + p.stderr[-4000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, p.stdout
@@ -99,11 +99,11 @@ def test_bench_two_ranks_without_a_launcher_on_one_gpu():
 
 
 def test_bench_nvf_mask_line():
-    """`bench.py --mask NVF` (BASELINE.json configs[1] / [4] name the NVF mask): four sweeps per frame, the NVF kernels in the
+    """`bench.py --full --mask NVF` (BASELINE.json configs[1] / [4] name the NVF mask): four sweeps per frame, the NVF kernels in the
     `kernels` block with their fractions, no ME-only legs"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mask", "NVF", "--steps", "3", "--warmup", "1", "--rows", "1080", "--cols", "1920",
-                        "--frames-per-slot", "8", "--slots", "2", "--sustain-seconds", "0.2", "--cpu-seconds", "1"], env=env, capture_output=True, text=True, timeout=600)
+                        "--frames-per-slot", "8", "--slots", "2", "--sustain-seconds", "0.2", "--cpu-seconds", "1", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-1000:] + p.stderr[-4000:]
     rec = json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])
     assert "NVF mask" in rec["metric"] and "k_nvf_stats" in rec["kernels"] and "k_me_stats" not in rec["kernels"]
@@ -112,3 +112,38 @@ def test_bench_nvf_mask_line():
     assert "stream" not in rec and "single_call" not in rec
     assert rec["parity"]["max_abs_dcorr_vs_oracle"] <= 1e-5 and rec["parity"]["max_rel_da_vs_oracle"] <= 1e-4
     assert rec["path_slot_out"]["frames_per_s"] > 0
+
+
+# what only a --full run measures or checks: none of it may run, or show, in a plain one
+FULL_ONLY = ("roofline", "kernels", "kernels_after_sustained_load", "serial_step_check", "sustained", "path_slot_out", "membench", "box",
+             "stream", "single_call", "cpu_baseline", "parity")
+
+
+def test_bench_plain_run_is_the_headline_only(tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W` at the default workload: one line with the contract fields and the run's record,
+    none of the --full legs, the four --dump-outputs arrays of the last timed step, and little time outside the steps"""
+    import time
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    steps, warmup = 5, 2
+    t0 = time.perf_counter()
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    wall = time.perf_counter() - t0
+    assert p.returncode == 0, p.stdout[-1000:] + p.stderr[-4000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, p.stdout
+    rec = json.loads(lines[0])
+    assert rec["metric"] == "frames/sec embed+detect (ME mask) at 3840x2160" and rec["unit"] == "frames/s" and rec["higher_is_better"] is True
+    assert rec["dtype"] == "f32" and rec["n_gpus"] == 1 and rec["steps"] == steps and rec["warmup"] == warmup
+    fps = rec["config"]["frames_per_step_per_gpu"] / (rec["ms_per_step"] * 1e-3)
+    assert rec["value"] > 0 and abs(fps - rec["value"]) <= 2e-3 * rec["value"]
+    assert rec["ranks_seen"] == 1 and len(rec["per_rank_frames_per_s"]) == 1 and len(rec["placement"]) == 1
+    assert rec["path"]["definition"].startswith("5 sweeps")
+    assert not [k for k in FULL_ONLY if k in rec]
+    assert sorted(os.listdir(tmp_path)) == ["correlation.npy", "strength.npy", "y_frame_sum.npy", "y_sample.npy"]
+    corr = np.load(os.path.join(tmp_path, "correlation.npy"))
+    assert corr.shape == (rec["config"]["frames_per_step_per_gpu"],) and np.all((0.2 < corr) & (corr < 1.0))
+    # the budget of a plain run: 30 s outside its steps, start to exit (the dump's seeded sample of 8 Mi pixels included here)
+    outside = wall - (steps + warmup) * rec["ms_per_step"] * 1e-3
+    print(f"plain run: {wall:.1f} s start to exit, {outside:.1f} s outside its steps")
+    assert outside <= 30.0, outside

@@ -1,5 +1,5 @@
 """Turns the rocprofv3 outputs of tools/run_nvf_profiles.sh (gpurun_out/nvf/) into the committed NVF profiles:
-  profiles/<rnd>_nvf_bench_<RxC>.json       the bench line of `bench.py --mask NVF` at that size (3 slots)
+  profiles/<rnd>_nvf_bench_<RxC>.json       the bench line of `bench.py --full --mask NVF` at that size (3 slots)
   profiles/<rnd>_nvf_kernel_stats.csv       rocprofv3 --kernel-trace --stats rows of the engine's kernels, per size
   profiles/<rnd>_nvf_pmc_summary.json       per size and kernel: counter means, durations, and the derived figures DESIGN.md quotes
                                             (vector instructions per launch, ns per vector instruction and SIMD, HBM bytes)
@@ -19,7 +19,7 @@ NSIMD = 1024
 os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
 
 stats_rows, header = [], None
-summary = {"_note": "rocprofv3 --kernel-trace --pmc passes of `bench.py --mask NVF --slots 1 --steps 5 --warmup 2 ...` (tools/run_nvf_profiles.sh), one "
+summary = {"_note": "rocprofv3 --kernel-trace --pmc passes of `bench.py --full --mask NVF --slots 1 --steps 5 --warmup 2 ...` (tools/run_nvf_profiles.sh), one "
                     "counter group per run; means over the launches seen.  Derived: ns_per_valu_inst_per_simd = duration / (SQ_INSTS_VALU / 1024 SIMDs); "
                     "hbm_bytes = 2 * FETCH_SIZE + WRITE_SIZE (KiB -> bytes)."}
 traffic_path = os.path.join(ROOT, "profiles", "pmc_traffic.json")

@@ -1,4 +1,4 @@
-"""Turns the rocprofv3 outputs of one GPU session (gpurun_out/) into the committed profiles/ summaries:
+"""Turns the rocprofv3 outputs of one GPU session (tools/run_round_profiles.sh; $WM_PROFILE_OUT, default profile_out/) into the committed profiles/ summaries:
   profiles/<rnd>_kernel_stats.csv      rocprofv3 --kernel-trace --stats summary (our kernels + totals) of the serialised bench
   profiles/<rnd>_pmc_summary.json      per-kernel means of the --pmc passes
   profiles/<rnd>_single_call_*         the same for the one-image-per-call loop (fused kernels)
@@ -11,7 +11,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 rnd = sys.argv[1] if len(sys.argv) > 1 else "r03"
 key = sys.argv[2] if len(sys.argv) > 2 else "2160x3840_f32_F16"
 os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-ks = os.path.join(ROOT, "gpurun_out", "prof_stats", f"{rnd}_kernel_stats.csv")
+OUT = os.path.join(ROOT, os.environ.get("WM_PROFILE_OUT", "profile_out"))  # where run_round_profiles.sh wrote
+ks = os.path.join(OUT, "prof_stats", f"{rnd}_kernel_stats.csv")
 if os.path.exists(ks):
     rows = list(csv.reader(open(ks)))
     with open(os.path.join(ROOT, "profiles", f"{rnd}_kernel_stats.csv"), "w", newline="") as f:
@@ -25,7 +26,7 @@ if os.path.exists(ks):
 # written with non-temporal stores (the second) -- so that a bimodal average can be attributed
 import glob  # noqa: E402
 import statistics  # noqa: E402
-kt = glob.glob(os.path.join(ROOT, "gpurun_out", "prof_stats", "**", f"{rnd}_kernel_trace.csv"), recursive=True)
+kt = glob.glob(os.path.join(OUT, "prof_stats", "**", f"{rnd}_kernel_trace.csv"), recursive=True)
 if kt:
     launches = []
     for row in csv.DictReader(open(kt[0])):
@@ -54,12 +55,12 @@ if kt:
         groups.setdefault(gkey, []).append(us)
     summ = {k: {"launches": len(v), "mean_us": round(statistics.mean(v), 2), "sd_us": round(statistics.pstdev(v), 2), "min_us": round(min(v), 2),
                 "max_us": round(max(v), 2), "median_us": round(statistics.median(v), 2)} for k, v in groups.items()}
-    summ["_note"] = ("rocprofv3 --kernel-trace of `bench.py --steps 5 --warmup 2 --slots 1 --frames-per-slot 16 ...`: warm-up + timed steps (one slot: "
+    summ["_note"] = ("rocprofv3 --kernel-trace of `bench.py --full --steps 5 --warmup 2 --slots 1 --frames-per-slot 16 ...`: warm-up + timed steps (one slot: "
                      "embed and detect of a batch back to back) + the 10 hipEvent steps (every launch bracketed by events, host sync per step)")
     json.dump(summ, open(os.path.join(ROOT, "profiles", f"{rnd}_kernel_trace_summary.json"), "w"), indent=1)
     print(json.dumps(summ, indent=1)[:2000])
 # the one-image-per-call loop (fused kernels; tools/f1_trace.py: ME then NVF, embed / detect / pairs)
-ks1 = os.path.join(ROOT, "gpurun_out", "prof_stats_single", f"{rnd}_single_kernel_stats.csv")
+ks1 = os.path.join(OUT, "prof_stats_single", f"{rnd}_single_kernel_stats.csv")
 if os.path.exists(ks1):
     rows = list(csv.reader(open(ks1)))
     with open(os.path.join(ROOT, "profiles", f"{rnd}_single_call_kernel_stats.csv"), "w", newline="") as f:
@@ -68,7 +69,7 @@ if os.path.exists(ks1):
         for r in rows[1:]:
             if "wmk::" in r[0]:
                 w.writerow(r)
-pm1 = os.path.join(ROOT, "gpurun_out", "pmc_single")
+pm1 = os.path.join(OUT, "pmc_single")
 if os.path.isdir(pm1):
     out1 = os.path.join(ROOT, "profiles", f"{rnd}_single_call_pmc_summary.json")
     subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "pmc_summary.py"), pm1, out1], stdout=subprocess.DEVNULL)
@@ -88,12 +89,12 @@ if os.path.isdir(pm1):
     json.dump(d1, open(out1, "w"), indent=1)
     print(json.dumps({k: {kk: vv for kk, vv in v.items() if kk in ("hbm_bytes_per_launch", "dur_us[fetch]", "SQ_INSTS_VALU")} for k, v in d1.items()}, indent=1))
 for name in (f"bench_{rnd}.json", f"bench_{rnd}_u8.json"):
-    src = os.path.join(ROOT, "gpurun_out", name)
+    src = os.path.join(OUT, name)
     if os.path.exists(src):
         line = open(src).read().strip().splitlines()[-1]
         json.loads(line)
         open(os.path.join(ROOT, "profiles", name.replace("bench_" + rnd, rnd + "_bench_n1")), "w").write(line + "\n")
-pm = os.path.join(ROOT, "gpurun_out", "pmc")
+pm = os.path.join(OUT, "pmc")
 if os.path.isdir(pm):
     out = os.path.join(ROOT, "profiles", f"{rnd}_pmc_summary.json")
     subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "pmc_summary.py"), pm, out], stdout=subprocess.DEVNULL)

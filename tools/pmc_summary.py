@@ -1,4 +1,4 @@
-"""dev helper: per-kernel means of rocprofv3 --pmc passes (gpurun_out/pmc/*/ *_counter_collection.csv)
+"""dev helper: per-kernel means of rocprofv3 --pmc passes (tools/run_pmc.sh: <output directory>/pmc/*/ *_counter_collection.csv)
 joined with kernel durations from the same pass's kernel trace -> prints a table and writes JSON."""
 import csv
 import glob
@@ -7,7 +7,7 @@ import os
 import sys
 from collections import defaultdict
 
-root = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/pmc"
+root = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.environ.get("WM_PROFILE_OUT", "profile_out"), "pmc")
 
 
 def short_name(name):

@@ -12,7 +12,7 @@ mkdir -p gpurun_out/nvf
 for sz in $SIZES; do
     rows=${sz%%x*}; rest=${sz#*x}; cols=${rest%%x*}; F=${rest#*x}
     tag=${rows}x${cols}
-    COMMON="--mask NVF --rows $rows --cols $cols --frames-per-slot $F --no-cpu-baseline --no-stream --no-single-call"
+    COMMON="--full --mask NVF --rows $rows --cols $cols --frames-per-slot $F --no-cpu-baseline --no-stream --no-single-call"
     python3 bench.py $COMMON --slots 3 > gpurun_out/nvf/bench_${tag}.json 2> gpurun_out/nvf/bench_${tag}.err || { tail -5 gpurun_out/nvf/bench_${tag}.err; exit 1; }
     SER="$COMMON --steps 5 --warmup 2 --slots 1 --no-slot-out --no-membench --sustain-seconds 0"
     rm -rf gpurun_out/nvf/stats_${tag}
