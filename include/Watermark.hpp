@@ -241,6 +241,19 @@ public:
         if (rc < 0) fail(rc, "detectWatermarkKeys");
         return corr;
     }
+    // where does a cropped copy lie in its key?  detectWatermark of one grey image against the windows of key `k` of `keys` (planes
+    // at least as large as the image) at the offsets (oy0 + i, ox0 + j), i < ny, j < nx, in one call (wm.h wm_detect_offsets):
+    // score [i * nx + j] is what detectWatermark returns with that window as W.  The prediction filter smears the peak over the
+    // 3x3 neighbourhood of the true offset: take the argmax
+    std::vector<float> detectOffsets(const wm::Image& watermarkedImage, const WatermarkKeys& keys, int k, int oy0, int ox0, int ny, int nx,
+                                     MASK_TYPE maskType) const
+    {
+        const wm_plane pimg = watermarkedImage.plane();
+        std::vector<float> corr((size_t)(ny > 0 ? ny : 0) * (size_t)(nx > 0 ? nx : 0), 0.0f);
+        const int rc = wm_detect_offsets(ctx, (int)maskType, &pimg, keys.handle(), k, oy0, ox0, ny, nx, corr.data(), nullptr, WM_SLOT_SYNC);
+        if (rc < 0) fail(rc, "detectOffsets");
+        return corr;
+    }
     // makeWatermark of one grey image with every key of `keys` as W in one call (wm.h wm_embed_keys): copy k is what
     // makeWatermark returns with key k as W, strengths[k] its strength.  Not solvable: every copy is `outputImage` itself and
     // `strengths` is left untouched (Watermark.cpp:164-165)

@@ -229,6 +229,40 @@ int wm_keys_generate(wm_keys* keys, int k, uint32_t seed);
  * _load_file / _generate / _destroy on it) until wm_sync of this slot has returned.  The library does not check this. */
 int wm_detect_keys(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* keys, float* corr_out, int* status_out, int slot);
 
+/* ---- Crop search: one image against a rectangle of window offsets into one key ---------------------------------------------
+ * A copy that was CROPPED after it was marked no longer lines up with its key: W is white noise, so one pixel of misalignment
+ * takes the score from ~0.54 to ~0.22 (ME) and two pixels to ~0.04.  The detector is local, though: a frame marked at KR x KC and
+ * cropped to rows x cols at (oy, ox) scores against the WINDOW key[oy : oy + rows, ox : ox + cols] almost what the full frame
+ * scores against the key.  wm_detect_offsets runs that search: detectWatermark (Watermark.cpp:234-250) of every frame of `img`
+ * against the windows of key `k` of the bank at the offsets (oy0 + i, ox0 + j), i < ny, j < nx.
+ * The context supplies the image shape rows x cols, p and the device -- its own W is not used.  `keys` is a bank on the same
+ * device whose planes are KR x KC with KR >= rows and KC >= cols.  Every window must lie inside the key plane: oy0 >= 0,
+ * ox0 >= 0, ny >= 1, nx >= 1, oy0 + ny - 1 + rows <= KR, ox0 + nx - 1 + cols <= KC (wm_offsets_check is that test on its own,
+ * WM_OK or WM_ERR_BAD_ARG).  WM_ERR_BAD_ARG, before any device work is queued, for a window outside the key plane, a null ctx /
+ * img / keys / corr_out, k out of range, a bank on another device or smaller than the image, and in band mode.
+ * corr_out[frames][ny][nx] (row-major), status_out[frames] (may be NULL), both written by wm_sync.  Takes every input
+ * wm_detect_keys takes (f32 / u8, any pitch and width, WM_MEM_HOST, WM_MEM_SLOT_OUT, batches up to max_frames, ME with p = 3 --
+ * WM_ERR_BAD_P otherwise --, NVF with p = 3..9).
+ * Score (i, j) is wm_detect's on the batched sweeps with W = the window copied out -- equivalently wm_detect_keys' on a rows x cols
+ * bank that holds the window -- BIT FOR BIT: the replicate border of u = m W is taken at the window's edge (key values outside
+ * an offset's window never enter its score), and the sweep geometry is chosen from the image plane alone.  The image side runs
+ * once (wm_detect's Gram sweep, hand-over included, and solve); one sweep (k_detect_offsets) then scores groups of horizontally
+ * adjacent offsets that share one stream of key rows, so no bank of candidate windows is built or read.  An unsolvable frame
+ * has status WM_UNSOLVABLE and 0.0f at every offset; a key that is all zero scores NaN, as in wm_detect_keys.
+ * The peak is not one pixel wide: the prediction filter smears it over the 3x3 neighbourhood, so the 8 offsets around the true
+ * one score 0.1-0.25 where offsets two or more pixels away score < 0.05.
+ * An ENQUEUE on the slot like wm_detect_keys (WM_SLOT_SYNC: slot 0, waits); it may share a slot with any other call in any order.
+ * frames * ny * nx results count against the slot's capacity of 4096 un-synced results; beyond it the call returns WM_ERR_BUSY.
+ * Never takes the fused single-launch kernels.
+ *
+ * HAZARD.  As for wm_detect_keys: the kernels read the bank when the stream reaches them: the bank must stay ALIVE and UNMODIFIED
+ * (no wm_keys_set / _load_file / _generate / _destroy on it) until wm_sync of this slot has returned.  The library does not
+ * check this. */
+int wm_offsets_check(int rows, int cols, int key_rows, int key_cols, int oy0, int ox0, int ny, int nx);
+int wm_detect_offsets_group(void);  /* G: horizontally adjacent offsets that share one stream of key rows (nx < G: one each) */
+int wm_detect_offsets(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* keys, int k, int oy0, int ox0, int ny, int nx,
+                      float* corr_out, int* status_out, int slot);
+
 /* makeWatermark (Watermark.cpp:156-172) of every frame of `in_gray` once with EVERY key of the bank as W: one marked copy per
  * recipient.  Copy (f, k) -- frame f marked with key k -- is frame f * nkeys + k of `out`, so out->frames must be
  * in_gray->frames * nkeys; `out` is a WM_MEM_DEVICE plane with the channels and dtype of `base` (any pitch and frame stride; it

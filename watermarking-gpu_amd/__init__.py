@@ -74,6 +74,10 @@ ABI = [
     ("wm_keys_generate", C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
     ("wm_detect_keys", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), C.c_void_p, _P(C.c_float), _P(C.c_int), C.c_int]),
     ("wm_embed_keys", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), _P(wm_plane), C.c_void_p, _P(wm_plane), _P(C.c_float), _P(C.c_int), C.c_int]),
+    ("wm_offsets_check", C.c_int, [C.c_int] * 8),
+    ("wm_detect_offsets_group", C.c_int, []),
+    ("wm_detect_offsets", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_float), _P(C.c_int),
+                                   C.c_int]),
     ("wm_compute_mask", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), _P(wm_plane), _P(wm_plane), _P(C.c_float), _P(C.c_int), C.c_int]),
     ("wm_gram", C.c_int, [_ctx_p, _P(wm_plane), _P(C.c_double), C.c_int]),
     ("wm_band_configure", C.c_int, [_ctx_p, C.c_int, C.c_int, C.c_longlong]),
@@ -461,6 +465,23 @@ class Watermark:
             _raise(rc, self._ctx)
         return corr[0] if image.dim() == 2 else corr
 
+    def detectOffsets(self, image, keys, k, oy0, ox0, ny, nx, maskType):
+        """where does a cropped copy lie in its key?  detectWatermark of `image` against the windows
+        keys[k][oy : oy + rows, ox : ox + cols] of a KeySet whose planes are at least as large as the image, at the offsets
+        (oy0 + i, ox0 + j), i < ny, j < nx, in one call (wm.h wm_detect_offsets): a float32 numpy array [frames, ny, nx]
+        ([ny, nx] for one grey frame); 0.0 at every offset of an unsolvable frame.  The peak is smeared over the 3x3
+        neighbourhood of the true offset by the prediction filter: take the argmax"""
+        import torch
+        pimg = plane_of(image, 1)
+        frames = pimg.frames
+        corr = np.zeros((frames, max(ny, 0), max(nx, 0)), np.float32)
+        torch.cuda.current_stream().synchronize()
+        rc = lib().wm_detect_offsets(self._ctx, int(maskType), C.byref(pimg), keys.handle, k, oy0, ox0, ny, nx,
+                                     corr.ctypes.data_as(_P(C.c_float)), None, WM_SLOT_SYNC)
+        if rc < 0:
+            _raise(rc, self._ctx)
+        return corr[0] if image.dim() == 2 else corr
+
     def makeWatermarkKeys(self, inputImage, outputImage, keys, maskType, out=None):
         """makeWatermark of `inputImage` with every key of the KeySet `keys` as W in one call (wm.h wm_embed_keys).  Returns
         (copies, strengths): copies [K, ...] for one frame ([F, K, ...] for a batch [F, R, C]), copy k marked with key k, each
@@ -549,6 +570,22 @@ class Watermark:
             status_out = status_out.ctypes.data_as(_P(C.c_int))
         rc = lib().wm_detect_keys(self._ctx, int(maskType), C.byref(pimg), keys.handle if isinstance(keys, KeySet) else keys,
                                   corr_out, status_out, slot)
+        if rc < 0:
+            _raise(rc, self._ctx)
+
+    def detect_offsets_async(self, image, keys, k, oy0, ox0, ny, nx, maskType, slot, corr_out, status_out=None):
+        """wm_detect_offsets enqueued on `slot`: corr_out (frames * ny * nx floats: a ctypes array or a C-contiguous float32 numpy
+        array) and status_out (frames ints, may be None) are written by sync(slot); `keys` must stay alive and unmodified until
+        then"""
+        pimg = self._as_plane(image, 1)
+        if isinstance(corr_out, np.ndarray):
+            assert corr_out.dtype == np.float32 and corr_out.flags.c_contiguous
+            corr_out = corr_out.ctypes.data_as(_P(C.c_float))
+        if isinstance(status_out, np.ndarray):
+            assert status_out.dtype == np.int32 and status_out.flags.c_contiguous
+            status_out = status_out.ctypes.data_as(_P(C.c_int))
+        rc = lib().wm_detect_offsets(self._ctx, int(maskType), C.byref(pimg), keys.handle if isinstance(keys, KeySet) else keys,
+                                     k, oy0, ox0, ny, nx, corr_out, status_out, slot)
         if rc < 0:
             _raise(rc, self._ctx)
 

@@ -39,10 +39,10 @@ constexpr int TARGET_WAVES_NVF = 2048;
 // (the checked hand-over of wm_detect: its k_gram_ho launch and the predicated redo launches behind it are counted apart from
 // the opt-in hand-over's k_gram_ho and from the Gram sweeps)
 enum KernelId { K_GRAM = 0, K_ME_STATS, K_NVF_STATS, K_EMBED, K_DETECT, K_MASK, K_FUSED_EMBED, K_FUSED_DETECT, K_GRAM_HO, K_FUSED_PAIR, K_DETECT_KEYS,
-                K_GRAM_HO_CHECKED, K_GRAM_REDO, K_DETECT_REDO, K_STATS_KEYS, K_EMBED_KEYS_FOLD, K_EMBED_KEYS, K_COUNT };
+                K_GRAM_HO_CHECKED, K_GRAM_REDO, K_DETECT_REDO, K_STATS_KEYS, K_EMBED_KEYS_FOLD, K_EMBED_KEYS, K_DETECT_OFFSETS, K_COUNT };
 const char* const kKernelNames[K_COUNT] = {"k_gram", "k_me_stats", "k_nvf_stats", "k_embed", "k_detect", "k_mask", "k_fused_embed", "k_fused_detect", "k_gram_ho", "k_fused_pair",
                                            "k_detect_keys", "k_gram_ho_checked", "k_gram_redo", "k_detect_redo", "k_stats_keys",
-                                           "k_embed_keys_fold", "k_embed_keys"};
+                                           "k_embed_keys_fold", "k_embed_keys", "k_detect_offsets"};
 
 // fused single-frame launches use every CU and wait for each other inside the launch: two of them in flight on one device
 // could each hold a part of the CUs and starve the other (their spins are bounded, so that would be a slow fallback, not a
@@ -88,7 +88,7 @@ struct Pending {
     int* status_out;
     float* coef_out;  // host destination for 8*frames coefficients (mask-only ops)
     int coef_off;
-    int nkeys = 0;    // wm_detect_keys / wm_embed_keys: frames * nkeys records, value_out [frames][nkeys], status_out [frames]
+    int nkeys = 0;    // wm_detect_keys / wm_embed_keys / wm_detect_offsets (ny * nx): frames * nkeys records, value_out [frames][nkeys], status_out [frames]
 };
 
 struct Slot {
@@ -1553,6 +1553,73 @@ int wm_detect_keys(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* ke
     if ((rc = push_pending(ctx, s, frames * nkeys, corr_out, status_out, nullptr)) != WM_OK) return rc;
     s.pending.back().frames = frames;
     s.pending.back().nkeys = nkeys;
+    return sync_after ? do_sync(ctx, s) : WM_OK;
+}
+
+// every window of the rectangle lies inside the key plane (no device needed: wm_detect_offsets' own check)
+int wm_offsets_check(int rows, int cols, int key_rows, int key_cols, int oy0, int ox0, int ny, int nx)
+{
+    if (rows < 1 || cols < 1 || key_rows < rows || key_cols < cols) return WM_ERR_BAD_ARG;
+    if (ny < 1 || nx < 1 || oy0 < 0 || ox0 < 0) return WM_ERR_BAD_ARG;
+    if ((long long)oy0 + ny - 1 + rows > key_rows || (long long)ox0 + nx - 1 + cols > key_cols) return WM_ERR_BAD_ARG;
+    return WM_OK;
+}
+
+int wm_detect_offsets_group(void) { return detect_offsets_group(); }
+
+// detectWatermark of every frame against the windows of ONE key at a rectangle of offsets: wm_detect_keys' input, slot and
+// result handling, k_detect_offsets as the sweep
+int wm_detect_offsets(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* keys, int k, int oy0, int ox0, int ny, int nx,
+                      float* corr_out, int* status_out, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    if (mask != WM_MASK_ME && mask != WM_MASK_NVF) return fail(ctx, WM_ERR_BAD_ARG, "bad mask type");
+    if (ctx->p != 3 && mask == WM_MASK_ME) return fail(ctx, WM_ERR_BAD_P, "ME mask needs p == 3 (main.cpp:89)");
+    if (!img || !keys || !corr_out) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_offsets: null img, keys or corr_out");
+    if (k < 0 || k >= keys->nkeys) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_offsets: key " + std::to_string(k) + " of a bank of " + std::to_string(keys->nkeys));
+    if (keys->device != ctx->device || keys->rows < ctx->rows || keys->cols < ctx->cols)
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_offsets: the key bank is " + std::to_string(keys->rows) + "x" + std::to_string(keys->cols) + " on device " +
+                                             std::to_string(keys->device) + ", the engine " + std::to_string(ctx->rows) + "x" + std::to_string(ctx->cols) +
+                                             " on device " + std::to_string(ctx->device) + " (the bank must be at least as large)");
+    if (wm_offsets_check(ctx->rows, ctx->cols, keys->rows, keys->cols, oy0, ox0, ny, nx) != WM_OK)
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_offsets: offsets (" + std::to_string(oy0) + "," + std::to_string(ox0) + ") + " + std::to_string(ny) + "x" +
+                                             std::to_string(nx) + " of " + std::to_string(ctx->rows) + "x" + std::to_string(ctx->cols) +
+                                             " windows leave the " + std::to_string(keys->rows) + "x" + std::to_string(keys->cols) + " key plane");
+    if (ctx->band_hi > 0) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_offsets: not in band mode");
+    Slot* sp; bool sync_after;
+    int rc = get_slot(ctx, slot, &sp, &sync_after);
+    if (rc != WM_OK) return rc;
+    Slot& s = *sp;
+    if ((rc = check_plane(ctx, img, 0, false, "image", true)) != WM_OK) return rc;
+    const int frames = img->frames;
+    const long long noff = (long long)ny * nx;
+    if ((long long)s.res_used + (long long)frames * noff > RES_CAP)
+        return fail(ctx, WM_ERR_BUSY, "too many un-synced results on this slot (frames x offsets count against " + std::to_string(RES_CAP) + ")");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    PlaneDesc xd;
+    if ((rc = prep_input(ctx, s, img, &xd)) != WM_OK) return rc;
+    LaunchGeom lg;
+    if ((rc = geom_checked(ctx, frames, mask, &lg)) != WM_OK) return rc;
+    // partial records: [frames][ny * nx][rstride][2] + [frames][rstride] (the scratch of wm_detect_keys: one stream, in order)
+    const int rstride = std::max(ctx->max_nblk, ctx->max_nrec);
+    const size_t need = (size_t)frames * (2 * (size_t)noff + 1) * rstride * sizeof(double);
+    if ((rc = ensure(ctx, &s.keys_part, &s.keys_part_bytes, need)) != WM_OK) return rc;
+    // the buffer descriptor of a window spans rows of the KEY plane's pitch: its extent decides the 32-bit offsets
+    const int aligned_w = fits_32bit(keys->rows, keys->cols, WM_F32) ? 1 : 0;
+    const float* key = keys->d + (size_t)k * keys->rows * keys->cols;
+    OpResult* res = s.d_res + s.res_used;
+    // the image side is wm_detect's: the Gram sweep (or the hand-over of the slot's last embed) and the solve
+    if ((rc = gram_sweep(ctx, s, lg, frames, xd, img)) != WM_OK) return rc;
+    {
+        ProfScope ps(ctx, K_DETECT_OFFSETS, s.stream);
+        if (launch_detect_offsets(s.stream, lg, frames, mask, ctx->p / 2, xd, key, keys->cols, oy0, ox0, ny, nx, aligned_w, s.d_coef,
+                                  s.d_status, (double*)s.keys_part, rstride, res) != 0)
+            return fail(ctx, WM_ERR_RUNTIME, "wm_detect_offsets: geometry exceeds the record arrays");
+    }
+    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
+    if ((rc = push_pending(ctx, s, frames * (int)noff, corr_out, status_out, nullptr)) != WM_OK) return rc;
+    s.pending.back().frames = frames;
+    s.pending.back().nkeys = (int)noff;
     return sync_after ? do_sync(ctx, s) : WM_OK;
 }
 

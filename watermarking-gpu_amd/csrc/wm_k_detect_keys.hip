@@ -275,7 +275,6 @@ __global__ __launch_bounds__(BLOCK, (PAD == 1 && HC == 1 ? (VEC ? (sizeof(T) == 
 // one block per (frame, key): the records folded in k_detect's order -- corr_finalize_frame's over the blocks, or (quad)
 // corr_fold's over the segments of each strip, then over the strips -- into corr = (float)dot / (float)(||e_w|| * ||e_u||)
 // (Watermark.cpp:230); unsolvable => 0.0f (:246-247)
-constexpr int KEYS_MAX_STRIPS = 256;
 __global__ __launch_bounds__(BLOCK) void k_keys_fold(const double* __restrict__ part, const double* __restrict__ partw, int rstride,
                                                      int nkeys, int quad, int nblk, int nsegs, int nstrips,
                                                      const int* __restrict__ status, OpResult* __restrict__ res)
@@ -394,9 +393,15 @@ int launch_detect_keys(hipStream_t s, const LaunchGeom& lg, int frames, int mask
     ka.W = Wbank; ka.kstride = kstride; ka.nkeys = nkeys; ka.ngroups = (nkeys + KG - 1) / KG; ka.rstride = rstride;
     ka.part = part; ka.partw = part + (size_t)frames * nkeys * rstride * 2;
     WM_DISPATCH_T(x.dtype, launch_detect_keys_t<T>(s, ld, frames, mask, pad, x, aligned_w, ka, coef, status, split));
-    WM_KLAUNCH(k_keys_fold, dim3((unsigned)(frames * nkeys)), dim3(BLOCK), 0, s, (const double*)ka.part, (const double*)ka.partw,
-               rstride, nkeys, quad ? 1 : 0, ld.nblk, ld.nsegs, ld.nstrips, status, res);
+    launch_keys_fold(s, ka.part, ka.partw, rstride, frames, nkeys, quad ? 1 : 0, ld.nblk, ld.nsegs, ld.nstrips, status, res);
     return 0;
+}
+
+void launch_keys_fold(hipStream_t s, const double* part, const double* partw, int rstride, int frames, int nkeys, int quad, int nblk,
+                      int nsegs, int nstrips, const int* status, OpResult* res)
+{
+    WM_KLAUNCH(k_keys_fold, dim3((unsigned)(frames * nkeys)), dim3(BLOCK), 0, s, part, partw, rstride, nkeys, quad, nblk, nsegs, nstrips,
+               status, res);
 }
 
 }  // namespace wmk

@@ -205,6 +205,21 @@ int launch_detect_keys(hipStream_t s, const LaunchGeom& lg, int frames, int mask
                        const float* Wbank, long long kstride, int nkeys, int aligned_w, const float* coef, const int* status,
                        double* part, int rstride, OpResult* res);
 int detect_keys_group(void);  // keys per group of k_detect_keys (compile-time KG)
+// k_keys_fold: one block per (frame, key) folds the records part [frames][nkeys][rstride][2] / partw [frames][rstride] of a
+// sweep in k_detect's order into res[frame * nkeys + key]; a strip-level fold (quad) covers KEYS_MAX_STRIPS strips
+constexpr int KEYS_MAX_STRIPS = 256;
+void launch_keys_fold(hipStream_t s, const double* part, const double* partw, int rstride, int frames, int nkeys, int quad, int nblk,
+                      int nsegs, int nstrips, const int* status, OpResult* res);
+// one image against a rectangle of window offsets into ONE key plane of pitch key_cols that is larger than the image
+// (wm_detect_offsets, wm_k_detect_offsets.hip): offset (oy0 + i, ox0 + j), i < ny, j < nx, scores the image against the window
+// key[oy : oy + rows, ox : ox + cols] -- k_detect_keys' sweep with groups of horizontally adjacent offsets as a grid axis, then
+// k_keys_fold into res[frame * ny * nx + i * nx + j].  The caller has checked that every window lies inside the plane.
+// aligned_w: the KEY plane's extent allows 32-bit offsets.  part: [frames][2 ny nx + 1][rstride] doubles of scratch.  Returns -1
+// when the sweep's records exceed rstride (nothing is launched)
+int launch_detect_offsets(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x,
+                          const float* key, int key_cols, int oy0, int ox0, int ny, int nx, int aligned_w, const float* coef,
+                          const int* status, double* part, int rstride, OpResult* res);
+int detect_offsets_group(void);  // offsets per group of k_detect_offsets' shared-row instances (compile-time OG)
 // one image embedded with every key of a bank (wm_embed_keys, wm_k_embed_keys.hip).  The image side is wm_embed's (launch_gram:
 // coef / status); then k_stats_keys (k_me_stats' / k_nvf_stats' sweep for every key, key groups as a grid axis), one fold block
 // per (frame, key) into res[frame * nkeys + key] and the scalars k_embed_keys reads, and k_embed_keys (k_embed's sweep for every
