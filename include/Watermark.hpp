@@ -254,6 +254,29 @@ public:
         if (rc < 0) fail(rc, "detectOffsets");
         return corr;
     }
+    // where in the frame is the mark?  detectWatermark of one grey image against this engine's W with the correlation's three sums
+    // kept per tile of tileRows x tileCols pixels (wm.h wm_detect_tiles; the last tile of each axis takes the remainder): score
+    // [i * nx + j] is tile (i, j)'s, NaN for a tile without energy, 0 everywhere when the system is not solvable.  ny / nx, if
+    // given, receive the tiles per axis (wm_tiles_shape)
+    std::vector<float> detectTiles(const wm::Image& watermarkedImage, int tileRows, int tileCols, MASK_TYPE maskType, int* ny = nullptr,
+                                   int* nx = nullptr) const
+    {
+        int ty = 0, tx = 0;
+        int rc = wm_tiles_shape(wm_rows(ctx), wm_cols(ctx), tileRows, tileCols, &ty, &tx);
+        if (rc < 0) fail(rc, "detectTiles");
+        if (ny) *ny = ty;
+        if (nx) *nx = tx;
+        const wm_plane pimg = watermarkedImage.plane();
+        std::vector<float> map((size_t)ty * (size_t)tx, 0.0f);
+        float* dmap = static_cast<float*>(wm_dev_alloc(wm_device(ctx), map.size() * sizeof(float)));
+        if (!dmap) fail(WM_ERR_ALLOC, "detectTiles");
+        rc = wm_detect_tiles(ctx, (int)maskType, &pimg, tileRows, tileCols, dmap, nullptr, nullptr, WM_SLOT_SYNC);
+        const int rd = rc < 0 ? WM_OK : wm_memcpy_d2h(map.data(), dmap, map.size() * sizeof(float));
+        wm_dev_free(dmap);
+        if (rc < 0) fail(rc, "detectTiles");
+        if (rd < 0) fail(rd, "detectTiles");
+        return map;
+    }
     // makeWatermark of one grey image with every key of `keys` as W in one call (wm.h wm_embed_keys): copy k is what
     // makeWatermark returns with key k as W, strengths[k] its strength.  Not solvable: every copy is `outputImage` itself and
     // `strengths` is left untouched (Watermark.cpp:164-165)

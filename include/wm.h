@@ -263,6 +263,47 @@ int wm_detect_offsets_group(void);  /* G: horizontally adjacent offsets that sha
 int wm_detect_offsets(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* keys, int k, int oy0, int ox0, int ny, int nx,
                       float* corr_out, int* status_out, int slot);
 
+/* ---- Tile map: where in the frame is the mark? -------------------------------------------------------------------------------
+ * wm_detect answers with one correlation for the whole plane.  A copy with a logo pasted over it, a picture-in-picture or a
+ * spliced region only lets that score sag.  The detector is local, though: after the one solve per frame, e_w, u = m W and e_u
+ * are 3x3 stencils, so the three sums of computeCorrelation can be kept PER TILE of the frame.
+ * wm_detect_tiles is detectWatermark (Watermark.cpp:234-250) of every frame of `img` against the context's own W -- one
+ * Gram sweep (the hand-over of the slot's last embed included, exactly as wm_detect_keys takes it) and one solve per frame, so
+ * ONE coefficient vector and ONE mask per frame -- with the sums <e_u,e_w>, ||e_u||^2, ||e_w||^2 kept per tile.
+ *
+ * wm_tiles_shape: tiles per axis: ny = max(1, rows / tile_rows), nx = max(1, cols / tile_cols) (integer division); pixel (r, c)
+ * belongs to tile (min(r / tile_rows, ny - 1), min(c / tile_cols, nx - 1)): the LAST tile of each axis takes the remainder, so no
+ * tile is smaller than tile_rows x tile_cols and there are no sliver tiles.  WM_OK, or WM_ERR_BAD_ARG unless tile_rows is a
+ * multiple of 8 and >= 32, tile_cols a multiple of 4 and >= 32, rows, cols in 1..32768 and ny, nx non-null.  Pure host arithmetic.
+ * (Tiles below 32 x 32 hold too few pixels for the 1e-5 agreement with the CPU oracle that every detector here keeps.)
+ *
+ * map_dev [frames][ny][nx] is a DEVICE f32 array on the context's device: (float)dot / (float)(sqrt(nw) * sqrt(nu)) of the tile's
+ * sums.  sums_dev [frames][ny][nx][3] is a DEVICE f64 array and may be NULL: {<e_u,e_w>, ||e_u||^2, ||e_w||^2}, the quantities
+ * wm_band_detect_sums reports; under ME they are taken with m = |e_w| (the 1 / max|e| cancels in every score and is not applied).
+ * Tile sums ADD: the score of any union of tiles is formed on the host from the sums of its tiles, and the sums added over all
+ * tiles give wm_detect's score of the frame on the sweeps to <= 2e-7 (a regrouping of the same products).
+ * Both arrays are written on the slot's stream and are valid once wm_sync(ctx, slot) has returned; they must stay allocated
+ * until then.  The map does not pass through the slot's result records (a 4K frame in 32 x 32 tiles is 8040 scores).
+ * status_out[frames] may be NULL; it is delivered by wm_sync like wm_detect's, and `frames` results count against the slot's
+ * capacity of 4096 un-synced results (WM_ERR_BUSY beyond it).
+ *   - An unsolvable frame has status WM_UNSOLVABLE, 0.0f in every tile and zero sums.
+ *   - A tile whose ||e_u||^2 or ||e_w||^2 is zero (a flat patch, a zero W) scores 0/0 = NaN with status WM_OK: wm_detect's
+ *     zero-W rule, per tile.
+ *   - Takes every input wm_detect takes on the sweeps: f32 / u8, any pitch and width, WM_MEM_HOST, WM_MEM_SLOT_OUT, batches up to
+ *     max_frames, ME with p = 3 (WM_ERR_BAD_P otherwise), NVF with p = 3..9.
+ *   - An ENQUEUE on the slot (WM_SLOT_SYNC: slot 0, waits); it may share a slot with any other call in any order.  The sweep's
+ *     record scratch is kept per slot and grown on demand (its size follows from the tile shape): the FIRST call on a slot that
+ *     needs more of it than any call before -- more frames, or a tile_rows with shorter segments -- reallocates it, which waits
+ *     for the whole device, the other slots' streams included.  Later calls only enqueue.
+ *   - Never takes the fused single-launch kernels.  Refused in band mode (WM_ERR_BAD_ARG).
+ *   - WM_ERR_BAD_ARG, before any device work, for a null ctx, img or map_dev and for a tile shape wm_tiles_shape refuses.
+ * Bits: a frame's map and sums do not depend on the batch it arrives in or on repetition (the sweep's segments follow from
+ * tile_rows alone; the fold adds in a fixed order, no atomics).  A WM_MEM_HOST plane gives the bits of the same plane on the
+ * device whenever both take the same strips: always for f32 planes and for widths that are multiples of 4. */
+int wm_tiles_shape(int rows, int cols, int tile_rows, int tile_cols, int* ny, int* nx);
+int wm_detect_tiles(wm_ctx* ctx, int mask, const wm_plane* img, int tile_rows, int tile_cols, float* map_dev, double* sums_dev,
+                    int* status_out, int slot);
+
 /* makeWatermark (Watermark.cpp:156-172) of every frame of `in_gray` once with EVERY key of the bank as W: one marked copy per
  * recipient.  Copy (f, k) -- frame f marked with key k -- is frame f * nkeys + k of `out`, so out->frames must be
  * in_gray->frames * nkeys; `out` is a WM_MEM_DEVICE plane with the channels and dtype of `base` (any pitch and frame stride; it

@@ -78,6 +78,8 @@ ABI = [
     ("wm_detect_offsets_group", C.c_int, []),
     ("wm_detect_offsets", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_float), _P(C.c_int),
                                    C.c_int]),
+    ("wm_tiles_shape", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_int), _P(C.c_int)]),
+    ("wm_detect_tiles", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), C.c_int, C.c_int, C.c_void_p, C.c_void_p, _P(C.c_int), C.c_int]),
     ("wm_compute_mask", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), _P(wm_plane), _P(wm_plane), _P(C.c_float), _P(C.c_int), C.c_int]),
     ("wm_gram", C.c_int, [_ctx_p, _P(wm_plane), _P(C.c_double), C.c_int]),
     ("wm_band_configure", C.c_int, [_ctx_p, C.c_int, C.c_int, C.c_longlong]),
@@ -482,6 +484,35 @@ class Watermark:
             _raise(rc, self._ctx)
         return corr[0] if image.dim() == 2 else corr
 
+    @staticmethod
+    def tiles_shape(rows, cols, tile_rows, tile_cols):
+        """(ny, nx) of wm_tiles_shape: ny = max(1, rows // tile_rows), nx = max(1, cols // tile_cols); the last tile of each axis
+        takes the remainder.  Raises for a tile shape the library refuses (rows: a multiple of 8, >= 32; columns: a multiple of
+        4, >= 32)"""
+        ny, nx = C.c_int(), C.c_int()
+        rc = lib().wm_tiles_shape(rows, cols, tile_rows, tile_cols, C.byref(ny), C.byref(nx))
+        if rc != WM_OK:
+            _raise(rc)
+        return ny.value, nx.value
+
+    def detectTiles(self, image, tile_rows, tile_cols, maskType, sums=False):
+        """where in the frame is the mark?  detectWatermark of `image` against the engine's W with the three sums kept per tile
+        (wm.h wm_detect_tiles): a float32 numpy array [frames, ny, nx] ([ny, nx] for one grey frame) of tile scores, 0.0 in every
+        tile of an unsolvable frame, NaN in a tile without energy.  sums=True: (map, sums) with sums float64 [..., ny, nx, 3] =
+        {<e_u,e_w>, |e_u|^2, |e_w|^2} per tile: they add, so any union of tiles is scored from them on the host"""
+        import torch
+        pimg = plane_of(image, 1)
+        frames = pimg.frames
+        ny, nx = self.tiles_shape(self.rows, self.cols, tile_rows, tile_cols)
+        map_t = torch.empty((frames, ny, nx), dtype=torch.float32, device=image.device)
+        sums_t = torch.empty((frames, ny, nx, 3), dtype=torch.float64, device=image.device) if sums else None
+        torch.cuda.current_stream().synchronize()
+        self.detect_tiles_async(image, tile_rows, tile_cols, maskType, WM_SLOT_SYNC, map_t, sums_t)
+        m = map_t.cpu().numpy()
+        if image.dim() == 2:
+            return (m[0], sums_t.cpu().numpy()[0]) if sums else m[0]
+        return (m, sums_t.cpu().numpy()) if sums else m
+
     def makeWatermarkKeys(self, inputImage, outputImage, keys, maskType, out=None):
         """makeWatermark of `inputImage` with every key of the KeySet `keys` as W in one call (wm.h wm_embed_keys).  Returns
         (copies, strengths): copies [K, ...] for one frame ([F, K, ...] for a batch [F, R, C]), copy k marked with key k, each
@@ -586,6 +617,26 @@ class Watermark:
             status_out = status_out.ctypes.data_as(_P(C.c_int))
         rc = lib().wm_detect_offsets(self._ctx, int(maskType), C.byref(pimg), keys.handle if isinstance(keys, KeySet) else keys,
                                      k, oy0, ox0, ny, nx, corr_out, status_out, slot)
+        if rc < 0:
+            _raise(rc, self._ctx)
+
+    def detect_tiles_async(self, image, tile_rows, tile_cols, maskType, slot, map_t, sums_t=None, status=None):
+        """wm_detect_tiles enqueued on `slot`: map_t (a contiguous float32 GPU tensor of frames * ny * nx elements) and sums_t
+        (float64, frames * ny * nx * 3, may be None) are written on the slot's stream and valid after sync(slot); status (frames
+        ints: a ctypes array or a C-contiguous int32 numpy array, may be None) is written by sync(slot)"""
+        import torch
+        pimg = self._as_plane(image, 1)
+        ny, nx = self.tiles_shape(self.rows, self.cols, tile_rows, tile_cols)
+        n = pimg.frames * ny * nx
+        if not (map_t.is_cuda and map_t.dtype == torch.float32 and map_t.is_contiguous() and map_t.numel() == n):
+            raise RuntimeError(f"map_t must be a contiguous float32 GPU tensor of {n} elements")
+        if sums_t is not None and not (sums_t.is_cuda and sums_t.dtype == torch.float64 and sums_t.is_contiguous() and sums_t.numel() == 3 * n):
+            raise RuntimeError(f"sums_t must be a contiguous float64 GPU tensor of {3 * n} elements")
+        if isinstance(status, np.ndarray):
+            assert status.dtype == np.int32 and status.flags.c_contiguous
+            status = status.ctypes.data_as(_P(C.c_int))
+        rc = lib().wm_detect_tiles(self._ctx, int(maskType), C.byref(pimg), tile_rows, tile_cols, C.c_void_p(map_t.data_ptr()),
+                                   C.c_void_p(sums_t.data_ptr()) if sums_t is not None else None, status, slot)
         if rc < 0:
             _raise(rc, self._ctx)
 

@@ -39,10 +39,11 @@ constexpr int TARGET_WAVES_NVF = 2048;
 // (the checked hand-over of wm_detect: its k_gram_ho launch and the predicated redo launches behind it are counted apart from
 // the opt-in hand-over's k_gram_ho and from the Gram sweeps)
 enum KernelId { K_GRAM = 0, K_ME_STATS, K_NVF_STATS, K_EMBED, K_DETECT, K_MASK, K_FUSED_EMBED, K_FUSED_DETECT, K_GRAM_HO, K_FUSED_PAIR, K_DETECT_KEYS,
-                K_GRAM_HO_CHECKED, K_GRAM_REDO, K_DETECT_REDO, K_STATS_KEYS, K_EMBED_KEYS_FOLD, K_EMBED_KEYS, K_DETECT_OFFSETS, K_COUNT };
+                K_GRAM_HO_CHECKED, K_GRAM_REDO, K_DETECT_REDO, K_STATS_KEYS, K_EMBED_KEYS_FOLD, K_EMBED_KEYS, K_DETECT_OFFSETS, K_DETECT_TILES, K_TILES_FOLD,
+                K_COUNT };
 const char* const kKernelNames[K_COUNT] = {"k_gram", "k_me_stats", "k_nvf_stats", "k_embed", "k_detect", "k_mask", "k_fused_embed", "k_fused_detect", "k_gram_ho", "k_fused_pair",
                                            "k_detect_keys", "k_gram_ho_checked", "k_gram_redo", "k_detect_redo", "k_stats_keys",
-                                           "k_embed_keys_fold", "k_embed_keys", "k_detect_offsets"};
+                                           "k_embed_keys_fold", "k_embed_keys", "k_detect_offsets", "k_detect_tiles", "k_tiles_fold"};
 
 // fused single-frame launches use every CU and wait for each other inside the launch: two of them in flight on one device
 // could each hold a part of the CUs and starve the other (their spins are bounded, so that would be a slow fallback, not a
@@ -151,6 +152,8 @@ struct Slot {
     void* keys_part = nullptr; size_t keys_part_bytes = 0;
     // wm_embed_keys: per-(frame, key) stats records and strengths of k_stats_keys (grown on demand)
     void* ekeys_part = nullptr; size_t ekeys_part_bytes = 0;
+    // wm_detect_tiles: per-lane records of k_detect_tiles [frames][nsegs][nstrips][3][64] f32 (grown on demand)
+    void* tiles_rec = nullptr; size_t tiles_rec_bytes = 0;
 };
 
 struct ProfRec { int kid; hipEvent_t a, b; bool first; };  // first: the sweep's first launch (counts the call)
@@ -345,7 +348,7 @@ void free_slot(Slot& s)
     if (s.h_res) (void)hipHostFree(s.h_res);
     if (s.h_coefres) (void)hipHostFree(s.h_coefres);
     (void)hipFree(s.st_in); (void)hipFree(s.st_base); (void)hipFree(s.st_out); (void)hipFree(s.fz_block); (void)hipFree(s.d_ho); (void)hipFree(s.d_hoseam);
-    (void)hipFree(s.d_hodig); (void)hipFree(s.keys_part); (void)hipFree(s.ekeys_part);
+    (void)hipFree(s.d_hodig); (void)hipFree(s.keys_part); (void)hipFree(s.ekeys_part); (void)hipFree(s.tiles_rec);
     s = Slot();
 }
 
@@ -1620,6 +1623,56 @@ int wm_detect_offsets(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys*
     if ((rc = push_pending(ctx, s, frames * (int)noff, corr_out, status_out, nullptr)) != WM_OK) return rc;
     s.pending.back().frames = frames;
     s.pending.back().nkeys = (int)noff;
+    return sync_after ? do_sync(ctx, s) : WM_OK;
+}
+
+// tiles per axis of wm_detect_tiles: the last tile of each axis takes the remainder (pure host arithmetic)
+int wm_tiles_shape(int rows, int cols, int tile_rows, int tile_cols, int* ny, int* nx)
+{
+    if (!ny || !nx) return WM_ERR_BAD_ARG;
+    if (rows < 1 || cols < 1 || rows > 32768 || cols > 32768) return WM_ERR_BAD_ARG;
+    if (tile_rows < 32 || tile_rows % 8 != 0 || tile_cols < 32 || tile_cols % 4 != 0) return WM_ERR_BAD_ARG;
+    *ny = std::max(1, rows / tile_rows);
+    *nx = std::max(1, cols / tile_cols);
+    return WM_OK;
+}
+
+// detectWatermark of every frame against the context's W with the three sums kept per tile: wm_detect's input and slot
+// handling on the sweeps, k_detect_tiles + k_tiles_fold in k_detect's place; the map stays on the device
+int wm_detect_tiles(wm_ctx* ctx, int mask, const wm_plane* img, int tile_rows, int tile_cols, float* map_dev, double* sums_dev,
+                    int* status_out, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    if (!img || !map_dev) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_tiles: null img or map_dev");
+    int ny = 0, nx = 0;
+    if (wm_tiles_shape(ctx->rows, ctx->cols, tile_rows, tile_cols, &ny, &nx) != WM_OK)
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_tiles: tile shape " + std::to_string(tile_rows) + "x" + std::to_string(tile_cols) +
+                                             " (rows: a multiple of 8, >= 32; columns: a multiple of 4, >= 32)");
+    if (mask != WM_MASK_ME && mask != WM_MASK_NVF) return fail(ctx, WM_ERR_BAD_ARG, "bad mask type");
+    if (ctx->p != 3 && mask == WM_MASK_ME) return fail(ctx, WM_ERR_BAD_P, "ME mask needs p == 3 (main.cpp:89)");
+    if (ctx->band_hi > 0) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_tiles: not in band mode");
+    Slot* sp; bool sync_after;
+    int rc = get_slot(ctx, slot, &sp, &sync_after);
+    if (rc != WM_OK) return rc;
+    Slot& s = *sp;
+    if ((rc = check_plane(ctx, img, 0, false, "image", true)) != WM_OK) return rc;
+    const int frames = img->frames;
+    if (s.res_used + frames > RES_CAP) return fail(ctx, WM_ERR_BUSY, "too many un-synced results on this slot");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    PlaneDesc xd;
+    if ((rc = prep_input(ctx, s, img, &xd)) != WM_OK) return rc;
+    LaunchGeom lg;
+    if ((rc = geom_checked(ctx, frames, mask, &lg)) != WM_OK) return rc;
+    const int aligned_w = fits_32bit(ctx->rows, ctx->cols, WM_F32) ? 1 : 0;
+    const TilesPlan pl = tiles_plan(lg, frames, mask, ctx->p / 2, xd, aligned_w, tile_rows, tile_cols, ny, nx);
+    if ((rc = ensure(ctx, &s.tiles_rec, &s.tiles_rec_bytes, pl.rec_bytes)) != WM_OK) return rc;
+    OpResult* res = s.d_res + s.res_used;
+    // the image side is wm_detect's: the Gram sweep (or the hand-over of the slot's last embed) and the solve
+    if ((rc = gram_sweep(ctx, s, lg, frames, xd, img)) != WM_OK) return rc;
+    { ProfScope ps(ctx, K_DETECT_TILES, s.stream); launch_detect_tiles(s.stream, pl, frames, mask, ctx->p / 2, xd, ctx->w->d_w, s.d_coef, s.d_status, (float*)s.tiles_rec); }
+    { ProfScope ps(ctx, K_TILES_FOLD, s.stream); launch_tiles_fold(s.stream, pl, frames, (const float*)s.tiles_rec, s.d_status, map_dev, sums_dev, res); }
+    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
+    if ((rc = push_pending(ctx, s, frames, nullptr, status_out, nullptr)) != WM_OK) return rc;
     return sync_after ? do_sync(ctx, s) : WM_OK;
 }
 

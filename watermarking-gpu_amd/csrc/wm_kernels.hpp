@@ -220,6 +220,32 @@ int launch_detect_offsets(hipStream_t s, const LaunchGeom& lg, int frames, int m
                           const float* key, int key_cols, int oy0, int ox0, int ny, int nx, int aligned_w, const float* coef,
                           const int* status, double* part, int rstride, OpResult* res);
 int detect_offsets_group(void);  // offsets per group of k_detect_offsets' shared-row instances (compile-time OG)
+// the detector's three sums per tile of the frame (wm_detect_tiles, wm_k_detect_tiles.hip).  k_detect_tiles is k_detect's sweep
+// with segments whose height divides tile_rows; every lane leaves its f32 partials in rec [frames][nsegs][nstrips][3][64], and
+// k_tiles_fold adds each tile's records in a fixed order in f64 into map [frames][ny][nx] (and sums [frames][ny][nx][3], may be
+// null) on the device and res[frame] = {status, 0}.  Pixel (r, c) belongs to tile (min(r / th, ny - 1), min(c / tw, nx - 1))
+struct TileGeom {
+    int th, tw, ny, nx;        // tile shape and tiles per axis (wm_tiles_shape)
+    int rps, nsegs, nstrips;   // the sweep's record geometry: segments of rps rows (rps divides th), strips
+    int layout;                // who owns a column group of 4: 0 = strips of 256, 1 = overlapped strips, 2 = overlapped + one generic strip
+    int nown;                  // layouts 1, 2: column groups the overlapped strips own
+    int ngroups;               // column groups in all (layout 2: the generic strip's 64 lanes count as the last 64)
+};
+struct TilesPlan {
+    LaunchGeom ld;             // the sweep's geometry (strips as launch_detect chooses them for this plane)
+    bool overlap, split;
+    TileGeom tg;
+    size_t rec_bytes;          // size of rec for this call
+    int fold_threads;          // threads per tile of k_tiles_fold: 64 or 256
+};
+int tiles_segment_rows(int tile_rows);  // the largest divisor of tile_rows in 8 .. 48 (tile_rows is a multiple of 8)
+// lg: make_geom's geometry of the call (the plan replaces its segments)
+TilesPlan tiles_plan(const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, int aligned_w, int tile_rows, int tile_cols,
+                     int ny, int nx);
+void launch_detect_tiles(hipStream_t s, const TilesPlan& pl, int frames, int mask, int pad, const PlaneDesc& x, const float* W,
+                         const float* coef, const int* status, float* rec);
+void launch_tiles_fold(hipStream_t s, const TilesPlan& pl, int frames, const float* rec, const int* status, float* map, double* sums,
+                       OpResult* res);
 // one image embedded with every key of a bank (wm_embed_keys, wm_k_embed_keys.hip).  The image side is wm_embed's (launch_gram:
 // coef / status); then k_stats_keys (k_me_stats' / k_nvf_stats' sweep for every key, key groups as a grid axis), one fold block
 // per (frame, key) into res[frame * nkeys + key] and the scalars k_embed_keys reads, and k_embed_keys (k_embed's sweep for every
