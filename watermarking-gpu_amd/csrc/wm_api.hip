@@ -45,6 +45,13 @@ const char* const kKernelNames[K_COUNT] = {"k_gram", "k_me_stats", "k_nvf_stats"
                                            "k_detect_keys", "k_gram_ho_checked", "k_gram_redo", "k_detect_redo", "k_stats_keys",
                                            "k_embed_keys_fold", "k_embed_keys", "k_detect_offsets", "k_detect_tiles", "k_tiles_fold"};
 
+// WM_X=1 / WM_X=0 switches: only a value that says the opposite of the default changes it (first character)
+bool env_flag(const char* name, bool dflt)
+{
+    const char* e = getenv(name);
+    return e ? (dflt ? e[0] != '0' : e[0] == '1') : dflt;
+}
+
 // fused single-frame launches use every CU and wait for each other inside the launch: two of them in flight on one device
 // could each hold a part of the CUs and starve the other (their spins are bounded, so that would be a slow fallback, not a
 // hang).  Synchronous calls hold this lock from launch to completion: a mutex between the threads of this process and an
@@ -82,14 +89,13 @@ struct WShared {
 };
 
 struct Pending {
-    bool keep_value_when_unsolvable = false;  // embed: `a` stays untouched (Watermark.cpp:164-165)
     int frames;
+    int per_frame;  // records per frame: 1, or the keys of wm_detect_keys / wm_embed_keys, or wm_detect_offsets' ny * nx (value_out [frames][per_frame])
+    bool keep_value_when_unsolvable;  // embed: `a` stays untouched (Watermark.cpp:164-165)
     int res_off;
     float* value_out;
-    int* status_out;
+    int* status_out;  // [frames]
     float* coef_out;  // host destination for 8*frames coefficients (mask-only ops)
-    int coef_off;
-    int nkeys = 0;    // wm_detect_keys / wm_embed_keys / wm_detect_offsets (ny * nx): frames * nkeys records, value_out [frames][nkeys], status_out [frames]
 };
 
 struct Slot {
@@ -168,10 +174,10 @@ struct wm_ctx {
     int nslots = 0, max_frames = 1;
     int rps_override = 0;
     int ncu = 0;
-    int fused_mode = 1;  // 1: synchronous one-frame calls take the fused kernels when the shape allows (wm_set_fused)
+    int fused_mode = env_flag("WM_FUSED", true);  // 1: synchronous one-frame calls take the fused kernels when the shape allows (wm_set_fused)
     // wm_embed_detect on one image: 1 = ONE launch for both halves (k_fused_pair).  Off unless WM_FUSED_PAIR=1: measured 1.5-2 us
     // SLOWER than the two launches back to back at 4K, equal at 1080p
-    int fused_pair = (getenv("WM_FUSED_PAIR") && getenv("WM_FUSED_PAIR")[0] == '1') ? 1 : 0;
+    int fused_pair = env_flag("WM_FUSED_PAIR", false);
     FusedGeom fg{};
     unsigned long long fused_fallbacks = 0;  // fused launches that timed out and were re-run on the sweeps
     unsigned long long fused_lock_skips = 0; // synchronous calls that took the sweeps because another process held the device's lock
@@ -180,9 +186,9 @@ struct wm_ctx {
     // process's kernels, a CU mask -- costs one time-out per window, not one per call
     int fused_backoff = 0, fused_skip = 0;
     int handover = 0;        // wm_set_handover
-    int handover_verify = (getenv("WM_HANDOVER_VERIFY") && getenv("WM_HANDOVER_VERIFY")[0] == '1') ? 1 : 0;  // debug: re-check every hand-over
+    int handover_verify = env_flag("WM_HANDOVER_VERIFY", false);  // debug: re-check every hand-over
     int pair_handover = 0;   // 1 inside wm_embed_detect: its detector reads the embed's output by construction
-    int checked_handover = (getenv("WM_CHECKED_HANDOVER") && getenv("WM_CHECKED_HANDOVER")[0] == '0') ? 0 : 1;  // wm_set_checked_handover
+    int checked_handover = env_flag("WM_CHECKED_HANDOVER", true);  // wm_set_checked_handover
     int pair_mode = 0;       // 1 inside wm_embed_detect: the fused embed does not wait (and the caller holds the FusedGuard)
     int fused_lock_fd = -1;  // per-device lock file shared with other processes (FusedGuard), -1: none
     int max_nblk = 0, max_nrec = 0;  // per-frame capacity of the slots' partial-record arrays (alloc_slots)
@@ -209,20 +215,27 @@ struct wm_keys {
 
 namespace {
 
+// a result record as the device left it in mapped host memory: ONE 64-bit acquire load, so status and value belong together
+// and nothing that follows is read ahead of it
+OpResult load_record(const OpResult* rec)
+{
+    static_assert(sizeof(OpResult) == 8 && sizeof(std::atomic<uint64_t>) == 8, "the record is one 8-byte word");
+    const uint64_t v = reinterpret_cast<const std::atomic<uint64_t>*>(rec)->load(std::memory_order_acquire);
+    OpResult r;
+    std::memcpy(&r, &v, 8);
+    return r;
+}
+
 // Wait for a fused launch by polling the result record its folding workgroup writes to device-mapped pinned memory (ONE 8-byte
-// store: status and value; embed: after every byte of the output has been written through to memory).  The record is read
-// with one 64-bit acquire load, so status and value belong together and nothing that follows is read ahead of it.  Returns
+// store: status and value; embed: after every byte of the output has been written through to memory: load_record).  Returns
 // true when the record arrived (copy in *got).  A launch whose hand-off timed out ends WITHOUT writing the record: once
 // the call is older than a normal one (150 us) the stream is queried every ~20 us, and a finished stream with the record
 // still pending returns false at once (it used to spin for 200 ms).  hipStreamSynchronize costs 5.5 us more per call than
 // this poll (tools/ubench/launch_sync.hip), so the normal path never touches the stream.
 bool poll_record(const OpResult* rec, int pending, hipStream_t stream, OpResult* got)
 {
-    static_assert(sizeof(OpResult) == 8 && sizeof(std::atomic<uint64_t>) == 8, "the record is one 8-byte word");
-    const std::atomic<uint64_t>* word = reinterpret_cast<const std::atomic<uint64_t>*>(rec);
     auto look = [&]() {
-        const uint64_t v = word->load(std::memory_order_acquire);
-        std::memcpy(got, &v, 8);
+        *got = load_record(rec);
         return got->status != pending;
     };
     const auto t0 = std::chrono::steady_clock::now();
@@ -422,7 +435,7 @@ int alloc_slots(wm_ctx* ctx, int nslots, int max_frames)
     const size_t nb = (size_t)ctx->max_nblk * max_frames;
     if (ctx->ncu == 0 && hipDeviceGetAttribute(&ctx->ncu, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess) ctx->ncu = 0;
     ctx->fg = fused_geometry(ctx->rows, ctx->cols, ctx->ncu);
-    if (ctx->fg.fusable && ctx->fused_lock_fd < 0 && !(getenv("WM_FUSED_XPROC_LOCK") && getenv("WM_FUSED_XPROC_LOCK")[0] == '0')) {
+    if (ctx->fg.fusable && ctx->fused_lock_fd < 0 && env_flag("WM_FUSED_XPROC_LOCK", true)) {
         char bus[64] = "dev";
         if (hipDeviceGetPCIBusId(bus, sizeof bus, ctx->device) != hipSuccess) snprintf(bus, sizeof bus, "ordinal%d", ctx->device);
         for (char* q = bus; *q; ++q) if (*q == ':' || *q == '/' || *q == '.') *q = '_';
@@ -549,6 +562,45 @@ int check_params(int rows, int cols, int p, float psnr)
     return WM_OK;
 }
 
+// W generated on the device from a seed (wm_create_generated; the current device is the context's)
+int generate_w(wm_ctx* ctx, uint32_t seed)
+{
+    auto ws = std::make_shared<WShared>();
+    ws->n = (size_t)ctx->rows * ctx->cols;
+    if (hipMalloc((void**)&ws->d_w, ws->n * sizeof(float)) != hipSuccess) return WM_ERR_ALLOC;
+    launch_gen_w(nullptr, ws->d_w, ctx->rows, ctx->cols, seed);
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return WM_ERR_RUNTIME;
+    ctx->w = ws;
+    return WM_OK;
+}
+
+// the device a create call names becomes the current one; an invalid ordinal means the default, 0 (main.cpp:73-78)
+int choose_device(int* device)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return WM_ERR_NO_DEVICE;
+    if (*device < 0 || *device >= ndev) *device = 0;
+    return hipSetDevice(*device) == hipSuccess ? WM_OK : WM_ERR_NO_DEVICE;
+}
+
+// wm_create / wm_create_generated: they differ in how W reaches the device (generated there from the seed, or w uploaded)
+int create_ctx(wm_ctx** out, int device, int rows, int cols, int p, float psnr, bool generated, const float* w, uint32_t seed)
+{
+    if (!out) return WM_ERR_BAD_ARG;
+    *out = nullptr;
+    int rc = check_params(rows, cols, p, psnr);
+    if (rc != WM_OK) return rc;
+    if (!generated && !w) return WM_ERR_BAD_ARG;
+    if ((rc = choose_device(&device)) != WM_OK) return rc;
+    std::unique_ptr<wm_ctx> ctx(new wm_ctx);
+    ctx->device = device; ctx->rows = rows; ctx->cols = cols; ctx->p = p; ctx->psnr = psnr;
+    ctx->sF = 255.0f / sqrtf(powf(10.0f, psnr / 10.0f));  // Watermark.cpp:22
+    if ((rc = generated ? generate_w(ctx.get(), seed) : upload_w(ctx.get(), w)) != WM_OK) return rc;
+    if ((rc = alloc_slots(ctx.get(), 2, 1)) != WM_OK) return rc;
+    *out = ctx.release();
+    return WM_OK;
+}
+
 // the aligned path addresses a plane as a buffer with 32-bit byte offsets (wm_device.hpp make_rsrc): one plane must stay
 // below 4 GiB (a 32768 x 32768 f32 plane is not: it takes the generic path)
 bool fits_32bit(int rows, long long pitch, int dtype)
@@ -666,32 +718,21 @@ int snapshot(wm_ctx* ctx, Slot& s, const PlaneDesc& src_d, const wm_plane* shape
     return WM_OK;
 }
 
-bool planes_overlap(const wm_plane* a, const wm_plane* b)
+// bytes from the first pixel of a plane to the end of its last one (all channels and frames)
+size_t plane_extent(const PlaneDesc& d, int rows, int cols, int frames)
 {
-    auto extent = [](const wm_plane* p) {
-        const size_t es = elem_size(p->dtype);
-        size_t n = (size_t)(p->rows - 1) * p->pitch + p->cols;
-        if (p->channels > 1) n += (size_t)(p->channels - 1) * p->channel_stride;
-        if (p->frames > 1) n += (size_t)(p->frames - 1) * p->frame_stride;
-        return n * es;
-    };
-    const char* a0 = (const char*)a->data; const char* a1 = a0 + extent(a);
-    const char* b0 = (const char*)b->data; const char* b1 = b0 + extent(b);
-    return a0 < b1 && b0 < a1;
+    size_t n = (size_t)(rows - 1) * d.pitch + cols;
+    if (d.channels > 1) n += (size_t)(d.channels - 1) * d.cstride;
+    if (frames > 1) n += (size_t)(frames - 1) * d.fstride;
+    return n * elem_size(d.dtype);
 }
 
-// the same question for RESOLVED planes (what the kernels will address: a WM_MEM_SLOT_OUT input is the slot's last output,
-// host planes are their staging buffers); frames_b > 0: `b` has that many frames (wm_embed_keys' K copies per input frame)
+// do two RESOLVED planes share a byte (what the kernels will address: a WM_MEM_SLOT_OUT input is the slot's last output, host
+// planes are their staging buffers)?  frames_b > 0: `b` has that many frames (wm_embed_keys' K copies per input frame)
 bool descs_overlap(const PlaneDesc& a, const PlaneDesc& b, int rows, int cols, int frames, int frames_b = 0)
 {
-    auto extent = [&](const PlaneDesc& d, int f) {
-        size_t n = (size_t)(rows - 1) * d.pitch + cols;
-        if (d.channels > 1) n += (size_t)(d.channels - 1) * d.cstride;
-        if (f > 1) n += (size_t)(f - 1) * d.fstride;
-        return n * (d.dtype == WM_F32 ? 4 : 1);
-    };
-    const char* a0 = (const char*)a.p; const char* a1 = a0 + extent(a, frames);
-    const char* b0 = (const char*)b.p; const char* b1 = b0 + extent(b, frames_b > 0 ? frames_b : frames);
+    const char* a0 = (const char*)a.p; const char* a1 = a0 + plane_extent(a, rows, cols, frames);
+    const char* b0 = (const char*)b.p; const char* b1 = b0 + plane_extent(b, rows, cols, frames_b > 0 ? frames_b : frames);
     return a0 < b1 && b0 < a1;
 }
 
@@ -701,35 +742,27 @@ bool descs_overlap(const PlaneDesc& a, const PlaneDesc& b, int rows, int cols, i
 void invalidate_handovers(wm_ctx* ctx, const PlaneDesc& written, int frames)
 {
     if (!written.p) return;
-    for (auto& t : ctx->slots) {
-        if (!t.ho.valid || t.last_out_frames == 0) continue;
-        auto extent = [&](const PlaneDesc& d, int f) {
-            size_t n = (size_t)(ctx->rows - 1) * d.pitch + ctx->cols;
-            if (d.channels > 1) n += (size_t)(d.channels - 1) * d.cstride;
-            if (f > 1) n += (size_t)(f - 1) * d.fstride;
-            return n * (d.dtype == WM_F32 ? 4 : 1);
-        };
-        const char* a0 = (const char*)t.last_out.p; const char* a1 = a0 + extent(t.last_out, t.last_out_frames);
-        const char* b0 = (const char*)written.p; const char* b1 = b0 + extent(written, frames);
-        if (a0 < b1 && b0 < a1) t.ho.valid = false;
-    }
+    for (auto& t : ctx->slots)
+        if (t.ho.valid && t.last_out_frames != 0 && descs_overlap(t.last_out, written, ctx->rows, ctx->cols, t.last_out_frames, frames)) t.ho.valid = false;
 }
 
 // a profiled sweep: while the scope is set, every kernel launched through WM_KLAUNCH draws its own start / stop event pair
 // (wm_kernels.hpp: the events are attached to the dispatch, so they bracket the kernel and nothing else); a sweep that is two
 // launches (aligned strips + generic remainder) counts as ONE call of its kernel with the two durations added
+constexpr int K_NONE = -1;  // a launch the profile leaves out (the band phases, the sweep of WM_HANDOVER_VERIFY)
 struct ProfScope {
     wm_ctx* ctx; int kid; hipStream_t st;
     LaunchProf lp;
+    bool on() const { return ctx->prof && kid != K_NONE; }
     ProfScope(wm_ctx* c, int k, hipStream_t s) : ctx(c), kid(k), st(s)
     {
-        if (!ctx->prof) return;
+        if (!on()) return;
         lp.get = &ProfScope::get; lp.owner = ctx;
         launch_prof_slot() = &lp;
     }
     ~ProfScope()
     {
-        if (!ctx->prof) return;
+        if (!on()) return;
         launch_prof_slot() = nullptr;
         for (int i = 0; i < lp.n; ++i) ctx->prof_recs.push_back({kid, lp.a[i], lp.b[i], i == 0});
     }
@@ -754,13 +787,34 @@ int prof_collect(wm_ctx* ctx)
     return WM_OK;
 }
 
-int get_slot(wm_ctx* ctx, int slot, Slot** out, bool* sync_after)
+// the slot a call names: check_slot, then slot_of.  WM_SLOT_SYNC is slot 0, and the call waits for its own result
+int slot_index(int slot) { return slot == WM_SLOT_SYNC ? 0 : slot; }
+int check_slot(wm_ctx* ctx, int slot)
 {
-    *sync_after = slot == WM_SLOT_SYNC;
-    const int idx = slot == WM_SLOT_SYNC ? 0 : slot;
-    if (idx < 0 || idx >= ctx->nslots) return fail(ctx, WM_ERR_BAD_ARG, "bad slot " + std::to_string(slot));
-    *out = &ctx->slots[idx];
+    if (slot_index(slot) < 0 || slot_index(slot) >= ctx->nslots) return fail(ctx, WM_ERR_BAD_ARG, "bad slot " + std::to_string(slot));
     return WM_OK;
+}
+Slot& slot_of(wm_ctx* ctx, int slot) { return ctx->slots[slot_index(slot)]; }
+
+int check_mask(wm_ctx* ctx, int mask)
+{
+    if (mask != WM_MASK_ME && mask != WM_MASK_NVF) return fail(ctx, WM_ERR_BAD_ARG, "bad mask type");
+    if (mask == WM_MASK_ME && ctx->p != 3) return fail(ctx, WM_ERR_BAD_P, "ME mask needs p == 3 (main.cpp:89)");
+    return WM_OK;
+}
+
+// may the sweeps address the context's W (or a key plane of its shape) as a buffer with 32-bit offsets?  (W is a dense f32
+// plane: 4-byte aligned rows suffice, vec_ok)
+int aligned_w_of(const wm_ctx* ctx) { return fits_32bit(ctx->rows, ctx->cols, WM_F32) ? 1 : 0; }
+
+// room for `records` more result records on the slot before its next wm_sync; noun: what multiplies the frames of a call with
+// several records per frame ("keys", "offsets"), nullptr for one record per frame
+int check_res_room(wm_ctx* ctx, const Slot& s, long long records, const char* noun = nullptr)
+{
+    if (s.res_used + records <= RES_CAP) return WM_OK;
+    std::string msg = "too many un-synced results on this slot";
+    if (noun) msg += std::string(" (frames x ") + noun + " count against " + std::to_string(RES_CAP) + ")";
+    return fail(ctx, WM_ERR_BUSY, msg);
 }
 
 // after the launches of one op: a failed launch may leave the sweep's last-block tickets half counted, so clear them
@@ -775,15 +829,42 @@ int launch_check(wm_ctx* ctx, Slot& s)
     return WM_OK;
 }
 
-// remember where to deliver the result records of one op (the kernels write them to mapped host memory)
-int push_pending(wm_ctx* ctx, Slot& s, int frames, float* value_out, int* status_out, float* coef_out)
+// ---- the sweeps' launches with the slot's scratch arrays filled in.  kid: the kernel the profile counts the launch as, K_NONE
+// for a launch it leaves out
+void sweep_gram(wm_ctx* ctx, Slot& s, int kid, const LaunchGeom& lg, int frames, const PlaneDesc& xd, double* totals = nullptr, const int* redo = nullptr)
 {
-    Pending pd;
-    pd.frames = frames; pd.res_off = s.res_used; pd.value_out = value_out; pd.status_out = status_out;
-    pd.coef_out = coef_out; pd.coef_off = s.res_used * 8;
-    s.res_used += frames;
-    s.pending.push_back(pd);
-    return WM_OK;
+    ProfScope ps(ctx, kid, s.stream);
+    launch_gram(s.stream, lg, frames, xd, s.d_gram, s.d_gramb, s.d_ticket, s.d_coef, s.d_status, totals ? totals : s.d_gramtot, redo);
+}
+// the stats sweep of the context's W (ME: behind the Gram sweep's solve); its fold tail leaves the strength records in `res`, the
+// embed scalars in s.d_scal and the raw totals in s.d_raw[0 .. frames)
+void sweep_stats(wm_ctx* ctx, Slot& s, bool profiled, const LaunchGeom& lg, int frames, int mask, const PlaneDesc& xd, OpResult* res)
+{
+    ProfScope ps(ctx, !profiled ? K_NONE : mask == WM_MASK_ME ? K_ME_STATS : K_NVF_STATS, s.stream);
+    unsigned* ticket = s.d_ticket + ctx->max_frames * TKS;
+    if (mask == WM_MASK_ME)
+        launch_me_stats(s.stream, lg, frames, xd, ctx->w->d_w, aligned_w_of(ctx), s.d_coef, s.d_status, s.d_pmax, s.d_pss, ticket, strip_tickets(ctx, s, 0), s.d_smax,
+                        s.d_sss, ctx->sF, sqrt_n(ctx), s.d_scal, res, s.d_raw);
+    else
+        launch_nvf_stats(s.stream, lg, frames, xd, ctx->w->d_w, aligned_w_of(ctx), ctx->p / 2, s.d_pss, ticket, strip_tickets(ctx, s, 0), s.d_sss, ctx->sF, sqrt_n(ctx),
+                         s.d_scal, res, s.d_raw);
+}
+// the detect sweep against the context's W; its fold tail leaves the scores in `res` and the raw sums in s.d_raw[max_frames ..)
+// (dc, mode: the checking detector of the checked hand-over and its redo launch, wm_kernels.hpp)
+void sweep_detect(wm_ctx* ctx, Slot& s, int kid, const LaunchGeom& lg, int frames, int mask, const PlaneDesc& xd, OpResult* res, const DigCheck* dc = nullptr,
+                  int mode = 0)
+{
+    ProfScope ps(ctx, kid, s.stream);
+    launch_detect(s.stream, lg, frames, mask, ctx->p / 2, xd, ctx->w->d_w, aligned_w_of(ctx), s.d_coef, s.d_status, s.d_pcorr, s.d_ticket + 2 * ctx->max_frames * TKS,
+                  strip_tickets(ctx, s, 1), s.d_scorr, res, s.d_raw + ctx->max_frames, dc, mode);
+}
+
+// remember where to deliver the result records of one op (the kernels write them to mapped host memory): frames * per_frame
+// records from s.res_used on; keep: an unsolvable frame leaves the caller's values as they are (the embeds)
+void push_pending(Slot& s, int frames, int per_frame, bool keep, float* value_out, int* status_out, float* coef_out)
+{
+    s.pending.push_back(Pending{frames, per_frame, keep, s.res_used, value_out, status_out, coef_out});
+    s.res_used += frames * per_frame;
 }
 
 // hand the result records of everything queued on the slot to the callers' pointers (the stream has completed)
@@ -791,24 +872,18 @@ int deliver(Slot& s)
 {
     int rc = WM_OK;
     for (auto& pd : s.pending) {
-        if (pd.nkeys > 0) {
-            // wm_detect_keys / wm_embed_keys: record f * nkeys + k; every key of a frame carries the frame's status
-            for (int f = 0; f < pd.frames; ++f) {
-                const int st = s.h_res[pd.res_off + f * pd.nkeys].status;
-                if (pd.status_out) pd.status_out[f] = st;
-                if (st != 0) rc = WM_UNSOLVABLE;
-                if (!pd.value_out || (st != 0 && pd.keep_value_when_unsolvable)) continue;
-                for (int k = 0; k < pd.nkeys; ++k) pd.value_out[f * pd.nkeys + k] = s.h_res[pd.res_off + f * pd.nkeys + k].value;
-            }
-            continue;
-        }
+        // record f * per_frame + k; every record of a frame carries the frame's status.  With one record per frame this is the
+        // plain loop over the frames: status, then the value unless an unsolvable embed keeps the caller's
         for (int f = 0; f < pd.frames; ++f) {
-            const OpResult& r = s.h_res[pd.res_off + f];
-            if (pd.status_out) pd.status_out[f] = r.status;
+            const OpResult* r = s.h_res + pd.res_off + f * pd.per_frame;
+            const int st = r[0].status;
+            if (pd.status_out) pd.status_out[f] = st;
+            if (st != 0) rc = WM_UNSOLVABLE;
             // unsolvable embed leaves `a` untouched (Watermark.cpp:164-165); detect delivers 0.0f (:246-247)
-            if (pd.value_out && !(r.status != 0 && pd.keep_value_when_unsolvable)) pd.value_out[f] = r.value;
-            if (r.status != 0) rc = WM_UNSOLVABLE;
+            if (!pd.value_out || (st != 0 && pd.keep_value_when_unsolvable)) continue;
+            for (int k = 0; k < pd.per_frame; ++k) pd.value_out[f * pd.per_frame + k] = r[k].value;
         }
+        // (mask-only ops, one record per frame: the coefficients lie beside the records)
         if (pd.coef_out) std::memcpy(pd.coef_out, s.h_coefres + (size_t)pd.res_off * 8, (size_t)pd.frames * 8 * sizeof(float));
     }
     s.pending.clear();
@@ -836,51 +911,12 @@ extern "C" {
 
 int wm_create(wm_ctx** out, int device, int rows, int cols, int p, float psnr, const float* w_rowmajor)
 {
-    if (!out) return WM_ERR_BAD_ARG;
-    *out = nullptr;
-    int rc = check_params(rows, cols, p, psnr);
-    if (rc != WM_OK) return rc;
-    if (!w_rowmajor) return WM_ERR_BAD_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return WM_ERR_NO_DEVICE;
-    if (device < 0 || device >= ndev) device = 0;  // main.cpp:73-78: invalid device -> default 0
-    std::unique_ptr<wm_ctx> ctx(new wm_ctx);
-    ctx->device = device; ctx->rows = rows; ctx->cols = cols; ctx->p = p; ctx->psnr = psnr;
-    ctx->sF = 255.0f / sqrtf(powf(10.0f, psnr / 10.0f));  // Watermark.cpp:22
-    if (const char* e = getenv("WM_FUSED")) ctx->fused_mode = e[0] == '0' ? 0 : 1;
-    if (hipSetDevice(device) != hipSuccess) return WM_ERR_NO_DEVICE;
-    rc = upload_w(ctx.get(), w_rowmajor);
-    if (rc != WM_OK) return rc;
-    rc = alloc_slots(ctx.get(), 2, 1);
-    if (rc != WM_OK) return rc;
-    *out = ctx.release();
-    return WM_OK;
+    return create_ctx(out, device, rows, cols, p, psnr, false, w_rowmajor, 0);
 }
 
 int wm_create_generated(wm_ctx** out, int device, int rows, int cols, int p, float psnr, uint32_t seed)
 {
-    if (!out) return WM_ERR_BAD_ARG;
-    *out = nullptr;
-    int rc = check_params(rows, cols, p, psnr);
-    if (rc != WM_OK) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return WM_ERR_NO_DEVICE;
-    if (device < 0 || device >= ndev) device = 0;
-    std::unique_ptr<wm_ctx> ctx(new wm_ctx);
-    ctx->device = device; ctx->rows = rows; ctx->cols = cols; ctx->p = p; ctx->psnr = psnr;
-    ctx->sF = 255.0f / sqrtf(powf(10.0f, psnr / 10.0f));  // Watermark.cpp:22
-    if (const char* e = getenv("WM_FUSED")) ctx->fused_mode = e[0] == '0' ? 0 : 1;
-    if (hipSetDevice(device) != hipSuccess) return WM_ERR_NO_DEVICE;
-    auto ws = std::make_shared<WShared>();
-    ws->n = (size_t)rows * cols;
-    if (hipMalloc((void**)&ws->d_w, ws->n * sizeof(float)) != hipSuccess) return WM_ERR_ALLOC;
-    launch_gen_w(nullptr, ws->d_w, rows, cols, seed);
-    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return WM_ERR_RUNTIME;
-    ctx->w = ws;
-    rc = alloc_slots(ctx.get(), 2, 1);
-    if (rc != WM_OK) return rc;
-    *out = ctx.release();
-    return WM_OK;
+    return create_ctx(out, device, rows, cols, p, psnr, true, nullptr, seed);
 }
 
 int wm_create_from_file(wm_ctx** out, int device, int rows, int cols, int p, float psnr, const char* w_path)
@@ -1062,8 +1098,7 @@ static int fused_wait(wm_ctx* ctx, Slot& s, const OpResult* hres, bool need_stre
     const bool arrived = poll_record(hres, FUSED_PENDING, s.stream, got);
     if (need_stream || !arrived) {
         HIPCHK(ctx, hipStreamSynchronize(s.stream));
-        const uint64_t v = reinterpret_cast<const std::atomic<uint64_t>*>(hres)->load(std::memory_order_acquire);
-        std::memcpy(got, &v, 8);
+        *got = load_record(hres);
     }
     return WM_OK;
 }
@@ -1092,49 +1127,87 @@ static int prep_input(wm_ctx* ctx, Slot& s, const wm_plane* in, PlaneDesc* xd)
     return WM_OK;
 }
 
+// the front half of a call that sweeps one grey input plane: the plane's checks, room for its result records (per_frame of them
+// for each frame, 0: the call queues none), the context's device, the plane staged / resolved and the launch geometry
+static int open_input(wm_ctx* ctx, Slot& s, const wm_plane* img, const char* what, int mask, long long per_frame, const char* noun, PlaneDesc* xd, LaunchGeom* lg)
+{
+    int rc;
+    if ((rc = check_plane(ctx, img, 0, false, what, true)) != WM_OK) return rc;
+    if ((rc = check_res_room(ctx, s, img->frames * per_frame, noun)) != WM_OK) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if ((rc = prep_input(ctx, s, img, xd)) != WM_OK) return rc;
+    return geom_checked(ctx, img->frames, mask, lg);
+}
+
+// the base plane of an embed, resolved like the input; a host base that IS the input plane (`xd`: prep_input's result) is not
+// staged a second time
+static int prep_base(wm_ctx* ctx, Slot& s, const wm_plane* in_gray, const wm_plane* base, const PlaneDesc& xd, PlaneDesc* bd)
+{
+    const bool base_is_in = base->data == in_gray->data && base->mem == in_gray->mem && base->mem != WM_MEM_SLOT_OUT && base->channels == 1 &&
+                            base->dtype == in_gray->dtype && base->pitch == in_gray->pitch;
+    if (base->mem != WM_MEM_HOST) *bd = desc_device(base);
+    else if (base_is_in) *bd = xd;
+    else {
+        const Staged st = staged_layout(base);
+        int rc = ensure(ctx, &s.st_base, &s.st_base_bytes, st.bytes);
+        if (rc != WM_OK) return rc;
+        if ((rc = stage_in(ctx, s, base, s.st_base, st)) != WM_OK) return rc;
+        *bd = st.d; bd->p = s.st_base;
+    }
+    return WM_OK;
+}
+
+// the output plane of an embed: a host plane is written to the slot's staging buffer (layout in *st, copied out by stage_out)
+static int prep_out(wm_ctx* ctx, Slot& s, const wm_plane* out, PlaneDesc* od, Staged* st)
+{
+    if (out->mem != WM_MEM_HOST) { *od = desc_device(out); return WM_OK; }
+    *st = staged_layout(out);
+    const int rc = ensure(ctx, &s.st_out, &s.st_out_bytes, st->bytes);
+    if (rc != WM_OK) return rc;
+    *od = st->d; od->p = s.st_out;
+    return WM_OK;
+}
+
+// a fused embed issued output stores over the call's own input or base and their completion was not observed
+static int fail_partly_watermarked(wm_ctx* ctx)
+{
+    return fail(ctx, WM_ERR_RUNTIME, "fused embed: the completion of the output stores was not observed and the output overlaps the input "
+                                     "or the base (in-place call): the frame may be partly watermarked and cannot be re-run");
+}
+
 int wm_embed(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* base, const wm_plane* out, float* a_out,
              int* status_out, int slot)
 {
     if (!ctx) return WM_ERR_BAD_ARG;
-    if (mask != WM_MASK_ME && mask != WM_MASK_NVF) return fail(ctx, WM_ERR_BAD_ARG, "bad mask type");
-    if (mask == WM_MASK_ME && ctx->p != 3) return fail(ctx, WM_ERR_BAD_P, "ME mask needs p == 3 (main.cpp:89)");
-    Slot* sp; bool sync_after;
-    int rc = get_slot(ctx, slot, &sp, &sync_after);
+    int rc = check_mask(ctx, mask);
     if (rc != WM_OK) return rc;
-    Slot& s = *sp;
+    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
+    const bool sync_after = slot == WM_SLOT_SYNC;
     if ((rc = check_plane(ctx, in_gray, 0, false, "in_gray", true)) != WM_OK) return rc;
     const int frames = in_gray->frames;
     if ((rc = check_plane(ctx, base, frames, true, "base")) != WM_OK) return rc;
     if ((rc = check_plane(ctx, out, frames, true, "out")) != WM_OK) return rc;
     if (out->channels != base->channels || out->dtype != base->dtype) return fail(ctx, WM_ERR_BAD_ARG, "out must have the shape and dtype of base");
     if (in_gray->dtype != base->dtype) return fail(ctx, WM_ERR_BAD_ARG, "in_gray and base must have the same dtype (the reference converts whole frames, main.cpp:355-357)");
-    if (s.res_used + frames > RES_CAP) return fail(ctx, WM_ERR_BUSY, "too many un-synced results on this slot");
+    if ((rc = check_res_room(ctx, s, frames)) != WM_OK) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
 
     PlaneDesc xd, bd, od;
-    if ((rc = prep_input(ctx, s, in_gray, &xd)) != WM_OK) return rc;
     Staged st_out_l;
-    const bool base_is_in = base->data == in_gray->data && base->mem == in_gray->mem && base->mem != WM_MEM_SLOT_OUT && base->channels == 1 &&
-                            base->dtype == in_gray->dtype && base->pitch == in_gray->pitch;
-    if (base->mem == WM_MEM_HOST) {
-        if (base_is_in) { bd = xd; }
-        else {
-            Staged st = staged_layout(base);
-            if ((rc = ensure(ctx, &s.st_base, &s.st_base_bytes, st.bytes)) != WM_OK) return rc;
-            if ((rc = stage_in(ctx, s, base, s.st_base, st)) != WM_OK) return rc;
-            bd = st.d; bd.p = s.st_base;
-        }
-    } else bd = desc_device(base);
-    if (out->mem == WM_MEM_HOST) {
-        st_out_l = staged_layout(out);
-        if ((rc = ensure(ctx, &s.st_out, &s.st_out_bytes, st_out_l.bytes)) != WM_OK) return rc;
-        od = st_out_l.d; od.p = s.st_out;
-    } else od = desc_device(out);
+    if ((rc = prep_input(ctx, s, in_gray, &xd)) != WM_OK) return rc;
+    if ((rc = prep_base(ctx, s, in_gray, base, xd, &bd)) != WM_OK) return rc;
+    if ((rc = prep_out(ctx, s, out, &od, &st_out_l)) != WM_OK) return rc;
     // in place = the output overlaps the plane the stencil reads, judged on the RESOLVED addresses (a WM_MEM_SLOT_OUT input is
     // the slot's last output buffer, which the caller may well pass as `out` again)
     const bool inplace = descs_overlap(xd, od, ctx->rows, ctx->cols, frames);
     s.ho.valid = false;  // (whatever this call writes replaces the plane a hand-over described)
     invalidate_handovers(ctx, od, frames);  // (... and that of any other slot whose last output this call overwrites)
+    // the call's result: `out` becomes the slot's last output, the strengths are queued (an unsolvable frame keeps the caller's)
+    auto queue_result = [&]() {
+        s.last_out = od; s.last_out_frames = frames; s.last_out_dtype = out->dtype;
+        push_pending(s, frames, 1, true, a_out, status_out, nullptr);
+    };
 
     // one image per synchronous call (the reference's call pattern): ONE launch with the frame's tiles resident in LDS
     // (wm_k_fused.hip).  Its y stores come after two chip-wide hand-offs behind every read of x, so an in-place call
@@ -1165,9 +1238,7 @@ int wm_embed(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* bas
                 // the detector's launch follows at once on the same stream; its record completes both (wm_detect's fused branch)
                 s.pair.armed = true; s.pair.res_index = s.res_used; s.pair.host_out = out->mem == WM_MEM_HOST;
                 s.pair.out_overlaps_inputs = inplace || descs_overlap(bd, od, ctx->rows, ctx->cols, frames);
-                s.last_out = od; s.last_out_frames = frames; s.last_out_dtype = out->dtype;
-                if ((rc = push_pending(ctx, s, frames, a_out, status_out, nullptr)) != WM_OK) return rc;
-                s.pending.back().keep_value_when_unsolvable = true;
+                queue_result();
                 return WM_OK;
             }
             // device output: the kernel writes y through to memory and reports last, so the record is the completion
@@ -1176,9 +1247,7 @@ int wm_embed(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* bas
             if ((rc = fused_wait(ctx, s, hres, out->mem == WM_MEM_HOST, &got)) != WM_OK) return rc;
             if (got.status != FUSED_PENDING && got.status != FUSED_INCOMPLETE) {
                 ctx->fused_backoff = 0;
-                s.last_out = od; s.last_out_frames = frames; s.last_out_dtype = out->dtype;
-                if ((rc = push_pending(ctx, s, frames, a_out, status_out, nullptr)) != WM_OK) return rc;
-                s.pending.back().keep_value_when_unsolvable = true;
+                queue_result();
                 return deliver(s);  // the record has arrived
             }
             // PENDING: a hand-off timed out before any output store (the workgroups were not all resident): nothing was
@@ -1188,9 +1257,7 @@ int wm_embed(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* bas
             if ((rc = fused_failed(ctx, s)) != WM_OK) return rc;
             if (got.status == FUSED_INCOMPLETE) {
                 HIPCHK(ctx, hipStreamSynchronize(s.stream));
-                if (inplace || descs_overlap(bd, od, ctx->rows, ctx->cols, frames))
-                    return fail(ctx, WM_ERR_RUNTIME, "fused embed: the completion of the output stores was not observed and the output overlaps the input "
-                                                     "or the base (in-place call): the frame may be partly watermarked and cannot be re-run");
+                if (inplace || descs_overlap(bd, od, ctx->rows, ctx->cols, frames)) return fail_partly_watermarked(ctx);
             }
         }
     }
@@ -1212,8 +1279,7 @@ int wm_embed(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* bas
     LaunchGeom lg;
     if ((rc = geom_checked(ctx, frames, mask, &lg)) != WM_OK) return rc;
     const float* W = ctx->w->d_w;
-    const int aligned_w = fits_32bit(ctx->rows, ctx->cols, WM_F32) ? 1 : 0  /* (W is a dense f32 plane: 4-byte aligned rows suffice, vec_ok) */;
-    const int pad = ctx->p / 2;
+    const int aligned_w = aligned_w_of(ctx);
     OpResult* res = s.d_res + s.res_used;
     // Gram hand-over (wm_set_handover): k_embed also leaves the tile-internal lag sums of y for a detector that reads this
     // output as WM_MEM_SLOT_OUT (grey f32 planes on the aligned path; launch_embed says whether it applied)
@@ -1227,20 +1293,17 @@ int wm_embed(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* bas
     const HandOver* hop = want_ho && ho_ready(s) && out->channels == 1 && ho.stride <= ho_stride_max(ctx) &&
                                   !descs_overlap(bd, od, ctx->rows, ctx->cols, frames) ? &ho : nullptr;
     bool handed = false;
-    if (mask == WM_MASK_ME) {
-        { ProfScope ps(ctx, K_GRAM, s.stream); launch_gram(s.stream, lg, frames, xd, s.d_gram, s.d_gramb, s.d_ticket, s.d_coef, s.d_status, s.d_gramtot); }
-        { ProfScope ps(ctx, K_ME_STATS, s.stream); launch_me_stats(s.stream, lg, frames, xd, W, aligned_w, s.d_coef, s.d_status, s.d_pmax, s.d_pss, s.d_ticket + ctx->max_frames * TKS, strip_tickets(ctx, s, 0), s.d_smax, s.d_sss, ctx->sF, sqrt_n(ctx), s.d_scal, res, s.d_raw); }
-        { ProfScope ps(ctx, K_EMBED, s.stream); handed = launch_embed(s.stream, lg, frames, 0, 1, xd, W, aligned_w, bd, od, s.d_coef, s.d_status, s.d_scal, hop); }
-    } else {
-        { ProfScope ps(ctx, K_NVF_STATS, s.stream); launch_nvf_stats(s.stream, lg, frames, xd, W, aligned_w, pad, s.d_pss, s.d_ticket + ctx->max_frames * TKS, strip_tickets(ctx, s, 0), s.d_sss, ctx->sF, sqrt_n(ctx), s.d_scal, res, s.d_raw); }
-        { ProfScope ps(ctx, K_EMBED, s.stream); handed = launch_embed(s.stream, lg, frames, 1, pad, xd, W, aligned_w, bd, od, nullptr, nullptr, s.d_scal, hop); }
+    if (mask == WM_MASK_ME) sweep_gram(ctx, s, K_GRAM, lg, frames, xd);
+    sweep_stats(ctx, s, true, lg, frames, mask, xd, res);
+    {
+        ProfScope ps(ctx, K_EMBED, s.stream);
+        if (mask == WM_MASK_ME) handed = launch_embed(s.stream, lg, frames, 0, 1, xd, W, aligned_w, bd, od, s.d_coef, s.d_status, s.d_scal, hop);
+        else handed = launch_embed(s.stream, lg, frames, 1, ctx->p / 2, xd, W, aligned_w, bd, od, nullptr, nullptr, s.d_scal, hop);
     }
     if (handed) { s.ho.valid = true; s.ho.promised = promised; s.ho.used = false; s.ho.lg = lg; s.ho.frames = frames; s.ho.stride = ho.stride; }
     if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
     if (out->mem == WM_MEM_HOST && (rc = stage_out(ctx, s, out, s.st_out, st_out_l)) != WM_OK) return rc;
-    s.last_out = od; s.last_out_frames = frames; s.last_out_dtype = out->dtype;
-    if ((rc = push_pending(ctx, s, frames, a_out, status_out, nullptr)) != WM_OK) return rc;
-    s.pending.back().keep_value_when_unsolvable = true;
+    queue_result();
     return sync_after && !ctx->pair_mode ? do_sync(ctx, s) : WM_OK;  // (wm_embed_detect: the detector's wait covers the embed)
 }
 
@@ -1255,12 +1318,12 @@ static void gram_from_handover(wm_ctx* ctx, Slot& s, int frames, const PlaneDesc
 
 // does this detector input take the checked hand-over (wm.h wm_detect)?  The plane the slot's last embed wrote -- the same
 // descriptor --, sums nobody has used yet, and the checking detector's path (f32, ME, overlapped aligned strips)
-static bool checked_handover_applies(const wm_ctx* ctx, const Slot& s, const LaunchGeom& lg, int frames, int mask, const PlaneDesc& xd, int aligned_w)
+static bool checked_handover_applies(const wm_ctx* ctx, const Slot& s, const LaunchGeom& lg, int frames, int mask, const PlaneDesc& xd)
 {
     const PlaneDesc& o = s.last_out;
     return ctx->checked_handover && s.ho.valid && !s.ho.used && ho_ready(s) && ctx->band_hi == 0 && s.ho.frames == frames &&
            s.last_out_frames == frames && xd.p == o.p && xd.pitch == o.pitch && xd.fstride == o.fstride && xd.dtype == o.dtype &&
-           s.last_out_dtype == WM_F32 && xd.channels == 1 && detect_checkable(lg, mask, ctx->p / 2, xd, aligned_w);
+           s.last_out_dtype == WM_F32 && xd.channels == 1 && detect_checkable(lg, mask, ctx->p / 2, xd, aligned_w_of(ctx));
 }
 
 // the Gram sweep of a detector-side call: k_gram over the plane -- or, when the plane is the slot's last embed output and that
@@ -1277,7 +1340,7 @@ static int gram_sweep(wm_ctx* ctx, Slot& s, const LaunchGeom& lg, int frames, co
         // (<= 1e-14 relative, tests/test_gpu_handover.py) unless a single pixel changed
         std::vector<double> t_ho((size_t)frames * NGRAM), t_now((size_t)frames * NGRAM);
         HIPCHK(ctx, hipMemcpyAsync(t_ho.data(), s.d_gramtot, t_ho.size() * sizeof(double), hipMemcpyDeviceToHost, s.stream));
-        launch_gram(s.stream, lg, frames, xd, s.d_gram, s.d_gramb, s.d_ticket, s.d_coef, s.d_status, s.d_gramtot);
+        sweep_gram(ctx, s, K_NONE, lg, frames, xd);
         HIPCHK(ctx, hipMemcpyAsync(t_now.data(), s.d_gramtot, t_now.size() * sizeof(double), hipMemcpyDeviceToHost, s.stream));
         HIPCHK(ctx, hipStreamSynchronize(s.stream));
         for (int f = 0; f < frames; ++f)
@@ -1294,23 +1357,21 @@ static int gram_sweep(wm_ctx* ctx, Slot& s, const LaunchGeom& lg, int frames, co
             }
         return WM_OK;
     }
-    ProfScope ps(ctx, K_GRAM, s.stream);
-    launch_gram(s.stream, lg, frames, xd, s.d_gram, s.d_gramb, s.d_ticket, s.d_coef, s.d_status, s.d_gramtot);
+    sweep_gram(ctx, s, K_GRAM, lg, frames, xd);
     return WM_OK;
 }
 
 int wm_detect(wm_ctx* ctx, int mask, const wm_plane* img, float* corr_out, int* status_out, int slot)
 {
     if (!ctx) return WM_ERR_BAD_ARG;
-    if (mask != WM_MASK_ME && mask != WM_MASK_NVF) return fail(ctx, WM_ERR_BAD_ARG, "bad mask type");
-    if (ctx->p != 3 && mask == WM_MASK_ME) return fail(ctx, WM_ERR_BAD_P, "ME mask needs p == 3 (main.cpp:89)");
-    Slot* sp; bool sync_after;
-    int rc = get_slot(ctx, slot, &sp, &sync_after);
+    int rc = check_mask(ctx, mask);
     if (rc != WM_OK) return rc;
-    Slot& s = *sp;
+    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
+    const bool sync_after = slot == WM_SLOT_SYNC;
     if ((rc = check_plane(ctx, img, 0, false, "image", true)) != WM_OK) return rc;
     const int frames = img->frames;
-    if (s.res_used + frames > RES_CAP) return fail(ctx, WM_ERR_BUSY, "too many un-synced results on this slot");
+    if ((rc = check_res_room(ctx, s, frames)) != WM_OK) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     PlaneDesc xd;
     if ((rc = prep_input(ctx, s, img, &xd)) != WM_OK) return rc;
@@ -1342,9 +1403,7 @@ int wm_detect(wm_ctx* ctx, int mask, const wm_plane* img, float* corr_out, int* 
             // the stream is in order: with the detector's record in (or the stream drained), the embed's record is final
             s.pair.armed = false;
             if (got.status == FUSED_PENDING) HIPCHK(ctx, hipStreamSynchronize(s.stream));
-            OpResult ge;
-            const uint64_t v = reinterpret_cast<const std::atomic<uint64_t>*>(s.h_res + s.pair.res_index)->load(std::memory_order_acquire);
-            std::memcpy(&ge, &v, 8);
+            const OpResult ge = load_record(s.h_res + s.pair.res_index);
             if (ge.status == FUSED_PENDING || ge.status == FUSED_INCOMPLETE) {
                 // the embed did not complete: forget its queued result, back off, and let wm_embed_detect redo both on the
                 // sweeps -- unless output stores went out over the call's own input (wm_embed's rule).  (A completed embed
@@ -1353,16 +1412,14 @@ int wm_detect(wm_ctx* ctx, int mask, const wm_plane* img, float* corr_out, int* 
                 s.res_used = s.pair.res_index;
                 s.last_out_frames = 0;
                 if ((rc = fused_failed(ctx, s)) != WM_OK) return rc;
-                if (ge.status == FUSED_INCOMPLETE && s.pair.out_overlaps_inputs)
-                    return fail(ctx, WM_ERR_RUNTIME, "fused embed: the completion of the output stores was not observed and the output overlaps the input "
-                                                     "or the base (in-place call): the frame may be partly watermarked and cannot be re-run");
+                if (ge.status == FUSED_INCOMPLETE && s.pair.out_overlaps_inputs) return fail_partly_watermarked(ctx);
                 return PAIR_RETRY;
             }
         }
         if (lrc == 0) {
             if (got.status != FUSED_PENDING) {
                 ctx->fused_backoff = 0;
-                if ((rc = push_pending(ctx, s, frames, corr_out, status_out, nullptr)) != WM_OK) return rc;
+                push_pending(s, frames, 1, false, corr_out, status_out, nullptr);
                 return deliver(s);  // the record has arrived
             }
             if ((rc = fused_failed(ctx, s)) != WM_OK) return rc;  // (a detector writes nothing: the sweeps can always take the call)
@@ -1371,26 +1428,23 @@ int wm_detect(wm_ctx* ctx, int mask, const wm_plane* img, float* corr_out, int* 
     guard.reset();
     LaunchGeom lg;
     if ((rc = geom_checked(ctx, frames, mask, &lg)) != WM_OK) return rc;
-    const float* W = ctx->w->d_w;
-    const int aligned_w = fits_32bit(ctx->rows, ctx->cols, WM_F32) ? 1 : 0  /* (W is a dense f32 plane: 4-byte aligned rows suffice, vec_ok) */;
     OpResult* res = s.d_res + s.res_used;
-    unsigned* dticket = s.d_ticket + 2 * ctx->max_frames * TKS;
     // (a WM_MEM_SLOT_OUT plane under wm_set_handover keeps the promised hand-over of gram_sweep)
-    if (!(img->mem == WM_MEM_SLOT_OUT && s.ho.promised) && checked_handover_applies(ctx, s, lg, frames, mask, xd, aligned_w)) {
+    if (!(img->mem == WM_MEM_SLOT_OUT && s.ho.promised) && checked_handover_applies(ctx, s, lg, frames, mask, xd)) {
         // checked hand-over: the Gram matrix from the embed's sums, the detector checks the plane against the embed's digest, and
         // the frames it does not trust are redone by the ordinary sweeps (predicated on the device: empty launches otherwise)
         s.ho.used = true;
         const DigCheck dc{s.d_pdig, s.d_sdig, handover_of(ctx, s, s.ho.stride).fdig, s.d_redo, s.d_hocnt};
         { ProfScope ps(ctx, K_GRAM_HO_CHECKED, s.stream); gram_from_handover(ctx, s, frames, xd); }
-        { ProfScope ps(ctx, K_DETECT, s.stream); launch_detect(s.stream, lg, frames, mask, ctx->p / 2, xd, W, aligned_w, s.d_coef, s.d_status, s.d_pcorr, dticket, strip_tickets(ctx, s, 1), s.d_scorr, res, s.d_raw + ctx->max_frames, &dc, 1); }
-        { ProfScope ps(ctx, K_GRAM_REDO, s.stream); launch_gram(s.stream, lg, frames, xd, s.d_gram, s.d_gramb, s.d_ticket, s.d_coef, s.d_status, s.d_gramtot, s.d_redo); }
-        { ProfScope ps(ctx, K_DETECT_REDO, s.stream); launch_detect(s.stream, lg, frames, mask, ctx->p / 2, xd, W, aligned_w, s.d_coef, s.d_status, s.d_pcorr, dticket, strip_tickets(ctx, s, 1), s.d_scorr, res, s.d_raw + ctx->max_frames, &dc, 2); }
+        sweep_detect(ctx, s, K_DETECT, lg, frames, mask, xd, res, &dc, 1);
+        sweep_gram(ctx, s, K_GRAM_REDO, lg, frames, xd, nullptr, s.d_redo);
+        sweep_detect(ctx, s, K_DETECT_REDO, lg, frames, mask, xd, res, &dc, 2);
     } else {
         if ((rc = gram_sweep(ctx, s, lg, frames, xd, img)) != WM_OK) return rc;
-        { ProfScope ps(ctx, K_DETECT, s.stream); launch_detect(s.stream, lg, frames, mask, ctx->p / 2, xd, W, aligned_w, s.d_coef, s.d_status, s.d_pcorr, dticket, strip_tickets(ctx, s, 1), s.d_scorr, res, s.d_raw + ctx->max_frames); }
+        sweep_detect(ctx, s, K_DETECT, lg, frames, mask, xd, res);
     }
     if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
-    if ((rc = push_pending(ctx, s, frames, corr_out, status_out, nullptr)) != WM_OK) return rc;
+    push_pending(s, frames, 1, false, corr_out, status_out, nullptr);
     return sync_after ? do_sync(ctx, s) : WM_OK;
 }
 
@@ -1399,10 +1453,10 @@ int wm_embed_detect(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_pla
 {
     if (!ctx || !out) return WM_ERR_BAD_ARG;
     if (out->channels != 1) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_detect: grey output only (the detector reads the plane the embed wrote)");
-    Slot* sp; bool sync_after;
-    int rc = get_slot(ctx, slot, &sp, &sync_after);
+    int rc = check_slot(ctx, slot);
     if (rc != WM_OK) return rc;
-    Slot& s = *sp;
+    Slot& s = slot_of(ctx, slot);
+    const bool sync_after = slot == WM_SLOT_SYNC;
     // the detector's input: the device copy of what the embed writes (WM_MEM_SLOT_OUT) -- so on the sweeps the embed can hand
     // its output's lag sums over whether or not wm_set_handover is on (the detector's Gram sweep is not run)
     wm_plane slot_plane = *out;
@@ -1458,10 +1512,8 @@ int wm_keys_create(wm_keys** out, int device, int rows, int cols, int nkeys)
     if (!out) return WM_ERR_BAD_ARG;
     *out = nullptr;
     if (rows < 1 || cols < 1 || rows > 32768 || cols > 32768 || nkeys < 1 || nkeys > WM_KEYS_MAX) return WM_ERR_BAD_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return WM_ERR_NO_DEVICE;
-    if (device < 0 || device >= ndev) device = 0;  // (wm_create's rule, main.cpp:73-78)
-    if (hipSetDevice(device) != hipSuccess) return WM_ERR_NO_DEVICE;
+    const int rc = choose_device(&device);
+    if (rc != WM_OK) return rc;
     std::unique_ptr<wm_keys> k(new wm_keys);
     k->device = device; k->rows = rows; k->cols = cols; k->nkeys = nkeys;
     const size_t bytes = (size_t)nkeys * rows * cols * sizeof(float);
@@ -1512,51 +1564,62 @@ int wm_keys_generate(wm_keys* keys, int k, uint32_t seed)
     return WM_OK;
 }
 
-int wm_detect_keys(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* keys, float* corr_out, int* status_out, int slot)
+// a key bank fits a call: it lives on the engine's device and its planes have the engine's shape (exact) or are at least as
+// large (wm_detect_offsets, whose windows move inside them)
+static int check_bank(wm_ctx* ctx, const wm_keys* keys, const char* who, bool exact)
 {
-    if (!ctx) return WM_ERR_BAD_ARG;
-    if (mask != WM_MASK_ME && mask != WM_MASK_NVF) return fail(ctx, WM_ERR_BAD_ARG, "bad mask type");
-    if (ctx->p != 3 && mask == WM_MASK_ME) return fail(ctx, WM_ERR_BAD_P, "ME mask needs p == 3 (main.cpp:89)");
-    if (!keys || !corr_out) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_keys: null keys or corr_out");
-    if (keys->device != ctx->device || keys->rows != ctx->rows || keys->cols != ctx->cols)
-        return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_keys: the key bank is " + std::to_string(keys->rows) + "x" + std::to_string(keys->cols) + " on device " +
-                                             std::to_string(keys->device) + ", the engine " + std::to_string(ctx->rows) + "x" + std::to_string(ctx->cols) +
-                                             " on device " + std::to_string(ctx->device));
-    if (ctx->band_hi > 0) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_keys: not in band mode");
-    Slot* sp; bool sync_after;
-    int rc = get_slot(ctx, slot, &sp, &sync_after);
+    const bool fits = exact ? keys->rows == ctx->rows && keys->cols == ctx->cols : keys->rows >= ctx->rows && keys->cols >= ctx->cols;
+    if (keys->device == ctx->device && fits) return WM_OK;
+    return fail(ctx, WM_ERR_BAD_ARG, std::string(who) + ": the key bank is " + std::to_string(keys->rows) + "x" + std::to_string(keys->cols) + " on device " +
+                                         std::to_string(keys->device) + ", the engine " + std::to_string(ctx->rows) + "x" + std::to_string(ctx->cols) +
+                                         " on device " + std::to_string(ctx->device) + (exact ? "" : " (the bank must be at least as large)"));
+}
+
+// detectWatermark of every frame with `count` scores per frame (wm_detect_keys: the keys of a bank; wm_detect_offsets: the windows
+// of one key): wm_detect's input, slot and Gram handling on the sweeps, the records [frames][count] delivered by wm_sync.
+// launch(s, lg, frames, xd, part, rstride, res): the sweep behind the solve, != 0 when its geometry does not fit
+extern "C++" {  // (a template cannot have C linkage)
+template <class Launch>
+static int detect_bank(wm_ctx* ctx, int mask, const wm_plane* img, long long count, const char* noun, const char* who, int kid, float* corr_out, int* status_out,
+                       int slot, Launch launch)
+{
+    int rc = check_slot(ctx, slot);
     if (rc != WM_OK) return rc;
-    Slot& s = *sp;
-    if ((rc = check_plane(ctx, img, 0, false, "image", true)) != WM_OK) return rc;
-    const int frames = img->frames;
-    const int nkeys = keys->nkeys;
-    if ((long long)s.res_used + (long long)frames * nkeys > RES_CAP)
-        return fail(ctx, WM_ERR_BUSY, "too many un-synced results on this slot (frames x keys count against " + std::to_string(RES_CAP) + ")");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Slot& s = slot_of(ctx, slot);
     PlaneDesc xd;
-    if ((rc = prep_input(ctx, s, img, &xd)) != WM_OK) return rc;
     LaunchGeom lg;
-    if ((rc = geom_checked(ctx, frames, mask, &lg)) != WM_OK) return rc;
-    // partial records: [frames][nkeys][rstride][2] + [frames][rstride]
+    if ((rc = open_input(ctx, s, img, "image", mask, count, noun, &xd, &lg)) != WM_OK) return rc;
+    const int frames = img->frames;
+    // partial records: [frames][count][rstride][2] + [frames][rstride] (one scratch for both calls: one stream, in order)
     const int rstride = std::max(ctx->max_nblk, ctx->max_nrec);
-    const size_t need = (size_t)frames * (2 * (size_t)nkeys + 1) * rstride * sizeof(double);
+    const size_t need = (size_t)frames * (2 * (size_t)count + 1) * rstride * sizeof(double);
     if ((rc = ensure(ctx, &s.keys_part, &s.keys_part_bytes, need)) != WM_OK) return rc;
-    const int aligned_w = fits_32bit(ctx->rows, ctx->cols, WM_F32) ? 1 : 0;
-    const long long kstride = (long long)ctx->rows * ctx->cols;
-    OpResult* res = s.d_res + s.res_used;
     // the image side is wm_detect's: the Gram sweep (or the hand-over of the slot's last embed) and the solve
     if ((rc = gram_sweep(ctx, s, lg, frames, xd, img)) != WM_OK) return rc;
     {
-        ProfScope ps(ctx, K_DETECT_KEYS, s.stream);
-        if (launch_detect_keys(s.stream, lg, frames, mask, ctx->p / 2, xd, keys->d, kstride, nkeys, aligned_w, s.d_coef, s.d_status,
-                               (double*)s.keys_part, rstride, res) != 0)
-            return fail(ctx, WM_ERR_RUNTIME, "wm_detect_keys: geometry exceeds the record arrays");
+        ProfScope ps(ctx, kid, s.stream);
+        if (launch(s, lg, frames, xd, (double*)s.keys_part, rstride, s.d_res + s.res_used) != 0)
+            return fail(ctx, WM_ERR_RUNTIME, std::string(who) + ": geometry exceeds the record arrays");
     }
     if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
-    if ((rc = push_pending(ctx, s, frames * nkeys, corr_out, status_out, nullptr)) != WM_OK) return rc;
-    s.pending.back().frames = frames;
-    s.pending.back().nkeys = nkeys;
-    return sync_after ? do_sync(ctx, s) : WM_OK;
+    push_pending(s, frames, (int)count, false, corr_out, status_out, nullptr);
+    return slot == WM_SLOT_SYNC ? do_sync(ctx, s) : WM_OK;
+}
+}  // extern "C++"
+
+int wm_detect_keys(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* keys, float* corr_out, int* status_out, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    int rc = check_mask(ctx, mask);
+    if (rc != WM_OK) return rc;
+    if (!keys || !corr_out) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_keys: null keys or corr_out");
+    if ((rc = check_bank(ctx, keys, "wm_detect_keys", true)) != WM_OK) return rc;
+    if (ctx->band_hi > 0) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_keys: not in band mode");
+    return detect_bank(ctx, mask, img, keys->nkeys, "keys", "wm_detect_keys", K_DETECT_KEYS, corr_out, status_out, slot,
+                       [&](Slot& s, const LaunchGeom& lg, int frames, const PlaneDesc& xd, double* part, int rstride, OpResult* res) {
+                           return launch_detect_keys(s.stream, lg, frames, mask, ctx->p / 2, xd, keys->d, (long long)ctx->rows * ctx->cols, keys->nkeys,
+                                                     aligned_w_of(ctx), s.d_coef, s.d_status, part, rstride, res);
+                       });
 }
 
 // every window of the rectangle lies inside the key plane (no device needed: wm_detect_offsets' own check)
@@ -1570,60 +1633,30 @@ int wm_offsets_check(int rows, int cols, int key_rows, int key_cols, int oy0, in
 
 int wm_detect_offsets_group(void) { return detect_offsets_group(); }
 
-// detectWatermark of every frame against the windows of ONE key at a rectangle of offsets: wm_detect_keys' input, slot and
-// result handling, k_detect_offsets as the sweep
+// detectWatermark of every frame against the windows of ONE key at a rectangle of offsets: k_detect_offsets as detect_bank's sweep
 int wm_detect_offsets(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* keys, int k, int oy0, int ox0, int ny, int nx,
                       float* corr_out, int* status_out, int slot)
 {
     if (!ctx) return WM_ERR_BAD_ARG;
-    if (mask != WM_MASK_ME && mask != WM_MASK_NVF) return fail(ctx, WM_ERR_BAD_ARG, "bad mask type");
-    if (ctx->p != 3 && mask == WM_MASK_ME) return fail(ctx, WM_ERR_BAD_P, "ME mask needs p == 3 (main.cpp:89)");
+    int rc = check_mask(ctx, mask);
+    if (rc != WM_OK) return rc;
     if (!img || !keys || !corr_out) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_offsets: null img, keys or corr_out");
     if (k < 0 || k >= keys->nkeys) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_offsets: key " + std::to_string(k) + " of a bank of " + std::to_string(keys->nkeys));
-    if (keys->device != ctx->device || keys->rows < ctx->rows || keys->cols < ctx->cols)
-        return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_offsets: the key bank is " + std::to_string(keys->rows) + "x" + std::to_string(keys->cols) + " on device " +
-                                             std::to_string(keys->device) + ", the engine " + std::to_string(ctx->rows) + "x" + std::to_string(ctx->cols) +
-                                             " on device " + std::to_string(ctx->device) + " (the bank must be at least as large)");
+    if ((rc = check_bank(ctx, keys, "wm_detect_offsets", false)) != WM_OK) return rc;
     if (wm_offsets_check(ctx->rows, ctx->cols, keys->rows, keys->cols, oy0, ox0, ny, nx) != WM_OK)
         return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_offsets: offsets (" + std::to_string(oy0) + "," + std::to_string(ox0) + ") + " + std::to_string(ny) + "x" +
                                              std::to_string(nx) + " of " + std::to_string(ctx->rows) + "x" + std::to_string(ctx->cols) +
                                              " windows leave the " + std::to_string(keys->rows) + "x" + std::to_string(keys->cols) + " key plane");
     if (ctx->band_hi > 0) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_offsets: not in band mode");
-    Slot* sp; bool sync_after;
-    int rc = get_slot(ctx, slot, &sp, &sync_after);
-    if (rc != WM_OK) return rc;
-    Slot& s = *sp;
-    if ((rc = check_plane(ctx, img, 0, false, "image", true)) != WM_OK) return rc;
-    const int frames = img->frames;
-    const long long noff = (long long)ny * nx;
-    if ((long long)s.res_used + (long long)frames * noff > RES_CAP)
-        return fail(ctx, WM_ERR_BUSY, "too many un-synced results on this slot (frames x offsets count against " + std::to_string(RES_CAP) + ")");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    PlaneDesc xd;
-    if ((rc = prep_input(ctx, s, img, &xd)) != WM_OK) return rc;
-    LaunchGeom lg;
-    if ((rc = geom_checked(ctx, frames, mask, &lg)) != WM_OK) return rc;
-    // partial records: [frames][ny * nx][rstride][2] + [frames][rstride] (the scratch of wm_detect_keys: one stream, in order)
-    const int rstride = std::max(ctx->max_nblk, ctx->max_nrec);
-    const size_t need = (size_t)frames * (2 * (size_t)noff + 1) * rstride * sizeof(double);
-    if ((rc = ensure(ctx, &s.keys_part, &s.keys_part_bytes, need)) != WM_OK) return rc;
-    // the buffer descriptor of a window spans rows of the KEY plane's pitch: its extent decides the 32-bit offsets
-    const int aligned_w = fits_32bit(keys->rows, keys->cols, WM_F32) ? 1 : 0;
+    // NOT aligned_w_of: the buffer descriptor of a window spans rows of the KEY plane's pitch, so that plane's extent decides the
+    // 32-bit offsets
+    const int aligned_key = fits_32bit(keys->rows, keys->cols, WM_F32) ? 1 : 0;
     const float* key = keys->d + (size_t)k * keys->rows * keys->cols;
-    OpResult* res = s.d_res + s.res_used;
-    // the image side is wm_detect's: the Gram sweep (or the hand-over of the slot's last embed) and the solve
-    if ((rc = gram_sweep(ctx, s, lg, frames, xd, img)) != WM_OK) return rc;
-    {
-        ProfScope ps(ctx, K_DETECT_OFFSETS, s.stream);
-        if (launch_detect_offsets(s.stream, lg, frames, mask, ctx->p / 2, xd, key, keys->cols, oy0, ox0, ny, nx, aligned_w, s.d_coef,
-                                  s.d_status, (double*)s.keys_part, rstride, res) != 0)
-            return fail(ctx, WM_ERR_RUNTIME, "wm_detect_offsets: geometry exceeds the record arrays");
-    }
-    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
-    if ((rc = push_pending(ctx, s, frames * (int)noff, corr_out, status_out, nullptr)) != WM_OK) return rc;
-    s.pending.back().frames = frames;
-    s.pending.back().nkeys = (int)noff;
-    return sync_after ? do_sync(ctx, s) : WM_OK;
+    return detect_bank(ctx, mask, img, (long long)ny * nx, "offsets", "wm_detect_offsets", K_DETECT_OFFSETS, corr_out, status_out, slot,
+                       [&](Slot& s, const LaunchGeom& lg, int frames, const PlaneDesc& xd, double* part, int rstride, OpResult* res) {
+                           return launch_detect_offsets(s.stream, lg, frames, mask, ctx->p / 2, xd, key, keys->cols, oy0, ox0, ny, nx, aligned_key, s.d_coef,
+                                                        s.d_status, part, rstride, res);
+                       });
 }
 
 // tiles per axis of wm_detect_tiles: the last tile of each axis takes the remainder (pure host arithmetic)
@@ -1648,23 +1681,16 @@ int wm_detect_tiles(wm_ctx* ctx, int mask, const wm_plane* img, int tile_rows, i
     if (wm_tiles_shape(ctx->rows, ctx->cols, tile_rows, tile_cols, &ny, &nx) != WM_OK)
         return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_tiles: tile shape " + std::to_string(tile_rows) + "x" + std::to_string(tile_cols) +
                                              " (rows: a multiple of 8, >= 32; columns: a multiple of 4, >= 32)");
-    if (mask != WM_MASK_ME && mask != WM_MASK_NVF) return fail(ctx, WM_ERR_BAD_ARG, "bad mask type");
-    if (ctx->p != 3 && mask == WM_MASK_ME) return fail(ctx, WM_ERR_BAD_P, "ME mask needs p == 3 (main.cpp:89)");
-    if (ctx->band_hi > 0) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_tiles: not in band mode");
-    Slot* sp; bool sync_after;
-    int rc = get_slot(ctx, slot, &sp, &sync_after);
+    int rc = check_mask(ctx, mask);
     if (rc != WM_OK) return rc;
-    Slot& s = *sp;
-    if ((rc = check_plane(ctx, img, 0, false, "image", true)) != WM_OK) return rc;
-    const int frames = img->frames;
-    if (s.res_used + frames > RES_CAP) return fail(ctx, WM_ERR_BUSY, "too many un-synced results on this slot");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (ctx->band_hi > 0) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_tiles: not in band mode");
+    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
     PlaneDesc xd;
-    if ((rc = prep_input(ctx, s, img, &xd)) != WM_OK) return rc;
     LaunchGeom lg;
-    if ((rc = geom_checked(ctx, frames, mask, &lg)) != WM_OK) return rc;
-    const int aligned_w = fits_32bit(ctx->rows, ctx->cols, WM_F32) ? 1 : 0;
-    const TilesPlan pl = tiles_plan(lg, frames, mask, ctx->p / 2, xd, aligned_w, tile_rows, tile_cols, ny, nx);
+    if ((rc = open_input(ctx, s, img, "image", mask, 1, nullptr, &xd, &lg)) != WM_OK) return rc;
+    const int frames = img->frames;
+    const TilesPlan pl = tiles_plan(lg, frames, mask, ctx->p / 2, xd, aligned_w_of(ctx), tile_rows, tile_cols, ny, nx);
     if ((rc = ensure(ctx, &s.tiles_rec, &s.tiles_rec_bytes, pl.rec_bytes)) != WM_OK) return rc;
     OpResult* res = s.d_res + s.res_used;
     // the image side is wm_detect's: the Gram sweep (or the hand-over of the slot's last embed) and the solve
@@ -1672,27 +1698,22 @@ int wm_detect_tiles(wm_ctx* ctx, int mask, const wm_plane* img, int tile_rows, i
     { ProfScope ps(ctx, K_DETECT_TILES, s.stream); launch_detect_tiles(s.stream, pl, frames, mask, ctx->p / 2, xd, ctx->w->d_w, s.d_coef, s.d_status, (float*)s.tiles_rec); }
     { ProfScope ps(ctx, K_TILES_FOLD, s.stream); launch_tiles_fold(s.stream, pl, frames, (const float*)s.tiles_rec, s.d_status, map_dev, sums_dev, res); }
     if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
-    if ((rc = push_pending(ctx, s, frames, nullptr, status_out, nullptr)) != WM_OK) return rc;
-    return sync_after ? do_sync(ctx, s) : WM_OK;
+    push_pending(s, frames, 1, false, nullptr, status_out, nullptr);
+    return slot == WM_SLOT_SYNC ? do_sync(ctx, s) : WM_OK;
 }
 
-// makeWatermark of every frame with every key of the bank: wm_embed's input handling, wm_detect_keys' bank and result handling
+// makeWatermark of every frame with every key of the bank: wm_embed's input and base handling, one record per (frame, key)
 int wm_embed_keys(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* base, const wm_keys* keys, const wm_plane* out,
                   float* a_out, int* status_out, int slot)
 {
     if (!ctx) return WM_ERR_BAD_ARG;
-    if (mask != WM_MASK_ME && mask != WM_MASK_NVF) return fail(ctx, WM_ERR_BAD_ARG, "bad mask type");
-    if (mask == WM_MASK_ME && ctx->p != 3) return fail(ctx, WM_ERR_BAD_P, "ME mask needs p == 3 (main.cpp:89)");
-    if (!keys || !out) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_keys: null keys or out");
-    if (keys->device != ctx->device || keys->rows != ctx->rows || keys->cols != ctx->cols)
-        return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_keys: the key bank is " + std::to_string(keys->rows) + "x" + std::to_string(keys->cols) + " on device " +
-                                             std::to_string(keys->device) + ", the engine " + std::to_string(ctx->rows) + "x" + std::to_string(ctx->cols) +
-                                             " on device " + std::to_string(ctx->device));
-    if (ctx->band_hi > 0) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_keys: not in band mode");
-    Slot* sp; bool sync_after;
-    int rc = get_slot(ctx, slot, &sp, &sync_after);
+    int rc = check_mask(ctx, mask);
     if (rc != WM_OK) return rc;
-    Slot& s = *sp;
+    if (!keys || !out) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_keys: null keys or out");
+    if ((rc = check_bank(ctx, keys, "wm_embed_keys", true)) != WM_OK) return rc;
+    if (ctx->band_hi > 0) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_keys: not in band mode");
+    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
     if ((rc = check_plane(ctx, in_gray, 0, false, "in_gray", true)) != WM_OK) return rc;
     const int frames = in_gray->frames;
     const int nkeys = keys->nkeys;
@@ -1710,23 +1731,12 @@ int wm_embed_keys(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane
     }
     if (out->channels != base->channels || out->dtype != base->dtype) return fail(ctx, WM_ERR_BAD_ARG, "out must have the shape and dtype of base");
     if (in_gray->dtype != base->dtype) return fail(ctx, WM_ERR_BAD_ARG, "in_gray and base must have the same dtype (the reference converts whole frames, main.cpp:355-357)");
-    if ((long long)s.res_used + (long long)frames * nkeys > RES_CAP)
-        return fail(ctx, WM_ERR_BUSY, "too many un-synced results on this slot (frames x keys count against " + std::to_string(RES_CAP) + ")");
+    if ((rc = check_res_room(ctx, s, (long long)frames * nkeys, "keys")) != WM_OK) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
 
     PlaneDesc xd, bd;
     if ((rc = prep_input(ctx, s, in_gray, &xd)) != WM_OK) return rc;
-    const bool base_is_in = base->data == in_gray->data && base->mem == in_gray->mem && base->mem != WM_MEM_SLOT_OUT && base->channels == 1 &&
-                            base->dtype == in_gray->dtype && base->pitch == in_gray->pitch;
-    if (base->mem == WM_MEM_HOST) {
-        if (base_is_in) { bd = xd; }
-        else {
-            Staged st = staged_layout(base);
-            if ((rc = ensure(ctx, &s.st_base, &s.st_base_bytes, st.bytes)) != WM_OK) return rc;
-            if ((rc = stage_in(ctx, s, base, s.st_base, st)) != WM_OK) return rc;
-            bd = st.d; bd.p = s.st_base;
-        }
-    } else bd = desc_device(base);
+    if ((rc = prep_base(ctx, s, in_gray, base, xd, &bd)) != WM_OK) return rc;
     const PlaneDesc od = desc_device(out);
     // K outputs of one input: an in-place call has no meaning (judged on the RESOLVED planes, as wm_embed judges them)
     if (descs_overlap(xd, od, ctx->rows, ctx->cols, frames, frames * nkeys) || descs_overlap(bd, od, ctx->rows, ctx->cols, frames, frames * nkeys))
@@ -1739,13 +1749,13 @@ int wm_embed_keys(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane
     if ((rc = geom_checked(ctx, frames, mask, &lg)) != WM_OK) return rc;
     const int rstride = std::max(ctx->max_nblk, ctx->max_nrec);
     if ((rc = ensure(ctx, &s.ekeys_part, &s.ekeys_part_bytes, embed_keys_scratch_bytes(frames, nkeys, rstride))) != WM_OK) return rc;
-    const int aligned_w = fits_32bit(ctx->rows, ctx->cols, WM_F32) ? 1 : 0  /* (W is a dense f32 plane: 4-byte aligned rows suffice, vec_ok) */;
+    const int aligned_w = aligned_w_of(ctx);  // (the bank's planes have W's shape)
     const long long kstride = (long long)ctx->rows * ctx->cols;
     const int pad = ctx->p / 2;
     OpResult* res = s.d_res + s.res_used;
     const int* status = mask == WM_MASK_ME ? s.d_status : nullptr;
     // the image side is wm_embed's: the Gram sweep and solve (ME)
-    if (mask == WM_MASK_ME) { ProfScope ps(ctx, K_GRAM, s.stream); launch_gram(s.stream, lg, frames, xd, s.d_gram, s.d_gramb, s.d_ticket, s.d_coef, s.d_status, s.d_gramtot); }
+    if (mask == WM_MASK_ME) sweep_gram(ctx, s, K_GRAM, lg, frames, xd);
     {
         ProfScope ps(ctx, K_STATS_KEYS, s.stream);
         if (launch_stats_keys(s.stream, lg, frames, mask, pad, xd, keys->d, kstride, nkeys, aligned_w, s.d_coef, status, s.ekeys_part, rstride) != 0)
@@ -1754,23 +1764,18 @@ int wm_embed_keys(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane
     { ProfScope ps(ctx, K_EMBED_KEYS_FOLD, s.stream); launch_embed_keys_fold(s.stream, lg, frames, mask, nkeys, status, s.ekeys_part, rstride, ctx->sF, sqrt_n(ctx), res); }
     { ProfScope ps(ctx, K_EMBED_KEYS, s.stream); launch_embed_keys(s.stream, lg, frames, mask, pad, xd, keys->d, kstride, nkeys, aligned_w, bd, od, s.d_coef, status, s.ekeys_part, rstride); }
     if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
-    if ((rc = push_pending(ctx, s, frames * nkeys, a_out, status_out, nullptr)) != WM_OK) return rc;
-    s.pending.back().frames = frames;
-    s.pending.back().nkeys = nkeys;
-    s.pending.back().keep_value_when_unsolvable = true;  // (wm_embed's rule: an unsolvable frame leaves its K strengths untouched)
-    return sync_after ? do_sync(ctx, s) : WM_OK;
+    push_pending(s, frames, nkeys, true, a_out, status_out, nullptr);  // (wm_embed's rule: an unsolvable frame leaves its K strengths untouched)
+    return slot == WM_SLOT_SYNC ? do_sync(ctx, s) : WM_OK;
 }
 
 int wm_compute_mask(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* mask_out, const wm_plane* e_out,
                     float* coef_out, int* status_out, int slot)
 {
     if (!ctx) return WM_ERR_BAD_ARG;
-    if (mask != WM_MASK_ME && mask != WM_MASK_NVF) return fail(ctx, WM_ERR_BAD_ARG, "bad mask type");
-    if (mask == WM_MASK_ME && ctx->p != 3) return fail(ctx, WM_ERR_BAD_P, "ME mask needs p == 3 (main.cpp:89)");
-    Slot* sp; bool sync_after;
-    int rc = get_slot(ctx, slot, &sp, &sync_after);
+    int rc = check_mask(ctx, mask);
     if (rc != WM_OK) return rc;
-    Slot& s = *sp;
+    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
     if ((rc = check_plane(ctx, in_gray, 0, false, "in_gray", true)) != WM_OK) return rc;
     const int frames = in_gray->frames;
     if ((rc = check_plane(ctx, mask_out, frames, false, "mask_out")) != WM_OK) return rc;
@@ -1779,14 +1784,12 @@ int wm_compute_mask(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_pla
         if ((rc = check_plane(ctx, e_out, frames, false, "e_out")) != WM_OK) return rc;
         if (e_out->dtype != WM_F32 || e_out->mem != WM_MEM_DEVICE) return fail(ctx, WM_ERR_BAD_ARG, "e_out must be a device f32 plane");
     }
-    if (s.res_used + frames > RES_CAP) return fail(ctx, WM_ERR_BUSY, "too many un-synced results on this slot");
+    if ((rc = check_res_room(ctx, s, frames)) != WM_OK) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     PlaneDesc xd;
     if ((rc = prep_input(ctx, s, in_gray, &xd)) != WM_OK) return rc;
     LaunchGeom lg;
     if ((rc = geom_checked(ctx, frames, mask, &lg)) != WM_OK) return rc;
-    const float* W = ctx->w->d_w;
-    const int aligned_w = fits_32bit(ctx->rows, ctx->cols, WM_F32) ? 1 : 0  /* (W is a dense f32 plane: 4-byte aligned rows suffice, vec_ok) */;
     PlaneDesc mo = desc_device(mask_out), eo;
     if (e_out) eo = desc_device(e_out); else { eo = mo; eo.p = nullptr; }
     invalidate_handovers(ctx, mo, frames);
@@ -1794,8 +1797,8 @@ int wm_compute_mask(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_pla
     OpResult* res = s.d_res + s.res_used;
     float* coefres = s.d_coefres + (size_t)s.res_used * 8;
     if (mask == WM_MASK_ME) {
-        { ProfScope ps(ctx, K_GRAM, s.stream); launch_gram(s.stream, lg, frames, xd, s.d_gram, s.d_gramb, s.d_ticket, s.d_coef, s.d_status, s.d_gramtot); }
-        { ProfScope ps(ctx, K_ME_STATS, s.stream); launch_me_stats(s.stream, lg, frames, xd, W, aligned_w, s.d_coef, s.d_status, s.d_pmax, s.d_pss, s.d_ticket + ctx->max_frames * TKS, strip_tickets(ctx, s, 0), s.d_smax, s.d_sss, ctx->sF, sqrt_n(ctx), s.d_scal, res, s.d_raw); }
+        sweep_gram(ctx, s, K_GRAM, lg, frames, xd);
+        sweep_stats(ctx, s, true, lg, frames, mask, xd, res);
         { ProfScope ps(ctx, K_MASK, s.stream); launch_mask(s.stream, lg, frames, 0, 1, xd, s.d_coef, s.d_status, s.d_scal, mo, eo); }
         launch_mask_result(s.stream, frames, s.d_status, s.d_coef, res, coefres);
     } else {
@@ -1803,24 +1806,20 @@ int wm_compute_mask(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_pla
         launch_mask_result(s.stream, frames, nullptr, nullptr, res, coefres);
     }
     if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
-    if ((rc = push_pending(ctx, s, frames, nullptr, status_out, coef_out)) != WM_OK) return rc;
-    return sync_after ? do_sync(ctx, s) : WM_OK;
+    push_pending(s, frames, 1, false, nullptr, status_out, coef_out);
+    return slot == WM_SLOT_SYNC ? do_sync(ctx, s) : WM_OK;
 }
 
 int wm_gram(wm_ctx* ctx, const wm_plane* img, double* gram_out, int slot)
 {
     if (!ctx || !gram_out) return WM_ERR_BAD_ARG;
-    Slot* sp; bool sync_after;
-    int rc = get_slot(ctx, slot, &sp, &sync_after);
+    int rc = check_slot(ctx, slot);
     if (rc != WM_OK) return rc;
-    Slot& s = *sp;
-    if ((rc = check_plane(ctx, img, 0, false, "image", true)) != WM_OK) return rc;
-    const int frames = img->frames;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Slot& s = slot_of(ctx, slot);
     PlaneDesc xd;
-    if ((rc = prep_input(ctx, s, img, &xd)) != WM_OK) return rc;
     LaunchGeom lg;
-    if ((rc = geom_checked(ctx, frames, WM_MASK_ME, &lg)) != WM_OK) return rc;
+    if ((rc = open_input(ctx, s, img, "image", WM_MASK_ME, 0, nullptr, &xd, &lg)) != WM_OK) return rc;
+    const int frames = img->frames;
     if ((rc = gram_sweep(ctx, s, lg, frames, xd, img)) != WM_OK) return rc;
     if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
     HIPCHK(ctx, hipStreamSynchronize(s.stream));
@@ -1849,10 +1848,9 @@ int wm_band_configure(wm_ctx* ctx, int own_lo, int own_hi, long long rows_global
 int wm_band_solve(wm_ctx* ctx, const double* totals, int frames, int* status_out, int slot)
 {
     if (!ctx || !totals || frames < 1 || frames > ctx->max_frames) return fail(ctx, WM_ERR_BAD_ARG, "wm_band_solve: bad arguments");
-    Slot* sp; bool sync_after;
-    int rc = get_slot(ctx, slot, &sp, &sync_after);
+    int rc = check_slot(ctx, slot);
     if (rc != WM_OK) return rc;
-    Slot& s = *sp;
+    Slot& s = slot_of(ctx, slot);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipMemcpyAsync(s.d_totals, totals, (size_t)frames * NGRAM * sizeof(double), hipMemcpyHostToDevice, s.stream));
     launch_solve_totals(s.stream, frames, s.d_totals, s.d_coef, s.d_status);
@@ -1869,34 +1867,17 @@ int wm_band_solve(wm_ctx* ctx, const double* totals, int frames, int* status_out
 }
 
 // ---- the launches of the band phases, shared by the host-exchange calls (totals copied to the caller's host arrays) and the
-// device-resident ones (wm_band_*_dev: totals handed over in device memory, nothing synchronises)
-static int band_check_mask(wm_ctx* ctx, int mask)
-{
-    if (mask != WM_MASK_ME && mask != WM_MASK_NVF) return fail(ctx, WM_ERR_BAD_ARG, "bad mask type");
-    if (mask == WM_MASK_ME && ctx->p != 3) return fail(ctx, WM_ERR_BAD_P, "ME mask needs p == 3 (main.cpp:89)");
-    return WM_OK;
-}
-static int aligned_w_of(const wm_ctx* ctx) { return fits_32bit(ctx->rows, ctx->cols, WM_F32) ? 1 : 0  /* (W is a dense f32 plane: 4-byte aligned rows suffice, vec_ok) */; }
-
+// device-resident ones (wm_band_*_dev: totals handed over in device memory, nothing synchronises); the profile leaves them out
 // stats sweep of the owned rows; the fold tail leaves {max|e| (or 1), sum} per frame in s.d_raw[0 .. frames)
 static int band_stats_launch(wm_ctx* ctx, Slot& s, int mask, const wm_plane* in_gray, int* frames_out)
 {
     int rc;
-    if ((rc = band_check_mask(ctx, mask)) != WM_OK) return rc;
-    if ((rc = check_plane(ctx, in_gray, 0, false, "inputImage", true)) != WM_OK) return rc;
-    const int frames = in_gray->frames;
-    if (s.res_used + frames > RES_CAP) return fail(ctx, WM_ERR_BUSY, "too many un-synced results on this slot");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if ((rc = check_mask(ctx, mask)) != WM_OK) return rc;
     PlaneDesc xd;
-    if ((rc = prep_input(ctx, s, in_gray, &xd)) != WM_OK) return rc;
     LaunchGeom lg;
-    if ((rc = geom_checked(ctx, frames, mask, &lg)) != WM_OK) return rc;
-    const float* W = ctx->w->d_w;
-    OpResult* res = s.d_res + s.res_used;  // written by the tail, not delivered (no pending record)
-    if (mask == WM_MASK_ME)
-        launch_me_stats(s.stream, lg, frames, xd, W, aligned_w_of(ctx), s.d_coef, s.d_status, s.d_pmax, s.d_pss, s.d_ticket + ctx->max_frames * TKS, strip_tickets(ctx, s, 0), s.d_smax, s.d_sss, ctx->sF, sqrt_n(ctx), s.d_scal, res, s.d_raw);
-    else
-        launch_nvf_stats(s.stream, lg, frames, xd, W, aligned_w_of(ctx), ctx->p / 2, s.d_pss, s.d_ticket + ctx->max_frames * TKS, strip_tickets(ctx, s, 0), s.d_sss, ctx->sF, sqrt_n(ctx), s.d_scal, res, s.d_raw);
+    if ((rc = open_input(ctx, s, in_gray, "inputImage", mask, 1, nullptr, &xd, &lg)) != WM_OK) return rc;
+    const int frames = in_gray->frames;
+    sweep_stats(ctx, s, false, lg, frames, mask, xd, s.d_res + s.res_used);  // (records written by the tail, not delivered: no pending entry)
     *frames_out = frames;
     return launch_check(ctx, s);
 }
@@ -1911,8 +1892,8 @@ static int band_embed_launch(wm_ctx* ctx, Slot& s, int mask, const wm_plane* in_
     if (out->channels != base->channels || out->dtype != base->dtype) return fail(ctx, WM_ERR_BAD_ARG, "out must match outputImage in channels and dtype");
     if (in_gray->mem != WM_MEM_DEVICE || base->mem != WM_MEM_DEVICE || out->mem != WM_MEM_DEVICE)
         return fail(ctx, WM_ERR_BAD_ARG, "wm_band_embed: device planes only");
-    if (planes_overlap(in_gray, out)) return fail(ctx, WM_ERR_BAD_ARG, "wm_band_embed: out must not overlap the input (halo rows are shared)");
     const PlaneDesc xd = desc_device(in_gray), bd = desc_device(base), od = desc_device(out);
+    if (descs_overlap(xd, od, ctx->rows, ctx->cols, frames)) return fail(ctx, WM_ERR_BAD_ARG, "wm_band_embed: out must not overlap the input (halo rows are shared)");
     invalidate_handovers(ctx, od, frames);
     LaunchGeom lg;
     if ((rc = geom_checked(ctx, frames, mask, &lg)) != WM_OK) return rc;
@@ -1925,31 +1906,22 @@ static int band_embed_launch(wm_ctx* ctx, Slot& s, int mask, const wm_plane* in_
 static int band_detect_launch(wm_ctx* ctx, Slot& s, int mask, const wm_plane* img, int* frames_out)
 {
     int rc;
-    if ((rc = band_check_mask(ctx, mask)) != WM_OK) return rc;
-    if ((rc = check_plane(ctx, img, 0, false, "image", true)) != WM_OK) return rc;
-    const int frames = img->frames;
-    if (s.res_used + frames > RES_CAP) return fail(ctx, WM_ERR_BUSY, "too many un-synced results on this slot");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if ((rc = check_mask(ctx, mask)) != WM_OK) return rc;
     PlaneDesc xd;
-    if ((rc = prep_input(ctx, s, img, &xd)) != WM_OK) return rc;
     LaunchGeom lg;
-    if ((rc = geom_checked(ctx, frames, mask, &lg)) != WM_OK) return rc;
-    OpResult* res = s.d_res + s.res_used;
-    launch_detect(s.stream, lg, frames, mask, ctx->p / 2, xd, ctx->w->d_w, aligned_w_of(ctx), s.d_coef, s.d_status, s.d_pcorr, s.d_ticket + 2 * ctx->max_frames * TKS, strip_tickets(ctx, s, 1), s.d_scorr, res, s.d_raw + ctx->max_frames);
+    if ((rc = open_input(ctx, s, img, "image", mask, 1, nullptr, &xd, &lg)) != WM_OK) return rc;
+    const int frames = img->frames;
+    sweep_detect(ctx, s, K_NONE, lg, frames, mask, xd, s.d_res + s.res_used);
     *frames_out = frames;
     return launch_check(ctx, s);
 }
 
-#define BAND_SLOT(ctx, slot)                                   \
-    Slot* sp; bool sync_after;                                 \
-    int rc = get_slot(ctx, slot, &sp, &sync_after);            \
-    if (rc != WM_OK) return rc;                                \
-    Slot& s = *sp; (void)sync_after
-
 int wm_band_stats(wm_ctx* ctx, int mask, const wm_plane* in_gray, double* out, int slot)
 {
     if (!ctx || !out) return WM_ERR_BAD_ARG;
-    BAND_SLOT(ctx, slot);
+    int rc = check_slot(ctx, slot);
+    if (rc != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
     int frames = 0;
     if ((rc = band_stats_launch(ctx, s, mask, in_gray, &frames)) != WM_OK) return rc;
     std::vector<RawSums> raw((size_t)frames);
@@ -1963,8 +1935,10 @@ int wm_band_embed(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane
                   const double* max_sum, float* a_out, int slot)
 {
     if (!ctx || !max_sum) return WM_ERR_BAD_ARG;
-    BAND_SLOT(ctx, slot);
-    if ((rc = band_check_mask(ctx, mask)) != WM_OK) return rc;
+    int rc = check_slot(ctx, slot);
+    if (rc != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
+    if ((rc = check_mask(ctx, mask)) != WM_OK) return rc;
     if ((rc = check_plane(ctx, in_gray, 0, false, "inputImage")) != WM_OK) return rc;
     const int frames = in_gray->frames;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -1986,7 +1960,9 @@ int wm_band_embed(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane
 int wm_band_detect_sums(wm_ctx* ctx, int mask, const wm_plane* img, double* out, int slot)
 {
     if (!ctx || !out) return WM_ERR_BAD_ARG;
-    BAND_SLOT(ctx, slot);
+    int rc = check_slot(ctx, slot);
+    if (rc != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
     int frames = 0;
     if ((rc = band_detect_launch(ctx, s, mask, img, &frames)) != WM_OK) return rc;
     std::vector<RawSums> raw((size_t)frames);
@@ -2002,23 +1978,24 @@ int wm_band_detect_sums(wm_ctx* ctx, int mask, const wm_plane* img, double* out,
 int wm_band_gram_dev(wm_ctx* ctx, const wm_plane* img, double* totals_dev, int slot)
 {
     if (!ctx || !totals_dev) return WM_ERR_BAD_ARG;
-    BAND_SLOT(ctx, slot);
-    if ((rc = check_plane(ctx, img, 0, false, "image", true)) != WM_OK) return rc;
-    const int frames = img->frames;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc = check_slot(ctx, slot);
+    if (rc != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
     PlaneDesc xd;
-    if ((rc = prep_input(ctx, s, img, &xd)) != WM_OK) return rc;
     LaunchGeom lg;
-    if ((rc = geom_checked(ctx, frames, WM_MASK_ME, &lg)) != WM_OK) return rc;
+    if ((rc = open_input(ctx, s, img, "image", WM_MASK_ME, 0, nullptr, &xd, &lg)) != WM_OK) return rc;
+    const int frames = img->frames;
     // (the sweep's solve tail also solves from the band's own partial totals into the slot: overwritten by wm_band_solve_dev)
-    launch_gram(s.stream, lg, frames, xd, s.d_gram, s.d_gramb, s.d_ticket, s.d_coef, s.d_status, totals_dev);
+    sweep_gram(ctx, s, K_NONE, lg, frames, xd, totals_dev);
     return launch_check(ctx, s);
 }
 
 int wm_band_solve_dev(wm_ctx* ctx, const double* totals_dev, int frames, int slot)
 {
     if (!ctx || !totals_dev || frames < 1 || frames > ctx->max_frames) return fail(ctx, WM_ERR_BAD_ARG, "wm_band_solve_dev: bad arguments");
-    BAND_SLOT(ctx, slot);
+    int rc = check_slot(ctx, slot);
+    if (rc != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     launch_solve_totals(s.stream, frames, totals_dev, s.d_coef, s.d_status);
     return launch_check(ctx, s);
@@ -2027,7 +2004,9 @@ int wm_band_solve_dev(wm_ctx* ctx, const double* totals_dev, int frames, int slo
 int wm_band_stats_dev(wm_ctx* ctx, int mask, const wm_plane* in_gray, double* max_sum_dev, int slot)
 {
     if (!ctx || !max_sum_dev) return WM_ERR_BAD_ARG;
-    BAND_SLOT(ctx, slot);
+    int rc = check_slot(ctx, slot);
+    if (rc != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
     int frames = 0;
     if ((rc = band_stats_launch(ctx, s, mask, in_gray, &frames)) != WM_OK) return rc;
     launch_band_pick(s.stream, frames, s.d_raw, 2, max_sum_dev);
@@ -2038,8 +2017,10 @@ int wm_band_embed_dev(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_p
                       const double* gathered_max_sum_dev, int nparts, float* a_dev, int slot)
 {
     if (!ctx || !gathered_max_sum_dev || nparts < 1) return WM_ERR_BAD_ARG;
-    BAND_SLOT(ctx, slot);
-    if ((rc = band_check_mask(ctx, mask)) != WM_OK) return rc;
+    int rc = check_slot(ctx, slot);
+    if (rc != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
+    if ((rc = check_mask(ctx, mask)) != WM_OK) return rc;
     if ((rc = check_plane(ctx, in_gray, 0, false, "inputImage")) != WM_OK) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     launch_band_scalars(s.stream, in_gray->frames, gathered_max_sum_dev, nparts, mask, ctx->sF, sqrt_n(ctx), mask == WM_MASK_ME ? s.d_status : nullptr, s.d_scal, a_dev);
@@ -2049,7 +2030,9 @@ int wm_band_embed_dev(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_p
 int wm_band_detect_sums_dev(wm_ctx* ctx, int mask, const wm_plane* img, double* sums_dev, int slot)
 {
     if (!ctx || !sums_dev) return WM_ERR_BAD_ARG;
-    BAND_SLOT(ctx, slot);
+    int rc = check_slot(ctx, slot);
+    if (rc != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
     int frames = 0;
     if ((rc = band_detect_launch(ctx, s, mask, img, &frames)) != WM_OK) return rc;
     launch_band_pick(s.stream, frames, s.d_raw + ctx->max_frames, 3, sums_dev);
@@ -2059,7 +2042,9 @@ int wm_band_detect_sums_dev(wm_ctx* ctx, int mask, const wm_plane* img, double* 
 int wm_band_corr_dev(wm_ctx* ctx, const double* sums_dev, int frames, float* corr_dev, int slot)
 {
     if (!ctx || !sums_dev || !corr_dev || frames < 1 || frames > ctx->max_frames) return fail(ctx, WM_ERR_BAD_ARG, "wm_band_corr_dev: bad arguments");
-    BAND_SLOT(ctx, slot);
+    int rc = check_slot(ctx, slot);
+    if (rc != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     launch_band_corr(s.stream, frames, sums_dev, s.d_status, corr_dev);
     return launch_check(ctx, s);
@@ -2068,11 +2053,10 @@ int wm_band_corr_dev(wm_ctx* ctx, const double* sums_dev, int frames, float* cor
 int wm_sync(wm_ctx* ctx, int slot)
 {
     if (!ctx) return WM_ERR_BAD_ARG;
-    Slot* sp; bool unused_sync_flag;
-    int rc = get_slot(ctx, slot, &sp, &unused_sync_flag);
+    const int rc = check_slot(ctx, slot);
     if (rc != WM_OK) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    return do_sync(ctx, *sp);
+    return do_sync(ctx, slot_of(ctx, slot));
 }
 
 int wm_set_stream(wm_ctx* ctx, int slot, void* hip_stream)
@@ -2136,15 +2120,12 @@ void wm_host_free(void* p) { if (p) (void)hipHostFree(p); }
 int wm_selftest_nvf_quotient(int device, int variant, uint32_t bits_lo, uint32_t bits_hi, unsigned long long* mismatches, uint32_t* first_bad)
 {
     if (variant < 0 || variant > 3 || bits_lo > bits_hi) return WM_ERR_BAD_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return WM_ERR_NO_DEVICE;
-    if (device < 0 || device >= ndev) device = 0;
-    if (hipSetDevice(device) != hipSuccess) return WM_ERR_NO_DEVICE;
+    int rc = choose_device(&device);
+    if (rc != WM_OK) return rc;
     unsigned long long* d = nullptr;
     if (hipMalloc((void**)&d, 16) != hipSuccess) return WM_ERR_ALLOC;
     const unsigned long long init[2] = {0ull, ~0ull};
     unsigned long long got[2] = {0ull, ~0ull};
-    int rc = WM_OK;
     if (hipMemcpy(d, init, 16, hipMemcpyHostToDevice) != hipSuccess) rc = WM_ERR_RUNTIME;
     if (rc == WM_OK) {
         launch_selftest_quot(nullptr, variant, bits_lo, bits_hi, d);
@@ -2159,17 +2140,15 @@ int wm_selftest_nvf_quotient(int device, int variant, uint32_t bits_lo, uint32_t
 int wm_membench(int device, int kind, size_t bytes, double seconds, double* mean_us, int* launches)
 {
     if (kind < 0 || kind > 5 || bytes < 4096 || !(seconds >= 0.0) || seconds > 30.0) return WM_ERR_BAD_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return WM_ERR_NO_DEVICE;
-    if (device < 0 || device >= ndev) device = 0;
-    if (hipSetDevice(device) != hipSuccess) return WM_ERR_NO_DEVICE;
+    int rc = choose_device(&device);
+    if (rc != WM_OK) return rc;
     const size_t n16 = bytes / 16;
     void *src = nullptr, *dst = nullptr;
     unsigned long long* sink = nullptr;
     hipStream_t st = nullptr;
     constexpr int NEV = 32;   // launches in flight between two waits
     hipEvent_t ea[NEV], eb[NEV];
-    int nev = 0, rc = WM_OK;
+    int nev = 0;
     double total_ms = 0.0;
     int count = 0;
     do {
