@@ -277,6 +277,28 @@ public:
         if (rd < 0) fail(rd, "detectTiles");
         return map;
     }
+    // whose mark is where?  detectTiles of one grey image with every key of `keys` in the place of this engine's W, in one call
+    // (wm.h wm_detect_keys_tiles): score [(k * ny + i) * nx + j] is what detectTiles returns for tile (i, j) with key k as W.  The
+    // argmax over k names the key a tile was marked with.  ny / nx, if given, receive the tiles per axis (wm_tiles_shape)
+    std::vector<float> detectKeysTiles(const wm::Image& watermarkedImage, const WatermarkKeys& keys, int tileRows, int tileCols,
+                                       MASK_TYPE maskType, int* ny = nullptr, int* nx = nullptr) const
+    {
+        int ty = 0, tx = 0;
+        int rc = wm_tiles_shape(wm_rows(ctx), wm_cols(ctx), tileRows, tileCols, &ty, &tx);
+        if (rc < 0) fail(rc, "detectKeysTiles");
+        if (ny) *ny = ty;
+        if (nx) *nx = tx;
+        const wm_plane pimg = watermarkedImage.plane();
+        std::vector<float> map((size_t)keys.count() * (size_t)ty * (size_t)tx, 0.0f);
+        float* dmap = static_cast<float*>(wm_dev_alloc(wm_device(ctx), map.size() * sizeof(float)));
+        if (!dmap) fail(WM_ERR_ALLOC, "detectKeysTiles");
+        rc = wm_detect_keys_tiles(ctx, (int)maskType, &pimg, keys.handle(), tileRows, tileCols, dmap, nullptr, nullptr, WM_SLOT_SYNC);
+        const int rd = rc < 0 ? WM_OK : wm_memcpy_d2h(map.data(), dmap, map.size() * sizeof(float));
+        wm_dev_free(dmap);
+        if (rc < 0) fail(rc, "detectKeysTiles");
+        if (rd < 0) fail(rd, "detectKeysTiles");
+        return map;
+    }
     // makeWatermark of one grey image with every key of `keys` as W in one call (wm.h wm_embed_keys): copy k is what
     // makeWatermark returns with key k as W, strengths[k] its strength.  Not solvable: every copy is `outputImage` itself and
     // `strengths` is left untouched (Watermark.cpp:164-165)

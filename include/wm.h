@@ -304,6 +304,50 @@ int wm_tiles_shape(int rows, int cols, int tile_rows, int tile_cols, int* ny, in
 int wm_detect_tiles(wm_ctx* ctx, int mask, const wm_plane* img, int tile_rows, int tile_cols, float* map_dev, double* sums_dev,
                     int* status_out, int slot);
 
+/* ---- Tile map per key: whose mark is where? ----------------------------------------------------------------------------------
+ * Collusion by mosaic: several recipients of per-key copies (wm_embed_keys) splice their copies together region by region.  The
+ * copies share one base image, so the seams are invisible; every colluder's whole-frame score falls by the number of colluders
+ * and wm_detect_keys shows a few weak keys it cannot tell from noise.  The per-tile, per-key map separates them: the argmax over
+ * keys names the source of every tile.
+ * wm_detect_keys_tiles is wm_detect_tiles with EVERY key of the bank in the place of the context's W: one Gram sweep (the
+ * hand-over of the slot's last embed included, exactly as wm_detect_keys takes it) and one solve per frame, then ONE sweep that
+ * reads the image once per group of keys and every key plane once (k_detect_keys_tiles), the three sums kept per
+ * (frame, key, tile).  The context supplies shape, p and device -- its own W is not used.
+ *
+ * map_dev [frames][nkeys][ny][nx] is a DEVICE f32 array on the context's device, sums_dev [frames][nkeys][ny][nx][3] a DEVICE f64
+ * array {<e_u,e_w>, ||e_u||^2, ||e_w||^2} that may be NULL; tile geometry (wm_tiles_shape) and the score expression are
+ * wm_detect_tiles', unchanged.  Key k's map and sums equal, BIT FOR BIT, what wm_detect_tiles gives on a context created with key
+ * k as W.  The sums ADD, in f64, per frame, key and tile: the caller may pool the tiles of a region or the frames of a clip on the
+ * host and score the total with the same expression; ||e_w||^2 does not depend on the key.
+ * Both arrays are written on the slot's stream and are valid once wm_sync(ctx, slot) has returned; they must stay allocated
+ * until then.  status_out[frames] may be NULL; it is delivered by wm_sync, and `frames` results count against the slot's capacity
+ * of 4096 un-synced results (WM_ERR_BUSY beyond it).
+ *   - Takes everything wm_detect_keys and wm_detect_tiles both take: f32 / u8, any pitch and width, WM_MEM_HOST, WM_MEM_SLOT_OUT,
+ *     batches up to max_frames, ME with p = 3 (WM_ERR_BAD_P otherwise), NVF with p = 3..9.
+ *   - An unsolvable frame has status WM_UNSOLVABLE, 0.0f in every tile of every key and zero sums.
+ *   - A zero key (a bank's planes start at zero) scores NaN in every tile with status WM_OK; a flat tile under NVF is NaN for
+ *     every key.  Other keys and other tiles are unaffected by either.
+ *   - An ENQUEUE on the slot (WM_SLOT_SYNC: slot 0, waits); it may share a slot with any other call in any order.  Never takes the
+ *     fused single-launch kernels.  Its two kernels are not in the wm_prof_* list.
+ *   - The sweep's record scratch is kept per slot and grown on demand:
+ *     frames * ceil(nkeys / G) * nsegs * nstrips * (2 G + 1) * 64 * 4 bytes, G = 2 keys per group, nsegs segments of the largest
+ *     divisor of tile_rows in 8..48 rows, nstrips strips of 248 columns -- about 11 MB for one 4K frame, 16 keys and tile_rows
+ *     128.  WM_ERR_ALLOC when it does not fit.  As for wm_detect_tiles, the FIRST call on a slot that needs more of it than any
+ *     call before -- more frames, more keys, or a tile_rows with shorter segments -- reallocates it, which waits for the whole
+ *     device, the other slots' streams included.  Later calls only enqueue.
+ *   - WM_ERR_BAD_ARG, before any device work, for a null ctx, img, keys or map_dev, a tile shape wm_tiles_shape refuses, a bank of
+ *     another shape or device, a bad slot, band mode, and frames * nkeys * ny * nx (or the sweep's blocks) beyond a launch grid of
+ *     31 bits.  Index arithmetic is 64-bit throughout.
+ * Bits: a (frame, key)'s map and sums do not depend on the batch the frame arrives in, on the key's position in the bank or on
+ * the other keys, or on repetition (segments follow from tile_rows alone; the fold adds in a fixed order, no atomics).  A
+ * WM_MEM_HOST plane gives the bits of the same plane on the device for f32 planes and for widths that are multiples of 4.
+ *
+ * HAZARD.  As for wm_detect_keys: the kernels read the bank when the stream reaches them: the bank must stay ALIVE and UNMODIFIED
+ * (no wm_keys_set / _load_file / _generate / _destroy on it) until wm_sync of this slot has returned.  The library does not
+ * check this. */
+int wm_detect_keys_tiles(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* keys, int tile_rows, int tile_cols,
+                         float* map_dev, double* sums_dev, int* status_out, int slot);
+
 /* makeWatermark (Watermark.cpp:156-172) of every frame of `in_gray` once with EVERY key of the bank as W: one marked copy per
  * recipient.  Copy (f, k) -- frame f marked with key k -- is frame f * nkeys + k of `out`, so out->frames must be
  * in_gray->frames * nkeys; `out` is a WM_MEM_DEVICE plane with the channels and dtype of `base` (any pitch and frame stride; it

@@ -80,6 +80,7 @@ ABI = [
                                    C.c_int]),
     ("wm_tiles_shape", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_int), _P(C.c_int)]),
     ("wm_detect_tiles", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), C.c_int, C.c_int, C.c_void_p, C.c_void_p, _P(C.c_int), C.c_int]),
+    ("wm_detect_keys_tiles", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _P(C.c_int), C.c_int]),
     ("wm_compute_mask", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), _P(wm_plane), _P(wm_plane), _P(C.c_float), _P(C.c_int), C.c_int]),
     ("wm_gram", C.c_int, [_ctx_p, _P(wm_plane), _P(C.c_double), C.c_int]),
     ("wm_band_configure", C.c_int, [_ctx_p, C.c_int, C.c_int, C.c_longlong]),
@@ -513,6 +514,25 @@ class Watermark:
             return (m[0], sums_t.cpu().numpy()[0]) if sums else m[0]
         return (m, sums_t.cpu().numpy()) if sums else m
 
+    def detectKeysTiles(self, image, keys, tile_rows, tile_cols, maskType, sums=False):
+        """whose mark is where?  detectTiles of `image` with every key of the KeySet `keys` in the place of the engine's W, in one
+        call (wm.h wm_detect_keys_tiles): a float32 numpy array [frames, K, ny, nx] ([K, ny, nx] for one grey frame) of tile
+        scores -- the argmax over K names the key a tile was marked with --, 0.0 in every tile of an unsolvable frame, NaN for a
+        zero key or a tile without energy.  sums=True: (map, sums) with sums float64 [..., K, ny, nx, 3] =
+        {<e_u,e_w>, |e_u|^2, |e_w|^2}: they add over tiles and over the frames of a clip"""
+        import torch
+        pimg = plane_of(image, 1)
+        frames, K = pimg.frames, keys.count
+        ny, nx = self.tiles_shape(self.rows, self.cols, tile_rows, tile_cols)
+        map_t = torch.empty((frames, K, ny, nx), dtype=torch.float32, device=image.device)
+        sums_t = torch.empty((frames, K, ny, nx, 3), dtype=torch.float64, device=image.device) if sums else None
+        torch.cuda.current_stream().synchronize()
+        self.detect_keys_tiles_async(image, keys, tile_rows, tile_cols, maskType, WM_SLOT_SYNC, map_t, sums_t)
+        m = map_t.cpu().numpy()
+        if image.dim() == 2:
+            return (m[0], sums_t.cpu().numpy()[0]) if sums else m[0]
+        return (m, sums_t.cpu().numpy()) if sums else m
+
     def makeWatermarkKeys(self, inputImage, outputImage, keys, maskType, out=None):
         """makeWatermark of `inputImage` with every key of the KeySet `keys` as W in one call (wm.h wm_embed_keys).  Returns
         (copies, strengths): copies [K, ...] for one frame ([F, K, ...] for a batch [F, R, C]), copy k marked with key k, each
@@ -637,6 +657,29 @@ class Watermark:
             status = status.ctypes.data_as(_P(C.c_int))
         rc = lib().wm_detect_tiles(self._ctx, int(maskType), C.byref(pimg), tile_rows, tile_cols, C.c_void_p(map_t.data_ptr()),
                                    C.c_void_p(sums_t.data_ptr()) if sums_t is not None else None, status, slot)
+        if rc < 0:
+            _raise(rc, self._ctx)
+
+    def detect_keys_tiles_async(self, image, keys, tile_rows, tile_cols, maskType, slot, map_t, sums_t=None, status=None):
+        """wm_detect_keys_tiles enqueued on `slot`: map_t (a contiguous float32 GPU tensor of frames * K * ny * nx elements) and
+        sums_t (float64, three times as many, may be None) are written on the slot's stream and valid after sync(slot); status
+        (frames ints: a ctypes array or a C-contiguous int32 numpy array, may be None) is written by sync(slot); `keys` must stay
+        alive and unmodified until then"""
+        import torch
+        pimg = self._as_plane(image, 1)
+        ny, nx = self.tiles_shape(self.rows, self.cols, tile_rows, tile_cols)
+        K = keys.count if isinstance(keys, KeySet) else lib().wm_keys_count(keys)
+        n = pimg.frames * K * ny * nx
+        if not (map_t.is_cuda and map_t.dtype == torch.float32 and map_t.is_contiguous() and map_t.numel() == n):
+            raise RuntimeError(f"map_t must be a contiguous float32 GPU tensor of {n} elements")
+        if sums_t is not None and not (sums_t.is_cuda and sums_t.dtype == torch.float64 and sums_t.is_contiguous() and sums_t.numel() == 3 * n):
+            raise RuntimeError(f"sums_t must be a contiguous float64 GPU tensor of {3 * n} elements")
+        if isinstance(status, np.ndarray):
+            assert status.dtype == np.int32 and status.flags.c_contiguous
+            status = status.ctypes.data_as(_P(C.c_int))
+        rc = lib().wm_detect_keys_tiles(self._ctx, int(maskType), C.byref(pimg), keys.handle if isinstance(keys, KeySet) else keys,
+                                        tile_rows, tile_cols, C.c_void_p(map_t.data_ptr()),
+                                        C.c_void_p(sums_t.data_ptr()) if sums_t is not None else None, status, slot)
         if rc < 0:
             _raise(rc, self._ctx)
 

@@ -160,6 +160,8 @@ struct Slot {
     void* ekeys_part = nullptr; size_t ekeys_part_bytes = 0;
     // wm_detect_tiles: per-lane records of k_detect_tiles [frames][nsegs][nstrips][3][64] f32 (grown on demand)
     void* tiles_rec = nullptr; size_t tiles_rec_bytes = 0;
+    // wm_detect_keys_tiles: per-lane records of k_detect_keys_tiles [frames][ngroups][nsegs][nstrips][2 G + 1][64] f32 (grown on demand)
+    void* keys_tiles_rec = nullptr; size_t keys_tiles_rec_bytes = 0;
 };
 
 struct ProfRec { int kid; hipEvent_t a, b; bool first; };  // first: the sweep's first launch (counts the call)
@@ -361,7 +363,7 @@ void free_slot(Slot& s)
     if (s.h_res) (void)hipHostFree(s.h_res);
     if (s.h_coefres) (void)hipHostFree(s.h_coefres);
     (void)hipFree(s.st_in); (void)hipFree(s.st_base); (void)hipFree(s.st_out); (void)hipFree(s.fz_block); (void)hipFree(s.d_ho); (void)hipFree(s.d_hoseam);
-    (void)hipFree(s.d_hodig); (void)hipFree(s.keys_part); (void)hipFree(s.ekeys_part); (void)hipFree(s.tiles_rec);
+    (void)hipFree(s.d_hodig); (void)hipFree(s.keys_part); (void)hipFree(s.ekeys_part); (void)hipFree(s.tiles_rec); (void)hipFree(s.keys_tiles_rec);
     s = Slot();
 }
 
@@ -671,12 +673,19 @@ Staged staged_layout(const wm_plane* pl)
     return s;
 }
 
-int ensure(wm_ctx* ctx, void** buf, size_t* have, size_t need)
+// grow-on-demand device scratch.  alloc_code: what an allocation that does not fit returns (the calls whose wm.h text promises
+// WM_ERR_ALLOC pass it; the others report it like any other runtime failure)
+int ensure(wm_ctx* ctx, void** buf, size_t* have, size_t need, int alloc_code = WM_ERR_RUNTIME)
 {
     if (*have >= need) return WM_OK;
     if (*buf) HIPCHK(ctx, hipFree(*buf));
     *buf = nullptr; *have = 0;
-    HIPCHK(ctx, hipMalloc(buf, need));
+    const hipError_t e = hipMalloc(buf, need);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        *buf = nullptr;
+        return fail(ctx, alloc_code, "hipMalloc(buf, need): " + std::string(hipGetErrorString(e)) + " (" + std::to_string(need) + " bytes of scratch)");
+    }
     *have = need;
     return WM_OK;
 }
@@ -1697,6 +1706,46 @@ int wm_detect_tiles(wm_ctx* ctx, int mask, const wm_plane* img, int tile_rows, i
     if ((rc = gram_sweep(ctx, s, lg, frames, xd, img)) != WM_OK) return rc;
     { ProfScope ps(ctx, K_DETECT_TILES, s.stream); launch_detect_tiles(s.stream, pl, frames, mask, ctx->p / 2, xd, ctx->w->d_w, s.d_coef, s.d_status, (float*)s.tiles_rec); }
     { ProfScope ps(ctx, K_TILES_FOLD, s.stream); launch_tiles_fold(s.stream, pl, frames, (const float*)s.tiles_rec, s.d_status, map_dev, sums_dev, res); }
+    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
+    push_pending(s, frames, 1, false, nullptr, status_out, nullptr);
+    return slot == WM_SLOT_SYNC ? do_sync(ctx, s) : WM_OK;
+}
+
+// wm_detect_tiles with every key of the bank in the place of the context's W: wm_detect_keys' image side (one Gram sweep or
+// hand-over and one solve per frame), k_detect_keys_tiles + k_keys_tiles_fold behind it; map and sums stay on the device.  The two
+// kernels are launched outside any ProfScope: the list of profiling names is not extended for them
+int wm_detect_keys_tiles(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* keys, int tile_rows, int tile_cols, float* map_dev,
+                         double* sums_dev, int* status_out, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    if (!img || !keys || !map_dev) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_keys_tiles: null img, keys or map_dev");
+    int ny = 0, nx = 0;
+    if (wm_tiles_shape(ctx->rows, ctx->cols, tile_rows, tile_cols, &ny, &nx) != WM_OK)
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_keys_tiles: tile shape " + std::to_string(tile_rows) + "x" + std::to_string(tile_cols) +
+                                             " (rows: a multiple of 8, >= 32; columns: a multiple of 4, >= 32)");
+    int rc = check_mask(ctx, mask);
+    if (rc != WM_OK) return rc;
+    if ((rc = check_bank(ctx, keys, "wm_detect_keys_tiles", true)) != WM_OK) return rc;
+    if (ctx->band_hi > 0) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_keys_tiles: not in band mode");
+    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
+    // (open_input checks the plane again: img->frames has to be known to be sane HERE, for the grid check in front of any device work)
+    if ((rc = check_plane(ctx, img, 0, false, "image", true)) != WM_OK) return rc;
+    const int frames = img->frames, nkeys = keys->nkeys;
+    if (!keys_tiles_grids_fit(ctx->rows, ctx->cols, tile_rows, frames, nkeys, ny, nx))
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_keys_tiles: " + std::to_string(frames) + " frames x " + std::to_string(nkeys) + " keys x " +
+                                             std::to_string(ny) + "x" + std::to_string(nx) + " tiles exceed a launch grid of 31 bits");
+    PlaneDesc xd;
+    LaunchGeom lg;
+    if ((rc = open_input(ctx, s, img, "image", mask, 1, nullptr, &xd, &lg)) != WM_OK) return rc;
+    const TilesPlan pl = tiles_plan(lg, frames, mask, ctx->p / 2, xd, aligned_w_of(ctx), tile_rows, tile_cols, ny, nx);
+    if ((rc = ensure(ctx, &s.keys_tiles_rec, &s.keys_tiles_rec_bytes, keys_tiles_rec_bytes(pl, frames, nkeys), WM_ERR_ALLOC)) != WM_OK) return rc;
+    OpResult* res = s.d_res + s.res_used;
+    // the image side is wm_detect's: the Gram sweep (or the hand-over of the slot's last embed) and the solve
+    if ((rc = gram_sweep(ctx, s, lg, frames, xd, img)) != WM_OK) return rc;
+    launch_detect_keys_tiles(s.stream, pl, frames, mask, ctx->p / 2, xd, keys->d, (long long)ctx->rows * ctx->cols, nkeys, s.d_coef, s.d_status,
+                             (float*)s.keys_tiles_rec);
+    launch_keys_tiles_fold(s.stream, pl, frames, nkeys, (const float*)s.keys_tiles_rec, s.d_status, map_dev, sums_dev, res);
     if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
     push_pending(s, frames, 1, false, nullptr, status_out, nullptr);
     return slot == WM_SLOT_SYNC ? do_sync(ctx, s) : WM_OK;

@@ -41,20 +41,6 @@ __global__ __launch_bounds__(BLOCK, WM_DET_BOUNDS) void k_detect_tiles(const T* 
 }
 #undef WM_DET_BOUNDS
 
-// which (strip, lane) of the sweep owns the column group q (columns 4q .. 4q + 3)?
-//   layout 0: strips of 256 columns (the generic instances);
-//   layout 1: overlapped strips, 248 owned columns each, the first owner is lane 1 but for strip 0 (make_job, Geom::sstride);
-//   layout 2: as 1 below column 4 * nown, and the groups nown .. nown + 63 are the 64 lanes of the ONE generic strip that owns
-//             the last 5 .. 7 columns of a width that is not a multiple of 4 (sweep_part_split_generic): all of the last tile column
-__device__ __forceinline__ void tile_owner(const TileGeom& tg, int q, int& strip, int& lane)
-{
-    if (tg.layout == 0) { strip = q >> 6; lane = q & (WAVE - 1); return; }
-    if (q >= tg.nown) { strip = tg.nstrips - 1; lane = q - tg.nown; return; }
-    constexpr int GPS = OV_STRIDE / 4;  // owned groups per overlapped strip
-    strip = q / GPS;
-    lane = q - strip * GPS + (strip > 0 ? OV_LEAD / 4 : 0);
-}
-
 // TPT threads per (frame, tile): thread t adds the tile's records t, t + TPT, ... (record i = segment i / ng, group i % ng of
 // the tile) in f64, the wave adds its lanes in wave_sum's fixed order, and (TPT = 256) thread 0 the four waves in order.
 //   corr = (float)dot / (float)(sqrt(nw) * sqrt(nu))   (Watermark.cpp:230) per tile; unsolvable => 0.0f and zero sums

@@ -246,6 +246,17 @@ void launch_detect_tiles(hipStream_t s, const TilesPlan& pl, int frames, int mas
                          const float* coef, const int* status, float* rec);
 void launch_tiles_fold(hipStream_t s, const TilesPlan& pl, int frames, const float* rec, const int* status, float* map, double* sums,
                        OpResult* res);
+// the detector's three sums per tile of the frame AND per key of a bank (wm_detect_keys_tiles, wm_k_detect_keys_tiles.hip):
+// k_detect_keys' sweep (key groups of detect_keys_group() keys as a grid axis) on the geometry of tiles_plan; every lane leaves its
+// f32 partials in rec [frames][ngroups][nsegs][nstrips][2 G + 1][64] (keys_tiles_rec_bytes), and k_keys_tiles_fold adds each
+// (frame, key, tile)'s records in k_tiles_fold's order into map [frames][nkeys][ny][nx] (and sums [...][3], may be null) on the
+// device and res[frame] = {status, 0}.  keys_tiles_grids_fit: both grids of such a call fit 31 bits (from the shapes alone)
+size_t keys_tiles_rec_bytes(const TilesPlan& pl, int frames, int nkeys);
+bool keys_tiles_grids_fit(int rows, int cols, int tile_rows, int frames, int nkeys, int ny, int nx);
+void launch_detect_keys_tiles(hipStream_t s, const TilesPlan& pl, int frames, int mask, int pad, const PlaneDesc& x, const float* Wbank,
+                              long long kstride, int nkeys, const float* coef, const int* status, float* rec);
+void launch_keys_tiles_fold(hipStream_t s, const TilesPlan& pl, int frames, int nkeys, const float* rec, const int* status, float* map,
+                            double* sums, OpResult* res);
 // one image embedded with every key of a bank (wm_embed_keys, wm_k_embed_keys.hip).  The image side is wm_embed's (launch_gram:
 // coef / status); then k_stats_keys (k_me_stats' / k_nvf_stats' sweep for every key, key groups as a grid axis), one fold block
 // per (frame, key) into res[frame * nkeys + key] and the scalars k_embed_keys reads, and k_embed_keys (k_embed's sweep for every

@@ -299,6 +299,20 @@ static inline SweepPart sweep_part_split_generic(const LaunchGeom& l2, int frame
     return sp;
 }
 
+// the tile folds (k_tiles_fold, k_keys_tiles_fold): which (strip, lane) of the sweep owns the column group q (columns 4q .. 4q + 3)?
+//   layout 0: strips of 256 columns (the generic instances);
+//   layout 1: overlapped strips, 248 owned columns each, the first owner is lane 1 but for strip 0 (make_job, Geom::sstride);
+//   layout 2: as 1 below column 4 * nown, and the groups nown .. nown + 63 are the 64 lanes of the ONE generic strip that owns
+//             the last 5 .. 7 columns of a width that is not a multiple of 4 (sweep_part_split_generic): all of the last tile column
+__device__ __forceinline__ void tile_owner(const TileGeom& tg, int q, int& strip, int& lane)
+{
+    if (tg.layout == 0) { strip = q >> 6; lane = q & (WAVE - 1); return; }
+    if (q >= tg.nown) { strip = tg.nstrips - 1; lane = q - tg.nown; return; }
+    constexpr int GPS = OV_STRIDE / 4;  // owned groups per overlapped strip
+    strip = q / GPS;
+    lane = q - strip * GPS + (strip > 0 ? OV_LEAD / 4 : 0);
+}
+
 // aligned: every plane of the sweep allows 4-pixel vector access at multiples of 4 columns (PlaneDesc::aligned);
 // the shifted strip starts at column cols - 256, which must be a vector boundary of every plane as well:
 // a multiple of 4 columns for f32 planes (16 B), of 16 columns when a u8 plane takes part (its vectors are 4 B, but the
