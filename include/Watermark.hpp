@@ -299,6 +299,71 @@ public:
         if (rd < 0) fail(rd, "detectKeysTiles");
         return map;
     }
+    // a payload in the mark, one bit per tile (wm.h wm_bits_layout): the bit every tile of an ny x nx grid carries, 0 .. nbits - 1,
+    // every bit on floor(T / nbits) or ceil(T / nbits) tiles spread over the frame by a shuffle seeded with `seed`
+    static std::vector<int32_t> bitsLayout(int ny, int nx, int nbits, uint64_t seed)
+    {
+        std::vector<int32_t> tileBit((size_t)(ny > 0 ? ny : 0) * (size_t)(nx > 0 ? nx : 0));
+        const int rc = wm_bits_layout(ny, nx, nbits, seed, tileBit.empty() ? nullptr : tileBit.data());
+        if (rc < 0) throw std::runtime_error(std::string("bitsLayout: ") + wm_strerror(rc));
+        return tileBit;
+    }
+    // makeWatermark with the watermark term of every pixel multiplied by the sign of its tile (wm.h wm_embed_signs): signs
+    // [i * nx + j] in {-1, 0, +1} for tile (i, j) of wm_tiles_shape's grid.  Never the fused kernels; otherwise makeWatermark's rules
+    wm::Image makeWatermarkSigns(const wm::Image& inputImage, const wm::Image& outputImage, float& watermarkStrength, int tileRows, int tileCols,
+                                 const std::vector<int8_t>& signs, MASK_TYPE maskType) const
+    {
+        int ty = 0, tx = 0;
+        int rc = wm_tiles_shape(wm_rows(ctx), wm_cols(ctx), tileRows, tileCols, &ty, &tx);
+        if (rc < 0 || signs.size() != (size_t)ty * (size_t)tx) fail(WM_ERR_BAD_ARG, "makeWatermarkSigns");
+        wm::Image out(outputImage.rows(), outputImage.cols(), outputImage.channels(), outputImage.type(), device);
+        const wm_plane pin = inputImage.plane(), pbase = outputImage.plane(), pout = out.plane();
+        float a = 0.0f;
+        int st = 0;
+        rc = wm_embed_signs(ctx, (int)maskType, &pin, &pbase, &pout, tileRows, tileCols, signs.data(), &a, &st, WM_SLOT_SYNC);
+        if (rc < 0) fail(rc, "makeWatermarkSigns");
+        if (st != 0) return outputImage;  // not solvable: output image without modification, strength untouched
+        watermarkStrength = a;
+        return out;
+    }
+    // makeWatermark that carries `payload` (wm.h wm_embed_bits): (nbits + 7) / 8 bytes, bit b = payload[b / 8] >> (b % 8) & 1; tile
+    // t is marked with +W where bit tileBit[t] is set, with -W where it is not, and left unmarked where tileBit[t] = -1
+    wm::Image makeWatermarkBits(const wm::Image& inputImage, const wm::Image& outputImage, float& watermarkStrength, int tileRows, int tileCols,
+                                const std::vector<int32_t>& tileBit, int nbits, const std::vector<uint8_t>& payload, MASK_TYPE maskType) const
+    {
+        int ty = 0, tx = 0;
+        int rc = wm_tiles_shape(wm_rows(ctx), wm_cols(ctx), tileRows, tileCols, &ty, &tx);
+        if (rc < 0 || tileBit.size() != (size_t)ty * (size_t)tx || nbits < 1 || payload.size() != (size_t)(nbits + 7) / 8) fail(WM_ERR_BAD_ARG, "makeWatermarkBits");
+        wm::Image out(outputImage.rows(), outputImage.cols(), outputImage.channels(), outputImage.type(), device);
+        const wm_plane pin = inputImage.plane(), pbase = outputImage.plane(), pout = out.plane();
+        float a = 0.0f;
+        int st = 0;
+        rc = wm_embed_bits(ctx, (int)maskType, &pin, &pbase, &pout, tileRows, tileCols, tileBit.data(), nbits, payload.data(), &a, &st, WM_SLOT_SYNC);
+        if (rc < 0) fail(rc, "makeWatermarkBits");
+        if (st != 0) return outputImage;
+        watermarkStrength = a;
+        return out;
+    }
+    // reads the payload back (wm.h wm_detect_bits): soft[b] is the score of the pooled tiles of bit b (0 when the system is not
+    // solvable, NaN for a bit without a tile), the decoded bit is soft[b] > 0; `payload`, if given, receives the bits packed as
+    // makeWatermarkBits takes them
+    std::vector<float> detectBits(const wm::Image& watermarkedImage, int tileRows, int tileCols, const std::vector<int32_t>& tileBit, int nbits,
+                                  MASK_TYPE maskType, std::vector<uint8_t>* payload = nullptr) const
+    {
+        int ty = 0, tx = 0;
+        int rc = wm_tiles_shape(wm_rows(ctx), wm_cols(ctx), tileRows, tileCols, &ty, &tx);
+        if (rc < 0 || tileBit.size() != (size_t)ty * (size_t)tx || nbits < 1) fail(WM_ERR_BAD_ARG, "detectBits");
+        const wm_plane pimg = watermarkedImage.plane();
+        std::vector<float> soft((size_t)nbits, 0.0f);
+        rc = wm_detect_bits(ctx, (int)maskType, &pimg, tileRows, tileCols, tileBit.data(), nbits, soft.data(), nullptr, WM_SLOT_SYNC);
+        if (rc < 0) fail(rc, "detectBits");
+        if (payload) {
+            payload->assign((size_t)(nbits + 7) / 8, 0);
+            for (int b = 0; b < nbits; ++b)
+                if (soft[(size_t)b] > 0.0f) (*payload)[(size_t)b / 8] |= (uint8_t)(1u << (b % 8));
+        }
+        return soft;
+    }
     // makeWatermark of one grey image with every key of `keys` as W in one call (wm.h wm_embed_keys): copy k is what
     // makeWatermark returns with key k as W, strengths[k] its strength.  Not solvable: every copy is `outputImage` itself and
     // `strengths` is left untouched (Watermark.cpp:164-165)

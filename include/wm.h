@@ -348,6 +348,77 @@ int wm_detect_tiles(wm_ctx* ctx, int mask, const wm_plane* img, int tile_rows, i
 int wm_detect_keys_tiles(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* keys, int tile_rows, int tile_cols,
                          float* map_dev, double* sums_dev, int* status_out, int slot);
 
+/* ---- A payload in the mark: one bit per tile -------------------------------------------------------------------------------------
+ * A frame is marked with a key or it is not: the mark carries no bits, and naming a recipient costs one key plane each.  But the
+ * detector is local and its score is SIGNED, wm_detect_tiles keeps <e_u,e_w>, ||e_u||^2 and ||e_w||^2 per tile and those sums add,
+ * and the strength a = sF / (||m W|| / sqrt(N)) does not change when W changes sign anywhere.  A frame whose tile (ty, tx) is marked
+ * with s W, s = +-1, therefore carries one bit per tile, read back from the sign of the tile's <e_u,e_w>; several tiles that carry
+ * the same bit pool their sums.  One ID of up to a few hundred bits costs one key and one wm_detect_tiles-sized call.
+ * Tile geometry is wm_tiles_shape's throughout, unchanged: tile_rows a multiple of 8 and >= 32, tile_cols a multiple of 4 and
+ * >= 32, the last tile of each axis takes the remainder; tables are row-major over (ty, tx), T = ny * nx entries.
+ * How many tiles per bit?  At psnr 40, p = 3, u8 output, the weakest bit of a marked frame scores |soft| 0.42 (ME) and 0.16 (NVF)
+ * with ONE 32 x 32 tile per bit, where an unmarked frame reaches 0.13 / 0.12: NVF with one 32 x 32 tile per bit is close to the
+ * unmarked level -- use two tiles per bit or more there (0.25 against 0.09 at 270 x 480 with 48 bits).
+ *
+ * wm_bits_layout: which bit does tile t carry?  perm = 0 .. T - 1; for i = T - 1 down to 1: j = next() mod (i + 1), swap perm[i] and
+ * perm[j]; tile_bit[t] = perm[t] mod nbits, where next() is splitmix64 started at state = seed (state += 0x9E3779B97F4A7C15;
+ * z = state; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; return z ^ z >> 31; modulo 2^64).
+ * Every bit gets floor(T / nbits) or ceil(T / nbits) tiles, spread over the frame.  WM_OK, or WM_ERR_BAD_ARG unless
+ * 1 <= nbits <= min(T, 4096), ny, nx >= 1 and tile_bit is non-null.  Pure host arithmetic; it touches no device.
+ *
+ * wm_embed_signs: makeWatermark (Watermark.cpp:156-172) with the watermark term of every pixel multiplied by the sign of its tile:
+ *     y = clamp(base + a * s(ty, tx) * m * W, 0, 255)
+ * signs is a HOST array [frames][ny][nx] of -1, 0 or +1.  The Gram sweep, the solve and the stats sweep are wm_embed's own (||u||
+ * does not see the signs); only the last sweep is new (k_embed_signs).  Bit for bit against wm_embed on the batched sweeps
+ * (wm_set_fused(0)): `a` is wm_embed's with the context's W; a pixel in a +1 tile is wm_embed's pixel; a pixel in a -1 tile is
+ * wm_embed's pixel on a context whose W is -W; a pixel in a 0 tile is clamp(base, 0, 255) -- for planes in the documented range base
+ * itself, which wm_embed with a zero W returns.  An unsolvable frame and a zero-energy frame follow wm_embed's rules unchanged.
+ *   - Takes every input wm_embed takes on the sweeps: f32 / u8, a grey or planar-RGB base (all channels take the tile's sign), a
+ *     base that is in_gray, in place (with the snapshot), any pitch and width, WM_MEM_HOST in and out, WM_MEM_SLOT_OUT for in_gray,
+ *     batches up to max_frames, ME with p = 3 (WM_ERR_BAD_P otherwise), NVF with p = 3..9.
+ *   - Never takes the fused single-launch kernels.  Refused in band mode (WM_ERR_BAD_ARG).
+ *   - An ENQUEUE on the slot like wm_embed (WM_SLOT_SYNC: slot 0, waits); `frames` results count against the slot's capacity of
+ *     4096 un-synced results.  Its output becomes what WM_MEM_SLOT_OUT names, as wm_embed's does.  Unlike wm_embed it leaves NO Gram
+ *     hand-over behind, checked or promised, and like every library write it ends a hand-over whose plane it overwrites.
+ *   - `signs` is read before the call returns: the caller may change or free it at once, and several un-synced calls on one slot
+ *     each keep their own table.  The copies live in a pinned host arena and a device arena per slot, reset by wm_sync and grown
+ *     on demand: the FIRST call on a slot that needs more of them than are left -- larger tables, or more un-synced calls than
+ *     before -- waits for the slot's stream and reallocates them, which waits for the whole device, the other slots' streams
+ *     included.  Later calls only enqueue.  k_embed_signs is not in the wm_prof_* list.
+ *   - WM_ERR_BAD_ARG, before any device work, for a null ctx, plane or signs, a tile shape wm_tiles_shape refuses and a sign
+ *     outside {-1, 0, +1}.
+ *
+ * wm_embed_bits: a host layer over wm_embed_signs.  tile_bit is a HOST array [ny * nx] (wm_bits_layout's, or the caller's own): a
+ * tile with tile_bit[t] = b >= 0 gets +1 where payload bit b is 1 and -1 where it is 0, a tile with tile_bit[t] = -1 gets 0 (left
+ * unmarked).  payload is a HOST array [frames][(nbits + 7) / 8], bit b = payload[b / 8] >> (b % 8) & 1.  WM_ERR_BAD_ARG unless
+ * 1 <= nbits <= 4096 and every entry lies in -1 .. nbits - 1; everything else is wm_embed_signs'.
+ *
+ * wm_detect_bits: wm_detect_tiles' call with one more fold.  Inputs, the Gram sweep with the hand-over, the solve, k_detect_tiles
+ * and k_tiles_fold (into slot-owned scratch) are wm_detect_tiles'; then for bit b the three f64 sums of the tiles with
+ * tile_bit == b are added IN ASCENDING TILE INDEX, one after the other (k_bits_fold), and
+ *     soft[f][b] = (float)dot / (float)(sqrt(nw) * sqrt(nu)),
+ * the expression every detector here uses.  The decoded bit is soft > 0.  soft_out is a HOST array [frames][nbits] written by
+ * wm_sync, status_out[frames] may be NULL.
+ *   - A bit with no tile scores NaN (the zero-W rule).  An unsolvable frame gives 0.0f for every bit and status WM_UNSOLVABLE.
+ *   - Delivery is through the slot's result records, as for wm_detect_keys: frames * nbits results count against the capacity of
+ *     4096 un-synced results; beyond it the call returns WM_ERR_BUSY.
+ *   - Bits: soft[f][b] equals, bit for bit, that expression over wm_detect_tiles' sums_dev of the same plane added sequentially
+ *     in that order; it does not depend on the batch or on repetition.
+ *   - tile_bit is read before the call returns (kept like wm_embed_signs' table, with the same caveat for the first call that
+ *     grows the arenas; the tile sums' scratch is grown on demand like wm_detect_tiles' record scratch).  Never takes the fused
+ *     kernels; refused in band mode; k_bits_fold is not in the wm_prof_* list.
+ *   - WM_ERR_BAD_ARG, before any device work, for a null ctx, img, tile_bit or soft_out, a tile shape wm_tiles_shape refuses,
+ *     nbits outside 1 .. 4096 and a tile_bit entry outside -1 .. nbits - 1. */
+int wm_bits_layout(int ny, int nx, int nbits, uint64_t seed, int32_t* tile_bit /* [ny*nx] */);
+int wm_embed_signs(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* base, const wm_plane* out, int tile_rows, int tile_cols,
+                   const int8_t* signs /* HOST [frames][ny][nx], -1 | 0 | +1 */, float* a_out, int* status_out, int slot);
+int wm_embed_bits(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* base, const wm_plane* out, int tile_rows, int tile_cols,
+                  const int32_t* tile_bit /* HOST [ny*nx], -1 .. nbits-1 */, int nbits,
+                  const uint8_t* payload /* HOST [frames][(nbits+7)/8], bit b = payload[b/8] >> (b%8) & 1 */, float* a_out,
+                  int* status_out, int slot);
+int wm_detect_bits(wm_ctx* ctx, int mask, const wm_plane* img, int tile_rows, int tile_cols, const int32_t* tile_bit, int nbits,
+                   float* soft_out /* HOST [frames][nbits], by wm_sync */, int* status_out, int slot);
+
 /* makeWatermark (Watermark.cpp:156-172) of every frame of `in_gray` once with EVERY key of the bank as W: one marked copy per
  * recipient.  Copy (f, k) -- frame f marked with key k -- is frame f * nkeys + k of `out`, so out->frames must be
  * in_gray->frames * nkeys; `out` is a WM_MEM_DEVICE plane with the channels and dtype of `base` (any pitch and frame stride; it

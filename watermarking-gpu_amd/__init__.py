@@ -81,6 +81,12 @@ ABI = [
     ("wm_tiles_shape", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_int), _P(C.c_int)]),
     ("wm_detect_tiles", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), C.c_int, C.c_int, C.c_void_p, C.c_void_p, _P(C.c_int), C.c_int]),
     ("wm_detect_keys_tiles", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _P(C.c_int), C.c_int]),
+    ("wm_bits_layout", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_uint64, _P(C.c_int32)]),
+    ("wm_embed_signs", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), _P(wm_plane), _P(wm_plane), C.c_int, C.c_int, C.c_void_p, _P(C.c_float), _P(C.c_int),
+                                C.c_int]),
+    ("wm_embed_bits", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), _P(wm_plane), _P(wm_plane), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                               _P(C.c_float), _P(C.c_int), C.c_int]),
+    ("wm_detect_bits", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), C.c_int, C.c_int, C.c_void_p, C.c_int, _P(C.c_float), _P(C.c_int), C.c_int]),
     ("wm_compute_mask", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), _P(wm_plane), _P(wm_plane), _P(C.c_float), _P(C.c_int), C.c_int]),
     ("wm_gram", C.c_int, [_ctx_p, _P(wm_plane), _P(C.c_double), C.c_int]),
     ("wm_band_configure", C.c_int, [_ctx_p, C.c_int, C.c_int, C.c_longlong]),
@@ -533,6 +539,57 @@ class Watermark:
             return (m[0], sums_t.cpu().numpy()[0]) if sums else m[0]
         return (m, sums_t.cpu().numpy()) if sums else m
 
+    @staticmethod
+    def bits_layout(ny, nx, nbits, seed):
+        """which bit does tile t carry?  wm_bits_layout's table: an int32 numpy array [ny * nx] with entries 0 .. nbits - 1, every
+        bit on floor(T / nbits) or ceil(T / nbits) tiles spread over the frame by a shuffle seeded with `seed`"""
+        tb = np.empty(max(ny, 0) * max(nx, 0), np.int32)
+        rc = lib().wm_bits_layout(ny, nx, nbits, int(seed) & 0xFFFFFFFFFFFFFFFF, tb.ctypes.data_as(_P(C.c_int32)))
+        if rc != WM_OK:
+            _raise(rc)
+        return tb
+
+    def _embed_tiles(self, how, inputImage, outputImage, maskType, out):
+        import torch
+        rgb = outputImage.dim() - inputImage.dim() == 1
+        if out is None:
+            out = torch.empty_like(outputImage)
+        frames = plane_of(inputImage, 1).frames
+        a = (C.c_float * frames)(*([float("nan")] * frames))
+        st = (C.c_int * frames)()
+        torch.cuda.current_stream().synchronize()
+        how(inputImage, outputImage, out, maskType, WM_SLOT_SYNC, a, st)
+        if inputImage.dim() == 2:
+            return out, (None if st[0] != 0 else a[0])
+        return out, [None if st[f] != 0 else a[f] for f in range(frames)]
+
+    def makeWatermarkSigns(self, inputImage, outputImage, tile_rows, tile_cols, signs, maskType, out=None):
+        """makeWatermark with the watermark term of every pixel multiplied by the sign of its tile (wm.h wm_embed_signs): `signs`
+        is an integer array [ny, nx] ([F, ny, nx] for a batch) of -1, 0 or +1.  Returns (watermarked, strength) as makeWatermark
+        does; never takes the fused kernels"""
+        return self._embed_tiles(lambda i, b, o, m, slot, a, st: self.embed_signs_async(i, b, o, tile_rows, tile_cols, signs, m, slot, a, st),
+                                 inputImage, outputImage, maskType, out)
+
+    def makeWatermarkBits(self, inputImage, outputImage, tile_rows, tile_cols, tile_bit, nbits, payload, maskType, out=None):
+        """makeWatermark that carries `payload` (wm.h wm_embed_bits): bytes (or a uint8 array) of (nbits + 7) // 8 bytes per frame,
+        bit b = payload[b // 8] >> (b % 8) & 1; tile t is marked with +W where bit tile_bit[t] is set, with -W where it is not, and
+        left unmarked where tile_bit[t] = -1 (tile_bit: bits_layout's table or the caller's own).  Returns (watermarked, strength)"""
+        return self._embed_tiles(lambda i, b, o, m, slot, a, st: self.embed_bits_async(i, b, o, tile_rows, tile_cols, tile_bit, nbits, payload, m, slot, a, st),
+                                 inputImage, outputImage, maskType, out)
+
+    def detectBits(self, image, tile_rows, tile_cols, tile_bit, nbits, maskType):
+        """reads the payload back (wm.h wm_detect_bits): (payload, soft) with soft a float32 numpy array [nbits] ([F, nbits] for a
+        batch) -- the score of the pooled tiles of every bit, 0.0 for an unsolvable frame, NaN for a bit without a tile -- and
+        payload the decoded bits soft > 0 packed as makeWatermarkBits takes them: bytes for one frame, a list of bytes for a batch"""
+        import torch
+        pimg = plane_of(image, 1)
+        frames = pimg.frames
+        soft = np.zeros((frames, max(nbits, 0)), np.float32)
+        torch.cuda.current_stream().synchronize()
+        self.detect_bits_async(image, tile_rows, tile_cols, tile_bit, nbits, maskType, WM_SLOT_SYNC, soft)
+        packed = [np.packbits(soft[f] > 0, bitorder="little").tobytes() for f in range(frames)]
+        return (packed[0], soft[0]) if image.dim() == 2 else (packed, soft)
+
     def makeWatermarkKeys(self, inputImage, outputImage, keys, maskType, out=None):
         """makeWatermark of `inputImage` with every key of the KeySet `keys` as W in one call (wm.h wm_embed_keys).  Returns
         (copies, strengths): copies [K, ...] for one frame ([F, K, ...] for a batch [F, R, C]), copy k marked with key k, each
@@ -705,6 +762,77 @@ class Watermark:
             status_out = status_out.ctypes.data_as(_P(C.c_int))
         rc = lib().wm_embed_keys(self._ctx, int(maskType), C.byref(pin), C.byref(pbase), keys.handle if isinstance(keys, KeySet) else keys,
                                  C.byref(pout), a_out, status_out, slot)
+        if rc < 0:
+            _raise(rc, self._ctx)
+
+    @staticmethod
+    def _host_table(a, dtype, n, what):
+        t = np.ascontiguousarray(a, dtype=dtype).reshape(-1)
+        if t.size != n:
+            raise RuntimeError(f"{what} must hold {n} entries, got {t.size}")
+        return t
+
+    @staticmethod
+    def _scalars_out(a_out, status_out):
+        if isinstance(a_out, np.ndarray):
+            assert a_out.dtype == np.float32 and a_out.flags.c_contiguous
+            a_out = a_out.ctypes.data_as(_P(C.c_float))
+        if isinstance(status_out, np.ndarray):
+            assert status_out.dtype == np.int32 and status_out.flags.c_contiguous
+            status_out = status_out.ctypes.data_as(_P(C.c_int))
+        return a_out, status_out
+
+    def _embed_planes(self, inputImage, outputImage, out):
+        if isinstance(outputImage, wm_plane):
+            ch = outputImage.channels
+        elif isinstance(inputImage, wm_plane):
+            raise RuntimeError("with a wm_plane inputImage, pass outputImage as a wm_plane too")
+        else:
+            ch = 3 if outputImage.dim() - inputImage.dim() == 1 else 1
+        return self._as_plane(inputImage, 1), self._as_plane(outputImage, ch), self._as_plane(out, ch)
+
+    def embed_signs_async(self, inputImage, outputImage, out, tile_rows, tile_cols, signs, maskType, slot, a_out=None, status_out=None):
+        """wm_embed_signs enqueued on `slot`: `signs` (frames * ny * nx integers of -1, 0, +1) is copied before the call returns;
+        a_out (frames floats) and status_out (frames ints) -- ctypes arrays or C-contiguous numpy arrays, may be None -- are
+        written by sync(slot)"""
+        pin, pbase, pout = self._embed_planes(inputImage, outputImage, out)
+        ny, nx = self.tiles_shape(self.rows, self.cols, tile_rows, tile_cols)
+        raw = np.asarray(signs)
+        if raw.dtype != np.int8 and raw.size and (raw.min() < -128 or raw.max() > 127):  # (values the int8 table cannot hold)
+            _raise(WM_ERR_BAD_ARG)
+        sg = self._host_table(raw, np.int8, pin.frames * ny * nx, "signs")
+        a_out, status_out = self._scalars_out(a_out, status_out)
+        rc = lib().wm_embed_signs(self._ctx, int(maskType), C.byref(pin), C.byref(pbase), C.byref(pout), tile_rows, tile_cols,
+                                  sg.ctypes.data_as(C.c_void_p), a_out, status_out, slot)
+        if rc < 0:
+            _raise(rc, self._ctx)
+
+    def embed_bits_async(self, inputImage, outputImage, out, tile_rows, tile_cols, tile_bit, nbits, payload, maskType, slot, a_out=None,
+                         status_out=None):
+        """wm_embed_bits enqueued on `slot`: tile_bit (ny * nx int32) and payload (frames * ((nbits + 7) // 8) bytes: bytes or a uint8
+        array) are read before the call returns; a_out / status_out as for embed_signs_async"""
+        pin, pbase, pout = self._embed_planes(inputImage, outputImage, out)
+        ny, nx = self.tiles_shape(self.rows, self.cols, tile_rows, tile_cols)
+        tb = self._host_table(tile_bit, np.int32, ny * nx, "tile_bit")
+        if isinstance(payload, (bytes, bytearray)):
+            payload = np.frombuffer(bytes(payload), np.uint8)
+        pl = self._host_table(payload, np.uint8, pin.frames * ((max(nbits, 1) + 7) // 8), "payload")
+        a_out, status_out = self._scalars_out(a_out, status_out)
+        rc = lib().wm_embed_bits(self._ctx, int(maskType), C.byref(pin), C.byref(pbase), C.byref(pout), tile_rows, tile_cols,
+                                 tb.ctypes.data_as(C.c_void_p), nbits, pl.ctypes.data_as(C.c_void_p), a_out, status_out, slot)
+        if rc < 0:
+            _raise(rc, self._ctx)
+
+    def detect_bits_async(self, image, tile_rows, tile_cols, tile_bit, nbits, maskType, slot, soft_out, status_out=None):
+        """wm_detect_bits enqueued on `slot`: tile_bit (ny * nx int32) is read before the call returns; soft_out (frames * nbits
+        floats: a ctypes array or a C-contiguous float32 numpy array) and status_out (frames ints, may be None) are written by
+        sync(slot)"""
+        pimg = self._as_plane(image, 1)
+        ny, nx = self.tiles_shape(self.rows, self.cols, tile_rows, tile_cols)
+        tb = self._host_table(tile_bit, np.int32, ny * nx, "tile_bit")
+        soft_out, status_out = self._scalars_out(soft_out, status_out)
+        rc = lib().wm_detect_bits(self._ctx, int(maskType), C.byref(pimg), tile_rows, tile_cols, tb.ctypes.data_as(C.c_void_p), nbits,
+                                  soft_out, status_out, slot)
         if rc < 0:
             _raise(rc, self._ctx)
 

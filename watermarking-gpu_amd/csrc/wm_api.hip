@@ -162,6 +162,12 @@ struct Slot {
     void* tiles_rec = nullptr; size_t tiles_rec_bytes = 0;
     // wm_detect_keys_tiles: per-lane records of k_detect_keys_tiles [frames][ngroups][nsegs][nstrips][2 G + 1][64] f32 (grown on demand)
     void* keys_tiles_rec = nullptr; size_t keys_tiles_rec_bytes = 0;
+    // wm_embed_signs / wm_detect_bits: the tables of the slot's un-synced calls (sign tables, tile lists per bit).  A call copies
+    // its table into the pinned host arena and queues the upload into the device arena at the same offset, so every queued call
+    // keeps its own; wm_sync resets both, table_room grows them on demand
+    void* tab_host = nullptr; void* tab_dev = nullptr; size_t tab_bytes = 0, tab_used = 0;
+    // wm_detect_bits: what its tile fold writes (sums [frames][ny * nx][3] f64, records [frames], map [frames][ny * nx] f32; grown on demand)
+    void* bits_scr = nullptr; size_t bits_scr_bytes = 0;
 };
 
 struct ProfRec { int kid; hipEvent_t a, b; bool first; };  // first: the sweep's first launch (counts the call)
@@ -364,6 +370,8 @@ void free_slot(Slot& s)
     if (s.h_coefres) (void)hipHostFree(s.h_coefres);
     (void)hipFree(s.st_in); (void)hipFree(s.st_base); (void)hipFree(s.st_out); (void)hipFree(s.fz_block); (void)hipFree(s.d_ho); (void)hipFree(s.d_hoseam);
     (void)hipFree(s.d_hodig); (void)hipFree(s.keys_part); (void)hipFree(s.ekeys_part); (void)hipFree(s.tiles_rec); (void)hipFree(s.keys_tiles_rec);
+    if (s.tab_host) (void)hipHostFree(s.tab_host);
+    (void)hipFree(s.tab_dev); (void)hipFree(s.bits_scr);
     s = Slot();
 }
 
@@ -690,6 +698,37 @@ int ensure(wm_ctx* ctx, void** buf, size_t* have, size_t need, int alloc_code = 
     return WM_OK;
 }
 
+// `bytes` of the slot's table arenas for one call (Slot::tab_host / tab_dev): the call fills *host and table_upload queues the
+// copy to *dev.  The arenas are reset by wm_sync; a call that does not fit waits for the slot's stream (the queued calls still
+// read their tables), then for the device (hipFree), and starts a larger pair
+int table_room(wm_ctx* ctx, Slot& s, size_t bytes, void** host, void** dev)
+{
+    bytes = (bytes + 255) & ~(size_t)255;
+    if (s.tab_used + bytes > s.tab_bytes) {
+        HIPCHK(ctx, hipStreamSynchronize(s.stream));
+        const size_t need = std::max(std::max(2 * s.tab_bytes, bytes), (size_t)65536);
+        if (s.tab_host) HIPCHK(ctx, hipHostFree(s.tab_host));
+        s.tab_host = nullptr;
+        if (s.tab_dev) HIPCHK(ctx, hipFree(s.tab_dev));
+        s.tab_dev = nullptr; s.tab_bytes = 0; s.tab_used = 0;
+        if (hipHostMalloc(&s.tab_host, need) != hipSuccess || hipMalloc(&s.tab_dev, need) != hipSuccess) {
+            (void)hipGetLastError();
+            if (s.tab_host) (void)hipHostFree(s.tab_host);
+            s.tab_host = nullptr; s.tab_dev = nullptr;
+            return fail(ctx, WM_ERR_ALLOC, "table arenas: " + std::to_string(need) + " bytes");
+        }
+        s.tab_bytes = need;
+    }
+    *host = (char*)s.tab_host + s.tab_used; *dev = (char*)s.tab_dev + s.tab_used;
+    s.tab_used += bytes;
+    return WM_OK;
+}
+int table_upload(wm_ctx* ctx, Slot& s, const void* host, void* dev, size_t bytes)
+{
+    HIPCHK(ctx, hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, s.stream));
+    return WM_OK;
+}
+
 // host plane -> staging (H2D), every (frame, channel) plane as one 2D copy (de-pitching like main.cpp:348-353)
 int stage_in(wm_ctx* ctx, Slot& s, const wm_plane* pl, void* dst, const Staged& st)
 {
@@ -897,6 +936,7 @@ int deliver(Slot& s)
     }
     s.pending.clear();
     s.res_used = 0;
+    s.tab_used = 0;  // (every queued call has run: their tables are free)
     return rc;
 }
 
@@ -1748,6 +1788,188 @@ int wm_detect_keys_tiles(wm_ctx* ctx, int mask, const wm_plane* img, const wm_ke
     launch_keys_tiles_fold(s.stream, pl, frames, nkeys, (const float*)s.keys_tiles_rec, s.d_status, map_dev, sums_dev, res);
     if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
     push_pending(s, frames, 1, false, nullptr, status_out, nullptr);
+    return slot == WM_SLOT_SYNC ? do_sync(ctx, s) : WM_OK;
+}
+
+// ---- a payload in the mark: wm_bits_layout, wm_embed_signs, wm_embed_bits, wm_detect_bits --------------------------------------
+// which bit does tile t carry?  A Fisher-Yates shuffle of 0 .. T - 1 driven by splitmix64(seed), then mod nbits: every bit owns
+// floor(T / nbits) or ceil(T / nbits) tiles, spread over the frame (pure host arithmetic)
+int wm_bits_layout(int ny, int nx, int nbits, uint64_t seed, int32_t* tile_bit)
+{
+    if (!tile_bit || ny < 1 || nx < 1) return WM_ERR_BAD_ARG;
+    const long long T = (long long)ny * nx;
+    if (nbits < 1 || nbits > 4096 || nbits > T || T > (1LL << 30)) return WM_ERR_BAD_ARG;
+    std::vector<int32_t> perm((size_t)T);
+    for (long long t = 0; t < T; ++t) perm[(size_t)t] = (int32_t)t;
+    uint64_t state = seed;
+    for (long long i = T - 1; i >= 1; --i) {
+        state += 0x9E3779B97F4A7C15ULL;
+        uint64_t z = state;
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+        z ^= z >> 31;
+        std::swap(perm[(size_t)i], perm[(size_t)(z % (uint64_t)(i + 1))]);
+    }
+    for (long long t = 0; t < T; ++t) tile_bit[t] = perm[(size_t)t] % nbits;
+    return WM_OK;
+}
+
+// makeWatermark with the watermark term of every pixel multiplied by the sign of its tile: wm_embed's input, base and output
+// handling and its Gram, solve and stats sweeps (||u|| does not see the signs); k_embed_signs in k_embed's place.  Never the fused
+// kernels, no Gram hand-over.  k_embed_signs is launched outside any ProfScope: the list of profiling names is not extended for it
+int wm_embed_signs(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* base, const wm_plane* out, int tile_rows, int tile_cols,
+                   const int8_t* signs, float* a_out, int* status_out, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    if (!in_gray || !base || !out || !signs) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_signs: null in_gray, base, out or signs");
+    int ny = 0, nx = 0;
+    if (wm_tiles_shape(ctx->rows, ctx->cols, tile_rows, tile_cols, &ny, &nx) != WM_OK)
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_signs: tile shape " + std::to_string(tile_rows) + "x" + std::to_string(tile_cols) +
+                                             " (rows: a multiple of 8, >= 32; columns: a multiple of 4, >= 32)");
+    int rc = check_mask(ctx, mask);
+    if (rc != WM_OK) return rc;
+    if (ctx->band_hi > 0) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_signs: not in band mode");
+    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
+    if ((rc = check_plane(ctx, in_gray, 0, false, "in_gray", true)) != WM_OK) return rc;
+    const int frames = in_gray->frames;
+    if ((rc = check_plane(ctx, base, frames, true, "base")) != WM_OK) return rc;
+    if ((rc = check_plane(ctx, out, frames, true, "out")) != WM_OK) return rc;
+    if (out->channels != base->channels || out->dtype != base->dtype) return fail(ctx, WM_ERR_BAD_ARG, "out must have the shape and dtype of base");
+    if (in_gray->dtype != base->dtype) return fail(ctx, WM_ERR_BAD_ARG, "in_gray and base must have the same dtype (the reference converts whole frames, main.cpp:355-357)");
+    const size_t nsigns = (size_t)frames * ny * nx;
+    for (size_t i = 0; i < nsigns; ++i)
+        if (signs[i] < -1 || signs[i] > 1)
+            return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_signs: sign " + std::to_string((int)signs[i]) + " at index " + std::to_string(i) + " (must be -1, 0 or +1)");
+    if ((rc = check_res_room(ctx, s, frames)) != WM_OK) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+
+    // the call's own copy of the table: the caller's array is free when this function returns
+    void *th = nullptr, *td = nullptr;
+    if ((rc = table_room(ctx, s, nsigns, &th, &td)) != WM_OK) return rc;
+    std::memcpy(th, signs, nsigns);
+    if ((rc = table_upload(ctx, s, th, td, nsigns)) != WM_OK) return rc;
+
+    PlaneDesc xd, bd, od;
+    Staged st_out_l;
+    if ((rc = prep_input(ctx, s, in_gray, &xd)) != WM_OK) return rc;
+    if ((rc = prep_base(ctx, s, in_gray, base, xd, &bd)) != WM_OK) return rc;
+    if ((rc = prep_out(ctx, s, out, &od, &st_out_l)) != WM_OK) return rc;
+    const bool inplace = descs_overlap(xd, od, ctx->rows, ctx->cols, frames);
+    s.ho.valid = false;  // (no hand-over of its own; whatever this call writes replaces the plane one described)
+    invalidate_handovers(ctx, od, frames);
+    if (inplace) {
+        // wm_embed's snapshot of the mask source (and of a base that is the input plane)
+        Staged st = staged_layout(in_gray);
+        if ((rc = ensure(ctx, &s.st_in, &s.st_in_bytes, st.bytes)) != WM_OK) return rc;
+        if ((rc = snapshot(ctx, s, xd, in_gray, s.st_in, st)) != WM_OK) return rc;
+        const bool base_is_input = bd.p == xd.p && bd.pitch == xd.pitch && bd.fstride == xd.fstride && bd.dtype == xd.dtype && bd.channels == 1;
+        xd = st.d; xd.p = s.st_in;
+        if (base_is_input) bd = xd;
+    }
+    LaunchGeom lg;
+    if ((rc = geom_checked(ctx, frames, mask, &lg)) != WM_OK) return rc;
+    OpResult* res = s.d_res + s.res_used;
+    if (mask == WM_MASK_ME) sweep_gram(ctx, s, K_GRAM, lg, frames, xd);
+    sweep_stats(ctx, s, true, lg, frames, mask, xd, res);
+    if (mask == WM_MASK_ME)
+        launch_embed_signs(s.stream, lg, frames, 0, 1, xd, ctx->w->d_w, aligned_w_of(ctx), bd, od, s.d_coef, s.d_status, s.d_scal, (const signed char*)td, tile_rows, tile_cols, ny, nx);
+    else
+        launch_embed_signs(s.stream, lg, frames, 1, ctx->p / 2, xd, ctx->w->d_w, aligned_w_of(ctx), bd, od, nullptr, nullptr, s.d_scal, (const signed char*)td, tile_rows, tile_cols, ny, nx);
+    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
+    if (out->mem == WM_MEM_HOST && (rc = stage_out(ctx, s, out, s.st_out, st_out_l)) != WM_OK) return rc;
+    s.last_out = od; s.last_out_frames = frames; s.last_out_dtype = out->dtype;
+    push_pending(s, frames, 1, true, a_out, status_out, nullptr);
+    return slot == WM_SLOT_SYNC ? do_sync(ctx, s) : WM_OK;
+}
+
+// tile_bit [ny * nx] in -1 .. nbits - 1 (the caller has checked nbits)
+static bool tile_bits_ok(const int32_t* tile_bit, long long T, int nbits)
+{
+    for (long long t = 0; t < T; ++t)
+        if (tile_bit[t] < -1 || tile_bit[t] >= nbits) return false;
+    return true;
+}
+
+// a host layer over wm_embed_signs: tile t carries payload bit tile_bit[t] as +1 (bit set) or -1, or nothing (tile_bit[t] = -1)
+int wm_embed_bits(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* base, const wm_plane* out, int tile_rows, int tile_cols,
+                  const int32_t* tile_bit, int nbits, const uint8_t* payload, float* a_out, int* status_out, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    if (!in_gray || !tile_bit || !payload) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_bits: null in_gray, tile_bit or payload");
+    int ny = 0, nx = 0;
+    if (wm_tiles_shape(ctx->rows, ctx->cols, tile_rows, tile_cols, &ny, &nx) != WM_OK)
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_bits: tile shape " + std::to_string(tile_rows) + "x" + std::to_string(tile_cols) +
+                                             " (rows: a multiple of 8, >= 32; columns: a multiple of 4, >= 32)");
+    const long long T = (long long)ny * nx;
+    if (nbits < 1 || nbits > 4096 || !tile_bits_ok(tile_bit, T, nbits))
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_bits: nbits must be 1 .. 4096 and every tile_bit entry -1 .. nbits - 1");
+    if (in_gray->frames < 1 || in_gray->frames > ctx->max_frames)
+        return fail(ctx, WM_ERR_BAD_ARG, "in_gray: frames=" + std::to_string(in_gray->frames) + " exceeds wm_configure max_frames=" + std::to_string(ctx->max_frames));
+    const int frames = in_gray->frames, pbytes = (nbits + 7) / 8;
+    std::vector<int8_t> signs((size_t)frames * T);
+    for (int f = 0; f < frames; ++f)
+        for (long long t = 0; t < T; ++t) {
+            const int b = tile_bit[t];
+            signs[(size_t)f * T + t] = b < 0 ? 0 : (((payload[(size_t)f * pbytes + b / 8] >> (b % 8)) & 1) ? 1 : -1);
+        }
+    return wm_embed_signs(ctx, mask, in_gray, base, out, tile_rows, tile_cols, signs.data(), a_out, status_out, slot);
+}
+
+// wm_detect_tiles with one more fold: the tile sums land in slot-owned scratch and k_bits_fold adds each bit's tiles in ascending
+// tile index into one result record per (frame, bit).  k_bits_fold is launched outside any ProfScope
+int wm_detect_bits(wm_ctx* ctx, int mask, const wm_plane* img, int tile_rows, int tile_cols, const int32_t* tile_bit, int nbits, float* soft_out,
+                   int* status_out, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    if (!img || !tile_bit || !soft_out) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_bits: null img, tile_bit or soft_out");
+    int ny = 0, nx = 0;
+    if (wm_tiles_shape(ctx->rows, ctx->cols, tile_rows, tile_cols, &ny, &nx) != WM_OK)
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_bits: tile shape " + std::to_string(tile_rows) + "x" + std::to_string(tile_cols) +
+                                             " (rows: a multiple of 8, >= 32; columns: a multiple of 4, >= 32)");
+    const int T = ny * nx;
+    if (nbits < 1 || nbits > 4096 || !tile_bits_ok(tile_bit, T, nbits))
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_bits: nbits must be 1 .. 4096 and every tile_bit entry -1 .. nbits - 1");
+    int rc = check_mask(ctx, mask);
+    if (rc != WM_OK) return rc;
+    if (ctx->band_hi > 0) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_bits: not in band mode");
+    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
+    PlaneDesc xd;
+    LaunchGeom lg;
+    if ((rc = open_input(ctx, s, img, "image", mask, nbits, "bits", &xd, &lg)) != WM_OK) return rc;
+    const int frames = img->frames;
+    const TilesPlan pl = tiles_plan(lg, frames, mask, ctx->p / 2, xd, aligned_w_of(ctx), tile_rows, tile_cols, ny, nx);
+    if ((rc = ensure(ctx, &s.tiles_rec, &s.tiles_rec_bytes, pl.rec_bytes)) != WM_OK) return rc;
+    // the tile fold's output: sums [frames][T][3] f64, its status records [frames], map [frames][T] f32
+    const size_t nt = (size_t)frames * T;
+    if ((rc = ensure(ctx, &s.bits_scr, &s.bits_scr_bytes, nt * 3 * sizeof(double) + (size_t)frames * sizeof(OpResult) + nt * sizeof(float))) != WM_OK) return rc;
+    double* sums = (double*)s.bits_scr;
+    OpResult* tres = (OpResult*)(sums + nt * 3);
+    float* map = (float*)(tres + frames);
+    // the tiles of every bit in ascending index: start [nbits + 1], idx [tiles that carry a bit] (a counting sort, stable)
+    void *th = nullptr, *td = nullptr;
+    const size_t tab = ((size_t)nbits + 1 + T) * sizeof(int);
+    if ((rc = table_room(ctx, s, tab, &th, &td)) != WM_OK) return rc;
+    int* start = (int*)th;
+    int* idx = start + nbits + 1;
+    std::fill(start, start + nbits + 1, 0);
+    for (int t = 0; t < T; ++t)
+        if (tile_bit[t] >= 0) start[tile_bit[t] + 1]++;
+    for (int b = 0; b < nbits; ++b) start[b + 1] += start[b];
+    {
+        std::vector<int> fill(start, start + nbits);
+        for (int t = 0; t < T; ++t)
+            if (tile_bit[t] >= 0) idx[fill[tile_bit[t]]++] = t;
+    }
+    if ((rc = table_upload(ctx, s, th, td, tab)) != WM_OK) return rc;
+    // the image side is wm_detect's: the Gram sweep (or the hand-over of the slot's last embed) and the solve
+    if ((rc = gram_sweep(ctx, s, lg, frames, xd, img)) != WM_OK) return rc;
+    { ProfScope ps(ctx, K_DETECT_TILES, s.stream); launch_detect_tiles(s.stream, pl, frames, mask, ctx->p / 2, xd, ctx->w->d_w, s.d_coef, s.d_status, (float*)s.tiles_rec); }
+    { ProfScope ps(ctx, K_TILES_FOLD, s.stream); launch_tiles_fold(s.stream, pl, frames, (const float*)s.tiles_rec, s.d_status, map, sums, tres); }
+    launch_bits_fold(s.stream, frames, nbits, T, sums, (const int*)td, (const int*)td + nbits + 1, s.d_status, s.d_res + s.res_used);
+    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
+    push_pending(s, frames, nbits, false, soft_out, status_out, nullptr);
     return slot == WM_SLOT_SYNC ? do_sync(ctx, s) : WM_OK;
 }
 

@@ -271,6 +271,15 @@ void launch_embed_keys(hipStream_t s, const LaunchGeom& lg, int frames, int mask
                        long long kstride, int nkeys, int aligned_w, const PlaneDesc& base, const PlaneDesc& out, const float* coef,
                        const int* status, void* scratch, int rstride);
 int embed_keys_group(void);  // keys per group of k_stats_keys / k_embed_keys (compile-time EKG)
+// a payload in the mark (wm_embed_signs / wm_detect_bits, wm_k_bits.hip).  k_embed_signs is k_embed's sweep (never the hand-over
+// instance) with u = m W multiplied by the sign of the pixel's tile: signs [frames][ny][nx] int8 in {-1, 0, +1} on the device, tile
+// geometry wm_tiles_shape's.  k_bits_fold: one wave per (frame, bit) adds the rows of sums [frames][ntiles][3] (k_tiles_fold's)
+// named by idx [start[bit], start[bit + 1]) one after the other and writes res[frame * nbits + bit] = {status, soft}
+void launch_embed_signs(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* W,
+                        int aligned_w, const PlaneDesc& base, const PlaneDesc& out, const float* coef, const int* status,
+                        const EmbedScalars* scal, const signed char* signs, int tile_rows, int tile_cols, int ny, int nx);
+void launch_bits_fold(hipStream_t s, int frames, int nbits, int ntiles, const double* sums, const int* start, const int* idx,
+                      const int* status, OpResult* res);
 // band mode: solve the 8x8 system from all-reduced Gram totals [frames][44]; writes coef / status like k_gram's tail
 void launch_solve_totals(hipStream_t s, int frames, const double* totals, float* coef, int* status);
 // band mode, device-resident exchange (wm_band_*_dev): glue kernels between the sweeps and the caller's collectives
