@@ -215,23 +215,17 @@ static void launch_embed_signs_tt(hipStream_t s, const LaunchGeom& lg, int frame
                                   const int* status, const EmbedScalars* scal, const SignTable& sg)
 {
     const int al = align_mode(lg, x.aligned && aligned_w && base.aligned && out.aligned);
-    // the base is the grey input itself (same plane, same layout): taken from the stencil window (launch_embed_tt's rule)
-    const bool bx = NCH == 1 && std::is_same<TX, TB>::value && base.p == x.p && base.pitch == x.pitch && base.fstride == x.fstride;
-#define EMS(MASK, P)                                                                                                            \
-    do {                                                                                                                        \
-        if (bx) WM_LAUNCH_SWEEP_Q(s, lg, frames, al, (k_embed_signs<TX, TB, 1, MASK, P, true, true>), (k_embed_signs<TX, TB, 1, MASK, P, false, true>),  \
-                                (const TX*)x.p, x.pitch, x.fstride, W, base, out, g, coef, status, scal, sg);                    \
-        else WM_LAUNCH_SWEEP_Q(s, lg, frames, al, (k_embed_signs<TX, TB, NCH, MASK, P, true, false>), (k_embed_signs<TX, TB, NCH, MASK, P, false, false>), \
-                             (const TX*)x.p, x.pitch, x.fstride, W, base, out, g, coef, status, scal, sg);                       \
-    } while (0)
-    if (mask == 0) { EMS(0, 1); return; }
-    switch (pad) {
-        case 1: EMS(1, 1); break;
-        case 2: EMS(1, 2); break;
-        case 3: EMS(1, 3); break;
-        case 4: EMS(1, 4); break;
-    }
-#undef EMS
+    const bool bx = NCH == 1 && std::is_same<TX, TB>::value && same_plane(x, base);
+    for_mask_pad(mask, pad, [&](auto m, auto p) {
+        auto sweep = [&](auto base_is_x) {
+            for_each_sweep_part(lg, frames, al, 1, [&](auto vec, const SweepPart& sp) {
+                constexpr bool BX = decltype(base_is_x)::value;
+                WM_KLAUNCH((k_embed_signs<TX, TB, (BX ? 1 : NCH), decltype(m)::value, decltype(p)::value, decltype(vec)::value, BX>), sp.grid,
+                           dim3(BLOCK), 0, s, (const TX*)x.p, x.pitch, x.fstride, W, base, out, sp.g, coef, status, scal, sg);
+            });
+        };
+        if (bx) sweep(std::true_type{}); else sweep(std::false_type{});
+    });
 }
 
 void launch_embed_signs(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* W,

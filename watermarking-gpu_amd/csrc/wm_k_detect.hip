@@ -207,45 +207,17 @@ __global__ void k_mask_result(const int* __restrict__ status, const float* __res
 
 // launchers
 template <typename T>
-static void launch_detect_t(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x,
-                            const float* W, int aligned_w, const float* coef, const int* status, double* pcorr,
-                            const CorrTail& tail, bool split, const DigCheck& dc)
+static void launch_detect_t(hipStream_t s, const DetectPlan& pl, int frames, int mask, int pad, const PlaneDesc& x, const float* W,
+                            const float* coef, const int* status, double* pcorr, const CorrTail& tail, const DigCheck& dc)
 {
-#define DET(MASK, P, HC)                                                                                                      \
-    WM_LAUNCH_SWEEP_Q(s, lg, frames, align_mode(lg, x.aligned && aligned_w && HC == 1), (k_detect<T, MASK, P, HC, true>), (k_detect<T, MASK, P, HC, false>), \
-                    (const T*)x.p, x.pitch, x.fstride, W, g, coef, status, pcorr, tail, dc)
-    // 3x3 masks: the aligned instantiation works on overlapped strips (every strip, when all planes allow vector access and
-    // the width is a multiple of 4); otherwise the whole image takes the generic instantiation
-#define DET3P(MASK, P)                                                                                                          \
-    do {                                                                                                                      \
-        if (align_mode(lg, x.aligned && aligned_w) == 2) {                                                                    \
-            const SweepPart pv_ = sweep_part_overlap(lg, frames, 1);                                                          \
-            const Geom g = pv_.g;                                                                                             \
-            WM_KLAUNCH((k_detect<T, MASK, P, 1, true>), pv_.grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, W, g, coef, status, pcorr, tail, dc); \
-        } else if (split) {                                                                                                   \
-            /* a width that is not a multiple of 4: overlapped strips below column B + one generic strip (wm_march.hpp) */     \
-            { const SweepPart pv_ = sweep_part_split_overlap(lg, frames, 1); const Geom g = pv_.g;                              \
-              WM_KLAUNCH((k_detect<T, MASK, P, 1, true>), pv_.grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, W, g, coef, status, pcorr, tail, dc); } \
-            { const SweepPart pg_ = sweep_part_split_generic(lg, frames, 1); const Geom g = pg_.g;                              \
-              WM_KLAUNCH((k_detect<T, MASK, P, 1, false>), pg_.grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, W, g, coef, status, pcorr, tail, dc); } \
-        } else {                                                                                                              \
-            WM_LAUNCH_SWEEP_Q(s, lg, frames, 0, (k_detect<T, MASK, P, 1, true>), (k_detect<T, MASK, P, 1, false>),           \
-                              (const T*)x.p, x.pitch, x.fstride, W, g, coef, status, pcorr, tail, dc);                            \
-        }                                                                                                                     \
-    } while (0)
-    if (mask == 0) { DET3P(0, 1); return; }
-    switch (pad) {
-        case 1: DET3P(1, 1); break;
-        case 2: DET3P(1, 2); break;
-        case 3: DET3P(1, 3); break;
-        case 4: DET(1, 4, 2); break;
-    }
-#undef DET
-#undef DET3P
+    for_each_detect_launch(pl, frames, mask, pad, [&](auto m, auto p, auto hc, auto vec, const SweepPart& sp) {
+        WM_KLAUNCH((k_detect<T, decltype(m)::value, decltype(p)::value, decltype(hc)::value, decltype(vec)::value>), sp.grid, dim3(BLOCK),
+                   0, s, (const T*)x.p, x.pitch, x.fstride, W, sp.g, coef, status, pcorr, tail, dc);
+    });
 }
 bool detect_checkable(const LaunchGeom& lg, int mask, int pad, const PlaneDesc& x, int aligned_w)
 {
-    return x.dtype == 0 && mask == 0 && pad == 1 && align_mode(lg, x.aligned && aligned_w) == 2;
+    return x.dtype == 0 && mask == 0 && pad == 1 && detect_plan(lg, mask, pad, x, aligned_w).overlap;
 }
 void launch_detect(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* W,
                    int aligned_w, const float* coef, const int* status, double* pcorr, unsigned* ticket, unsigned* ticket_strip,
@@ -261,14 +233,10 @@ void launch_detect(hipStream_t s, const LaunchGeom& lg, int frames, int mask, in
         return;
     }
     const DigCheck none{nullptr, nullptr, nullptr, nullptr, nullptr};
-    // the aligned 3x3 path runs on overlapped strips: more, narrower strips than the other sweeps of the call (overlap_geom);
-    // the records, the strip tickets and the fold follow that strip count
-    const bool overlap = (mask == 0 || pad <= 3) && align_mode(lg, x.aligned && aligned_w) == 2;
-    // ... and for widths that are not multiples of 4 on planes that allow vector access: overlapped strips + one generic strip
-    const bool split = (mask == 0 || pad == 1) && !overlap && x.aligned && aligned_w && split_applies(lg.cols);
-    const LaunchGeom ld = overlap ? overlap_geom(lg) : (split ? split_geom(lg) : lg);
+    const DetectPlan pl = detect_plan(lg, mask, pad, x, aligned_w);
+    const LaunchGeom& ld = pl.ld;
     const CorrTail tail{ticket, ticket_strip, ld.nblk, ld.nsegs, ld.nstrips, scorr, res, raw};
-    WM_DISPATCH_T(x.dtype, launch_detect_t<T>(s, ld, frames, mask, pad, x, W, aligned_w, coef, status, pcorr, tail, split, none));
+    WM_DISPATCH_T(x.dtype, launch_detect_t<T>(s, pl, frames, mask, pad, x, W, coef, status, pcorr, tail, none));
 }
 
 // ---- W on the device: the counter-based N(0,1) generator of csrc/app/wm_genw.cpp (the replacement of the reference's

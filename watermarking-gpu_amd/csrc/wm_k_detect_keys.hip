@@ -163,34 +163,14 @@ __global__ __launch_bounds__(BLOCK) void k_keys_fold(const double* __restrict__ 
 }
 
 template <typename T>
-static void launch_detect_keys_t(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x,
-                                 int aligned_w, const KeysArgs& ka, const float* coef, const int* status, bool split)
+static void launch_detect_keys_t(hipStream_t s, const DetectPlan& pl, int frames, int mask, int pad, const PlaneDesc& x, const KeysArgs& ka,
+                                 const float* coef, const int* status)
 {
-    // k_detect's launch plan (launch_detect_t), every grid times the key groups
-#define KEYS_GO(KER, SP)                                                                                                   \
-    do {                                                                                                                   \
-        const SweepPart sp_ = (SP);                                                                                        \
-        if (sp_.run) WM_KLAUNCH(KER, dim3(sp_.grid.x * (unsigned)ka.ngroups), dim3(BLOCK), 0, s, (const T*)x.p, x.pitch,   \
-                                x.fstride, ka, sp_.g, coef, status);                                                       \
-    } while (0)
-#define KEYS3P(MASK, P)                                                                                                    \
-    do {                                                                                                                   \
-        if (align_mode(lg, x.aligned && aligned_w) == 2) {                                                                 \
-            KEYS_GO((k_detect_keys<T, MASK, P, 1, true>), sweep_part_overlap(lg, frames, 1));                               \
-        } else if (split) {                                                                                                \
-            KEYS_GO((k_detect_keys<T, MASK, P, 1, true>), sweep_part_split_overlap(lg, frames, 1));                         \
-            KEYS_GO((k_detect_keys<T, MASK, P, 1, false>), sweep_part_split_generic(lg, frames, 1));                        \
-        } else {                                                                                                           \
-            KEYS_GO((k_detect_keys<T, MASK, P, 1, false>), sweep_part(lg, frames, false, 0, 1));                            \
-        }                                                                                                                  \
-    } while (0)
-    if (mask == 0) { KEYS3P(0, 1); }
-    else if (pad == 1) { KEYS3P(1, 1); }
-    else if (pad == 2) { KEYS3P(1, 2); }
-    else if (pad == 3) { KEYS3P(1, 3); }
-    else { KEYS_GO((k_detect_keys<T, 1, 4, 2, false>), sweep_part(lg, frames, false, 0, 1)); }
-#undef KEYS3P
-#undef KEYS_GO
+    // every grid times the key groups
+    for_each_detect_launch(pl, frames, mask, pad, [&](auto m, auto p, auto hc, auto vec, const SweepPart& sp) {
+        WM_KLAUNCH((k_detect_keys<T, decltype(m)::value, decltype(p)::value, decltype(hc)::value, decltype(vec)::value>),
+                   dim3(sp.grid.x * (unsigned)ka.ngroups), dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, ka, sp.g, coef, status);
+    });
 }
 
 int detect_keys_group(void) { return KG; }
@@ -199,17 +179,14 @@ int launch_detect_keys(hipStream_t s, const LaunchGeom& lg, int frames, int mask
                        const float* Wbank, long long kstride, int nkeys, int aligned_w, const float* coef, const int* status,
                        double* part, int rstride, OpResult* res)
 {
-    // the geometry k_detect takes for this plane (launch_detect): overlapped strips, overlapped strips + one generic strip,
-    // or the plain strips
-    const bool overlap = (mask == 0 || pad <= 3) && align_mode(lg, x.aligned && aligned_w) == 2;
-    const bool split = (mask == 0 || pad == 1) && !overlap && x.aligned && aligned_w && split_applies(lg.cols);
-    const LaunchGeom ld = overlap ? overlap_geom(lg) : (split ? split_geom(lg) : lg);
+    const DetectPlan pl = detect_plan(lg, mask, pad, x, aligned_w);
+    const LaunchGeom& ld = pl.ld;
     const bool quad = frames >= 4;
     if (ld.nblk > rstride || ld.nstrips * ld.nsegs > rstride || ld.nstrips > KEYS_MAX_STRIPS) return -1;
     KeysArgs ka;
     ka.W = Wbank; ka.kstride = kstride; ka.nkeys = nkeys; ka.ngroups = (nkeys + KG - 1) / KG; ka.rstride = rstride;
     ka.part = part; ka.partw = part + (size_t)frames * nkeys * rstride * 2;
-    WM_DISPATCH_T(x.dtype, launch_detect_keys_t<T>(s, ld, frames, mask, pad, x, aligned_w, ka, coef, status, split));
+    WM_DISPATCH_T(x.dtype, launch_detect_keys_t<T>(s, pl, frames, mask, pad, x, ka, coef, status));
     launch_keys_fold(s, ka.part, ka.partw, rstride, frames, nkeys, quad ? 1 : 0, ld.nblk, ld.nsegs, ld.nstrips, status, res);
     return 0;
 }

@@ -129,32 +129,13 @@ template <typename T>
 static void launch_detect_keys_tiles_t(hipStream_t s, const TilesPlan& pl, int frames, int mask, int pad, const PlaneDesc& x, const float* Wbank,
                                        long long kstride, int nkeys, const float* coef, const int* status, float* rec)
 {
-    const LaunchGeom& ld = pl.ld;
     const int ngroups = (nkeys + KG - 1) / KG;
-    // launch_detect_tiles_t's choice of instances (wm_k_detect_tiles.hip), every grid times the key groups
-#define KTIL(KV, PART)                                                                                                          \
-    do {                                                                                                                        \
-        const SweepPart pp_ = PART;                                                                                             \
-        if (pp_.run) WM_KLAUNCH(KV, dim3(pp_.grid.x * (unsigned)ngroups), dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, \
-                                Wbank, kstride, nkeys, ngroups, pp_.g, coef, status, rec);                                      \
-    } while (0)
-#define KTIL3P(MASK, P)                                                                                                         \
-    do {                                                                                                                        \
-        if (pl.overlap) KTIL((k_detect_keys_tiles<T, MASK, P, 1, true>), sweep_part_overlap(ld, frames, 1));                    \
-        else if (pl.split) {                                                                                                    \
-            KTIL((k_detect_keys_tiles<T, MASK, P, 1, true>), sweep_part_split_overlap(ld, frames, 1));                          \
-            KTIL((k_detect_keys_tiles<T, MASK, P, 1, false>), sweep_part_split_generic(ld, frames, 1));                         \
-        } else KTIL((k_detect_keys_tiles<T, MASK, P, 1, false>), sweep_part(ld, frames, false, 0, 1));                          \
-    } while (0)
-    if (mask == 0) { KTIL3P(0, 1); return; }
-    switch (pad) {
-        case 1: KTIL3P(1, 1); break;
-        case 2: KTIL3P(1, 2); break;
-        case 3: KTIL3P(1, 3); break;
-        case 4: KTIL((k_detect_keys_tiles<T, 1, 4, 2, false>), sweep_part(ld, frames, false, 0, 1)); break;
-    }
-#undef KTIL3P
-#undef KTIL
+    // every grid times the key groups
+    for_each_detect_launch(pl, frames, mask, pad, [&](auto m, auto p, auto hc, auto vec, const SweepPart& sp) {
+        WM_KLAUNCH((k_detect_keys_tiles<T, decltype(m)::value, decltype(p)::value, decltype(hc)::value, decltype(vec)::value>),
+                   dim3(sp.grid.x * (unsigned)ngroups), dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, Wbank, kstride, nkeys, ngroups,
+                   sp.g, coef, status, rec);
+    });
 }
 
 void launch_detect_keys_tiles(hipStream_t s, const TilesPlan& pl, int frames, int mask, int pad, const PlaneDesc& x, const float* Wbank,

@@ -373,10 +373,9 @@ __global__ __launch_bounds__(BLOCK, offsets_min_blocks(PAD, HC, VEC, (int)sizeof
 }
 
 template <typename T>
-static void launch_detect_offsets_t(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x,
-                                    int aligned_w, const OffsArgs& oa1, const float* coef, const int* status, bool split)
+static void launch_detect_offsets_t(hipStream_t s, const DetectPlan& pl, int frames, int mask, int pad, const PlaneDesc& x,
+                                    const OffsArgs& oa1, const float* coef, const int* status)
 {
-    // k_detect_keys' launch plan (launch_detect_keys_t), every grid times the offset groups of its instance;
     // columns(): the columns [lo, lo + n) of every row offset in groups of G
     auto columns = [&](int G, int lo, int n, int write_w) {
         OffsArgs a = oa1;
@@ -384,44 +383,28 @@ static void launch_detect_offsets_t(hipStream_t s, const LaunchGeom& lg, int fra
         a.ngx = (n + G - 1) / G; a.ngroups = a.ny * a.ngx;
         return a;
     };
-#define OFFS_GO(KER, OA, SP)                                                                                               \
-    do {                                                                                                                   \
-        const SweepPart sp_ = (SP);                                                                                        \
-        const OffsArgs oa_ = (OA);                                                                                         \
-        if (sp_.run) WM_KLAUNCH(KER, dim3(sp_.grid.x * (unsigned)oa_.ngroups), dim3(BLOCK), 0, s, (const T*)x.p, x.pitch,  \
-                                x.fstride, oa_, sp_.g, coef, status);                                                      \
-    } while (0)
     // the aligned instance of the 3x3 windows: the shared row when a full group exists.  A remainder of nx % G columns costs a
     // whole group when the last group is moved left to be full; up to G / 2 columns are cheaper as one offset per block (the
     // G = 1 instance) in a launch of their own
     const int rem = oa1.nx % OG, tail = oa1.nx >= OG && 2 * rem <= OG ? rem : 0;
     const OffsArgs all1 = columns(1, 0, oa1.nx, 1);  // every offset a block of its own
-#define OFFS_VEC(MASK, P, SP)                                                                                              \
-    do {                                                                                                                   \
-        if (P == 1 && oa1.nx >= OG) {                                                                                      \
-            OFFS_GO((k_detect_offsets<T, MASK, P, 1, true, (P == 1 ? OG : 1)>), columns(OG, 0, oa1.nx - tail, 1), SP);     \
-            if (tail) OFFS_GO((k_detect_offsets<T, MASK, P, 1, true, 1>), columns(1, oa1.nx - tail, tail, 0), SP);         \
-        } else OFFS_GO((k_detect_offsets<T, MASK, P, 1, true, 1>), all1, SP);                                              \
-    } while (0)
-#define OFFS3P(MASK, P)                                                                                                    \
-    do {                                                                                                                   \
-        if (align_mode(lg, x.aligned && aligned_w) == 2) {                                                                 \
-            OFFS_VEC(MASK, P, sweep_part_overlap(lg, frames, 1));                                                          \
-        } else if (split) {                                                                                                \
-            OFFS_VEC(MASK, P, sweep_part_split_overlap(lg, frames, 1));                                                    \
-            OFFS_GO((k_detect_offsets<T, MASK, P, 1, false, 1>), all1, sweep_part_split_generic(lg, frames, 1));                   \
-        } else {                                                                                                           \
-            OFFS_GO((k_detect_offsets<T, MASK, P, 1, false, 1>), all1, sweep_part(lg, frames, false, 0, 1));                       \
-        }                                                                                                                  \
-    } while (0)
-    if (mask == 0) { OFFS3P(0, 1); }
-    else if (pad == 1) { OFFS3P(1, 1); }
-    else if (pad == 2) { OFFS3P(1, 2); }
-    else if (pad == 3) { OFFS3P(1, 3); }
-    else { OFFS_GO((k_detect_offsets<T, 1, 4, 2, false, 1>), all1, sweep_part(lg, frames, false, 0, 1)); }
-#undef OFFS3P
-#undef OFFS_VEC
-#undef OFFS_GO
+    // every grid times the offset groups of its instance
+    for_each_detect_launch(pl, frames, mask, pad, [&](auto m, auto p, auto hc, auto vec, const SweepPart& sp) {
+        constexpr int MASK = decltype(m)::value, PAD = decltype(p)::value, HC = decltype(hc)::value;
+        constexpr bool VEC = decltype(vec)::value;
+        auto go = [&](auto g, const OffsArgs& oa) {
+            WM_KLAUNCH((k_detect_offsets<T, MASK, PAD, HC, VEC, decltype(g)::value>), dim3(sp.grid.x * (unsigned)oa.ngroups), dim3(BLOCK), 0, s,
+                       (const T*)x.p, x.pitch, x.fstride, oa, sp.g, coef, status);
+        };
+        if constexpr (VEC && PAD == 1) {
+            if (oa1.nx >= OG) {
+                go(IC<OG>{}, columns(OG, 0, oa1.nx - tail, 1));
+                if (tail) go(IC<1>{}, columns(1, oa1.nx - tail, tail, 0));
+                return;
+            }
+        }
+        go(IC<1>{}, all1);
+    });
 }
 
 int detect_offsets_group(void) { return OG; }
@@ -430,17 +413,16 @@ int launch_detect_offsets(hipStream_t s, const LaunchGeom& lg, int frames, int m
                           const float* key, int key_cols, int oy0, int ox0, int ny, int nx, int aligned_w, const float* coef,
                           const int* status, double* part, int rstride, OpResult* res)
 {
-    // the geometry comes from the IMAGE plane alone, exactly as launch_detect_keys chooses it
-    const bool overlap = (mask == 0 || pad <= 3) && align_mode(lg, x.aligned && aligned_w) == 2;
-    const bool split = (mask == 0 || pad == 1) && !overlap && x.aligned && aligned_w && split_applies(lg.cols);
-    const LaunchGeom ld = overlap ? overlap_geom(lg) : (split ? split_geom(lg) : lg);
+    // the geometry comes from the IMAGE plane alone (detect_plan, as for every detector)
+    const DetectPlan pl = detect_plan(lg, mask, pad, x, aligned_w);
+    const LaunchGeom& ld = pl.ld;
     const bool quad = frames >= 4;
     if (ld.nblk > rstride || ld.nstrips * ld.nsegs > rstride || ld.nstrips > KEYS_MAX_STRIPS) return -1;
     const int noff = ny * nx;
     OffsArgs oa;
     oa.key = key; oa.kc = key_cols; oa.oy0 = oy0; oa.ox0 = ox0; oa.ny = ny; oa.nx = nx; oa.jx_lo = 0; oa.nxl = nx; oa.ngx = nx; oa.ngroups = noff; oa.write_w = 1;
     oa.rstride = rstride; oa.part = part; oa.partw = part + (size_t)frames * noff * rstride * 2;
-    WM_DISPATCH_T(x.dtype, launch_detect_offsets_t<T>(s, ld, frames, mask, pad, x, aligned_w, oa, coef, status, split));
+    WM_DISPATCH_T(x.dtype, launch_detect_offsets_t<T>(s, pl, frames, mask, pad, x, oa, coef, status));
     launch_keys_fold(s, oa.part, oa.partw, rstride, frames, noff, quad ? 1 : 0, ld.nblk, ld.nsegs, ld.nstrips, status, res);
     return 0;
 }

@@ -95,7 +95,7 @@ int tiles_segment_rows(int tile_rows)
 }
 
 // the sweep's geometry: segments of tiles_segment_rows(tile_rows) rows -- from the tile shape alone, so that a frame's records
-// (and bits) do not depend on the batch it arrives in --, strips as launch_detect chooses them
+// (and bits) do not depend on the batch it arrives in --, strips as detect_plan chooses them
 TilesPlan tiles_plan(const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, int aligned_w, int tile_rows, int tile_cols,
                      int ny, int nx)
 {
@@ -104,9 +104,8 @@ TilesPlan tiles_plan(const LaunchGeom& lg, int frames, int mask, int pad, const 
     lt.rps = std::min(tiles_segment_rows(tile_rows), lg.row_hi - lg.row_lo);
     lt.nsegs = (lg.row_hi - lg.row_lo + lt.rps - 1) / lt.rps;
     lt.nblk = lt.nstrips * ((lt.nsegs + WPB - 1) / WPB);
-    pl.overlap = (mask == 0 || pad <= 3) && align_mode(lt, x.aligned && aligned_w) == 2;
-    pl.split = (mask == 0 || pad == 1) && !pl.overlap && x.aligned && aligned_w && split_applies(lt.cols);
-    pl.ld = pl.overlap ? overlap_geom(lt) : (pl.split ? split_geom(lt) : lt);
+    const DetectPlan dp = detect_plan(lt, mask, pad, x, aligned_w);
+    pl.ld = dp.ld; pl.overlap = dp.overlap; pl.split = dp.split;
     const LaunchGeom& ld = pl.ld;
     TileGeom& tg = pl.tg;
     tg.th = tile_rows; tg.tw = tile_cols; tg.ny = ny; tg.nx = nx;
@@ -126,30 +125,10 @@ template <typename T>
 static void launch_detect_tiles_t(hipStream_t s, const TilesPlan& pl, int frames, int mask, int pad, const PlaneDesc& x, const float* W,
                                   const float* coef, const int* status, float* rec)
 {
-    const LaunchGeom& ld = pl.ld;
-    // launch_detect_t's choice of instances (wm_k_detect.hip)
-#define TIL(KV, PART)                                                                                                             \
-    do {                                                                                                                        \
-        const SweepPart pp_ = PART; const Geom g = pp_.g;                                                                       \
-        if (pp_.run) WM_KLAUNCH(KV, pp_.grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, W, g, coef, status, rec);  \
-    } while (0)
-#define TIL3P(MASK, P)                                                                                                          \
-    do {                                                                                                                        \
-        if (pl.overlap) TIL((k_detect_tiles<T, MASK, P, 1, true>), sweep_part_overlap(ld, frames, 1));                          \
-        else if (pl.split) {                                                                                                    \
-            TIL((k_detect_tiles<T, MASK, P, 1, true>), sweep_part_split_overlap(ld, frames, 1));                                \
-            TIL((k_detect_tiles<T, MASK, P, 1, false>), sweep_part_split_generic(ld, frames, 1));                               \
-        } else TIL((k_detect_tiles<T, MASK, P, 1, false>), sweep_part(ld, frames, false, 0, 1));                                \
-    } while (0)
-    if (mask == 0) { TIL3P(0, 1); return; }
-    switch (pad) {
-        case 1: TIL3P(1, 1); break;
-        case 2: TIL3P(1, 2); break;
-        case 3: TIL3P(1, 3); break;
-        case 4: TIL((k_detect_tiles<T, 1, 4, 2, false>), sweep_part(ld, frames, false, 0, 1)); break;
-    }
-#undef TIL3P
-#undef TIL
+    for_each_detect_launch(pl, frames, mask, pad, [&](auto m, auto p, auto hc, auto vec, const SweepPart& sp) {
+        WM_KLAUNCH((k_detect_tiles<T, decltype(m)::value, decltype(p)::value, decltype(hc)::value, decltype(vec)::value>), sp.grid,
+                   dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, W, sp.g, coef, status, rec);
+    });
 }
 
 void launch_detect_tiles(hipStream_t s, const TilesPlan& pl, int frames, int mask, int pad, const PlaneDesc& x, const float* W,

@@ -558,8 +558,10 @@ void launch_me_stats(hipStream_t s, const LaunchGeom& lg, int frames, const Plan
 {
     const int al = align_mode(lg, x.aligned && aligned_w);
     const ScalarsTail tail = scalars_tail(lg, ticket, ticket_strip, smax, sss, sF, sqrt_n, scal, res, raw);
-    WM_DISPATCH_T(x.dtype, WM_LAUNCH_SWEEP_Q(s, lg, frames, al, (k_me_stats<T, true>), (k_me_stats<T, false>), (const T*)x.p, x.pitch,
-                                           x.fstride, W, g, coef, status, pmax, pss, tail));
+    WM_DISPATCH_T(x.dtype, for_each_sweep_part(lg, frames, al, 1, [&](auto vec, const SweepPart& sp) {
+        WM_KLAUNCH((k_me_stats<T, decltype(vec)::value>), sp.grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, W, sp.g, coef, status,
+                   pmax, pss, tail);
+    }));
 }
 
 template <typename T>
@@ -567,13 +569,12 @@ static void launch_nvf_stats_t(hipStream_t s, const LaunchGeom& lg, int frames, 
                                int aligned_w, int pad, double* pss, const ScalarsTail& tail)
 {
     const int al = align_mode(lg, x.aligned && aligned_w);
-#define NVF_CASE(P)                                                                                                           \
-    case P:                                                                                                                   \
-        WM_LAUNCH_SWEEP_Q(s, lg, frames, al, (k_nvf_stats<T, P, true>), (k_nvf_stats<T, P, false>), (const T*)x.p, x.pitch, x.fstride, \
-                        W, g, pss, tail);                                                                                     \
-        break;
-    switch (pad) { NVF_CASE(1) NVF_CASE(2) NVF_CASE(3) NVF_CASE(4) }
-#undef NVF_CASE
+    for_mask_pad(1, pad, [&](auto, auto p) {
+        for_each_sweep_part(lg, frames, al, 1, [&](auto vec, const SweepPart& sp) {
+            WM_KLAUNCH((k_nvf_stats<T, decltype(p)::value, decltype(vec)::value>), sp.grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch,
+                       x.fstride, W, sp.g, pss, tail);
+        });
+    });
 }
 void launch_nvf_stats(hipStream_t s, const LaunchGeom& lg, int frames, const PlaneDesc& x, const float* W, int aligned_w,
                       int pad, double* pss, unsigned* ticket, unsigned* ticket_strip, double* sss, float sF, double sqrt_n,
@@ -589,8 +590,7 @@ static bool launch_embed_tt(hipStream_t s, const LaunchGeom& lg, int frames, int
                             const int* status, const EmbedScalars* scal, const HandOver* ho)
 {
     const int al = align_mode(lg, x.aligned && aligned_w && base.aligned && out.aligned);
-    // the base is the grey input itself (same plane, same layout): k_embed then takes it from its stencil window
-    const bool bx = NCH == 1 && std::is_same<TX, TB>::value && base.p == x.p && base.pitch == x.pitch && base.fstride == x.fstride;
+    const bool bx = NCH == 1 && std::is_same<TX, TB>::value && same_plane(x, base);
     const HandOver none{nullptr, 0, nullptr, nullptr, nullptr};
     if constexpr (NCH == 1 && std::is_same<TX, float>::value && std::is_same<TB, float>::value) {
         // Gram hand-over: every strip on the aligned path (one launch), 3x3 windows, a core, segments of two rows or more; two
@@ -611,21 +611,16 @@ static bool launch_embed_tt(hipStream_t s, const LaunchGeom& lg, int frames, int
             return true;
         }
     }
-#define EMB(MASK, P)                                                                                                            \
-    do {                                                                                                                        \
-        if (bx) WM_LAUNCH_SWEEP_Q(s, lg, frames, al, (k_embed<TX, TB, 1, MASK, P, true, true>), (k_embed<TX, TB, 1, MASK, P, false, true>),  \
-                                (const TX*)x.p, x.pitch, x.fstride, W, base, out, g, coef, status, scal, none);                  \
-        else WM_LAUNCH_SWEEP_Q(s, lg, frames, al, (k_embed<TX, TB, NCH, MASK, P, true, false>), (k_embed<TX, TB, NCH, MASK, P, false, false>), \
-                             (const TX*)x.p, x.pitch, x.fstride, W, base, out, g, coef, status, scal, none);                     \
-    } while (0)
-    if (mask == 0) { EMB(0, 1); return false; }
-    switch (pad) {
-        case 1: EMB(1, 1); break;
-        case 2: EMB(1, 2); break;
-        case 3: EMB(1, 3); break;
-        case 4: EMB(1, 4); break;
-    }
-#undef EMB
+    for_mask_pad(mask, pad, [&](auto m, auto p) {
+        auto sweep = [&](auto base_is_x) {
+            for_each_sweep_part(lg, frames, al, 1, [&](auto vec, const SweepPart& sp) {
+                constexpr bool BX = decltype(base_is_x)::value;
+                WM_KLAUNCH((k_embed<TX, TB, (BX ? 1 : NCH), decltype(m)::value, decltype(p)::value, decltype(vec)::value, BX>), sp.grid,
+                           dim3(BLOCK), 0, s, (const TX*)x.p, x.pitch, x.fstride, W, base, out, sp.g, coef, status, scal, none);
+            });
+        };
+        if (bx) sweep(std::true_type{}); else sweep(std::false_type{});
+    });
     return false;
 }
 template <typename TX, typename TB>
@@ -653,17 +648,12 @@ static void launch_mask_t(hipStream_t s, const LaunchGeom& lg, int frames, int m
 {
     // exercises the same two input paths as the production kernels (DPP for aligned full strips, LDS otherwise)
     const int al = align_mode(lg, x.aligned != 0);
-#define MSK(MASK, P)                                                                                                      \
-    WM_LAUNCH_SWEEP(s, lg, frames, al, (k_mask<T, MASK, P, true>), (k_mask<T, MASK, P, false>), (const T*)x.p, x.pitch, x.fstride, g, \
-                    coef, status, scal, mo, eo)
-    if (mask == 0) { MSK(0, 1); return; }
-    switch (pad) {
-        case 1: MSK(1, 1); break;
-        case 2: MSK(1, 2); break;
-        case 3: MSK(1, 3); break;
-        case 4: MSK(1, 4); break;
-    }
-#undef MSK
+    for_mask_pad(mask, pad, [&](auto m, auto p) {
+        for_each_sweep_part(lg, frames, al, 0, [&](auto vec, const SweepPart& sp) {
+            WM_KLAUNCH((k_mask<T, decltype(m)::value, decltype(p)::value, decltype(vec)::value>), sp.grid, dim3(BLOCK), 0, s, (const T*)x.p,
+                       x.pitch, x.fstride, sp.g, coef, status, scal, mo, eo);
+        });
+    });
 }
 void launch_mask(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* coef,
                  const int* status, const EmbedScalars* scal, const PlaneDesc& mo, const PlaneDesc& eo)

@@ -420,15 +420,6 @@ __global__ __launch_bounds__(BLOCK) void k_embed_keys(const T* __restrict__ x, l
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------
-// WM_LAUNCH_SWEEP_Q's two launches, every grid times the key groups
-#define EKEYS_SWEEP(KVEC, KGEN, ...)                                                                                       \
-    do {                                                                                                                   \
-        const SweepPart pv_ = sweep_part(lg, frames, true, al, 1);                                                         \
-        if (pv_.run) { const Geom g = pv_.g; WM_KLAUNCH(KVEC, dim3(pv_.grid.x * (unsigned)ka.ngroups), dim3(BLOCK), 0, s, __VA_ARGS__); } \
-        const SweepPart pg_ = sweep_part(lg, frames, false, al, 1);                                                        \
-        if (pg_.run) { const Geom g = pg_.g; WM_KLAUNCH(KGEN, dim3(pg_.grid.x * (unsigned)ka.ngroups), dim3(BLOCK), 0, s, __VA_ARGS__); } \
-    } while (0)
-
 static EKeysArgs ekeys_args(const float* Wbank, long long kstride, int nkeys, int frames, void* scratch, int rstride)
 {
     EKeysArgs ka;
@@ -450,15 +441,13 @@ template <typename T>
 static void launch_stats_keys_t(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, int al,
                                 const EKeysArgs& ka, const float* coef, const int* status)
 {
-#define SK(MASK, P) EKEYS_SWEEP((k_stats_keys<T, MASK, P, true>), (k_stats_keys<T, MASK, P, false>), (const T*)x.p, x.pitch, x.fstride, ka, g, coef, status)
-    if (mask == 0) { SK(0, 1); return; }
-    switch (pad) {
-        case 1: SK(1, 1); break;
-        case 2: SK(1, 2); break;
-        case 3: SK(1, 3); break;
-        case 4: SK(1, 4); break;
-    }
-#undef SK
+    // every grid times the key groups
+    for_mask_pad(mask, pad, [&](auto m, auto p) {
+        for_each_sweep_part(lg, frames, al, 1, [&](auto vec, const SweepPart& sp) {
+            WM_KLAUNCH((k_stats_keys<T, decltype(m)::value, decltype(p)::value, decltype(vec)::value>), dim3(sp.grid.x * (unsigned)ka.ngroups),
+                       dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, ka, sp.g, coef, status);
+        });
+    });
 }
 
 int launch_stats_keys(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* Wbank,
@@ -487,28 +476,24 @@ static void launch_embed_keys_t(hipStream_t s, const LaunchGeom& lg, int frames,
 {
     // k_embed's launch plan (launch_embed_tt, no hand-over), once per channel of the base
     const int al = align_mode(lg, x.aligned && aligned_w && base.aligned && out.aligned);
-    const bool bx = base.channels == 1 && base.p == x.p && base.pitch == x.pitch && base.fstride == x.fstride;
-#define EK(MASK, P)                                                                                                        \
-    do {                                                                                                                   \
-        if (bx) EKEYS_SWEEP((k_embed_keys<T, MASK, P, true, true>), (k_embed_keys<T, MASK, P, false, true>), (const T*)x.p,   \
-                            x.pitch, x.fstride, ka, bc, oc, g, coef, status);                                               \
-        else EKEYS_SWEEP((k_embed_keys<T, MASK, P, true, false>), (k_embed_keys<T, MASK, P, false, false>), (const T*)x.p,    \
-                         x.pitch, x.fstride, ka, bc, oc, g, coef, status);                                                  \
-    } while (0)
+    const bool bx = base.channels == 1 && same_plane(x, base);
     for (int ch = 0; ch < base.channels; ++ch) {
         PlaneDesc bc = base, oc = out;
         bc.p = static_cast<const T*>(base.p) + (long long)ch * base.cstride;
         oc.p = static_cast<const T*>(out.p) + (long long)ch * out.cstride;
         bc.channels = oc.channels = 1;
-        if (mask == 0) { EK(0, 1); continue; }
-        switch (pad) {
-            case 1: EK(1, 1); break;
-            case 2: EK(1, 2); break;
-            case 3: EK(1, 3); break;
-            case 4: EK(1, 4); break;
-        }
+        // every grid times the key groups
+        for_mask_pad(mask, pad, [&](auto m, auto p) {
+            auto sweep = [&](auto base_is_x) {
+                for_each_sweep_part(lg, frames, al, 1, [&](auto vec, const SweepPart& sp) {
+                    WM_KLAUNCH((k_embed_keys<T, decltype(m)::value, decltype(p)::value, decltype(vec)::value, decltype(base_is_x)::value>),
+                               dim3(sp.grid.x * (unsigned)ka.ngroups), dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, ka, bc, oc, sp.g,
+                               coef, status);
+                });
+            };
+            if (bx) sweep(std::true_type{}); else sweep(std::false_type{});
+        });
     }
-#undef EK
 }
 
 void launch_embed_keys(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* Wbank,
@@ -521,7 +506,5 @@ void launch_embed_keys(hipStream_t s, const LaunchGeom& lg, int frames, int mask
 }
 
 int embed_keys_group(void) { return EKG; }
-
-#undef EKEYS_SWEEP
 
 }  // namespace wmk

@@ -556,30 +556,20 @@ void launch_gram(hipStream_t s, const LaunchGeom& lg, int frames, const PlaneDes
 {
     // the border blocks ride in the first launch of the sweep (the aligned-path one when it exists)
     const int al = align_mode(lg, x.aligned != 0);
-    const SweepPart pv = sweep_part(lg, frames, true, al);
-    const SweepPart pg = sweep_part(lg, frames, false, al);
-    const int nbb_v = pv.run ? lg.nbb : 0;
-    const int nbb_g = pv.run ? 0 : lg.nbb;
     // every block of both launches takes a ticket of its frame; the last one folds the partials and solves
     const SolveTail tail{ticket, lg.nblk + lg.nbb, lg.nbb, coef, status, gram_tot};
-    if (pv.run) {
-        Geom g = pv.g;
+    int nbb = lg.nbb;
+    for_each_sweep_part(lg, frames, al, 0, [&](auto vec, const SweepPart& sp) {
+        constexpr bool VEC = decltype(vec)::value;
+        Geom g = sp.g;
         g.frame_fastest = 0;  // the Gram sweep reads no W: keep a frame's tiles together (halo rows stay in L2)
-        const dim3 grid(pv.grid.x + nbb_v * frames, 1, 1);
-        if (redo) WM_DISPATCH_T(x.dtype, WM_KLAUNCH((k_gram_redo<T, true>), grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, g, nbb_v,
-                                                             pmain, pborder, tail, redo));
-        else WM_DISPATCH_T(x.dtype, WM_KLAUNCH((k_gram<T, true>), grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, g, nbb_v,
-                                                        pmain, pborder, tail));
-    }
-    if (pg.run) {
-        Geom g = pg.g;
-        g.frame_fastest = 0;
-        const dim3 grid(pg.grid.x + nbb_g * frames, 1, 1);
-        if (redo) WM_DISPATCH_T(x.dtype, WM_KLAUNCH((k_gram_redo<T, false>), grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, g, nbb_g,
-                                                             pmain, pborder, tail, redo));
-        else WM_DISPATCH_T(x.dtype, WM_KLAUNCH((k_gram<T, false>), grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, g, nbb_g,
-                                                        pmain, pborder, tail));
-    }
+        const dim3 grid(sp.grid.x + nbb * frames, 1, 1);
+        if (redo) WM_DISPATCH_T(x.dtype, WM_KLAUNCH((k_gram_redo<T, VEC>), grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, g, nbb,
+                                                    pmain, pborder, tail, redo));
+        else WM_DISPATCH_T(x.dtype, WM_KLAUNCH((k_gram<T, VEC>), grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, g, nbb, pmain,
+                                               pborder, tail));
+        nbb = 0;
+    });
 }
 
 }  // namespace wmk

@@ -62,6 +62,12 @@ struct LaunchGeom {
     int row_lo, row_hi;
 };
 
+// Which strips a detector sweep runs on (detect_plan, wm_march.hpp): the records, the strip tickets and the folds follow ld
+struct DetectPlan {
+    LaunchGeom ld;        // the sweep's geometry
+    bool overlap, split;  // overlapped strips / overlapped strips + one generic strip; neither: the plain strips
+};
+
 struct EmbedScalars {
     float a;     // watermark strength (Watermark.cpp:170)
     float maxe;  // max|e| (ME) or 1
@@ -231,9 +237,7 @@ struct TileGeom {
     int nown;                  // layouts 1, 2: column groups the overlapped strips own
     int ngroups;               // column groups in all (layout 2: the generic strip's 64 lanes count as the last 64)
 };
-struct TilesPlan {
-    LaunchGeom ld;             // the sweep's geometry (strips as launch_detect chooses them for this plane)
-    bool overlap, split;
+struct TilesPlan : DetectPlan {  // the sweep's geometry: strips as every detector takes them for this plane
     TileGeom tg;
     size_t rec_bytes;          // size of rec for this call
     int fold_threads;          // threads per tile of k_tiles_fold: 64 or 256

@@ -322,23 +322,67 @@ static inline int align_mode(const LaunchGeom& lg, bool aligned)
     if (!aligned) return 0;
     return lg.cols % 4 == 0 ? 2 : 1;
 }
-// launches KERNEL<..., true> and KERNEL<..., false> over their strips
-#define WM_LAUNCH_SWEEP(stream, lg, frames, aligned, KVEC, KGEN, ...)                                   \
-    do {                                                                                                \
-        const SweepPart pv_ = sweep_part(lg, frames, true, aligned);                                    \
-        if (pv_.run) { const Geom g = pv_.g; WM_KLAUNCH(KVEC, pv_.grid, dim3(BLOCK), 0, stream, __VA_ARGS__); } \
-        const SweepPart pg_ = sweep_part(lg, frames, false, aligned);                                   \
-        if (pg_.run) { const Geom g = pg_.g; WM_KLAUNCH(KGEN, pg_.grid, dim3(BLOCK), 0, stream, __VA_ARGS__); } \
-    } while (0)
+// launches the aligned part and then the generic part of a sweep: go(true_type / false_type, part) for each part that has strips.
+// quad: the 4-frames-per-block mapping where the batch allows it (sweeps that read W)
+template <typename F>
+static inline void for_each_sweep_part(const LaunchGeom& lg, int frames, int aligned, int quad, F&& go)
+{
+    const SweepPart pv = sweep_part(lg, frames, true, aligned, quad);
+    if (pv.run) go(std::true_type{}, pv);
+    const SweepPart pg = sweep_part(lg, frames, false, aligned, quad);
+    if (pg.run) go(std::false_type{}, pg);
+}
 
-// the same with the 4-frames-per-block mapping where the batch allows it (sweeps that read W)
-#define WM_LAUNCH_SWEEP_Q(stream, lg, frames, aligned, KVEC, KGEN, ...)                                 \
-    do {                                                                                                \
-        const SweepPart pv_ = sweep_part(lg, frames, true, aligned, 1);                                 \
-        if (pv_.run) { const Geom g = pv_.g; WM_KLAUNCH(KVEC, pv_.grid, dim3(BLOCK), 0, stream, __VA_ARGS__); } \
-        const SweepPart pg_ = sweep_part(lg, frames, false, aligned, 1);                                \
-        if (pg_.run) { const Geom g = pg_.g; WM_KLAUNCH(KGEN, pg_.grid, dim3(BLOCK), 0, stream, __VA_ARGS__); } \
-    } while (0)
+// the one mask / window switch: f(IC<MASK>, IC<PAD>) for ME (always 3x3) and for NVF windows of 2 * pad + 1
+template <typename F>
+static inline void for_mask_pad(int mask, int pad, F&& f)
+{
+    if (mask == 0) { f(IC<0>{}, IC<1>{}); return; }
+    switch (pad) {
+        case 1: f(IC<1>{}, IC<1>{}); break;
+        case 2: f(IC<1>{}, IC<2>{}); break;
+        case 3: f(IC<1>{}, IC<3>{}); break;
+        case 4: f(IC<1>{}, IC<4>{}); break;
+    }
+}
+
+// the embed sweeps: the base is the grey input itself (same plane, same layout), so the kernel takes it from its stencil window
+static inline bool same_plane(const PlaneDesc& x, const PlaneDesc& base)
+{
+    return base.p == x.p && base.pitch == x.pitch && base.fstride == x.fstride;
+}
+
+// Which strips a detector sweep (k_detect and the kernels that share its geometry) runs on.  Windows up to 7x7 on planes that
+// allow vector access and whose width is a multiple of 4: overlapped strips, more and narrower than the other sweeps of the call.
+// 3x3 windows on such planes with another width of STRIP + 8 or more: overlapped strips + one generic strip.  Else the plain strips
+static inline DetectPlan detect_plan(const LaunchGeom& lg, int mask, int pad, const PlaneDesc& x, int aligned_w)
+{
+    DetectPlan pl;
+    pl.overlap = (mask == 0 || pad <= 3) && align_mode(lg, x.aligned && aligned_w) == 2;
+    pl.split = (mask == 0 || pad == 1) && !pl.overlap && x.aligned && aligned_w && split_applies(lg.cols);
+    pl.ld = pl.overlap ? overlap_geom(lg) : (pl.split ? split_geom(lg) : lg);
+    return pl;
+}
+// The one choice of instances for a plan: go(IC<MASK>, IC<PAD>, IC<HC>, true_type / false_type, part) for every launch.  Overlapped
+// strips run the aligned instance; a split plane the aligned instance on its overlapped strips, then the generic one on its
+// generic strip; everything else is generic, a 9x9 window always and with HC = 2
+template <typename F>
+static inline void for_each_detect_launch(const DetectPlan& pl, int frames, int mask, int pad, F&& go)
+{
+    for_mask_pad(mask, pad, [&](auto m, auto p) {
+        constexpr int PAD = decltype(p)::value;
+        const IC<(PAD == 4 ? 2 : 1)> hc;
+        auto part = [&](auto vec, const SweepPart& sp) { if (sp.run) go(m, p, hc, vec, sp); };
+        if constexpr (PAD < 4) {
+            if (pl.overlap) return part(std::true_type{}, sweep_part_overlap(pl.ld, frames, 1));
+            if (pl.split) {
+                part(std::true_type{}, sweep_part_split_overlap(pl.ld, frames, 1));
+                return part(std::false_type{}, sweep_part_split_generic(pl.ld, frames, 1));
+            }
+        }
+        part(std::false_type{}, sweep_part(pl.ld, frames, false, 0, 1));
+    });
+}
 
 #define WM_DISPATCH_T(dtype, ...)                   \
     do {                                            \
