@@ -91,6 +91,8 @@ def main():
     import torch
     sys.path.insert(0, ROOT)
     wm = importlib.import_module("watermarking-gpu_amd")
+    if os.environ.get("WM_AB_LIB"):  # another build of the library (the parent commit's)
+        wm.LIB_PATH = os.environ["WM_AB_LIB"]
     synth = importlib.import_module("watermarking-gpu_amd.synth")
     R, Cc = a.rows, a.cols
     th, tw = (int(v) for v in a.tile.split("x"))

@@ -1,14 +1,5 @@
 // wm_k_embed.hip -- embed-side kernels: k_me_stats, k_nvf_stats (fold tail embed_scalars_frame), k_embed, k_mask (see wm_k_gram.hip header)
-#include "wm_march.hpp"
-
-#ifndef WM_RING3
-#define WM_RING3 UNROLL   // ring length of the 3-row x windows of k_me_stats / k_embed (rows in flight per wave = ring - 3)
-#endif
-
-#ifndef WM_HO_PFW
-#define WM_HO_PFW 3   // W / base rows in flight per wave in the hand-over instantiation of k_embed: 3 instead of 6 brings it from
-                      // 174 to 162 VGPRs, i.e. three waves per SIMD instead of two (+0.8 % frames/s on the hand-over leg)
-#endif
+#include "wm_embed_march.hpp"
 
 namespace wmk {
 
@@ -275,168 +266,9 @@ __global__ __launch_bounds__(BLOCK) void k_nvf_stats(const T* __restrict__ x, lo
 }
 
 // =================================================================================================
-// Gram hand-over (HandOver, wm_kernels.hpp): the lag products of y that stay inside this wave's tile, accumulated as
-// k_gram's march accumulates them (f64 FMAs of exact products; window of rows q, q+1, q+2 x columns c0-2 .. c0+5 in rotating
-// slots).  The partner rows behind the segment (q+1, q+2 of its last q rows) are computed here as well -- the march runs two
-// rows further, without storing them -- so that no product is left open between vertically adjacent tiles; what a lane cannot
-// see is y in other strips (lanes 0 / 63 get zeros for the neighbour they do not have): k_gram_ho's column seams (wm_k_gram.hip),
-// for which the lanes at a strip's two ends also store their two outermost columns of every row to a compact array (read back
-// from the plane, those 16 bytes per row and boundary would cost two 128-byte lines each).
+// k_embed: y = clamp(base + a * m * W, 0, 255) with the mask recomputed on the fly (WM_EMBED_BODY / embed_march, wm_embed_march.hpp)
+//   MASK 0 (ME): m = |e| / max|e|;  MASK 1 (NVF): m = nvf(x);  HO: with the Gram hand-over
 // =================================================================================================
-struct HoState {
-    double w[3][8];
-    double acc[13];
-    bool cv[4];
-};
-// the products of q row `w0` with itself (dr = 0), with `w1` (dr = 1) and with `w2` (dr = 2)
-__device__ __forceinline__ void ho_products(HoState& h, const double* w0, const double* w1, const double* w2)
-{
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const double xq = h.cv[k] ? w0[2 + k] : 0.0;
-        h.acc[0] = fma(xq, w0[2 + k], h.acc[0]);
-        h.acc[1] = fma(xq, w0[3 + k], h.acc[1]);
-        h.acc[2] = fma(xq, w0[4 + k], h.acc[2]);
-#pragma unroll
-        for (int b = 0; b < 5; ++b) {
-            h.acc[3 + b] = fma(xq, w1[k + b], h.acc[3 + b]);
-            h.acc[8 + b] = fma(xq, w2[k + b], h.acc[8 + b]);
-        }
-    }
-}
-// row r of y enters slot S; q row r - 2 (slot S + 1) is complete when `qvalid` (a core row of this segment)
-template <int S>
-__device__ __forceinline__ void ho_row(HoState& h, const float4& y, bool qvalid)
-{
-    double* s2 = h.w[S];
-    s2[0] = (double)dpp_from_prev(y.z, 0.0f); s2[1] = (double)dpp_from_prev(y.w, 0.0f);
-    s2[2] = (double)y.x; s2[3] = (double)y.y; s2[4] = (double)y.z; s2[5] = (double)y.w;
-    s2[6] = (double)dpp_from_next(y.x, 0.0f); s2[7] = (double)dpp_from_next(y.y, 0.0f);
-    if (qvalid) ho_products(h, h.w[(S + 1) % 3], h.w[(S + 2) % 3], s2);
-}
-
-// =================================================================================================
-// k_embed: y = clamp(base + a * m * W, 0, 255) with the mask recomputed on the fly
-//   MASK 0 (ME): m = |e| / max|e|;  MASK 1 (NVF): m = nvf(x)
-// =================================================================================================
-template <typename TX, typename TB, int NCH, int MASK, int PAD, bool VEC, bool BX, bool EDGE, bool HO = false>
-__device__ __forceinline__ void embed_march(const TX* __restrict__ xf, long long pitch, const float* __restrict__ W,
-                                            const TB* __restrict__ bptr, TB* __restrict__ optr, const PlaneDesc& base,
-                                            const PlaneDesc& out, const Geom& g, const WaveJob& j, float* lds, float* obuf,
-                                            const float (&c)[8], float a, float maxe, bool pass = false, double* horec = nullptr,
-                                            float* hoseam = nullptr, unsigned long long* hodig = nullptr)
-{
-    static_assert(!HO || (VEC && NCH == 1 && sizeof(TB) == 4), "hand-over: grey f32 planes on the aligned path");
-    constexpr int NR = MASK == 0 ? 3 : 2 * PAD + 1;
-    constexpr int HR = MASK == 0 ? 1 : PAD;  // halo rows above/below = halo columns left/right
-    constexpr int RG = VEC && NR == 3 ? WM_RING3 : UNROLL;
-    XMarch<TX, 1, HR, NR, VEC, PFX, EDGE, false, RG> xm;
-    constexpr int PW = HO ? WM_HO_PFW : PFW;  // rows of W / base in flight per wave
-    PMarch<float, VEC, PW> wm_;
-    // m = |e| / max|e| (Watermark.cpp:213-214): one reciprocal per wave, then div_by() per pixel (same quotient)
-    const float inv_maxe = 1.0f / maxe;
-    // BX: the base IS the grey input plane (video frames, grey images): its pixels are already in the stencil window,
-    // so the base stream -- a third of this kernel's loads -- is not issued at all
-    PMarch<TB, VEC, PW> bm[BX ? 1 : NCH];
-    // (hand-over: up to two rows of y behind the segment are computed, not stored -- the partner rows of its last q rows)
-    const int nout = j.re - j.rs, nrow = nout + (HO ? min(2, g.rows - j.re) : 0), n = nrow + 2 * HR;
-    const int c0 = j.c0s + 4 * j.lane;
-    xm.start(xf, pitch, g, j, lds, j.rs - HR, n);
-    wm_.start(W, g.cols, g.cols, j, j.rs, nrow);
-    if (!BX) {
-#pragma unroll
-        for (int ch = 0; ch < NCH; ++ch) bm[ch].start(bptr + (long long)ch * base.cstride, base.pitch, g.cols, j, j.rs, nrow);
-    }
-    HoState ho;
-    if constexpr (HO) {
-        static_assert(!HO || (HR == 1 && RG % 3 == 0), "hand-over: 3x3 windows (one x row ahead of the output row)");
-#pragma unroll
-        for (int a_ = 0; a_ < 3; ++a_)
-#pragma unroll
-            for (int b_ = 0; b_ < 8; ++b_) ho.w[a_][b_] = 0.0;
-#pragma unroll
-        for (int l = 0; l < 13; ++l) ho.acc[l] = 0.0;
-        // q pixels: the core columns 2 .. C-3 this lane owns (k_gram's column factor)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) ho.cv[k] = !EDGE || (c0 + k >= 2 && c0 + k <= g.cols - 3 && 4 * j.lane >= j.dup);
-    }
-    // digest of the stored y (dig_add, wm_device.hpp): the pixels this lane stores, as stored
-    unsigned long long dig = 0;
-    const uint32_t dcb = HO ? dig_col_key4(c0) : 0u;
-    // this lane's entry of the seam array, or null: lane 63 holds columns S-2, S-1 of the boundary behind its strip, the first
-    // lane that owns pixels (lane 0, or dup / 4 in a shifted last strip) holds columns S, S+1 of the boundary in front of it
-    float* seamp = nullptr;
-    bool seam_right = false;  // this lane stores its LAST two columns (the boundary behind the strip), else its first two
-    if constexpr (HO) {
-        const long long per_frame = (long long)(g.nstrips_total - 1) * g.rows * 4;
-        if (j.lane == WAVE - 1 && j.strip < g.nstrips_total - 1) { seamp = hoseam + (long long)j.frame * per_frame + (long long)j.strip * g.rows * 4; seam_right = true; }
-        else if (4 * j.lane == j.dup && j.strip > 0) seamp = hoseam + (long long)j.frame * per_frame + (long long)(j.strip - 1) * g.rows * 4 + 2;
-    }
-    march_n<2 * HR, RG>(n, [&](int i, auto qc, auto emit) {
-        constexpr int Q = decltype(qc)::value;
-        xm.template step<Q>(i);
-        if (decltype(emit)::value) {
-            const int o = i - 2 * HR;
-            constexpr int SLOT = (Q + 4 * UNROLL - 2 * HR) % PW;
-            const float4 w = wm_.template take<SLOT>();
-            float u[4];
-            float pr[4] = {0.f, 0.f, 0.f, 0.f};
-            if (MASK == 0) predict4<4>(xm.template row<Q>(0), xm.template row<Q>(1), xm.template row<Q>(2), c, pr);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                float m;
-                if (MASK == 0) {
-                    const float* mid = xm.template row<Q>(1);
-                    const float e = mid[4 + k] - pr[k];
-                    m = div_by(fabsf(e), maxe, inv_maxe);
-                } else {
-                    m = nvf_value<PAD, 4, Q>(xm, k);
-                }
-                u[k] = m * f4get(w, k);  // Watermark.cpp:169
-            }
-#pragma unroll
-            for (int ch = 0; ch < NCH; ++ch) {
-                float4 b;
-                if (BX) {
-                    const float* ctr = xm.template row<Q>(HR);  // the output row itself
-                    b = make_float4(ctr[4], ctr[5], ctr[6], ctr[7]);
-                } else {
-                    b = bm[ch].template take<SLOT>();
-                }
-                float4 y;
-                y.x = fminf(fmaxf(fmaf(u[0], a, b.x), 0.0f), 255.0f);
-                y.y = fminf(fmaxf(fmaf(u[1], a, b.y), 0.0f), 255.0f);
-                y.z = fminf(fmaxf(fmaf(u[2], a, b.z), 0.0f), 255.0f);
-                y.w = fminf(fmaxf(fmaf(u[3], a, b.w), 0.0f), 255.0f);
-                if constexpr (HO) {
-                    if (pass) y = b;  // unsolvable frame: out = base bit-exact (Watermark.cpp:164-165), and that is the plane the detector reads
-                    const int rq = j.rs + o - 2;  // the q row that row o completes (core rows 1 .. R-3; rq < re by construction)
-                    ho_row<Q % 3>(ho, y, o >= 2 && rq >= 1 && rq < g.rows - 2);
-                    if (seamp && o < nout)
-                        *reinterpret_cast<float2*>(seamp + (long long)(j.rs + o) * 4) = seam_right ? make_float2(y.z, y.w) : make_float2(y.x, y.y);
-                    if (o < nout && (!EDGE || 4 * j.lane >= j.dup))  // (duplicate lanes of a shifted last strip store nothing)
-                        dig_add4(dig, y.x, y.y, y.z, y.w, dig_row_key(j.rs + o), dcb);
-                }
-                if constexpr (VEC) {
-                    if ((!EDGE || 4 * j.lane >= j.dup) && (!HO || o < nout))  // duplicate lanes of a shifted last strip: the previous strip stores these pixels
-                        store4<TB, true>(optr + (long long)ch * out.cstride, out.pitch, j.rs + o, c0, g.cols, y);
-                } else {
-                    store_row_generic<TB>(optr + (long long)ch * out.cstride, out.pitch, j.rs + o, j.c0s, j.lane, g.cols, y, obuf);
-                }
-                if (!BX) bm[ch].template refill<SLOT>(o);
-            }
-            wm_.template refill<SLOT>(o);
-        }
-    });
-    if constexpr (HO) {
-        int idx;
-        const double t = wave_sum_multi<13>(ho.acc, j.lane, idx);
-        if (idx < 13) horec[idx] = t;
-        const unsigned long long dw = wave_sum_u64(dig);
-        if (j.lane == 0) *hodig = dw;
-    }
-}
-
 #ifndef WM_HO_BLOCKS
 #define WM_HO_BLOCKS 1
 #endif
@@ -446,46 +278,7 @@ __global__ __launch_bounds__(BLOCK, HO ? WM_HO_BLOCKS : 1) void k_embed(const TX
                                                  const float* __restrict__ coef, const int* __restrict__ status,
                                                  const EmbedScalars* __restrict__ scal, HandOver ho)
 {
-    __shared__ __attribute__((aligned(16))) float s_row[WPB][2 * RowBuf<1>::N];
-    __shared__ __attribute__((aligned(16))) float s_out[VEC ? 1 : WPB][VEC ? 4 : STRIP];  // generic path: store re-layout rows
-    const WaveJob j = make_job(g);
-    const int frame = j.frame;
-    if (!j.valid) return;
-    const TB* bptr = static_cast<const TB*>(base.p) + (long long)frame * base.fstride;
-    TB* optr = static_cast<TB*>(const_cast<void*>(out.p)) + (long long)frame * out.fstride;
-    const int st = MASK == 0 ? status[frame] : 0;
-    if (!HO && st != 0) {
-        // unsolvable: out = base bit-exact (Watermark.cpp:164-165)
-        if (bptr != optr) {
-            const int c0 = j.c0s + 4 * j.lane;
-            for (int ch = 0; ch < NCH; ++ch)
-                for (int r = j.rs; r < j.re; ++r) {
-                    const TB* rb = bptr + (long long)ch * base.cstride + (long long)r * base.pitch;
-                    TB* ro = optr + (long long)ch * out.cstride + (long long)r * out.pitch;
-                    for (int k = 0; k < 4; ++k)
-                        if (c0 + k < g.cols) ro[c0 + k] = rb[c0 + k];
-                }
-        }
-        return;
-    }
-    float c[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (MASK == 0) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) c[k] = coef[frame * 8 + k];
-    }
-    const float a = applied_strength(scal[frame].a);
-    const float maxe = scal[frame].maxe;
-    const TX* xf = x + (long long)frame * fstride;
-    // hand-over: an unsolvable frame runs the march too (y = base, selected per row) -- its lag sums are the detector's
-    const bool pass = HO && st != 0;
-    double* horec = HO ? ho.rec + ((long long)frame * ho.stride + j.rec) * 13 : nullptr;
-    float* hoseam = HO ? ho.seam : nullptr;
-    unsigned long long* hodig = HO ? ho.dig + (long long)frame * ho.stride + j.rec : nullptr;
-    // NVF windows (PAD > 1) keep the single instance: their halo fix-up is a small share of the step
-    if (MASK != 0 || strip_on_edge<VEC>(g, j))
-        embed_march<TX, TB, NCH, MASK, PAD, VEC, BX, true, HO>(xf, pitch, W, bptr, optr, base, out, g, j, s_row[j.wave], s_out[VEC ? 0 : j.wave], c, a, maxe, pass, horec, hoseam, hodig);
-    else
-        embed_march<TX, TB, NCH, MASK, PAD, VEC, BX, (MASK != 0), HO>(xf, pitch, W, bptr, optr, base, out, g, j, s_row[j.wave], s_out[VEC ? 0 : j.wave], c, a, maxe, pass, horec, hoseam, hodig);
+    WM_EMBED_BODY(HO, false, ho, nullptr);
 }
 
 // =================================================================================================
@@ -611,34 +404,21 @@ static bool launch_embed_tt(hipStream_t s, const LaunchGeom& lg, int frames, int
             return true;
         }
     }
-    for_mask_pad(mask, pad, [&](auto m, auto p) {
-        auto sweep = [&](auto base_is_x) {
-            for_each_sweep_part(lg, frames, al, 1, [&](auto vec, const SweepPart& sp) {
-                constexpr bool BX = decltype(base_is_x)::value;
-                WM_KLAUNCH((k_embed<TX, TB, (BX ? 1 : NCH), decltype(m)::value, decltype(p)::value, decltype(vec)::value, BX>), sp.grid,
-                           dim3(BLOCK), 0, s, (const TX*)x.p, x.pitch, x.fstride, W, base, out, sp.g, coef, status, scal, none);
-            });
-        };
-        if (bx) sweep(std::true_type{}); else sweep(std::false_type{});
+    for_each_embed_launch<NCH>(lg, frames, mask, pad, al, bx, [&](auto m, auto p, auto vec, auto nch, auto base_is_x, const SweepPart& sp) {
+        WM_KLAUNCH((k_embed<TX, TB, decltype(nch)::value, decltype(m)::value, decltype(p)::value, decltype(vec)::value, decltype(base_is_x)::value>),
+                   sp.grid, dim3(BLOCK), 0, s, (const TX*)x.p, x.pitch, x.fstride, W, base, out, sp.g, coef, status, scal, none);
     });
     return false;
-}
-template <typename TX, typename TB>
-static bool launch_embed_t(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x,
-                           const float* W, int aligned_w, const PlaneDesc& base, const PlaneDesc& out, const float* coef,
-                           const int* status, const EmbedScalars* scal, const HandOver* ho)
-{
-    if (base.channels == 3) return launch_embed_tt<TX, TB, 3>(s, lg, frames, mask, pad, x, W, aligned_w, base, out, coef, status, scal, ho);
-    return launch_embed_tt<TX, TB, 1>(s, lg, frames, mask, pad, x, W, aligned_w, base, out, coef, status, scal, ho);
 }
 bool launch_embed(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* W,
                   int aligned_w, const PlaneDesc& base, const PlaneDesc& out, const float* coef, const int* status,
                   const EmbedScalars* scal, const HandOver* ho)
 {
-    if (x.dtype == 0 && base.dtype == 0) return launch_embed_t<float, float>(s, lg, frames, mask, pad, x, W, aligned_w, base, out, coef, status, scal, ho);
-    if (x.dtype == 1 && base.dtype == 1) return launch_embed_t<uint8_t, uint8_t>(s, lg, frames, mask, pad, x, W, aligned_w, base, out, coef, status, scal, ho);
-    // mixed f32/u8 planes are rejected by the API layer (the reference converts whole frames, main.cpp:355-357)
-    return false;
+    bool handed = false;
+    for_embed_planes(x, base, [&](auto t, auto nch) {
+        handed = launch_embed_tt<decltype(t), decltype(t), decltype(nch)::value>(s, lg, frames, mask, pad, x, W, aligned_w, base, out, coef, status, scal, ho);
+    });
+    return handed;
 }
 
 template <typename T>

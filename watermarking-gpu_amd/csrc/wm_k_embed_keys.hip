@@ -285,7 +285,7 @@ __global__ __launch_bounds__(BLOCK) void k_embed_keys_fold(EKeysArgs ka, int qua
 }
 
 // =================================================================================================
-// k_embed_keys: embed_march (wm_k_embed.hip) with y = clamp(base + a_k * m * W_k, 0, 255) for every key of the group, on ONE
+// k_embed_keys: embed_march (wm_embed_march.hpp) with y = clamp(base + a_k * m * W_k, 0, 255) for every key of the group, on ONE
 // channel of the base (a planar-RGB base is three launches, one per channel: y of a channel depends on that channel's base only)
 // =================================================================================================
 template <typename T, int MASK, int PAD, bool VEC, bool BX, bool EDGE>

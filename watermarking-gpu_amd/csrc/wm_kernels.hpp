@@ -275,8 +275,8 @@ void launch_embed_keys(hipStream_t s, const LaunchGeom& lg, int frames, int mask
                        long long kstride, int nkeys, int aligned_w, const PlaneDesc& base, const PlaneDesc& out, const float* coef,
                        const int* status, void* scratch, int rstride);
 int embed_keys_group(void);  // keys per group of k_stats_keys / k_embed_keys (compile-time EKG)
-// a payload in the mark (wm_embed_signs / wm_detect_bits, wm_k_bits.hip).  k_embed_signs is k_embed's sweep (never the hand-over
-// instance) with u = m W multiplied by the sign of the pixel's tile: signs [frames][ny][nx] int8 in {-1, 0, +1} on the device, tile
+// a payload in the mark (wm_embed_signs / wm_detect_bits, wm_k_bits.hip).  k_embed_signs is k_embed's sweep (the same body, march
+// and launch loop, wm_embed_march.hpp; never the hand-over) with u = m W multiplied by the sign of the pixel's tile: signs [frames][ny][nx] int8 in {-1, 0, +1} on the device, tile
 // geometry wm_tiles_shape's.  k_bits_fold: one wave per (frame, bit) adds the rows of sums [frames][ntiles][3] (k_tiles_fold's)
 // named by idx [start[bit], start[bit + 1]) one after the other and writes res[frame * nbits + bit] = {status, soft}
 void launch_embed_signs(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* W,
