@@ -31,31 +31,40 @@ def _faults(wm):
     return {"mask": (bad, b"bad mask type"), "me_p": (wm.WM_ERR_BAD_P, b"ME mask needs p == 3"), "slot": (bad, b"bad slot"),
             "shape": (bad, b"engine was initialised for"), "dtype_pair": (bad, b"same dtype"), "dtype": (bad, b"bad dtype"),
             "mask_out": (bad, b"mask_out must be"), "bank": (bad, b"the key bank is"), "tile": (bad, b"tile shape"),
-            "key": (bad, b"of a bank of"), "window": (bad, b"leave the")}
+            "key": (bad, b"of a bank of"), "window": (bad, b"leave the"), "band": (bad, b"not in band mode")}
 
 
 # the order in which each entry point looks at its arguments: of the faults present, the first one listed is reported
 # ("me_p": the ME mask on an engine with p != 3; "dtype_pair": in_gray f32 with a u8 base and out; "dtype": a plane whose dtype
-# is no dtype; "mask_out": a u8 mask plane)
+# is no dtype; "mask_out": a u8 mask plane; "band": the engine in band mode (wm_band_configure), which these calls refuse)
 ORDER = {
     "wm_embed": ["mask", "me_p", "slot", "shape", "dtype_pair"],
     "wm_detect": ["mask", "me_p", "slot", "shape", "dtype"],
-    "wm_detect_keys": ["mask", "me_p", "bank", "slot", "shape", "dtype"],
-    "wm_detect_offsets": ["mask", "me_p", "key", "bank", "window", "slot", "shape", "dtype"],
-    "wm_detect_tiles": ["tile", "mask", "me_p", "slot", "shape", "dtype"],
-    "wm_embed_keys": ["mask", "me_p", "bank", "slot", "shape", "dtype_pair"],
+    "wm_detect_keys": ["mask", "me_p", "bank", "band", "slot", "shape", "dtype"],
+    "wm_detect_offsets": ["mask", "me_p", "key", "bank", "window", "band", "slot", "shape", "dtype"],
+    "wm_detect_tiles": ["tile", "mask", "me_p", "band", "slot", "shape", "dtype"],
+    "wm_detect_keys_tiles": ["tile", "mask", "me_p", "bank", "band", "slot", "shape", "dtype"],
+    "wm_embed_signs": ["tile", "mask", "me_p", "band", "slot", "shape", "dtype_pair"],
+    "wm_embed_bits": ["tile", "mask", "me_p", "band", "slot", "shape", "dtype_pair"],
+    "wm_detect_bits": ["tile", "mask", "me_p", "band", "slot", "shape", "dtype"],
+    "wm_embed_keys": ["mask", "me_p", "bank", "band", "slot", "shape", "dtype_pair"],
     "wm_compute_mask": ["mask", "me_p", "slot", "shape", "mask_out"],
     "wm_band_stats": ["slot", "mask", "me_p", "shape", "dtype"],
     "wm_band_detect_sums": ["slot", "mask", "me_p", "shape", "dtype"],
 }
 COMMON = [{"mask", "slot"}, {"slot", "shape"}]
+BAND = [{"mask", "band"}, {"band", "slot"}]  # (with p = 5 the first also sets "me_p" against "band")
 PAIRS = {
     "wm_embed": COMMON + [{"shape", "dtype_pair"}],
     "wm_detect": COMMON + [{"shape", "dtype"}],
-    "wm_detect_keys": COMMON + [{"shape", "dtype"}, {"bank", "slot"}],
-    "wm_detect_offsets": COMMON + [{"shape", "dtype"}, {"bank", "slot"}, {"key", "window"}],
-    "wm_detect_tiles": COMMON + [{"shape", "dtype"}, {"tile", "mask"}],
-    "wm_embed_keys": COMMON + [{"shape", "dtype_pair"}, {"bank", "slot"}],
+    "wm_detect_keys": COMMON + [{"shape", "dtype"}, {"bank", "slot"}] + BAND + [{"bank", "band"}],
+    "wm_detect_offsets": COMMON + [{"shape", "dtype"}, {"bank", "slot"}, {"key", "window"}] + BAND + [{"window", "band"}],
+    "wm_detect_tiles": COMMON + [{"shape", "dtype"}, {"tile", "mask"}] + BAND,
+    "wm_detect_keys_tiles": COMMON + [{"shape", "dtype"}, {"tile", "mask"}, {"bank", "slot"}] + BAND + [{"bank", "band"}],
+    "wm_embed_signs": COMMON + [{"shape", "dtype_pair"}, {"tile", "mask"}] + BAND,
+    "wm_embed_bits": COMMON + [{"shape", "dtype_pair"}, {"tile", "mask"}] + BAND,
+    "wm_detect_bits": COMMON + [{"shape", "dtype"}, {"tile", "mask"}] + BAND,
+    "wm_embed_keys": COMMON + [{"shape", "dtype_pair"}, {"bank", "slot"}] + BAND + [{"bank", "band"}],
     "wm_compute_mask": COMMON + [{"shape", "mask_out"}],
     "wm_band_stats": COMMON + [{"shape", "dtype"}],
     "wm_band_detect_sums": COMMON + [{"shape", "dtype"}],
@@ -80,6 +89,14 @@ def test_error_precedence(wm, tc):
     yk = torch.empty((K, R, CC), dtype=torch.float32, device="cuda")
     yk8 = torch.empty((K, R, CC), dtype=torch.uint8, device="cuda")
     mp = torch.zeros((1, CC // 32), dtype=torch.float32, device="cuda")
+    mkp = torch.zeros((K, 1, CC // 32), dtype=torch.float32, device="cuda")
+    NBITS = 2
+    signs = np.ones(CC // 32, np.int8)  # one frame of 1 x 8 tiles
+    tile_bit = wm.Watermark.bits_layout(1, CC // 32, NBITS, 5)
+    payload = np.array([2], np.uint8)
+
+    def vp(a):
+        return a.ctypes.data_as(C.c_void_p)
     bank = wm.KeySet(R, CC, K)
     bank_other = wm.KeySet(R, CC - 4, K)      # not the engine's shape, and smaller than it
     bank_large = wm.KeySet(KEY_R, KEY_C, K)
@@ -99,6 +116,13 @@ def test_error_precedence(wm, tc):
             pin.dtype = 7
         pair8 = "dtype_pair" in present
         ref = C.byref
+        tr = 36 if "tile" in present else 32
+        if "band" in present:  # the whole plane as one band: band mode with no halo to ask for
+            assert L.wm_band_configure(ctx, 0, R, R) == wm.WM_OK
+            try:
+                return call(ctx, name, mask, present - {"band"})
+            finally:
+                assert L.wm_band_configure(ctx, 0, 0, 0) == wm.WM_OK
         if name == "wm_embed":
             return L.wm_embed(ctx, m, ref(pin), ref(good8 if pair8 else good), ref(pout8 if pair8 else pout), fbuf, None, slot)
         if name == "wm_detect":
@@ -110,7 +134,17 @@ def test_error_precedence(wm, tc):
             return L.wm_detect_offsets(ctx, m, ref(pin), kb.handle, K + 2 if "key" in present else 1, 3 if "window" in present else 0, 0, 2, 2,
                                        fbuf, None, slot)
         if name == "wm_detect_tiles":
-            return L.wm_detect_tiles(ctx, m, ref(pin), 36 if "tile" in present else 32, 32, C.c_void_p(mp.data_ptr()), None, None, slot)
+            return L.wm_detect_tiles(ctx, m, ref(pin), tr, 32, C.c_void_p(mp.data_ptr()), None, None, slot)
+        if name == "wm_detect_keys_tiles":
+            return L.wm_detect_keys_tiles(ctx, m, ref(pin), (bank_other if "bank" in present else bank).handle, tr, 32, C.c_void_p(mkp.data_ptr()), None,
+                                          None, slot)
+        if name == "wm_embed_signs":
+            return L.wm_embed_signs(ctx, m, ref(pin), ref(good8 if pair8 else good), ref(pout8 if pair8 else pout), tr, 32, vp(signs), fbuf, None, slot)
+        if name == "wm_embed_bits":
+            return L.wm_embed_bits(ctx, m, ref(pin), ref(good8 if pair8 else good), ref(pout8 if pair8 else pout), tr, 32, vp(tile_bit), NBITS,
+                                   vp(payload), fbuf, None, slot)
+        if name == "wm_detect_bits":
+            return L.wm_detect_bits(ctx, m, ref(pin), tr, 32, vp(tile_bit), NBITS, fbuf, None, slot)
         if name == "wm_embed_keys":
             return L.wm_embed_keys(ctx, m, ref(pin), ref(good8 if pair8 else good), (bank_other if "bank" in present else bank).handle,
                                    ref(pk8 if pair8 else pk), fbuf, None, slot)
@@ -133,7 +167,7 @@ def test_error_precedence(wm, tc):
                         present.add("me_p")
                     first = next(f for f in ORDER[name] if f in present)
                     want_rc, want_text = faults[first]
-                    rc = call(eng._ctx, name, mask, pair)
+                    rc = call(eng._ctx, name, mask, set(pair))
                     text = L.wm_last_error(eng._ctx)
                     assert rc == want_rc, (p, name, sorted(pair), mask, first, rc, text)
                     assert want_text in text, (p, name, sorted(pair), mask, first, text)
@@ -156,11 +190,13 @@ def test_error_precedence(wm, tc):
 
 # ---- one wm_sync behind every kind of queued call --------------------------------------------------------------------------
 SENTINEL = -7.5
+NBITS = 2
 
 
 def _run_all(wm, torch, eng, mask, slot, inputs):
-    """embed, detect of WM_MEM_SLOT_OUT, detect_keys, embed_keys, detect_offsets, detect_tiles and wm_compute_mask on `slot`;
-    returns every buffer the calls deliver into (the caller syncs a real slot; WM_SLOT_SYNC has delivered on return)"""
+    """embed, detect of WM_MEM_SLOT_OUT, detect_keys, embed_keys, detect_offsets, detect_tiles, wm_compute_mask, detect_keys_tiles,
+    detect_bits and embed_signs on `slot`; returns every buffer the calls deliver into (the caller syncs a real slot; WM_SLOT_SYNC
+    has delivered on return)"""
     L = wm.lib()
     xt, bank, bank_large = inputs
     mt = wm.MASK_TYPE(mask)
@@ -176,7 +212,13 @@ def _run_all(wm, torch, eng, mask, slot, inputs):
         "sums": torch.zeros((F, ny, nx, 3), dtype=torch.float64, device="cuda"), "map_st": np.full(F, -5, np.int32),
         "m": torch.zeros_like(xt), "e": torch.zeros_like(xt),
         "coef": (C.c_float * (8 * F))(*([SENTINEL] * (8 * F))), "coef_st": (C.c_int * F)(*([-5] * F)),
+        "kmap": torch.zeros((F, K, ny, nx), dtype=torch.float32, device="cuda"),
+        "ksums": torch.zeros((F, K, ny, nx, 3), dtype=torch.float64, device="cuda"), "kmap_st": np.full(F, -5, np.int32),
+        "soft": np.full((F, NBITS), SENTINEL, np.float32), "soft_st": np.full(F, -5, np.int32),
+        "ys": torch.zeros_like(xt), "as": np.full(F, SENTINEL, np.float32), "as_st": np.full(F, -5, np.int32),
     }
+    tile_bit = wm.Watermark.bits_layout(ny, nx, NBITS, 5)
+    signs = np.where(np.arange(F * ny * nx) % 3 == 0, -1, 1).astype(np.int8)
     torch.cuda.synchronize()
     slot_plane = wm.wm_plane(None, R, CC, 1, wm.WM_F32, wm.WM_MEM_SLOT_OUT, F, CC, 0, R * CC)
     eng.embed_async(xt, xt, d["y"], mt, slot, d["a"], d["a_st"])
@@ -188,6 +230,9 @@ def _run_all(wm, torch, eng, mask, slot, inputs):
     pin, pm, pe = wm.plane_of(xt, 1), wm.plane_of(d["m"], 1), wm.plane_of(d["e"], 1)
     rc = L.wm_compute_mask(eng._ctx, mask, C.byref(pin), C.byref(pm), C.byref(pe), d["coef"], d["coef_st"], slot)
     assert rc >= 0, L.wm_last_error(eng._ctx)
+    eng.detect_keys_tiles_async(d["y"], bank, 32, 32, mt, slot, d["kmap"], d["ksums"], d["kmap_st"])
+    eng.detect_bits_async(d["y"], 32, 32, tile_bit, NBITS, mt, slot, d["soft"], d["soft_st"])
+    eng.embed_signs_async(xt, xt, d["ys"], 32, 32, signs, mt, slot, d["as"], d["as_st"])
     return d
 
 
@@ -199,7 +244,7 @@ def _bits(v):
 
 @pytest.mark.parametrize("mask", [0, 1])
 def test_mixed_queue_delivers_like_sync(wm, tc, mask):
-    """Seven calls of seven kinds queued on one slot, frame 1 a flat frame, then ONE wm_sync: every value, status, coefficient and
+    """Ten calls of ten kinds queued on one slot, frame 1 a flat frame, then ONE wm_sync: every value, status, coefficient and
     plane equals, bit for bit, what the same calls deliver when each is made with WM_SLOT_SYNC on a fresh engine.  Under ME the
     flat frame is unsolvable for every call and its strengths (single and all K) keep their sentinel; under NVF it is solvable
     for the embed-side calls and unsolvable for the detectors, which solve the prediction system under either mask"""
@@ -237,13 +282,16 @@ def test_mixed_queue_delivers_like_sync(wm, tc, mask):
         assert list(got[name]) == embed_st, (name, list(got[name]))
     for name in ("corr_st", "ck_st", "co_st", "map_st"):
         assert list(got[name]) == detect_st, (name, list(got[name]))
+    assert list(got["as_st"]) == embed_st and list(got["kmap_st"]) == detect_st and list(got["soft_st"]) == detect_st
     assert rc == wm.WM_UNSOLVABLE
     assert got["corr"][1] == 0.0 and np.all(got["ck"][1] == 0.0) and np.all(got["co"][1] == 0.0)  # detectors deliver 0
     if mask == 0:
         assert got["a"][1] == SENTINEL and np.all(got["ak"][1] == SENTINEL)  # embeds keep the caller's value
+        assert got["as"][1] == SENTINEL
     else:
         assert np.isinf(got["a"][1]) and np.all(np.isinf(got["ak"][1]))  # solvable, no energy: the oracle's +inf is delivered
     assert got["a"][0] != SENTINEL and np.all(got["ak"][0] != SENTINEL) and np.all(got["ck"][0] != SENTINEL)
+    assert got["as"][0] != SENTINEL and np.all(got["soft"][0] != SENTINEL) and np.all(got["soft"][1] == 0.0)
     # the marked frame answers to key 1, the engine's W (an unmarked frame of this size scores about 1 / sqrt(R CC) = 0.01)
     print("mask", mask, "a", got["a"][0], "corr", got["corr"][0], "keys", got["ck"][0], "offsets", got["co"][0].ravel())
     assert float(got["corr"][0]) > 0.1 and float(got["ck"][0, 1]) > 0.1 and float(got["co"][0, 1, 1]) > 0.1

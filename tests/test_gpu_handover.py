@@ -300,3 +300,41 @@ def test_handover_verify_mode_catches_a_plane_modified_behind_the_embed(wm, tc, 
     plain.sync(1)
     assert max(abs(p - q) for p, q in zip(corr2, ref)) <= 1e-6
     eng.close(); plain.close()
+
+
+@pytest.mark.parametrize("writer", ["embed", "signs"])
+def test_an_embed_on_another_slot_over_the_plane_ends_the_handover(wm, tc, writer):
+    """slot 0 embeds into B under wm_set_handover and keeps the lag sums of B (a detector of its WM_MEM_SLOT_OUT takes them: one
+    k_gram_ho); wm_embed / wm_embed_signs on slot 1 then writes another frame's output over B.  The next detector of slot 0's
+    WM_MEM_SLOT_OUT must take the ordinary Gram sweep (no second k_gram_ho) and score B as it now is, bit for bit as an engine
+    without hand-overs does -- not from the sums of the plane that is gone"""
+    torch = tc
+    R, Cc, F = 100, 512, 2  # (k_embed hands over from two frames on)
+    W = synth_watermark(R, Cc)
+    eng = wm.Watermark(R, Cc, W, 3, 40.0, nslots=2, max_frames=F)
+    eng.set_handover(True)
+    eng.prof_enable(True)
+    x0 = torch.from_numpy(np.stack([synth_frame(R, Cc, frame=4 + f) for f in range(F)])).cuda()
+    x1 = torch.from_numpy(np.stack([synth_frame(R, Cc, frame=12 + f) for f in range(F)])).cuda()
+    B = torch.empty_like(x0)
+    torch.cuda.synchronize()
+    before, got, ref = (C.c_float * F)(), (C.c_float * F)(), (C.c_float * F)()
+    eng.embed_async(x0, x0, B, wm.MASK_TYPE.ME, 0)
+    eng.detect_async(slot_plane(wm, R, Cc, F), wm.MASK_TYPE.ME, 0, corr_out=before)
+    eng.sync(0)
+    assert eng.prof_report()["k_gram_ho"][0] == 1  # the hand-over is live
+    if writer == "embed":
+        eng.embed_async(x1, x1, B, wm.MASK_TYPE.ME, 1)
+    else:
+        ny, nx = wm.Watermark.tiles_shape(R, Cc, 32, 32)
+        eng.embed_signs_async(x1, x1, B, 32, 32, np.ones(F * ny * nx, np.int8), wm.MASK_TYPE.ME, 1)
+    eng.sync(1)
+    eng.detect_async(slot_plane(wm, R, Cc, F), wm.MASK_TYPE.ME, 0, corr_out=got)
+    eng.sync(0)
+    assert eng.prof_report()["k_gram_ho"][0] == 1, "the detector took the sums of a plane another slot has overwritten"
+    plain = wm.Watermark(R, Cc, W, 3, 40.0, nslots=2, max_frames=F)
+    plain.set_checked_handover(False)
+    plain.detect_async(B, wm.MASK_TYPE.ME, 0, corr_out=ref)
+    plain.sync(0)
+    assert list(got) == list(ref) and list(got) != list(before), (writer, list(before), list(got), list(ref))
+    eng.close(); plain.close()

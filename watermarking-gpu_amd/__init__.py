@@ -289,6 +289,11 @@ class KeySet:
             pass
 
 
+def _keys_handle(keys):
+    """a KeySet or a raw wm_keys handle"""
+    return keys.handle if isinstance(keys, KeySet) else keys
+
+
 class Watermark:
     """Functions for watermark computation and detection (Watermark.hpp:26-72).
 
@@ -312,6 +317,12 @@ class Watermark:
             _raise(rc)
         if (nslots, max_frames) != (2, 1):
             self.configure(nslots, max_frames)
+
+    def _chk(self, rc):
+        """a call's return code: raises for an error (negative), passes WM_OK / WM_UNSOLVABLE on"""
+        if rc < 0:
+            _raise(rc, self._ctx)
+        return rc
 
     @classmethod
     def generated(cls, rows, cols, seed, p, psnr, device=0, nslots=2, max_frames=1):
@@ -429,22 +440,13 @@ class Watermark:
         the reference returns the array and writes the strength through a float& argument.
         Unsolvable system: returns outputImage unchanged and strength None (reference leaves it unset)."""
         import torch
-        rgb = outputImage.dim() - inputImage.dim() == 1
-        pin = plane_of(inputImage, 1)
-        pbase = plane_of(outputImage, 3 if rgb else 1)
         if out is None:
             out = torch.empty_like(outputImage)
-        pout = plane_of(out, 3 if rgb else 1)
-        frames = pin.frames
-        a = (C.c_float * frames)(*([float("nan")] * frames))
-        st = (C.c_int * frames)()
+        pin, pbase, pout = self._embed_planes(inputImage, outputImage, out)
+        a, st = self._strength_bufs(pin.frames)
         torch.cuda.current_stream().synchronize()
-        rc = lib().wm_embed(self._ctx, int(maskType), C.byref(pin), C.byref(pbase), C.byref(pout), a, st, WM_SLOT_SYNC)
-        if rc < 0:
-            _raise(rc, self._ctx)
-        if inputImage.dim() == 2:
-            return out, (None if st[0] != 0 else a[0])
-        return out, [None if st[f] != 0 else a[f] for f in range(frames)]
+        self._chk(lib().wm_embed(self._ctx, int(maskType), C.byref(pin), C.byref(pbase), C.byref(pout), a, st, WM_SLOT_SYNC))
+        return out, self._strengths(a, st, inputImage.dim() == 2)
 
     def detectWatermark(self, watermarkedImage, maskType):
         """Watermark.cpp:234-250; 0.0 for an unsolvable system"""
@@ -453,9 +455,7 @@ class Watermark:
         frames = pimg.frames
         corr = (C.c_float * frames)()
         torch.cuda.current_stream().synchronize()
-        rc = lib().wm_detect(self._ctx, int(maskType), C.byref(pimg), corr, None, WM_SLOT_SYNC)
-        if rc < 0:
-            _raise(rc, self._ctx)
+        self._chk(lib().wm_detect(self._ctx, int(maskType), C.byref(pimg), corr, None, WM_SLOT_SYNC))
         if watermarkedImage.dim() == 2:
             return corr[0]
         return list(corr)
@@ -468,10 +468,8 @@ class Watermark:
         frames, K = pimg.frames, keys.count
         corr = np.zeros((frames, K), np.float32)
         torch.cuda.current_stream().synchronize()
-        rc = lib().wm_detect_keys(self._ctx, int(maskType), C.byref(pimg), keys.handle, corr.ctypes.data_as(_P(C.c_float)), None,
-                                  WM_SLOT_SYNC)
-        if rc < 0:
-            _raise(rc, self._ctx)
+        self._chk(lib().wm_detect_keys(self._ctx, int(maskType), C.byref(pimg), keys.handle, corr.ctypes.data_as(_P(C.c_float)), None,
+                                       WM_SLOT_SYNC))
         return corr[0] if image.dim() == 2 else corr
 
     def detectOffsets(self, image, keys, k, oy0, ox0, ny, nx, maskType):
@@ -485,10 +483,8 @@ class Watermark:
         frames = pimg.frames
         corr = np.zeros((frames, max(ny, 0), max(nx, 0)), np.float32)
         torch.cuda.current_stream().synchronize()
-        rc = lib().wm_detect_offsets(self._ctx, int(maskType), C.byref(pimg), keys.handle, k, oy0, ox0, ny, nx,
-                                     corr.ctypes.data_as(_P(C.c_float)), None, WM_SLOT_SYNC)
-        if rc < 0:
-            _raise(rc, self._ctx)
+        self._chk(lib().wm_detect_offsets(self._ctx, int(maskType), C.byref(pimg), keys.handle, k, oy0, ox0, ny, nx,
+                                          corr.ctypes.data_as(_P(C.c_float)), None, WM_SLOT_SYNC))
         return corr[0] if image.dim() == 2 else corr
 
     @staticmethod
@@ -549,19 +545,25 @@ class Watermark:
             _raise(rc)
         return tb
 
+    @staticmethod
+    def _strength_bufs(frames):
+        """(a, st) a synchronous embed delivers into: NaN strengths and zero statuses, one per frame"""
+        return (C.c_float * frames)(*([float("nan")] * frames)), (C.c_int * frames)()
+
+    @staticmethod
+    def _strengths(a, st, single):
+        """the strength, or None for an unsolvable system, of every frame (of the one grey frame: single)"""
+        got = [None if st[f] != 0 else a[f] for f in range(len(st))]
+        return got[0] if single else got
+
     def _embed_tiles(self, how, inputImage, outputImage, maskType, out):
         import torch
-        rgb = outputImage.dim() - inputImage.dim() == 1
         if out is None:
             out = torch.empty_like(outputImage)
-        frames = plane_of(inputImage, 1).frames
-        a = (C.c_float * frames)(*([float("nan")] * frames))
-        st = (C.c_int * frames)()
+        a, st = self._strength_bufs(plane_of(inputImage, 1).frames)
         torch.cuda.current_stream().synchronize()
         how(inputImage, outputImage, out, maskType, WM_SLOT_SYNC, a, st)
-        if inputImage.dim() == 2:
-            return out, (None if st[0] != 0 else a[0])
-        return out, [None if st[f] != 0 else a[f] for f in range(frames)]
+        return out, self._strengths(a, st, inputImage.dim() == 2)
 
     def makeWatermarkSigns(self, inputImage, outputImage, tile_rows, tile_cols, signs, maskType, out=None):
         """makeWatermark with the watermark term of every pixel multiplied by the sign of its tile (wm.h wm_embed_signs): `signs`
@@ -611,10 +613,8 @@ class Watermark:
         pout = plane_of(out.view((frames * K,) + per), ch)
         a = np.full((frames, K), np.nan, np.float32)
         torch.cuda.current_stream().synchronize()
-        rc = lib().wm_embed_keys(self._ctx, int(maskType), C.byref(pin), C.byref(pbase), keys.handle, C.byref(pout),
-                                 a.ctypes.data_as(_P(C.c_float)), None, WM_SLOT_SYNC)
-        if rc < 0:
-            _raise(rc, self._ctx)
+        self._chk(lib().wm_embed_keys(self._ctx, int(maskType), C.byref(pin), C.byref(pbase), keys.handle, C.byref(pout),
+                                      a.ctypes.data_as(_P(C.c_float)), None, WM_SLOT_SYNC))
         return out, (a if batched else a[0])
 
     def makeAndDetect(self, inputImage, outputImage, maskType, out=None):
@@ -625,17 +625,12 @@ class Watermark:
         if out is None:
             out = torch.empty_like(outputImage)
         pout = plane_of(out, 1)
-        frames = pin.frames
-        a = (C.c_float * frames)(*([float("nan")] * frames))
-        corr = (C.c_float * frames)()
-        st = (C.c_int * frames)()
+        a, st = self._strength_bufs(pin.frames)
+        corr = (C.c_float * pin.frames)()
         torch.cuda.current_stream().synchronize()
-        rc = lib().wm_embed_detect(self._ctx, int(maskType), C.byref(pin), C.byref(pbase), C.byref(pout), a, corr, st, WM_SLOT_SYNC)
-        if rc < 0:
-            _raise(rc, self._ctx)
-        if inputImage.dim() == 2:
-            return out, (None if st[0] != 0 else a[0]), corr[0]
-        return out, [None if st[f] != 0 else a[f] for f in range(frames)], list(corr)
+        self._chk(lib().wm_embed_detect(self._ctx, int(maskType), C.byref(pin), C.byref(pbase), C.byref(pout), a, corr, st, WM_SLOT_SYNC))
+        single = inputImage.dim() == 2
+        return out, self._strengths(a, st, single), (corr[0] if single else list(corr))
 
     # north_star aliases
     embed = makeWatermark
@@ -649,121 +644,64 @@ class Watermark:
         return t if isinstance(t, wm_plane) else plane_of(t, channels)
 
     def embed_async(self, inputImage, outputImage, out, maskType, slot, a_out=None, status_out=None):
-        if isinstance(outputImage, wm_plane):
-            ch = outputImage.channels
-        else:
-            ch = 3 if outputImage.dim() - inputImage.dim() == 1 else 1
-        pin = self._as_plane(inputImage, 1)
-        pbase = self._as_plane(outputImage, ch)
-        pout = self._as_plane(out, ch)
-        rc = lib().wm_embed(self._ctx, int(maskType), C.byref(pin), C.byref(pbase), C.byref(pout), a_out, status_out, slot)
-        if rc < 0:
-            _raise(rc, self._ctx)
+        pin, pbase, pout = self._embed_planes(inputImage, outputImage, out)
+        self._chk(lib().wm_embed(self._ctx, int(maskType), C.byref(pin), C.byref(pbase), C.byref(pout), a_out, status_out, slot))
 
     def detect_async(self, image, maskType, slot, corr_out=None, status_out=None):
         pimg = self._as_plane(image, 1)
-        rc = lib().wm_detect(self._ctx, int(maskType), C.byref(pimg), corr_out, status_out, slot)
-        if rc < 0:
-            _raise(rc, self._ctx)
+        self._chk(lib().wm_detect(self._ctx, int(maskType), C.byref(pimg), corr_out, status_out, slot))
 
     def detect_keys_async(self, image, keys, maskType, slot, corr_out, status_out=None):
         """wm_detect_keys enqueued on `slot`: corr_out (frames * K floats: a ctypes array or a C-contiguous float32 numpy array)
         and status_out (frames ints, may be None) are written by sync(slot); `keys` must stay alive and unmodified until then"""
         pimg = self._as_plane(image, 1)
-        if isinstance(corr_out, np.ndarray):
-            assert corr_out.dtype == np.float32 and corr_out.flags.c_contiguous
-            corr_out = corr_out.ctypes.data_as(_P(C.c_float))
-        if isinstance(status_out, np.ndarray):
-            assert status_out.dtype == np.int32 and status_out.flags.c_contiguous
-            status_out = status_out.ctypes.data_as(_P(C.c_int))
-        rc = lib().wm_detect_keys(self._ctx, int(maskType), C.byref(pimg), keys.handle if isinstance(keys, KeySet) else keys,
-                                  corr_out, status_out, slot)
-        if rc < 0:
-            _raise(rc, self._ctx)
+        corr_out, status_out = self._scalars_out(corr_out, status_out)
+        self._chk(lib().wm_detect_keys(self._ctx, int(maskType), C.byref(pimg), _keys_handle(keys),
+                                       corr_out, status_out, slot))
 
     def detect_offsets_async(self, image, keys, k, oy0, ox0, ny, nx, maskType, slot, corr_out, status_out=None):
         """wm_detect_offsets enqueued on `slot`: corr_out (frames * ny * nx floats: a ctypes array or a C-contiguous float32 numpy
         array) and status_out (frames ints, may be None) are written by sync(slot); `keys` must stay alive and unmodified until
         then"""
         pimg = self._as_plane(image, 1)
-        if isinstance(corr_out, np.ndarray):
-            assert corr_out.dtype == np.float32 and corr_out.flags.c_contiguous
-            corr_out = corr_out.ctypes.data_as(_P(C.c_float))
-        if isinstance(status_out, np.ndarray):
-            assert status_out.dtype == np.int32 and status_out.flags.c_contiguous
-            status_out = status_out.ctypes.data_as(_P(C.c_int))
-        rc = lib().wm_detect_offsets(self._ctx, int(maskType), C.byref(pimg), keys.handle if isinstance(keys, KeySet) else keys,
-                                     k, oy0, ox0, ny, nx, corr_out, status_out, slot)
-        if rc < 0:
-            _raise(rc, self._ctx)
+        corr_out, status_out = self._scalars_out(corr_out, status_out)
+        self._chk(lib().wm_detect_offsets(self._ctx, int(maskType), C.byref(pimg), _keys_handle(keys),
+                                          k, oy0, ox0, ny, nx, corr_out, status_out, slot))
 
     def detect_tiles_async(self, image, tile_rows, tile_cols, maskType, slot, map_t, sums_t=None, status=None):
         """wm_detect_tiles enqueued on `slot`: map_t (a contiguous float32 GPU tensor of frames * ny * nx elements) and sums_t
         (float64, frames * ny * nx * 3, may be None) are written on the slot's stream and valid after sync(slot); status (frames
         ints: a ctypes array or a C-contiguous int32 numpy array, may be None) is written by sync(slot)"""
-        import torch
         pimg = self._as_plane(image, 1)
         ny, nx = self.tiles_shape(self.rows, self.cols, tile_rows, tile_cols)
         n = pimg.frames * ny * nx
-        if not (map_t.is_cuda and map_t.dtype == torch.float32 and map_t.is_contiguous() and map_t.numel() == n):
-            raise RuntimeError(f"map_t must be a contiguous float32 GPU tensor of {n} elements")
-        if sums_t is not None and not (sums_t.is_cuda and sums_t.dtype == torch.float64 and sums_t.is_contiguous() and sums_t.numel() == 3 * n):
-            raise RuntimeError(f"sums_t must be a contiguous float64 GPU tensor of {3 * n} elements")
-        if isinstance(status, np.ndarray):
-            assert status.dtype == np.int32 and status.flags.c_contiguous
-            status = status.ctypes.data_as(_P(C.c_int))
-        rc = lib().wm_detect_tiles(self._ctx, int(maskType), C.byref(pimg), tile_rows, tile_cols, C.c_void_p(map_t.data_ptr()),
-                                   C.c_void_p(sums_t.data_ptr()) if sums_t is not None else None, status, slot)
-        if rc < 0:
-            _raise(rc, self._ctx)
+        pmap, psums = self._tile_tensors(map_t, sums_t, n)
+        _, status = self._scalars_out(None, status)
+        self._chk(lib().wm_detect_tiles(self._ctx, int(maskType), C.byref(pimg), tile_rows, tile_cols, pmap, psums, status, slot))
 
     def detect_keys_tiles_async(self, image, keys, tile_rows, tile_cols, maskType, slot, map_t, sums_t=None, status=None):
         """wm_detect_keys_tiles enqueued on `slot`: map_t (a contiguous float32 GPU tensor of frames * K * ny * nx elements) and
         sums_t (float64, three times as many, may be None) are written on the slot's stream and valid after sync(slot); status
         (frames ints: a ctypes array or a C-contiguous int32 numpy array, may be None) is written by sync(slot); `keys` must stay
         alive and unmodified until then"""
-        import torch
         pimg = self._as_plane(image, 1)
         ny, nx = self.tiles_shape(self.rows, self.cols, tile_rows, tile_cols)
         K = keys.count if isinstance(keys, KeySet) else lib().wm_keys_count(keys)
         n = pimg.frames * K * ny * nx
-        if not (map_t.is_cuda and map_t.dtype == torch.float32 and map_t.is_contiguous() and map_t.numel() == n):
-            raise RuntimeError(f"map_t must be a contiguous float32 GPU tensor of {n} elements")
-        if sums_t is not None and not (sums_t.is_cuda and sums_t.dtype == torch.float64 and sums_t.is_contiguous() and sums_t.numel() == 3 * n):
-            raise RuntimeError(f"sums_t must be a contiguous float64 GPU tensor of {3 * n} elements")
-        if isinstance(status, np.ndarray):
-            assert status.dtype == np.int32 and status.flags.c_contiguous
-            status = status.ctypes.data_as(_P(C.c_int))
-        rc = lib().wm_detect_keys_tiles(self._ctx, int(maskType), C.byref(pimg), keys.handle if isinstance(keys, KeySet) else keys,
-                                        tile_rows, tile_cols, C.c_void_p(map_t.data_ptr()),
-                                        C.c_void_p(sums_t.data_ptr()) if sums_t is not None else None, status, slot)
-        if rc < 0:
-            _raise(rc, self._ctx)
+        pmap, psums = self._tile_tensors(map_t, sums_t, n)
+        _, status = self._scalars_out(None, status)
+        self._chk(lib().wm_detect_keys_tiles(self._ctx, int(maskType), C.byref(pimg), _keys_handle(keys),
+                                             tile_rows, tile_cols, pmap, psums, status, slot))
 
     def embed_keys_async(self, inputImage, outputImage, out, keys, maskType, slot, a_out=None, status_out=None):
         """wm_embed_keys enqueued on `slot`: `out` holds frames * K copies (a tensor [frames * K, ...] or a wm_plane; copy (f, k) is
         frame f * K + k); a_out (frames * K floats) and status_out (frames ints) -- ctypes arrays or C-contiguous numpy arrays, may
         be None -- are written by sync(slot); `keys` must stay alive and unmodified until then.  With a wm_plane inputImage,
         outputImage is a wm_plane as well (its channels cannot be told from a tensor's rank then)"""
-        if isinstance(outputImage, wm_plane):
-            ch = outputImage.channels
-        elif isinstance(inputImage, wm_plane):
-            raise RuntimeError("embed_keys_async: with a wm_plane inputImage, pass outputImage as a wm_plane too")
-        else:
-            ch = 3 if outputImage.dim() - inputImage.dim() == 1 else 1
-        pin = self._as_plane(inputImage, 1)
-        pbase = self._as_plane(outputImage, ch)
-        pout = self._as_plane(out, ch)
-        if isinstance(a_out, np.ndarray):
-            assert a_out.dtype == np.float32 and a_out.flags.c_contiguous
-            a_out = a_out.ctypes.data_as(_P(C.c_float))
-        if isinstance(status_out, np.ndarray):
-            assert status_out.dtype == np.int32 and status_out.flags.c_contiguous
-            status_out = status_out.ctypes.data_as(_P(C.c_int))
-        rc = lib().wm_embed_keys(self._ctx, int(maskType), C.byref(pin), C.byref(pbase), keys.handle if isinstance(keys, KeySet) else keys,
-                                 C.byref(pout), a_out, status_out, slot)
-        if rc < 0:
-            _raise(rc, self._ctx)
+        pin, pbase, pout = self._embed_planes(inputImage, outputImage, out)
+        a_out, status_out = self._scalars_out(a_out, status_out)
+        self._chk(lib().wm_embed_keys(self._ctx, int(maskType), C.byref(pin), C.byref(pbase), _keys_handle(keys),
+                                      C.byref(pout), a_out, status_out, slot))
 
     @staticmethod
     def _host_table(a, dtype, n, what):
@@ -781,6 +719,16 @@ class Watermark:
             assert status_out.dtype == np.int32 and status_out.flags.c_contiguous
             status_out = status_out.ctypes.data_as(_P(C.c_int))
         return a_out, status_out
+
+    @staticmethod
+    def _tile_tensors(map_t, sums_t, n):
+        """the device tensors of the tiles calls as pointers: map_t n float32, sums_t (may be None) 3 n float64, both contiguous"""
+        import torch
+        if not (map_t.is_cuda and map_t.dtype == torch.float32 and map_t.is_contiguous() and map_t.numel() == n):
+            raise RuntimeError(f"map_t must be a contiguous float32 GPU tensor of {n} elements")
+        if sums_t is not None and not (sums_t.is_cuda and sums_t.dtype == torch.float64 and sums_t.is_contiguous() and sums_t.numel() == 3 * n):
+            raise RuntimeError(f"sums_t must be a contiguous float64 GPU tensor of {3 * n} elements")
+        return C.c_void_p(map_t.data_ptr()), (C.c_void_p(sums_t.data_ptr()) if sums_t is not None else None)
 
     def _embed_planes(self, inputImage, outputImage, out):
         if isinstance(outputImage, wm_plane):
@@ -802,10 +750,8 @@ class Watermark:
             _raise(WM_ERR_BAD_ARG)
         sg = self._host_table(raw, np.int8, pin.frames * ny * nx, "signs")
         a_out, status_out = self._scalars_out(a_out, status_out)
-        rc = lib().wm_embed_signs(self._ctx, int(maskType), C.byref(pin), C.byref(pbase), C.byref(pout), tile_rows, tile_cols,
-                                  sg.ctypes.data_as(C.c_void_p), a_out, status_out, slot)
-        if rc < 0:
-            _raise(rc, self._ctx)
+        self._chk(lib().wm_embed_signs(self._ctx, int(maskType), C.byref(pin), C.byref(pbase), C.byref(pout), tile_rows, tile_cols,
+                                       sg.ctypes.data_as(C.c_void_p), a_out, status_out, slot))
 
     def embed_bits_async(self, inputImage, outputImage, out, tile_rows, tile_cols, tile_bit, nbits, payload, maskType, slot, a_out=None,
                          status_out=None):
@@ -818,10 +764,8 @@ class Watermark:
             payload = np.frombuffer(bytes(payload), np.uint8)
         pl = self._host_table(payload, np.uint8, pin.frames * ((max(nbits, 1) + 7) // 8), "payload")
         a_out, status_out = self._scalars_out(a_out, status_out)
-        rc = lib().wm_embed_bits(self._ctx, int(maskType), C.byref(pin), C.byref(pbase), C.byref(pout), tile_rows, tile_cols,
-                                 tb.ctypes.data_as(C.c_void_p), nbits, pl.ctypes.data_as(C.c_void_p), a_out, status_out, slot)
-        if rc < 0:
-            _raise(rc, self._ctx)
+        self._chk(lib().wm_embed_bits(self._ctx, int(maskType), C.byref(pin), C.byref(pbase), C.byref(pout), tile_rows, tile_cols,
+                                      tb.ctypes.data_as(C.c_void_p), nbits, pl.ctypes.data_as(C.c_void_p), a_out, status_out, slot))
 
     def detect_bits_async(self, image, tile_rows, tile_cols, tile_bit, nbits, maskType, slot, soft_out, status_out=None):
         """wm_detect_bits enqueued on `slot`: tile_bit (ny * nx int32) is read before the call returns; soft_out (frames * nbits
@@ -831,16 +775,11 @@ class Watermark:
         ny, nx = self.tiles_shape(self.rows, self.cols, tile_rows, tile_cols)
         tb = self._host_table(tile_bit, np.int32, ny * nx, "tile_bit")
         soft_out, status_out = self._scalars_out(soft_out, status_out)
-        rc = lib().wm_detect_bits(self._ctx, int(maskType), C.byref(pimg), tile_rows, tile_cols, tb.ctypes.data_as(C.c_void_p), nbits,
-                                  soft_out, status_out, slot)
-        if rc < 0:
-            _raise(rc, self._ctx)
+        self._chk(lib().wm_detect_bits(self._ctx, int(maskType), C.byref(pimg), tile_rows, tile_cols, tb.ctypes.data_as(C.c_void_p), nbits,
+                                       soft_out, status_out, slot))
 
     def sync(self, slot):
-        rc = lib().wm_sync(self._ctx, slot)
-        if rc < 0:
-            _raise(rc, self._ctx)
-        return rc
+        return self._chk(lib().wm_sync(self._ctx, slot))
 
     # -- parity-test building blocks (private in the reference: Watermark.cpp:96-114,176-218) -------------
     def computeMask(self, inputImage, maskType, want_error_sequence=False):
@@ -855,10 +794,8 @@ class Watermark:
         coef = (C.c_float * (8 * frames))()
         st = (C.c_int * frames)()
         torch.cuda.current_stream().synchronize()
-        rc = lib().wm_compute_mask(self._ctx, int(maskType), C.byref(pin), C.byref(pm), C.byref(pe) if pe else None, coef,
-                                   st, WM_SLOT_SYNC)
-        if rc < 0:
-            _raise(rc, self._ctx)
+        self._chk(lib().wm_compute_mask(self._ctx, int(maskType), C.byref(pin), C.byref(pm), C.byref(pe) if pe else None, coef,
+                                        st, WM_SLOT_SYNC))
         c = np.array(coef[:], dtype=np.float32).reshape(frames, 8)
         if inputImage.dim() == 2:
             return m, e, c[0], st[0]
@@ -866,14 +803,7 @@ class Watermark:
 
     def gram(self, image):
         """(Rx [8,8] f64, rx [8] f64) of a grey image: the sums the me kernel + af::sum produce"""
-        import torch
-        pimg = plane_of(image, 1)
-        buf = (C.c_double * (44 * pimg.frames))()
-        torch.cuda.current_stream().synchronize()
-        rc = lib().wm_gram(self._ctx, C.byref(pimg), buf, 0)
-        if rc < 0:
-            _raise(rc, self._ctx)
-        tot = np.array(buf[:44], dtype=np.float64)
+        tot = self.gram_totals(image)[:44]
         Rx = np.zeros((8, 8))
         k = 0
         for i in range(8):
@@ -889,22 +819,16 @@ class Watermark:
         pimg = plane_of(image, 1)
         buf = (C.c_double * (44 * pimg.frames))()
         torch.cuda.current_stream().synchronize()
-        rc = lib().wm_gram(self._ctx, C.byref(pimg), buf, 0)
-        if rc < 0:
-            _raise(rc, self._ctx)
+        self._chk(lib().wm_gram(self._ctx, C.byref(pimg), buf, 0))
         return np.array(buf[:], dtype=np.float64)
 
     def band_configure(self, own_lo, own_hi, rows_global):
-        rc = lib().wm_band_configure(self._ctx, int(own_lo), int(own_hi), int(rows_global))
-        if rc < 0:
-            _raise(rc, self._ctx)
+        self._chk(lib().wm_band_configure(self._ctx, int(own_lo), int(own_hi), int(rows_global)))
 
     def band_solve(self, totals):
         t = np.ascontiguousarray(totals, dtype=np.float64)
         st = (C.c_int * 1)()
-        rc = lib().wm_band_solve(self._ctx, t.ctypes.data_as(_P(C.c_double)), 1, st, 0)
-        if rc < 0:
-            _raise(rc, self._ctx)
+        self._chk(lib().wm_band_solve(self._ctx, t.ctypes.data_as(_P(C.c_double)), 1, st, 0))
         return st[0]
 
     def band_stats(self, image, maskType):
@@ -912,21 +836,16 @@ class Watermark:
         pimg = plane_of(image, 1)
         out = (C.c_double * 2)()
         torch.cuda.current_stream().synchronize()
-        rc = lib().wm_band_stats(self._ctx, int(maskType), C.byref(pimg), out, 0)
-        if rc < 0:
-            _raise(rc, self._ctx)
+        self._chk(lib().wm_band_stats(self._ctx, int(maskType), C.byref(pimg), out, 0))
         return out[0], out[1]
 
     def band_embed(self, image, base, out, maskType, max_e, ss):
         import torch
-        ch = 3 if base.dim() - image.dim() == 1 else 1
-        pin, pbase, pout = plane_of(image, 1), plane_of(base, ch), plane_of(out, ch)
+        pin, pbase, pout = self._embed_planes(image, base, out)
         ms = (C.c_double * 2)(max_e, ss)
         a = (C.c_float * 1)()
         torch.cuda.current_stream().synchronize()
-        rc = lib().wm_band_embed(self._ctx, int(maskType), C.byref(pin), C.byref(pbase), C.byref(pout), ms, a, 0)
-        if rc < 0:
-            _raise(rc, self._ctx)
+        self._chk(lib().wm_band_embed(self._ctx, int(maskType), C.byref(pin), C.byref(pbase), C.byref(pout), ms, a, 0))
         return a[0]
 
     def band_detect_sums(self, image, maskType):
@@ -934,9 +853,7 @@ class Watermark:
         pimg = plane_of(image, 1)
         out = (C.c_double * 3)()
         torch.cuda.current_stream().synchronize()
-        rc = lib().wm_band_detect_sums(self._ctx, int(maskType), C.byref(pimg), out, 0)
-        if rc < 0:
-            _raise(rc, self._ctx)
+        self._chk(lib().wm_band_detect_sums(self._ctx, int(maskType), C.byref(pimg), out, 0))
         return out[0], out[1], out[2]
 
     # -- the same with the exchange resident in device memory (wm.h wm_band_*_dev): device tensors in, nothing synchronises.
@@ -946,13 +863,7 @@ class Watermark:
         # torch's default stream has the handle 0, which wm_set_stream reads as "back to the slot's own stream": name the legacy
         # default stream by HIP's handle for it (hipStreamLegacy = 1)
         h = torch.cuda.current_stream().cuda_stream
-        rc = lib().wm_set_stream(self._ctx, slot, C.c_void_p(h if h else 1))
-        if rc < 0:
-            _raise(rc, self._ctx)
-
-    def _chk(self, rc):
-        if rc < 0:
-            _raise(rc, self._ctx)
+        self._chk(lib().wm_set_stream(self._ctx, slot, C.c_void_p(h if h else 1)))
 
     def band_gram_dev(self, image, totals):
         """totals: float64 CUDA tensor [44] (one frame): receives this band's Gram sums"""
@@ -967,10 +878,9 @@ class Watermark:
         self._chk(lib().wm_band_stats_dev(self._ctx, int(maskType), C.byref(pimg), C.c_void_p(max_sum.data_ptr()), 0))
 
     def band_embed_dev(self, image, base, out, maskType, gathered, nparts, a_dev):
-        ch = 3 if base.dim() - image.dim() == 1 else 1
-        pin, pbase, pout = plane_of(image, 1), plane_of(base, ch), plane_of(out, ch)
+        pin, pbase, pout = self._embed_planes(image, base, out)
         self._chk(lib().wm_band_embed_dev(self._ctx, int(maskType), C.byref(pin), C.byref(pbase), C.byref(pout), C.c_void_p(gathered.data_ptr()), nparts,
-                                           C.c_void_p(a_dev.data_ptr()), 0))
+                                                C.c_void_p(a_dev.data_ptr()), 0))
 
     def band_detect_sums_dev(self, image, maskType, sums):
         pimg = plane_of(image, 1)

@@ -753,19 +753,6 @@ int stage_out(wm_ctx* ctx, Slot& s, const wm_plane* pl, const void* src, const S
     return WM_OK;
 }
 
-// device -> device snapshot of a RESOLVED grey plane (a device plane, or the slot's last output behind WM_MEM_SLOT_OUT) into
-// the dense staging layout `st` (staged_layout of the caller's plane: same rows, cols, frames, dtype)
-int snapshot(wm_ctx* ctx, Slot& s, const PlaneDesc& src_d, const wm_plane* shape, void* dst, const Staged& st)
-{
-    const size_t es = elem_size(shape->dtype);
-    for (int f = 0; f < shape->frames; ++f) {
-        const char* src = (const char*)src_d.p + (size_t)f * src_d.fstride * es;
-        char* d = (char*)dst + (size_t)f * st.d.fstride * es;
-        HIPCHK(ctx, hipMemcpy2DAsync(d, st.pitch * es, src, src_d.pitch * es, shape->cols * es, shape->rows, hipMemcpyDeviceToDevice, s.stream));
-    }
-    return WM_OK;
-}
-
 // bytes from the first pixel of a plane to the end of its last one (all channels and frames)
 size_t plane_extent(const PlaneDesc& d, int rows, int cols, int frames)
 {
@@ -849,6 +836,20 @@ int check_mask(wm_ctx* ctx, int mask)
     if (mask != WM_MASK_ME && mask != WM_MASK_NVF) return fail(ctx, WM_ERR_BAD_ARG, "bad mask type");
     if (mask == WM_MASK_ME && ctx->p != 3) return fail(ctx, WM_ERR_BAD_P, "ME mask needs p == 3 (main.cpp:89)");
     return WM_OK;
+}
+
+// the calls that sweep whole images only (a band's totals are exchanged by the wm_band_* phases)
+int refuse_band(wm_ctx* ctx, const char* who)
+{
+    return ctx->band_hi > 0 ? fail(ctx, WM_ERR_BAD_ARG, std::string(who) + ": not in band mode") : WM_OK;
+}
+
+// what the embed-side launchers take for a mask type: the kernels' mask index, the window's pad (ME: p == 3, check_mask), and the Gram
+// sweep's solve (coefficients and status per frame), which only ME has; the detectors solve under either mask and always pass the slot's
+struct MaskRoute { int mask, pad; const float* coef; const int* status; };
+MaskRoute mask_route(const wm_ctx* ctx, const Slot& s, int mask)
+{
+    return mask == WM_MASK_ME ? MaskRoute{0, 1, s.d_coef, s.d_status} : MaskRoute{1, ctx->p / 2, nullptr, nullptr};
 }
 
 // may the sweeps address the context's W (or a key plane of its shape) as a buffer with 32-bit offsets?  (W is a dense f32
@@ -944,6 +945,15 @@ int do_sync(wm_ctx* ctx, Slot& s)
 {
     HIPCHK(ctx, hipStreamSynchronize(s.stream));
     return deliver(s);
+}
+
+// the back half of a call behind its launches: their check, the records queued for delivery, and the wait of a synchronous call
+int finish_call(wm_ctx* ctx, Slot& s, int slot, int frames, int per_frame, bool keep, float* value_out, int* status_out, float* coef_out = nullptr)
+{
+    const int rc = launch_check(ctx, s);
+    if (rc != WM_OK) return rc;
+    push_pending(s, frames, per_frame, keep, value_out, status_out, coef_out);
+    return slot == WM_SLOT_SYNC ? do_sync(ctx, s) : WM_OK;
 }
 
 }  // namespace
@@ -1206,15 +1216,84 @@ static int prep_base(wm_ctx* ctx, Slot& s, const wm_plane* in_gray, const wm_pla
     return WM_OK;
 }
 
-// the output plane of an embed: a host plane is written to the slot's staging buffer (layout in *st, copied out by stage_out)
-static int prep_out(wm_ctx* ctx, Slot& s, const wm_plane* out, PlaneDesc* od, Staged* st)
+// ---- the embed frame: what the embed calls share around their sweeps.  wm_embed and wm_embed_signs take all of it;
+// wm_embed_keys, with K outputs per input frame, takes the dtype rules and stages its planes itself
+// (xd, bd, od: the RESOLVED planes, what the kernels address; st_out: the staging layout of a host output, copied out by stage_out)
+struct EmbedCall { int frames; PlaneDesc xd, bd, od; Staged st_out; bool inplace; };
+static int check_embed_dtypes(wm_ctx* ctx, const wm_plane* in_gray, const wm_plane* base, const wm_plane* out)
 {
-    if (out->mem != WM_MEM_HOST) { *od = desc_device(out); return WM_OK; }
-    *st = staged_layout(out);
-    const int rc = ensure(ctx, &s.st_out, &s.st_out_bytes, st->bytes);
-    if (rc != WM_OK) return rc;
-    *od = st->d; od->p = s.st_out;
+    if (out->channels != base->channels || out->dtype != base->dtype) return fail(ctx, WM_ERR_BAD_ARG, "out must have the shape and dtype of base");
+    if (in_gray->dtype != base->dtype) return fail(ctx, WM_ERR_BAD_ARG, "in_gray and base must have the same dtype (the reference converts whole frames, main.cpp:355-357)");
     return WM_OK;
+}
+static int check_embed_planes(wm_ctx* ctx, const wm_plane* in_gray, const wm_plane* base, const wm_plane* out)
+{
+    int rc;
+    if ((rc = check_plane(ctx, in_gray, 0, false, "in_gray", true)) != WM_OK) return rc;
+    if ((rc = check_plane(ctx, base, in_gray->frames, true, "base")) != WM_OK) return rc;
+    if ((rc = check_plane(ctx, out, in_gray->frames, true, "out")) != WM_OK) return rc;
+    return check_embed_dtypes(ctx, in_gray, base, out);
+}
+
+// the three planes staged / resolved, the in-place judgement, and the end of every hand-over whose plane this call's output replaces
+static int embed_stage(wm_ctx* ctx, Slot& s, const wm_plane* in_gray, const wm_plane* base, const wm_plane* out, EmbedCall* c)
+{
+    int rc;
+    c->frames = in_gray->frames;
+    if ((rc = prep_input(ctx, s, in_gray, &c->xd)) != WM_OK) return rc;
+    if ((rc = prep_base(ctx, s, in_gray, base, c->xd, &c->bd)) != WM_OK) return rc;
+    if (out->mem != WM_MEM_HOST) c->od = desc_device(out);
+    else {  // (a host plane is written to the slot's staging buffer)
+        c->st_out = staged_layout(out);
+        if ((rc = ensure(ctx, &s.st_out, &s.st_out_bytes, c->st_out.bytes)) != WM_OK) return rc;
+        c->od = c->st_out.d; c->od.p = s.st_out;
+    }
+    // in place = the output overlaps the plane the stencil reads, judged on the RESOLVED addresses (a WM_MEM_SLOT_OUT input is
+    // the slot's last output buffer, which the caller may well pass as `out` again)
+    c->inplace = descs_overlap(c->xd, c->od, ctx->rows, ctx->cols, c->frames);
+    s.ho.valid = false;  // (whatever this call writes replaces the plane a hand-over described)
+    invalidate_handovers(ctx, c->od, c->frames);  // (... and that of any other slot whose last output this call overwrites)
+    return WM_OK;
+}
+
+// in-place embed on the sweeps (the video path hands the same frame as input, base and output, main.cpp:356,380):
+// the stencil must keep reading the ORIGINAL pixels while rows of `out` are being written, so the mask
+// source is snapshotted into the slot's staging buffer first: one extra device copy of the RESOLVED grey plane (a device plane,
+// or the slot's last output behind WM_MEM_SLOT_OUT) into the dense staging layout of the caller's plane
+static int embed_snapshot(wm_ctx* ctx, Slot& s, const wm_plane* in_gray, EmbedCall* c)
+{
+    if (!c->inplace) return WM_OK;
+    const Staged st = staged_layout(in_gray);
+    const int rc = ensure(ctx, &s.st_in, &s.st_in_bytes, st.bytes);
+    if (rc != WM_OK) return rc;
+    const size_t es = elem_size(in_gray->dtype);
+    for (int f = 0; f < c->frames; ++f) {
+        const char* src = (const char*)c->xd.p + (size_t)f * c->xd.fstride * es;
+        char* d = (char*)s.st_in + (size_t)f * st.d.fstride * es;
+        HIPCHK(ctx, hipMemcpy2DAsync(d, st.pitch * es, src, c->xd.pitch * es, in_gray->cols * es, in_gray->rows, hipMemcpyDeviceToDevice, s.stream));
+    }
+    // the base IS the input plane (video frames: input, base and output are one plane): read it from the snapshot too --
+    // k_embed then takes the base from its stencil window (no base stream) and nothing reads the plane being overwritten
+    const bool base_is_input = c->bd.p == c->xd.p && c->bd.pitch == c->xd.pitch && c->bd.fstride == c->xd.fstride && c->bd.dtype == c->xd.dtype && c->bd.channels == 1;
+    c->xd = st.d; c->xd.p = s.st_in;
+    if (base_is_input) c->bd = c->xd;
+    return WM_OK;
+}
+
+// the call's result: `out` becomes the slot's last output, the strengths are queued (an unsolvable frame keeps the caller's)
+static void embed_queue_result(Slot& s, const wm_plane* out, const EmbedCall& c, float* a_out, int* status_out)
+{
+    s.last_out = c.od; s.last_out_frames = c.frames; s.last_out_dtype = out->dtype;
+    push_pending(s, c.frames, 1, true, a_out, status_out, nullptr);
+}
+// behind the sweeps' launches: their check, a host output copied out, the result queued, a synchronous call's wait (wm_embed_detect: the detector's covers it)
+static int embed_close(wm_ctx* ctx, Slot& s, const wm_plane* out, const EmbedCall& c, float* a_out, int* status_out, int slot)
+{
+    int rc;
+    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
+    if (out->mem == WM_MEM_HOST && (rc = stage_out(ctx, s, out, s.st_out, c.st_out)) != WM_OK) return rc;
+    embed_queue_result(s, out, c, a_out, status_out);
+    return slot == WM_SLOT_SYNC && !ctx->pair_mode ? do_sync(ctx, s) : WM_OK;
 }
 
 // a fused embed issued output stores over the call's own input or base and their completion was not observed
@@ -1233,30 +1312,14 @@ int wm_embed(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* bas
     if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
     Slot& s = slot_of(ctx, slot);
     const bool sync_after = slot == WM_SLOT_SYNC;
-    if ((rc = check_plane(ctx, in_gray, 0, false, "in_gray", true)) != WM_OK) return rc;
+    if ((rc = check_embed_planes(ctx, in_gray, base, out)) != WM_OK) return rc;
     const int frames = in_gray->frames;
-    if ((rc = check_plane(ctx, base, frames, true, "base")) != WM_OK) return rc;
-    if ((rc = check_plane(ctx, out, frames, true, "out")) != WM_OK) return rc;
-    if (out->channels != base->channels || out->dtype != base->dtype) return fail(ctx, WM_ERR_BAD_ARG, "out must have the shape and dtype of base");
-    if (in_gray->dtype != base->dtype) return fail(ctx, WM_ERR_BAD_ARG, "in_gray and base must have the same dtype (the reference converts whole frames, main.cpp:355-357)");
     if ((rc = check_res_room(ctx, s, frames)) != WM_OK) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-
-    PlaneDesc xd, bd, od;
-    Staged st_out_l;
-    if ((rc = prep_input(ctx, s, in_gray, &xd)) != WM_OK) return rc;
-    if ((rc = prep_base(ctx, s, in_gray, base, xd, &bd)) != WM_OK) return rc;
-    if ((rc = prep_out(ctx, s, out, &od, &st_out_l)) != WM_OK) return rc;
-    // in place = the output overlaps the plane the stencil reads, judged on the RESOLVED addresses (a WM_MEM_SLOT_OUT input is
-    // the slot's last output buffer, which the caller may well pass as `out` again)
-    const bool inplace = descs_overlap(xd, od, ctx->rows, ctx->cols, frames);
-    s.ho.valid = false;  // (whatever this call writes replaces the plane a hand-over described)
-    invalidate_handovers(ctx, od, frames);  // (... and that of any other slot whose last output this call overwrites)
-    // the call's result: `out` becomes the slot's last output, the strengths are queued (an unsolvable frame keeps the caller's)
-    auto queue_result = [&]() {
-        s.last_out = od; s.last_out_frames = frames; s.last_out_dtype = out->dtype;
-        push_pending(s, frames, 1, true, a_out, status_out, nullptr);
-    };
+    EmbedCall c;
+    if ((rc = embed_stage(ctx, s, in_gray, base, out, &c)) != WM_OK) return rc;
+    PlaneDesc &xd = c.xd, &bd = c.bd, &od = c.od;
+    const bool inplace = c.inplace;
 
     // one image per synchronous call (the reference's call pattern): ONE launch with the frame's tiles resident in LDS
     // (wm_k_fused.hip).  Its y stores come after two chip-wide hand-offs behind every read of x, so an in-place call
@@ -1282,12 +1345,12 @@ int wm_embed(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* bas
         else { ProfScope ps(ctx, K_FUSED_EMBED, s.stream); lrc = launch_fused_embed(s.stream, ctx->fg, s.fz, s.fz_epoch, mask, xd, ctx->w->d_w, bd, od, ctx->sF, sqrt_n(ctx), s.d_res + s.res_used); }
         if (lrc == 0) {
             if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
-            if (out->mem == WM_MEM_HOST && (rc = stage_out(ctx, s, out, s.st_out, st_out_l)) != WM_OK) return rc;
+            if (out->mem == WM_MEM_HOST && (rc = stage_out(ctx, s, out, s.st_out, c.st_out)) != WM_OK) return rc;
             if (ctx->pair_mode) {
                 // the detector's launch follows at once on the same stream; its record completes both (wm_detect's fused branch)
                 s.pair.armed = true; s.pair.res_index = s.res_used; s.pair.host_out = out->mem == WM_MEM_HOST;
                 s.pair.out_overlaps_inputs = inplace || descs_overlap(bd, od, ctx->rows, ctx->cols, frames);
-                queue_result();
+                embed_queue_result(s, out, c, a_out, status_out);
                 return WM_OK;
             }
             // device output: the kernel writes y through to memory and reports last, so the record is the completion
@@ -1296,7 +1359,7 @@ int wm_embed(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* bas
             if ((rc = fused_wait(ctx, s, hres, out->mem == WM_MEM_HOST, &got)) != WM_OK) return rc;
             if (got.status != FUSED_PENDING && got.status != FUSED_INCOMPLETE) {
                 ctx->fused_backoff = 0;
-                queue_result();
+                embed_queue_result(s, out, c, a_out, status_out);
                 return deliver(s);  // the record has arrived
             }
             // PENDING: a hand-off timed out before any output store (the workgroups were not all resident): nothing was
@@ -1311,24 +1374,11 @@ int wm_embed(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* bas
         }
     }
     guard.reset();  // (the sweeps below do not need the device to themselves)
-    if (inplace) {
-        // in-place embed (the video path hands the same frame as input, base and output, main.cpp:356,380):
-        // the stencil must keep reading the ORIGINAL pixels while rows of `out` are being written, so the mask
-        // source is snapshotted into the slot's staging buffer first (one extra device copy of the grey plane)
-        Staged st = staged_layout(in_gray);
-        if ((rc = ensure(ctx, &s.st_in, &s.st_in_bytes, st.bytes)) != WM_OK) return rc;
-        if ((rc = snapshot(ctx, s, xd, in_gray, s.st_in, st)) != WM_OK) return rc;
-        // the base IS the input plane (video frames: input, base and output are one plane): read it from the snapshot too --
-        // k_embed then takes the base from its stencil window (no base stream) and nothing reads the plane being overwritten
-        const bool base_is_input = bd.p == xd.p && bd.pitch == xd.pitch && bd.fstride == xd.fstride && bd.dtype == xd.dtype && bd.channels == 1;
-        xd = st.d; xd.p = s.st_in;
-        if (base_is_input) bd = xd;
-    }
+    if ((rc = embed_snapshot(ctx, s, in_gray, &c)) != WM_OK) return rc;
 
     LaunchGeom lg;
     if ((rc = geom_checked(ctx, frames, mask, &lg)) != WM_OK) return rc;
-    const float* W = ctx->w->d_w;
-    const int aligned_w = aligned_w_of(ctx);
+    const MaskRoute mr = mask_route(ctx, s, mask);
     OpResult* res = s.d_res + s.res_used;
     // Gram hand-over (wm_set_handover): k_embed also leaves the tile-internal lag sums of y for a detector that reads this
     // output as WM_MEM_SLOT_OUT (grey f32 planes on the aligned path; launch_embed says whether it applied)
@@ -1346,14 +1396,10 @@ int wm_embed(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* bas
     sweep_stats(ctx, s, true, lg, frames, mask, xd, res);
     {
         ProfScope ps(ctx, K_EMBED, s.stream);
-        if (mask == WM_MASK_ME) handed = launch_embed(s.stream, lg, frames, 0, 1, xd, W, aligned_w, bd, od, s.d_coef, s.d_status, s.d_scal, hop);
-        else handed = launch_embed(s.stream, lg, frames, 1, ctx->p / 2, xd, W, aligned_w, bd, od, nullptr, nullptr, s.d_scal, hop);
+        handed = launch_embed(s.stream, lg, frames, mr.mask, mr.pad, xd, ctx->w->d_w, aligned_w_of(ctx), bd, od, mr.coef, mr.status, s.d_scal, hop);
     }
     if (handed) { s.ho.valid = true; s.ho.promised = promised; s.ho.used = false; s.ho.lg = lg; s.ho.frames = frames; s.ho.stride = ho.stride; }
-    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
-    if (out->mem == WM_MEM_HOST && (rc = stage_out(ctx, s, out, s.st_out, st_out_l)) != WM_OK) return rc;
-    queue_result();
-    return sync_after && !ctx->pair_mode ? do_sync(ctx, s) : WM_OK;  // (wm_embed_detect: the detector's wait covers the embed)
+    return embed_close(ctx, s, out, c, a_out, status_out, slot);
 }
 
 // k_gram_ho over the sums the slot's last embed left (the border blocks are this short launch's longest: as many of them as the
@@ -1492,9 +1538,7 @@ int wm_detect(wm_ctx* ctx, int mask, const wm_plane* img, float* corr_out, int* 
         if ((rc = gram_sweep(ctx, s, lg, frames, xd, img)) != WM_OK) return rc;
         sweep_detect(ctx, s, K_DETECT, lg, frames, mask, xd, res);
     }
-    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
-    push_pending(s, frames, 1, false, corr_out, status_out, nullptr);
-    return sync_after ? do_sync(ctx, s) : WM_OK;
+    return finish_call(ctx, s, slot, frames, 1, false, corr_out, status_out);
 }
 
 int wm_embed_detect(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* base, const wm_plane* out, float* a_out,
@@ -1650,9 +1694,7 @@ static int detect_bank(wm_ctx* ctx, int mask, const wm_plane* img, long long cou
         if (launch(s, lg, frames, xd, (double*)s.keys_part, rstride, s.d_res + s.res_used) != 0)
             return fail(ctx, WM_ERR_RUNTIME, std::string(who) + ": geometry exceeds the record arrays");
     }
-    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
-    push_pending(s, frames, (int)count, false, corr_out, status_out, nullptr);
-    return slot == WM_SLOT_SYNC ? do_sync(ctx, s) : WM_OK;
+    return finish_call(ctx, s, slot, frames, (int)count, false, corr_out, status_out);
 }
 }  // extern "C++"
 
@@ -1663,7 +1705,7 @@ int wm_detect_keys(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* ke
     if (rc != WM_OK) return rc;
     if (!keys || !corr_out) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_keys: null keys or corr_out");
     if ((rc = check_bank(ctx, keys, "wm_detect_keys", true)) != WM_OK) return rc;
-    if (ctx->band_hi > 0) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_keys: not in band mode");
+    if ((rc = refuse_band(ctx, "wm_detect_keys")) != WM_OK) return rc;
     return detect_bank(ctx, mask, img, keys->nkeys, "keys", "wm_detect_keys", K_DETECT_KEYS, corr_out, status_out, slot,
                        [&](Slot& s, const LaunchGeom& lg, int frames, const PlaneDesc& xd, double* part, int rstride, OpResult* res) {
                            return launch_detect_keys(s.stream, lg, frames, mask, ctx->p / 2, xd, keys->d, (long long)ctx->rows * ctx->cols, keys->nkeys,
@@ -1696,7 +1738,7 @@ int wm_detect_offsets(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys*
         return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_offsets: offsets (" + std::to_string(oy0) + "," + std::to_string(ox0) + ") + " + std::to_string(ny) + "x" +
                                              std::to_string(nx) + " of " + std::to_string(ctx->rows) + "x" + std::to_string(ctx->cols) +
                                              " windows leave the " + std::to_string(keys->rows) + "x" + std::to_string(keys->cols) + " key plane");
-    if (ctx->band_hi > 0) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_offsets: not in band mode");
+    if ((rc = refuse_band(ctx, "wm_detect_offsets")) != WM_OK) return rc;
     // NOT aligned_w_of: the buffer descriptor of a window spans rows of the KEY plane's pitch, so that plane's extent decides the
     // 32-bit offsets
     const int aligned_key = fits_32bit(keys->rows, keys->cols, WM_F32) ? 1 : 0;
@@ -1719,6 +1761,22 @@ int wm_tiles_shape(int rows, int cols, int tile_rows, int tile_cols, int* ny, in
     return WM_OK;
 }
 
+// ---- the tile calls' front: the tile grid of the engine's plane, and a payload's table over it
+static int tiles_checked(wm_ctx* ctx, const char* who, int tile_rows, int tile_cols, int* ny, int* nx)
+{
+    if (wm_tiles_shape(ctx->rows, ctx->cols, tile_rows, tile_cols, ny, nx) == WM_OK) return WM_OK;
+    return fail(ctx, WM_ERR_BAD_ARG, std::string(who) + ": tile shape " + std::to_string(tile_rows) + "x" + std::to_string(tile_cols) +
+                                         " (rows: a multiple of 8, >= 32; columns: a multiple of 4, >= 32)");
+}
+
+// nbits and tile_bit [T] of wm_embed_bits / wm_detect_bits: every entry in -1 .. nbits - 1
+static int tile_bits_checked(wm_ctx* ctx, const char* who, const int32_t* tile_bit, long long T, int nbits)
+{
+    bool ok = nbits >= 1 && nbits <= 4096;
+    for (long long t = 0; ok && t < T; ++t) ok = tile_bit[t] >= -1 && tile_bit[t] < nbits;
+    return ok ? WM_OK : fail(ctx, WM_ERR_BAD_ARG, std::string(who) + ": nbits must be 1 .. 4096 and every tile_bit entry -1 .. nbits - 1");
+}
+
 // detectWatermark of every frame against the context's W with the three sums kept per tile: wm_detect's input and slot
 // handling on the sweeps, k_detect_tiles + k_tiles_fold in k_detect's place; the map stays on the device
 int wm_detect_tiles(wm_ctx* ctx, int mask, const wm_plane* img, int tile_rows, int tile_cols, float* map_dev, double* sums_dev,
@@ -1726,13 +1784,10 @@ int wm_detect_tiles(wm_ctx* ctx, int mask, const wm_plane* img, int tile_rows, i
 {
     if (!ctx) return WM_ERR_BAD_ARG;
     if (!img || !map_dev) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_tiles: null img or map_dev");
-    int ny = 0, nx = 0;
-    if (wm_tiles_shape(ctx->rows, ctx->cols, tile_rows, tile_cols, &ny, &nx) != WM_OK)
-        return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_tiles: tile shape " + std::to_string(tile_rows) + "x" + std::to_string(tile_cols) +
-                                             " (rows: a multiple of 8, >= 32; columns: a multiple of 4, >= 32)");
-    int rc = check_mask(ctx, mask);
-    if (rc != WM_OK) return rc;
-    if (ctx->band_hi > 0) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_tiles: not in band mode");
+    int ny = 0, nx = 0, rc;
+    if ((rc = tiles_checked(ctx, "wm_detect_tiles", tile_rows, tile_cols, &ny, &nx)) != WM_OK) return rc;
+    if ((rc = check_mask(ctx, mask)) != WM_OK) return rc;
+    if ((rc = refuse_band(ctx, "wm_detect_tiles")) != WM_OK) return rc;
     if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
     Slot& s = slot_of(ctx, slot);
     PlaneDesc xd;
@@ -1746,9 +1801,7 @@ int wm_detect_tiles(wm_ctx* ctx, int mask, const wm_plane* img, int tile_rows, i
     if ((rc = gram_sweep(ctx, s, lg, frames, xd, img)) != WM_OK) return rc;
     { ProfScope ps(ctx, K_DETECT_TILES, s.stream); launch_detect_tiles(s.stream, pl, frames, mask, ctx->p / 2, xd, ctx->w->d_w, s.d_coef, s.d_status, (float*)s.tiles_rec); }
     { ProfScope ps(ctx, K_TILES_FOLD, s.stream); launch_tiles_fold(s.stream, pl, frames, (const float*)s.tiles_rec, s.d_status, map_dev, sums_dev, res); }
-    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
-    push_pending(s, frames, 1, false, nullptr, status_out, nullptr);
-    return slot == WM_SLOT_SYNC ? do_sync(ctx, s) : WM_OK;
+    return finish_call(ctx, s, slot, frames, 1, false, nullptr, status_out);
 }
 
 // wm_detect_tiles with every key of the bank in the place of the context's W: wm_detect_keys' image side (one Gram sweep or
@@ -1759,14 +1812,11 @@ int wm_detect_keys_tiles(wm_ctx* ctx, int mask, const wm_plane* img, const wm_ke
 {
     if (!ctx) return WM_ERR_BAD_ARG;
     if (!img || !keys || !map_dev) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_keys_tiles: null img, keys or map_dev");
-    int ny = 0, nx = 0;
-    if (wm_tiles_shape(ctx->rows, ctx->cols, tile_rows, tile_cols, &ny, &nx) != WM_OK)
-        return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_keys_tiles: tile shape " + std::to_string(tile_rows) + "x" + std::to_string(tile_cols) +
-                                             " (rows: a multiple of 8, >= 32; columns: a multiple of 4, >= 32)");
-    int rc = check_mask(ctx, mask);
-    if (rc != WM_OK) return rc;
+    int ny = 0, nx = 0, rc;
+    if ((rc = tiles_checked(ctx, "wm_detect_keys_tiles", tile_rows, tile_cols, &ny, &nx)) != WM_OK) return rc;
+    if ((rc = check_mask(ctx, mask)) != WM_OK) return rc;
     if ((rc = check_bank(ctx, keys, "wm_detect_keys_tiles", true)) != WM_OK) return rc;
-    if (ctx->band_hi > 0) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_keys_tiles: not in band mode");
+    if ((rc = refuse_band(ctx, "wm_detect_keys_tiles")) != WM_OK) return rc;
     if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
     Slot& s = slot_of(ctx, slot);
     // (open_input checks the plane again: img->frames has to be known to be sane HERE, for the grid check in front of any device work)
@@ -1786,9 +1836,7 @@ int wm_detect_keys_tiles(wm_ctx* ctx, int mask, const wm_plane* img, const wm_ke
     launch_detect_keys_tiles(s.stream, pl, frames, mask, ctx->p / 2, xd, keys->d, (long long)ctx->rows * ctx->cols, nkeys, s.d_coef, s.d_status,
                              (float*)s.keys_tiles_rec);
     launch_keys_tiles_fold(s.stream, pl, frames, nkeys, (const float*)s.keys_tiles_rec, s.d_status, map_dev, sums_dev, res);
-    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
-    push_pending(s, frames, 1, false, nullptr, status_out, nullptr);
-    return slot == WM_SLOT_SYNC ? do_sync(ctx, s) : WM_OK;
+    return finish_call(ctx, s, slot, frames, 1, false, nullptr, status_out);
 }
 
 // ---- a payload in the mark: wm_bits_layout, wm_embed_signs, wm_embed_bits, wm_detect_bits --------------------------------------
@@ -1822,21 +1870,14 @@ int wm_embed_signs(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plan
 {
     if (!ctx) return WM_ERR_BAD_ARG;
     if (!in_gray || !base || !out || !signs) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_signs: null in_gray, base, out or signs");
-    int ny = 0, nx = 0;
-    if (wm_tiles_shape(ctx->rows, ctx->cols, tile_rows, tile_cols, &ny, &nx) != WM_OK)
-        return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_signs: tile shape " + std::to_string(tile_rows) + "x" + std::to_string(tile_cols) +
-                                             " (rows: a multiple of 8, >= 32; columns: a multiple of 4, >= 32)");
-    int rc = check_mask(ctx, mask);
-    if (rc != WM_OK) return rc;
-    if (ctx->band_hi > 0) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_signs: not in band mode");
+    int ny = 0, nx = 0, rc;
+    if ((rc = tiles_checked(ctx, "wm_embed_signs", tile_rows, tile_cols, &ny, &nx)) != WM_OK) return rc;
+    if ((rc = check_mask(ctx, mask)) != WM_OK) return rc;
+    if ((rc = refuse_band(ctx, "wm_embed_signs")) != WM_OK) return rc;
     if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
     Slot& s = slot_of(ctx, slot);
-    if ((rc = check_plane(ctx, in_gray, 0, false, "in_gray", true)) != WM_OK) return rc;
+    if ((rc = check_embed_planes(ctx, in_gray, base, out)) != WM_OK) return rc;
     const int frames = in_gray->frames;
-    if ((rc = check_plane(ctx, base, frames, true, "base")) != WM_OK) return rc;
-    if ((rc = check_plane(ctx, out, frames, true, "out")) != WM_OK) return rc;
-    if (out->channels != base->channels || out->dtype != base->dtype) return fail(ctx, WM_ERR_BAD_ARG, "out must have the shape and dtype of base");
-    if (in_gray->dtype != base->dtype) return fail(ctx, WM_ERR_BAD_ARG, "in_gray and base must have the same dtype (the reference converts whole frames, main.cpp:355-357)");
     const size_t nsigns = (size_t)frames * ny * nx;
     for (size_t i = 0; i < nsigns; ++i)
         if (signs[i] < -1 || signs[i] > 1)
@@ -1844,51 +1885,23 @@ int wm_embed_signs(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plan
     if ((rc = check_res_room(ctx, s, frames)) != WM_OK) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
 
-    // the call's own copy of the table: the caller's array is free when this function returns
+    // the call's own copy of the table: the caller's array is free when this function returns (uploaded in front of the planes' staging copies)
     void *th = nullptr, *td = nullptr;
     if ((rc = table_room(ctx, s, nsigns, &th, &td)) != WM_OK) return rc;
     std::memcpy(th, signs, nsigns);
     if ((rc = table_upload(ctx, s, th, td, nsigns)) != WM_OK) return rc;
 
-    PlaneDesc xd, bd, od;
-    Staged st_out_l;
-    if ((rc = prep_input(ctx, s, in_gray, &xd)) != WM_OK) return rc;
-    if ((rc = prep_base(ctx, s, in_gray, base, xd, &bd)) != WM_OK) return rc;
-    if ((rc = prep_out(ctx, s, out, &od, &st_out_l)) != WM_OK) return rc;
-    const bool inplace = descs_overlap(xd, od, ctx->rows, ctx->cols, frames);
-    s.ho.valid = false;  // (no hand-over of its own; whatever this call writes replaces the plane one described)
-    invalidate_handovers(ctx, od, frames);
-    if (inplace) {
-        // wm_embed's snapshot of the mask source (and of a base that is the input plane)
-        Staged st = staged_layout(in_gray);
-        if ((rc = ensure(ctx, &s.st_in, &s.st_in_bytes, st.bytes)) != WM_OK) return rc;
-        if ((rc = snapshot(ctx, s, xd, in_gray, s.st_in, st)) != WM_OK) return rc;
-        const bool base_is_input = bd.p == xd.p && bd.pitch == xd.pitch && bd.fstride == xd.fstride && bd.dtype == xd.dtype && bd.channels == 1;
-        xd = st.d; xd.p = s.st_in;
-        if (base_is_input) bd = xd;
-    }
+    EmbedCall c;  // (no hand-over of its own)
+    if ((rc = embed_stage(ctx, s, in_gray, base, out, &c)) != WM_OK) return rc;
+    if ((rc = embed_snapshot(ctx, s, in_gray, &c)) != WM_OK) return rc;
     LaunchGeom lg;
     if ((rc = geom_checked(ctx, frames, mask, &lg)) != WM_OK) return rc;
-    OpResult* res = s.d_res + s.res_used;
-    if (mask == WM_MASK_ME) sweep_gram(ctx, s, K_GRAM, lg, frames, xd);
-    sweep_stats(ctx, s, true, lg, frames, mask, xd, res);
-    if (mask == WM_MASK_ME)
-        launch_embed_signs(s.stream, lg, frames, 0, 1, xd, ctx->w->d_w, aligned_w_of(ctx), bd, od, s.d_coef, s.d_status, s.d_scal, (const signed char*)td, tile_rows, tile_cols, ny, nx);
-    else
-        launch_embed_signs(s.stream, lg, frames, 1, ctx->p / 2, xd, ctx->w->d_w, aligned_w_of(ctx), bd, od, nullptr, nullptr, s.d_scal, (const signed char*)td, tile_rows, tile_cols, ny, nx);
-    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
-    if (out->mem == WM_MEM_HOST && (rc = stage_out(ctx, s, out, s.st_out, st_out_l)) != WM_OK) return rc;
-    s.last_out = od; s.last_out_frames = frames; s.last_out_dtype = out->dtype;
-    push_pending(s, frames, 1, true, a_out, status_out, nullptr);
-    return slot == WM_SLOT_SYNC ? do_sync(ctx, s) : WM_OK;
-}
-
-// tile_bit [ny * nx] in -1 .. nbits - 1 (the caller has checked nbits)
-static bool tile_bits_ok(const int32_t* tile_bit, long long T, int nbits)
-{
-    for (long long t = 0; t < T; ++t)
-        if (tile_bit[t] < -1 || tile_bit[t] >= nbits) return false;
-    return true;
+    const MaskRoute mr = mask_route(ctx, s, mask);
+    if (mask == WM_MASK_ME) sweep_gram(ctx, s, K_GRAM, lg, frames, c.xd);
+    sweep_stats(ctx, s, true, lg, frames, mask, c.xd, s.d_res + s.res_used);
+    launch_embed_signs(s.stream, lg, frames, mr.mask, mr.pad, c.xd, ctx->w->d_w, aligned_w_of(ctx), c.bd, c.od, mr.coef, mr.status, s.d_scal, (const signed char*)td,
+                       tile_rows, tile_cols, ny, nx);
+    return embed_close(ctx, s, out, c, a_out, status_out, slot);
 }
 
 // a host layer over wm_embed_signs: tile t carries payload bit tile_bit[t] as +1 (bit set) or -1, or nothing (tile_bit[t] = -1)
@@ -1897,13 +1910,10 @@ int wm_embed_bits(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane
 {
     if (!ctx) return WM_ERR_BAD_ARG;
     if (!in_gray || !tile_bit || !payload) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_bits: null in_gray, tile_bit or payload");
-    int ny = 0, nx = 0;
-    if (wm_tiles_shape(ctx->rows, ctx->cols, tile_rows, tile_cols, &ny, &nx) != WM_OK)
-        return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_bits: tile shape " + std::to_string(tile_rows) + "x" + std::to_string(tile_cols) +
-                                             " (rows: a multiple of 8, >= 32; columns: a multiple of 4, >= 32)");
+    int ny = 0, nx = 0, rc;
+    if ((rc = tiles_checked(ctx, "wm_embed_bits", tile_rows, tile_cols, &ny, &nx)) != WM_OK) return rc;
     const long long T = (long long)ny * nx;
-    if (nbits < 1 || nbits > 4096 || !tile_bits_ok(tile_bit, T, nbits))
-        return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_bits: nbits must be 1 .. 4096 and every tile_bit entry -1 .. nbits - 1");
+    if ((rc = tile_bits_checked(ctx, "wm_embed_bits", tile_bit, T, nbits)) != WM_OK) return rc;
     if (in_gray->frames < 1 || in_gray->frames > ctx->max_frames)
         return fail(ctx, WM_ERR_BAD_ARG, "in_gray: frames=" + std::to_string(in_gray->frames) + " exceeds wm_configure max_frames=" + std::to_string(ctx->max_frames));
     const int frames = in_gray->frames, pbytes = (nbits + 7) / 8;
@@ -1923,16 +1933,12 @@ int wm_detect_bits(wm_ctx* ctx, int mask, const wm_plane* img, int tile_rows, in
 {
     if (!ctx) return WM_ERR_BAD_ARG;
     if (!img || !tile_bit || !soft_out) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_bits: null img, tile_bit or soft_out");
-    int ny = 0, nx = 0;
-    if (wm_tiles_shape(ctx->rows, ctx->cols, tile_rows, tile_cols, &ny, &nx) != WM_OK)
-        return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_bits: tile shape " + std::to_string(tile_rows) + "x" + std::to_string(tile_cols) +
-                                             " (rows: a multiple of 8, >= 32; columns: a multiple of 4, >= 32)");
+    int ny = 0, nx = 0, rc;
+    if ((rc = tiles_checked(ctx, "wm_detect_bits", tile_rows, tile_cols, &ny, &nx)) != WM_OK) return rc;
     const int T = ny * nx;
-    if (nbits < 1 || nbits > 4096 || !tile_bits_ok(tile_bit, T, nbits))
-        return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_bits: nbits must be 1 .. 4096 and every tile_bit entry -1 .. nbits - 1");
-    int rc = check_mask(ctx, mask);
-    if (rc != WM_OK) return rc;
-    if (ctx->band_hi > 0) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_bits: not in band mode");
+    if ((rc = tile_bits_checked(ctx, "wm_detect_bits", tile_bit, T, nbits)) != WM_OK) return rc;
+    if ((rc = check_mask(ctx, mask)) != WM_OK) return rc;
+    if ((rc = refuse_band(ctx, "wm_detect_bits")) != WM_OK) return rc;
     if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
     Slot& s = slot_of(ctx, slot);
     PlaneDesc xd;
@@ -1968,9 +1974,7 @@ int wm_detect_bits(wm_ctx* ctx, int mask, const wm_plane* img, int tile_rows, in
     { ProfScope ps(ctx, K_DETECT_TILES, s.stream); launch_detect_tiles(s.stream, pl, frames, mask, ctx->p / 2, xd, ctx->w->d_w, s.d_coef, s.d_status, (float*)s.tiles_rec); }
     { ProfScope ps(ctx, K_TILES_FOLD, s.stream); launch_tiles_fold(s.stream, pl, frames, (const float*)s.tiles_rec, s.d_status, map, sums, tres); }
     launch_bits_fold(s.stream, frames, nbits, T, sums, (const int*)td, (const int*)td + nbits + 1, s.d_status, s.d_res + s.res_used);
-    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
-    push_pending(s, frames, nbits, false, soft_out, status_out, nullptr);
-    return slot == WM_SLOT_SYNC ? do_sync(ctx, s) : WM_OK;
+    return finish_call(ctx, s, slot, frames, nbits, false, soft_out, status_out);
 }
 
 // makeWatermark of every frame with every key of the bank: wm_embed's input and base handling, one record per (frame, key)
@@ -1982,7 +1986,7 @@ int wm_embed_keys(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane
     if (rc != WM_OK) return rc;
     if (!keys || !out) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_keys: null keys or out");
     if ((rc = check_bank(ctx, keys, "wm_embed_keys", true)) != WM_OK) return rc;
-    if (ctx->band_hi > 0) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_keys: not in band mode");
+    if ((rc = refuse_band(ctx, "wm_embed_keys")) != WM_OK) return rc;
     if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
     Slot& s = slot_of(ctx, slot);
     if ((rc = check_plane(ctx, in_gray, 0, false, "in_gray", true)) != WM_OK) return rc;
@@ -2000,8 +2004,7 @@ int wm_embed_keys(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane
         if (out->frames > 1 && out->frame_stride < (int64_t)(out->channels - 1) * (out->channels > 1 ? out->channel_stride : 0) + (int64_t)out->rows * out->pitch)
             return fail(ctx, WM_ERR_BAD_ARG, "out: frame_stride too small (frames overlap)");
     }
-    if (out->channels != base->channels || out->dtype != base->dtype) return fail(ctx, WM_ERR_BAD_ARG, "out must have the shape and dtype of base");
-    if (in_gray->dtype != base->dtype) return fail(ctx, WM_ERR_BAD_ARG, "in_gray and base must have the same dtype (the reference converts whole frames, main.cpp:355-357)");
+    if ((rc = check_embed_dtypes(ctx, in_gray, base, out)) != WM_OK) return rc;
     if ((rc = check_res_room(ctx, s, (long long)frames * nkeys, "keys")) != WM_OK) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
 
@@ -2022,21 +2025,18 @@ int wm_embed_keys(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane
     if ((rc = ensure(ctx, &s.ekeys_part, &s.ekeys_part_bytes, embed_keys_scratch_bytes(frames, nkeys, rstride))) != WM_OK) return rc;
     const int aligned_w = aligned_w_of(ctx);  // (the bank's planes have W's shape)
     const long long kstride = (long long)ctx->rows * ctx->cols;
-    const int pad = ctx->p / 2;
+    const MaskRoute mr = mask_route(ctx, s, mask);  // (these launchers take the mask type itself and the slot's coefficients under either)
     OpResult* res = s.d_res + s.res_used;
-    const int* status = mask == WM_MASK_ME ? s.d_status : nullptr;
     // the image side is wm_embed's: the Gram sweep and solve (ME)
     if (mask == WM_MASK_ME) sweep_gram(ctx, s, K_GRAM, lg, frames, xd);
     {
         ProfScope ps(ctx, K_STATS_KEYS, s.stream);
-        if (launch_stats_keys(s.stream, lg, frames, mask, pad, xd, keys->d, kstride, nkeys, aligned_w, s.d_coef, status, s.ekeys_part, rstride) != 0)
+        if (launch_stats_keys(s.stream, lg, frames, mask, mr.pad, xd, keys->d, kstride, nkeys, aligned_w, s.d_coef, mr.status, s.ekeys_part, rstride) != 0)
             return fail(ctx, WM_ERR_RUNTIME, "wm_embed_keys: geometry exceeds the record arrays");
     }
-    { ProfScope ps(ctx, K_EMBED_KEYS_FOLD, s.stream); launch_embed_keys_fold(s.stream, lg, frames, mask, nkeys, status, s.ekeys_part, rstride, ctx->sF, sqrt_n(ctx), res); }
-    { ProfScope ps(ctx, K_EMBED_KEYS, s.stream); launch_embed_keys(s.stream, lg, frames, mask, pad, xd, keys->d, kstride, nkeys, aligned_w, bd, od, s.d_coef, status, s.ekeys_part, rstride); }
-    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
-    push_pending(s, frames, nkeys, true, a_out, status_out, nullptr);  // (wm_embed's rule: an unsolvable frame leaves its K strengths untouched)
-    return slot == WM_SLOT_SYNC ? do_sync(ctx, s) : WM_OK;
+    { ProfScope ps(ctx, K_EMBED_KEYS_FOLD, s.stream); launch_embed_keys_fold(s.stream, lg, frames, mask, nkeys, mr.status, s.ekeys_part, rstride, ctx->sF, sqrt_n(ctx), res); }
+    { ProfScope ps(ctx, K_EMBED_KEYS, s.stream); launch_embed_keys(s.stream, lg, frames, mask, mr.pad, xd, keys->d, kstride, nkeys, aligned_w, bd, od, s.d_coef, mr.status, s.ekeys_part, rstride); }
+    return finish_call(ctx, s, slot, frames, nkeys, true, a_out, status_out);  // (wm_embed's rule: an unsolvable frame leaves its K strengths untouched)
 }
 
 int wm_compute_mask(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* mask_out, const wm_plane* e_out,
@@ -2067,18 +2067,15 @@ int wm_compute_mask(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_pla
     invalidate_handovers(ctx, eo, frames);
     OpResult* res = s.d_res + s.res_used;
     float* coefres = s.d_coefres + (size_t)s.res_used * 8;
+    const MaskRoute mr = mask_route(ctx, s, mask);
+    // (ME: the prediction error scaled by the stats sweep's maximum, behind the Gram and stats sweeps; NVF needs neither, nor scalars)
     if (mask == WM_MASK_ME) {
         sweep_gram(ctx, s, K_GRAM, lg, frames, xd);
         sweep_stats(ctx, s, true, lg, frames, mask, xd, res);
-        { ProfScope ps(ctx, K_MASK, s.stream); launch_mask(s.stream, lg, frames, 0, 1, xd, s.d_coef, s.d_status, s.d_scal, mo, eo); }
-        launch_mask_result(s.stream, frames, s.d_status, s.d_coef, res, coefres);
-    } else {
-        { ProfScope ps(ctx, K_MASK, s.stream); launch_mask(s.stream, lg, frames, 1, ctx->p / 2, xd, nullptr, nullptr, nullptr, mo, eo); }
-        launch_mask_result(s.stream, frames, nullptr, nullptr, res, coefres);
     }
-    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
-    push_pending(s, frames, 1, false, nullptr, status_out, coef_out);
-    return slot == WM_SLOT_SYNC ? do_sync(ctx, s) : WM_OK;
+    { ProfScope ps(ctx, K_MASK, s.stream); launch_mask(s.stream, lg, frames, mr.mask, mr.pad, xd, mr.coef, mr.status, mask == WM_MASK_ME ? s.d_scal : nullptr, mo, eo); }
+    launch_mask_result(s.stream, frames, mr.status, mr.coef, res, coefres);
+    return finish_call(ctx, s, slot, frames, 1, false, nullptr, status_out, coef_out);
 }
 
 int wm_gram(wm_ctx* ctx, const wm_plane* img, double* gram_out, int slot)
@@ -2168,8 +2165,8 @@ static int band_embed_launch(wm_ctx* ctx, Slot& s, int mask, const wm_plane* in_
     invalidate_handovers(ctx, od, frames);
     LaunchGeom lg;
     if ((rc = geom_checked(ctx, frames, mask, &lg)) != WM_OK) return rc;
-    if (mask == WM_MASK_ME) launch_embed(s.stream, lg, frames, 0, 1, xd, ctx->w->d_w, aligned_w_of(ctx), bd, od, s.d_coef, s.d_status, s.d_scal);
-    else launch_embed(s.stream, lg, frames, 1, ctx->p / 2, xd, ctx->w->d_w, aligned_w_of(ctx), bd, od, nullptr, nullptr, s.d_scal);
+    const MaskRoute mr = mask_route(ctx, s, mask);
+    launch_embed(s.stream, lg, frames, mr.mask, mr.pad, xd, ctx->w->d_w, aligned_w_of(ctx), bd, od, mr.coef, mr.status, s.d_scal);
     return launch_check(ctx, s);
 }
 
