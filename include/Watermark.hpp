@@ -384,6 +384,43 @@ public:
         strengths = a;
         return copies;
     }
+    // one image, K payload copies in one call (wm.h wm_embed_signs_multi): signs[k] is makeWatermarkSigns' table of copy k, copy k what
+    // makeWatermarkSigns returns with it; ONE strength for all copies.  Not solvable: every copy is `outputImage` itself and
+    // `watermarkStrength` is left untouched
+    std::vector<wm::Image> makeWatermarkSignsMulti(const wm::Image& inputImage, const wm::Image& outputImage, float& watermarkStrength, int tileRows,
+                                                   int tileCols, const std::vector<std::vector<int8_t>>& signs, MASK_TYPE maskType) const
+    {
+        int ty = 0, tx = 0;
+        const int rc = wm_tiles_shape(wm_rows(ctx), wm_cols(ctx), tileRows, tileCols, &ty, &tx);
+        const size_t T = (size_t)ty * (size_t)tx;
+        if (rc < 0 || signs.empty()) fail(WM_ERR_BAD_ARG, "makeWatermarkSignsMulti");
+        std::vector<int8_t> flat;
+        for (const auto& s : signs) {
+            if (s.size() != T) fail(WM_ERR_BAD_ARG, "makeWatermarkSignsMulti");
+            flat.insert(flat.end(), s.begin(), s.end());
+        }
+        return embedMulti("makeWatermarkSignsMulti", inputImage, outputImage, watermarkStrength, (int)signs.size(), [&](const wm_plane* pin, const wm_plane* pbase, const wm_plane* pout, float* a, int* st) {
+            return wm_embed_signs_multi(ctx, (int)maskType, pin, pbase, pout, tileRows, tileCols, (int)signs.size(), flat.data(), a, st, WM_SLOT_SYNC);
+        });
+    }
+    // one image, K payloads in one call (wm.h wm_embed_bits_multi): payloads[k] is makeWatermarkBits' payload of copy k
+    std::vector<wm::Image> makeWatermarkBitsMulti(const wm::Image& inputImage, const wm::Image& outputImage, float& watermarkStrength, int tileRows,
+                                                  int tileCols, const std::vector<int32_t>& tileBit, int nbits,
+                                                  const std::vector<std::vector<uint8_t>>& payloads, MASK_TYPE maskType) const
+    {
+        int ty = 0, tx = 0;
+        const int rc = wm_tiles_shape(wm_rows(ctx), wm_cols(ctx), tileRows, tileCols, &ty, &tx);
+        if (rc < 0 || tileBit.size() != (size_t)ty * (size_t)tx || nbits < 1 || payloads.empty()) fail(WM_ERR_BAD_ARG, "makeWatermarkBitsMulti");
+        std::vector<uint8_t> flat;
+        for (const auto& p : payloads) {
+            if (p.size() != (size_t)(nbits + 7) / 8) fail(WM_ERR_BAD_ARG, "makeWatermarkBitsMulti");
+            flat.insert(flat.end(), p.begin(), p.end());
+        }
+        return embedMulti("makeWatermarkBitsMulti", inputImage, outputImage, watermarkStrength, (int)payloads.size(), [&](const wm_plane* pin, const wm_plane* pbase, const wm_plane* pout, float* a, int* st) {
+            return wm_embed_bits_multi(ctx, (int)maskType, pin, pbase, pout, tileRows, tileCols, tileBit.data(), nbits, (int)payloads.size(), flat.data(), a, st,
+                                       WM_SLOT_SYNC);
+        });
+    }
     // makeWatermark, then detectWatermark on its result (the pair testForImage runs per image, main.cpp:165-220), as ONE call:
     // same results, one wait (wm.h wm_embed_detect; grey output images)
     wm::Image makeAndDetectWatermark(const wm::Image& inputImage, const wm::Image& outputImage, float& watermarkStrength, float& correlation,
@@ -425,6 +462,24 @@ private:
     {
         throw std::runtime_error(std::string("ERROR in ") + where + ": " + wm_strerror(rc) + " " + (ctx ? wm_last_error(ctx) : "") +
                                  " Error code: " + std::to_string(rc) + "\n");
+    }
+    // the *Multi embeds around their C call: K stacked copies of one image as makeWatermarkKeys stacks them, one strength
+    template <typename Call>
+    std::vector<wm::Image> embedMulti(const char* where, const wm::Image& inputImage, const wm::Image& outputImage, float& watermarkStrength, int K,
+                                      Call&& call) const
+    {
+        std::vector<wm::Image> copies = wm::Image::stack(K, outputImage.rows(), outputImage.cols(), outputImage.channels(), outputImage.type(), device);
+        const wm_plane pin = inputImage.plane(), pbase = outputImage.plane();
+        wm_plane pout = copies[0].plane();
+        pout.frames = K;
+        pout.frame_stride = (int64_t)outputImage.elements();
+        float a = 0.0f;
+        int st = 0;
+        const int rc = call(&pin, &pbase, &pout, &a, &st);
+        if (rc < 0) fail(rc, where);
+        if (st != 0) return std::vector<wm::Image>((size_t)K, outputImage);
+        watermarkStrength = a;
+        return copies;
     }
     void check(int rc, const char* where) const
     {

@@ -419,6 +419,51 @@ int wm_embed_bits(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane
 int wm_detect_bits(wm_ctx* ctx, int mask, const wm_plane* img, int tile_rows, int tile_cols, const int32_t* tile_bit, int nbits,
                    float* soft_out /* HOST [frames][nbits], by wm_sync */, int* status_out, int slot);
 
+/* ---- One frame, many payload copies: K recipients, one key, one call ---------------------------------------------------------------
+ * A distributor marks one frame for K recipients, each copy with its own ID and all of them with the context's W.  Nothing on the
+ * image side depends on the payload: the Gram sums, the coefficients, the mask and max|e| are the frame's, and so is the strength,
+ * since ||m W|| does not see the signs.  wm_embed_signs_multi runs ONE Gram sweep, ONE solve and ONE stats sweep per frame (wm_embed's
+ * own, with the context's W -- not wm_embed_keys' per-key statistics) and ONE embed sweep (k_embed_signs_multi) that forms m, the W
+ * row, u = m W and the base row once per row for a group of wm_embed_signs_group() copies and then, per copy, multiplies by the tile's
+ * sign and stores: K stores of y, and x, W and base read once per group.
+ *
+ * signs is a HOST array [frames][ncopies][ny][nx] of -1, 0 or +1.  Copy (f, k) is frame f * ncopies + k of `out` and equals, bit for
+ * bit, what wm_embed_signs on the batched sweeps writes for frame f with the table signs[f][k]; a_out[frames] is wm_embed_signs'
+ * strength, which is wm_embed's: ONE strength per frame, not per copy.  status_out[frames]; either may be NULL; both are written by
+ * wm_sync.
+ *   - in_gray and base take everything wm_embed_keys takes: f32 / u8, a grey or planar-RGB base (run once per channel), a base that is
+ *     in_gray itself, any pitch and width, WM_MEM_HOST, WM_MEM_SLOT_OUT for in_gray, batches up to max_frames, ME with p = 3
+ *     (WM_ERR_BAD_P otherwise), NVF with p = 3..9.
+ *   - `out` follows wm_embed_keys' rules: a WM_MEM_DEVICE plane with the channels and dtype of `base`, out->frames ==
+ *     in_gray->frames * ncopies (it may exceed max_frames), any pitch and frame stride; its frames must not overlap each other,
+ *     in_gray or base (WM_ERR_BAD_ARG, judged on the resolved planes).
+ *   - 1 <= ncopies <= 4096, and the sweep's grid times the copy groups must fit a launch grid of 31 bits: WM_ERR_BAD_ARG before any
+ *     device work otherwise.
+ *   - An unsolvable frame has status WM_UNSOLVABLE: all its copies equal base bit for bit and a_out[f] is left untouched.  A
+ *     zero-energy frame follows wm_embed's rule: a = +inf, copies equal base.
+ *   - An ENQUEUE on the slot (WM_SLOT_SYNC: slot 0, waits); `frames` results count against the slot's capacity of 4096 un-synced
+ *     results.  Like wm_embed_keys it leaves no Gram hand-over behind, does not change what WM_MEM_SLOT_OUT names, and ends a
+ *     hand-over whose plane its copies overwrite.  Never takes the fused kernels; refused in band mode (WM_ERR_BAD_ARG).
+ *     k_embed_signs_multi is not in the wm_prof_* list.
+ *   - `signs` is read before the call returns and kept like wm_embed_signs' table, frames * ncopies * ny * nx bytes in the slot's
+ *     pinned host arena and device arena: the FIRST call on a slot that needs more of them than are left waits for the slot's stream
+ *     and reallocates them, which waits for the whole device, the other slots' streams included.  Later calls only enqueue.
+ *   - WM_ERR_BAD_ARG, before any device work, for a null ctx, plane or signs, a tile shape wm_tiles_shape refuses and a sign outside
+ *     {-1, 0, +1} (its index is in the message).  Arguments are looked at in wm_embed_signs' order: null pointers, tile shape, mask,
+ *     band mode, slot, planes, ncopies, signs, record room.
+ *
+ * wm_embed_bits_multi: a host layer over it.  payloads is a HOST array [frames][ncopies][(nbits + 7) / 8]; the table of copy (f, k)
+ * is built exactly as wm_embed_bits builds its table from payloads[f][k].  tile_bit and nbits as for wm_embed_bits.
+ *
+ * wm_embed_signs_group: G, the copies whose stores share one march (a compile-time constant of the library). */
+int wm_embed_signs_group(void);
+int wm_embed_signs_multi(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* base, const wm_plane* out, int tile_rows,
+                         int tile_cols, int ncopies, const int8_t* signs /* HOST [frames][ncopies][ny][nx], -1 | 0 | +1 */,
+                         float* a_out /* [frames] */, int* status_out /* [frames] */, int slot);
+int wm_embed_bits_multi(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* base, const wm_plane* out, int tile_rows,
+                        int tile_cols, const int32_t* tile_bit /* HOST [ny*nx] */, int nbits, int ncopies,
+                        const uint8_t* payloads /* HOST [frames][ncopies][(nbits+7)/8] */, float* a_out, int* status_out, int slot);
+
 /* makeWatermark (Watermark.cpp:156-172) of every frame of `in_gray` once with EVERY key of the bank as W: one marked copy per
  * recipient.  Copy (f, k) -- frame f marked with key k -- is frame f * nkeys + k of `out`, so out->frames must be
  * in_gray->frames * nkeys; `out` is a WM_MEM_DEVICE plane with the channels and dtype of `base` (any pitch and frame stride; it

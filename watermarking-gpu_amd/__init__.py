@@ -87,6 +87,11 @@ ABI = [
     ("wm_embed_bits", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), _P(wm_plane), _P(wm_plane), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                _P(C.c_float), _P(C.c_int), C.c_int]),
     ("wm_detect_bits", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), C.c_int, C.c_int, C.c_void_p, C.c_int, _P(C.c_float), _P(C.c_int), C.c_int]),
+    ("wm_embed_signs_group", C.c_int, []),
+    ("wm_embed_signs_multi", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), _P(wm_plane), _P(wm_plane), C.c_int, C.c_int, C.c_int, C.c_void_p, _P(C.c_float),
+                                      _P(C.c_int), C.c_int]),
+    ("wm_embed_bits_multi", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), _P(wm_plane), _P(wm_plane), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                     C.c_void_p, _P(C.c_float), _P(C.c_int), C.c_int]),
     ("wm_compute_mask", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), _P(wm_plane), _P(wm_plane), _P(C.c_float), _P(C.c_int), C.c_int]),
     ("wm_gram", C.c_int, [_ctx_p, _P(wm_plane), _P(C.c_double), C.c_int]),
     ("wm_band_configure", C.c_int, [_ctx_p, C.c_int, C.c_int, C.c_longlong]),
@@ -617,6 +622,43 @@ class Watermark:
                                       a.ctypes.data_as(_P(C.c_float)), None, WM_SLOT_SYNC))
         return out, (a if batched else a[0])
 
+    def _embed_multi(self, how, inputImage, outputImage, K, maskType, out):
+        """the synchronous front of the *_multi embeds: K copies per frame shaped as makeWatermarkKeys returns them, one strength per
+        frame (NaN for an unsolvable frame, whose copies equal outputImage)"""
+        import torch
+        batched = inputImage.dim() == 3
+        frames = plane_of(inputImage, 1).frames
+        per = tuple(outputImage.shape[1:] if batched else outputImage.shape)
+        shape = ((frames,) if batched else ()) + (K,) + per
+        if out is None:
+            out = torch.empty(shape, dtype=outputImage.dtype, device=outputImage.device)
+        elif tuple(out.shape) != shape or out.dtype != outputImage.dtype:
+            raise RuntimeError(f"out must be {outputImage.dtype} of shape {shape}, got {out.dtype} {tuple(out.shape)}")
+        a, st = self._strength_bufs(frames)
+        torch.cuda.current_stream().synchronize()
+        how(inputImage, outputImage, out.view((frames * K,) + per), maskType, WM_SLOT_SYNC, a, st)
+        return out, np.array([np.nan if st[f] != 0 else a[f] for f in range(frames)], np.float32)
+
+    def makeWatermarkSignsMulti(self, inputImage, outputImage, tile_rows, tile_cols, signs, maskType, out=None):
+        """one frame, K payload copies in one call (wm.h wm_embed_signs_multi): `signs` is an integer array [F, K, ny, nx] ([K, ny, nx]
+        for one frame) of -1, 0 or +1.  Returns (copies, a): copies [F, K, ...] ([K, ...] for one frame) shaped as makeWatermarkKeys
+        returns them, copy (f, k) what makeWatermarkSigns writes with signs[f][k]; a float32 [F], one strength per frame"""
+        frames = plane_of(inputImage, 1).frames
+        K = np.asarray(signs).size // max(1, frames * int(np.prod(self.tiles_shape(self.rows, self.cols, tile_rows, tile_cols))))
+        return self._embed_multi(lambda i, b, o, m, slot, a, st: self.embed_signs_multi_async(i, b, o, tile_rows, tile_cols, K, signs, m, slot, a, st),
+                                 inputImage, outputImage, K, maskType, out)
+
+    def makeWatermarkBitsMulti(self, inputImage, outputImage, tile_rows, tile_cols, tile_bit, nbits, payloads, maskType, out=None):
+        """one frame, K payloads in one call (wm.h wm_embed_bits_multi): `payloads` is a uint8 array [F, K, (nbits + 7) // 8]
+        ([K, ...] for one frame) or a list of K bytes objects for one frame.  Returns (copies, a) as makeWatermarkSignsMulti does"""
+        frames = plane_of(inputImage, 1).frames
+        if isinstance(payloads, (list, tuple)) and payloads and isinstance(payloads[0], (bytes, bytearray)):
+            payloads = np.stack([np.frombuffer(bytes(b), np.uint8) for b in payloads])
+        K = np.asarray(payloads).size // max(1, frames * ((max(nbits, 1) + 7) // 8))
+        return self._embed_multi(lambda i, b, o, m, slot, a, st: self.embed_bits_multi_async(i, b, o, tile_rows, tile_cols, tile_bit, nbits, K, payloads,
+                                                                                             m, slot, a, st),
+                                 inputImage, outputImage, K, maskType, out)
+
     def makeAndDetect(self, inputImage, outputImage, maskType, out=None):
         """makeWatermark followed by detectWatermark on its result (testForImage's pair, main.cpp:165-220) as one call
         (wm.h wm_embed_detect; grey output).  Returns (watermarked, strength or None, correlation)."""
@@ -766,6 +808,33 @@ class Watermark:
         a_out, status_out = self._scalars_out(a_out, status_out)
         self._chk(lib().wm_embed_bits(self._ctx, int(maskType), C.byref(pin), C.byref(pbase), C.byref(pout), tile_rows, tile_cols,
                                       tb.ctypes.data_as(C.c_void_p), nbits, pl.ctypes.data_as(C.c_void_p), a_out, status_out, slot))
+
+    def embed_signs_multi_async(self, inputImage, outputImage, out, tile_rows, tile_cols, ncopies, signs, maskType, slot, a_out=None,
+                                status_out=None):
+        """wm_embed_signs_multi enqueued on `slot`: `out` holds frames * ncopies copies (a tensor [frames * ncopies, ...] or a wm_plane;
+        copy (f, k) is frame f * ncopies + k); `signs` (frames * ncopies * ny * nx integers of -1, 0, +1) is copied before the call
+        returns; a_out (frames floats) and status_out (frames ints) as for embed_signs_async"""
+        pin, pbase, pout = self._embed_planes(inputImage, outputImage, out)
+        ny, nx = self.tiles_shape(self.rows, self.cols, tile_rows, tile_cols)
+        raw = np.asarray(signs)
+        if raw.dtype != np.int8 and raw.size and (raw.min() < -128 or raw.max() > 127):  # (values the int8 table cannot hold)
+            _raise(WM_ERR_BAD_ARG)
+        sg = self._host_table(raw, np.int8, pin.frames * max(ncopies, 0) * ny * nx, "signs")
+        a_out, status_out = self._scalars_out(a_out, status_out)
+        self._chk(lib().wm_embed_signs_multi(self._ctx, int(maskType), C.byref(pin), C.byref(pbase), C.byref(pout), tile_rows, tile_cols, ncopies,
+                                             sg.ctypes.data_as(C.c_void_p), a_out, status_out, slot))
+
+    def embed_bits_multi_async(self, inputImage, outputImage, out, tile_rows, tile_cols, tile_bit, nbits, ncopies, payloads, maskType, slot,
+                               a_out=None, status_out=None):
+        """wm_embed_bits_multi enqueued on `slot`: tile_bit (ny * nx int32) and payloads (frames * ncopies * ((nbits + 7) // 8) bytes)
+        are read before the call returns; `out`, a_out and status_out as for embed_signs_multi_async"""
+        pin, pbase, pout = self._embed_planes(inputImage, outputImage, out)
+        ny, nx = self.tiles_shape(self.rows, self.cols, tile_rows, tile_cols)
+        tb = self._host_table(tile_bit, np.int32, ny * nx, "tile_bit")
+        pl = self._host_table(payloads, np.uint8, pin.frames * max(ncopies, 0) * ((max(nbits, 1) + 7) // 8), "payloads")
+        a_out, status_out = self._scalars_out(a_out, status_out)
+        self._chk(lib().wm_embed_bits_multi(self._ctx, int(maskType), C.byref(pin), C.byref(pbase), C.byref(pout), tile_rows, tile_cols,
+                                            tb.ctypes.data_as(C.c_void_p), nbits, ncopies, pl.ctypes.data_as(C.c_void_p), a_out, status_out, slot))
 
     def detect_bits_async(self, image, tile_rows, tile_cols, tile_bit, nbits, maskType, slot, soft_out, status_out=None):
         """wm_detect_bits enqueued on `slot`: tile_bit (ny * nx int32) is read before the call returns; soft_out (frames * nbits

@@ -2039,6 +2039,99 @@ int wm_embed_keys(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane
     return finish_call(ctx, s, slot, frames, nkeys, true, a_out, status_out);  // (wm_embed's rule: an unsolvable frame leaves its K strengths untouched)
 }
 
+int wm_embed_signs_group(void) { return embed_signs_group(); }
+
+// wm_embed_signs of every frame once per table of signs [frames][ncopies][ny][nx]: wm_embed_signs' table handling, Gram, solve and
+// single-W stats sweeps (one strength per frame), wm_embed_keys' planes (K device outputs per frame, no overlap, no last_out, no
+// hand-over), k_embed_signs_multi in k_embed_signs' place -- launched outside any ProfScope, like it
+int wm_embed_signs_multi(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* base, const wm_plane* out, int tile_rows, int tile_cols,
+                         int ncopies, const int8_t* signs, float* a_out, int* status_out, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    if (!in_gray || !base || !out || !signs) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_signs_multi: null in_gray, base, out or signs");
+    int ny = 0, nx = 0, rc;
+    if ((rc = tiles_checked(ctx, "wm_embed_signs_multi", tile_rows, tile_cols, &ny, &nx)) != WM_OK) return rc;
+    if ((rc = check_mask(ctx, mask)) != WM_OK) return rc;
+    if ((rc = refuse_band(ctx, "wm_embed_signs_multi")) != WM_OK) return rc;
+    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
+    if ((rc = check_plane(ctx, in_gray, 0, false, "in_gray", true)) != WM_OK) return rc;
+    const int frames = in_gray->frames;
+    if ((rc = check_plane(ctx, base, frames, true, "base")) != WM_OK) return rc;
+    // out: frames * ncopies device planes (more than max_frames is fine: the sweeps' scratch is per input frame)
+    if (out->mem != WM_MEM_DEVICE) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_signs_multi: out must be a WM_MEM_DEVICE plane");
+    if (ncopies < 1 || ncopies > 4096) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_signs_multi: ncopies must be 1 .. 4096");
+    if ((long long)out->frames != (long long)frames * ncopies)
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_signs_multi: out->frames must be in_gray->frames * ncopies = " + std::to_string((long long)frames * ncopies));
+    {
+        wm_plane one = *out;
+        one.frames = 1;
+        if ((rc = check_plane(ctx, &one, 1, true, "out")) != WM_OK) return rc;
+        if (out->frames > 1 && out->frame_stride < (int64_t)(out->channels - 1) * (out->channels > 1 ? out->channel_stride : 0) + (int64_t)out->rows * out->pitch)
+            return fail(ctx, WM_ERR_BAD_ARG, "out: frame_stride too small (frames overlap)");
+    }
+    if ((rc = check_embed_dtypes(ctx, in_gray, base, out)) != WM_OK) return rc;
+    const LaunchGeom lg0 = make_geom(ctx, frames, mask);
+    if (!embed_signs_multi_grid_fits(lg0, frames, ncopies))
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_signs_multi: the sweep's grid times the copy groups exceeds a launch grid of 31 bits");
+    const size_t nsigns = (size_t)frames * ncopies * ny * nx;
+    for (size_t i = 0; i < nsigns; ++i)
+        if (signs[i] < -1 || signs[i] > 1)
+            return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_signs_multi: sign " + std::to_string((int)signs[i]) + " at index " + std::to_string(i) + " (must be -1, 0 or +1)");
+    if ((rc = check_res_room(ctx, s, frames)) != WM_OK) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+
+    // the call's own copy of the tables, as wm_embed_signs keeps its one
+    void *th = nullptr, *td = nullptr;
+    if ((rc = table_room(ctx, s, nsigns, &th, &td)) != WM_OK) return rc;
+    std::memcpy(th, signs, nsigns);
+    if ((rc = table_upload(ctx, s, th, td, nsigns)) != WM_OK) return rc;
+
+    PlaneDesc xd, bd;
+    if ((rc = prep_input(ctx, s, in_gray, &xd)) != WM_OK) return rc;
+    if ((rc = prep_base(ctx, s, in_gray, base, xd, &bd)) != WM_OK) return rc;
+    const PlaneDesc od = desc_device(out);
+    // K outputs of one input: an in-place call has no meaning (judged on the RESOLVED planes, as wm_embed_keys judges them)
+    if (descs_overlap(xd, od, ctx->rows, ctx->cols, frames, frames * ncopies) || descs_overlap(bd, od, ctx->rows, ctx->cols, frames, frames * ncopies))
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_signs_multi: out overlaps in_gray or base");
+    // no hand-over of its own, and WM_MEM_SLOT_OUT keeps naming the last wm_embed output; a hand-over whose plane the copies
+    // overwrite ends here
+    invalidate_handovers(ctx, od, frames * ncopies);
+
+    LaunchGeom lg;
+    if ((rc = geom_checked(ctx, frames, mask, &lg)) != WM_OK) return rc;
+    const MaskRoute mr = mask_route(ctx, s, mask);
+    if (mask == WM_MASK_ME) sweep_gram(ctx, s, K_GRAM, lg, frames, xd);
+    sweep_stats(ctx, s, true, lg, frames, mask, xd, s.d_res + s.res_used);
+    launch_embed_signs_multi(s.stream, lg, frames, mr.mask, mr.pad, xd, ctx->w->d_w, aligned_w_of(ctx), bd, od, mr.coef, mr.status, s.d_scal,
+                             (const signed char*)td, ncopies, tile_rows, tile_cols, ny, nx);
+    return finish_call(ctx, s, slot, frames, 1, true, a_out, status_out);
+}
+
+// a host layer over wm_embed_signs_multi: the table of copy (f, k) is wm_embed_bits' table for payloads[f][k]
+int wm_embed_bits_multi(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* base, const wm_plane* out, int tile_rows, int tile_cols,
+                        const int32_t* tile_bit, int nbits, int ncopies, const uint8_t* payloads, float* a_out, int* status_out, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    if (!in_gray || !tile_bit || !payloads) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_bits_multi: null in_gray, tile_bit or payloads");
+    int ny = 0, nx = 0, rc;
+    if ((rc = tiles_checked(ctx, "wm_embed_bits_multi", tile_rows, tile_cols, &ny, &nx)) != WM_OK) return rc;
+    const long long T = (long long)ny * nx;
+    if ((rc = tile_bits_checked(ctx, "wm_embed_bits_multi", tile_bit, T, nbits)) != WM_OK) return rc;
+    if (in_gray->frames < 1 || in_gray->frames > ctx->max_frames)
+        return fail(ctx, WM_ERR_BAD_ARG, "in_gray: frames=" + std::to_string(in_gray->frames) + " exceeds wm_configure max_frames=" + std::to_string(ctx->max_frames));
+    if (ncopies < 1 || ncopies > 4096) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_bits_multi: ncopies must be 1 .. 4096");
+    const long long copies = (long long)in_gray->frames * ncopies;
+    const int pbytes = (nbits + 7) / 8;
+    std::vector<int8_t> signs((size_t)(copies * T));
+    for (long long fk = 0; fk < copies; ++fk)
+        for (long long t = 0; t < T; ++t) {
+            const int b = tile_bit[t];
+            signs[(size_t)(fk * T + t)] = b < 0 ? 0 : (((payloads[(size_t)fk * pbytes + b / 8] >> (b % 8)) & 1) ? 1 : -1);
+        }
+    return wm_embed_signs_multi(ctx, mask, in_gray, base, out, tile_rows, tile_cols, ncopies, signs.data(), a_out, status_out, slot);
+}
+
 int wm_compute_mask(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* mask_out, const wm_plane* e_out,
                     float* coef_out, int* status_out, int slot)
 {

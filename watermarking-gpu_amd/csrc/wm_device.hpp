@@ -359,6 +359,17 @@ __device__ __forceinline__ WaveJob make_job(const Geom& g, int block_id)
 }
 __device__ __forceinline__ WaveJob make_job(const Geom& g) { return make_job(g, (int)blockIdx.x); }
 
+// the wave's job and group in a grid of `ngroups` blocks per tile (the key groups of k_stats_keys / k_embed_keys, the copy groups of
+// k_embed_signs_multi): block order of k_detect_keys (the groups of one (tile, frame) block are consecutive logical indices of one
+// XCD; inside a group the order is the sweep's own)
+__device__ __forceinline__ WaveJob keys_job(const Geom& g, int ngroups, int& grp)
+{
+    const int nb = (int)gridDim.x / ngroups;
+    const int pidx = xcd_remap((int)blockIdx.x, (int)gridDim.x);
+    grp = pidx % ngroups;
+    return make_job(g, xcd_unmap(pidx / ngroups, nb));
+}
+
 // ---- cross-lane neighbour exchange without LDS (aligned path) ----------------------------------
 // DPP wave shifts: lane i receives lane i-1's (resp. i+1's) value; the lane with no source keeps `edge`
 // (the DPP "old" operand), which is where the strip's halo column enters.

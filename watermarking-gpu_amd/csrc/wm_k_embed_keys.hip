@@ -42,15 +42,7 @@ struct EKeysArgs {
     EmbedScalars* scal;  // [frames][nkeys]           written by k_embed_keys_fold
 };
 
-// the wave's job and key group: block order of k_detect_keys (the key groups of one (tile, frame) block are consecutive
-// logical indices of one XCD; inside a group the order is the sweep's own)
-__device__ __forceinline__ WaveJob keys_job(const Geom& g, int ngroups, int& grp)
-{
-    const int nb = (int)gridDim.x / ngroups;
-    const int pidx = xcd_remap((int)blockIdx.x, (int)gridDim.x);
-    grp = pidx % ngroups;
-    return make_job(g, xcd_unmap(pidx / ngroups, nb));
-}
+// (the wave's job and key group: keys_job, wm_device.hpp)
 
 // =================================================================================================
 // k_stats_keys: me_stats_march / nvf_stats_march with the sum of (m W)^2 repeated for the keys of the group

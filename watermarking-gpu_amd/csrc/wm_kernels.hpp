@@ -284,6 +284,16 @@ void launch_embed_signs(hipStream_t s, const LaunchGeom& lg, int frames, int mas
                         const EmbedScalars* scal, const signed char* signs, int tile_rows, int tile_cols, int ny, int nx);
 void launch_bits_fold(hipStream_t s, int frames, int nbits, int ntiles, const double* sums, const int* start, const int* idx,
                       const int* status, OpResult* res);
+// one frame, many payload copies (wm_embed_signs_multi, wm_k_embed_signs_multi.hip): k_embed_signs' sweep with the image side formed
+// once per row and the sign, fmaf, clamp and store repeated for a compile-time group of copies; copy groups are a grid axis
+// (k_embed_keys' block order).  signs [frames][ncopies][ny][nx] on the device; copy (frame, k) is frame frame * ncopies + k of `out`;
+// scal: the frame's scalars of the single-W stats sweep.  embed_signs_multi_grid_fits: every grid of the sweep times the copy groups
+// fits 31 bits (from the shapes alone)
+bool embed_signs_multi_grid_fits(const LaunchGeom& lg, int frames, int ncopies);
+void launch_embed_signs_multi(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* W,
+                              int aligned_w, const PlaneDesc& base, const PlaneDesc& out, const float* coef, const int* status,
+                              const EmbedScalars* scal, const signed char* signs, int ncopies, int tile_rows, int tile_cols, int ny, int nx);
+int embed_signs_group(void);  // copies per group of k_embed_signs_multi (compile-time SMG)
 // band mode: solve the 8x8 system from all-reduced Gram totals [frames][44]; writes coef / status like k_gram's tail
 void launch_solve_totals(hipStream_t s, int frames, const double* totals, float* coef, int* status);
 // band mode, device-resident exchange (wm_band_*_dev): glue kernels between the sweeps and the caller's collectives
