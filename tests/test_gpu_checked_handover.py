@@ -4,7 +4,9 @@ plane it reads and holds it against the one the embed left; a frame whose digest
 ordinary sweeps (k_gram_redo / k_detect_redo).  Checked here: plain calls hand over over the tile geometries (every frame
 trusted, no Gram sweep over y, scores as the ordinary path's); pixels changed behind the embed from another stream -- one
 pixel, one bit, a zero-sum (+d, -2d, +d) triple, two swapped pixels -- are caught frame by frame and give the ordinary path's
-scores bit for bit; whatever the hand-over does not cover takes the ordinary path; results are bit-stable."""
+scores bit for bit; whatever the hand-over does not cover takes the ordinary path; results are bit-stable.
+test_gpu_checked_handover_coverage.py goes on from here: every pixel of small planes, both block mappings of the detector, every redo
+pattern, and the calls that follow a redo on the slot."""
 import ctypes as C
 
 import numpy as np
