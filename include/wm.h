@@ -117,6 +117,11 @@ int wm_set_fused(wm_ctx* ctx, int mode);
  * products across tile seams, the border frame and the solve: one of the five sweeps of an embed + detect pair is not run.
  * The 44 sums are the same exact products in another f64 summation order (agreement ~1e-16 relative, tests/test_gpu_handover.py);
  * any other detector input, dtype or shape takes the ordinary Gram sweep.  Costs ~19 MB of device memory per slot at 4K.
+ * The sums describe the plane, not a detector: every detector-side call that names the plane as WM_MEM_SLOT_OUT with the embed's
+ * frame count (wm_detect, wm_detect_keys, wm_detect_offsets, wm_detect_tiles, wm_detect_keys_tiles, wm_detect_bits, wm_gram, under
+ * either mask) takes them, a second one after the first as well, until a library write ends the hand-over.  An in-place embed
+ * (out overlaps in_gray) hands over like any other, the stencil reads the snapshot; an embed whose out overlaps a base that is not
+ * its input leaves no hand-over, and neither does a one-frame embed.
  *
  * HAZARD.  The hand-over is only as good as the caller's promise that the output plane is UNMODIFIED between the embed and the
  * detector that names it as WM_MEM_SLOT_OUT.  The library ends a hand-over whenever it writes that plane itself (the slot's
@@ -172,7 +177,11 @@ int wm_embed(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* bas
  * of the pixels it reads that any change of a single pixel alters.  A frame whose digest equals the one the embed left
  * keeps its score; any other frame is redone on the device from the plane as it is (k_gram_redo + k_detect_redo, launched
  * after every checked detect, empty when nothing changed) -- the result is then the ordinary path's.  Scores agree with the
- * ordinary path to the rounding of the Gram sums' grouping (<= 1.2e-7).  wm_set_checked_handover switches this off. */
+ * ordinary path to the rounding of the Gram sums' grouping (<= 1.2e-7).  wm_set_checked_handover switches this off.
+ * The checked hand-over is taken under the ME mask of the DETECTOR; the embed handed its sums over if it ran under the ME mask or,
+ * under either mask, under wm_set_handover.  Naming the plane as WM_MEM_SLOT_OUT counts as naming its pointer -- unless the embed ran
+ * under wm_set_handover: then WM_MEM_SLOT_OUT takes the promised hand-over, unchecked, and only the pointer takes the checked one.  A
+ * promised hand-over that a detector has taken is used up for the checked one too. */
 int wm_detect(wm_ctx* ctx, int mask, const wm_plane* img, float* corr_out, int* status_out, int slot);
 /* the checked hand-over of wm_detect: 1 (default; environment WM_CHECKED_HANDOVER=0 changes the default) on, 0 off -- every
  * wm_detect then takes the ordinary Gram sweep and wm_embed leaves sums behind only under wm_set_handover, as before */
@@ -189,7 +198,9 @@ int wm_checked_handover_counts(wm_ctx* ctx, unsigned long long* trusted, unsigne
  * (WM_MEM_SLOT_OUT), so a host-staged frame crosses the host link once each way.  Synchronous one-image calls on the fused
  * kernels launch both operations back to back and wait once (one launch-to-completion round trip less than two calls;
  * environment WM_FUSED_PAIR=1: both halves in ONE launch, the same bits, measured 1.5-2 us slower at 4K -- DESIGN.md section 8);
- * everything else queues the two operations on the slot.  status_out[frames] (may be NULL): the embed's status. */
+ * everything else queues the two operations on the slot.  status_out[frames] (may be NULL): the embed's status.
+ * The hand-over inside the pair is the pair's own: without wm_set_handover it ends with the pair's detector, and a later detector of
+ * the slot's WM_MEM_SLOT_OUT (or of the plane's pointer) takes the ordinary Gram sweep over the plane as it then is. */
 int wm_embed_detect(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* base, const wm_plane* out, float* a_out,
                     float* corr_out, int* status_out, int slot);
 
@@ -282,6 +293,9 @@ int wm_detect_offsets(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys*
  * wm_band_detect_sums reports; under ME they are taken with m = |e_w| (the 1 / max|e| cancels in every score and is not applied).
  * Tile sums ADD: the score of any union of tiles is formed on the host from the sums of its tiles, and the sums added over all
  * tiles give wm_detect's score of the frame on the sweeps to <= 2e-7 (a regrouping of the same products).
+ * Behind a Gram hand-over (a WM_MEM_SLOT_OUT plane under a promise) the f32 coefficients may differ from the Gram sweep's by one ulp:
+ * a tile's score then agrees with the ordinary path's to <= 2e-7 and each of its sums to <= 1e-5 relative (wm_detect_keys_tiles
+ * likewise); statuses and everything else are the ordinary path's bits.
  * Both arrays are written on the slot's stream and are valid once wm_sync(ctx, slot) has returned; they must stay allocated
  * until then.  The map does not pass through the slot's result records (a 4K frame in 32 x 32 tiles is 8040 scores).
  * status_out[frames] may be NULL; it is delivered by wm_sync like wm_detect's, and `frames` results count against the slot's

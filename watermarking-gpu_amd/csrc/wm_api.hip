@@ -1554,7 +1554,13 @@ int wm_embed_detect(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_pla
     // its output's lag sums over whether or not wm_set_handover is on (the detector's Gram sweep is not run)
     wm_plane slot_plane = *out;
     slot_plane.data = nullptr; slot_plane.mem = WM_MEM_SLOT_OUT;
-    struct PairHo { wm_ctx* c; explicit PairHo(wm_ctx* c_) : c(c_) { c->pair_handover = 1; } ~PairHo() { c->pair_handover = 0; } } pair_ho(ctx);
+    // the embed's promise is the pair's own (its detector reads the plane by construction): it ends with the pair.  Without
+    // wm_set_handover the caller has promised nothing about the plane afterwards, so no later WM_MEM_SLOT_OUT detector may take the sums
+    struct PairHo {
+        wm_ctx* c; Slot& s;
+        PairHo(wm_ctx* c_, Slot& s_) : c(c_), s(s_) { c->pair_handover = 1; }
+        ~PairHo() { c->pair_handover = 0; if (!c->handover && s.ho.promised) { s.ho.promised = false; s.ho.used = true; } }
+    } pair_ho(ctx, s);
     if (!sync_after) {
         // a slot in flight: the two operations queue behind each other, wm_sync delivers both
         if ((rc = wm_embed(ctx, mask, in_gray, base, out, a_out, status_out, slot)) < 0) return rc;
