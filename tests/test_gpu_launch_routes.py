@@ -36,7 +36,7 @@ ROUTES = [("overlap", 272, "f32", 0), ("overlap", 272, "u8", 0), ("split", 267, 
 WINDOWS = [("ME", 3), ("NVF", 3), ("NVF", 5), ("NVF", 7), ("NVF", 9)]
 FRAMES = [1, 5]
 DETECT_CALLS = ["detect", "detect_keys", "detect_offsets", "detect_tiles", "detect_keys_tiles", "compute_mask"]
-EMBED_CALLS = ["embed", "embed_signs", "embed_keys"]
+EMBED_CALLS = ["embed", "embed_signs", "embed_keys", "embed_signs_multi"]
 BASES = ["in", "grey"]
 NKEYS, NKEYS_EMBED = 3, 5   # one more than a key group of k_detect_keys (2) / k_embed_keys (4): a full group and a short one; W is the last
 KEY_SEED = 8800
@@ -83,6 +83,7 @@ class Setting:
         npdt = np.uint8 if self.dtype == "u8" else np.float32
         # the key plane is larger than the image; W is its window at (0, 0)
         self.G = wm.lib().wm_detect_offsets_group()
+        self.KS = wm.lib().wm_embed_signs_group() + 1   # copies of wm_embed_signs_multi: a full copy group and a short one
         self.key = synth_watermark(R + 1, Cc + self.G + 4, KEY_SEED)
         self.W = np.ascontiguousarray(self.key[:R, :Cc])
         self.xs = np.stack([synth_frame(R, Cc, frame=3 + f, dtype=npdt) for f in range(F)])
@@ -91,7 +92,7 @@ class Setting:
         # the route this setting is named after is the one its planes take: the width rule of csrc/wm_march.hpp (overlapped strips
         # for multiples of 4, the split from 264 columns on) and, where the route is not generic anyway, the vector-path rule
         assert {"overlap": Cc % 4 == 0, "split": Cc % 4 != 0 and Cc >= 264, "generic": Cc % 4 != 0 and Cc < 264, "unaligned": True}[self.route]
-        for t in (self.xv, self.gv, self.empty_like_plane(), self.empty_like_plane(F * NKEYS_EMBED)):
+        for t in (self.xv, self.gv, self.empty_like_plane(), self.empty_like_plane(F * NKEYS_EMBED), self.empty_like_plane(F * self.KS)):
             if self.route != "generic":
                 assert self.vector_path(t) == (self.route != "unaligned"), (self.route, t.stride(), t.data_ptr())
         self.eng = wm.Watermark(R, Cc, self.W, self.p, 40.0, nslots=2, max_frames=F)
@@ -310,9 +311,26 @@ def check_embed_keys(s, base):
     assert not bits_equal(copies[:, 0], y)
 
 
+def check_embed_signs_multi(s, base):
+    """one copy more than a copy group; the last copy's table is all +1: its planes and the call's strengths are wm_embed's, bit for
+    bit (tests/test_gpu_signs_multi.py); the first copy's is all -1: its planes differ"""
+    K = s.KS
+    ny, nx = TM.tiles_shape(R, s.cols, TH, TW)
+    signs = np.ones((s.F, K, ny, nx), np.int8)
+    signs[:, 0] = -1
+    ov = s.empty_like_plane(s.F * K)
+    a, st = np.full(s.F, np.nan, np.float32), np.full(s.F, -5, np.int32)
+    s.torch.cuda.synchronize()
+    s.eng.embed_signs_multi_async(s.xv, s.xv if base == "in" else s.gv, ov, TH, TW, K, signs, s.mt, s.wm.WM_SLOT_SYNC, a, st)
+    y, ar = s.embed(base)
+    copies = ov.cpu().numpy().reshape(s.F, K, R, s.cols)
+    assert (st == 0).all() and bits_equal(copies[:, K - 1], y) and bits_equal(a, ar)
+    assert not bits_equal(copies[:, 0], y)
+
+
 CHECKS = {"detect": check_detect, "detect_keys": check_detect_keys, "detect_offsets": check_detect_offsets, "detect_tiles": check_detect_tiles,
           "detect_keys_tiles": check_detect_keys_tiles, "compute_mask": check_compute_mask, "embed": check_embed, "embed_signs": check_embed_signs,
-          "embed_keys": check_embed_keys}
+          "embed_keys": check_embed_keys, "embed_signs_multi": check_embed_signs_multi}
 
 
 @pytest.mark.parametrize("case", CASES, ids=case_id)
@@ -331,5 +349,5 @@ def test_the_case_list_is_complete():
     """every call x route x window x frame count is a case (the embed family with both bases), none twice, and REFUSED names
     cases of the list only"""
     ids = [case_id(c) for c in CASES]
-    assert len(ids) == len(set(ids)) == len(SETTINGS) * (len(DETECT_CALLS) + len(EMBED_CALLS) * len(BASES)) == 840
+    assert len(ids) == len(set(ids)) == len(SETTINGS) * (len(DETECT_CALLS) + len(EMBED_CALLS) * len(BASES)) == 980
     assert set(REFUSED) <= set(ids)

@@ -844,17 +844,27 @@ int refuse_band(wm_ctx* ctx, const char* who)
     return ctx->band_hi > 0 ? fail(ctx, WM_ERR_BAD_ARG, std::string(who) + ": not in band mode") : WM_OK;
 }
 
-// what the embed-side launchers take for a mask type: the kernels' mask index, the window's pad (ME: p == 3, check_mask), and the Gram
-// sweep's solve (coefficients and status per frame), which only ME has; the detectors solve under either mask and always pass the slot's
-struct MaskRoute { int mask, pad; const float* coef; const int* status; };
-MaskRoute mask_route(const wm_ctx* ctx, const Slot& s, int mask)
+// ---- the launch records (wm_kernels.hpp): a call fills its Sweep once, behind its geometry and its resolved input plane, and hands
+// it to every launch it makes.  The mask type is the kernels' mask index, the window's pad is p / 2 (ME: p == 3, check_mask).
+// detect_sweep: the detector side, which solves under either mask and reads the slot's coefficients and status.  mask_route: the
+// embed side (embeds, stats, wm_compute_mask), where only ME has a solve: under NVF the record carries null for both
+Sweep detect_sweep(const wm_ctx* ctx, const Slot& s, const LaunchGeom& lg, int frames, int mask, const PlaneDesc& xd)
 {
-    return mask == WM_MASK_ME ? MaskRoute{0, 1, s.d_coef, s.d_status} : MaskRoute{1, ctx->p / 2, nullptr, nullptr};
+    return Sweep{s.stream, lg, frames, mask, ctx->p / 2, xd, s.d_coef, s.d_status};
+}
+Sweep mask_route(const wm_ctx* ctx, const Slot& s, const LaunchGeom& lg, int frames, int mask, const PlaneDesc& xd)
+{
+    Sweep sw = detect_sweep(ctx, s, lg, frames, mask, xd);
+    if (mask != WM_MASK_ME) { sw.coef = nullptr; sw.status = nullptr; }
+    return sw;
 }
 
 // may the sweeps address the context's W (or a key plane of its shape) as a buffer with 32-bit offsets?  (W is a dense f32
 // plane: 4-byte aligned rows suffice, vec_ok)
 int aligned_w_of(const wm_ctx* ctx) { return fits_32bit(ctx->rows, ctx->cols, WM_F32) ? 1 : 0; }
+// the key side of a sweep: the context's own W (a bank of one), or a bank whose planes have W's shape
+KeyBank own_w(const wm_ctx* ctx) { return KeyBank{ctx->w->d_w, 0, 1, aligned_w_of(ctx)}; }
+KeyBank bank_of(const wm_ctx* ctx, const wm_keys* keys) { return KeyBank{keys->d, (long long)ctx->rows * ctx->cols, keys->nkeys, aligned_w_of(ctx)}; }
 
 // room for `records` more result records on the slot before its next wm_sync; noun: what multiplies the frames of a call with
 // several records per frame ("keys", "offsets"), nullptr for one record per frame
@@ -880,32 +890,28 @@ int launch_check(wm_ctx* ctx, Slot& s)
 
 // ---- the sweeps' launches with the slot's scratch arrays filled in.  kid: the kernel the profile counts the launch as, K_NONE
 // for a launch it leaves out
-void sweep_gram(wm_ctx* ctx, Slot& s, int kid, const LaunchGeom& lg, int frames, const PlaneDesc& xd, double* totals = nullptr, const int* redo = nullptr)
+void sweep_gram(wm_ctx* ctx, Slot& s, int kid, const Sweep& sw, double* totals = nullptr, const int* redo = nullptr)
 {
     ProfScope ps(ctx, kid, s.stream);
-    launch_gram(s.stream, lg, frames, xd, s.d_gram, s.d_gramb, s.d_ticket, s.d_coef, s.d_status, totals ? totals : s.d_gramtot, redo);
+    launch_gram(sw, s.d_gram, s.d_gramb, s.d_ticket, s.d_coef, s.d_status, totals ? totals : s.d_gramtot, redo);
 }
-// the stats sweep of the context's W (ME: behind the Gram sweep's solve); its fold tail leaves the strength records in `res`, the
-// embed scalars in s.d_scal and the raw totals in s.d_raw[0 .. frames)
-void sweep_stats(wm_ctx* ctx, Slot& s, bool profiled, const LaunchGeom& lg, int frames, int mask, const PlaneDesc& xd, OpResult* res)
+// the stats sweep of the context's W (sw: mask_route's; ME: behind the Gram sweep's solve); its fold tail leaves the strength records
+// in `res`, the embed scalars in s.d_scal and the raw totals in s.d_raw[0 .. frames)
+void sweep_stats(wm_ctx* ctx, Slot& s, bool profiled, const Sweep& sw, OpResult* res)
 {
-    ProfScope ps(ctx, !profiled ? K_NONE : mask == WM_MASK_ME ? K_ME_STATS : K_NVF_STATS, s.stream);
+    ProfScope ps(ctx, !profiled ? K_NONE : sw.mask == WM_MASK_ME ? K_ME_STATS : K_NVF_STATS, s.stream);
     unsigned* ticket = s.d_ticket + ctx->max_frames * TKS;
-    if (mask == WM_MASK_ME)
-        launch_me_stats(s.stream, lg, frames, xd, ctx->w->d_w, aligned_w_of(ctx), s.d_coef, s.d_status, s.d_pmax, s.d_pss, ticket, strip_tickets(ctx, s, 0), s.d_smax,
-                        s.d_sss, ctx->sF, sqrt_n(ctx), s.d_scal, res, s.d_raw);
+    if (sw.mask == WM_MASK_ME)
+        launch_me_stats(sw, own_w(ctx), s.d_pmax, s.d_pss, ticket, strip_tickets(ctx, s, 0), s.d_smax, s.d_sss, ctx->sF, sqrt_n(ctx), s.d_scal, res, s.d_raw);
     else
-        launch_nvf_stats(s.stream, lg, frames, xd, ctx->w->d_w, aligned_w_of(ctx), ctx->p / 2, s.d_pss, ticket, strip_tickets(ctx, s, 0), s.d_sss, ctx->sF, sqrt_n(ctx),
-                         s.d_scal, res, s.d_raw);
+        launch_nvf_stats(sw, own_w(ctx), s.d_pss, ticket, strip_tickets(ctx, s, 0), s.d_sss, ctx->sF, sqrt_n(ctx), s.d_scal, res, s.d_raw);
 }
-// the detect sweep against the context's W; its fold tail leaves the scores in `res` and the raw sums in s.d_raw[max_frames ..)
-// (dc, mode: the checking detector of the checked hand-over and its redo launch, wm_kernels.hpp)
-void sweep_detect(wm_ctx* ctx, Slot& s, int kid, const LaunchGeom& lg, int frames, int mask, const PlaneDesc& xd, OpResult* res, const DigCheck* dc = nullptr,
-                  int mode = 0)
+// the detect sweep against the context's W (sw: detect_sweep's); its fold tail leaves the scores in `res` and the raw sums in
+// s.d_raw[max_frames ..)  (dc, mode: the checking detector of the checked hand-over and its redo launch, wm_kernels.hpp)
+void sweep_detect(wm_ctx* ctx, Slot& s, int kid, const Sweep& sw, OpResult* res, const DigCheck* dc = nullptr, int mode = 0)
 {
     ProfScope ps(ctx, kid, s.stream);
-    launch_detect(s.stream, lg, frames, mask, ctx->p / 2, xd, ctx->w->d_w, aligned_w_of(ctx), s.d_coef, s.d_status, s.d_pcorr, s.d_ticket + 2 * ctx->max_frames * TKS,
-                  strip_tickets(ctx, s, 1), s.d_scorr, res, s.d_raw + ctx->max_frames, dc, mode);
+    launch_detect(sw, own_w(ctx), s.d_pcorr, s.d_ticket + 2 * ctx->max_frames * TKS, strip_tickets(ctx, s, 1), s.d_scorr, res, s.d_raw + ctx->max_frames, dc, mode);
 }
 
 // remember where to deliver the result records of one op (the kernels write them to mapped host memory): frames * per_frame
@@ -1187,15 +1193,20 @@ static int prep_input(wm_ctx* ctx, Slot& s, const wm_plane* in, PlaneDesc* xd)
 }
 
 // the front half of a call that sweeps one grey input plane: the plane's checks, room for its result records (per_frame of them
-// for each frame, 0: the call queues none), the context's device, the plane staged / resolved and the launch geometry
-static int open_input(wm_ctx* ctx, Slot& s, const wm_plane* img, const char* what, int mask, long long per_frame, const char* noun, PlaneDesc* xd, LaunchGeom* lg)
+// for each frame, 0: the call queues none), the context's device, the plane staged / resolved, the launch geometry, and from
+// them the call's sweep record (detect_sweep's)
+static int open_input(wm_ctx* ctx, Slot& s, const wm_plane* img, const char* what, int mask, long long per_frame, const char* noun, Sweep* sw)
 {
     int rc;
+    PlaneDesc xd;
+    LaunchGeom lg;
     if ((rc = check_plane(ctx, img, 0, false, what, true)) != WM_OK) return rc;
     if ((rc = check_res_room(ctx, s, img->frames * per_frame, noun)) != WM_OK) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if ((rc = prep_input(ctx, s, img, xd)) != WM_OK) return rc;
-    return geom_checked(ctx, img->frames, mask, lg);
+    if ((rc = prep_input(ctx, s, img, &xd)) != WM_OK) return rc;
+    if ((rc = geom_checked(ctx, img->frames, mask, &lg)) != WM_OK) return rc;
+    *sw = detect_sweep(ctx, s, lg, img->frames, mask, xd);
+    return WM_OK;
 }
 
 // the base plane of an embed, resolved like the input; a host base that IS the input plane (`xd`: prep_input's result) is not
@@ -1217,7 +1228,7 @@ static int prep_base(wm_ctx* ctx, Slot& s, const wm_plane* in_gray, const wm_pla
 }
 
 // ---- the embed frame: what the embed calls share around their sweeps.  wm_embed and wm_embed_signs take all of it;
-// wm_embed_keys, with K outputs per input frame, takes the dtype rules and stages its planes itself
+// wm_embed_keys and wm_embed_signs_multi, with K outputs per input frame, take the dtype rules and the K-output frame below
 // (xd, bd, od: the RESOLVED planes, what the kernels address; st_out: the staging layout of a host output, copied out by stage_out)
 struct EmbedCall { int frames; PlaneDesc xd, bd, od; Staged st_out; bool inplace; };
 static int check_embed_dtypes(wm_ctx* ctx, const wm_plane* in_gray, const wm_plane* base, const wm_plane* out)
@@ -1294,6 +1305,37 @@ static int embed_close(wm_ctx* ctx, Slot& s, const wm_plane* out, const EmbedCal
     if (out->mem == WM_MEM_HOST && (rc = stage_out(ctx, s, out, s.st_out, c.st_out)) != WM_OK) return rc;
     embed_queue_result(s, out, c, a_out, status_out);
     return slot == WM_SLOT_SYNC && !ctx->pair_mode ? do_sync(ctx, s) : WM_OK;
+}
+
+// ---- the K-output frame: wm_embed_keys and wm_embed_signs_multi write K device planes per input frame (`who`: the caller's name;
+// `count`: what K counts, "nkeys" / "ncopies").  They check in_gray, base and the memory kind of `out` themselves, then:
+// out: frames * K planes (more than max_frames is fine: the sweeps' scratch is per input frame), each a plane check_plane admits
+static int check_out_copies(wm_ctx* ctx, const char* who, const char* count, const wm_plane* out, int frames, int K)
+{
+    if ((long long)out->frames != (long long)frames * K)
+        return fail(ctx, WM_ERR_BAD_ARG, std::string(who) + ": out->frames must be in_gray->frames * " + count + " = " + std::to_string((long long)frames * K));
+    wm_plane one = *out;
+    one.frames = 1;
+    const int rc = check_plane(ctx, &one, 1, true, "out");
+    if (rc != WM_OK) return rc;
+    if (out->frames > 1 && out->frame_stride < (int64_t)(out->channels - 1) * (out->channels > 1 ? out->channel_stride : 0) + (int64_t)out->rows * out->pitch)
+        return fail(ctx, WM_ERR_BAD_ARG, "out: frame_stride too small (frames overlap)");
+    return WM_OK;
+}
+// the planes staged / resolved into c (embed_stage's part for a device `out` of K planes per frame).  K outputs of one input: an
+// in-place call has no meaning (judged on the RESOLVED planes, as wm_embed judges them).  No hand-over of its own, and
+// WM_MEM_SLOT_OUT keeps naming the last wm_embed output; a hand-over whose plane the copies overwrite ends here
+static int copies_stage(wm_ctx* ctx, Slot& s, const char* who, const wm_plane* in_gray, const wm_plane* base, const wm_plane* out, int K, EmbedCall* c)
+{
+    int rc;
+    const int frames = c->frames = in_gray->frames;
+    if ((rc = prep_input(ctx, s, in_gray, &c->xd)) != WM_OK) return rc;
+    if ((rc = prep_base(ctx, s, in_gray, base, c->xd, &c->bd)) != WM_OK) return rc;
+    c->od = desc_device(out);
+    if (descs_overlap(c->xd, c->od, ctx->rows, ctx->cols, frames, frames * K) || descs_overlap(c->bd, c->od, ctx->rows, ctx->cols, frames, frames * K))
+        return fail(ctx, WM_ERR_BAD_ARG, std::string(who) + ": out overlaps in_gray or base");
+    invalidate_handovers(ctx, c->od, frames * K);
+    return WM_OK;
 }
 
 // a fused embed issued output stores over the call's own input or base and their completion was not observed
@@ -1378,7 +1420,7 @@ int wm_embed(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* bas
 
     LaunchGeom lg;
     if ((rc = geom_checked(ctx, frames, mask, &lg)) != WM_OK) return rc;
-    const MaskRoute mr = mask_route(ctx, s, mask);
+    const Sweep sw = mask_route(ctx, s, lg, frames, mask, xd);
     OpResult* res = s.d_res + s.res_used;
     // Gram hand-over (wm_set_handover): k_embed also leaves the tile-internal lag sums of y for a detector that reads this
     // output as WM_MEM_SLOT_OUT (grey f32 planes on the aligned path; launch_embed says whether it applied)
@@ -1392,11 +1434,11 @@ int wm_embed(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* bas
     const HandOver* hop = want_ho && ho_ready(s) && out->channels == 1 && ho.stride <= ho_stride_max(ctx) &&
                                   !descs_overlap(bd, od, ctx->rows, ctx->cols, frames) ? &ho : nullptr;
     bool handed = false;
-    if (mask == WM_MASK_ME) sweep_gram(ctx, s, K_GRAM, lg, frames, xd);
-    sweep_stats(ctx, s, true, lg, frames, mask, xd, res);
+    if (mask == WM_MASK_ME) sweep_gram(ctx, s, K_GRAM, sw);
+    sweep_stats(ctx, s, true, sw, res);
     {
         ProfScope ps(ctx, K_EMBED, s.stream);
-        handed = launch_embed(s.stream, lg, frames, mr.mask, mr.pad, xd, ctx->w->d_w, aligned_w_of(ctx), bd, od, mr.coef, mr.status, s.d_scal, hop);
+        handed = launch_embed(sw, own_w(ctx), EmbedPlanes{bd, od, s.d_scal}, hop);
     }
     if (handed) { s.ho.valid = true; s.ho.promised = promised; s.ho.used = false; s.ho.lg = lg; s.ho.frames = frames; s.ho.stride = ho.stride; }
     return embed_close(ctx, s, out, c, a_out, status_out, slot);
@@ -1404,30 +1446,32 @@ int wm_embed(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* bas
 
 // k_gram_ho over the sums the slot's last embed left (the border blocks are this short launch's longest: as many of them as the
 // record array holds, not the batched sweep's 16)
-static void gram_from_handover(wm_ctx* ctx, Slot& s, int frames, const PlaneDesc& xd)
+static void gram_from_handover(wm_ctx* ctx, Slot& s, const Sweep& sw)
 {
-    LaunchGeom l2 = s.ho.lg;
-    l2.nbb = border_blocks(ctx->rows, ctx->cols);
-    launch_gram_ho(s.stream, l2, frames, xd, handover_of(ctx, s, s.ho.stride), s.d_gramb, s.d_ticket, s.d_coef, s.d_status, s.d_gramtot);
+    Sweep h = sw;  // (the plane as the call resolved it, on the geometry of the embed that left the sums)
+    h.lg = s.ho.lg;
+    h.lg.nbb = border_blocks(ctx->rows, ctx->cols);
+    launch_gram_ho(h, handover_of(ctx, s, s.ho.stride), s.d_gramb, s.d_ticket, s.d_coef, s.d_status, s.d_gramtot);
 }
 
 // does this detector input take the checked hand-over (wm.h wm_detect)?  The plane the slot's last embed wrote -- the same
 // descriptor --, sums nobody has used yet, and the checking detector's path (f32, ME, overlapped aligned strips)
-static bool checked_handover_applies(const wm_ctx* ctx, const Slot& s, const LaunchGeom& lg, int frames, int mask, const PlaneDesc& xd)
+static bool checked_handover_applies(const wm_ctx* ctx, const Slot& s, const Sweep& sw)
 {
-    const PlaneDesc& o = s.last_out;
-    return ctx->checked_handover && s.ho.valid && !s.ho.used && ho_ready(s) && ctx->band_hi == 0 && s.ho.frames == frames &&
-           s.last_out_frames == frames && xd.p == o.p && xd.pitch == o.pitch && xd.fstride == o.fstride && xd.dtype == o.dtype &&
-           s.last_out_dtype == WM_F32 && xd.channels == 1 && detect_checkable(lg, mask, ctx->p / 2, xd, aligned_w_of(ctx));
+    const PlaneDesc &o = s.last_out, &xd = sw.x;
+    return ctx->checked_handover && s.ho.valid && !s.ho.used && ho_ready(s) && ctx->band_hi == 0 && s.ho.frames == sw.frames &&
+           s.last_out_frames == sw.frames && xd.p == o.p && xd.pitch == o.pitch && xd.fstride == o.fstride && xd.dtype == o.dtype &&
+           s.last_out_dtype == WM_F32 && xd.channels == 1 && detect_checkable(sw, aligned_w_of(ctx));
 }
 
 // the Gram sweep of a detector-side call: k_gram over the plane -- or, when the plane is the slot's last embed output and that
 // embed left its tile-internal lag sums (wm_set_handover), only the seams, the border frame and the solve (k_gram_ho)
-static int gram_sweep(wm_ctx* ctx, Slot& s, const LaunchGeom& lg, int frames, const PlaneDesc& xd, const wm_plane* img)
+static int gram_sweep(wm_ctx* ctx, Slot& s, const Sweep& sw, const wm_plane* img)
 {
+    const int frames = sw.frames;
     if (img->mem == WM_MEM_SLOT_OUT && s.ho.valid && s.ho.promised && s.ho.frames == frames && ho_ready(s) && ctx->band_hi == 0) {
         s.ho.used = true;
-        { ProfScope ps(ctx, K_GRAM_HO, s.stream); gram_from_handover(ctx, s, frames, xd); }
+        { ProfScope ps(ctx, K_GRAM_HO, s.stream); gram_from_handover(ctx, s, sw); }
         if (!ctx->handover_verify) return WM_OK;
         // WM_HANDOVER_VERIFY=1 (a debug mode, it synchronises): the hand-over rests on the caller's promise that the plane
         // behind WM_MEM_SLOT_OUT is still what the embed wrote.  Run the ordinary Gram sweep over the plane as it is NOW and
@@ -1435,7 +1479,7 @@ static int gram_sweep(wm_ctx* ctx, Slot& s, const LaunchGeom& lg, int frames, co
         // (<= 1e-14 relative, tests/test_gpu_handover.py) unless a single pixel changed
         std::vector<double> t_ho((size_t)frames * NGRAM), t_now((size_t)frames * NGRAM);
         HIPCHK(ctx, hipMemcpyAsync(t_ho.data(), s.d_gramtot, t_ho.size() * sizeof(double), hipMemcpyDeviceToHost, s.stream));
-        sweep_gram(ctx, s, K_NONE, lg, frames, xd);
+        sweep_gram(ctx, s, K_NONE, sw);
         HIPCHK(ctx, hipMemcpyAsync(t_now.data(), s.d_gramtot, t_now.size() * sizeof(double), hipMemcpyDeviceToHost, s.stream));
         HIPCHK(ctx, hipStreamSynchronize(s.stream));
         for (int f = 0; f < frames; ++f)
@@ -1452,7 +1496,7 @@ static int gram_sweep(wm_ctx* ctx, Slot& s, const LaunchGeom& lg, int frames, co
             }
         return WM_OK;
     }
-    sweep_gram(ctx, s, K_GRAM, lg, frames, xd);
+    sweep_gram(ctx, s, K_GRAM, sw);
     return WM_OK;
 }
 
@@ -1523,20 +1567,21 @@ int wm_detect(wm_ctx* ctx, int mask, const wm_plane* img, float* corr_out, int* 
     guard.reset();
     LaunchGeom lg;
     if ((rc = geom_checked(ctx, frames, mask, &lg)) != WM_OK) return rc;
+    const Sweep sw = detect_sweep(ctx, s, lg, frames, mask, xd);
     OpResult* res = s.d_res + s.res_used;
     // (a WM_MEM_SLOT_OUT plane under wm_set_handover keeps the promised hand-over of gram_sweep)
-    if (!(img->mem == WM_MEM_SLOT_OUT && s.ho.promised) && checked_handover_applies(ctx, s, lg, frames, mask, xd)) {
+    if (!(img->mem == WM_MEM_SLOT_OUT && s.ho.promised) && checked_handover_applies(ctx, s, sw)) {
         // checked hand-over: the Gram matrix from the embed's sums, the detector checks the plane against the embed's digest, and
         // the frames it does not trust are redone by the ordinary sweeps (predicated on the device: empty launches otherwise)
         s.ho.used = true;
         const DigCheck dc{s.d_pdig, s.d_sdig, handover_of(ctx, s, s.ho.stride).fdig, s.d_redo, s.d_hocnt};
-        { ProfScope ps(ctx, K_GRAM_HO_CHECKED, s.stream); gram_from_handover(ctx, s, frames, xd); }
-        sweep_detect(ctx, s, K_DETECT, lg, frames, mask, xd, res, &dc, 1);
-        sweep_gram(ctx, s, K_GRAM_REDO, lg, frames, xd, nullptr, s.d_redo);
-        sweep_detect(ctx, s, K_DETECT_REDO, lg, frames, mask, xd, res, &dc, 2);
+        { ProfScope ps(ctx, K_GRAM_HO_CHECKED, s.stream); gram_from_handover(ctx, s, sw); }
+        sweep_detect(ctx, s, K_DETECT, sw, res, &dc, 1);
+        sweep_gram(ctx, s, K_GRAM_REDO, sw, nullptr, s.d_redo);
+        sweep_detect(ctx, s, K_DETECT_REDO, sw, res, &dc, 2);
     } else {
-        if ((rc = gram_sweep(ctx, s, lg, frames, xd, img)) != WM_OK) return rc;
-        sweep_detect(ctx, s, K_DETECT, lg, frames, mask, xd, res);
+        if ((rc = gram_sweep(ctx, s, sw, img)) != WM_OK) return rc;
+        sweep_detect(ctx, s, K_DETECT, sw, res);
     }
     return finish_call(ctx, s, slot, frames, 1, false, corr_out, status_out);
 }
@@ -1676,7 +1721,7 @@ static int check_bank(wm_ctx* ctx, const wm_keys* keys, const char* who, bool ex
 
 // detectWatermark of every frame with `count` scores per frame (wm_detect_keys: the keys of a bank; wm_detect_offsets: the windows
 // of one key): wm_detect's input, slot and Gram handling on the sweeps, the records [frames][count] delivered by wm_sync.
-// launch(s, lg, frames, xd, part, rstride, res): the sweep behind the solve, != 0 when its geometry does not fit
+// launch(sw, part, rstride, res): the sweep behind the solve, != 0 when its geometry does not fit
 extern "C++" {  // (a template cannot have C linkage)
 template <class Launch>
 static int detect_bank(wm_ctx* ctx, int mask, const wm_plane* img, long long count, const char* noun, const char* who, int kid, float* corr_out, int* status_out,
@@ -1685,19 +1730,18 @@ static int detect_bank(wm_ctx* ctx, int mask, const wm_plane* img, long long cou
     int rc = check_slot(ctx, slot);
     if (rc != WM_OK) return rc;
     Slot& s = slot_of(ctx, slot);
-    PlaneDesc xd;
-    LaunchGeom lg;
-    if ((rc = open_input(ctx, s, img, "image", mask, count, noun, &xd, &lg)) != WM_OK) return rc;
+    Sweep sw;
+    if ((rc = open_input(ctx, s, img, "image", mask, count, noun, &sw)) != WM_OK) return rc;
     const int frames = img->frames;
     // partial records: [frames][count][rstride][2] + [frames][rstride] (one scratch for both calls: one stream, in order)
     const int rstride = std::max(ctx->max_nblk, ctx->max_nrec);
     const size_t need = (size_t)frames * (2 * (size_t)count + 1) * rstride * sizeof(double);
     if ((rc = ensure(ctx, &s.keys_part, &s.keys_part_bytes, need)) != WM_OK) return rc;
     // the image side is wm_detect's: the Gram sweep (or the hand-over of the slot's last embed) and the solve
-    if ((rc = gram_sweep(ctx, s, lg, frames, xd, img)) != WM_OK) return rc;
+    if ((rc = gram_sweep(ctx, s, sw, img)) != WM_OK) return rc;
     {
         ProfScope ps(ctx, kid, s.stream);
-        if (launch(s, lg, frames, xd, (double*)s.keys_part, rstride, s.d_res + s.res_used) != 0)
+        if (launch(sw, (double*)s.keys_part, rstride, s.d_res + s.res_used) != 0)
             return fail(ctx, WM_ERR_RUNTIME, std::string(who) + ": geometry exceeds the record arrays");
     }
     return finish_call(ctx, s, slot, frames, (int)count, false, corr_out, status_out);
@@ -1713,10 +1757,7 @@ int wm_detect_keys(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* ke
     if ((rc = check_bank(ctx, keys, "wm_detect_keys", true)) != WM_OK) return rc;
     if ((rc = refuse_band(ctx, "wm_detect_keys")) != WM_OK) return rc;
     return detect_bank(ctx, mask, img, keys->nkeys, "keys", "wm_detect_keys", K_DETECT_KEYS, corr_out, status_out, slot,
-                       [&](Slot& s, const LaunchGeom& lg, int frames, const PlaneDesc& xd, double* part, int rstride, OpResult* res) {
-                           return launch_detect_keys(s.stream, lg, frames, mask, ctx->p / 2, xd, keys->d, (long long)ctx->rows * ctx->cols, keys->nkeys,
-                                                     aligned_w_of(ctx), s.d_coef, s.d_status, part, rstride, res);
-                       });
+                       [&](const Sweep& sw, double* part, int rstride, OpResult* res) { return launch_detect_keys(sw, bank_of(ctx, keys), part, rstride, res); });
 }
 
 // every window of the rectangle lies inside the key plane (no device needed: wm_detect_offsets' own check)
@@ -1747,12 +1788,10 @@ int wm_detect_offsets(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys*
     if ((rc = refuse_band(ctx, "wm_detect_offsets")) != WM_OK) return rc;
     // NOT aligned_w_of: the buffer descriptor of a window spans rows of the KEY plane's pitch, so that plane's extent decides the
     // 32-bit offsets
-    const int aligned_key = fits_32bit(keys->rows, keys->cols, WM_F32) ? 1 : 0;
-    const float* key = keys->d + (size_t)k * keys->rows * keys->cols;
+    const KeyBank key{keys->d + (size_t)k * keys->rows * keys->cols, 0, 1, fits_32bit(keys->rows, keys->cols, WM_F32) ? 1 : 0};
     return detect_bank(ctx, mask, img, (long long)ny * nx, "offsets", "wm_detect_offsets", K_DETECT_OFFSETS, corr_out, status_out, slot,
-                       [&](Slot& s, const LaunchGeom& lg, int frames, const PlaneDesc& xd, double* part, int rstride, OpResult* res) {
-                           return launch_detect_offsets(s.stream, lg, frames, mask, ctx->p / 2, xd, key, keys->cols, oy0, ox0, ny, nx, aligned_key, s.d_coef,
-                                                        s.d_status, part, rstride, res);
+                       [&](const Sweep& sw, double* part, int rstride, OpResult* res) {
+                           return launch_detect_offsets(sw, key, keys->cols, oy0, ox0, ny, nx, part, rstride, res);
                        });
 }
 
@@ -1768,9 +1807,10 @@ int wm_tiles_shape(int rows, int cols, int tile_rows, int tile_cols, int* ny, in
 }
 
 // ---- the tile calls' front: the tile grid of the engine's plane, and a payload's table over it
-static int tiles_checked(wm_ctx* ctx, const char* who, int tile_rows, int tile_cols, int* ny, int* nx)
+static int tiles_checked(wm_ctx* ctx, const char* who, int tile_rows, int tile_cols, TileShape* ts)
 {
-    if (wm_tiles_shape(ctx->rows, ctx->cols, tile_rows, tile_cols, ny, nx) == WM_OK) return WM_OK;
+    ts->th = tile_rows; ts->tw = tile_cols;
+    if (wm_tiles_shape(ctx->rows, ctx->cols, tile_rows, tile_cols, &ts->ny, &ts->nx) == WM_OK) return WM_OK;
     return fail(ctx, WM_ERR_BAD_ARG, std::string(who) + ": tile shape " + std::to_string(tile_rows) + "x" + std::to_string(tile_cols) +
                                          " (rows: a multiple of 8, >= 32; columns: a multiple of 4, >= 32)");
 }
@@ -1790,22 +1830,22 @@ int wm_detect_tiles(wm_ctx* ctx, int mask, const wm_plane* img, int tile_rows, i
 {
     if (!ctx) return WM_ERR_BAD_ARG;
     if (!img || !map_dev) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_tiles: null img or map_dev");
-    int ny = 0, nx = 0, rc;
-    if ((rc = tiles_checked(ctx, "wm_detect_tiles", tile_rows, tile_cols, &ny, &nx)) != WM_OK) return rc;
+    TileShape ts;
+    int rc;
+    if ((rc = tiles_checked(ctx, "wm_detect_tiles", tile_rows, tile_cols, &ts)) != WM_OK) return rc;
     if ((rc = check_mask(ctx, mask)) != WM_OK) return rc;
     if ((rc = refuse_band(ctx, "wm_detect_tiles")) != WM_OK) return rc;
     if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
     Slot& s = slot_of(ctx, slot);
-    PlaneDesc xd;
-    LaunchGeom lg;
-    if ((rc = open_input(ctx, s, img, "image", mask, 1, nullptr, &xd, &lg)) != WM_OK) return rc;
+    Sweep sw;
+    if ((rc = open_input(ctx, s, img, "image", mask, 1, nullptr, &sw)) != WM_OK) return rc;
     const int frames = img->frames;
-    const TilesPlan pl = tiles_plan(lg, frames, mask, ctx->p / 2, xd, aligned_w_of(ctx), tile_rows, tile_cols, ny, nx);
+    const TilesPlan pl = tiles_plan(sw, aligned_w_of(ctx), ts);
     if ((rc = ensure(ctx, &s.tiles_rec, &s.tiles_rec_bytes, pl.rec_bytes)) != WM_OK) return rc;
     OpResult* res = s.d_res + s.res_used;
     // the image side is wm_detect's: the Gram sweep (or the hand-over of the slot's last embed) and the solve
-    if ((rc = gram_sweep(ctx, s, lg, frames, xd, img)) != WM_OK) return rc;
-    { ProfScope ps(ctx, K_DETECT_TILES, s.stream); launch_detect_tiles(s.stream, pl, frames, mask, ctx->p / 2, xd, ctx->w->d_w, s.d_coef, s.d_status, (float*)s.tiles_rec); }
+    if ((rc = gram_sweep(ctx, s, sw, img)) != WM_OK) return rc;
+    { ProfScope ps(ctx, K_DETECT_TILES, s.stream); launch_detect_tiles(sw, pl, own_w(ctx), (float*)s.tiles_rec); }
     { ProfScope ps(ctx, K_TILES_FOLD, s.stream); launch_tiles_fold(s.stream, pl, frames, (const float*)s.tiles_rec, s.d_status, map_dev, sums_dev, res); }
     return finish_call(ctx, s, slot, frames, 1, false, nullptr, status_out);
 }
@@ -1818,8 +1858,9 @@ int wm_detect_keys_tiles(wm_ctx* ctx, int mask, const wm_plane* img, const wm_ke
 {
     if (!ctx) return WM_ERR_BAD_ARG;
     if (!img || !keys || !map_dev) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_keys_tiles: null img, keys or map_dev");
-    int ny = 0, nx = 0, rc;
-    if ((rc = tiles_checked(ctx, "wm_detect_keys_tiles", tile_rows, tile_cols, &ny, &nx)) != WM_OK) return rc;
+    TileShape ts;
+    int rc;
+    if ((rc = tiles_checked(ctx, "wm_detect_keys_tiles", tile_rows, tile_cols, &ts)) != WM_OK) return rc;
     if ((rc = check_mask(ctx, mask)) != WM_OK) return rc;
     if ((rc = check_bank(ctx, keys, "wm_detect_keys_tiles", true)) != WM_OK) return rc;
     if ((rc = refuse_band(ctx, "wm_detect_keys_tiles")) != WM_OK) return rc;
@@ -1828,19 +1869,17 @@ int wm_detect_keys_tiles(wm_ctx* ctx, int mask, const wm_plane* img, const wm_ke
     // (open_input checks the plane again: img->frames has to be known to be sane HERE, for the grid check in front of any device work)
     if ((rc = check_plane(ctx, img, 0, false, "image", true)) != WM_OK) return rc;
     const int frames = img->frames, nkeys = keys->nkeys;
-    if (!keys_tiles_grids_fit(ctx->rows, ctx->cols, tile_rows, frames, nkeys, ny, nx))
+    if (!keys_tiles_grids_fit(ctx->rows, ctx->cols, tile_rows, frames, nkeys, ts.ny, ts.nx))
         return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_keys_tiles: " + std::to_string(frames) + " frames x " + std::to_string(nkeys) + " keys x " +
-                                             std::to_string(ny) + "x" + std::to_string(nx) + " tiles exceed a launch grid of 31 bits");
-    PlaneDesc xd;
-    LaunchGeom lg;
-    if ((rc = open_input(ctx, s, img, "image", mask, 1, nullptr, &xd, &lg)) != WM_OK) return rc;
-    const TilesPlan pl = tiles_plan(lg, frames, mask, ctx->p / 2, xd, aligned_w_of(ctx), tile_rows, tile_cols, ny, nx);
+                                             std::to_string(ts.ny) + "x" + std::to_string(ts.nx) + " tiles exceed a launch grid of 31 bits");
+    Sweep sw;
+    if ((rc = open_input(ctx, s, img, "image", mask, 1, nullptr, &sw)) != WM_OK) return rc;
+    const TilesPlan pl = tiles_plan(sw, aligned_w_of(ctx), ts);
     if ((rc = ensure(ctx, &s.keys_tiles_rec, &s.keys_tiles_rec_bytes, keys_tiles_rec_bytes(pl, frames, nkeys), WM_ERR_ALLOC)) != WM_OK) return rc;
     OpResult* res = s.d_res + s.res_used;
     // the image side is wm_detect's: the Gram sweep (or the hand-over of the slot's last embed) and the solve
-    if ((rc = gram_sweep(ctx, s, lg, frames, xd, img)) != WM_OK) return rc;
-    launch_detect_keys_tiles(s.stream, pl, frames, mask, ctx->p / 2, xd, keys->d, (long long)ctx->rows * ctx->cols, nkeys, s.d_coef, s.d_status,
-                             (float*)s.keys_tiles_rec);
+    if ((rc = gram_sweep(ctx, s, sw, img)) != WM_OK) return rc;
+    launch_detect_keys_tiles(sw, pl, bank_of(ctx, keys), (float*)s.keys_tiles_rec);
     launch_keys_tiles_fold(s.stream, pl, frames, nkeys, (const float*)s.keys_tiles_rec, s.d_status, map_dev, sums_dev, res);
     return finish_call(ctx, s, slot, frames, 1, false, nullptr, status_out);
 }
@@ -1876,15 +1915,16 @@ int wm_embed_signs(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plan
 {
     if (!ctx) return WM_ERR_BAD_ARG;
     if (!in_gray || !base || !out || !signs) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_signs: null in_gray, base, out or signs");
-    int ny = 0, nx = 0, rc;
-    if ((rc = tiles_checked(ctx, "wm_embed_signs", tile_rows, tile_cols, &ny, &nx)) != WM_OK) return rc;
+    TileShape ts;
+    int rc;
+    if ((rc = tiles_checked(ctx, "wm_embed_signs", tile_rows, tile_cols, &ts)) != WM_OK) return rc;
     if ((rc = check_mask(ctx, mask)) != WM_OK) return rc;
     if ((rc = refuse_band(ctx, "wm_embed_signs")) != WM_OK) return rc;
     if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
     Slot& s = slot_of(ctx, slot);
     if ((rc = check_embed_planes(ctx, in_gray, base, out)) != WM_OK) return rc;
     const int frames = in_gray->frames;
-    const size_t nsigns = (size_t)frames * ny * nx;
+    const size_t nsigns = (size_t)frames * ts.ny * ts.nx;
     for (size_t i = 0; i < nsigns; ++i)
         if (signs[i] < -1 || signs[i] > 1)
             return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_signs: sign " + std::to_string((int)signs[i]) + " at index " + std::to_string(i) + " (must be -1, 0 or +1)");
@@ -1902,11 +1942,10 @@ int wm_embed_signs(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plan
     if ((rc = embed_snapshot(ctx, s, in_gray, &c)) != WM_OK) return rc;
     LaunchGeom lg;
     if ((rc = geom_checked(ctx, frames, mask, &lg)) != WM_OK) return rc;
-    const MaskRoute mr = mask_route(ctx, s, mask);
-    if (mask == WM_MASK_ME) sweep_gram(ctx, s, K_GRAM, lg, frames, c.xd);
-    sweep_stats(ctx, s, true, lg, frames, mask, c.xd, s.d_res + s.res_used);
-    launch_embed_signs(s.stream, lg, frames, mr.mask, mr.pad, c.xd, ctx->w->d_w, aligned_w_of(ctx), c.bd, c.od, mr.coef, mr.status, s.d_scal, (const signed char*)td,
-                       tile_rows, tile_cols, ny, nx);
+    const Sweep sw = mask_route(ctx, s, lg, frames, mask, c.xd);
+    if (mask == WM_MASK_ME) sweep_gram(ctx, s, K_GRAM, sw);
+    sweep_stats(ctx, s, true, sw, s.d_res + s.res_used);
+    launch_embed_signs(sw, own_w(ctx), EmbedPlanes{c.bd, c.od, s.d_scal}, (const signed char*)td, ts);
     return embed_close(ctx, s, out, c, a_out, status_out, slot);
 }
 
@@ -1916,9 +1955,10 @@ int wm_embed_bits(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane
 {
     if (!ctx) return WM_ERR_BAD_ARG;
     if (!in_gray || !tile_bit || !payload) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_bits: null in_gray, tile_bit or payload");
-    int ny = 0, nx = 0, rc;
-    if ((rc = tiles_checked(ctx, "wm_embed_bits", tile_rows, tile_cols, &ny, &nx)) != WM_OK) return rc;
-    const long long T = (long long)ny * nx;
+    TileShape ts;
+    int rc;
+    if ((rc = tiles_checked(ctx, "wm_embed_bits", tile_rows, tile_cols, &ts)) != WM_OK) return rc;
+    const long long T = (long long)ts.ny * ts.nx;
     if ((rc = tile_bits_checked(ctx, "wm_embed_bits", tile_bit, T, nbits)) != WM_OK) return rc;
     if (in_gray->frames < 1 || in_gray->frames > ctx->max_frames)
         return fail(ctx, WM_ERR_BAD_ARG, "in_gray: frames=" + std::to_string(in_gray->frames) + " exceeds wm_configure max_frames=" + std::to_string(ctx->max_frames));
@@ -1939,19 +1979,19 @@ int wm_detect_bits(wm_ctx* ctx, int mask, const wm_plane* img, int tile_rows, in
 {
     if (!ctx) return WM_ERR_BAD_ARG;
     if (!img || !tile_bit || !soft_out) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_bits: null img, tile_bit or soft_out");
-    int ny = 0, nx = 0, rc;
-    if ((rc = tiles_checked(ctx, "wm_detect_bits", tile_rows, tile_cols, &ny, &nx)) != WM_OK) return rc;
-    const int T = ny * nx;
+    TileShape ts;
+    int rc;
+    if ((rc = tiles_checked(ctx, "wm_detect_bits", tile_rows, tile_cols, &ts)) != WM_OK) return rc;
+    const int T = ts.ny * ts.nx;
     if ((rc = tile_bits_checked(ctx, "wm_detect_bits", tile_bit, T, nbits)) != WM_OK) return rc;
     if ((rc = check_mask(ctx, mask)) != WM_OK) return rc;
     if ((rc = refuse_band(ctx, "wm_detect_bits")) != WM_OK) return rc;
     if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
     Slot& s = slot_of(ctx, slot);
-    PlaneDesc xd;
-    LaunchGeom lg;
-    if ((rc = open_input(ctx, s, img, "image", mask, nbits, "bits", &xd, &lg)) != WM_OK) return rc;
+    Sweep sw;
+    if ((rc = open_input(ctx, s, img, "image", mask, nbits, "bits", &sw)) != WM_OK) return rc;
     const int frames = img->frames;
-    const TilesPlan pl = tiles_plan(lg, frames, mask, ctx->p / 2, xd, aligned_w_of(ctx), tile_rows, tile_cols, ny, nx);
+    const TilesPlan pl = tiles_plan(sw, aligned_w_of(ctx), ts);
     if ((rc = ensure(ctx, &s.tiles_rec, &s.tiles_rec_bytes, pl.rec_bytes)) != WM_OK) return rc;
     // the tile fold's output: sums [frames][T][3] f64, its status records [frames], map [frames][T] f32
     const size_t nt = (size_t)frames * T;
@@ -1976,8 +2016,8 @@ int wm_detect_bits(wm_ctx* ctx, int mask, const wm_plane* img, int tile_rows, in
     }
     if ((rc = table_upload(ctx, s, th, td, tab)) != WM_OK) return rc;
     // the image side is wm_detect's: the Gram sweep (or the hand-over of the slot's last embed) and the solve
-    if ((rc = gram_sweep(ctx, s, lg, frames, xd, img)) != WM_OK) return rc;
-    { ProfScope ps(ctx, K_DETECT_TILES, s.stream); launch_detect_tiles(s.stream, pl, frames, mask, ctx->p / 2, xd, ctx->w->d_w, s.d_coef, s.d_status, (float*)s.tiles_rec); }
+    if ((rc = gram_sweep(ctx, s, sw, img)) != WM_OK) return rc;
+    { ProfScope ps(ctx, K_DETECT_TILES, s.stream); launch_detect_tiles(sw, pl, own_w(ctx), (float*)s.tiles_rec); }
     { ProfScope ps(ctx, K_TILES_FOLD, s.stream); launch_tiles_fold(s.stream, pl, frames, (const float*)s.tiles_rec, s.d_status, map, sums, tres); }
     launch_bits_fold(s.stream, frames, nbits, T, sums, (const int*)td, (const int*)td + nbits + 1, s.d_status, s.d_res + s.res_used);
     return finish_call(ctx, s, slot, frames, nbits, false, soft_out, status_out);
@@ -1999,49 +2039,29 @@ int wm_embed_keys(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane
     const int frames = in_gray->frames;
     const int nkeys = keys->nkeys;
     if ((rc = check_plane(ctx, base, frames, true, "base")) != WM_OK) return rc;
-    // out: frames * nkeys device planes (more than max_frames is fine: the sweeps' scratch is per input frame)
     if (out->mem != WM_MEM_DEVICE) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_keys: out must be a WM_MEM_DEVICE plane");
-    if ((long long)out->frames != (long long)frames * nkeys)
-        return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_keys: out->frames must be in_gray->frames * nkeys = " + std::to_string((long long)frames * nkeys));
-    {
-        wm_plane one = *out;
-        one.frames = 1;
-        if ((rc = check_plane(ctx, &one, 1, true, "out")) != WM_OK) return rc;
-        if (out->frames > 1 && out->frame_stride < (int64_t)(out->channels - 1) * (out->channels > 1 ? out->channel_stride : 0) + (int64_t)out->rows * out->pitch)
-            return fail(ctx, WM_ERR_BAD_ARG, "out: frame_stride too small (frames overlap)");
-    }
+    if ((rc = check_out_copies(ctx, "wm_embed_keys", "nkeys", out, frames, nkeys)) != WM_OK) return rc;
     if ((rc = check_embed_dtypes(ctx, in_gray, base, out)) != WM_OK) return rc;
     if ((rc = check_res_room(ctx, s, (long long)frames * nkeys, "keys")) != WM_OK) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
 
-    PlaneDesc xd, bd;
-    if ((rc = prep_input(ctx, s, in_gray, &xd)) != WM_OK) return rc;
-    if ((rc = prep_base(ctx, s, in_gray, base, xd, &bd)) != WM_OK) return rc;
-    const PlaneDesc od = desc_device(out);
-    // K outputs of one input: an in-place call has no meaning (judged on the RESOLVED planes, as wm_embed judges them)
-    if (descs_overlap(xd, od, ctx->rows, ctx->cols, frames, frames * nkeys) || descs_overlap(bd, od, ctx->rows, ctx->cols, frames, frames * nkeys))
-        return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_keys: out overlaps in_gray or base");
-    // no hand-over of its own, and WM_MEM_SLOT_OUT keeps naming the last wm_embed output; a hand-over whose plane the copies
-    // overwrite ends here
-    invalidate_handovers(ctx, od, frames * nkeys);
-
+    EmbedCall c;
+    if ((rc = copies_stage(ctx, s, "wm_embed_keys", in_gray, base, out, nkeys, &c)) != WM_OK) return rc;
     LaunchGeom lg;
     if ((rc = geom_checked(ctx, frames, mask, &lg)) != WM_OK) return rc;
     const int rstride = std::max(ctx->max_nblk, ctx->max_nrec);
     if ((rc = ensure(ctx, &s.ekeys_part, &s.ekeys_part_bytes, embed_keys_scratch_bytes(frames, nkeys, rstride))) != WM_OK) return rc;
-    const int aligned_w = aligned_w_of(ctx);  // (the bank's planes have W's shape)
-    const long long kstride = (long long)ctx->rows * ctx->cols;
-    const MaskRoute mr = mask_route(ctx, s, mask);  // (these launchers take the mask type itself and the slot's coefficients under either)
+    const Sweep sw = mask_route(ctx, s, lg, frames, mask, c.xd);
+    const KeyBank bank = bank_of(ctx, keys);
     OpResult* res = s.d_res + s.res_used;
     // the image side is wm_embed's: the Gram sweep and solve (ME)
-    if (mask == WM_MASK_ME) sweep_gram(ctx, s, K_GRAM, lg, frames, xd);
+    if (mask == WM_MASK_ME) sweep_gram(ctx, s, K_GRAM, sw);
     {
         ProfScope ps(ctx, K_STATS_KEYS, s.stream);
-        if (launch_stats_keys(s.stream, lg, frames, mask, mr.pad, xd, keys->d, kstride, nkeys, aligned_w, s.d_coef, mr.status, s.ekeys_part, rstride) != 0)
-            return fail(ctx, WM_ERR_RUNTIME, "wm_embed_keys: geometry exceeds the record arrays");
+        if (launch_stats_keys(sw, bank, s.ekeys_part, rstride) != 0) return fail(ctx, WM_ERR_RUNTIME, "wm_embed_keys: geometry exceeds the record arrays");
     }
-    { ProfScope ps(ctx, K_EMBED_KEYS_FOLD, s.stream); launch_embed_keys_fold(s.stream, lg, frames, mask, nkeys, mr.status, s.ekeys_part, rstride, ctx->sF, sqrt_n(ctx), res); }
-    { ProfScope ps(ctx, K_EMBED_KEYS, s.stream); launch_embed_keys(s.stream, lg, frames, mask, mr.pad, xd, keys->d, kstride, nkeys, aligned_w, bd, od, s.d_coef, mr.status, s.ekeys_part, rstride); }
+    { ProfScope ps(ctx, K_EMBED_KEYS_FOLD, s.stream); launch_embed_keys_fold(sw, nkeys, s.ekeys_part, rstride, ctx->sF, sqrt_n(ctx), res); }
+    { ProfScope ps(ctx, K_EMBED_KEYS, s.stream); launch_embed_keys(sw, bank, EmbedPlanes{c.bd, c.od, nullptr}, s.ekeys_part, rstride); }
     return finish_call(ctx, s, slot, frames, nkeys, true, a_out, status_out);  // (wm_embed's rule: an unsolvable frame leaves its K strengths untouched)
 }
 
@@ -2055,8 +2075,9 @@ int wm_embed_signs_multi(wm_ctx* ctx, int mask, const wm_plane* in_gray, const w
 {
     if (!ctx) return WM_ERR_BAD_ARG;
     if (!in_gray || !base || !out || !signs) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_signs_multi: null in_gray, base, out or signs");
-    int ny = 0, nx = 0, rc;
-    if ((rc = tiles_checked(ctx, "wm_embed_signs_multi", tile_rows, tile_cols, &ny, &nx)) != WM_OK) return rc;
+    TileShape ts;
+    int rc;
+    if ((rc = tiles_checked(ctx, "wm_embed_signs_multi", tile_rows, tile_cols, &ts)) != WM_OK) return rc;
     if ((rc = check_mask(ctx, mask)) != WM_OK) return rc;
     if ((rc = refuse_band(ctx, "wm_embed_signs_multi")) != WM_OK) return rc;
     if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
@@ -2064,23 +2085,14 @@ int wm_embed_signs_multi(wm_ctx* ctx, int mask, const wm_plane* in_gray, const w
     if ((rc = check_plane(ctx, in_gray, 0, false, "in_gray", true)) != WM_OK) return rc;
     const int frames = in_gray->frames;
     if ((rc = check_plane(ctx, base, frames, true, "base")) != WM_OK) return rc;
-    // out: frames * ncopies device planes (more than max_frames is fine: the sweeps' scratch is per input frame)
     if (out->mem != WM_MEM_DEVICE) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_signs_multi: out must be a WM_MEM_DEVICE plane");
     if (ncopies < 1 || ncopies > 4096) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_signs_multi: ncopies must be 1 .. 4096");
-    if ((long long)out->frames != (long long)frames * ncopies)
-        return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_signs_multi: out->frames must be in_gray->frames * ncopies = " + std::to_string((long long)frames * ncopies));
-    {
-        wm_plane one = *out;
-        one.frames = 1;
-        if ((rc = check_plane(ctx, &one, 1, true, "out")) != WM_OK) return rc;
-        if (out->frames > 1 && out->frame_stride < (int64_t)(out->channels - 1) * (out->channels > 1 ? out->channel_stride : 0) + (int64_t)out->rows * out->pitch)
-            return fail(ctx, WM_ERR_BAD_ARG, "out: frame_stride too small (frames overlap)");
-    }
+    if ((rc = check_out_copies(ctx, "wm_embed_signs_multi", "ncopies", out, frames, ncopies)) != WM_OK) return rc;
     if ((rc = check_embed_dtypes(ctx, in_gray, base, out)) != WM_OK) return rc;
     const LaunchGeom lg0 = make_geom(ctx, frames, mask);
     if (!embed_signs_multi_grid_fits(lg0, frames, ncopies))
         return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_signs_multi: the sweep's grid times the copy groups exceeds a launch grid of 31 bits");
-    const size_t nsigns = (size_t)frames * ncopies * ny * nx;
+    const size_t nsigns = (size_t)frames * ncopies * ts.ny * ts.nx;
     for (size_t i = 0; i < nsigns; ++i)
         if (signs[i] < -1 || signs[i] > 1)
             return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_signs_multi: sign " + std::to_string((int)signs[i]) + " at index " + std::to_string(i) + " (must be -1, 0 or +1)");
@@ -2093,24 +2105,14 @@ int wm_embed_signs_multi(wm_ctx* ctx, int mask, const wm_plane* in_gray, const w
     std::memcpy(th, signs, nsigns);
     if ((rc = table_upload(ctx, s, th, td, nsigns)) != WM_OK) return rc;
 
-    PlaneDesc xd, bd;
-    if ((rc = prep_input(ctx, s, in_gray, &xd)) != WM_OK) return rc;
-    if ((rc = prep_base(ctx, s, in_gray, base, xd, &bd)) != WM_OK) return rc;
-    const PlaneDesc od = desc_device(out);
-    // K outputs of one input: an in-place call has no meaning (judged on the RESOLVED planes, as wm_embed_keys judges them)
-    if (descs_overlap(xd, od, ctx->rows, ctx->cols, frames, frames * ncopies) || descs_overlap(bd, od, ctx->rows, ctx->cols, frames, frames * ncopies))
-        return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_signs_multi: out overlaps in_gray or base");
-    // no hand-over of its own, and WM_MEM_SLOT_OUT keeps naming the last wm_embed output; a hand-over whose plane the copies
-    // overwrite ends here
-    invalidate_handovers(ctx, od, frames * ncopies);
-
+    EmbedCall c;
+    if ((rc = copies_stage(ctx, s, "wm_embed_signs_multi", in_gray, base, out, ncopies, &c)) != WM_OK) return rc;
     LaunchGeom lg;
     if ((rc = geom_checked(ctx, frames, mask, &lg)) != WM_OK) return rc;
-    const MaskRoute mr = mask_route(ctx, s, mask);
-    if (mask == WM_MASK_ME) sweep_gram(ctx, s, K_GRAM, lg, frames, xd);
-    sweep_stats(ctx, s, true, lg, frames, mask, xd, s.d_res + s.res_used);
-    launch_embed_signs_multi(s.stream, lg, frames, mr.mask, mr.pad, xd, ctx->w->d_w, aligned_w_of(ctx), bd, od, mr.coef, mr.status, s.d_scal,
-                             (const signed char*)td, ncopies, tile_rows, tile_cols, ny, nx);
+    const Sweep sw = mask_route(ctx, s, lg, frames, mask, c.xd);
+    if (mask == WM_MASK_ME) sweep_gram(ctx, s, K_GRAM, sw);
+    sweep_stats(ctx, s, true, sw, s.d_res + s.res_used);
+    launch_embed_signs_multi(sw, own_w(ctx), EmbedPlanes{c.bd, c.od, s.d_scal}, (const signed char*)td, ncopies, ts);
     return finish_call(ctx, s, slot, frames, 1, true, a_out, status_out);
 }
 
@@ -2120,9 +2122,10 @@ int wm_embed_bits_multi(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm
 {
     if (!ctx) return WM_ERR_BAD_ARG;
     if (!in_gray || !tile_bit || !payloads) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_bits_multi: null in_gray, tile_bit or payloads");
-    int ny = 0, nx = 0, rc;
-    if ((rc = tiles_checked(ctx, "wm_embed_bits_multi", tile_rows, tile_cols, &ny, &nx)) != WM_OK) return rc;
-    const long long T = (long long)ny * nx;
+    TileShape ts;
+    int rc;
+    if ((rc = tiles_checked(ctx, "wm_embed_bits_multi", tile_rows, tile_cols, &ts)) != WM_OK) return rc;
+    const long long T = (long long)ts.ny * ts.nx;
     if ((rc = tile_bits_checked(ctx, "wm_embed_bits_multi", tile_bit, T, nbits)) != WM_OK) return rc;
     if (in_gray->frames < 1 || in_gray->frames > ctx->max_frames)
         return fail(ctx, WM_ERR_BAD_ARG, "in_gray: frames=" + std::to_string(in_gray->frames) + " exceeds wm_configure max_frames=" + std::to_string(ctx->max_frames));
@@ -2166,14 +2169,14 @@ int wm_compute_mask(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_pla
     invalidate_handovers(ctx, eo, frames);
     OpResult* res = s.d_res + s.res_used;
     float* coefres = s.d_coefres + (size_t)s.res_used * 8;
-    const MaskRoute mr = mask_route(ctx, s, mask);
+    const Sweep sw = mask_route(ctx, s, lg, frames, mask, xd);
     // (ME: the prediction error scaled by the stats sweep's maximum, behind the Gram and stats sweeps; NVF needs neither, nor scalars)
     if (mask == WM_MASK_ME) {
-        sweep_gram(ctx, s, K_GRAM, lg, frames, xd);
-        sweep_stats(ctx, s, true, lg, frames, mask, xd, res);
+        sweep_gram(ctx, s, K_GRAM, sw);
+        sweep_stats(ctx, s, true, sw, res);
     }
-    { ProfScope ps(ctx, K_MASK, s.stream); launch_mask(s.stream, lg, frames, mr.mask, mr.pad, xd, mr.coef, mr.status, mask == WM_MASK_ME ? s.d_scal : nullptr, mo, eo); }
-    launch_mask_result(s.stream, frames, mr.status, mr.coef, res, coefres);
+    { ProfScope ps(ctx, K_MASK, s.stream); launch_mask(sw, mask == WM_MASK_ME ? s.d_scal : nullptr, mo, eo); }
+    launch_mask_result(s.stream, frames, sw.status, sw.coef, res, coefres);
     return finish_call(ctx, s, slot, frames, 1, false, nullptr, status_out, coef_out);
 }
 
@@ -2183,11 +2186,10 @@ int wm_gram(wm_ctx* ctx, const wm_plane* img, double* gram_out, int slot)
     int rc = check_slot(ctx, slot);
     if (rc != WM_OK) return rc;
     Slot& s = slot_of(ctx, slot);
-    PlaneDesc xd;
-    LaunchGeom lg;
-    if ((rc = open_input(ctx, s, img, "image", WM_MASK_ME, 0, nullptr, &xd, &lg)) != WM_OK) return rc;
+    Sweep sw;
+    if ((rc = open_input(ctx, s, img, "image", WM_MASK_ME, 0, nullptr, &sw)) != WM_OK) return rc;
     const int frames = img->frames;
-    if ((rc = gram_sweep(ctx, s, lg, frames, xd, img)) != WM_OK) return rc;
+    if ((rc = gram_sweep(ctx, s, sw, img)) != WM_OK) return rc;
     if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
     HIPCHK(ctx, hipStreamSynchronize(s.stream));
     HIPCHK(ctx, hipMemcpy(gram_out, s.d_gramtot, (size_t)frames * NGRAM * sizeof(double), hipMemcpyDeviceToHost));
@@ -2240,11 +2242,10 @@ static int band_stats_launch(wm_ctx* ctx, Slot& s, int mask, const wm_plane* in_
 {
     int rc;
     if ((rc = check_mask(ctx, mask)) != WM_OK) return rc;
-    PlaneDesc xd;
-    LaunchGeom lg;
-    if ((rc = open_input(ctx, s, in_gray, "inputImage", mask, 1, nullptr, &xd, &lg)) != WM_OK) return rc;
+    Sweep sw;
+    if ((rc = open_input(ctx, s, in_gray, "inputImage", mask, 1, nullptr, &sw)) != WM_OK) return rc;
     const int frames = in_gray->frames;
-    sweep_stats(ctx, s, false, lg, frames, mask, xd, s.d_res + s.res_used);  // (records written by the tail, not delivered: no pending entry)
+    sweep_stats(ctx, s, false, mask_route(ctx, s, sw.lg, frames, mask, sw.x), s.d_res + s.res_used);  // (records written by the tail, not delivered: no pending entry)
     *frames_out = frames;
     return launch_check(ctx, s);
 }
@@ -2264,8 +2265,7 @@ static int band_embed_launch(wm_ctx* ctx, Slot& s, int mask, const wm_plane* in_
     invalidate_handovers(ctx, od, frames);
     LaunchGeom lg;
     if ((rc = geom_checked(ctx, frames, mask, &lg)) != WM_OK) return rc;
-    const MaskRoute mr = mask_route(ctx, s, mask);
-    launch_embed(s.stream, lg, frames, mr.mask, mr.pad, xd, ctx->w->d_w, aligned_w_of(ctx), bd, od, mr.coef, mr.status, s.d_scal);
+    launch_embed(mask_route(ctx, s, lg, frames, mask, xd), own_w(ctx), EmbedPlanes{bd, od, s.d_scal});
     return launch_check(ctx, s);
 }
 
@@ -2274,11 +2274,10 @@ static int band_detect_launch(wm_ctx* ctx, Slot& s, int mask, const wm_plane* im
 {
     int rc;
     if ((rc = check_mask(ctx, mask)) != WM_OK) return rc;
-    PlaneDesc xd;
-    LaunchGeom lg;
-    if ((rc = open_input(ctx, s, img, "image", mask, 1, nullptr, &xd, &lg)) != WM_OK) return rc;
+    Sweep sw;
+    if ((rc = open_input(ctx, s, img, "image", mask, 1, nullptr, &sw)) != WM_OK) return rc;
     const int frames = img->frames;
-    sweep_detect(ctx, s, K_NONE, lg, frames, mask, xd, s.d_res + s.res_used);
+    sweep_detect(ctx, s, K_NONE, sw, s.d_res + s.res_used);
     *frames_out = frames;
     return launch_check(ctx, s);
 }
@@ -2348,12 +2347,10 @@ int wm_band_gram_dev(wm_ctx* ctx, const wm_plane* img, double* totals_dev, int s
     int rc = check_slot(ctx, slot);
     if (rc != WM_OK) return rc;
     Slot& s = slot_of(ctx, slot);
-    PlaneDesc xd;
-    LaunchGeom lg;
-    if ((rc = open_input(ctx, s, img, "image", WM_MASK_ME, 0, nullptr, &xd, &lg)) != WM_OK) return rc;
-    const int frames = img->frames;
+    Sweep sw;
+    if ((rc = open_input(ctx, s, img, "image", WM_MASK_ME, 0, nullptr, &sw)) != WM_OK) return rc;
     // (the sweep's solve tail also solves from the band's own partial totals into the slot: overwritten by wm_band_solve_dev)
-    sweep_gram(ctx, s, K_NONE, lg, frames, xd, totals_dev);
+    sweep_gram(ctx, s, K_NONE, sw, totals_dev);
     return launch_check(ctx, s);
 }
 

@@ -1,6 +1,7 @@
 // wm_embed_march.hpp -- embed_march, the embed sweep's march over one wave's segment, and WM_EMBED_BODY, the kernel body around it:
 // shared by k_embed (wm_k_embed.hip; plain and with the Gram hand-over) and k_embed_signs (wm_k_bits.hip; the tile's sign in the
-// row step), with the launch loop the two have in common
+// row step), with the launch loop the two have in common and the per-channel loop around it of the multi-copy embed kernels
+// (k_embed_keys, k_embed_signs_multi)
 #pragma once
 #include "wm_march.hpp"
 
@@ -294,16 +295,35 @@ static inline void for_embed_planes(const PlaneDesc& x, const PlaneDesc& base, F
 // the launches of one embed sweep over planes of NCH channels: go(IC<MASK>, IC<PAD>, vec, IC<channels of the instance>, base_is_x, part)
 // for the aligned and the generic part.  al: align_mode of all four planes; bx: the base is the grey input plane (same_plane)
 template <int NCH, typename F>
-static inline void for_each_embed_launch(const LaunchGeom& lg, int frames, int mask, int pad, int al, bool bx, F&& go)
+static inline void for_each_embed_launch(const Sweep& sw, int al, bool bx, F&& go)
 {
-    for_mask_pad(mask, pad, [&](auto m, auto p) {
+    for_mask_pad(sw.mask, sw.pad, [&](auto m, auto p) {
         auto sweep = [&](auto base_is_x) {
-            for_each_sweep_part(lg, frames, al, 1, [&](auto vec, const SweepPart& sp) {
+            for_each_sweep_part(sw, al, 1, [&](auto vec, const SweepPart& sp) {
                 go(m, p, vec, IC<(decltype(base_is_x)::value ? 1 : NCH)>{}, base_is_x, sp);
             });
         };
         if (bx) sweep(std::true_type{}); else sweep(std::false_type{});
     });
+}
+// the launches of a multi-copy embed sweep (k_embed_keys, k_embed_signs_multi): the plan above once per channel of the base, on
+// one-channel views of base and out, every grid times the copy groups: go(IC<MASK>, IC<PAD>, vec, base_is_x, grid, Geom, base view, out view).
+// T: the planes' element type (the API layer admits same-dtype planes only, as for wm_embed)
+template <typename T, typename F>
+static inline void for_each_embed_group_launch(const Sweep& sw, int aligned_w, const EmbedPlanes& ep, int ngroups, F&& go)
+{
+    const PlaneDesc &base = ep.base, &out = ep.out;
+    const int al = align_mode(sw.lg, sw.x.aligned && aligned_w && base.aligned && out.aligned);
+    const bool bx = base.channels == 1 && same_plane(sw.x, base);
+    for (int ch = 0; ch < base.channels; ++ch) {
+        PlaneDesc bc = base, oc = out;
+        bc.p = static_cast<const T*>(base.p) + (long long)ch * base.cstride;
+        oc.p = static_cast<const T*>(out.p) + (long long)ch * out.cstride;
+        bc.channels = oc.channels = 1;
+        for_each_embed_launch<1>(sw, al, bx, [&](auto m, auto p, auto vec, auto, auto base_is_x, const SweepPart& sp) {
+            go(m, p, vec, base_is_x, dim3(sp.grid.x * (unsigned)ngroups), sp.g, bc, oc);
+        });
+    }
 }
 
 }  // namespace wmk

@@ -63,19 +63,18 @@ __global__ __launch_bounds__(BLOCK) void k_bits_fold(const double* __restrict__ 
 }
 
 // launchers
-void launch_embed_signs(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* W,
-                        int aligned_w, const PlaneDesc& base, const PlaneDesc& out, const float* coef, const int* status,
-                        const EmbedScalars* scal, const signed char* signs, int tile_rows, int tile_cols, int ny, int nx)
+void launch_embed_signs(const Sweep& sw, const KeyBank& w, const EmbedPlanes& ep, const signed char* signs, const TileShape& ts)
 {
-    const SignTable sg{signs, tile_rows, tile_cols, ny, nx};
-    const int al = align_mode(lg, x.aligned && aligned_w && base.aligned && out.aligned);
-    for_embed_planes(x, base, [&](auto t, auto nch_base) {
+    const PlaneDesc& x = sw.x;
+    const SignTable sg{signs, ts.th, ts.tw, ts.ny, ts.nx};
+    const int al = align_mode(sw.lg, x.aligned && w.aligned_w && ep.base.aligned && ep.out.aligned);
+    for_embed_planes(x, ep.base, [&](auto t, auto nch_base) {
         using T = decltype(t);
         constexpr int NCH = decltype(nch_base)::value;
-        const bool bx = NCH == 1 && same_plane(x, base);
-        for_each_embed_launch<NCH>(lg, frames, mask, pad, al, bx, [&](auto m, auto p, auto vec, auto nch, auto base_is_x, const SweepPart& sp) {
+        const bool bx = NCH == 1 && same_plane(x, ep.base);
+        for_each_embed_launch<NCH>(sw, al, bx, [&](auto m, auto p, auto vec, auto nch, auto base_is_x, const SweepPart& sp) {
             WM_KLAUNCH((k_embed_signs<T, T, decltype(nch)::value, decltype(m)::value, decltype(p)::value, decltype(vec)::value, decltype(base_is_x)::value>),
-                       sp.grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, W, base, out, sp.g, coef, status, scal, sg);
+                       sp.grid, dim3(BLOCK), 0, sw.s, (const T*)x.p, x.pitch, x.fstride, w.W, ep.base, ep.out, sp.g, sw.coef, sw.status, ep.scal, sg);
         });
     });
 }

@@ -207,36 +207,36 @@ __global__ void k_mask_result(const int* __restrict__ status, const float* __res
 
 // launchers
 template <typename T>
-static void launch_detect_t(hipStream_t s, const DetectPlan& pl, int frames, int mask, int pad, const PlaneDesc& x, const float* W,
-                            const float* coef, const int* status, double* pcorr, const CorrTail& tail, const DigCheck& dc)
+static void launch_detect_t(const Sweep& sw, const DetectPlan& pl, const float* W, double* pcorr, const CorrTail& tail, const DigCheck& dc)
 {
-    for_each_detect_launch(pl, frames, mask, pad, [&](auto m, auto p, auto hc, auto vec, const SweepPart& sp) {
+    const PlaneDesc& x = sw.x;
+    for_each_detect_launch(pl, sw, [&](auto m, auto p, auto hc, auto vec, const SweepPart& sp) {
         WM_KLAUNCH((k_detect<T, decltype(m)::value, decltype(p)::value, decltype(hc)::value, decltype(vec)::value>), sp.grid, dim3(BLOCK),
-                   0, s, (const T*)x.p, x.pitch, x.fstride, W, sp.g, coef, status, pcorr, tail, dc);
+                   0, sw.s, (const T*)x.p, x.pitch, x.fstride, W, sp.g, sw.coef, sw.status, pcorr, tail, dc);
     });
 }
-bool detect_checkable(const LaunchGeom& lg, int mask, int pad, const PlaneDesc& x, int aligned_w)
+bool detect_checkable(const Sweep& sw, int aligned_w)
 {
-    return x.dtype == 0 && mask == 0 && pad == 1 && detect_plan(lg, mask, pad, x, aligned_w).overlap;
+    return sw.x.dtype == 0 && sw.mask == 0 && sw.pad == 1 && detect_plan(sw, aligned_w).overlap;
 }
-void launch_detect(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* W,
-                   int aligned_w, const float* coef, const int* status, double* pcorr, unsigned* ticket, unsigned* ticket_strip,
-                   double* scorr, OpResult* res, RawSums* raw, const DigCheck* dc, int mode)
+void launch_detect(const Sweep& sw, const KeyBank& w, double* pcorr, unsigned* ticket, unsigned* ticket_strip, double* scorr, OpResult* res,
+                   RawSums* raw, const DigCheck* dc, int mode)
 {
+    const PlaneDesc& x = sw.x;
     if (mode != 0) {
         // the checking instance and its redo launch: f32, ME, overlapped strips (detect_checkable, checked by the caller)
-        const LaunchGeom ld = overlap_geom(lg);
+        const LaunchGeom ld = overlap_geom(sw.lg);
         const CorrTail tail{ticket, ticket_strip, ld.nblk, ld.nsegs, ld.nstrips, scorr, res, raw};
-        const SweepPart pv = sweep_part_overlap(ld, frames, 1);
-        if (mode == 1) WM_KLAUNCH((k_detect<float, 0, 1, 1, true, 1>), pv.grid, dim3(BLOCK), 0, s, (const float*)x.p, x.pitch, x.fstride, W, pv.g, coef, status, pcorr, tail, *dc);
-        else WM_KLAUNCH((k_detect_redo<float, 0, 1, 1, true>), pv.grid, dim3(BLOCK), 0, s, (const float*)x.p, x.pitch, x.fstride, W, pv.g, coef, status, pcorr, tail, *dc);
+        const SweepPart pv = sweep_part_overlap(ld, sw.frames, 1);
+        if (mode == 1) WM_KLAUNCH((k_detect<float, 0, 1, 1, true, 1>), pv.grid, dim3(BLOCK), 0, sw.s, (const float*)x.p, x.pitch, x.fstride, w.W, pv.g, sw.coef, sw.status, pcorr, tail, *dc);
+        else WM_KLAUNCH((k_detect_redo<float, 0, 1, 1, true>), pv.grid, dim3(BLOCK), 0, sw.s, (const float*)x.p, x.pitch, x.fstride, w.W, pv.g, sw.coef, sw.status, pcorr, tail, *dc);
         return;
     }
     const DigCheck none{nullptr, nullptr, nullptr, nullptr, nullptr};
-    const DetectPlan pl = detect_plan(lg, mask, pad, x, aligned_w);
+    const DetectPlan pl = detect_plan(sw, w.aligned_w);
     const LaunchGeom& ld = pl.ld;
     const CorrTail tail{ticket, ticket_strip, ld.nblk, ld.nsegs, ld.nstrips, scorr, res, raw};
-    WM_DISPATCH_T(x.dtype, launch_detect_t<T>(s, pl, frames, mask, pad, x, W, coef, status, pcorr, tail, none));
+    WM_DISPATCH_T(x.dtype, launch_detect_t<T>(sw, pl, w.W, pcorr, tail, none));
 }
 
 // ---- W on the device: the counter-based N(0,1) generator of csrc/app/wm_genw.cpp (the replacement of the reference's

@@ -163,31 +163,30 @@ __global__ __launch_bounds__(BLOCK) void k_keys_fold(const double* __restrict__ 
 }
 
 template <typename T>
-static void launch_detect_keys_t(hipStream_t s, const DetectPlan& pl, int frames, int mask, int pad, const PlaneDesc& x, const KeysArgs& ka,
-                                 const float* coef, const int* status)
+static void launch_detect_keys_t(const Sweep& sw, const DetectPlan& pl, const KeysArgs& ka)
 {
+    const PlaneDesc& x = sw.x;
     // every grid times the key groups
-    for_each_detect_launch(pl, frames, mask, pad, [&](auto m, auto p, auto hc, auto vec, const SweepPart& sp) {
+    for_each_detect_launch(pl, sw, [&](auto m, auto p, auto hc, auto vec, const SweepPart& sp) {
         WM_KLAUNCH((k_detect_keys<T, decltype(m)::value, decltype(p)::value, decltype(hc)::value, decltype(vec)::value>),
-                   dim3(sp.grid.x * (unsigned)ka.ngroups), dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, ka, sp.g, coef, status);
+                   dim3(sp.grid.x * (unsigned)ka.ngroups), dim3(BLOCK), 0, sw.s, (const T*)x.p, x.pitch, x.fstride, ka, sp.g, sw.coef, sw.status);
     });
 }
 
 int detect_keys_group(void) { return KG; }
 
-int launch_detect_keys(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x,
-                       const float* Wbank, long long kstride, int nkeys, int aligned_w, const float* coef, const int* status,
-                       double* part, int rstride, OpResult* res)
+int launch_detect_keys(const Sweep& sw, const KeyBank& bank, double* part, int rstride, OpResult* res)
 {
-    const DetectPlan pl = detect_plan(lg, mask, pad, x, aligned_w);
+    const DetectPlan pl = detect_plan(sw, bank.aligned_w);
     const LaunchGeom& ld = pl.ld;
+    const int frames = sw.frames, nkeys = bank.nkeys;
     const bool quad = frames >= 4;
     if (ld.nblk > rstride || ld.nstrips * ld.nsegs > rstride || ld.nstrips > KEYS_MAX_STRIPS) return -1;
     KeysArgs ka;
-    ka.W = Wbank; ka.kstride = kstride; ka.nkeys = nkeys; ka.ngroups = (nkeys + KG - 1) / KG; ka.rstride = rstride;
+    ka.W = bank.W; ka.kstride = bank.kstride; ka.nkeys = nkeys; ka.ngroups = (nkeys + KG - 1) / KG; ka.rstride = rstride;
     ka.part = part; ka.partw = part + (size_t)frames * nkeys * rstride * 2;
-    WM_DISPATCH_T(x.dtype, launch_detect_keys_t<T>(s, pl, frames, mask, pad, x, ka, coef, status));
-    launch_keys_fold(s, ka.part, ka.partw, rstride, frames, nkeys, quad ? 1 : 0, ld.nblk, ld.nsegs, ld.nstrips, status, res);
+    WM_DISPATCH_T(sw.x.dtype, launch_detect_keys_t<T>(sw, pl, ka));
+    launch_keys_fold(sw.s, ka.part, ka.partw, rstride, frames, nkeys, quad ? 1 : 0, ld.nblk, ld.nsegs, ld.nstrips, sw.status, res);
     return 0;
 }
 

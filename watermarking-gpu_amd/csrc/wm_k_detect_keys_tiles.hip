@@ -126,22 +126,21 @@ bool keys_tiles_grids_fit(int rows, int cols, int tile_rows, int frames, int nke
 }
 
 template <typename T>
-static void launch_detect_keys_tiles_t(hipStream_t s, const TilesPlan& pl, int frames, int mask, int pad, const PlaneDesc& x, const float* Wbank,
-                                       long long kstride, int nkeys, const float* coef, const int* status, float* rec)
+static void launch_detect_keys_tiles_t(const Sweep& sw, const TilesPlan& pl, const KeyBank& bank, float* rec)
 {
-    const int ngroups = (nkeys + KG - 1) / KG;
+    const PlaneDesc& x = sw.x;
+    const int ngroups = (bank.nkeys + KG - 1) / KG;
     // every grid times the key groups
-    for_each_detect_launch(pl, frames, mask, pad, [&](auto m, auto p, auto hc, auto vec, const SweepPart& sp) {
+    for_each_detect_launch(pl, sw, [&](auto m, auto p, auto hc, auto vec, const SweepPart& sp) {
         WM_KLAUNCH((k_detect_keys_tiles<T, decltype(m)::value, decltype(p)::value, decltype(hc)::value, decltype(vec)::value>),
-                   dim3(sp.grid.x * (unsigned)ngroups), dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, Wbank, kstride, nkeys, ngroups,
-                   sp.g, coef, status, rec);
+                   dim3(sp.grid.x * (unsigned)ngroups), dim3(BLOCK), 0, sw.s, (const T*)x.p, x.pitch, x.fstride, bank.W, bank.kstride, bank.nkeys,
+                   ngroups, sp.g, sw.coef, sw.status, rec);
     });
 }
 
-void launch_detect_keys_tiles(hipStream_t s, const TilesPlan& pl, int frames, int mask, int pad, const PlaneDesc& x, const float* Wbank,
-                              long long kstride, int nkeys, const float* coef, const int* status, float* rec)
+void launch_detect_keys_tiles(const Sweep& sw, const TilesPlan& pl, const KeyBank& bank, float* rec)
 {
-    WM_DISPATCH_T(x.dtype, launch_detect_keys_tiles_t<T>(s, pl, frames, mask, pad, x, Wbank, kstride, nkeys, coef, status, rec));
+    WM_DISPATCH_T(sw.x.dtype, launch_detect_keys_tiles_t<T>(sw, pl, bank, rec));
 }
 
 void launch_keys_tiles_fold(hipStream_t s, const TilesPlan& pl, int frames, int nkeys, const float* rec, const int* status, float* map,

@@ -373,9 +373,9 @@ __global__ __launch_bounds__(BLOCK, offsets_min_blocks(PAD, HC, VEC, (int)sizeof
 }
 
 template <typename T>
-static void launch_detect_offsets_t(hipStream_t s, const DetectPlan& pl, int frames, int mask, int pad, const PlaneDesc& x,
-                                    const OffsArgs& oa1, const float* coef, const int* status)
+static void launch_detect_offsets_t(const Sweep& sw, const DetectPlan& pl, const OffsArgs& oa1)
 {
+    const PlaneDesc& x = sw.x;
     // columns(): the columns [lo, lo + n) of every row offset in groups of G
     auto columns = [&](int G, int lo, int n, int write_w) {
         OffsArgs a = oa1;
@@ -389,12 +389,12 @@ static void launch_detect_offsets_t(hipStream_t s, const DetectPlan& pl, int fra
     const int rem = oa1.nx % OG, tail = oa1.nx >= OG && 2 * rem <= OG ? rem : 0;
     const OffsArgs all1 = columns(1, 0, oa1.nx, 1);  // every offset a block of its own
     // every grid times the offset groups of its instance
-    for_each_detect_launch(pl, frames, mask, pad, [&](auto m, auto p, auto hc, auto vec, const SweepPart& sp) {
+    for_each_detect_launch(pl, sw, [&](auto m, auto p, auto hc, auto vec, const SweepPart& sp) {
         constexpr int MASK = decltype(m)::value, PAD = decltype(p)::value, HC = decltype(hc)::value;
         constexpr bool VEC = decltype(vec)::value;
         auto go = [&](auto g, const OffsArgs& oa) {
-            WM_KLAUNCH((k_detect_offsets<T, MASK, PAD, HC, VEC, decltype(g)::value>), dim3(sp.grid.x * (unsigned)oa.ngroups), dim3(BLOCK), 0, s,
-                       (const T*)x.p, x.pitch, x.fstride, oa, sp.g, coef, status);
+            WM_KLAUNCH((k_detect_offsets<T, MASK, PAD, HC, VEC, decltype(g)::value>), dim3(sp.grid.x * (unsigned)oa.ngroups), dim3(BLOCK), 0, sw.s,
+                       (const T*)x.p, x.pitch, x.fstride, oa, sp.g, sw.coef, sw.status);
         };
         if constexpr (VEC && PAD == 1) {
             if (oa1.nx >= OG) {
@@ -409,21 +409,21 @@ static void launch_detect_offsets_t(hipStream_t s, const DetectPlan& pl, int fra
 
 int detect_offsets_group(void) { return OG; }
 
-int launch_detect_offsets(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x,
-                          const float* key, int key_cols, int oy0, int ox0, int ny, int nx, int aligned_w, const float* coef,
-                          const int* status, double* part, int rstride, OpResult* res)
+int launch_detect_offsets(const Sweep& sw, const KeyBank& key, int key_cols, int oy0, int ox0, int ny, int nx, double* part, int rstride,
+                          OpResult* res)
 {
     // the geometry comes from the IMAGE plane alone (detect_plan, as for every detector)
-    const DetectPlan pl = detect_plan(lg, mask, pad, x, aligned_w);
+    const DetectPlan pl = detect_plan(sw, key.aligned_w);
     const LaunchGeom& ld = pl.ld;
+    const int frames = sw.frames;
     const bool quad = frames >= 4;
     if (ld.nblk > rstride || ld.nstrips * ld.nsegs > rstride || ld.nstrips > KEYS_MAX_STRIPS) return -1;
     const int noff = ny * nx;
     OffsArgs oa;
-    oa.key = key; oa.kc = key_cols; oa.oy0 = oy0; oa.ox0 = ox0; oa.ny = ny; oa.nx = nx; oa.jx_lo = 0; oa.nxl = nx; oa.ngx = nx; oa.ngroups = noff; oa.write_w = 1;
+    oa.key = key.W; oa.kc = key_cols; oa.oy0 = oy0; oa.ox0 = ox0; oa.ny = ny; oa.nx = nx; oa.jx_lo = 0; oa.nxl = nx; oa.ngx = nx; oa.ngroups = noff; oa.write_w = 1;
     oa.rstride = rstride; oa.part = part; oa.partw = part + (size_t)frames * noff * rstride * 2;
-    WM_DISPATCH_T(x.dtype, launch_detect_offsets_t<T>(s, pl, frames, mask, pad, x, oa, coef, status));
-    launch_keys_fold(s, oa.part, oa.partw, rstride, frames, noff, quad ? 1 : 0, ld.nblk, ld.nsegs, ld.nstrips, status, res);
+    WM_DISPATCH_T(sw.x.dtype, launch_detect_offsets_t<T>(sw, pl, oa));
+    launch_keys_fold(sw.s, oa.part, oa.partw, rstride, frames, noff, quad ? 1 : 0, ld.nblk, ld.nsegs, ld.nstrips, sw.status, res);
     return 0;
 }
 

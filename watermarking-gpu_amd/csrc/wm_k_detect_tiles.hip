@@ -96,45 +96,44 @@ int tiles_segment_rows(int tile_rows)
 
 // the sweep's geometry: segments of tiles_segment_rows(tile_rows) rows -- from the tile shape alone, so that a frame's records
 // (and bits) do not depend on the batch it arrives in --, strips as detect_plan chooses them
-TilesPlan tiles_plan(const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, int aligned_w, int tile_rows, int tile_cols,
-                     int ny, int nx)
+TilesPlan tiles_plan(const Sweep& sw, int aligned_w, const TileShape& ts)
 {
     TilesPlan pl;
-    LaunchGeom lt = lg;
-    lt.rps = std::min(tiles_segment_rows(tile_rows), lg.row_hi - lg.row_lo);
-    lt.nsegs = (lg.row_hi - lg.row_lo + lt.rps - 1) / lt.rps;
+    Sweep st = sw;
+    LaunchGeom& lt = st.lg;
+    lt.rps = std::min(tiles_segment_rows(ts.th), lt.row_hi - lt.row_lo);
+    lt.nsegs = (lt.row_hi - lt.row_lo + lt.rps - 1) / lt.rps;
     lt.nblk = lt.nstrips * ((lt.nsegs + WPB - 1) / WPB);
-    const DetectPlan dp = detect_plan(lt, mask, pad, x, aligned_w);
+    const DetectPlan dp = detect_plan(st, aligned_w);
     pl.ld = dp.ld; pl.overlap = dp.overlap; pl.split = dp.split;
     const LaunchGeom& ld = pl.ld;
     TileGeom& tg = pl.tg;
-    tg.th = tile_rows; tg.tw = tile_cols; tg.ny = ny; tg.nx = nx;
+    tg.th = ts.th; tg.tw = ts.tw; tg.ny = ts.ny; tg.nx = ts.nx;
     tg.rps = ld.rps; tg.nsegs = ld.nsegs; tg.nstrips = ld.nstrips;
     tg.layout = pl.overlap ? 1 : (pl.split ? 2 : 0);
     tg.nown = pl.overlap ? ld.cols / 4 : (pl.split ? split_own_cols(ld.cols) / 4 : 0);
     tg.ngroups = pl.overlap ? tg.nown : (pl.split ? tg.nown + WAVE : (ld.cols + 3) / 4);
-    pl.rec_bytes = (size_t)frames * ld.nsegs * ld.nstrips * 3 * WAVE * sizeof(float);
+    pl.rec_bytes = (size_t)sw.frames * ld.nsegs * ld.nstrips * 3 * WAVE * sizeof(float);
     // threads per tile from the geometry alone: a wave for tiles of a few hundred records, a block for larger ones (the last
     // tile of each axis takes the remainder; one tile may be the whole plane)
-    const long long worst = (long long)(ld.nsegs - (ny - 1) * (tile_rows / ld.rps)) * (tg.ngroups - (nx - 1) * (tile_cols / 4));
+    const long long worst = (long long)(ld.nsegs - (ts.ny - 1) * (ts.th / ld.rps)) * (tg.ngroups - (ts.nx - 1) * (ts.tw / 4));
     pl.fold_threads = worst > 512 ? BLOCK : WAVE;
     return pl;
 }
 
 template <typename T>
-static void launch_detect_tiles_t(hipStream_t s, const TilesPlan& pl, int frames, int mask, int pad, const PlaneDesc& x, const float* W,
-                                  const float* coef, const int* status, float* rec)
+static void launch_detect_tiles_t(const Sweep& sw, const TilesPlan& pl, const float* W, float* rec)
 {
-    for_each_detect_launch(pl, frames, mask, pad, [&](auto m, auto p, auto hc, auto vec, const SweepPart& sp) {
+    const PlaneDesc& x = sw.x;
+    for_each_detect_launch(pl, sw, [&](auto m, auto p, auto hc, auto vec, const SweepPart& sp) {
         WM_KLAUNCH((k_detect_tiles<T, decltype(m)::value, decltype(p)::value, decltype(hc)::value, decltype(vec)::value>), sp.grid,
-                   dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, W, sp.g, coef, status, rec);
+                   dim3(BLOCK), 0, sw.s, (const T*)x.p, x.pitch, x.fstride, W, sp.g, sw.coef, sw.status, rec);
     });
 }
 
-void launch_detect_tiles(hipStream_t s, const TilesPlan& pl, int frames, int mask, int pad, const PlaneDesc& x, const float* W,
-                         const float* coef, const int* status, float* rec)
+void launch_detect_tiles(const Sweep& sw, const TilesPlan& pl, const KeyBank& w, float* rec)
 {
-    WM_DISPATCH_T(x.dtype, launch_detect_tiles_t<T>(s, pl, frames, mask, pad, x, W, coef, status, rec));
+    WM_DISPATCH_T(sw.x.dtype, launch_detect_tiles_t<T>(sw, pl, w.W, rec));
 }
 
 void launch_tiles_fold(hipStream_t s, const TilesPlan& pl, int frames, const float* rec, const int* status, float* map, double* sums,

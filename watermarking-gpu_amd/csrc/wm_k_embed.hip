@@ -345,100 +345,95 @@ static ScalarsTail scalars_tail(const LaunchGeom& lg, unsigned* ticket, unsigned
     return ScalarsTail{ticket, ticket_strip, lg.nblk, lg.nsegs, lg.nstrips, smax, sss, sF, sqrt_n, scal, res, raw};
 }
 
-void launch_me_stats(hipStream_t s, const LaunchGeom& lg, int frames, const PlaneDesc& x, const float* W, int aligned_w,
-                     const float* coef, const int* status, float* pmax, double* pss, unsigned* ticket, unsigned* ticket_strip,
-                     float* smax, double* sss, float sF, double sqrt_n, EmbedScalars* scal, OpResult* res, RawSums* raw)
+void launch_me_stats(const Sweep& sw, const KeyBank& w, float* pmax, double* pss, unsigned* ticket, unsigned* ticket_strip, float* smax,
+                     double* sss, float sF, double sqrt_n, EmbedScalars* scal, OpResult* res, RawSums* raw)
 {
-    const int al = align_mode(lg, x.aligned && aligned_w);
-    const ScalarsTail tail = scalars_tail(lg, ticket, ticket_strip, smax, sss, sF, sqrt_n, scal, res, raw);
-    WM_DISPATCH_T(x.dtype, for_each_sweep_part(lg, frames, al, 1, [&](auto vec, const SweepPart& sp) {
-        WM_KLAUNCH((k_me_stats<T, decltype(vec)::value>), sp.grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, W, sp.g, coef, status,
-                   pmax, pss, tail);
+    const PlaneDesc& x = sw.x;
+    const int al = align_mode(sw.lg, x.aligned && w.aligned_w);
+    const ScalarsTail tail = scalars_tail(sw.lg, ticket, ticket_strip, smax, sss, sF, sqrt_n, scal, res, raw);
+    WM_DISPATCH_T(x.dtype, for_each_sweep_part(sw, al, 1, [&](auto vec, const SweepPart& sp) {
+        WM_KLAUNCH((k_me_stats<T, decltype(vec)::value>), sp.grid, dim3(BLOCK), 0, sw.s, (const T*)x.p, x.pitch, x.fstride, w.W, sp.g, sw.coef,
+                   sw.status, pmax, pss, tail);
     }));
 }
 
 template <typename T>
-static void launch_nvf_stats_t(hipStream_t s, const LaunchGeom& lg, int frames, const PlaneDesc& x, const float* W,
-                               int aligned_w, int pad, double* pss, const ScalarsTail& tail)
+static void launch_nvf_stats_t(const Sweep& sw, const KeyBank& w, double* pss, const ScalarsTail& tail)
 {
-    const int al = align_mode(lg, x.aligned && aligned_w);
-    for_mask_pad(1, pad, [&](auto, auto p) {
-        for_each_sweep_part(lg, frames, al, 1, [&](auto vec, const SweepPart& sp) {
-            WM_KLAUNCH((k_nvf_stats<T, decltype(p)::value, decltype(vec)::value>), sp.grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch,
-                       x.fstride, W, sp.g, pss, tail);
+    const PlaneDesc& x = sw.x;
+    const int al = align_mode(sw.lg, x.aligned && w.aligned_w);
+    for_mask_pad(1, sw.pad, [&](auto, auto p) {
+        for_each_sweep_part(sw, al, 1, [&](auto vec, const SweepPart& sp) {
+            WM_KLAUNCH((k_nvf_stats<T, decltype(p)::value, decltype(vec)::value>), sp.grid, dim3(BLOCK), 0, sw.s, (const T*)x.p, x.pitch,
+                       x.fstride, w.W, sp.g, pss, tail);
         });
     });
 }
-void launch_nvf_stats(hipStream_t s, const LaunchGeom& lg, int frames, const PlaneDesc& x, const float* W, int aligned_w,
-                      int pad, double* pss, unsigned* ticket, unsigned* ticket_strip, double* sss, float sF, double sqrt_n,
-                      EmbedScalars* scal, OpResult* res, RawSums* raw)
+void launch_nvf_stats(const Sweep& sw, const KeyBank& w, double* pss, unsigned* ticket, unsigned* ticket_strip, double* sss, float sF,
+                      double sqrt_n, EmbedScalars* scal, OpResult* res, RawSums* raw)
 {
-    const ScalarsTail tail = scalars_tail(lg, ticket, ticket_strip, nullptr, sss, sF, sqrt_n, scal, res, raw);
-    WM_DISPATCH_T(x.dtype, launch_nvf_stats_t<T>(s, lg, frames, x, W, aligned_w, pad, pss, tail));
+    const ScalarsTail tail = scalars_tail(sw.lg, ticket, ticket_strip, nullptr, sss, sF, sqrt_n, scal, res, raw);
+    WM_DISPATCH_T(sw.x.dtype, launch_nvf_stats_t<T>(sw, w, pss, tail));
 }
 
 template <typename TX, typename TB, int NCH>
-static bool launch_embed_tt(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x,
-                            const float* W, int aligned_w, const PlaneDesc& base, const PlaneDesc& out, const float* coef,
-                            const int* status, const EmbedScalars* scal, const HandOver* ho)
+static bool launch_embed_tt(const Sweep& sw, const KeyBank& w, const EmbedPlanes& ep, const HandOver* ho)
 {
-    const int al = align_mode(lg, x.aligned && aligned_w && base.aligned && out.aligned);
-    const bool bx = NCH == 1 && std::is_same<TX, TB>::value && same_plane(x, base);
+    const LaunchGeom& lg = sw.lg;
+    const PlaneDesc& x = sw.x;
+    const int al = align_mode(lg, x.aligned && w.aligned_w && ep.base.aligned && ep.out.aligned);
+    const bool bx = NCH == 1 && std::is_same<TX, TB>::value && same_plane(x, ep.base);
     const HandOver none{nullptr, 0, nullptr, nullptr, nullptr};
     if constexpr (NCH == 1 && std::is_same<TX, float>::value && std::is_same<TB, float>::value) {
         // Gram hand-over: every strip on the aligned path (one launch), 3x3 windows, a core, segments of two rows or more; two
         // frames or more (measured at 4K: one frame -3 %, two +2 %, four +6..9 %, eight and more +9..11 % -- a one-frame launch of
         // k_gram_ho is as latency-bound as the k_gram it replaces)
-        if (ho && ho->rec && ho->dig && frames >= 2 && al == 2 && lg.nfull > 0 && pad == 1 && lg.rps >= 2 && lg.rows >= 4 && lg.cols >= 5 && lg.row_lo == 0 && lg.row_hi == lg.rows) {
-            const SweepPart pv_ = sweep_part(lg, frames, true, al, 1);
+        if (ho && ho->rec && ho->dig && sw.frames >= 2 && al == 2 && lg.nfull > 0 && sw.pad == 1 && lg.rps >= 2 && lg.rows >= 4 && lg.cols >= 5 && lg.row_lo == 0 && lg.row_hi == lg.rows) {
+            const SweepPart pv_ = sweep_part(lg, sw.frames, true, al, 1);
             const Geom g = pv_.g;
 #define EMB_HO(MASK)                                                                                                            \
             do {                                                                                                                \
-                if (bx) WM_KLAUNCH((k_embed<float, float, 1, MASK, 1, true, true, true>), pv_.grid, dim3(BLOCK), 0, s, (const float*)x.p, x.pitch, \
-                                   x.fstride, W, base, out, g, coef, status, scal, *ho);                                         \
-                else WM_KLAUNCH((k_embed<float, float, 1, MASK, 1, true, false, true>), pv_.grid, dim3(BLOCK), 0, s, (const float*)x.p, x.pitch,  \
-                                x.fstride, W, base, out, g, coef, status, scal, *ho);                                            \
+                if (bx) WM_KLAUNCH((k_embed<float, float, 1, MASK, 1, true, true, true>), pv_.grid, dim3(BLOCK), 0, sw.s, (const float*)x.p, x.pitch, \
+                                   x.fstride, w.W, ep.base, ep.out, g, sw.coef, sw.status, ep.scal, *ho);                        \
+                else WM_KLAUNCH((k_embed<float, float, 1, MASK, 1, true, false, true>), pv_.grid, dim3(BLOCK), 0, sw.s, (const float*)x.p, x.pitch,  \
+                                x.fstride, w.W, ep.base, ep.out, g, sw.coef, sw.status, ep.scal, *ho);                           \
             } while (0)
-            if (mask == 0) EMB_HO(0); else EMB_HO(1);
+            if (sw.mask == 0) EMB_HO(0); else EMB_HO(1);
 #undef EMB_HO
             return true;
         }
     }
-    for_each_embed_launch<NCH>(lg, frames, mask, pad, al, bx, [&](auto m, auto p, auto vec, auto nch, auto base_is_x, const SweepPart& sp) {
+    for_each_embed_launch<NCH>(sw, al, bx, [&](auto m, auto p, auto vec, auto nch, auto base_is_x, const SweepPart& sp) {
         WM_KLAUNCH((k_embed<TX, TB, decltype(nch)::value, decltype(m)::value, decltype(p)::value, decltype(vec)::value, decltype(base_is_x)::value>),
-                   sp.grid, dim3(BLOCK), 0, s, (const TX*)x.p, x.pitch, x.fstride, W, base, out, sp.g, coef, status, scal, none);
+                   sp.grid, dim3(BLOCK), 0, sw.s, (const TX*)x.p, x.pitch, x.fstride, w.W, ep.base, ep.out, sp.g, sw.coef, sw.status, ep.scal, none);
     });
     return false;
 }
-bool launch_embed(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* W,
-                  int aligned_w, const PlaneDesc& base, const PlaneDesc& out, const float* coef, const int* status,
-                  const EmbedScalars* scal, const HandOver* ho)
+bool launch_embed(const Sweep& sw, const KeyBank& w, const EmbedPlanes& ep, const HandOver* ho)
 {
     bool handed = false;
-    for_embed_planes(x, base, [&](auto t, auto nch) {
-        handed = launch_embed_tt<decltype(t), decltype(t), decltype(nch)::value>(s, lg, frames, mask, pad, x, W, aligned_w, base, out, coef, status, scal, ho);
+    for_embed_planes(sw.x, ep.base, [&](auto t, auto nch) {
+        handed = launch_embed_tt<decltype(t), decltype(t), decltype(nch)::value>(sw, w, ep, ho);
     });
     return handed;
 }
 
 template <typename T>
-static void launch_mask_t(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x,
-                          const float* coef, const int* status, const EmbedScalars* scal, const PlaneDesc& mo,
-                          const PlaneDesc& eo)
+static void launch_mask_t(const Sweep& sw, const EmbedScalars* scal, const PlaneDesc& mo, const PlaneDesc& eo)
 {
+    const PlaneDesc& x = sw.x;
     // exercises the same two input paths as the production kernels (DPP for aligned full strips, LDS otherwise)
-    const int al = align_mode(lg, x.aligned != 0);
-    for_mask_pad(mask, pad, [&](auto m, auto p) {
-        for_each_sweep_part(lg, frames, al, 0, [&](auto vec, const SweepPart& sp) {
-            WM_KLAUNCH((k_mask<T, decltype(m)::value, decltype(p)::value, decltype(vec)::value>), sp.grid, dim3(BLOCK), 0, s, (const T*)x.p,
-                       x.pitch, x.fstride, sp.g, coef, status, scal, mo, eo);
+    const int al = align_mode(sw.lg, x.aligned != 0);
+    for_mask_pad(sw.mask, sw.pad, [&](auto m, auto p) {
+        for_each_sweep_part(sw, al, 0, [&](auto vec, const SweepPart& sp) {
+            WM_KLAUNCH((k_mask<T, decltype(m)::value, decltype(p)::value, decltype(vec)::value>), sp.grid, dim3(BLOCK), 0, sw.s, (const T*)x.p,
+                       x.pitch, x.fstride, sp.g, sw.coef, sw.status, scal, mo, eo);
         });
     });
 }
-void launch_mask(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* coef,
-                 const int* status, const EmbedScalars* scal, const PlaneDesc& mo, const PlaneDesc& eo)
+void launch_mask(const Sweep& sw, const EmbedScalars* scal, const PlaneDesc& mo, const PlaneDesc& eo)
 {
-    WM_DISPATCH_T(x.dtype, launch_mask_t<T>(s, lg, frames, mask, pad, x, coef, status, scal, mo, eo));
+    WM_DISPATCH_T(sw.x.dtype, launch_mask_t<T>(sw, scal, mo, eo));
 }
 
 }  // namespace wmk

@@ -11,11 +11,8 @@
 // with the key-dependent half inside the row step: m and the base row are formed / read once, then every key of the group takes
 // its W row and stores its copy of y.  Key groups are a grid axis, as in k_detect_keys: the groups of one tile are consecutive
 // blocks of one XCD, so the re-reads of x and base are L2 hits.
-#include "wm_march.hpp"
+#include "wm_embed_march.hpp"   // (WM_RING3, the ring length of the 3-row x windows on the aligned path, and the launch loop)
 
-#ifndef WM_RING3
-#define WM_RING3 UNROLL   // (as wm_k_embed.hip) ring length of the 3-row x windows on the aligned path
-#endif
 #ifndef WM_EMBED_KEYS_G
 #define WM_EMBED_KEYS_G 4   // keys per group (registers vs. x / base re-reads)
 #endif
@@ -430,71 +427,47 @@ size_t embed_keys_scratch_bytes(int frames, int nkeys, int rstride)
 }
 
 template <typename T>
-static void launch_stats_keys_t(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, int al,
-                                const EKeysArgs& ka, const float* coef, const int* status)
+static void launch_stats_keys_t(const Sweep& sw, int al, const EKeysArgs& ka)
 {
+    const PlaneDesc& x = sw.x;
     // every grid times the key groups
-    for_mask_pad(mask, pad, [&](auto m, auto p) {
-        for_each_sweep_part(lg, frames, al, 1, [&](auto vec, const SweepPart& sp) {
+    for_mask_pad(sw.mask, sw.pad, [&](auto m, auto p) {
+        for_each_sweep_part(sw, al, 1, [&](auto vec, const SweepPart& sp) {
             WM_KLAUNCH((k_stats_keys<T, decltype(m)::value, decltype(p)::value, decltype(vec)::value>), dim3(sp.grid.x * (unsigned)ka.ngroups),
-                       dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, ka, sp.g, coef, status);
+                       dim3(BLOCK), 0, sw.s, (const T*)x.p, x.pitch, x.fstride, ka, sp.g, sw.coef, sw.status);
         });
     });
 }
 
-int launch_stats_keys(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* Wbank,
-                      long long kstride, int nkeys, int aligned_w, const float* coef, const int* status, void* scratch, int rstride)
+int launch_stats_keys(const Sweep& sw, const KeyBank& bank, void* scratch, int rstride)
 {
+    const LaunchGeom& lg = sw.lg;
     // k_me_stats' / k_nvf_stats' geometry and record layout (launch_me_stats): the fold's order depends on it
     if (lg.nblk > rstride || lg.nstrips * lg.nsegs > rstride || lg.nstrips > EKEYS_MAX_STRIPS) return -1;
-    const EKeysArgs ka = ekeys_args(Wbank, kstride, nkeys, frames, scratch, rstride);
-    const int al = align_mode(lg, x.aligned && aligned_w);
-    WM_DISPATCH_T(x.dtype, launch_stats_keys_t<T>(s, lg, frames, mask, pad, x, al, ka, coef, status));
+    const EKeysArgs ka = ekeys_args(bank.W, bank.kstride, bank.nkeys, sw.frames, scratch, rstride);
+    const int al = align_mode(lg, sw.x.aligned && bank.aligned_w);
+    WM_DISPATCH_T(sw.x.dtype, launch_stats_keys_t<T>(sw, al, ka));
     return 0;
 }
 
-void launch_embed_keys_fold(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int nkeys, const int* status, void* scratch,
-                            int rstride, float sF, double sqrt_n, OpResult* res)
+void launch_embed_keys_fold(const Sweep& sw, int nkeys, void* scratch, int rstride, float sF, double sqrt_n, OpResult* res)
 {
-    const EKeysArgs ka = ekeys_args(nullptr, 0, nkeys, frames, scratch, rstride);
-    const int quad = frames >= 4 ? 1 : 0;  // (sweep_part's quad mapping of the stats sweep)
-    WM_KLAUNCH(k_embed_keys_fold, dim3((unsigned)(frames * nkeys)), dim3(BLOCK), 0, s, ka, quad, lg.nblk, lg.nsegs, lg.nstrips,
-               mask == 0 ? 1 : 0, sF, sqrt_n, mask == 0 ? status : nullptr, res);
+    const LaunchGeom& lg = sw.lg;
+    const EKeysArgs ka = ekeys_args(nullptr, 0, nkeys, sw.frames, scratch, rstride);
+    const int quad = sw.frames >= 4 ? 1 : 0;  // (sweep_part's quad mapping of the stats sweep)
+    WM_KLAUNCH(k_embed_keys_fold, dim3((unsigned)(sw.frames * nkeys)), dim3(BLOCK), 0, sw.s, ka, quad, lg.nblk, lg.nsegs, lg.nstrips,
+               sw.mask == 0 ? 1 : 0, sF, sqrt_n, sw.mask == 0 ? sw.status : nullptr, res);
 }
 
-template <typename T>
-static void launch_embed_keys_t(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, int aligned_w,
-                                const PlaneDesc& base, const PlaneDesc& out, const EKeysArgs& ka, const float* coef, const int* status)
+void launch_embed_keys(const Sweep& sw, const KeyBank& bank, const EmbedPlanes& ep, void* scratch, int rstride)
 {
-    // k_embed's launch plan (launch_embed_tt, no hand-over), once per channel of the base
-    const int al = align_mode(lg, x.aligned && aligned_w && base.aligned && out.aligned);
-    const bool bx = base.channels == 1 && same_plane(x, base);
-    for (int ch = 0; ch < base.channels; ++ch) {
-        PlaneDesc bc = base, oc = out;
-        bc.p = static_cast<const T*>(base.p) + (long long)ch * base.cstride;
-        oc.p = static_cast<const T*>(out.p) + (long long)ch * out.cstride;
-        bc.channels = oc.channels = 1;
-        // every grid times the key groups
-        for_mask_pad(mask, pad, [&](auto m, auto p) {
-            auto sweep = [&](auto base_is_x) {
-                for_each_sweep_part(lg, frames, al, 1, [&](auto vec, const SweepPart& sp) {
-                    WM_KLAUNCH((k_embed_keys<T, decltype(m)::value, decltype(p)::value, decltype(vec)::value, decltype(base_is_x)::value>),
-                               dim3(sp.grid.x * (unsigned)ka.ngroups), dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, ka, bc, oc, sp.g,
-                               coef, status);
-                });
-            };
-            if (bx) sweep(std::true_type{}); else sweep(std::false_type{});
-        });
-    }
-}
-
-void launch_embed_keys(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* Wbank,
-                       long long kstride, int nkeys, int aligned_w, const PlaneDesc& base, const PlaneDesc& out, const float* coef,
-                       const int* status, void* scratch, int rstride)
-{
-    const EKeysArgs ka = ekeys_args(Wbank, kstride, nkeys, frames, scratch, rstride);
-    // (the API layer admits same-dtype planes only, as for wm_embed)
-    WM_DISPATCH_T(x.dtype, launch_embed_keys_t<T>(s, lg, frames, mask, pad, x, aligned_w, base, out, ka, coef, status));
+    const PlaneDesc& x = sw.x;
+    const EKeysArgs ka = ekeys_args(bank.W, bank.kstride, bank.nkeys, sw.frames, scratch, rstride);
+    WM_DISPATCH_T(x.dtype, for_each_embed_group_launch<T>(sw, bank.aligned_w, ep, ka.ngroups, [&](auto m, auto p, auto vec, auto base_is_x, dim3 grid, const Geom& g,
+                                                                                                 const PlaneDesc& bc, const PlaneDesc& oc) {
+        WM_KLAUNCH((k_embed_keys<T, decltype(m)::value, decltype(p)::value, decltype(vec)::value, decltype(base_is_x)::value>), grid, dim3(BLOCK), 0,
+                   sw.s, (const T*)x.p, x.pitch, x.fstride, ka, bc, oc, g, sw.coef, sw.status);
+    }));
 }
 
 int embed_keys_group(void) { return EKG; }

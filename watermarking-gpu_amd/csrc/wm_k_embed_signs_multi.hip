@@ -208,43 +208,23 @@ bool embed_signs_multi_grid_fits(const LaunchGeom& lg, int frames, int ncopies)
     const long long ng = signs_multi_groups(ncopies);
     bool ok = true;
     for (int al = 0; al <= 2; ++al)
-        for_each_sweep_part(lg, frames, al, 1, [&](auto, const SweepPart& sp) { ok = ok && (long long)sp.grid.x * ng <= 0x7fffffffLL; });
+        for (int vec = 0; vec <= 1; ++vec) {
+            const SweepPart sp = sweep_part(lg, frames, vec != 0, al, 1);
+            ok = ok && (!sp.run || (long long)sp.grid.x * ng <= 0x7fffffffLL);
+        }
     return ok;
 }
 
-template <typename T>
-static void launch_embed_signs_multi_t(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* W,
-                                       int aligned_w, const PlaneDesc& base, const PlaneDesc& out, const float* coef, const int* status,
-                                       const EmbedScalars* scal, const SignsMultiArgs& sa)
+void launch_embed_signs_multi(const Sweep& sw, const KeyBank& w, const EmbedPlanes& ep, const signed char* signs, int ncopies, const TileShape& ts)
 {
+    const PlaneDesc& x = sw.x;
+    const SignsMultiArgs sa{signs, ts.th, ts.tw, ts.ny, ts.nx, ncopies, signs_multi_groups(ncopies)};
     // k_embed_signs' launch plan, once per channel of the base, every grid times the copy groups
-    const int al = align_mode(lg, x.aligned && aligned_w && base.aligned && out.aligned);
-    const bool bx = base.channels == 1 && same_plane(x, base);
-    for (int ch = 0; ch < base.channels; ++ch) {
-        PlaneDesc bc = base, oc = out;
-        bc.p = static_cast<const T*>(base.p) + (long long)ch * base.cstride;
-        oc.p = static_cast<const T*>(out.p) + (long long)ch * out.cstride;
-        bc.channels = oc.channels = 1;
-        for_mask_pad(mask, pad, [&](auto m, auto p) {
-            auto sweep = [&](auto base_is_x) {
-                for_each_sweep_part(lg, frames, al, 1, [&](auto vec, const SweepPart& sp) {
-                    WM_KLAUNCH((k_embed_signs_multi<T, decltype(m)::value, decltype(p)::value, decltype(vec)::value, decltype(base_is_x)::value>),
-                               dim3(sp.grid.x * (unsigned)sa.ngroups), dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, W, bc, oc, sp.g, coef,
-                               status, scal, sa);
-                });
-            };
-            if (bx) sweep(std::true_type{}); else sweep(std::false_type{});
-        });
-    }
-}
-
-void launch_embed_signs_multi(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* W,
-                              int aligned_w, const PlaneDesc& base, const PlaneDesc& out, const float* coef, const int* status,
-                              const EmbedScalars* scal, const signed char* signs, int ncopies, int tile_rows, int tile_cols, int ny, int nx)
-{
-    const SignsMultiArgs sa{signs, tile_rows, tile_cols, ny, nx, ncopies, signs_multi_groups(ncopies)};
-    // (the API layer admits same-dtype planes only, as for wm_embed)
-    WM_DISPATCH_T(x.dtype, launch_embed_signs_multi_t<T>(s, lg, frames, mask, pad, x, W, aligned_w, base, out, coef, status, scal, sa));
+    WM_DISPATCH_T(x.dtype, for_each_embed_group_launch<T>(sw, w.aligned_w, ep, sa.ngroups, [&](auto m, auto p, auto vec, auto base_is_x, dim3 grid, const Geom& g,
+                                                                                              const PlaneDesc& bc, const PlaneDesc& oc) {
+        WM_KLAUNCH((k_embed_signs_multi<T, decltype(m)::value, decltype(p)::value, decltype(vec)::value, decltype(base_is_x)::value>), grid, dim3(BLOCK), 0,
+                   sw.s, (const T*)x.p, x.pitch, x.fstride, w.W, bc, oc, g, sw.coef, sw.status, ep.scal, sa);
+    }));
 }
 
 int embed_signs_group(void) { return SMG; }

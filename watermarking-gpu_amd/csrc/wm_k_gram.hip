@@ -540,33 +540,36 @@ int handover_seam_blocks(const LaunchGeom& lg)
     return n > 0 ? n : 1;  // one strip: a block without seams still folds the wave records
 }
 
-void launch_gram_ho(hipStream_t s, const LaunchGeom& lg, int frames, const PlaneDesc& y, const HandOver& ho, double* pborder,
-                    unsigned* ticket, float* coef, int* status, double* gram_tot)
+void launch_gram_ho(const Sweep& sw, const HandOver& ho, double* pborder, unsigned* ticket, float* coef, int* status, double* gram_tot)
 {
+    const LaunchGeom& lg = sw.lg;
+    const PlaneDesc& y = sw.x;
     // the geometry of the embed's aligned launch (every strip on the aligned path: launch_embed's hand-over condition)
-    const SweepPart pv = sweep_part(lg, frames, true, 2);
+    const SweepPart pv = sweep_part(lg, sw.frames, true, 2);
     const int nsb = handover_seam_blocks(lg);
     const SolveTail tail{ticket, lg.nbb + nsb, lg.nbb, coef, status, gram_tot};
-    const dim3 grid((unsigned)((lg.nbb + nsb) * frames), 1, 1);
-    WM_KLAUNCH(k_gram_ho, grid, dim3(BLOCK), 0, s, (const float*)y.p, y.pitch, y.fstride, pv.g, lg.nbb, nsb, ho, pborder, tail);
+    const dim3 grid((unsigned)((lg.nbb + nsb) * sw.frames), 1, 1);
+    WM_KLAUNCH(k_gram_ho, grid, dim3(BLOCK), 0, sw.s, (const float*)y.p, y.pitch, y.fstride, pv.g, lg.nbb, nsb, ho, pborder, tail);
 }
 
-void launch_gram(hipStream_t s, const LaunchGeom& lg, int frames, const PlaneDesc& x, double* pmain, double* pborder,
-                 unsigned* ticket, float* coef, int* status, double* gram_tot, const int* redo)
+void launch_gram(const Sweep& sw, double* pmain, double* pborder, unsigned* ticket, float* coef, int* status, double* gram_tot,
+                 const int* redo)
 {
+    const LaunchGeom& lg = sw.lg;
+    const PlaneDesc& x = sw.x;
     // the border blocks ride in the first launch of the sweep (the aligned-path one when it exists)
     const int al = align_mode(lg, x.aligned != 0);
     // every block of both launches takes a ticket of its frame; the last one folds the partials and solves
     const SolveTail tail{ticket, lg.nblk + lg.nbb, lg.nbb, coef, status, gram_tot};
     int nbb = lg.nbb;
-    for_each_sweep_part(lg, frames, al, 0, [&](auto vec, const SweepPart& sp) {
+    for_each_sweep_part(sw, al, 0, [&](auto vec, const SweepPart& sp) {
         constexpr bool VEC = decltype(vec)::value;
         Geom g = sp.g;
         g.frame_fastest = 0;  // the Gram sweep reads no W: keep a frame's tiles together (halo rows stay in L2)
-        const dim3 grid(sp.grid.x + nbb * frames, 1, 1);
-        if (redo) WM_DISPATCH_T(x.dtype, WM_KLAUNCH((k_gram_redo<T, VEC>), grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, g, nbb,
+        const dim3 grid(sp.grid.x + nbb * sw.frames, 1, 1);
+        if (redo) WM_DISPATCH_T(x.dtype, WM_KLAUNCH((k_gram_redo<T, VEC>), grid, dim3(BLOCK), 0, sw.s, (const T*)x.p, x.pitch, x.fstride, g, nbb,
                                                     pmain, pborder, tail, redo));
-        else WM_DISPATCH_T(x.dtype, WM_KLAUNCH((k_gram<T, VEC>), grid, dim3(BLOCK), 0, s, (const T*)x.p, x.pitch, x.fstride, g, nbb, pmain,
+        else WM_DISPATCH_T(x.dtype, WM_KLAUNCH((k_gram<T, VEC>), grid, dim3(BLOCK), 0, sw.s, (const T*)x.p, x.pitch, x.fstride, g, nbb, pmain,
                                                pborder, tail));
         nbb = 0;
     });

@@ -73,6 +73,36 @@ struct EmbedScalars {
     float maxe;  // max|e| (ME) or 1
 };
 
+// ---- the launch records: what the sweep launchers below share, filled once per call (wm_api.hip) and described here only ----
+// What every launcher of a call is told about it.  coef / status: the Gram sweep's solve per frame as the sweeps behind it read
+// it; null where the call's route has no solve (the embed side under NVF)
+struct Sweep {
+    hipStream_t s;
+    LaunchGeom lg;
+    int frames;
+    int mask, pad;       // the kernels' mask index (0 ME, 1 NVF) and the half width of the window (ME: 1)
+    PlaneDesc x;         // the grey input plane
+    const float* coef;   // [frames][8]
+    const int* status;   // [frames]
+};
+// The key side of a sweep: one W plane (the context's own: a bank of one) or a bank of nkeys planes kstride elements apart.
+// aligned_w: the planes may be addressed as buffers with 32-bit offsets
+struct KeyBank {
+    const float* W;
+    long long kstride;
+    int nkeys;
+    int aligned_w;
+};
+// The planes an embed sweep reads and writes beside x, and the frames' scalars of the stats sweep (null: the launcher has its own)
+struct EmbedPlanes {
+    PlaneDesc base, out;
+    const EmbedScalars* scal;
+};
+// Tile shape and tiles per axis (wm_tiles_shape): pixel (r, c) belongs to tile (min(r / th, ny - 1), min(c / tw, nx - 1))
+struct TileShape {
+    int th, tw, ny, nx;
+};
+
 // raw totals of the stats and detect sweeps, written by the fold tails beside the finished scalars: what a row band of a
 // sharded image contributes to the all-reduce (wm_band_*)
 struct RawSums {
@@ -152,14 +182,13 @@ int launch_fused_detect(hipStream_t s, const FusedGeom& fg, const FusedScratch& 
                         const float* W, OpResult* res);
 
 // redo: frames with redo[f] == 0 are skipped (k_gram_redo, the fallback of a checked hand-over), null: every frame (k_gram)
-void launch_gram(hipStream_t s, const LaunchGeom& lg, int frames, const PlaneDesc& x, double* pmain, double* pborder,
-                 unsigned* ticket, float* coef, int* status, double* gram_tot, const int* redo = nullptr);
-void launch_me_stats(hipStream_t s, const LaunchGeom& lg, int frames, const PlaneDesc& x, const float* W, int aligned_w,
-                     const float* coef, const int* status, float* pmax, double* pss, unsigned* ticket, unsigned* ticket_strip,
-                     float* smax, double* sss, float sF, double sqrt_n, EmbedScalars* scal, OpResult* res, RawSums* raw);
-void launch_nvf_stats(hipStream_t s, const LaunchGeom& lg, int frames, const PlaneDesc& x, const float* W, int aligned_w,
-                      int pad, double* pss, unsigned* ticket, unsigned* ticket_strip, double* sss, float sF, double sqrt_n,
-                      EmbedScalars* scal, OpResult* res, RawSums* raw);
+// coef / status (here and in launch_gram_ho): where the solve tail writes what the later sweeps read as sw.coef / sw.status
+void launch_gram(const Sweep& sw, double* pmain, double* pborder, unsigned* ticket, float* coef, int* status, double* gram_tot,
+                 const int* redo = nullptr);
+void launch_me_stats(const Sweep& sw, const KeyBank& w, float* pmax, double* pss, unsigned* ticket, unsigned* ticket_strip, float* smax,
+                     double* sss, float sF, double sqrt_n, EmbedScalars* scal, OpResult* res, RawSums* raw);
+void launch_nvf_stats(const Sweep& sw, const KeyBank& w, double* pss, unsigned* ticket, unsigned* ticket_strip, double* sss, float sF,
+                      double sqrt_n, EmbedScalars* scal, OpResult* res, RawSums* raw);
 // Gram hand-over from an embed to the detector that reads its output (wm_set_handover, WM_MEM_SLOT_OUT): k_embed holds every
 // row of y in registers, so it also accumulates y's 13 lag sums over the products that stay inside a wave's tile (its strip's
 // columns x its segment's rows and the two rows behind them) and leaves one record per wave, plus a compact copy of the two
@@ -190,26 +219,19 @@ struct DigCheck {
 };
 int handover_seam_blocks(const LaunchGeom& lg);   // seam blocks per frame of k_gram_ho for this geometry
 // returns true when the hand-over instantiation ran (f32 grey planes on the aligned path, p = 3, segments of >= 2 rows)
-bool launch_embed(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* W,
-                  int aligned_w, const PlaneDesc& base, const PlaneDesc& out, const float* coef, const int* status,
-                  const EmbedScalars* scal, const HandOver* ho = nullptr);
-// lg: the geometry of the embed that left the wave records
-void launch_gram_ho(hipStream_t s, const LaunchGeom& lg, int frames, const PlaneDesc& y, const HandOver& ho, double* pborder,
-                    unsigned* ticket, float* coef, int* status, double* gram_tot);
-void launch_mask(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* coef,
-                 const int* status, const EmbedScalars* scal, const PlaneDesc& mo, const PlaneDesc& eo);
+bool launch_embed(const Sweep& sw, const KeyBank& w, const EmbedPlanes& ep, const HandOver* ho = nullptr);
+// sw.x: y, the plane the embed wrote; sw.lg: the geometry of the embed that left the wave records
+void launch_gram_ho(const Sweep& sw, const HandOver& ho, double* pborder, unsigned* ticket, float* coef, int* status, double* gram_tot);
+void launch_mask(const Sweep& sw, const EmbedScalars* scal, const PlaneDesc& mo, const PlaneDesc& eo);
 // dc / mode: 0 = the ordinary sweep (dc unused); 1 = the checking instance (f32 planes on the overlapped aligned 3x3 path:
 // detect_checkable); 2 = k_detect_redo, the frames with dc->redo[f] != 0 only
-void launch_detect(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* W,
-                   int aligned_w, const float* coef, const int* status, double* pcorr, unsigned* ticket, unsigned* ticket_strip,
-                   double* scorr, OpResult* res, RawSums* raw, const DigCheck* dc = nullptr, int mode = 0);
-bool detect_checkable(const LaunchGeom& lg, int mask, int pad, const PlaneDesc& x, int aligned_w);
+void launch_detect(const Sweep& sw, const KeyBank& w, double* pcorr, unsigned* ticket, unsigned* ticket_strip, double* scorr, OpResult* res,
+                   RawSums* raw, const DigCheck* dc = nullptr, int mode = 0);
+bool detect_checkable(const Sweep& sw, int aligned_w);
 // one image against a bank of keys (wm_detect_keys, wm_k_detect_keys.hip): k_detect's sweep for every key of the bank, key
 // groups as a grid axis, then one fold block per (frame, key) into res[frame * nkeys + key].  part: [frames][2 nkeys + 1][rstride]
 // doubles of scratch.  Returns -1 when the sweep's records exceed rstride (nothing is launched)
-int launch_detect_keys(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x,
-                       const float* Wbank, long long kstride, int nkeys, int aligned_w, const float* coef, const int* status,
-                       double* part, int rstride, OpResult* res);
+int launch_detect_keys(const Sweep& sw, const KeyBank& bank, double* part, int rstride, OpResult* res);
 int detect_keys_group(void);  // keys per group of k_detect_keys (compile-time KG)
 // k_keys_fold: one block per (frame, key) folds the records part [frames][nkeys][rstride][2] / partw [frames][rstride] of a
 // sweep in k_detect's order into res[frame * nkeys + key]; a strip-level fold (quad) covers KEYS_MAX_STRIPS strips
@@ -220,18 +242,17 @@ void launch_keys_fold(hipStream_t s, const double* part, const double* partw, in
 // (wm_detect_offsets, wm_k_detect_offsets.hip): offset (oy0 + i, ox0 + j), i < ny, j < nx, scores the image against the window
 // key[oy : oy + rows, ox : ox + cols] -- k_detect_keys' sweep with groups of horizontally adjacent offsets as a grid axis, then
 // k_keys_fold into res[frame * ny * nx + i * nx + j].  The caller has checked that every window lies inside the plane.
-// aligned_w: the KEY plane's extent allows 32-bit offsets.  part: [frames][2 ny nx + 1][rstride] doubles of scratch.  Returns -1
-// when the sweep's records exceed rstride (nothing is launched)
-int launch_detect_offsets(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x,
-                          const float* key, int key_cols, int oy0, int ox0, int ny, int nx, int aligned_w, const float* coef,
-                          const int* status, double* part, int rstride, OpResult* res);
+// key: the one plane (nkeys 1, kstride unused), aligned_w: the KEY plane's extent allows 32-bit offsets.  part: [frames][2 ny nx + 1][rstride]
+// doubles of scratch.  Returns -1 when the sweep's records exceed rstride (nothing is launched)
+int launch_detect_offsets(const Sweep& sw, const KeyBank& key, int key_cols, int oy0, int ox0, int ny, int nx, double* part, int rstride,
+                          OpResult* res);
 int detect_offsets_group(void);  // offsets per group of k_detect_offsets' shared-row instances (compile-time OG)
 // the detector's three sums per tile of the frame (wm_detect_tiles, wm_k_detect_tiles.hip).  k_detect_tiles is k_detect's sweep
 // with segments whose height divides tile_rows; every lane leaves its f32 partials in rec [frames][nsegs][nstrips][3][64], and
 // k_tiles_fold adds each tile's records in a fixed order in f64 into map [frames][ny][nx] (and sums [frames][ny][nx][3], may be
-// null) on the device and res[frame] = {status, 0}.  Pixel (r, c) belongs to tile (min(r / th, ny - 1), min(c / tw, nx - 1))
+// null) on the device and res[frame] = {status, 0}
 struct TileGeom {
-    int th, tw, ny, nx;        // tile shape and tiles per axis (wm_tiles_shape)
+    int th, tw, ny, nx;        // the call's TileShape
     int rps, nsegs, nstrips;   // the sweep's record geometry: segments of rps rows (rps divides th), strips
     int layout;                // who owns a column group of 4: 0 = strips of 256, 1 = overlapped strips, 2 = overlapped + one generic strip
     int nown;                  // layouts 1, 2: column groups the overlapped strips own
@@ -243,11 +264,9 @@ struct TilesPlan : DetectPlan {  // the sweep's geometry: strips as every detect
     int fold_threads;          // threads per tile of k_tiles_fold: 64 or 256
 };
 int tiles_segment_rows(int tile_rows);  // the largest divisor of tile_rows in 8 .. 48 (tile_rows is a multiple of 8)
-// lg: make_geom's geometry of the call (the plan replaces its segments)
-TilesPlan tiles_plan(const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, int aligned_w, int tile_rows, int tile_cols,
-                     int ny, int nx);
-void launch_detect_tiles(hipStream_t s, const TilesPlan& pl, int frames, int mask, int pad, const PlaneDesc& x, const float* W,
-                         const float* coef, const int* status, float* rec);
+// sw.lg: make_geom's geometry of the call (the plan replaces its segments; the launchers that take a plan sweep on pl.ld)
+TilesPlan tiles_plan(const Sweep& sw, int aligned_w, const TileShape& ts);
+void launch_detect_tiles(const Sweep& sw, const TilesPlan& pl, const KeyBank& w, float* rec);
 void launch_tiles_fold(hipStream_t s, const TilesPlan& pl, int frames, const float* rec, const int* status, float* map, double* sums,
                        OpResult* res);
 // the detector's three sums per tile of the frame AND per key of a bank (wm_detect_keys_tiles, wm_k_detect_keys_tiles.hip):
@@ -257,8 +276,7 @@ void launch_tiles_fold(hipStream_t s, const TilesPlan& pl, int frames, const flo
 // device and res[frame] = {status, 0}.  keys_tiles_grids_fit: both grids of such a call fit 31 bits (from the shapes alone)
 size_t keys_tiles_rec_bytes(const TilesPlan& pl, int frames, int nkeys);
 bool keys_tiles_grids_fit(int rows, int cols, int tile_rows, int frames, int nkeys, int ny, int nx);
-void launch_detect_keys_tiles(hipStream_t s, const TilesPlan& pl, int frames, int mask, int pad, const PlaneDesc& x, const float* Wbank,
-                              long long kstride, int nkeys, const float* coef, const int* status, float* rec);
+void launch_detect_keys_tiles(const Sweep& sw, const TilesPlan& pl, const KeyBank& bank, float* rec);
 void launch_keys_tiles_fold(hipStream_t s, const TilesPlan& pl, int frames, int nkeys, const float* rec, const int* status, float* map,
                             double* sums, OpResult* res);
 // one image embedded with every key of a bank (wm_embed_keys, wm_k_embed_keys.hip).  The image side is wm_embed's (launch_gram:
@@ -267,32 +285,24 @@ void launch_keys_tiles_fold(hipStream_t s, const TilesPlan& pl, int frames, int 
 // key: copy (frame, key) is frame frame * nkeys + key of `out`).  scratch: embed_keys_scratch_bytes of device memory, the same
 // for the three launches.  launch_stats_keys returns -1 when the sweep's records exceed rstride (nothing is launched)
 size_t embed_keys_scratch_bytes(int frames, int nkeys, int rstride);
-int launch_stats_keys(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* Wbank,
-                      long long kstride, int nkeys, int aligned_w, const float* coef, const int* status, void* scratch, int rstride);
-void launch_embed_keys_fold(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int nkeys, const int* status, void* scratch,
-                            int rstride, float sF, double sqrt_n, OpResult* res);
-void launch_embed_keys(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* Wbank,
-                       long long kstride, int nkeys, int aligned_w, const PlaneDesc& base, const PlaneDesc& out, const float* coef,
-                       const int* status, void* scratch, int rstride);
+int launch_stats_keys(const Sweep& sw, const KeyBank& bank, void* scratch, int rstride);
+void launch_embed_keys_fold(const Sweep& sw, int nkeys, void* scratch, int rstride, float sF, double sqrt_n, OpResult* res);
+void launch_embed_keys(const Sweep& sw, const KeyBank& bank, const EmbedPlanes& ep, void* scratch, int rstride);  // (ep.scal: null, the scalars lie in scratch)
 int embed_keys_group(void);  // keys per group of k_stats_keys / k_embed_keys (compile-time EKG)
 // a payload in the mark (wm_embed_signs / wm_detect_bits, wm_k_bits.hip).  k_embed_signs is k_embed's sweep (the same body, march
-// and launch loop, wm_embed_march.hpp; never the hand-over) with u = m W multiplied by the sign of the pixel's tile: signs [frames][ny][nx] int8 in {-1, 0, +1} on the device, tile
-// geometry wm_tiles_shape's.  k_bits_fold: one wave per (frame, bit) adds the rows of sums [frames][ntiles][3] (k_tiles_fold's)
+// and launch loop, wm_embed_march.hpp; never the hand-over) with u = m W multiplied by the sign of the pixel's tile: signs [frames][ny][nx]
+// int8 in {-1, 0, +1} on the device.  k_bits_fold: one wave per (frame, bit) adds the rows of sums [frames][ntiles][3] (k_tiles_fold's)
 // named by idx [start[bit], start[bit + 1]) one after the other and writes res[frame * nbits + bit] = {status, soft}
-void launch_embed_signs(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* W,
-                        int aligned_w, const PlaneDesc& base, const PlaneDesc& out, const float* coef, const int* status,
-                        const EmbedScalars* scal, const signed char* signs, int tile_rows, int tile_cols, int ny, int nx);
+void launch_embed_signs(const Sweep& sw, const KeyBank& w, const EmbedPlanes& ep, const signed char* signs, const TileShape& ts);
 void launch_bits_fold(hipStream_t s, int frames, int nbits, int ntiles, const double* sums, const int* start, const int* idx,
                       const int* status, OpResult* res);
 // one frame, many payload copies (wm_embed_signs_multi, wm_k_embed_signs_multi.hip): k_embed_signs' sweep with the image side formed
 // once per row and the sign, fmaf, clamp and store repeated for a compile-time group of copies; copy groups are a grid axis
-// (k_embed_keys' block order).  signs [frames][ncopies][ny][nx] on the device; copy (frame, k) is frame frame * ncopies + k of `out`;
-// scal: the frame's scalars of the single-W stats sweep.  embed_signs_multi_grid_fits: every grid of the sweep times the copy groups
-// fits 31 bits (from the shapes alone)
+// (k_embed_keys' block order).  signs [frames][ncopies][ny][nx] on the device; copy (frame, k) is frame frame * ncopies + k of ep.out;
+// ep.scal: the frame's scalars of the single-W stats sweep.  embed_signs_multi_grid_fits: every grid of the sweep times the copy groups
+// fits 31 bits -- from the shapes alone, asked before the call has resolved a plane, so from the geometry and not from a Sweep
 bool embed_signs_multi_grid_fits(const LaunchGeom& lg, int frames, int ncopies);
-void launch_embed_signs_multi(hipStream_t s, const LaunchGeom& lg, int frames, int mask, int pad, const PlaneDesc& x, const float* W,
-                              int aligned_w, const PlaneDesc& base, const PlaneDesc& out, const float* coef, const int* status,
-                              const EmbedScalars* scal, const signed char* signs, int ncopies, int tile_rows, int tile_cols, int ny, int nx);
+void launch_embed_signs_multi(const Sweep& sw, const KeyBank& w, const EmbedPlanes& ep, const signed char* signs, int ncopies, const TileShape& ts);
 int embed_signs_group(void);  // copies per group of k_embed_signs_multi (compile-time SMG)
 // band mode: solve the 8x8 system from all-reduced Gram totals [frames][44]; writes coef / status like k_gram's tail
 void launch_solve_totals(hipStream_t s, int frames, const double* totals, float* coef, int* status);

@@ -325,11 +325,11 @@ static inline int align_mode(const LaunchGeom& lg, bool aligned)
 // launches the aligned part and then the generic part of a sweep: go(true_type / false_type, part) for each part that has strips.
 // quad: the 4-frames-per-block mapping where the batch allows it (sweeps that read W)
 template <typename F>
-static inline void for_each_sweep_part(const LaunchGeom& lg, int frames, int aligned, int quad, F&& go)
+static inline void for_each_sweep_part(const Sweep& sw, int aligned, int quad, F&& go)
 {
-    const SweepPart pv = sweep_part(lg, frames, true, aligned, quad);
+    const SweepPart pv = sweep_part(sw.lg, sw.frames, true, aligned, quad);
     if (pv.run) go(std::true_type{}, pv);
-    const SweepPart pg = sweep_part(lg, frames, false, aligned, quad);
+    const SweepPart pg = sweep_part(sw.lg, sw.frames, false, aligned, quad);
     if (pg.run) go(std::false_type{}, pg);
 }
 
@@ -355,11 +355,12 @@ static inline bool same_plane(const PlaneDesc& x, const PlaneDesc& base)
 // Which strips a detector sweep (k_detect and the kernels that share its geometry) runs on.  Windows up to 7x7 on planes that
 // allow vector access and whose width is a multiple of 4: overlapped strips, more and narrower than the other sweeps of the call.
 // 3x3 windows on such planes with another width of STRIP + 8 or more: overlapped strips + one generic strip.  Else the plain strips
-static inline DetectPlan detect_plan(const LaunchGeom& lg, int mask, int pad, const PlaneDesc& x, int aligned_w)
+static inline DetectPlan detect_plan(const Sweep& sw, int aligned_w)
 {
+    const LaunchGeom& lg = sw.lg;
     DetectPlan pl;
-    pl.overlap = (mask == 0 || pad <= 3) && align_mode(lg, x.aligned && aligned_w) == 2;
-    pl.split = (mask == 0 || pad == 1) && !pl.overlap && x.aligned && aligned_w && split_applies(lg.cols);
+    pl.overlap = (sw.mask == 0 || sw.pad <= 3) && align_mode(lg, sw.x.aligned && aligned_w) == 2;
+    pl.split = (sw.mask == 0 || sw.pad == 1) && !pl.overlap && sw.x.aligned && aligned_w && split_applies(lg.cols);
     pl.ld = pl.overlap ? overlap_geom(lg) : (pl.split ? split_geom(lg) : lg);
     return pl;
 }
@@ -367,9 +368,10 @@ static inline DetectPlan detect_plan(const LaunchGeom& lg, int mask, int pad, co
 // strips run the aligned instance; a split plane the aligned instance on its overlapped strips, then the generic one on its
 // generic strip; everything else is generic, a 9x9 window always and with HC = 2
 template <typename F>
-static inline void for_each_detect_launch(const DetectPlan& pl, int frames, int mask, int pad, F&& go)
+static inline void for_each_detect_launch(const DetectPlan& pl, const Sweep& sw, F&& go)
 {
-    for_mask_pad(mask, pad, [&](auto m, auto p) {
+    const int frames = sw.frames;
+    for_mask_pad(sw.mask, sw.pad, [&](auto m, auto p) {
         constexpr int PAD = decltype(p)::value;
         const IC<(PAD == 4 ? 2 : 1)> hc;
         auto part = [&](auto vec, const SweepPart& sp) { if (sp.run) go(m, p, hc, vec, sp); };
