@@ -20,6 +20,7 @@
 #include <mutex>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 using dim_t = long long;  // ArrayFire's dim_t
@@ -230,6 +231,38 @@ public:
         const int rc = wm_detect(ctx, (int)maskType, &pimg, &corr, nullptr, WM_SLOT_SYNC);
         if (rc < 0) fail(rc, "detectWatermark");
         return corr;
+    }
+    // af::rgb2gray(img, r, g, b) (main.cpp:153-154,196-197) on the device (wm.h wm_rgb2gray): the f32 grey of a planar RGB image,
+    // f32 or u8, (r R + g G) + b B in f32
+    wm::Image rgb2gray(const wm::Image& rgb, float r = 0.299f, float g = 0.587f, float b = 0.114f) const
+    {
+        wm::Image gray(rgb.rows(), rgb.cols(), 1, wm::dtype::f32, device);
+        const wm_plane prgb = rgb.plane(), pg = gray.plane();
+        const float w[3] = {r, g, b};
+        const int rc = wm_rgb2gray(ctx, &prgb, &pg, w, WM_SLOT_SYNC);
+        if (rc < 0) fail(rc, "rgb2gray");
+        return gray;
+    }
+    // interleaved 8-bit pixels on the host (rows * cols * 3 bytes, R G B) -> {planar f32 RGB, f32 grey (empty unless wantGray)} on
+    // the device: the image crosses the host link once, as bytes (wm.h wm_unpack_rgb8)
+    std::pair<wm::Image, wm::Image> unpackRgb8(const uint8_t* interleavedHost, bool wantGray) const
+    {
+        wm::Image rgb(dims.rows, dims.cols, 3, wm::dtype::f32, device), gray;
+        if (wantGray) gray = wm::Image(dims.rows, dims.cols, 1, wm::dtype::f32, device);
+        const wm_packed pk = packed(const_cast<uint8_t*>(interleavedHost));
+        const wm_plane prgb = rgb.plane(), pg = wantGray ? gray.plane() : wm_plane{};
+        const int rc = wm_unpack_rgb8(ctx, &pk, &prgb, wantGray ? &pg : nullptr, nullptr, WM_SLOT_SYNC);
+        if (rc < 0) fail(rc, "unpackRgb8");
+        return {rgb, gray};
+    }
+    // the .as(u8) in front of af::saveImageNative (main.cpp:235-237): a planar RGB image -> interleaved 8-bit pixels on the host,
+    // packed on the device and downloaded as 3 bytes per pixel (wm.h wm_pack_rgb8)
+    void packRgb8(const wm::Image& rgb, uint8_t* interleavedHost) const
+    {
+        const wm_plane prgb = rgb.plane();
+        const wm_packed pk = packed(interleavedHost);
+        const int rc = wm_pack_rgb8(ctx, &prgb, &pk, WM_SLOT_SYNC);
+        if (rc < 0) fail(rc, "packRgb8");
     }
     // detectWatermark of one grey image against every key of `keys` in one call (wm.h wm_detect_keys): score k is what
     // detectWatermark returns with key k as W (0.0f for every key when the prediction system is not solvable)
@@ -462,6 +495,14 @@ private:
     {
         throw std::runtime_error(std::string("ERROR in ") + where + ": " + wm_strerror(rc) + " " + (ctx ? wm_last_error(ctx) : "") +
                                  " Error code: " + std::to_string(rc) + "\n");
+    }
+    // a dense interleaved host buffer of the engine's shape as wm_packed
+    wm_packed packed(uint8_t* interleavedHost) const
+    {
+        wm_packed pk{};
+        pk.data = interleavedHost; pk.rows = (int32_t)dims.rows; pk.cols = (int32_t)dims.cols; pk.mem = WM_MEM_HOST; pk.frames = 1;
+        pk.pitch_bytes = 3 * (int64_t)dims.cols; pk.frame_stride_bytes = 0;
+        return pk;
     }
     // the *Multi embeds around their C call: K stacked copies of one image as makeWatermarkKeys stacks them, one strength
     template <typename Call>

@@ -61,7 +61,8 @@ typedef enum wm_mask_type { WM_MASK_ME = 0, WM_MASK_NVF = 1 } wm_mask_type;
 typedef enum wm_dtype { WM_F32 = 0, WM_U8 = 1 } wm_dtype;
 /* WM_MEM_SLOT_OUT (input planes only, `data` ignored): the device copy of what the last wm_embed on the same slot wrote
  * (grey output; same frames / dtype).  A streamed frame staged from host memory is then detected without crossing the host
- * link a second time: wm_embed(host in, host out, slot) ; wm_detect(SLOT_OUT plane, slot).  Valid until the slot's next embed. */
+ * link a second time: wm_embed(host in, host out, slot) ; wm_detect(SLOT_OUT plane, slot).  Valid until the slot's next embed.
+ * wm_rgb2gray and wm_pack_rgb8 take the slot's last 3-CHANNEL output under the same name. */
 typedef enum wm_mem { WM_MEM_DEVICE = 0, WM_MEM_HOST = 1, WM_MEM_SLOT_OUT = 2 } wm_mem;
 
 /* Stand-in for the af::array arguments of makeWatermark/detectWatermark (Watermark.hpp:69-70):
@@ -503,6 +504,56 @@ int wm_embed_bits_multi(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm
  * HAZARD.  As for wm_detect_keys: the bank must stay ALIVE and UNMODIFIED until wm_sync of this slot has returned. */
 int wm_embed_keys(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* base, const wm_keys* keys, const wm_plane* out,
                   float* a_out, int* status_out, int slot);
+
+/* ---- Pixel formats: RGB to grey, interleaved 8-bit pixels to planes and back ----------------------------------------------------
+ * The reference's image mode converts on the device around its two calls: af::rgb2gray of the RGB input for the mask source,
+ * af::rgb2gray of every watermarked RGB result for the detector, .as(u8) in front of af::saveImageNative (main.cpp:153-154,196-197,
+ * 235-237).  These three calls are that front: element-wise kernels, one lane per four consecutive pixels of a row (DESIGN.md
+ * section 18).  Speed follows wm_plane's rule per plane: f32 planes with a 4-byte aligned base and u8 planes whose base, pitch and
+ * strides are multiples of 4 move as 16-byte / dword accesses, packed pixels whose `data`, pitch_bytes and frame_stride_bytes are
+ * multiples of 4 as 12-byte accesses; a width that is not a multiple of 4 costs a per-pixel tail at the right edge, any other layout
+ * is moved pixel by pixel.  All of it is correct for any base address, pitch and stride.
+ * All three are ENQUEUES on the slot like every other call (WM_SLOT_SYNC: slot 0, waits).  They deliver no scalar results and take
+ * none of the slot's 4096 result records; they may share a slot with any other call in any order; their kernels are not in the
+ * wm_prof_* list.  They do not change what WM_MEM_SLOT_OUT names and leave no hand-over; like every library write they end a
+ * hand-over whose plane an output overlaps.  WM_MEM_HOST planes and packed buffers are staged through the slot's staging buffers
+ * with hipMemcpy2DAsync on the slot's stream (a packed buffer as rows of 3 * cols bytes).
+ * Arguments are looked at in this order, and the first failure is WM_ERR_BAD_ARG before any device work: null pointers (ctx, a
+ * plane or packed buffer or its data); shapes (rows x cols of every plane must be the context's); channels, dtype and what else one
+ * plane must satisfy on its own (pitch, strides, mem, frames within max_frames; pitch_bytes >= 3 * cols); frame counts that differ
+ * between the planes; overlap of two device planes of the call; the slot; a weight that is not finite; a WM_MEM_SLOT_OUT input that
+ * does not match the slot's last wm_embed output, or that the output overlaps (overlap is judged on the resolved planes: host planes
+ * resolve to staging buffers of their own and overlap nothing).
+ *
+ * wm_packed: interleaved 8-bit pixels, three bytes per pixel in R, G, B order, as image files and most decoders hold them.
+ * pixel (r, c) of frame f starts at data + f * frame_stride_bytes + r * pitch_bytes + 3 * c. */
+typedef struct wm_packed {
+    void* data;
+    int32_t rows, cols;
+    int32_t mem;                 /* WM_MEM_DEVICE or WM_MEM_HOST */
+    int32_t frames;              /* >= 1 */
+    int64_t pitch_bytes;         /* bytes between rows (>= 3 * cols, any value) */
+    int64_t frame_stride_bytes;  /* bytes between frames (>= rows * pitch_bytes; ignored when frames == 1) */
+} wm_packed;
+
+/* af::rgb2gray(img, r, g, b)  (main.cpp:153-154,196-197).  rgb: a 3-channel planar plane, f32 or u8, device, host, or
+ * WM_MEM_SLOT_OUT when the slot's last wm_embed wrote a 3-channel output with the same frames and dtype (a host-staged RGB image is
+ * then converted without crossing the host link again); batches up to max_frames.  gray_out: a 1-channel f32 plane, device or host,
+ * with the same frame count, that does not overlap rgb.  weights[3] = {r, g, b}; NULL means 0.299, 0.587, 0.114.
+ * grey = (r * R + g * G) + b * B in f32, each product and sum rounded on its own (no fused multiply-add); u8 samples are converted
+ * to f32 first, which is exact.  Bit for bit the oracle's wmo_rgb2gray. */
+int wm_rgb2gray(wm_ctx* ctx, const wm_plane* rgb, const wm_plane* gray_out, const float* weights /* [3] or NULL */, int slot);
+/* Interleaved 8-bit pixels -> the engine's planar layout and, in the same pass, the grey: one kernel that reads every source byte
+ * once.  packed: device or host.  rgb_out: 3-channel planar, f32 or u8, device or host, may be NULL; gray_out: 1-channel f32, device
+ * or host, may be NULL; not both NULL; same frame count as packed; none of the three may overlap another.  The planar samples are the
+ * source bytes exactly; the grey equals wm_rgb2gray(rgb_out, weights) bit for bit. */
+int wm_unpack_rgb8(wm_ctx* ctx, const wm_packed* packed, const wm_plane* rgb_out /* or NULL */, const wm_plane* gray_out /* or NULL */,
+                   const float* weights /* [3] or NULL */, int slot);
+/* The .as(u8) in front of af::saveImageNative (main.cpp:235-237): a planar 3-channel plane (f32 or u8; device, host, or the slot's
+ * 3-channel WM_MEM_SLOT_OUT) -> interleaved 8-bit pixels, device or host.  f32 samples are clamped to [0, 255] and truncated toward
+ * zero, NaN gives 0 (for the in-range values wm_embed produces: the C cast to uint8_t).  Bytes of a padded packed row beyond
+ * 3 * cols are left untouched. */
+int wm_pack_rgb8(wm_ctx* ctx, const wm_plane* rgb, const wm_packed* packed_out, int slot);
 
 /* Building blocks exposed for parity tests (the reference keeps them private):
  * computeCustomMask / computePredictionErrorMask (Watermark.cpp:96-114,176-218).

@@ -38,6 +38,12 @@ class wm_plane(C.Structure):
                 ("channel_stride", C.c_int64), ("frame_stride", C.c_int64)]
 
 
+class wm_packed(C.Structure):
+    """interleaved 8-bit R, G, B pixels (wm.h wm_packed); strides in bytes"""
+    _fields_ = [("data", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32), ("mem", C.c_int32), ("frames", C.c_int32),
+                ("pitch_bytes", C.c_int64), ("frame_stride_bytes", C.c_int64)]
+
+
 # every symbol include/wm.h declares: (name, restype, argtypes)
 _P = C.POINTER
 _ctx_p = C.c_void_p
@@ -92,6 +98,9 @@ ABI = [
                                       _P(C.c_int), C.c_int]),
     ("wm_embed_bits_multi", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), _P(wm_plane), _P(wm_plane), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                      C.c_void_p, _P(C.c_float), _P(C.c_int), C.c_int]),
+    ("wm_rgb2gray", C.c_int, [_ctx_p, _P(wm_plane), _P(wm_plane), _P(C.c_float), C.c_int]),
+    ("wm_unpack_rgb8", C.c_int, [_ctx_p, _P(wm_packed), _P(wm_plane), _P(wm_plane), _P(C.c_float), C.c_int]),
+    ("wm_pack_rgb8", C.c_int, [_ctx_p, _P(wm_plane), _P(wm_packed), C.c_int]),
     ("wm_compute_mask", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), _P(wm_plane), _P(wm_plane), _P(C.c_float), _P(C.c_int), C.c_int]),
     ("wm_gram", C.c_int, [_ctx_p, _P(wm_plane), _P(C.c_double), C.c_int]),
     ("wm_band_configure", C.c_int, [_ctx_p, C.c_int, C.c_int, C.c_longlong]),
@@ -198,6 +207,19 @@ def plane_of(t, channels=1, batched=None):
         raise RuntimeError("channel dimension mismatch")
     return wm_plane(t.data_ptr(), t.shape[-2], t.shape[-1], channels, dt, WM_MEM_DEVICE, frames, t.stride(-2), cstride,
                     fstride)
+
+
+def packed_of(t):
+    """wm_packed view of a uint8 torch tensor of interleaved pixels: [R, C, 3] or a batch [F, R, C, 3] whose pixels are three
+    adjacent bytes (rows and frames may be padded).  A GPU tensor is a device buffer, a CPU tensor a WM_MEM_HOST one (it must stay
+    alive until the slot is synced)"""
+    import torch
+    if t.dtype != torch.uint8:
+        raise RuntimeError(f"packed pixels must be uint8, got {t.dtype}")
+    if t.dim() not in (3, 4) or t.shape[-1] != 3 or t.stride(-1) != 1 or t.stride(-2) != 3:
+        raise RuntimeError("packed pixels must be [R, C, 3] or [F, R, C, 3] with three adjacent bytes per pixel")
+    frames, fstride = (t.shape[0], t.stride(0)) if t.dim() == 4 else (1, 0)
+    return wm_packed(t.data_ptr(), t.shape[-3], t.shape[-2], WM_MEM_DEVICE if t.is_cuda else WM_MEM_HOST, frames, t.stride(-3), fstride)
 
 
 class KeySet:
@@ -674,6 +696,42 @@ class Watermark:
         single = inputImage.dim() == 2
         return out, self._strengths(a, st, single), (corr[0] if single else list(corr))
 
+    # -- pixel formats (wm.h wm_rgb2gray / wm_unpack_rgb8 / wm_pack_rgb8) ------------------------------------------------
+    def rgb2gray(self, rgb, weights=None, out=None):
+        """af::rgb2gray (main.cpp:153-154): the grey [R, C] ([F, R, C]) float32 of a planar RGB tensor [3, R, C] ([F, 3, R, C]),
+        float32 or uint8; weights (r, g, b), default 0.299, 0.587, 0.114; grey = (r R + g G) + b B in f32"""
+        import torch
+        if out is None:
+            out = torch.empty(tuple(rgb.shape[:-3]) + tuple(rgb.shape[-2:]), dtype=torch.float32, device=rgb.device)
+        torch.cuda.current_stream().synchronize()
+        self.rgb2gray_async(rgb, out, WM_SLOT_SYNC, weights)
+        return out
+
+    def unpackRgb8(self, packed, dtype, gray=True):
+        """interleaved uint8 pixels [R, C, 3] ([F, R, C, 3]; a GPU tensor, or a CPU tensor that is staged) -> (rgb, grey): the planar
+        tensor [3, R, C] ([F, 3, R, C]) of `dtype` (torch.float32 or torch.uint8) and, unless gray is false (then None), its grey
+        float32 [R, C] ([F, R, C]) as rgb2gray gives it, both on the engine's device, in one pass over the source"""
+        import torch
+        dev = packed.device if packed.is_cuda else torch.device("cuda", lib().wm_device(self._ctx))
+        lead = tuple(packed.shape[:-3])
+        R, Cc = packed.shape[-3], packed.shape[-2]
+        rgb = torch.empty(lead + (3, R, Cc), dtype=dtype, device=dev)
+        g = torch.empty(lead + (R, Cc), dtype=torch.float32, device=dev) if gray else None
+        torch.cuda.current_stream().synchronize()
+        self.unpack_rgb8_async(packed, rgb, g, WM_SLOT_SYNC)
+        return rgb, g
+
+    def packRgb8(self, rgb, out=None):
+        """the .as(u8) in front of saving (main.cpp:235-237): planar [3, R, C] ([F, 3, R, C]) float32 or uint8 -> interleaved uint8
+        [R, C, 3] ([F, R, C, 3]); float32 is clamped to [0, 255] and truncated, NaN gives 0.  `out`: a uint8 tensor of that shape
+        on the GPU, or on the CPU (then the pixels are downloaded into it)"""
+        import torch
+        if out is None:
+            out = torch.empty(tuple(rgb.shape[:-3]) + tuple(rgb.shape[-2:]) + (3,), dtype=torch.uint8, device=rgb.device)
+        torch.cuda.current_stream().synchronize()
+        self.pack_rgb8_async(rgb, out, WM_SLOT_SYNC)
+        return out
+
     # north_star aliases
     embed = makeWatermark
     detect = detectWatermark
@@ -846,6 +904,35 @@ class Watermark:
         soft_out, status_out = self._scalars_out(soft_out, status_out)
         self._chk(lib().wm_detect_bits(self._ctx, int(maskType), C.byref(pimg), tile_rows, tile_cols, tb.ctypes.data_as(C.c_void_p), nbits,
                                        soft_out, status_out, slot))
+
+    @staticmethod
+    def _as_packed(t):
+        return t if isinstance(t, wm_packed) else packed_of(t)
+
+    @staticmethod
+    def _weights(weights):
+        return None if weights is None else (C.c_float * 3)(*[float(v) for v in weights])
+
+    def rgb2gray_async(self, rgb, gray_out, slot, weights=None):
+        """wm_rgb2gray enqueued on `slot`: rgb a planar tensor [3, R, C] / [F, 3, R, C] or a 3-channel wm_plane (WM_MEM_SLOT_OUT: the
+        slot's last 3-channel embed output), gray_out a float32 tensor [R, C] / [F, R, C] or a wm_plane; weights (r, g, b) or None"""
+        prgb, pg = self._as_plane(rgb, 3), self._as_plane(gray_out, 1)
+        self._chk(lib().wm_rgb2gray(self._ctx, C.byref(prgb), C.byref(pg), self._weights(weights), slot))
+
+    def unpack_rgb8_async(self, packed, rgb_out, gray_out, slot, weights=None):
+        """wm_unpack_rgb8 enqueued on `slot`: packed a uint8 tensor [R, C, 3] / [F, R, C, 3] (packed_of) or a wm_packed; rgb_out
+        (planar, float32 or uint8) and gray_out (float32) tensors or wm_planes, either may be None"""
+        pp = self._as_packed(packed)
+        pr = None if rgb_out is None else self._as_plane(rgb_out, 3)
+        pg = None if gray_out is None else self._as_plane(gray_out, 1)
+        self._chk(lib().wm_unpack_rgb8(self._ctx, C.byref(pp), C.byref(pr) if pr is not None else None, C.byref(pg) if pg is not None else None,
+                                       self._weights(weights), slot))
+
+    def pack_rgb8_async(self, rgb, packed_out, slot):
+        """wm_pack_rgb8 enqueued on `slot`: rgb as for rgb2gray_async, packed_out a uint8 tensor [R, C, 3] / [F, R, C, 3] or a
+        wm_packed"""
+        prgb, pp = self._as_plane(rgb, 3), self._as_packed(packed_out)
+        self._chk(lib().wm_pack_rgb8(self._ctx, C.byref(prgb), C.byref(pp), slot))
 
     def sync(self, slot):
         return self._chk(lib().wm_sync(self._ctx, slot))

@@ -2,7 +2,8 @@
 //
 // Reads the reference's settings.ini unchanged (same sections/keys, settings.ini:1-25; `opencl_device` is taken as
 // the HIP device ordinal) and runs either
-//   * testForImage (main.cpp:140-242): load RGB image, grey = 0.299R+0.587G+0.114B, warm-up, `loops_for_test` timed
+//   * testForImage (main.cpp:140-242): load RGB image (it goes up once, as interleaved bytes, and is unpacked into planar f32 RGB
+//     and the grey = 0.299R+0.587G+0.114B on the device, as the reference converts there), warm-up, `loops_for_test` timed
 //     NVF and ME embeds on the RGB base, detects on the grey of the watermarked images, prints strength, FPS and the
 //     two correlations in the reference's format, optionally saves <name>_W_NVF / <name>_W_ME, or
 //   * testForVideo (main.cpp:245-410): raw yuv420p frames (a .y4m file, or a headerless .yuv with the optional keys
@@ -55,14 +56,6 @@ static void checkError(bool cond, const string& msg)  // main.cpp:47-54
     if (cond) { cout << msg << "\n"; exitProgram(EXIT_FAILURE); }
 }
 
-// rgb2gray with the harness weights (main.cpp:142-144,154): f32, (r*R + g*G) + b*B
-static std::vector<float> rgb2gray(const std::vector<float>& planar, size_t n)
-{
-    std::vector<float> g(n);
-    for (size_t i = 0; i < n; ++i) g[i] = 0.299f * planar[i] + 0.587f * planar[n + i] + 0.114f * planar[2 * n + i];
-    return g;
-}
-
 // The image protocol of the reference's sample application (main.cpp:140-242), restructured as a table over the two masks:
 // load + grey conversion, one warm-up call per mask, `loops_for_test` timed synchronous calls per operation (average, as
 // seconds or FPS), the strengths, the correlations of the grey of the watermarked images, optional saving.  The printed
@@ -72,9 +65,8 @@ struct MaskRun {
     MASK_TYPE type;
     const char* name;        // "NVF" / "ME" as the reference prints them
     const char* suffix;      // output file suffix (Utilities.cpp:7-11 naming)
-    wm::Image marked;        // makeWatermark's result on the RGB base
-    std::vector<float> host; // ... downloaded (planar RGB)
-    wm::Image markedGray;    // its grey, what the detector is given (main.cpp:196-197)
+    wm::Image marked;        // makeWatermark's result on the RGB base (unquantised)
+    wm::Image markedGray;    // its grey, formed on the device: what the detector is given (main.cpp:196-197)
     float strength = 0.0f, correlation = 0.0f;
 };
 
@@ -104,17 +96,21 @@ static int testForImage(const INIReader& inir, const int p, const float psnr, co
     const RgbImage im = read_image(imageFile);
     const dim_t rows = im.rows, cols = im.cols;
     const size_t n = (size_t)rows * cols;
-    std::vector<float> planar(3 * n);  // interleaved u8 -> planar f32 (the engine's RGB layout)
-    for (int ch = 0; ch < 3; ++ch)
-        for (size_t i = 0; i < n; ++i) planar[ch * n + i] = (float)im.rgb[3 * i + ch];
-    const wm::Image rgbImage = wm::Image::fromHost(planar.data(), rows, cols, 3, device);
-    const wm::Image image = wm::Image::fromHost(rgb2gray(planar, n).data(), rows, cols, 1, device);
     timer::end();
-    cout << "Time to load and transfer RGB image from disk to VRAM: " << timer::elapsedSeconds() << "\n\n";
-    checkError(cols < 64 || rows < 64, "Image dimensions too low");  // main.cpp:161
+    const float loadSeconds = timer::elapsedSeconds();
+    const bool tooSmall = cols < 64 || rows < 64;
+    if (tooSmall) cout << "Time to load and transfer RGB image from disk to VRAM: " << loadSeconds << "\n\n";
+    checkError(tooSmall, "Image dimensions too low");  // main.cpp:161
 
     const Watermark engine(rows, cols, inir.Get("paths", "watermark", ""), p, psnr, device);
-    MaskRun runs[2] = {{MASK_TYPE::NVF, "NVF", "_W_NVF", {}, {}, {}}, {MASK_TYPE::ME, "ME", "_W_ME", {}, {}, {}}};
+    // the image crosses the host link once, as interleaved bytes: planar f32 RGB (the engine's layout) and the grey with the
+    // harness weights (main.cpp:142-144,153-154) are formed on the device in one pass
+    timer::start();
+    const std::pair<wm::Image, wm::Image> unpacked = engine.unpackRgb8(im.rgb.data(), true);
+    const wm::Image &rgbImage = unpacked.first, &image = unpacked.second;
+    timer::end();
+    cout << "Time to load and transfer RGB image from disk to VRAM: " << loadSeconds + timer::elapsedSeconds() << "\n\n";
+    MaskRun runs[2] = {{MASK_TYPE::NVF, "NVF", "_W_NVF", {}, {}}, {MASK_TYPE::ME, "ME", "_W_ME", {}, {}}};
     const auto parameters = [&] { cout << " columns and parameters:\np = " << p << "  PSNR(dB) = " << psnr << "\n"; };
 
     for (MaskRun& r : runs) engine.makeWatermark(image, rgbImage, r.strength, r.type);  // warm-up (main.cpp:169-170)
@@ -125,9 +121,7 @@ static int testForImage(const INIReader& inir, const int p, const float psnr, co
         cout << executionTime(showFps, secs) << "\n\n";
     }
     for (MaskRun& r : runs) {
-        r.host.resize(3 * n);
-        r.marked.host(r.host.data());  // the unquantised watermarked image
-        r.markedGray = wm::Image::fromHost(rgb2gray(r.host, n).data(), rows, cols, 1, device);
+        r.markedGray = engine.rgb2gray(r.marked);  // of the unquantised watermarked image, without leaving the device
         engine.detectWatermark(r.markedGray, r.type);  // warm-up
     }
     for (MaskRun& r : runs) {
@@ -146,8 +140,7 @@ static int testForImage(const INIReader& inir, const int p, const float psnr, co
         cout << "\nSaving watermarked files to disk...\n";
         for (const MaskRun& r : runs) {
             std::vector<uint8_t> interleaved(3 * n);
-            for (int ch = 0; ch < 3; ++ch)
-                for (size_t i = 0; i < n; ++i) interleaved[3 * i + ch] = (uint8_t)r.host[ch * n + i];
+            engine.packRgb8(r.marked, interleaved.data());  // packed on the device: 3 bytes per pixel come down
             string name = addSuffixBeforeExtension(imageFile, r.suffix);
             const auto dot = name.find_last_of('.');
             name = (dot == string::npos ? name : name.substr(0, dot)) + ".ppm";

@@ -110,6 +110,38 @@ int main(int argc, char** argv)
     }
     CHECK(rgb_ok, "RGB base: 3 channels out, same strength, same increment per channel");
 
+    // ---- the pixel-format front: interleaved bytes up, planes and grey on the device, the grey of the result, packed bytes down
+    {
+        std::vector<uint8_t> px((size_t)3 * R * C), px_back(px.size()), px_marked(px.size());
+        for (size_t i = 0; i < x.size(); ++i)
+            for (int ch = 0; ch < 3; ++ch) px[3 * i + ch] = (uint8_t)rgb[(size_t)ch * R * C + i];
+        const std::pair<wm::Image, wm::Image> up = wm1.unpackRgb8(px.data(), true);
+        std::vector<float> planar((size_t)3 * R * C), g((size_t)R * C), g2(g.size());
+        up.first.host(planar.data());
+        up.second.host(g.data());
+        wm1.rgb2gray(up.first).host(g2.data());
+        bool planes_ok = up.first.channels() == 3 && up.second.channels() == 1, gray_ok = g == g2;
+        for (size_t i = 0; i < g.size(); ++i) {
+            for (int ch = 0; ch < 3; ++ch) planes_ok = planes_ok && planar[(size_t)ch * R * C + i] == (float)px[3 * i + ch];
+            gray_ok = gray_ok && g[i] == (0.299f * px[3 * i] + 0.587f * px[3 * i + 1]) + 0.114f * px[3 * i + 2];
+        }
+        CHECK(planes_ok, "unpackRgb8: the planes are the source bytes");
+        CHECK(gray_ok, "unpackRgb8 / rgb2gray: (0.299 R + 0.587 G) + 0.114 B in f32, the same bits from both");
+        wm1.packRgb8(up.first, px_back.data());
+        CHECK(px_back == px, "packRgb8 of the unpacked planes returns the bytes");
+        float a_px = 0.0f;
+        const wm::Image y_px = wm1.makeWatermark(up.second, up.first, a_px, ME);
+        const float c_px = wm1.detectWatermark(wm1.rgb2gray(y_px), ME);
+        std::vector<float> yp((size_t)3 * R * C);
+        y_px.host(yp.data());
+        wm1.packRgb8(y_px, px_marked.data());
+        bool cast_ok = true;
+        for (size_t i = 0; i < g.size(); ++i)
+            for (int ch = 0; ch < 3; ++ch) cast_ok = cast_ok && px_marked[3 * i + ch] == (uint8_t)yp[(size_t)ch * R * C + i];
+        CHECK(a_px > 0.0f && c_px > 0.2f, "RGB round on the device: embed on the unpacked base, detect on the grey of the result");
+        CHECK(cast_ok, "packRgb8 of a watermarked image is the cast to 8 bits");
+    }
+
     // ---- deep copy that shares W (Watermark.cpp:30-51): same results, independent lifetime
     float a_copy = 0.0f, a_assign = 0.0f;
     {

@@ -2180,6 +2180,241 @@ int wm_compute_mask(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_pla
     return finish_call(ctx, s, slot, frames, 1, false, nullptr, status_out, coef_out);
 }
 
+// ---- the pixel-format front: wm_rgb2gray, wm_unpack_rgb8, wm_pack_rgb8 (wm.h; kernels in wm_k_convert.hip) -----------------------
+// The three calls look at their arguments in one order (wm.h): null pointers, shapes, channels / dtype (and everything else
+// check_plane asks of a single plane), frame counts, overlap of device planes, slot, weights, and last what needs the slot: a
+// WM_MEM_SLOT_OUT input.  Nothing is staged or launched before all of them have passed.
+// Host planes: inputs are staged in Slot::st_in, outputs in Slot::st_base -- never in st_out, which may hold the plane
+// WM_MEM_SLOT_OUT names (the conversions neither read their input from the buffer they write nor change what the name means).
+static bool plane_null(const wm_plane* pl) { return !pl || (!pl->data && pl->mem != WM_MEM_SLOT_OUT); }
+static int check_shape(wm_ctx* ctx, int rows, int cols, const char* what)
+{
+    if (rows == ctx->rows && cols == ctx->cols) return WM_OK;
+    return fail(ctx, WM_ERR_BAD_ARG, std::string(what) + ": plane is " + std::to_string(rows) + "x" + std::to_string(cols) + ", engine was initialised for " +
+                                         std::to_string(ctx->rows) + "x" + std::to_string(ctx->cols));
+}
+static int check_packed(wm_ctx* ctx, const wm_packed* pk, const char* what)
+{
+    if (pk->mem != WM_MEM_DEVICE && pk->mem != WM_MEM_HOST) return fail(ctx, WM_ERR_BAD_ARG, std::string(what) + ": bad mem (device or host)");
+    if (pk->pitch_bytes < 3 * (int64_t)pk->cols) return fail(ctx, WM_ERR_BAD_ARG, std::string(what) + ": pitch_bytes < 3 * cols");
+    if (pk->frames < 1 || pk->frames > ctx->max_frames)
+        return fail(ctx, WM_ERR_BAD_ARG, std::string(what) + ": frames=" + std::to_string(pk->frames) + " exceeds wm_configure max_frames=" + std::to_string(ctx->max_frames));
+    if (pk->frames > 1 && pk->frame_stride_bytes < (int64_t)pk->rows * pk->pitch_bytes)
+        return fail(ctx, WM_ERR_BAD_ARG, std::string(what) + ": frame_stride_bytes too small (frames overlap)");
+    return WM_OK;
+}
+static int check_rgb_plane(wm_ctx* ctx, const wm_plane* pl, const char* what, bool allow_slot_out)
+{
+    const int rc = check_plane(ctx, pl, 0, true, what, allow_slot_out);
+    if (rc != WM_OK) return rc;
+    return pl->channels == 3 ? WM_OK : fail(ctx, WM_ERR_BAD_ARG, std::string(what) + ": channels must be 3 (planar RGB)");
+}
+static int check_gray_f32(wm_ctx* ctx, const wm_plane* pl, const char* what)
+{
+    const int rc = check_plane(ctx, pl, 0, false, what);
+    if (rc != WM_OK) return rc;
+    return pl->dtype == WM_F32 ? WM_OK : fail(ctx, WM_ERR_BAD_ARG, std::string(what) + ": must be a 1-channel f32 plane");
+}
+static int check_weights(wm_ctx* ctx, const float* weights, float* w)
+{
+    w[0] = 0.299f; w[1] = 0.587f; w[2] = 0.114f;  // af::rgb2gray's defaults (main.cpp:153-154)
+    if (!weights) return WM_OK;
+    for (int i = 0; i < 3; ++i) {
+        if (!std::isfinite(weights[i])) return fail(ctx, WM_ERR_BAD_ARG, "weights: not finite");
+        w[i] = weights[i];
+    }
+    return WM_OK;
+}
+// the bytes a device plane / packed buffer spans
+struct ByteRange { const char* lo; const char* hi; };
+static ByteRange range_of(const wm_ctx* ctx, const PlaneDesc& d, int frames) { return ByteRange{(const char*)d.p, (const char*)d.p + plane_extent(d, ctx->rows, ctx->cols, frames)}; }
+static ByteRange range_of(const wm_ctx* ctx, const PackedDesc& d, int frames)
+{
+    return ByteRange{(const char*)d.p, (const char*)d.p + (size_t)(frames - 1) * d.fstride + (size_t)(ctx->rows - 1) * d.pitch + 3 * (size_t)ctx->cols};
+}
+static bool ranges_overlap(const ByteRange& a, const ByteRange& b) { return a.lo && b.lo && a.lo < b.hi && b.lo < a.hi; }
+static PackedDesc desc_packed(const wm_packed* pk)
+{
+    PackedDesc d;
+    d.p = pk->data; d.pitch = pk->pitch_bytes; d.fstride = pk->frames > 1 ? pk->frame_stride_bytes : 0;
+    d.aligned = reinterpret_cast<uintptr_t>(pk->data) % 4 == 0 && d.pitch % 4 == 0 && d.fstride % 4 == 0;
+    return d;
+}
+// dense staging layout of a host packed buffer: rows of 3 * cols bytes, the pitch rounded up to 4
+static PackedDesc staged_packed(const wm_packed* pk, size_t* bytes)
+{
+    PackedDesc d;
+    d.p = nullptr; d.pitch = (3LL * pk->cols + 3) & ~3LL; d.fstride = d.pitch * pk->rows; d.aligned = 1;
+    *bytes = (size_t)d.fstride * pk->frames;
+    return d;
+}
+// a hand-over whose plane a packed output overwrites ends, like under every library write (invalidate_handovers for packed rows)
+static void invalidate_handovers_packed(wm_ctx* ctx, const PackedDesc& written, int frames)
+{
+    const ByteRange w = range_of(ctx, written, frames);
+    for (auto& t : ctx->slots)
+        if (t.ho.valid && t.last_out_frames != 0 && ranges_overlap(range_of(ctx, t.last_out, t.last_out_frames), w)) t.ho.valid = false;
+}
+// the planar RGB input of wm_rgb2gray / wm_pack_rgb8, resolved: the slot's last 3-channel embed output, the staged copy of a host
+// plane, or the device plane
+static int prep_rgb_input(wm_ctx* ctx, Slot& s, const wm_plane* rgb, PlaneDesc* d)
+{
+    if (rgb->mem == WM_MEM_SLOT_OUT) { *d = s.last_out; return WM_OK; }  // (matched by slot_out_rgb before anything was queued)
+    if (rgb->mem != WM_MEM_HOST) { *d = desc_device(rgb); return WM_OK; }
+    const Staged st = staged_layout(rgb);
+    int rc = ensure(ctx, &s.st_in, &s.st_in_bytes, st.bytes);
+    if (rc != WM_OK) return rc;
+    if ((rc = stage_in(ctx, s, rgb, s.st_in, st)) != WM_OK) return rc;
+    *d = st.d; d->p = s.st_in;
+    return WM_OK;
+}
+static int slot_out_rgb(wm_ctx* ctx, const Slot& s, const wm_plane* rgb)
+{
+    if (rgb->mem != WM_MEM_SLOT_OUT) return WM_OK;
+    if (s.last_out_frames == 0 || s.last_out.channels != 3 || rgb->frames != s.last_out_frames || rgb->dtype != s.last_out_dtype)
+        return fail(ctx, WM_ERR_BAD_ARG, "WM_MEM_SLOT_OUT: no matching 3-channel embed output on this slot (frames / dtype must equal the last wm_embed's)");
+    return WM_OK;
+}
+// host outputs of one call side by side in Slot::st_base: `need` bytes each rounded up to 256
+static size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+int wm_rgb2gray(wm_ctx* ctx, const wm_plane* rgb, const wm_plane* gray_out, const float* weights, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    if (plane_null(rgb) || plane_null(gray_out)) return fail(ctx, WM_ERR_BAD_ARG, "wm_rgb2gray: null plane");
+    int rc;
+    if ((rc = check_shape(ctx, rgb->rows, rgb->cols, "rgb")) != WM_OK || (rc = check_shape(ctx, gray_out->rows, gray_out->cols, "gray_out")) != WM_OK) return rc;
+    if ((rc = check_rgb_plane(ctx, rgb, "rgb", true)) != WM_OK || (rc = check_gray_f32(ctx, gray_out, "gray_out")) != WM_OK) return rc;
+    const int frames = rgb->frames;
+    if (gray_out->frames != frames) return fail(ctx, WM_ERR_BAD_ARG, "gray_out: frame count mismatch");
+    if (!convert_grid_fits(ctx->rows, frames)) return fail(ctx, WM_ERR_BAD_ARG, "wm_rgb2gray: rows or frames beyond the launch grid");
+    // overlap, on the resolved planes: host planes resolve to staging buffers of their own, a WM_MEM_SLOT_OUT input below
+    const bool dev_in = rgb->mem == WM_MEM_DEVICE, dev_out = gray_out->mem == WM_MEM_DEVICE;
+    if (dev_in && dev_out && ranges_overlap(range_of(ctx, desc_device(rgb), frames), range_of(ctx, desc_device(gray_out), frames)))
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_rgb2gray: gray_out overlaps rgb");
+    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
+    float w[3];
+    if ((rc = check_weights(ctx, weights, w)) != WM_OK) return rc;
+    if ((rc = slot_out_rgb(ctx, s, rgb)) != WM_OK) return rc;
+    if (rgb->mem == WM_MEM_SLOT_OUT && dev_out && ranges_overlap(range_of(ctx, s.last_out, frames), range_of(ctx, desc_device(gray_out), frames)))
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_rgb2gray: gray_out overlaps rgb (the slot's last output)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    PlaneDesc xd, gd;
+    if ((rc = prep_rgb_input(ctx, s, rgb, &xd)) != WM_OK) return rc;
+    Staged st_g{};
+    if (dev_out) gd = desc_device(gray_out);
+    else {
+        st_g = staged_layout(gray_out);
+        if ((rc = ensure(ctx, &s.st_base, &s.st_base_bytes, st_g.bytes)) != WM_OK) return rc;
+        gd = st_g.d; gd.p = s.st_base;
+    }
+    invalidate_handovers(ctx, gd, frames);
+    launch_rgb2gray(s.stream, ctx->rows, ctx->cols, frames, xd, gd, w);
+    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
+    if (!dev_out && (rc = stage_out(ctx, s, gray_out, s.st_base, st_g)) != WM_OK) return rc;
+    return finish_call(ctx, s, slot, 0, 0, false, nullptr, nullptr);
+}
+
+int wm_unpack_rgb8(wm_ctx* ctx, const wm_packed* packed, const wm_plane* rgb_out, const wm_plane* gray_out, const float* weights, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    if (!packed || !packed->data) return fail(ctx, WM_ERR_BAD_ARG, "wm_unpack_rgb8: null packed buffer");
+    if (!rgb_out && !gray_out) return fail(ctx, WM_ERR_BAD_ARG, "wm_unpack_rgb8: rgb_out and gray_out are both null");
+    if ((rgb_out && !rgb_out->data) || (gray_out && !gray_out->data)) return fail(ctx, WM_ERR_BAD_ARG, "wm_unpack_rgb8: null plane");
+    int rc;
+    if ((rc = check_shape(ctx, packed->rows, packed->cols, "packed")) != WM_OK) return rc;
+    if (rgb_out && (rc = check_shape(ctx, rgb_out->rows, rgb_out->cols, "rgb_out")) != WM_OK) return rc;
+    if (gray_out && (rc = check_shape(ctx, gray_out->rows, gray_out->cols, "gray_out")) != WM_OK) return rc;
+    if ((rc = check_packed(ctx, packed, "packed")) != WM_OK) return rc;
+    if (rgb_out && (rc = check_rgb_plane(ctx, rgb_out, "rgb_out", false)) != WM_OK) return rc;
+    if (gray_out && (rc = check_gray_f32(ctx, gray_out, "gray_out")) != WM_OK) return rc;
+    const int frames = packed->frames;
+    if (rgb_out && rgb_out->frames != frames) return fail(ctx, WM_ERR_BAD_ARG, "rgb_out: frame count mismatch");
+    if (gray_out && gray_out->frames != frames) return fail(ctx, WM_ERR_BAD_ARG, "gray_out: frame count mismatch");
+    if (!convert_grid_fits(ctx->rows, frames)) return fail(ctx, WM_ERR_BAD_ARG, "wm_unpack_rgb8: rows or frames beyond the launch grid");
+    const bool dev_in = packed->mem == WM_MEM_DEVICE, dev_rgb = rgb_out && rgb_out->mem == WM_MEM_DEVICE, dev_gray = gray_out && gray_out->mem == WM_MEM_DEVICE;
+    {
+        const ByteRange none{nullptr, nullptr};
+        const ByteRange rp = dev_in ? range_of(ctx, desc_packed(packed), frames) : none;
+        const ByteRange rr = dev_rgb ? range_of(ctx, desc_device(rgb_out), frames) : none;
+        const ByteRange rg = dev_gray ? range_of(ctx, desc_device(gray_out), frames) : none;
+        if (ranges_overlap(rp, rr) || ranges_overlap(rp, rg) || ranges_overlap(rr, rg)) return fail(ctx, WM_ERR_BAD_ARG, "wm_unpack_rgb8: packed, rgb_out and gray_out must not overlap");
+    }
+    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
+    float w[3];
+    if ((rc = check_weights(ctx, weights, w)) != WM_OK) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    PackedDesc pd;
+    if (dev_in) pd = desc_packed(packed);
+    else {  // a host buffer goes up as rows of 3 * cols bytes
+        size_t bytes;
+        pd = staged_packed(packed, &bytes);
+        if ((rc = ensure(ctx, &s.st_in, &s.st_in_bytes, bytes)) != WM_OK) return rc;
+        pd.p = s.st_in;
+        for (int f = 0; f < frames; ++f)
+            HIPCHK(ctx, hipMemcpy2DAsync((char*)s.st_in + (size_t)f * pd.fstride, pd.pitch, (const char*)packed->data + (size_t)f * (frames > 1 ? packed->frame_stride_bytes : 0),
+                                         packed->pitch_bytes, 3 * (size_t)packed->cols, packed->rows, hipMemcpyHostToDevice, s.stream));
+    }
+    // host outputs: side by side in st_base
+    Staged st_r{}, st_g{};
+    if (rgb_out && !dev_rgb) st_r = staged_layout(rgb_out);
+    if (gray_out && !dev_gray) st_g = staged_layout(gray_out);
+    const size_t off_g = rgb_out && !dev_rgb ? round256(st_r.bytes) : 0;
+    const size_t host_bytes = off_g + (gray_out && !dev_gray ? st_g.bytes : 0);
+    if (host_bytes && (rc = ensure(ctx, &s.st_base, &s.st_base_bytes, host_bytes)) != WM_OK) return rc;
+    PlaneDesc rd{}, gd{};
+    if (rgb_out) { if (dev_rgb) rd = desc_device(rgb_out); else { rd = st_r.d; rd.p = s.st_base; } }
+    if (gray_out) { if (dev_gray) gd = desc_device(gray_out); else { gd = st_g.d; gd.p = (char*)s.st_base + off_g; } }
+    if (rgb_out) invalidate_handovers(ctx, rd, frames);
+    if (gray_out) invalidate_handovers(ctx, gd, frames);
+    launch_unpack_rgb8(s.stream, ctx->rows, ctx->cols, frames, pd, rd, gd, w);
+    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
+    if (rgb_out && !dev_rgb && (rc = stage_out(ctx, s, rgb_out, rd.p, st_r)) != WM_OK) return rc;
+    if (gray_out && !dev_gray && (rc = stage_out(ctx, s, gray_out, gd.p, st_g)) != WM_OK) return rc;
+    return finish_call(ctx, s, slot, 0, 0, false, nullptr, nullptr);
+}
+
+int wm_pack_rgb8(wm_ctx* ctx, const wm_plane* rgb, const wm_packed* packed_out, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    if (plane_null(rgb) || !packed_out || !packed_out->data) return fail(ctx, WM_ERR_BAD_ARG, "wm_pack_rgb8: null plane or packed buffer");
+    int rc;
+    if ((rc = check_shape(ctx, rgb->rows, rgb->cols, "rgb")) != WM_OK || (rc = check_shape(ctx, packed_out->rows, packed_out->cols, "packed_out")) != WM_OK) return rc;
+    if ((rc = check_rgb_plane(ctx, rgb, "rgb", true)) != WM_OK || (rc = check_packed(ctx, packed_out, "packed_out")) != WM_OK) return rc;
+    const int frames = rgb->frames;
+    if (packed_out->frames != frames) return fail(ctx, WM_ERR_BAD_ARG, "packed_out: frame count mismatch");
+    if (!convert_grid_fits(ctx->rows, frames)) return fail(ctx, WM_ERR_BAD_ARG, "wm_pack_rgb8: rows or frames beyond the launch grid");
+    const bool dev_in = rgb->mem == WM_MEM_DEVICE, dev_out = packed_out->mem == WM_MEM_DEVICE;
+    if (dev_in && dev_out && ranges_overlap(range_of(ctx, desc_device(rgb), frames), range_of(ctx, desc_packed(packed_out), frames)))
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_pack_rgb8: packed_out overlaps rgb");
+    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
+    if ((rc = slot_out_rgb(ctx, s, rgb)) != WM_OK) return rc;
+    if (rgb->mem == WM_MEM_SLOT_OUT && dev_out && ranges_overlap(range_of(ctx, s.last_out, frames), range_of(ctx, desc_packed(packed_out), frames)))
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_pack_rgb8: packed_out overlaps rgb (the slot's last output)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    PlaneDesc xd;
+    if ((rc = prep_rgb_input(ctx, s, rgb, &xd)) != WM_OK) return rc;
+    PackedDesc pd;
+    if (dev_out) pd = desc_packed(packed_out);
+    else {
+        size_t bytes;
+        pd = staged_packed(packed_out, &bytes);
+        if ((rc = ensure(ctx, &s.st_base, &s.st_base_bytes, bytes)) != WM_OK) return rc;
+        pd.p = s.st_base;
+    }
+    invalidate_handovers_packed(ctx, pd, frames);
+    launch_pack_rgb8(s.stream, ctx->rows, ctx->cols, frames, xd, pd);
+    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
+    if (!dev_out)
+        for (int f = 0; f < frames; ++f)
+            HIPCHK(ctx, hipMemcpy2DAsync((char*)packed_out->data + (size_t)f * (frames > 1 ? packed_out->frame_stride_bytes : 0), packed_out->pitch_bytes,
+                                         (const char*)s.st_base + (size_t)f * pd.fstride, pd.pitch, 3 * (size_t)packed_out->cols, packed_out->rows, hipMemcpyDeviceToHost, s.stream));
+    return finish_call(ctx, s, slot, 0, 0, false, nullptr, nullptr);
+}
+
 int wm_gram(wm_ctx* ctx, const wm_plane* img, double* gram_out, int slot)
 {
     if (!ctx || !gram_out) return WM_ERR_BAD_ARG;

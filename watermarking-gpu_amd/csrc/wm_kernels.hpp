@@ -304,6 +304,20 @@ void launch_bits_fold(hipStream_t s, int frames, int nbits, int ntiles, const do
 bool embed_signs_multi_grid_fits(const LaunchGeom& lg, int frames, int ncopies);
 void launch_embed_signs_multi(const Sweep& sw, const KeyBank& w, const EmbedPlanes& ep, const signed char* signs, int ncopies, const TileShape& ts);
 int embed_signs_group(void);  // copies per group of k_embed_signs_multi (compile-time SMG)
+// the pixel-format front (wm_rgb2gray / wm_unpack_rgb8 / wm_pack_rgb8, wm_k_convert.hip): element-wise kernels, a lane per four
+// consecutive pixels of a row, grid (column chunks, rows, frames) -- convert_grid_fits: rows and frames fit the grid's y and z.
+// PackedDesc: interleaved 8-bit R, G, B (wm_packed) in BYTES; aligned: base, pitch and frame stride are multiples of 4, so a
+// lane's four pixels are three dwords.  PlaneDesc::aligned says the same of a planar plane (vec_ok's rule); a null PlaneDesc::p
+// is an output the call leaves out.  w: the three grey weights; grey = (w[0] * R + w[1] * G) + w[2] * B in f32
+struct PackedDesc {
+    const void* p;
+    long long pitch, fstride;  // bytes
+    int aligned;
+};
+bool convert_grid_fits(int rows, int frames);
+void launch_rgb2gray(hipStream_t s, int rows, int cols, int frames, const PlaneDesc& rgb, const PlaneDesc& gray, const float* w);
+void launch_unpack_rgb8(hipStream_t s, int rows, int cols, int frames, const PackedDesc& pk, const PlaneDesc& rgb, const PlaneDesc& gray, const float* w);
+void launch_pack_rgb8(hipStream_t s, int rows, int cols, int frames, const PlaneDesc& rgb, const PackedDesc& pk);
 // band mode: solve the 8x8 system from all-reduced Gram totals [frames][44]; writes coef / status like k_gram's tail
 void launch_solve_totals(hipStream_t s, int frames, const double* totals, float* coef, int* status);
 // band mode, device-resident exchange (wm_band_*_dev): glue kernels between the sweeps and the caller's collectives
