@@ -264,6 +264,44 @@ public:
         const int rc = wm_pack_rgb8(ctx, &prgb, &pk, WM_SLOT_SYNC);
         if (rc < 0) fail(rc, "packRgb8");
     }
+    // Samples of 9 to 16 bits (10-bit video; wm.h wm_unpack16 ...): dense host planes of the engine's shape, `channels` planar
+    // planes of uint16 in the host's byte order, in the low bits of their 16 or, msbAligned, in the high bits (P010's Y plane).
+    // unpack16: the f32 image on [0, 255] on the device, min(v, 2^bits - 1) * (float)(255.0 / (2^bits - 1))
+    wm::Image unpack16(const uint16_t* host, int channels, int bits, bool msbAligned = false) const
+    {
+        wm::Image out(dims.rows, dims.cols, channels, wm::dtype::f32, device);
+        const wm_plane src = plane16(const_cast<uint16_t*>(host), channels), po = out.plane();
+        const int rc = wm_unpack16(ctx, &src, bits, msbAligned ? 1 : 0, &po, WM_SLOT_SYNC);
+        if (rc < 0) fail(rc, "unpack16");
+        return out;
+    }
+    // pack16: an f32 image -> samples on the host, clamped and rounded to nearest (ties to even); unpack16's inverse on every code
+    void pack16(const wm::Image& image, uint16_t* host, int bits, bool msbAligned = false) const
+    {
+        const wm_plane src = image.plane(), po = plane16(host, image.channels());
+        const int rc = wm_pack16(ctx, &src, &po, bits, msbAligned ? 1 : 0, WM_SLOT_SYNC);
+        if (rc < 0) fail(rc, "pack16");
+    }
+    // makeWatermark of a grey `bits`-bit frame IN PLACE (wm.h wm_embed16: unpack, embed onto the frame itself, pack, one wait).
+    // Returns the strength; a frame whose system is not solvable comes back unchanged and the strength is 0
+    float makeWatermark16(uint16_t* hostY, int bits, MASK_TYPE maskType, bool msbAligned = false) const
+    {
+        const wm_plane py = plane16(hostY, 1);
+        float a = 0.0f;
+        int st = 0;
+        const int rc = wm_embed16(ctx, (int)maskType, &py, &py, bits, msbAligned ? 1 : 0, &a, &st, WM_SLOT_SYNC);
+        if (rc < 0) fail(rc, "makeWatermark16");
+        return st != 0 ? 0.0f : a;
+    }
+    // detectWatermark of a grey `bits`-bit frame (wm.h wm_detect16); 0.0f when the prediction system is not solvable
+    float detectWatermark16(const uint16_t* hostY, int bits, MASK_TYPE maskType, bool msbAligned = false) const
+    {
+        const wm_plane py = plane16(const_cast<uint16_t*>(hostY), 1);
+        float corr = 0.0f;
+        const int rc = wm_detect16(ctx, (int)maskType, &py, bits, msbAligned ? 1 : 0, &corr, nullptr, WM_SLOT_SYNC);
+        if (rc < 0) fail(rc, "detectWatermark16");
+        return corr;
+    }
     // detectWatermark of one grey image against every key of `keys` in one call (wm.h wm_detect_keys): score k is what
     // detectWatermark returns with key k as W (0.0f for every key when the prediction system is not solvable)
     std::vector<float> detectWatermarkKeys(const wm::Image& watermarkedImage, const WatermarkKeys& keys, MASK_TYPE maskType) const
@@ -495,6 +533,14 @@ private:
     {
         throw std::runtime_error(std::string("ERROR in ") + where + ": " + wm_strerror(rc) + " " + (ctx ? wm_last_error(ctx) : "") +
                                  " Error code: " + std::to_string(rc) + "\n");
+    }
+    // a dense host buffer of `channels` planar uint16 planes of the engine's shape as wm_plane
+    wm_plane plane16(uint16_t* host, int channels) const
+    {
+        wm_plane pl{};
+        pl.data = host; pl.rows = (int32_t)dims.rows; pl.cols = (int32_t)dims.cols; pl.channels = channels; pl.dtype = WM_U16; pl.mem = WM_MEM_HOST;
+        pl.frames = 1; pl.pitch = dims.cols; pl.channel_stride = dims.rows * dims.cols; pl.frame_stride = 0;
+        return pl;
     }
     // a dense interleaved host buffer of the engine's shape as wm_packed
     wm_packed packed(uint8_t* interleavedHost) const

@@ -58,7 +58,9 @@ typedef struct wm_ctx wm_ctx;
 
 /* enum MASK_TYPE { ME, NVF }  (Watermark.hpp:10-14) -- same order and values */
 typedef enum wm_mask_type { WM_MASK_ME = 0, WM_MASK_NVF = 1 } wm_mask_type;
-typedef enum wm_dtype { WM_F32 = 0, WM_U8 = 1 } wm_dtype;
+/* WM_U16: 2-byte samples of 9 to 16 bits (10-bit video).  Only wm_unpack16, wm_pack16, wm_embed16 and wm_detect16 take it; every
+ * other entry point refuses it as a bad dtype. */
+typedef enum wm_dtype { WM_F32 = 0, WM_U8 = 1, WM_U16 = 2 } wm_dtype;
 /* WM_MEM_SLOT_OUT (input planes only, `data` ignored): the device copy of what the last wm_embed on the same slot wrote
  * (grey output; same frames / dtype).  A streamed frame staged from host memory is then detected without crossing the host
  * link a second time: wm_embed(host in, host out, slot) ; wm_detect(SLOT_OUT plane, slot).  Valid until the slot's next embed.
@@ -75,7 +77,7 @@ typedef struct wm_plane {
     void* data;
     int32_t rows, cols;
     int32_t channels;
-    int32_t dtype;           /* wm_dtype: f32 in [0,255], or u8 (video Y plane, main.cpp:355-357) */
+    int32_t dtype;           /* wm_dtype: f32 in [0,255], or u8 (video Y plane, main.cpp:355-357); u16 for the four *16 calls only */
     int32_t mem;             /* wm_mem */
     int32_t frames;          /* >= 1 */
     int64_t pitch;           /* elements between rows (>= cols) */
@@ -554,6 +556,57 @@ int wm_unpack_rgb8(wm_ctx* ctx, const wm_packed* packed, const wm_plane* rgb_out
  * zero, NaN gives 0 (for the in-range values wm_embed produces: the C cast to uint8_t).  Bytes of a padded packed row beyond
  * 3 * cols are left untouched. */
 int wm_pack_rgb8(wm_ctx* ctx, const wm_plane* rgb, const wm_packed* packed_out, int slot);
+
+/* ---- Samples of 9 to 16 bits: 10-bit video (yuv420p10le, P010, y4m C420p10) and its kin ------------------------------------------
+ * The engine's arithmetic takes any f32 value in [0, 255]; a d-bit sample is brought onto that scale and back (DESIGN.md section
+ * 19).  bits = d in 9..16, maxv = 2^d - 1, and two constants, each the double quotient rounded once to f32:
+ *     k_in = (float)(255.0 / maxv)        k_out = (float)(maxv / 255.0)
+ * Unpack of a sample v (uint16):  s = msb_aligned ? v >> (16 - d) : min(v, maxv);  g = (float)s * k_in  (one f32 multiply).
+ * Pack of a value g (f32):        t = g * k_out  (one f32 multiply);  t = fmin(fmax(t, 0), maxv), NaN gives 0 as in wm_pack_rgb8;
+ *                                 q = rint(t), ties to even -- NOT truncation;  v = msb_aligned ? q << (16 - d) : q.
+ * With these constants pack(unpack(v)) == v for every v <= maxv and every d, and maxv maps to exactly 255.0f: a pixel the embed
+ * leaves alone survives the round trip bit for bit (truncation would not give that).  A PSNR against peak 255 on the scaled plane
+ * is the PSNR against peak maxv on the samples.  msb_aligned = 1: the sample sits in the high bits of its 16 (the Y plane of P010,
+ * P012, P016; on unpack the low 16 - d bits are ignored, on pack they are written as zero); msb_aligned = 0: in the low bits
+ * (yuv420p10le / p12le, y4m C420pNN; on unpack a code above maxv is clamped to maxv).  Samples are in the host's byte order.
+ *
+ * A WM_U16 plane has 2-byte elements; pitch and strides are in elements and `data` must be 2-byte aligned.  Speed: a plane whose
+ * base is a multiple of 4 bytes and whose pitch and used strides are even moves as one 8-byte access per four pixels, any other
+ * pixel by pixel; the f32 side follows wm_plane's rule; a width that is not a multiple of 4 costs a per-pixel tail at the right edge.
+ *
+ * wm_unpack16 and wm_pack16 behave like the pixel-format front above: ENQUEUES on the slot (WM_SLOT_SYNC: slot 0, waits), no result
+ * records, kernels outside the wm_prof_* list, no change of what WM_MEM_SLOT_OUT names, no hand-over left, and the end of a
+ * hand-over whose plane an output overlaps.  WM_MEM_HOST planes are staged with hipMemcpy2DAsync on the slot's stream.  Arguments are
+ * looked at in that front's order, and the first failure is WM_ERR_BAD_ARG before any device work: null pointers; shapes; channels
+ * (1 or 3, planar), dtype and what else one plane must satisfy on its own (2-byte alignment of a u16 plane among it); channel
+ * counts, then frame counts, that differ between the two planes; overlap of two device planes; the slot; `bits` outside 9..16 or
+ * msb_aligned outside {0, 1}; a WM_MEM_SLOT_OUT input that does not match the slot's last wm_embed output or that the output
+ * overlaps. */
+
+/* The two scale constants of `bits` (pure host arithmetic, touches no device).  WM_OK, or WM_ERR_BAD_ARG for bits outside 9..16 or
+ * a null pointer. */
+int wm_depth_scale(int bits, float* to255, float* from255);
+/* src16: WM_U16, device or host.  out_f32: WM_F32, device or host.  Both with 1 or 3 planar channels, the same channel and frame
+ * count (batches up to max_frames) and the context's shape; they must not overlap. */
+int wm_unpack16(wm_ctx* ctx, const wm_plane* src16, int bits, int msb_aligned, const wm_plane* out_f32, int slot);
+/* src_f32: WM_F32; device, host, or WM_MEM_SLOT_OUT: the slot's last wm_embed output when that is an f32 plane of the same channels
+ * (1 or 3) and frames.  out16: WM_U16, device or host, not overlapping src_f32.  Elements of a padded row beyond cols are left
+ * untouched. */
+int wm_pack16(wm_ctx* ctx, const wm_plane* src_f32, const wm_plane* out16, int bits, int msb_aligned, int slot);
+/* The video call: watermark d-bit grey frames.  out16 may be in16 itself (in place): in16 is read completely before out16 is written.
+ * A host layer over three enqueues on the slot: wm_unpack16(in16) into a slot-owned f32 plane X, wm_embed(X, X, Y) into a second
+ * slot-owned f32 plane Y (not in place: no snapshot; queued as a batched call, so it never takes the fused kernels, whatever the
+ * slot), wm_pack16(Y) into out16.  With WM_SLOT_SYNC it waits once at the end.  The bytes and the strength are those of the three
+ * calls made one by one.  Everything wm_embed documents holds for Y: the strength, WM_UNSOLVABLE and zero-energy frames (such a frame
+ * comes back as pack(unpack(in16))), hand-overs, and afterwards the slot's WM_MEM_SLOT_OUT names Y, an f32 grey plane wm_detect
+ * accepts.  `frames` results count against the slot's 4096.  ME with p = 3 (WM_ERR_BAD_P otherwise), NVF with p = 3..9; refused in
+ * band mode.  X and Y are kept per slot and grown on demand: the FIRST call on a slot that needs more of them than any call before
+ * reallocates them, which waits for the whole device, the other slots' streams included.  Later calls only enqueue. */
+int wm_embed16(wm_ctx* ctx, int mask, const wm_plane* in16, const wm_plane* out16, int bits, int msb_aligned, float* a_out,
+               int* status_out, int slot);
+/* wm_unpack16(img16) into the slot's X, then wm_detect(X) on the sweeps (never the fused kernels): the score of
+ * wm_detect(wm_unpack16(img16)) bit for bit.  Grey only; masks, band mode, result records and X as for wm_embed16. */
+int wm_detect16(wm_ctx* ctx, int mask, const wm_plane* img16, int bits, int msb_aligned, float* corr_out, int* status_out, int slot);
 
 /* Building blocks exposed for parity tests (the reference keeps them private):
  * computeCustomMask / computePredictionErrorMask (Watermark.cpp:96-114,176-218).

@@ -21,7 +21,7 @@ WM_OK, WM_UNSOLVABLE = 0, 1
 WM_ERR_BAD_P, WM_ERR_W_OPEN, WM_ERR_W_SIZE, WM_ERR_RUNTIME = -1, -2, -3, -4
 WM_ERR_BAD_ARG, WM_ERR_NO_DEVICE, WM_ERR_ALLOC, WM_ERR_PSNR, WM_ERR_BUSY = -5, -6, -7, -8, -9
 WM_SLOT_SYNC = -1
-WM_F32, WM_U8 = 0, 1
+WM_F32, WM_U8, WM_U16 = 0, 1, 2
 WM_MEM_DEVICE, WM_MEM_HOST, WM_MEM_SLOT_OUT = 0, 1, 2
 WM_KEYS_MAX = 4096
 
@@ -101,6 +101,11 @@ ABI = [
     ("wm_rgb2gray", C.c_int, [_ctx_p, _P(wm_plane), _P(wm_plane), _P(C.c_float), C.c_int]),
     ("wm_unpack_rgb8", C.c_int, [_ctx_p, _P(wm_packed), _P(wm_plane), _P(wm_plane), _P(C.c_float), C.c_int]),
     ("wm_pack_rgb8", C.c_int, [_ctx_p, _P(wm_plane), _P(wm_packed), C.c_int]),
+    ("wm_depth_scale", C.c_int, [C.c_int, _P(C.c_float), _P(C.c_float)]),
+    ("wm_unpack16", C.c_int, [_ctx_p, _P(wm_plane), C.c_int, C.c_int, _P(wm_plane), C.c_int]),
+    ("wm_pack16", C.c_int, [_ctx_p, _P(wm_plane), _P(wm_plane), C.c_int, C.c_int, C.c_int]),
+    ("wm_embed16", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), _P(wm_plane), C.c_int, C.c_int, _P(C.c_float), _P(C.c_int), C.c_int]),
+    ("wm_detect16", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), C.c_int, C.c_int, _P(C.c_float), _P(C.c_int), C.c_int]),
     ("wm_compute_mask", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), _P(wm_plane), _P(wm_plane), _P(C.c_float), _P(C.c_int), C.c_int]),
     ("wm_gram", C.c_int, [_ctx_p, _P(wm_plane), _P(C.c_double), C.c_int]),
     ("wm_band_configure", C.c_int, [_ctx_p, C.c_int, C.c_int, C.c_longlong]),
@@ -220,6 +225,41 @@ def packed_of(t):
         raise RuntimeError("packed pixels must be [R, C, 3] or [F, R, C, 3] with three adjacent bytes per pixel")
     frames, fstride = (t.shape[0], t.stride(0)) if t.dim() == 4 else (1, 0)
     return wm_packed(t.data_ptr(), t.shape[-3], t.shape[-2], WM_MEM_DEVICE if t.is_cuda else WM_MEM_HOST, frames, t.stride(-3), fstride)
+
+
+def depth_scale(bits):
+    """(k_in, k_out) of wm.h wm_depth_scale: the f32 constants that take a `bits`-bit sample to [0, 255] and back"""
+    a, b = C.c_float(), C.c_float()
+    rc = lib().wm_depth_scale(int(bits), C.byref(a), C.byref(b))
+    if rc != WM_OK:
+        _raise(rc)
+    return a.value, b.value
+
+
+def plane_any(t, channels=1):
+    """wm_plane view of a row-major array for the 16-bit calls (wm.h wm_unpack16 ...): [R,C], [3,R,C] (channels=3) or a batch of
+    either.  A numpy array or a CPU torch tensor is a WM_MEM_HOST plane (it must stay alive until the slot is synced), a GPU torch
+    tensor a device plane.  float32 is WM_F32; numpy uint16 and torch uint16 / int16 (the 16-bit pattern is the sample) are WM_U16"""
+    import numpy as np
+    if isinstance(t, np.ndarray):
+        if t.dtype not in (np.float32, np.uint16) or any(st % t.itemsize for st in t.strides):
+            raise RuntimeError(f"unsupported numpy array {t.dtype} / strides {t.strides}")
+        dt = WM_F32 if t.dtype == np.float32 else WM_U16
+        shape, strides, ptr, mem = t.shape, [st // t.itemsize for st in t.strides], t.ctypes.data, WM_MEM_HOST
+    else:
+        import torch
+        if t.dtype == torch.float32:
+            dt = WM_F32
+        elif t.dtype in (torch.int16, getattr(torch, "uint16", torch.int16)):
+            dt = WM_U16
+        else:
+            raise RuntimeError(f"unsupported dtype {t.dtype}")
+        shape, strides, ptr, mem = tuple(t.shape), list(t.stride()), t.data_ptr(), WM_MEM_DEVICE if t.is_cuda else WM_MEM_HOST
+    nd, base_nd = len(shape), 2 if channels == 1 else 3
+    if nd not in (base_nd, base_nd + 1) or strides[-1] != 1 or (channels > 1 and shape[-3] != channels):
+        raise RuntimeError(f"bad shape {tuple(shape)} / strides {tuple(strides)} for channels={channels}")
+    frames, fstride = (shape[0], strides[0]) if nd == base_nd + 1 else (1, 0)
+    return wm_plane(ptr, shape[-2], shape[-1], channels, dt, mem, frames, strides[-2], strides[-3] if channels > 1 else 0, fstride)
 
 
 class KeySet:
@@ -732,6 +772,54 @@ class Watermark:
         self.pack_rgb8_async(rgb, out, WM_SLOT_SYNC)
         return out
 
+    # -- samples of 9 to 16 bits (wm.h wm_unpack16 / wm_pack16 / wm_embed16 / wm_detect16) ---------------------------------
+    # samples: numpy uint16 arrays or torch uint16 / int16 tensors (CPU: staged; GPU: device planes), [R,C] or [F,R,C]
+    def _dev(self):
+        import torch
+        return torch.device("cuda", lib().wm_device(self._ctx))
+
+    def unpack16(self, samples, bits, msbAligned=False, channels=1, out=None):
+        """`bits`-bit samples -> float32 on [0, 255] on the engine's device: min(v, 2^bits - 1) * k_in (msbAligned: v >> (16 - bits))"""
+        import torch
+        if out is None:
+            out = torch.empty(tuple(samples.shape), dtype=torch.float32, device=self._dev())
+        torch.cuda.current_stream().synchronize()
+        self.unpack16_async(samples, bits, out, WM_SLOT_SYNC, msbAligned, channels)
+        return out
+
+    def pack16(self, image, bits, msbAligned=False, channels=1, out=None):
+        """float32 on [0, 255] -> `bits`-bit samples, clamped and rounded to nearest (ties to even), NaN gives 0.  `out`: a 16-bit
+        array or tensor of image's shape; default a new numpy uint16 array (the samples are downloaded)"""
+        import numpy as np
+        import torch
+        if out is None:
+            out = np.empty(tuple(image.shape), dtype=np.uint16)
+        torch.cuda.current_stream().synchronize()
+        self.pack16_async(image, out, bits, WM_SLOT_SYNC, msbAligned, channels)
+        return out
+
+    def makeWatermark16(self, samples, bits, maskType, msbAligned=False, out=None):
+        """makeWatermark of grey `bits`-bit frames (wm.h wm_embed16): unpack, embed onto the frame itself, pack.  `out`: where the
+        marked samples go, `samples` itself for an in-place call; default a new array like `samples`.  Returns (out, strength)"""
+        import numpy as np
+        import torch
+        if out is None:
+            out = np.empty_like(samples) if isinstance(samples, np.ndarray) else torch.empty_like(samples)
+        pin = plane_any(samples, 1)
+        a, st = self._strength_bufs(pin.frames)
+        torch.cuda.current_stream().synchronize()
+        self.embed16_async(pin, out, bits, maskType, WM_SLOT_SYNC, msbAligned, a, st)
+        return out, self._strengths(a, st, len(samples.shape) == 2)
+
+    def detectWatermark16(self, samples, bits, maskType, msbAligned=False):
+        """detectWatermark of grey `bits`-bit frames (wm.h wm_detect16); 0.0 for an unsolvable system"""
+        import torch
+        pimg = plane_any(samples, 1)
+        corr = (C.c_float * pimg.frames)()
+        torch.cuda.current_stream().synchronize()
+        self.detect16_async(pimg, bits, maskType, WM_SLOT_SYNC, msbAligned, corr)
+        return corr[0] if len(samples.shape) == 2 else list(corr)
+
     # north_star aliases
     embed = makeWatermark
     detect = detectWatermark
@@ -933,6 +1021,30 @@ class Watermark:
         wm_packed"""
         prgb, pp = self._as_plane(rgb, 3), self._as_packed(packed_out)
         self._chk(lib().wm_pack_rgb8(self._ctx, C.byref(prgb), C.byref(pp), slot))
+
+    @staticmethod
+    def _as_plane_any(t, channels):
+        return t if isinstance(t, wm_plane) else plane_any(t, channels)
+
+    def unpack16_async(self, samples, bits, out_f32, slot, msbAligned=False, channels=1):
+        """wm_unpack16 enqueued on `slot`: samples / out_f32 arrays or tensors (plane_any) or wm_planes"""
+        ps, po = self._as_plane_any(samples, channels), self._as_plane_any(out_f32, channels)
+        self._chk(lib().wm_unpack16(self._ctx, C.byref(ps), int(bits), int(msbAligned), C.byref(po), slot))
+
+    def pack16_async(self, src_f32, out16, bits, slot, msbAligned=False, channels=1):
+        """wm_pack16 enqueued on `slot`: src_f32 may be a WM_MEM_SLOT_OUT wm_plane (the slot's last f32 embed output)"""
+        ps, po = self._as_plane_any(src_f32, channels), self._as_plane_any(out16, channels)
+        self._chk(lib().wm_pack16(self._ctx, C.byref(ps), C.byref(po), int(bits), int(msbAligned), slot))
+
+    def embed16_async(self, in16, out16, bits, maskType, slot, msbAligned=False, a_out=None, status_out=None):
+        """wm_embed16 enqueued on `slot`: grey frames, out16 may be in16"""
+        pi, po = self._as_plane_any(in16, 1), self._as_plane_any(out16, 1)
+        self._chk(lib().wm_embed16(self._ctx, int(maskType), C.byref(pi), C.byref(po), int(bits), int(msbAligned), a_out, status_out, slot))
+
+    def detect16_async(self, img16, bits, maskType, slot, msbAligned=False, corr_out=None, status_out=None):
+        """wm_detect16 enqueued on `slot`"""
+        pi = self._as_plane_any(img16, 1)
+        self._chk(lib().wm_detect16(self._ctx, int(maskType), C.byref(pi), int(bits), int(msbAligned), corr_out, status_out, slot))
 
     def sync(self, slot):
         return self._chk(lib().wm_sync(self._ctx, slot))

@@ -11,6 +11,9 @@
 //     watermarked (ME mask) and Y'UV frames are written in order to `encode_watermark_file_path` (.y4m/.yuv, or "-"
 //     for stdout so that an external `ffmpeg -f rawvideo ...` can encode as the reference's pipe does), or, when
 //     `watermark_detection = true`, "Correlation for frame: i: c" is printed per interval frame.
+//     A y4m colour tag 420pNN with NN in 9..16 (C420p10: 10-bit masters), or the optional key video_bit_depth for a headerless
+//     .yuv, selects NN-bit samples: 16-bit little-endian, in the low bits; the Y plane goes through wm_embed16 / wm_detect16,
+//     chroma passes through as bytes, two per sample.  Every other 420* tag is 8-bit.
 // FFmpeg demux/decode/encode (main.cpp:255-263,284-293) is out of scope: containers are decoded outside.
 // Frames are staged from pinned host buffers through the engine's slots, several frames in flight.
 #include "../../../include/Watermark.hpp"
@@ -155,9 +158,11 @@ static int testForImage(const INIReader& inir, const int p, const float psnr, co
 struct YuvReader {
     FILE* f = nullptr;
     int width = 0, height = 0;
+    int bits = 8;  // sample depth: 8, or 9..16 (two bytes per sample, little-endian, LSB-aligned)
     bool y4m = false;
     string header;
-    bool open(const string& path, int w, int h)
+    size_t bps() const { return bits > 8 ? 2 : 1; }
+    bool open(const string& path, int w, int h, int depth)
     {
         f = std::fopen(path.c_str(), "rb");
         if (!f) return false;
@@ -172,9 +177,17 @@ struct YuvReader {
                     if (header[i + 1] == 'W') width = std::atoi(&header[i + 2]);
                     if (header[i + 1] == 'H') height = std::atoi(&header[i + 2]);
                     if (header[i + 1] == 'C' && header.compare(i + 2, 3, "420") != 0) return false;  // only 4:2:0 (main.cpp:458-459)
+                    if (header[i + 1] == 'C' && header.compare(i + 2, 4, "420p") == 0) {  // C420pNN: NN-bit samples (C420paldv etc.: 8)
+                        size_t e = i + 6;
+                        int nn = 0;
+                        while (e < header.size() && header[e] >= '0' && header[e] <= '9' && nn < 100) nn = 10 * nn + (header[e++] - '0');
+                        const bool ends = e >= header.size() || header[e] == ' ' || header[e] == '\n';
+                        if (e > i + 6 && ends && nn >= 9 && nn <= 16) bits = nn;
+                    }
                 }
             }
-        } else { width = w; height = h; }
+        } else { width = w; height = h; bits = depth; }
+        if (bits != 8 && (bits < 9 || bits > 16)) return false;
         return width > 0 && height > 0;
     }
     bool next(uint8_t* y, uint8_t* uv)
@@ -183,7 +196,7 @@ struct YuvReader {
             char line[128];
             if (!std::fgets(line, sizeof line, f)) return false;  // "FRAME\n"
         }
-        const size_t ny = (size_t)width * height, nuv = 2 * ((size_t)(width / 2) * (height / 2));
+        const size_t ny = bps() * width * height, nuv = bps() * 2 * ((size_t)(width / 2) * (height / 2));
         if (std::fread(y, 1, ny, f) != ny) return false;
         return std::fread(uv, 1, nuv, f) == nuv;
     }
@@ -195,10 +208,12 @@ static int testForVideo(const string& videoFile, const INIReader& inir, const in
     const bool showFps = inir.GetBoolean("options", "execution_time_in_fps", false);
     const int watermarkInterval = (int)inir.GetInteger("parameters_video", "watermark_interval", 30);
     YuvReader in;
-    checkError(!in.open(videoFile, (int)inir.GetInteger("parameters_video", "video_width", 0), (int)inir.GetInteger("parameters_video", "video_height", 0)),
-               "ERROR: Failed to open input video file (need a yuv420p .y4m, or .yuv with video_width/video_height)");
-    const int width = in.width, height = in.height;
-    const size_t ny = (size_t)width * height, nuv = 2 * ((size_t)(width / 2) * (height / 2));
+    checkError(!in.open(videoFile, (int)inir.GetInteger("parameters_video", "video_width", 0), (int)inir.GetInteger("parameters_video", "video_height", 0),
+                        (int)inir.GetInteger("parameters_video", "video_bit_depth", 8)),
+               "ERROR: Failed to open input video file (need a yuv420p .y4m, or .yuv with video_width/video_height; video_bit_depth 8 or 9..16)");
+    const int width = in.width, height = in.height, bits = in.bits;
+    const bool deep = bits > 8;  // 16-bit samples: the Y plane is a pinned u16 plane and takes wm_embed16 / wm_detect16
+    const size_t ny = in.bps() * width * height, nuv = in.bps() * 2 * ((size_t)(width / 2) * (height / 2));  // bytes
     const Watermark watermarkObj(height, width, inir.Get("paths", "watermark", ""), p, psnr, device);
     wm_ctx* ctx = watermarkObj.handle();
     constexpr int SLOTS = 3;  // frames in flight
@@ -214,7 +229,7 @@ static int testForVideo(const string& videoFile, const INIReader& inir, const in
     }
     auto plane_of = [&](uint8_t* y) {
         wm_plane pl{};
-        pl.data = y; pl.rows = height; pl.cols = width; pl.channels = 1; pl.dtype = WM_U8; pl.mem = WM_MEM_HOST; pl.frames = 1; pl.pitch = width;
+        pl.data = y; pl.rows = height; pl.cols = width; pl.channels = 1; pl.dtype = deep ? WM_U16 : WM_U8; pl.mem = WM_MEM_HOST; pl.frames = 1; pl.pitch = width;
         return pl;
     };
 
@@ -228,7 +243,8 @@ static int testForVideo(const string& videoFile, const INIReader& inir, const in
         out = outPath == "-" ? stdout : std::fopen(outPath.c_str(), "wb");
         checkError(!out, "Error: Could not open output");
         outY4m = outPath.size() > 4 && outPath.substr(outPath.size() - 4) == ".y4m";
-        if (outY4m) std::fputs(in.y4m ? in.header.c_str() : ("YUV4MPEG2 W" + std::to_string(width) + " H" + std::to_string(height) + " F30:1 Ip C420\n").c_str(), out);
+        if (outY4m) std::fputs(in.y4m ? in.header.c_str() : ("YUV4MPEG2 W" + std::to_string(width) + " H" + std::to_string(height) + " F30:1 Ip C420" +
+                                                              (deep ? "p" + std::to_string(bits) : string()) + "\n").c_str(), out);
     }
     auto retire = [&](InFlight& s, int slot) {  // in frame order: slots are reused round-robin
         if (!s.busy) return;
@@ -255,7 +271,8 @@ static int testForVideo(const string& videoFile, const INIReader& inir, const in
         if (s.marked) {
             const wm_plane pl = plane_of(s.y);
             int rc;
-            if (doEmbed) rc = wm_embed(ctx, WM_MASK_ME, &pl, &pl, &pl, &s.a, &s.status, slot);  // makeWatermark(frame, frame, ME)
+            if (deep) rc = doEmbed ? wm_embed16(ctx, WM_MASK_ME, &pl, &pl, bits, 0, &s.a, &s.status, slot) : wm_detect16(ctx, WM_MASK_ME, &pl, bits, 0, &s.corr, &s.status, slot);
+            else if (doEmbed) rc = wm_embed(ctx, WM_MASK_ME, &pl, &pl, &pl, &s.a, &s.status, slot);  // makeWatermark(frame, frame, ME)
             else rc = wm_detect(ctx, WM_MASK_ME, &pl, &s.corr, &s.status, slot);
             checkError(rc < 0, string("ERROR: ") + wm_last_error(ctx));
         }

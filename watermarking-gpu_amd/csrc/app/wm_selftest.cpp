@@ -142,6 +142,23 @@ int main(int argc, char** argv)
         CHECK(cast_ok, "packRgb8 of a watermarked image is the cast to 8 bits");
     }
 
+    // ---- 10-bit samples: every code survives unpack16 / pack16, makeWatermark16 marks a frame in place, detectWatermark16 finds it
+    {
+        std::vector<uint16_t> v((size_t)R * C), back(v.size()), marked;
+        for (size_t i = 0; i < v.size(); ++i) v[i] = (uint16_t)std::lrint(x[i] * (1023.0f / 255.0f));
+        for (size_t i = 0; i < 1024; ++i) v[i] = (uint16_t)i;
+        const wm::Image up = wm1.unpack16(v.data(), 1, 10);
+        std::vector<float> g((size_t)R * C);
+        up.host(g.data());
+        wm1.pack16(up, back.data(), 10);
+        CHECK(g[0] == 0.0f && g[1023] == 255.0f && back == v, "unpack16 / pack16: full scale is 255, every 10-bit code comes back");
+        marked = v;
+        const float a16 = wm1.makeWatermark16(marked.data(), 10, ME);
+        const float c16 = wm1.detectWatermark16(marked.data(), 10, ME);
+        CHECK(a16 > 0.0f && marked != v && c16 > 0.2f && std::fabs(wm1.detectWatermark16(v.data(), 10, ME)) < 0.05f,
+              "makeWatermark16 in place, detectWatermark16: the marked samples correlate, the source does not");
+    }
+
     // ---- deep copy that shares W (Watermark.cpp:30-51): same results, independent lifetime
     float a_copy = 0.0f, a_assign = 0.0f;
     {

@@ -168,6 +168,10 @@ struct Slot {
     void* tab_host = nullptr; void* tab_dev = nullptr; size_t tab_bytes = 0, tab_used = 0;
     // wm_detect_bits: what its tile fold writes (sums [frames][ny * nx][3] f64, records [frames], map [frames][ny * nx] f32; grown on demand)
     void* bits_scr = nullptr; size_t bits_scr_bytes = 0;
+    // wm_embed16 / wm_detect16: the f32 planes X (the unpacked samples) and Y (the embed's output, what WM_MEM_SLOT_OUT then names),
+    // dense in staged_layout's form (grown on demand)
+    void* x16 = nullptr; size_t x16_bytes = 0;
+    void* y16 = nullptr; size_t y16_bytes = 0;
 };
 
 struct ProfRec { int kid; hipEvent_t a, b; bool first; };  // first: the sweep's first launch (counts the call)
@@ -371,7 +375,7 @@ void free_slot(Slot& s)
     (void)hipFree(s.st_in); (void)hipFree(s.st_base); (void)hipFree(s.st_out); (void)hipFree(s.fz_block); (void)hipFree(s.d_ho); (void)hipFree(s.d_hoseam);
     (void)hipFree(s.d_hodig); (void)hipFree(s.keys_part); (void)hipFree(s.ekeys_part); (void)hipFree(s.tiles_rec); (void)hipFree(s.keys_tiles_rec);
     if (s.tab_host) (void)hipHostFree(s.tab_host);
-    (void)hipFree(s.tab_dev); (void)hipFree(s.bits_scr);
+    (void)hipFree(s.tab_dev); (void)hipFree(s.bits_scr); (void)hipFree(s.x16); (void)hipFree(s.y16);
     s = Slot();
 }
 
@@ -615,7 +619,7 @@ int create_ctx(wm_ctx** out, int device, int rows, int cols, int p, float psnr, 
 // below 4 GiB (a 32768 x 32768 f32 plane is not: it takes the generic path)
 bool fits_32bit(int rows, long long pitch, int dtype)
 {
-    return (long long)rows * pitch * (dtype == WM_F32 ? 4 : 1) < (1LL << 32) - 4096;
+    return (long long)rows * pitch * (dtype == WM_F32 ? 4 : dtype == WM_U16 ? 2 : 1) < (1LL << 32) - 4096;
 }
 
 bool vec_ok(const void* p, int rows, long long pitch, long long fstride, long long cstride, int dtype, int frames, int channels)
@@ -656,7 +660,7 @@ int check_plane(wm_ctx* ctx, const wm_plane* pl, int frames_expected, bool allow
     return WM_OK;
 }
 
-size_t elem_size(int dtype) { return dtype == WM_F32 ? 4 : 1; }
+size_t elem_size(int dtype) { return dtype == WM_F32 ? 4 : dtype == WM_U16 ? 2 : 1; }
 
 PlaneDesc desc_device(const wm_plane* pl)
 {
@@ -2413,6 +2417,206 @@ int wm_pack_rgb8(wm_ctx* ctx, const wm_plane* rgb, const wm_packed* packed_out, 
             HIPCHK(ctx, hipMemcpy2DAsync((char*)packed_out->data + (size_t)f * (frames > 1 ? packed_out->frame_stride_bytes : 0), packed_out->pitch_bytes,
                                          (const char*)s.st_base + (size_t)f * pd.fstride, pd.pitch, 3 * (size_t)packed_out->cols, packed_out->rows, hipMemcpyDeviceToHost, s.stream));
     return finish_call(ctx, s, slot, 0, 0, false, nullptr, nullptr);
+}
+
+// ---- samples of 9 to 16 bits: wm_depth_scale, wm_unpack16, wm_pack16 and the host layers wm_embed16, wm_detect16 (wm.h; kernels in
+// wm_k_convert16.hip).  The two conversions are the pixel-format front once more: the same order of checks (`bits` and msb_aligned
+// where the weights stood), host inputs in Slot::st_in, host outputs in Slot::st_base, no result records.
+int wm_depth_scale(int bits, float* to255, float* from255)
+{
+    if (bits < 9 || bits > 16 || !to255 || !from255) return WM_ERR_BAD_ARG;
+    const double maxv = (double)((1u << bits) - 1u);
+    *to255 = (float)(255.0 / maxv);
+    *from255 = (float)(maxv / 255.0);
+    return WM_OK;
+}
+// what a u16 plane must satisfy on its own: check_plane's rules for 2-byte elements (check_plane itself keeps refusing the dtype
+// for every other entry point) and a 2-byte aligned base
+static int check_plane16(wm_ctx* ctx, const wm_plane* pl, const char* what)
+{
+    if (pl->dtype != WM_U16) return fail(ctx, WM_ERR_BAD_ARG, std::string(what) + ": must be a WM_U16 plane");
+    wm_plane t = *pl;
+    t.dtype = WM_U8;  // (the rules below do not depend on the element size)
+    const int rc = check_plane(ctx, &t, 0, true, what);
+    if (rc != WM_OK) return rc;
+    return reinterpret_cast<uintptr_t>(pl->data) % 2 == 0 ? WM_OK : fail(ctx, WM_ERR_BAD_ARG, std::string(what) + ": data must be 2-byte aligned");
+}
+static int check_plane_f32(wm_ctx* ctx, const wm_plane* pl, const char* what, bool allow_slot_out)
+{
+    if (pl->dtype != WM_F32) return fail(ctx, WM_ERR_BAD_ARG, std::string(what) + ": must be a WM_F32 plane");
+    return check_plane(ctx, pl, 0, true, what, allow_slot_out);
+}
+static int check_depth(wm_ctx* ctx, int bits, int msb_aligned)
+{
+    if (bits < 9 || bits > 16) return fail(ctx, WM_ERR_BAD_ARG, "bits=" + std::to_string(bits) + ": must be 9..16");
+    return msb_aligned == 0 || msb_aligned == 1 ? WM_OK : fail(ctx, WM_ERR_BAD_ARG, "msb_aligned must be 0 or 1");
+}
+// a device u16 plane, described: four samples of a lane are one 8-byte access when the base is a multiple of 4 bytes and the pitch
+// and the used strides are even
+static PlaneDesc desc_device16(const wm_plane* pl)
+{
+    PlaneDesc d;
+    d.p = pl->data; d.pitch = pl->pitch; d.fstride = pl->frames > 1 ? pl->frame_stride : 0;
+    d.cstride = pl->channels > 1 ? pl->channel_stride : 0;
+    d.dtype = WM_U16; d.channels = pl->channels;
+    d.aligned = reinterpret_cast<uintptr_t>(pl->data) % 4 == 0 && d.pitch % 2 == 0 && d.fstride % 2 == 0 && d.cstride % 2 == 0 ? 1 : 0;
+    return d;
+}
+// the planes' shared front: what both must satisfy together (channels, frames, the launch grid)
+static int check_pair16(wm_ctx* ctx, const char* who, const wm_plane* a, const wm_plane* b)
+{
+    if (a->channels != b->channels) return fail(ctx, WM_ERR_BAD_ARG, std::string(who) + ": channel count mismatch");
+    if (a->frames != b->frames) return fail(ctx, WM_ERR_BAD_ARG, std::string(who) + ": frame count mismatch");
+    if (!convert_grid_fits(ctx->rows, a->frames * a->channels)) return fail(ctx, WM_ERR_BAD_ARG, std::string(who) + ": rows or frames beyond the launch grid");
+    return WM_OK;
+}
+
+int wm_unpack16(wm_ctx* ctx, const wm_plane* src16, int bits, int msb_aligned, const wm_plane* out_f32, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    if (!src16 || !src16->data || !out_f32 || !out_f32->data) return fail(ctx, WM_ERR_BAD_ARG, "wm_unpack16: null plane");
+    int rc;
+    if ((rc = check_shape(ctx, src16->rows, src16->cols, "src16")) != WM_OK || (rc = check_shape(ctx, out_f32->rows, out_f32->cols, "out_f32")) != WM_OK) return rc;
+    if ((rc = check_plane16(ctx, src16, "src16")) != WM_OK || (rc = check_plane_f32(ctx, out_f32, "out_f32", false)) != WM_OK) return rc;
+    if ((rc = check_pair16(ctx, "wm_unpack16", src16, out_f32)) != WM_OK) return rc;
+    const int frames = src16->frames;
+    const bool dev_in = src16->mem == WM_MEM_DEVICE, dev_out = out_f32->mem == WM_MEM_DEVICE;
+    if (dev_in && dev_out && ranges_overlap(range_of(ctx, desc_device16(src16), frames), range_of(ctx, desc_device(out_f32), frames)))
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_unpack16: out_f32 overlaps src16");
+    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
+    if ((rc = check_depth(ctx, bits, msb_aligned)) != WM_OK) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    PlaneDesc xd, od;
+    if (dev_in) xd = desc_device16(src16);
+    else {
+        const Staged st = staged_layout(src16);
+        if ((rc = ensure(ctx, &s.st_in, &s.st_in_bytes, st.bytes)) != WM_OK) return rc;
+        if ((rc = stage_in(ctx, s, src16, s.st_in, st)) != WM_OK) return rc;
+        xd = st.d; xd.p = s.st_in;
+    }
+    Staged st_o{};
+    if (dev_out) od = desc_device(out_f32);
+    else {
+        st_o = staged_layout(out_f32);
+        if ((rc = ensure(ctx, &s.st_base, &s.st_base_bytes, st_o.bytes)) != WM_OK) return rc;
+        od = st_o.d; od.p = s.st_base;
+    }
+    invalidate_handovers(ctx, od, frames);
+    float k_in, k_out;
+    (void)wm_depth_scale(bits, &k_in, &k_out);
+    launch_unpack16(s.stream, ctx->rows, ctx->cols, frames, xd, od, bits, msb_aligned, k_in);
+    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
+    if (!dev_out && (rc = stage_out(ctx, s, out_f32, s.st_base, st_o)) != WM_OK) return rc;
+    return finish_call(ctx, s, slot, 0, 0, false, nullptr, nullptr);
+}
+
+int wm_pack16(wm_ctx* ctx, const wm_plane* src_f32, const wm_plane* out16, int bits, int msb_aligned, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    if (plane_null(src_f32) || !out16 || !out16->data) return fail(ctx, WM_ERR_BAD_ARG, "wm_pack16: null plane");
+    int rc;
+    if ((rc = check_shape(ctx, src_f32->rows, src_f32->cols, "src_f32")) != WM_OK || (rc = check_shape(ctx, out16->rows, out16->cols, "out16")) != WM_OK) return rc;
+    if ((rc = check_plane_f32(ctx, src_f32, "src_f32", true)) != WM_OK || (rc = check_plane16(ctx, out16, "out16")) != WM_OK) return rc;
+    if ((rc = check_pair16(ctx, "wm_pack16", src_f32, out16)) != WM_OK) return rc;
+    const int frames = src_f32->frames;
+    const bool dev_in = src_f32->mem == WM_MEM_DEVICE, dev_out = out16->mem == WM_MEM_DEVICE, slot_in = src_f32->mem == WM_MEM_SLOT_OUT;
+    if (dev_in && dev_out && ranges_overlap(range_of(ctx, desc_device(src_f32), frames), range_of(ctx, desc_device16(out16), frames)))
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_pack16: out16 overlaps src_f32");
+    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
+    if ((rc = check_depth(ctx, bits, msb_aligned)) != WM_OK) return rc;
+    if (slot_in && (s.last_out_frames == 0 || s.last_out.channels != src_f32->channels || frames != s.last_out_frames || s.last_out_dtype != WM_F32))
+        return fail(ctx, WM_ERR_BAD_ARG, "WM_MEM_SLOT_OUT: no matching f32 embed output on this slot (channels / frames must equal the last wm_embed's)");
+    if (slot_in && dev_out && ranges_overlap(range_of(ctx, s.last_out, frames), range_of(ctx, desc_device16(out16), frames)))
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_pack16: out16 overlaps src_f32 (the slot's last output)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    PlaneDesc xd, od;
+    if (slot_in) xd = s.last_out;
+    else if (dev_in) xd = desc_device(src_f32);
+    else {
+        const Staged st = staged_layout(src_f32);
+        if ((rc = ensure(ctx, &s.st_in, &s.st_in_bytes, st.bytes)) != WM_OK) return rc;
+        if ((rc = stage_in(ctx, s, src_f32, s.st_in, st)) != WM_OK) return rc;
+        xd = st.d; xd.p = s.st_in;
+    }
+    Staged st_o{};
+    if (dev_out) od = desc_device16(out16);
+    else {
+        st_o = staged_layout(out16);
+        if ((rc = ensure(ctx, &s.st_base, &s.st_base_bytes, st_o.bytes)) != WM_OK) return rc;
+        od = st_o.d; od.p = s.st_base;
+    }
+    invalidate_handovers(ctx, od, frames);  // (by the bytes the u16 plane spans)
+    float k_in, k_out;
+    (void)wm_depth_scale(bits, &k_in, &k_out);
+    launch_pack16(s.stream, ctx->rows, ctx->cols, frames, xd, od, bits, msb_aligned, k_out);
+    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
+    if (!dev_out && (rc = stage_out(ctx, s, out16, s.st_base, st_o)) != WM_OK) return rc;
+    return finish_call(ctx, s, slot, 0, 0, false, nullptr, nullptr);
+}
+
+// the front of the two host layers: everything they refuse themselves, before anything is queued; then the slot's f32 plane(s),
+// dense in staged_layout's form, described as device planes for the calls below
+static int open16(wm_ctx* ctx, const char* who, int mask, const wm_plane* p16, const char* what, int bits, int msb_aligned, int slot)
+{
+    int rc;
+    if ((rc = check_mask(ctx, mask)) != WM_OK || (rc = refuse_band(ctx, who)) != WM_OK) return rc;
+    if ((rc = check_shape(ctx, p16->rows, p16->cols, what)) != WM_OK || (rc = check_plane16(ctx, p16, what)) != WM_OK) return rc;
+    if (p16->channels != 1) return fail(ctx, WM_ERR_BAD_ARG, std::string(who) + ": grey planes only");
+    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    if ((rc = check_depth(ctx, bits, msb_aligned)) != WM_OK) return rc;
+    return check_res_room(ctx, slot_of(ctx, slot), p16->frames);
+}
+static int slot_plane16(wm_ctx* ctx, void** buf, size_t* have, const wm_plane* like, wm_plane* pl)
+{
+    *pl = *like;
+    pl->dtype = WM_F32; pl->mem = WM_MEM_DEVICE; pl->channels = 1; pl->channel_stride = 0;
+    const Staged st = staged_layout(pl);
+    pl->pitch = st.pitch; pl->frame_stride = st.d.fstride;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int rc = ensure(ctx, buf, have, st.bytes, WM_ERR_ALLOC);
+    pl->data = *buf;
+    return rc;
+}
+
+int wm_embed16(wm_ctx* ctx, int mask, const wm_plane* in16, const wm_plane* out16, int bits, int msb_aligned, float* a_out, int* status_out, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    if (!in16 || !in16->data || !out16 || !out16->data) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed16: null plane");
+    int rc;
+    if ((rc = check_shape(ctx, out16->rows, out16->cols, "out16")) != WM_OK) return rc;
+    if ((rc = open16(ctx, "wm_embed16", mask, in16, "in16", bits, msb_aligned, slot)) != WM_OK) return rc;
+    if ((rc = check_plane16(ctx, out16, "out16")) != WM_OK) return rc;
+    if (out16->channels != 1 || out16->frames != in16->frames) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed16: out16 must be a grey plane with in16's frame count");
+    Slot& s = slot_of(ctx, slot);
+    wm_plane X, Y;
+    if ((rc = slot_plane16(ctx, &s.x16, &s.x16_bytes, in16, &X)) != WM_OK) return rc;
+    // (a Y that moves takes the plane WM_MEM_SLOT_OUT named with it)
+    if (s.y16_bytes < (size_t)X.frame_stride * X.frames * sizeof(float) && s.last_out.p == s.y16) { s.last_out_frames = 0; s.ho.valid = false; }
+    if ((rc = slot_plane16(ctx, &s.y16, &s.y16_bytes, in16, &Y)) != WM_OK) return rc;
+    // three enqueues; the embed as a batched call (never the fused kernels), one wait at the end of a synchronous call.
+    // in16 is read completely before out16 is written (stream order): out16 may be in16
+    const int q = slot_index(slot);
+    if ((rc = wm_unpack16(ctx, in16, bits, msb_aligned, &X, q)) != WM_OK) return rc;
+    if ((rc = wm_embed(ctx, mask, &X, &X, &Y, a_out, status_out, q)) != WM_OK) return rc;
+    if ((rc = wm_pack16(ctx, &Y, out16, bits, msb_aligned, q)) != WM_OK) return rc;
+    return slot == WM_SLOT_SYNC ? do_sync(ctx, s) : WM_OK;
+}
+
+int wm_detect16(wm_ctx* ctx, int mask, const wm_plane* img16, int bits, int msb_aligned, float* corr_out, int* status_out, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    if (!img16 || !img16->data) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect16: null plane");
+    int rc;
+    if ((rc = open16(ctx, "wm_detect16", mask, img16, "img16", bits, msb_aligned, slot)) != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
+    wm_plane X;
+    if ((rc = slot_plane16(ctx, &s.x16, &s.x16_bytes, img16, &X)) != WM_OK) return rc;
+    const int q = slot_index(slot);
+    if ((rc = wm_unpack16(ctx, img16, bits, msb_aligned, &X, q)) != WM_OK) return rc;
+    if ((rc = wm_detect(ctx, mask, &X, corr_out, status_out, q)) != WM_OK) return rc;
+    return slot == WM_SLOT_SYNC ? do_sync(ctx, s) : WM_OK;
 }
 
 int wm_gram(wm_ctx* ctx, const wm_plane* img, double* gram_out, int slot)

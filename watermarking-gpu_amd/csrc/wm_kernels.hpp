@@ -46,7 +46,7 @@ struct PlaneDesc {
     long long pitch;    // elements
     long long fstride;  // elements between frames
     long long cstride;  // elements between channels
-    int dtype;          // 0 f32, 1 u8
+    int dtype;          // 0 f32, 1 u8 (2 u16: wm_k_convert16.hip only)
     int channels;
     int aligned;        // base/pitch/strides allow 4-pixel vector access
 };
@@ -318,6 +318,12 @@ bool convert_grid_fits(int rows, int frames);
 void launch_rgb2gray(hipStream_t s, int rows, int cols, int frames, const PlaneDesc& rgb, const PlaneDesc& gray, const float* w);
 void launch_unpack_rgb8(hipStream_t s, int rows, int cols, int frames, const PackedDesc& pk, const PlaneDesc& rgb, const PlaneDesc& gray, const float* w);
 void launch_pack_rgb8(hipStream_t s, int rows, int cols, int frames, const PlaneDesc& rgb, const PackedDesc& pk);
+// samples of 9 to 16 bits (wm_unpack16 / wm_pack16, wm_k_convert16.hip): the same lane mapping with frames x channels as the grid's
+// z (convert_grid_fits(rows, frames * channels)).  One plane has dtype 2 (u16: 2-byte elements; aligned: base a multiple of 4 bytes,
+// pitch and used strides even, so a lane's four samples are one 8-byte access), the other is f32; both have the same channels.
+// k_in / k_out: wm_depth_scale's constants of `bits`
+void launch_unpack16(hipStream_t s, int rows, int cols, int frames, const PlaneDesc& src, const PlaneDesc& out, int bits, int msb_aligned, float k_in);
+void launch_pack16(hipStream_t s, int rows, int cols, int frames, const PlaneDesc& src, const PlaneDesc& out, int bits, int msb_aligned, float k_out);
 // band mode: solve the 8x8 system from all-reduced Gram totals [frames][44]; writes coef / status like k_gram's tail
 void launch_solve_totals(hipStream_t s, int frames, const double* totals, float* coef, int* status);
 // band mode, device-resident exchange (wm_band_*_dev): glue kernels between the sweeps and the caller's collectives
