@@ -455,6 +455,78 @@ public:
         strengths = a;
         return copies;
     }
+    // ---- a key per frame of a batch (wm.h wm_key_schedule, wm_embed_select, wm_detect_select).  A batch is a stack of images
+    // (wm::Image::stack: one buffer, image i at i * elements()); the engine must have been configured for that many frames
+    // (configure(nslots, maxFrames)).
+    // which key does frame n of a video take?  Entry i is a function of (seed, firstFrame + i) alone, in 0 .. nkeys - 1
+    static std::vector<int32_t> keySchedule(int nkeys, uint64_t seed, uint64_t firstFrame, int frames)
+    {
+        std::vector<int32_t> keyOfFrame((size_t)(frames > 0 ? frames : 0));
+        const int rc = wm_key_schedule(nkeys, seed, firstFrame, frames, keyOfFrame.empty() ? nullptr : keyOfFrame.data());
+        if (rc < 0) throw std::runtime_error(std::string("keySchedule: ") + wm_strerror(rc));
+        return keyOfFrame;
+    }
+    void configure(int nslots, int maxFrames) const
+    {
+        const int rc = wm_configure(ctx, nslots, maxFrames);
+        if (rc < 0) fail(rc, "configure");
+    }
+    // makeWatermark of image f of the stack with key keyOfFrame[f] of `keys` as W in one call: image f of the result is what
+    // makeWatermark returns with that key as W, strengths[f] its strength.  An image that is not solvable comes back as its base,
+    // bit for bit, and its strength is left as it was (Watermark.cpp:164-165); the context's own W is not used
+    std::vector<wm::Image> makeWatermarkSelect(const std::vector<wm::Image>& inputStack, const std::vector<wm::Image>& outputStack,
+                                               const WatermarkKeys& keys, const std::vector<int32_t>& keyOfFrame, std::vector<float>& strengths,
+                                               MASK_TYPE maskType) const
+    {
+        const wm_plane pin = stackPlane(inputStack, "makeWatermarkSelect"), pbase = stackPlane(outputStack, "makeWatermarkSelect");
+        const size_t F = inputStack.size();
+        if (keyOfFrame.size() != F || outputStack.size() != F) fail(WM_ERR_BAD_ARG, "makeWatermarkSelect");
+        const wm::Image& b0 = outputStack[0];
+        std::vector<wm::Image> out = wm::Image::stack((int)F, b0.rows(), b0.cols(), b0.channels(), b0.type(), device);
+        const wm_plane pout = stackPlane(out, "makeWatermarkSelect");
+        std::vector<float> a(F, 0.0f);
+        std::vector<int> st(F, 0);
+        const int rc = wm_embed_select(ctx, (int)maskType, &pin, &pbase, &pout, keys.handle(), keyOfFrame.data(), a.data(), st.data(), WM_SLOT_SYNC);
+        if (rc < 0) fail(rc, "makeWatermarkSelect");
+        strengths.resize(F, 0.0f);
+        for (size_t f = 0; f < F; ++f)
+            if (st[f] == 0) strengths[f] = a[f];
+        return out;
+    }
+    // detectWatermark of image f of the stack against key keyOfFrame[f] of `keys` in one call: score f is what detectWatermark
+    // returns with that key as W (0.0f where the prediction system is not solvable)
+    std::vector<float> detectWatermarkSelect(const std::vector<wm::Image>& watermarkedStack, const WatermarkKeys& keys,
+                                             const std::vector<int32_t>& keyOfFrame, MASK_TYPE maskType) const
+    {
+        const wm_plane pimg = stackPlane(watermarkedStack, "detectWatermarkSelect");
+        if (keyOfFrame.size() != watermarkedStack.size()) fail(WM_ERR_BAD_ARG, "detectWatermarkSelect");
+        std::vector<float> corr(keyOfFrame.size(), 0.0f);
+        const int rc = wm_detect_select(ctx, (int)maskType, &pimg, keys.handle(), keyOfFrame.data(), corr.data(), nullptr, WM_SLOT_SYNC);
+        if (rc < 0) fail(rc, "detectWatermarkSelect");
+        return corr;
+    }
+    // the same two enqueued on `slot` (wm.h: planes of any memory kind, WM_MEM_SLOT_OUT included; keyOfFrame is copied before the
+    // call returns; strengths / correlations [frames] and status [frames], may be null, are written by sync(slot); `keys` must stay
+    // alive and unmodified until then)
+    void makeWatermarkSelectAsync(const wm_plane& input, const wm_plane& base, const wm_plane& out, const WatermarkKeys& keys,
+                                  const int32_t* keyOfFrame, float* strengths, int* status, MASK_TYPE maskType, int slot) const
+    {
+        const int rc = wm_embed_select(ctx, (int)maskType, &input, &base, &out, keys.handle(), keyOfFrame, strengths, status, slot);
+        if (rc < 0) fail(rc, "makeWatermarkSelectAsync");
+    }
+    void detectWatermarkSelectAsync(const wm_plane& image, const WatermarkKeys& keys, const int32_t* keyOfFrame, float* correlations, int* status,
+                                    MASK_TYPE maskType, int slot) const
+    {
+        const int rc = wm_detect_select(ctx, (int)maskType, &image, keys.handle(), keyOfFrame, correlations, status, slot);
+        if (rc < 0) fail(rc, "detectWatermarkSelectAsync");
+    }
+    // waits for everything enqueued on `slot` and delivers its results: WM_OK, or WM_UNSOLVABLE when a frame's system was not solvable
+    int sync(int slot) const
+    {
+        const int rc = wm_sync(ctx, slot);
+        if (rc < 0) fail(rc, "sync");
+        return rc;
+    }
     // one image, K payload copies in one call (wm.h wm_embed_signs_multi): signs[k] is makeWatermarkSigns' table of copy k, copy k what
     // makeWatermarkSigns returns with it; ONE strength for all copies.  Not solvable: every copy is `outputImage` itself and
     // `watermarkStrength` is left untouched
@@ -540,6 +612,21 @@ private:
         wm_plane pl{};
         pl.data = host; pl.rows = (int32_t)dims.rows; pl.cols = (int32_t)dims.cols; pl.channels = channels; pl.dtype = WM_U16; pl.mem = WM_MEM_HOST;
         pl.frames = 1; pl.pitch = dims.cols; pl.channel_stride = dims.rows * dims.cols; pl.frame_stride = 0;
+        return pl;
+    }
+    // a stack of images (wm::Image::stack) as one batched plane: every image of the first one's shape, image i at i * elements()
+    wm_plane stackPlane(const std::vector<wm::Image>& v, const char* where) const
+    {
+        if (v.empty() || v[0].isempty()) fail(WM_ERR_BAD_ARG, where);
+        wm_plane pl = v[0].plane();
+        for (size_t i = 0; i < v.size(); ++i) {
+            const wm::Image& im = v[i];
+            if (im.rows() != v[0].rows() || im.cols() != v[0].cols() || im.channels() != v[0].channels() || im.type() != v[0].type() ||
+                static_cast<const char*>(im.device_ptr()) != static_cast<const char*>(v[0].device_ptr()) + i * v[0].bytes())
+                fail(WM_ERR_BAD_ARG, where);
+        }
+        pl.frames = (int32_t)v.size();
+        pl.frame_stride = (int64_t)v[0].elements();
         return pl;
     }
     // a dense interleaved host buffer of the engine's shape as wm_packed

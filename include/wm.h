@@ -507,6 +507,64 @@ int wm_embed_bits_multi(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm
 int wm_embed_keys(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* base, const wm_keys* keys, const wm_plane* out,
                   float* a_out, int* status_out, int slot);
 
+/* ---- A key per frame of a batch: frame f is marked, or scored, with key key_of_frame[f] of a bank --------------------------------
+ * A batch is what makes the engine fast, and a batch of wm_embed / wm_detect has one watermark: the context's W.  wm_embed_keys and
+ * wm_detect_keys pair every frame with EVERY key.  These two calls pair frame f with ONE key, key_of_frame[f]: a clip whose key
+ * rotates by a secret schedule (the same additive pattern on every frame is what a frame-averaging estimate recovers), or a batch
+ * filled with frames of several customers' streams.  Everything on the image side is independent of the key -- the Gram sweep, the
+ * solve, the mask, max|e| -- and the sweeps that read W take it as one pointer, so a W per frame is a pointer per frame
+ * (wm_k_select.hip).
+ *
+ * wm_key_schedule: a schedule from a seed.  key_of_frame[i] = z(first_frame + i) mod nkeys, i < frames, where z(n) is the (n + 1)-th
+ * value of the splitmix64 of wm_bits_layout started at `seed`, formed directly from n:
+ *     state = seed + (n + 1) * 0x9E3779B97F4A7C15;  z = state;  z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *     z = (z ^ z >> 27) * 0x94D049BB133111EB;  z(n) = z ^ z >> 31                                              (all modulo 2^64)
+ * so a clip cut from the middle of a video gets its schedule from the number of its first frame alone.  WM_OK, or WM_ERR_BAD_ARG
+ * unless 1 <= nkeys <= WM_KEYS_MAX, frames >= 1 and key_of_frame is non-null.  Pure host arithmetic; it touches no device.
+ *
+ * wm_embed_select: makeWatermark (Watermark.cpp:156-172) of frame f with key key_of_frame[f] of the bank as W.  The context supplies
+ * shape, p, psnr and device; its own W is not used.  Frame f of `out` and a_out[f] equal, bit for bit, what wm_embed on the batched
+ * sweeps (wm_set_fused(0)) gives for frame f of the SAME batch on a context whose W is that key.  The Gram sweep and the solve are
+ * wm_embed's own; then one stats sweep and one embed sweep, each launched once for the whole batch.
+ *   - Takes every input wm_embed takes on the sweeps: f32 / u8, a grey or planar-RGB base, a base that is in_gray, in place (with the
+ *     snapshot), any pitch and width, WM_MEM_HOST in and out, WM_MEM_SLOT_OUT for in_gray, batches up to max_frames, ME with p = 3
+ *     (WM_ERR_BAD_P otherwise), NVF with p = 3..9.
+ *   - An unsolvable frame follows wm_embed's rule, independent of the other frames: status WM_UNSOLVABLE, out = base bit for bit,
+ *     a_out[f] untouched.  A zero-energy frame -- one whose key is an all-zero plane included -- follows wm_embed's rule too:
+ *     a = +inf, out = base.
+ *   - Like wm_embed_signs: an ENQUEUE on the slot (WM_SLOT_SYNC: slot 0, waits); `frames` results count against the slot's capacity
+ *     of 4096 un-synced results; its output becomes what WM_MEM_SLOT_OUT names; it leaves NO Gram hand-over behind, checked or
+ *     promised, and ends a hand-over whose plane it overwrites; it never takes the fused kernels and is refused in band mode.
+ *
+ * wm_detect_select: detectWatermark (Watermark.cpp:234-250) of frame f against key key_of_frame[f].  corr_out[f] equals, bit for
+ * bit, wm_detect's on the batched sweeps for frame f of the same batch on a context whose W is that key.  The image side is
+ * wm_detect_keys': every input it takes, the Gram sweep and the solve exactly as it takes them, a promised hand-over of a
+ * WM_MEM_SLOT_OUT plane (wm_set_handover) included.  Never the checked hand-over, never the fused kernels; refused in band mode.
+ * One result per frame.  A zero key scores NaN with status WM_OK; an unsolvable frame gives 0.0f and WM_UNSOLVABLE.
+ *
+ * Both calls:
+ *   - key_of_frame is a HOST array [frames], read before the call returns: the caller may change or free it at once, and several
+ *     un-synced calls on one slot each keep their own table.  The copies live in the slot's pinned host arena and device arena, like
+ *     wm_embed_signs' table, with its caveat: the FIRST call on a slot that needs more of them than are left waits for the slot's
+ *     stream and reallocates them, which waits for the whole device.  Later calls only enqueue.
+ *   - WM_ERR_BAD_ARG before any device work, looked at in wm_embed_signs' order: null pointers, mask, band mode, slot, planes, a bank
+ *     of another shape or device, an index outside 0 .. nkeys - 1 (wm_last_error names the frame); then record room (WM_ERR_BUSY).
+ *   - What a table costs: in a single-key batch the frames of a launch share one W plane -- the four waves of a block read the same
+ *     W rows, and all but the first frame's reads are cache hits.  With distinct keys every frame streams its own plane from memory
+ *     in each of the three sweeps that read W (stats, embed, detect).  Runs of equal keys in the table get the sharing back by
+ *     themselves: with an all-equal table every sweep runs at its single-key twin's speed, and the call adds the copy of the table
+ *     in front of them.  Measured at 4K, F = 16: 16 distinct keys cost 1.16 (u8 NVF) to 1.68 (u8 ME) times the single-key embed +
+ *     detect pair, f32 ME 1.36, and 0.31-0.82 of 16 queued one-frame calls on 16 contexts.
+ *   - The new kernels are not in the wm_prof_* list.
+ *
+ * HAZARD.  As for wm_detect_keys: the kernels read the bank when the stream reaches them: the bank must stay ALIVE and UNMODIFIED (no
+ * wm_keys_set / _load_file / _generate / _destroy on it) until wm_sync of this slot has returned.  The library does not check this. */
+int wm_key_schedule(int nkeys, uint64_t seed, uint64_t first_frame, int frames, int32_t* key_of_frame /* [frames] */);
+int wm_embed_select(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* base, const wm_plane* out, const wm_keys* keys,
+                    const int32_t* key_of_frame /* HOST [frames] */, float* a_out, int* status_out, int slot);
+int wm_detect_select(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* keys, const int32_t* key_of_frame /* HOST [frames] */,
+                     float* corr_out, int* status_out, int slot);
+
 /* ---- Pixel formats: RGB to grey, interleaved 8-bit pixels to planes and back ----------------------------------------------------
  * The reference's image mode converts on the device around its two calls: af::rgb2gray of the RGB input for the mask source,
  * af::rgb2gray of every watermarked RGB result for the detector, .as(u8) in front of af::saveImageNative (main.cpp:153-154,196-197,

@@ -98,6 +98,10 @@ ABI = [
                                       _P(C.c_int), C.c_int]),
     ("wm_embed_bits_multi", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), _P(wm_plane), _P(wm_plane), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                      C.c_void_p, _P(C.c_float), _P(C.c_int), C.c_int]),
+    ("wm_key_schedule", C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.c_int, _P(C.c_int32)]),
+    ("wm_embed_select", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), _P(wm_plane), _P(wm_plane), C.c_void_p, _P(C.c_int32), _P(C.c_float), _P(C.c_int),
+                                 C.c_int]),
+    ("wm_detect_select", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), C.c_void_p, _P(C.c_int32), _P(C.c_float), _P(C.c_int), C.c_int]),
     ("wm_rgb2gray", C.c_int, [_ctx_p, _P(wm_plane), _P(wm_plane), _P(C.c_float), C.c_int]),
     ("wm_unpack_rgb8", C.c_int, [_ctx_p, _P(wm_packed), _P(wm_plane), _P(wm_plane), _P(C.c_float), C.c_int]),
     ("wm_pack_rgb8", C.c_int, [_ctx_p, _P(wm_plane), _P(wm_packed), C.c_int]),
@@ -684,6 +688,34 @@ class Watermark:
                                       a.ctypes.data_as(_P(C.c_float)), None, WM_SLOT_SYNC))
         return out, (a if batched else a[0])
 
+    @staticmethod
+    def key_schedule(nkeys, seed, first_frame, frames):
+        """which key does frame n of a video take?  wm_key_schedule's table for frames first_frame .. first_frame + frames - 1: an
+        int32 numpy array [frames] with entries 0 .. nkeys - 1, entry i a function of (seed, first_frame + i) alone"""
+        kt = np.empty(max(frames, 0), np.int32)
+        rc = lib().wm_key_schedule(nkeys, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_frame) & 0xFFFFFFFFFFFFFFFF, frames,
+                                   kt.ctypes.data_as(_P(C.c_int32)))
+        if rc != WM_OK:
+            _raise(rc)
+        return kt
+
+    def makeWatermarkSelect(self, inputImage, outputImage, keys, key_of_frame, maskType, out=None):
+        """makeWatermark of frame f with key key_of_frame[f] of the KeySet `keys` as W (wm.h wm_embed_select): key_of_frame is an
+        integer array [F] (one entry, or an int, for one grey frame).  Returns (watermarked, strength) as makeWatermark does; the
+        context's own W is not used; never takes the fused kernels"""
+        return self._embed_tiles(lambda i, b, o, m, slot, a, st: self.embed_select_async(i, b, o, keys, key_of_frame, m, slot, a, st),
+                                 inputImage, outputImage, maskType, out)
+
+    def detectSelect(self, image, keys, key_of_frame, maskType):
+        """detectWatermark of frame f against key key_of_frame[f] of the KeySet `keys` (wm.h wm_detect_select): the score of one
+        grey frame, a list of scores for a batch; 0.0 for an unsolvable frame"""
+        import torch
+        frames = plane_of(image, 1).frames
+        corr = (C.c_float * frames)()
+        torch.cuda.current_stream().synchronize()
+        self.detect_select_async(image, keys, key_of_frame, maskType, WM_SLOT_SYNC, corr)
+        return corr[0] if image.dim() == 2 else list(corr)
+
     def _embed_multi(self, how, inputImage, outputImage, K, maskType, out):
         """the synchronous front of the *_multi embeds: K copies per frame shaped as makeWatermarkKeys returns them, one strength per
         frame (NaN for an unsolvable frame, whose copies equal outputImage)"""
@@ -890,6 +922,35 @@ class Watermark:
         a_out, status_out = self._scalars_out(a_out, status_out)
         self._chk(lib().wm_embed_keys(self._ctx, int(maskType), C.byref(pin), C.byref(pbase), _keys_handle(keys),
                                       C.byref(pout), a_out, status_out, slot))
+
+    def _key_table(self, key_of_frame, frames):
+        """the table of a select call as a pointer (None: a null pointer, which the library refuses)"""
+        if key_of_frame is None:
+            return None, None
+        raw = np.atleast_1d(np.asarray(key_of_frame))
+        if raw.size and (raw.min() < -2 ** 31 or raw.max() > 2 ** 31 - 1):  # (values the int32 table cannot hold)
+            _raise(WM_ERR_BAD_ARG)
+        kt = self._host_table(raw, np.int32, frames, "key_of_frame")
+        return kt, kt.ctypes.data_as(_P(C.c_int32))
+
+    def embed_select_async(self, inputImage, outputImage, out, keys, key_of_frame, maskType, slot, a_out=None, status_out=None):
+        """wm_embed_select enqueued on `slot`: key_of_frame (frames integers in 0 .. K - 1) is copied before the call returns; a_out
+        (frames floats) and status_out (frames ints) -- ctypes arrays or C-contiguous numpy arrays, may be None -- are written by
+        sync(slot); `keys` must stay alive and unmodified until then"""
+        pin, pbase, pout = self._embed_planes(inputImage, outputImage, out)
+        kt, pk = self._key_table(key_of_frame, pin.frames)
+        a_out, status_out = self._scalars_out(a_out, status_out)
+        self._chk(lib().wm_embed_select(self._ctx, int(maskType), C.byref(pin), C.byref(pbase), C.byref(pout), _keys_handle(keys), pk,
+                                        a_out, status_out, slot))
+
+    def detect_select_async(self, image, keys, key_of_frame, maskType, slot, corr_out, status_out=None):
+        """wm_detect_select enqueued on `slot`: key_of_frame (frames integers in 0 .. K - 1) is copied before the call returns;
+        corr_out (frames floats) and status_out (frames ints, may be None) are written by sync(slot); `keys` must stay alive and
+        unmodified until then"""
+        pimg = self._as_plane(image, 1)
+        kt, pk = self._key_table(key_of_frame, pimg.frames)
+        corr_out, status_out = self._scalars_out(corr_out, status_out)
+        self._chk(lib().wm_detect_select(self._ctx, int(maskType), C.byref(pimg), _keys_handle(keys), pk, corr_out, status_out, slot))
 
     @staticmethod
     def _host_table(a, dtype, n, what):

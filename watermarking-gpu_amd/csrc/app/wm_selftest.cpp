@@ -159,6 +159,45 @@ int main(int argc, char** argv)
               "makeWatermark16 in place, detectWatermark16: the marked samples correlate, the source does not");
     }
 
+    // ---- a key per frame: 3 generated keys, 4 frames with a schedule, embed, detect on the slot's output with the right schedule and
+    // with the schedule rotated by one key
+    {
+        const int K = 3, F = 4;
+        WatermarkKeys keys(R, C, K);
+        for (int k = 0; k < K; ++k) keys.generate(k, 700u + (uint32_t)k);
+        Watermark sel(R, C, w1, 3, 40.0f);  // (its own W is not used)
+        sel.configure(2, F);
+        const std::vector<int32_t> sched = Watermark::keySchedule(K, 2024, 100, F);
+        std::vector<int32_t> rotated(sched);
+        for (auto& k : rotated) k = (k + 1) % K;
+        std::vector<wm::Image> frames = wm::Image::stack(F, R, C, 1);
+        for (int f = 0; f < F; ++f) {
+            const std::vector<float> xf = make_frame(R, C, 40u + (uint32_t)f);
+            if (wm_memcpy_h2d(frames[(size_t)f].device_ptr(), xf.data(), xf.size() * sizeof(float)) != WM_OK) ++failures;
+        }
+        std::vector<float> a_sel;
+        const std::vector<wm::Image> marked = sel.makeWatermarkSelect(frames, frames, keys, sched, a_sel, ME);
+        // the detector reads the device copy of what the embed wrote (WM_MEM_SLOT_OUT), enqueued on slot 0
+        wm_plane slot_out = marked[0].plane();
+        slot_out.data = nullptr; slot_out.mem = WM_MEM_SLOT_OUT; slot_out.frames = F; slot_out.frame_stride = (int64_t)marked[0].elements();
+        std::vector<float> right((size_t)F, 0.0f), wrong((size_t)F, 0.0f);
+        sel.detectWatermarkSelectAsync(slot_out, keys, sched.data(), right.data(), nullptr, ME, 0);
+        sel.detectWatermarkSelectAsync(slot_out, keys, rotated.data(), wrong.data(), nullptr, ME, 0);
+        sel.sync(0);
+        const std::vector<float> again = sel.detectWatermarkSelect(marked, keys, sched, ME);
+        bool sched_ok = (int)sched.size() == F, split = true, strengths = (int)a_sel.size() == F;
+        for (int f = 0; f < F; ++f) {
+            sched_ok = sched_ok && sched[(size_t)f] >= 0 && sched[(size_t)f] < K && Watermark::keySchedule(K, 2024, 100 + (uint64_t)f, 1)[0] == sched[(size_t)f];
+            strengths = strengths && a_sel[(size_t)f] > 0.0f;
+            split = split && right[(size_t)f] > 0.2f && std::fabs(wrong[(size_t)f]) < 0.05f && again[(size_t)f] == right[(size_t)f];
+            std::printf("      frame %d key %d: a = %.4f, score %.4f, with key %d %.4f\n", f, (int)sched[(size_t)f], a_sel[(size_t)f], right[(size_t)f],
+                        (int)rotated[(size_t)f], wrong[(size_t)f]);
+        }
+        CHECK(sched_ok, "keySchedule: entries in range, a clip's schedule follows from its first frame");
+        CHECK(strengths, "makeWatermarkSelect: one strength per frame");
+        CHECK(split, "detectWatermarkSelect: the right schedule correlates, the rotated one does not; slot output and stack agree");
+    }
+
     // ---- deep copy that shares W (Watermark.cpp:30-51): same results, independent lifetime
     float a_copy = 0.0f, a_assign = 0.0f;
     {

@@ -2069,6 +2069,113 @@ int wm_embed_keys(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane
     return finish_call(ctx, s, slot, frames, nkeys, true, a_out, status_out);  // (wm_embed's rule: an unsolvable frame leaves its K strengths untouched)
 }
 
+// ---- a key per frame of a batch: wm_key_schedule, wm_embed_select, wm_detect_select ------------------------------------------------
+// key_of_frame[i] = z(first_frame + i) mod nkeys, z(n) the (n + 1)-th value of wm_bits_layout's splitmix64 started at `seed`, formed
+// directly from n (pure host arithmetic)
+int wm_key_schedule(int nkeys, uint64_t seed, uint64_t first_frame, int frames, int32_t* key_of_frame)
+{
+    if (!key_of_frame || nkeys < 1 || nkeys > WM_KEYS_MAX || frames < 1) return WM_ERR_BAD_ARG;
+    for (int i = 0; i < frames; ++i) {
+        uint64_t z = seed + (first_frame + (uint64_t)i + 1) * 0x9E3779B97F4A7C15ULL;
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+        z ^= z >> 31;
+        key_of_frame[i] = (int32_t)(z % (uint64_t)nkeys);
+    }
+    return WM_OK;
+}
+
+// every entry of a call's key table names a key of the bank
+static int key_table_checked(wm_ctx* ctx, const char* who, const wm_keys* keys, const int32_t* key_of_frame, int frames)
+{
+    for (int f = 0; f < frames; ++f)
+        if (key_of_frame[f] < 0 || key_of_frame[f] >= keys->nkeys)
+            return fail(ctx, WM_ERR_BAD_ARG, std::string(who) + ": key_of_frame[" + std::to_string(f) + "] = " + std::to_string(key_of_frame[f]) + " for frame " +
+                                                 std::to_string(f) + " (the bank has keys 0 .. " + std::to_string(keys->nkeys - 1) + ")");
+    return WM_OK;
+}
+// the call's own copy of the table, kept like wm_embed_signs': the caller's array is free when the call returns
+static int key_table_upload(wm_ctx* ctx, Slot& s, const int32_t* key_of_frame, int frames, const int** kidx)
+{
+    void *th = nullptr, *td = nullptr;
+    const size_t bytes = (size_t)frames * sizeof(int32_t);
+    int rc;
+    if ((rc = table_room(ctx, s, bytes, &th, &td)) != WM_OK) return rc;
+    std::memcpy(th, key_of_frame, bytes);
+    if ((rc = table_upload(ctx, s, th, td, bytes)) != WM_OK) return rc;
+    *kidx = (const int*)td;
+    return WM_OK;
+}
+
+// makeWatermark of frame f with key key_of_frame[f] of the bank as W: wm_embed's input, base and output handling and its Gram sweep and
+// solve on the sweeps; then the stats and embed sweeps with W resolved per frame (k_me_stats_sel / k_nvf_stats_sel, k_embed_sel), each
+// launched once for the batch.  Never the fused kernels, no Gram hand-over.  The *_sel kernels are launched outside any ProfScope: the
+// list of profiling names is not extended for them
+int wm_embed_select(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_plane* base, const wm_plane* out, const wm_keys* keys,
+                    const int32_t* key_of_frame, float* a_out, int* status_out, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    if (!in_gray || !base || !out || !keys || !key_of_frame) return fail(ctx, WM_ERR_BAD_ARG, "wm_embed_select: null in_gray, base, out, keys or key_of_frame");
+    int rc;
+    if ((rc = check_mask(ctx, mask)) != WM_OK) return rc;
+    if ((rc = refuse_band(ctx, "wm_embed_select")) != WM_OK) return rc;
+    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
+    if ((rc = check_embed_planes(ctx, in_gray, base, out)) != WM_OK) return rc;
+    const int frames = in_gray->frames;
+    if ((rc = check_bank(ctx, keys, "wm_embed_select", true)) != WM_OK) return rc;
+    if ((rc = key_table_checked(ctx, "wm_embed_select", keys, key_of_frame, frames)) != WM_OK) return rc;
+    if ((rc = check_res_room(ctx, s, frames)) != WM_OK) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+
+    const int* kidx = nullptr;
+    if ((rc = key_table_upload(ctx, s, key_of_frame, frames, &kidx)) != WM_OK) return rc;
+    EmbedCall c;  // (no hand-over of its own)
+    if ((rc = embed_stage(ctx, s, in_gray, base, out, &c)) != WM_OK) return rc;
+    if ((rc = embed_snapshot(ctx, s, in_gray, &c)) != WM_OK) return rc;
+    LaunchGeom lg;
+    if ((rc = geom_checked(ctx, frames, mask, &lg)) != WM_OK) return rc;
+    const Sweep sw = mask_route(ctx, s, lg, frames, mask, c.xd);
+    const KeyBank bank = bank_of(ctx, keys);
+    OpResult* res = s.d_res + s.res_used;
+    // the image side is wm_embed's: the Gram sweep and solve (ME); the scratch arrays are sweep_stats'
+    if (mask == WM_MASK_ME) sweep_gram(ctx, s, K_GRAM, sw);
+    unsigned* ticket = s.d_ticket + ctx->max_frames * TKS;
+    if (mask == WM_MASK_ME)
+        launch_me_stats_sel(sw, bank, kidx, s.d_pmax, s.d_pss, ticket, strip_tickets(ctx, s, 0), s.d_smax, s.d_sss, ctx->sF, sqrt_n(ctx), s.d_scal, res, s.d_raw);
+    else
+        launch_nvf_stats_sel(sw, bank, kidx, s.d_pss, ticket, strip_tickets(ctx, s, 0), s.d_sss, ctx->sF, sqrt_n(ctx), s.d_scal, res, s.d_raw);
+    launch_embed_sel(sw, bank, EmbedPlanes{c.bd, c.od, s.d_scal}, kidx);
+    return embed_close(ctx, s, out, c, a_out, status_out, slot);
+}
+
+// detectWatermark of frame f against key key_of_frame[f]: detect_bank's image side (wm_detect's input handling on the sweeps, the Gram
+// sweep -- a promised hand-over of a WM_MEM_SLOT_OUT plane included, never the checked one -- and the solve), then k_detect_sel on
+// sweep_detect's scratch arrays, one record per frame
+int wm_detect_select(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* keys, const int32_t* key_of_frame, float* corr_out,
+                     int* status_out, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    if (!img || !keys || !key_of_frame || !corr_out) return fail(ctx, WM_ERR_BAD_ARG, "wm_detect_select: null img, keys, key_of_frame or corr_out");
+    int rc;
+    if ((rc = check_mask(ctx, mask)) != WM_OK) return rc;
+    if ((rc = refuse_band(ctx, "wm_detect_select")) != WM_OK) return rc;
+    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
+    if ((rc = check_plane(ctx, img, 0, false, "image", true)) != WM_OK) return rc;
+    const int frames = img->frames;
+    if ((rc = check_bank(ctx, keys, "wm_detect_select", true)) != WM_OK) return rc;
+    if ((rc = key_table_checked(ctx, "wm_detect_select", keys, key_of_frame, frames)) != WM_OK) return rc;
+    Sweep sw;
+    if ((rc = open_input(ctx, s, img, "image", mask, 1, nullptr, &sw)) != WM_OK) return rc;  // (record room, device, the plane resolved)
+    const int* kidx = nullptr;
+    if ((rc = key_table_upload(ctx, s, key_of_frame, frames, &kidx)) != WM_OK) return rc;
+    if ((rc = gram_sweep(ctx, s, sw, img)) != WM_OK) return rc;
+    launch_detect_sel(sw, bank_of(ctx, keys), kidx, s.d_pcorr, s.d_ticket + 2 * ctx->max_frames * TKS, strip_tickets(ctx, s, 1), s.d_scorr,
+                      s.d_res + s.res_used, s.d_raw + ctx->max_frames);
+    return finish_call(ctx, s, slot, frames, 1, false, corr_out, status_out);
+}
+
 int wm_embed_signs_group(void) { return embed_signs_group(); }
 
 // wm_embed_signs of every frame once per table of signs [frames][ncopies][ny][nx]: wm_embed_signs' table handling, Gram, solve and

@@ -1,5 +1,6 @@
 // wm_detect_march.hpp -- detect_march, the detector's march over one wave's segment: shared by k_detect (wm_k_detect.hip) and
-// k_detect_tiles (wm_k_detect_tiles.hip), which differ only in what becomes of the three sums
+// k_detect_tiles (wm_k_detect_tiles.hip), which differ only in what becomes of the three sums; and detect_body with its fold
+// tails (corr_fold, corr_finalize_frame), k_detect's kernel body, which k_detect_sel (wm_k_select.hip) runs with a W per frame
 #pragma once
 #include "wm_march.hpp"
 
@@ -226,5 +227,182 @@ __device__ __forceinline__ void detect_march(const T* __restrict__ xf, long long
         if constexpr (DIG) dig = mine ? dig : 0ull;
     }
 }
+
+// ---- detect_body, the body of k_detect / k_detect_redo (wm_k_detect.hip) and of k_detect_sel (wm_k_select.hip, with the frame's own
+// key plane as W), and its fold tails
+// corr_fold (tail of k_detect; take_ticket, wm_device.hpp): the last wave of a strip folds the strip's records, the last
+// strip's wave folds the frame:
+// corr = (float)dot / (float)(||e_w|| * ||e_u||)   (Watermark.cpp:230); unsolvable => 0.0f (:246-247)
+// publish a frame's score -- or, in the checking instance (CK = 1), only when the digest of the plane this sweep read equals the
+// one the embed left (DigCheck); else flag the frame for the redo launches
+template <int CK>
+__device__ __forceinline__ void corr_publish(int frame, double a0, double a1, double a2, unsigned long long dg,
+                                             const int* __restrict__ status, OpResult* res, RawSums* raw, const DigCheck& dc)
+{
+    if constexpr (CK == 1) {
+        const bool ok = dg == dc.want[frame];
+        dc.redo[frame] = ok ? 0 : 1;
+        atomicAdd(dc.count + (ok ? 0 : 1), 1ull);
+        if (!ok) return;
+    }
+    const int st = status[frame];
+    float corr = 0.0f;
+    if (st == 0) corr = (float)a0 / (float)(sqrt(a2) * sqrt(a1));
+    res[frame].status = st;
+    res[frame].value = corr;
+    RawSums rw;
+    rw.v[0] = a0; rw.v[1] = a1; rw.v[2] = a2; rw.v[3] = 0.0;
+    raw[frame] = rw;
+}
+
+template <int CK>
+__device__ __forceinline__ void corr_fold(int frame, const WaveJob& j, const double* pcorr, int nrec,
+                                          const int* __restrict__ status, const CorrTail& tl, const DigCheck& dc)
+{
+    const int lane = j.lane;
+    if (!take_ticket(tl.ticket_strip + (frame * tl.nstrips + j.strip) * TKS, (unsigned)tl.nsegs, lane)) return;
+    unsigned long long dg = 0;
+    if constexpr (CK == 1) {
+        for (int s0 = lane; s0 < tl.nsegs; s0 += WAVE) dg += ld_agent(dc.pdig + (long long)frame * nrec + (long long)s0 * tl.nstrips + j.strip);
+        dg = wave_sum_u64(dg);
+        if (lane == 0) st_agent(dc.sdig + (long long)frame * tl.nstrips + j.strip, dg);
+    }
+    // all loads of a batch are issued before the first is used (index clamped, surplus terms dropped): agent-scope loads
+    // come from the memory side, a dependent chain of them costs a memory latency per term
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    for (int s0 = lane; s0 < tl.nsegs; s0 += 2 * WAVE) {
+        double v[2][3];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const double* p = pcorr + ((long long)frame * nrec + (long long)min(s0 + u * WAVE, tl.nsegs - 1) * tl.nstrips + j.strip) * 3;
+            v[u][0] = ld_agent(p); v[u][1] = ld_agent(p + 1); v[u][2] = ld_agent(p + 2);
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const bool in = s0 + u * WAVE < tl.nsegs;
+            a0 += in ? v[u][0] : 0.0; a1 += in ? v[u][1] : 0.0; a2 += in ? v[u][2] : 0.0;
+        }
+    }
+    a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2);
+    if (lane == 0) {
+        double* q = tl.scorr + ((long long)frame * tl.nstrips + j.strip) * 3;
+        st_agent(q, a0); st_agent(q + 1, a1); st_agent(q + 2, a2);
+    }
+    if (!take_ticket(tl.ticket + frame * TKS, (unsigned)tl.nstrips, lane)) return;
+    a0 = 0.0; a1 = 0.0; a2 = 0.0;
+    dg = 0;
+    for (int s0 = lane; s0 < tl.nstrips; s0 += WAVE) {
+        const double* q = tl.scorr + ((long long)frame * tl.nstrips + s0) * 3;
+        const double v0 = ld_agent(q), v1 = ld_agent(q + 1), v2 = ld_agent(q + 2);
+        a0 += v0; a1 += v1; a2 += v2;
+        if constexpr (CK == 1) dg += ld_agent(dc.sdig + (long long)frame * tl.nstrips + s0);
+    }
+    a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2);
+    if constexpr (CK == 1) dg = wave_sum_u64(dg);
+    if (lane == 0) corr_publish<CK>(frame, a0, a1, a2, dg, status, tl.res, tl.raw, dc);
+}
+
+// corr_finalize_frame (tail of k_detect, run by the frame's last block):
+// corr = (float)dot / (float)(||e_w|| * ||e_u||)   (Watermark.cpp:230); unsolvable => 0.0f (:246-247)
+template <int CK>
+__device__ __forceinline__ void corr_finalize_frame(int frame, const double* pcorr, int nblk, const int* __restrict__ status,
+                                                    OpResult* __restrict__ res, RawSums* __restrict__ raw, const DigCheck& dc)
+{
+    __shared__ double s[3][BLOCK];
+    const int t = threadIdx.x;
+    unsigned long long dg = 0;
+    if constexpr (CK == 1) {
+        if (t < WAVE) {
+            for (int b = t; b < nblk; b += WAVE) dg += ld_agent(dc.pdig + (long long)frame * nblk + b);
+            dg = wave_sum_u64(dg);
+        }
+    }
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    // 2 x 3 partials in flight per thread (index clamped, surplus terms dropped), see solve_frame
+    for (int b0 = t; b0 < nblk; b0 += 2 * BLOCK) {
+        double v[2][3];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const double* p = pcorr + ((long long)frame * nblk + min(b0 + u * BLOCK, nblk - 1)) * 3;
+            v[u][0] = ld_agent(p); v[u][1] = ld_agent(p + 1); v[u][2] = ld_agent(p + 2);
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const bool in = b0 + u * BLOCK < nblk;
+            a0 += in ? v[u][0] : 0.0; a1 += in ? v[u][1] : 0.0; a2 += in ? v[u][2] : 0.0;
+        }
+    }
+    s[0][t] = a0; s[1][t] = a1; s[2][t] = a2;
+    __syncthreads();
+    for (int o = BLOCK / 2; o > 0; o >>= 1) {
+        if (t < o) { s[0][t] += s[0][t + o]; s[1][t] += s[1][t + o]; s[2][t] += s[2][t + o]; }
+        __syncthreads();
+    }
+    if (t == 0) corr_publish<CK>(frame, s[0][0], s[1][0], s[2][0], dg, status, res, raw, dc);
+}
+
+// CK: 0 = the ordinary sweep; 1 = the checking instance of a checked hand-over (DigCheck, wm_kernels.hpp: every frame's march
+// runs -- an unsolvable one too, its sums dropped -- for the digest); 2 = k_detect_redo (frames with dc.redo[f] == 0 leave first)
+template <typename T, int MASK, int PAD, int HC, bool VEC, int CK>
+__device__ __forceinline__ void detect_body(const T* __restrict__ x, long long pitch, long long fstride, const float* __restrict__ W,
+                                            const Geom& g, const float* __restrict__ coef, const int* __restrict__ status,
+                                            double* pcorr, const CorrTail& tail, const DigCheck& dc)
+{
+    __shared__ __attribute__((aligned(16))) float s_row[WPB][2 * RowBuf<HC>::N];
+    __shared__ __attribute__((aligned(16))) float s_u[WPB][2 * RowBuf<1>::N];
+    __shared__ double s_red[WPB][3];
+    __shared__ unsigned long long s_dig[WPB];
+    const WaveJob j = make_job(g);
+    const int frame = j.frame;
+    if constexpr (CK == 2) {
+        // quad: the waves of a block are different frames (surplus waves of a short last quad have none) -- a wave-uniform exit, no
+        // barrier on that path; else the block is one frame (its waves past the last segment still take part in the barrier)
+        if (g.quad ? (!j.valid || dc.redo[frame] == 0) : dc.redo[frame] == 0) return;
+    }
+    float dot = 0.0f, nu = 0.0f, nw = 0.0f;
+    unsigned long long dig = 0;
+    const int st = j.valid ? status[frame] : 1;
+    if (j.valid && (CK == 1 || st == 0)) {
+        float c[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) c[k] = coef[frame * 8 + k];
+        const T* xf = x + (long long)frame * fstride;
+        constexpr bool DPP_OK = HC == 1;  // the halo of p = 9 (HC = 2) exceeds one neighbour chunk: LDS path only
+        constexpr bool V = VEC && DPP_OK;
+        constexpr bool D = CK == 1;
+        if (MASK != 0 || strip_on_edge<V>(g, j)) detect_march<T, MASK, PAD, HC, V, true, D>(xf, pitch, W, g, j, s_row[j.wave], s_u[j.wave], c, dot, nu, nw, dig);
+        else detect_march<T, MASK, PAD, HC, V, (MASK != 0), D>(xf, pitch, W, g, j, s_row[j.wave], s_u[j.wave], c, dot, nu, nw, dig);
+        if (CK == 1 && st != 0) { dot = 0.0f; nu = 0.0f; nw = 0.0f; }  // (what the ordinary sweep sums for an unsolvable frame)
+    }
+    const double d0 = wave_sum((double)dot), d1 = wave_sum((double)nu), d2 = wave_sum((double)nw);
+    if constexpr (CK == 1) dig = wave_sum_u64(dig);
+    if (g.quad) {
+        // the waves of this block are 4 frames: one record per wave, folded per strip and then per frame (corr_fold)
+        if (!j.valid) return;  // surplus wave of a short last quad (wave-uniform; no barrier below)
+        if (j.lane == 0) {
+            double* p = pcorr + ((long long)frame * g.nrec + j.rec) * 3;
+            st_agent(p, d0); st_agent(p + 1, d1); st_agent(p + 2, d2);
+            if constexpr (CK == 1) st_agent(dc.pdig + (long long)frame * g.nrec + j.rec, dig);
+        }
+        corr_fold<CK>(frame, j, pcorr, g.nrec, status, tail, dc);
+        return;
+    }
+    // the waves of this block are 4 segments of one frame: one record per block, folded by the frame's last block
+    if (j.lane == 0) { s_red[j.wave][0] = d0; s_red[j.wave][1] = d1; s_red[j.wave][2] = d2; s_dig[j.wave] = dig; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int k = threadIdx.x;
+        st_agent(pcorr + ((long long)frame * g.nblk_total + g.pb0 + j.tile) * 3 + k, ((s_red[0][k] + s_red[1][k]) + s_red[2][k]) + s_red[3][k]);
+    }
+    if (CK == 1 && threadIdx.x == 3)
+        st_agent(dc.pdig + (long long)frame * g.nblk_total + g.pb0 + j.tile, s_dig[0] + s_dig[1] + s_dig[2] + s_dig[3]);
+    if (last_block_of_frame(tail.ticket + frame * TKS, (unsigned)tail.expected))
+        corr_finalize_frame<CK>(frame, pcorr, g.nblk_total, status, tail.res, tail.raw, dc);
+}
+
+// occupancy floor: 4 waves per SIMD for the aligned 3x3 instances (105 / 106 / 91 VGPRs); the generic instances (LDS re-lay,
+// halo predictions of their own) need ~150 registers -- bound to 4 they spilled 48-70 VGPRs to scratch, at 3 they do not
+// (expands inside a kernel template with k_detect's parameters PAD, HC, VEC; the file that uses it #undefs it behind its kernels)
+#define WM_DET_BOUNDS (PAD == 1 && HC == 1 ? (VEC ? WM_DET_WAVES : 3) : 1)
 
 }  // namespace wmk

@@ -304,6 +304,18 @@ void launch_bits_fold(hipStream_t s, int frames, int nbits, int ntiles, const do
 bool embed_signs_multi_grid_fits(const LaunchGeom& lg, int frames, int ncopies);
 void launch_embed_signs_multi(const Sweep& sw, const KeyBank& w, const EmbedPlanes& ep, const signed char* signs, int ncopies, const TileShape& ts);
 int embed_signs_group(void);  // copies per group of k_embed_signs_multi (compile-time SMG)
+// a key per frame of a batch (wm_embed_select / wm_detect_select, wm_k_select.hip): the single-key sweeps above -- their bodies, launch
+// plans and scratch arrays -- with W resolved per frame, W_f = bank.W + kidx[frame] * bank.kstride.  kidx [frames] on the device, every
+// entry in 0 .. bank.nkeys - 1 (checked by the caller); bank.aligned_w: every plane of the bank may be addressed with 32-bit offsets.
+// launch_embed_sel never hands over; launch_detect_sel is launch_detect's ordinary sweep (mode 0)
+void launch_me_stats_sel(const Sweep& sw, const KeyBank& bank, const int* kidx, float* pmax, double* pss, unsigned* ticket,
+                         unsigned* ticket_strip, float* smax, double* sss, float sF, double sqrt_n, EmbedScalars* scal, OpResult* res,
+                         RawSums* raw);
+void launch_nvf_stats_sel(const Sweep& sw, const KeyBank& bank, const int* kidx, double* pss, unsigned* ticket, unsigned* ticket_strip,
+                          double* sss, float sF, double sqrt_n, EmbedScalars* scal, OpResult* res, RawSums* raw);
+void launch_embed_sel(const Sweep& sw, const KeyBank& bank, const EmbedPlanes& ep, const int* kidx);
+void launch_detect_sel(const Sweep& sw, const KeyBank& bank, const int* kidx, double* pcorr, unsigned* ticket, unsigned* ticket_strip,
+                       double* scorr, OpResult* res, RawSums* raw);
 // the pixel-format front (wm_rgb2gray / wm_unpack_rgb8 / wm_pack_rgb8, wm_k_convert.hip): element-wise kernels, a lane per four
 // consecutive pixels of a row, grid (column chunks, rows, frames) -- convert_grid_fits: rows and frames fit the grid's y and z.
 // PackedDesc: interleaved 8-bit R, G, B (wm_packed) in BYTES; aligned: base, pitch and frame stride are multiples of 4, so a
