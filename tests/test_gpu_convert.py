@@ -268,8 +268,42 @@ def test_unpack_rgb8_host_input(wm, tc, shape, F, pitch):
         assert_bits(g2.cpu().numpy(), gray[0], "Watermark.unpackRgb8: grey")
 
 
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_unpack_rgb8_host_outputs(wm, tc, dtype):
+    """WM_MEM_HOST outputs, F = 2 at (7, 67) -- the staged pitch is 68, so the staged frame and channel strides differ from the
+    planes' own: both outputs on the host (staged side by side), then each with the other on the device.  rgb_out in the odd layout,
+    gray_out in the pitched one: the pixels in place, the padding of host and device buffers untouched"""
+    shape, F = (7, 67), 2
+    R, Cc = shape
+    eng = engine(wm, shape, F)
+    px = packed_pixels(shape, F)
+    planar = np.ascontiguousarray(px.transpose(0, 3, 1, 2)).astype(npdt(dtype))
+    gray = gray_oracle(planar, (shape, F, "u8"))
+    pbuf = tc.from_numpy(packed_expect(px, "padded")).cuda()
+    pk = packed_desc(wm, pbuf.data_ptr(), "padded", R, Cc, F, wm.WM_MEM_DEVICE)
+    lay_rgb, lay_g = LY.make("odd", R, Cc, 3, F), LY.make("pitched", R, Cc, 1, F)
+    want_rgb, want_g = LY.expect(planar, lay_rgb, poison_of(dtype), 3), LY.expect(gray, lay_g, poison_of("f32"), 1)
+    for host_rgb, host_gray in ((True, True), (True, False), (False, True)):
+        hr = np.full(lay_rgb.length, poison_of(dtype), npdt(dtype))
+        hg = np.full(lay_g.length, poison_of("f32"), np.float32)
+        rbuf, rgb_dev = out_buffer(tc, lay_rgb, planar.shape, dtype, 3)
+        gbuf, gray_dev = out_buffer(tc, lay_g, gray.shape, "f32", 1)
+        tc.cuda.synchronize()
+        eng.unpack_rgb8_async(pk, host_plane(wm, hr, lay_rgb, R, Cc, 3, dtype, F) if host_rgb else rgb_dev,
+                              host_plane(wm, hg, lay_g, R, Cc, 1, "f32", F) if host_gray else gray_dev, 1)
+        eng.sync(1)
+        what = f"unpack host outputs {dtype} rgb_out={'host' if host_rgb else 'device'} gray_out={'host' if host_gray else 'device'}"
+        got_rgb, idle_rgb = (hr, rbuf.cpu().numpy()) if host_rgb else (rbuf.cpu().numpy(), hr)
+        got_g, idle_g = (hg, gbuf.cpu().numpy()) if host_gray else (gbuf.cpu().numpy(), hg)
+        assert_bits(got_rgb, want_rgb, what + ": planes")
+        assert_bits(got_g, want_g, what + ": grey")
+        assert (LY.raw(idle_rgb) == LY.raw(np.full(1, poison_of(dtype)))[0]).all(), what + ": the rgb buffer the call was not given"
+        assert (LY.raw(idle_g) == LY.raw(np.full(1, poison_of("f32")))[0]).all(), what + ": the grey buffer the call was not given"
+    assert_bits(pbuf.cpu().numpy(), packed_expect(px, "padded"), "the source is left as it was")
+
+
 # ---- wm_pack_rgb8 --------------------------------------------------------------------------------------------------------------------
-SPECIALS = np.array([0.0, 255.0, 254.999, 255.5, -0.5, -3.0, 1e9, np.nan], np.float32)
+SPECIALS =np.array([0.0, 255.0, 254.999, 255.5, -0.5, -3.0, 1e9, np.nan], np.float32)
 
 
 def pack_input(shape, F, dtype):
@@ -324,6 +358,28 @@ def test_pack_rgb8_host_planes(wm, tc, shape):
     cpu = tc.full((F, R, Cc, 3), 7, dtype=tc.uint8)
     eng.packRgb8(tc.from_numpy(x).cuda(), out=cpu)
     assert_bits(cpu.numpy(), want_px, "Watermark.packRgb8 into a CPU tensor")
+
+
+def test_pack_rgb8_host_output_from_slot_out(wm, tc):
+    """WM_MEM_SLOT_OUT in, a host packed buffer (padded pitch) out: the bytes are the clipped, truncated pixels of the output the
+    embed delivered, the padding keeps its 0xA5"""
+    shape = (33, 258)
+    R, Cc = shape
+    eng = wm.Watermark(R, Cc, synth_watermark(R, Cc), 3, 40.0, nslots=2, max_frames=1)  # (its slot 1 is left naming `out`)
+    rgb = rgb_frames(shape, 1, "f32")[0]
+    gray_dev, rgb_dev = tc.from_numpy(np.array(gray_oracle(rgb, (shape, 1, "f32")))).cuda(), tc.from_numpy(np.array(rgb)).cuda()
+    out = tc.empty((3, R, Cc), dtype=tc.float32, device="cuda")
+    hout = np.full(packed_strides("padded", R, Cc, 1)[3], POISON8, np.uint8)
+    a, st = (C.c_float * 1)(), (C.c_int * 1)()
+    tc.cuda.synchronize()
+    eng.embed_async(gray_dev, rgb_dev, out, wm.MASK_TYPE.NVF, 1, a, st)
+    eng.pack_rgb8_async(slot_out_plane(wm, shape, wm.WM_F32), packed_desc(wm, hout.ctypes.data, "padded", R, Cc, 1, wm.WM_MEM_HOST), 1)
+    eng.sync(1)
+    y = out.cpu().numpy()
+    assert st[0] == 0 and (y != rgb).any()
+    want = np.clip(np.where(np.isnan(y), np.float32(0), y), 0, 255).astype(np.uint8)
+    assert_bits(hout, packed_expect(np.ascontiguousarray(want.transpose(1, 2, 0))[None], "padded"), "pack of SLOT_OUT into a host buffer")
+    eng.close()
 
 
 # ---- the image protocol on the device ------------------------------------------------------------------------------------------------
@@ -437,9 +493,9 @@ def test_error_precedence(wm, tc):
     ctx = eng._ctx
     byref = C.byref
 
-    def refused(rc, text):
+    def refused(rc, text, at=None):
         assert rc == wm.WM_ERR_BAD_ARG, (rc, text)
-        msg = L.wm_last_error(ctx).decode()
+        msg = L.wm_last_error(ctx if at is None else at).decode()
         assert text in msg, (text, msg)
 
     rgb_t = tc.zeros((3, R, Cc), dtype=tc.float32, device="cuda")
@@ -514,5 +570,54 @@ def test_error_precedence(wm, tc):
     refused(L.wm_pack_rgb8(ctx, byref(slot_out), byref(pk), BAD_SLOT), "bad slot")
     refused(L.wm_pack_rgb8(ctx, byref(slot_out), byref(pk), 1), "WM_MEM_SLOT_OUT: no matching 3-channel embed output")
 
+    # the refusals no case above reaches.  One operand's own rules: check_plane's through rgb, check_packed's, the remaining shapes
+    u8 = dict(dtype=wm.WM_U8)
+    refused(L.wm_rgb2gray(ctx, byref(plane(rgb, dtype=7)), byref(plane(gray, **u8)), None, 0), "rgb: bad dtype")
+    refused(L.wm_rgb2gray(ctx, byref(plane(rgb, mem=9)), byref(plane(gray, **u8)), None, 0), "rgb: bad mem")
+    refused(L.wm_rgb2gray(ctx, byref(plane(rgb, pitch=Cc - 1)), byref(plane(gray, **u8)), None, 0), "rgb: pitch < cols")
+    refused(L.wm_rgb2gray(ctx, byref(plane(rgb, frames=F + 1, frame_stride=3 * R * Cc)), byref(plane(gray, **u8)), None, 0), "rgb: frames=4 exceeds wm_configure max_frames=3")
+    refused(L.wm_rgb2gray(ctx, byref(plane(rgb, channel_stride=R * Cc - 1)), byref(plane(gray, **u8)), None, 0), "rgb: channel_stride too small")
+    refused(L.wm_rgb2gray(ctx, byref(plane(rgb, frames=2, frame_stride=3 * R * Cc - 1)), byref(plane(gray, **u8)), None, 0), "rgb: frame_stride too small")
+    refused(L.wm_rgb2gray(ctx, byref(rgb), byref(plane(gray, pitch=Cc - 1, **two)), None, 0), "gray_out: pitch < cols")
+    refused(L.wm_unpack_rgb8(ctx, byref(packed(pitch_bytes=3 * Cc - 1)), byref(plane(rgb, **wrong)), byref(gray), None, 0), "rgb_out: plane is")
+    refused(L.wm_unpack_rgb8(ctx, byref(packed(mem=wm.WM_MEM_SLOT_OUT)), byref(plane(rgb, channels=1)), byref(gray), None, 0), "packed: bad mem (device or host)")
+    refused(L.wm_unpack_rgb8(ctx, byref(packed(frames=F + 1, frame_stride_bytes=3 * R * Cc)), byref(plane(rgb, channels=1)), byref(gray), None, 0),
+            "packed: frames=4 exceeds wm_configure max_frames=3")
+    refused(L.wm_unpack_rgb8(ctx, byref(packed(frames=2, frame_stride_bytes=3 * R * Cc - 1)), byref(plane(rgb, channels=1)), byref(gray), None, 0),
+            "packed: frame_stride_bytes too small")
+    refused(L.wm_unpack_rgb8(ctx, byref(pk), byref(plane(rgb, **two)), byref(overlapping_gray), None, BAD_SLOT), "rgb_out: frame count mismatch")
+    refused(L.wm_unpack_rgb8(ctx, byref(pk), None, byref(plane(gray, data=pk.data)), nan_w, BAD_SLOT), "must not overlap")
+    refused(L.wm_pack_rgb8(ctx, byref(plane(rgb, **wrong)), byref(packed(pitch_bytes=3 * Cc - 1)), 0), "rgb: plane is")
+    # (the launch grid's refusals cannot be reached: wm_create stops at 32768 rows and wm_configure at 4096 frames, the grid at 65535)
+
     # nothing above left work or results behind
     assert eng.sync(0) == wm.WM_OK and eng.sync(1) == wm.WM_OK
+
+    # what needs an embed's output on the slot: a WM_MEM_SLOT_OUT input that does not match it, and an output laid over it
+    shape2 = (33, 258)
+    R2, C2 = shape2
+    eng2 = wm.Watermark(R2, C2, synth_watermark(R2, C2), 3, 40.0, nslots=2, max_frames=2)
+    ctx2 = eng2._ctx
+    x = rgb_frames(shape2, 1, "f32")[0]
+    gray_in, base = tc.from_numpy(np.array(gray_oracle(x, (shape2, 1, "f32")))).cuda(), tc.from_numpy(np.array(x)).cuda()
+    y = tc.empty((2, 3, R2, C2), dtype=tc.float32, device="cuda")[0]  # (room for the two frames one case below asks for)
+    gray2, free_pk = tc.zeros((2, R2, C2), dtype=tc.float32, device="cuda"), tc.zeros((R2, C2, 3), dtype=tc.uint8, device="cuda")
+    free_gray = gray2[0]
+    tc.cuda.synchronize()
+    eng2.embed_async(gray_in, base, y, wm.MASK_TYPE.NVF, 1)
+    assert eng2.sync(1) == wm.WM_OK
+    named = slot_out_plane(wm, shape2, wm.WM_F32)
+    gray_over_y = plane(wm.plane_of(free_gray, 1), data=y.data_ptr() + 4 * (2 * R2 * C2))  # the blue plane of y
+    pk_over_y = wm.packed_of(free_pk)
+    pk_over_y.data = y.data_ptr()
+    assert L.wm_rgb2gray(ctx2, byref(named), byref(wm.plane_of(free_gray, 1)), None, 1) == wm.WM_OK
+    assert L.wm_pack_rgb8(ctx2, byref(named), byref(wm.packed_of(free_pk)), 1) == wm.WM_OK
+    no_match = "WM_MEM_SLOT_OUT: no matching 3-channel embed output"
+    refused(L.wm_rgb2gray(ctx2, byref(slot_out_plane(wm, shape2, wm.WM_U8)), byref(gray_over_y), None, 1), no_match, ctx2)
+    refused(L.wm_rgb2gray(ctx2, byref(plane(named, frames=2, frame_stride=3 * R2 * C2)), byref(wm.plane_of(gray2, 1)), None, 1), no_match, ctx2)
+    refused(L.wm_pack_rgb8(ctx2, byref(slot_out_plane(wm, shape2, wm.WM_U8)), byref(pk_over_y), 1), no_match, ctx2)
+    refused(L.wm_rgb2gray(ctx2, byref(named), byref(gray_over_y), nan_w, 1), "weights: not finite", ctx2)
+    refused(L.wm_rgb2gray(ctx2, byref(named), byref(gray_over_y), None, 1), "wm_rgb2gray: gray_out overlaps rgb (the slot's last output)", ctx2)
+    refused(L.wm_pack_rgb8(ctx2, byref(named), byref(pk_over_y), 1), "wm_pack_rgb8: packed_out overlaps rgb (the slot's last output)", ctx2)
+    assert eng2.sync(1) == wm.WM_OK
+    eng2.close()

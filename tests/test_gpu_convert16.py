@@ -456,9 +456,9 @@ def test_error_precedence(wm, tc):
     ctx = eng._ctx
     byref = C.byref
 
-    def refused(rc, text, code=wm.WM_ERR_BAD_ARG):
+    def refused(rc, text, code=wm.WM_ERR_BAD_ARG, at=None):
         assert rc == code, (rc, text)
-        msg = L.wm_last_error(ctx).decode()
+        msg = L.wm_last_error(ctx if at is None else at).decode()
         assert text in msg, (text, msg)
 
     u_t = tc.zeros((R, Cc + 1), dtype=tc.int16, device="cuda")[:, :Cc]
@@ -548,8 +548,37 @@ def test_error_precedence(wm, tc):
     assert L.wm_detect16(p5._ctx, 0, byref(u), 10, 0, a, st, 0) == wm.WM_ERR_BAD_P
     p5.close()
 
+    # the refusals of the two conversions that no case above reaches
+    refused(L.wm_pack16(ctx, byref(plane(f, **wrong)), byref(plane(u, dtype=wm.WM_F32)), 10, 0, 0), "src_f32: plane is")
+    refused(L.wm_pack16(ctx, byref(plane(f, mem=wm.WM_MEM_SLOT_OUT, channels=2)), byref(plane(u, **two)), 10, 0, 0), "src_f32: channels must be 1 or 3")
+    refused(L.wm_unpack16(ctx, byref(plane(u, mem=wm.WM_MEM_SLOT_OUT)), 10, 0, byref(plane(f, **two)), 0), "src16: WM_MEM_SLOT_OUT is valid for")
+    refused(L.wm_unpack16(ctx, byref(u), 10, 0, byref(plane(f, pitch=Cc - 1, **two)), 0), "out_f32: pitch < cols")
+    # (the launch grid's refusals cannot be reached: wm_create stops at 32768 rows and wm_configure at 4096 frames, the grid at 65535)
+
     # nothing above left work or results behind
     assert eng.sync(0) == wm.WM_OK and eng.sync(1) == wm.WM_OK
+
+    # what needs an embed's output on the slot: a WM_MEM_SLOT_OUT input that does not match it, and an output laid over it
+    R2, C2 = 33, 258
+    eng2 = wm.Watermark(R2, C2, synth_watermark(R2, C2), 3, 40.0, nslots=2, max_frames=2)
+    ctx2 = eng2._ctx
+    x = tc.from_numpy(np.ascontiguousarray(D.unpack(samples((R2, C2), 1, 10)[0, 0], 10))).cuda()
+    y = tc.empty((2, R2, C2), dtype=tc.float32, device="cuda")[0]  # (room for the two frames one case below asks for)
+    free16 = tc.zeros((2, R2, C2), dtype=tc.int16, device="cuda")
+    tc.cuda.synchronize()
+    eng2.embed_async(x, x, y, wm.MASK_TYPE.NVF, 1)
+    assert eng2.sync(1) == wm.WM_OK
+    named = wm.wm_plane(None, R2, C2, 1, wm.WM_F32, wm.WM_MEM_SLOT_OUT, 1, C2, 0, 0)
+    u_free = wm.plane_any(free16[0])
+    u_over_y = plane(u_free, data=y.data_ptr())
+    assert L.wm_pack16(ctx2, byref(named), byref(u_free), 10, 0, 1) == wm.WM_OK
+    no_match = "WM_MEM_SLOT_OUT: no matching f32 embed output"
+    refused(L.wm_pack16(ctx2, byref(plane(named, frames=2, frame_stride=R2 * C2)), byref(wm.plane_any(free16)), 10, 0, 1), no_match, at=ctx2)
+    refused(L.wm_pack16(ctx2, byref(plane(named, channels=3, channel_stride=R2 * C2)), byref(plane(u_over_y, channels=3, channel_stride=R2 * C2)), 10, 0, 1), no_match, at=ctx2)
+    refused(L.wm_pack16(ctx2, byref(named), byref(u_over_y), 8, 0, 1), "bits=8", at=ctx2)
+    refused(L.wm_pack16(ctx2, byref(named), byref(u_over_y), 10, 0, 1), "wm_pack16: out16 overlaps src_f32 (the slot's last output)", at=ctx2)
+    assert eng2.sync(1) == wm.WM_OK
+    eng2.close()
 
 
 # ---- wm_app: a C420p10 y4m ---------------------------------------------------------------------------------------------------------------

@@ -668,7 +668,10 @@ PlaneDesc desc_device(const wm_plane* pl)
     d.p = pl->data; d.pitch = pl->pitch; d.fstride = pl->frames > 1 ? pl->frame_stride : 0;
     d.cstride = pl->channels > 1 ? pl->channel_stride : 0;
     d.dtype = pl->dtype; d.channels = pl->channels;
-    d.aligned = vec_ok(pl->data, pl->rows, d.pitch, d.fstride, d.cstride, pl->dtype, pl->frames, pl->channels) ? 1 : 0;
+    // a u16 plane (the 16-bit conversions only, check_plane refuses it elsewhere): four samples of a lane are one 8-byte access when
+    // the base is a multiple of 4 bytes and the pitch and the used strides are even
+    if (pl->dtype == WM_U16) d.aligned = reinterpret_cast<uintptr_t>(pl->data) % 4 == 0 && d.pitch % 2 == 0 && d.fstride % 2 == 0 && d.cstride % 2 == 0 ? 1 : 0;
+    else d.aligned = vec_ok(pl->data, pl->rows, d.pitch, d.fstride, d.cstride, pl->dtype, pl->frames, pl->channels) ? 1 : 0;
     return d;
 }
 
@@ -757,6 +760,19 @@ int stage_out(wm_ctx* ctx, Slot& s, const wm_plane* pl, const void* src, const S
     return WM_OK;
 }
 
+// a caller's own plane as the kernels address it: a device plane described, a host plane staged into the slot's buffer *buf (grown
+// on demand) and described there
+int resolve_plane(wm_ctx* ctx, Slot& s, const wm_plane* pl, void** buf, size_t* have, PlaneDesc* d)
+{
+    if (pl->mem != WM_MEM_HOST) { *d = desc_device(pl); return WM_OK; }
+    const Staged st = staged_layout(pl);
+    int rc = ensure(ctx, buf, have, st.bytes);
+    if (rc != WM_OK) return rc;
+    if ((rc = stage_in(ctx, s, pl, *buf, st)) != WM_OK) return rc;
+    *d = st.d; d->p = *buf;
+    return WM_OK;
+}
+
 // bytes from the first pixel of a plane to the end of its last one (all channels and frames)
 size_t plane_extent(const PlaneDesc& d, int rows, int cols, int frames)
 {
@@ -765,6 +781,10 @@ size_t plane_extent(const PlaneDesc& d, int rows, int cols, int frames)
     if (frames > 1) n += (size_t)(frames - 1) * d.fstride;
     return n * elem_size(d.dtype);
 }
+// ... as a byte range (a null plane has none and overlaps nothing)
+struct ByteRange { const char* lo; const char* hi; };
+ByteRange range_of(const PlaneDesc& d, int rows, int cols, int frames) { return ByteRange{(const char*)d.p, (const char*)d.p + plane_extent(d, rows, cols, frames)}; }
+bool ranges_overlap(const ByteRange& a, const ByteRange& b) { return a.lo && b.lo && a.lo < b.hi && b.lo < a.hi; }
 
 // do two RESOLVED planes share a byte (what the kernels will address: a WM_MEM_SLOT_OUT input is the slot's last output, host
 // planes are their staging buffers)?  frames_b > 0: `b` has that many frames (wm_embed_keys' K copies per input frame)
@@ -778,12 +798,12 @@ bool descs_overlap(const PlaneDesc& a, const PlaneDesc& b, int rows, int cols, i
 // A hand-over describes the plane a slot's last embed wrote (Slot::last_out).  Whatever the library itself writes over that
 // plane afterwards -- an embed on ANOTHER slot into the same buffer, a band embed, wm_compute_mask's mask / error planes --
 // ends the description; writes by the caller are the caller's contract (wm.h, WM_HANDOVER_VERIFY checks it)
-void invalidate_handovers(wm_ctx* ctx, const PlaneDesc& written, int frames)
+void invalidate_handovers(wm_ctx* ctx, const ByteRange& written)
 {
-    if (!written.p) return;
     for (auto& t : ctx->slots)
-        if (t.ho.valid && t.last_out_frames != 0 && descs_overlap(t.last_out, written, ctx->rows, ctx->cols, t.last_out_frames, frames)) t.ho.valid = false;
+        if (t.ho.valid && t.last_out_frames != 0 && ranges_overlap(range_of(t.last_out, ctx->rows, ctx->cols, t.last_out_frames), written)) t.ho.valid = false;
 }
+void invalidate_handovers(wm_ctx* ctx, const PlaneDesc& written, int frames) { invalidate_handovers(ctx, range_of(written, ctx->rows, ctx->cols, frames)); }
 
 // a profiled sweep: while the scope is set, every kernel launched through WM_KLAUNCH draws its own start / stop event pair
 // (wm_kernels.hpp: the events are attached to the dispatch, so they bracket the kernel and nothing else); a sweep that is two
@@ -1183,17 +1203,7 @@ static int prep_input(wm_ctx* ctx, Slot& s, const wm_plane* in, PlaneDesc* xd)
         *xd = s.last_out;
         return WM_OK;
     }
-    if (in->mem == WM_MEM_HOST) {
-        Staged st = staged_layout(in);
-        int rc = ensure(ctx, &s.st_in, &s.st_in_bytes, st.bytes);
-        if (rc != WM_OK) return rc;
-        rc = stage_in(ctx, s, in, s.st_in, st);
-        if (rc != WM_OK) return rc;
-        *xd = st.d; xd->p = s.st_in;
-    } else {
-        *xd = desc_device(in);
-    }
-    return WM_OK;
+    return resolve_plane(ctx, s, in, &s.st_in, &s.st_in_bytes, xd);
 }
 
 // the front half of a call that sweeps one grey input plane: the plane's checks, room for its result records (per_frame of them
@@ -1219,16 +1229,8 @@ static int prep_base(wm_ctx* ctx, Slot& s, const wm_plane* in_gray, const wm_pla
 {
     const bool base_is_in = base->data == in_gray->data && base->mem == in_gray->mem && base->mem != WM_MEM_SLOT_OUT && base->channels == 1 &&
                             base->dtype == in_gray->dtype && base->pitch == in_gray->pitch;
-    if (base->mem != WM_MEM_HOST) *bd = desc_device(base);
-    else if (base_is_in) *bd = xd;
-    else {
-        const Staged st = staged_layout(base);
-        int rc = ensure(ctx, &s.st_base, &s.st_base_bytes, st.bytes);
-        if (rc != WM_OK) return rc;
-        if ((rc = stage_in(ctx, s, base, s.st_base, st)) != WM_OK) return rc;
-        *bd = st.d; bd->p = s.st_base;
-    }
-    return WM_OK;
+    if (base->mem == WM_MEM_HOST && base_is_in) { *bd = xd; return WM_OK; }
+    return resolve_plane(ctx, s, base, &s.st_base, &s.st_base_bytes, bd);
 }
 
 // ---- the embed frame: what the embed calls share around their sweeps.  wm_embed and wm_embed_signs take all of it;
@@ -2291,12 +2293,10 @@ int wm_compute_mask(wm_ctx* ctx, int mask, const wm_plane* in_gray, const wm_pla
     return finish_call(ctx, s, slot, frames, 1, false, nullptr, status_out, coef_out);
 }
 
-// ---- the pixel-format front: wm_rgb2gray, wm_unpack_rgb8, wm_pack_rgb8 (wm.h; kernels in wm_k_convert.hip) -----------------------
-// The three calls look at their arguments in one order (wm.h): null pointers, shapes, channels / dtype (and everything else
-// check_plane asks of a single plane), frame counts, overlap of device planes, slot, weights, and last what needs the slot: a
-// WM_MEM_SLOT_OUT input.  Nothing is staged or launched before all of them have passed.
-// Host planes: inputs are staged in Slot::st_in, outputs in Slot::st_base -- never in st_out, which may hold the plane
-// WM_MEM_SLOT_OUT names (the conversions neither read their input from the buffer they write nor change what the name means).
+// ---- the conversion calls (wm.h): the pixel-format front wm_rgb2gray, wm_unpack_rgb8, wm_pack_rgb8 (kernels in wm_k_convert.hip) and
+// the samples of 9 to 16 bits, wm_unpack16 and wm_pack16 (wm_k_convert16.hip), with their host layers wm_embed16 and wm_detect16.
+// One frame, convert_call below, runs all five conversions: an entry point tests its pointers, lists its operands with their rules
+// and hands over its scalar check and its launch.  First this family's rules for one operand and one scalar argument
 static bool plane_null(const wm_plane* pl) { return !pl || (!pl->data && pl->mem != WM_MEM_SLOT_OUT); }
 static int check_shape(wm_ctx* ctx, int rows, int cols, const char* what)
 {
@@ -2336,199 +2336,20 @@ static int check_weights(wm_ctx* ctx, const float* weights, float* w)
     }
     return WM_OK;
 }
-// the bytes a device plane / packed buffer spans
-struct ByteRange { const char* lo; const char* hi; };
-static ByteRange range_of(const wm_ctx* ctx, const PlaneDesc& d, int frames) { return ByteRange{(const char*)d.p, (const char*)d.p + plane_extent(d, ctx->rows, ctx->cols, frames)}; }
-static ByteRange range_of(const wm_ctx* ctx, const PackedDesc& d, int frames)
-{
-    return ByteRange{(const char*)d.p, (const char*)d.p + (size_t)(frames - 1) * d.fstride + (size_t)(ctx->rows - 1) * d.pitch + 3 * (size_t)ctx->cols};
-}
-static bool ranges_overlap(const ByteRange& a, const ByteRange& b) { return a.lo && b.lo && a.lo < b.hi && b.lo < a.hi; }
-static PackedDesc desc_packed(const wm_packed* pk)
-{
-    PackedDesc d;
-    d.p = pk->data; d.pitch = pk->pitch_bytes; d.fstride = pk->frames > 1 ? pk->frame_stride_bytes : 0;
-    d.aligned = reinterpret_cast<uintptr_t>(pk->data) % 4 == 0 && d.pitch % 4 == 0 && d.fstride % 4 == 0;
-    return d;
-}
-// dense staging layout of a host packed buffer: rows of 3 * cols bytes, the pitch rounded up to 4
-static PackedDesc staged_packed(const wm_packed* pk, size_t* bytes)
-{
-    PackedDesc d;
-    d.p = nullptr; d.pitch = (3LL * pk->cols + 3) & ~3LL; d.fstride = d.pitch * pk->rows; d.aligned = 1;
-    *bytes = (size_t)d.fstride * pk->frames;
-    return d;
-}
-// a hand-over whose plane a packed output overwrites ends, like under every library write (invalidate_handovers for packed rows)
-static void invalidate_handovers_packed(wm_ctx* ctx, const PackedDesc& written, int frames)
-{
-    const ByteRange w = range_of(ctx, written, frames);
-    for (auto& t : ctx->slots)
-        if (t.ho.valid && t.last_out_frames != 0 && ranges_overlap(range_of(ctx, t.last_out, t.last_out_frames), w)) t.ho.valid = false;
-}
-// the planar RGB input of wm_rgb2gray / wm_pack_rgb8, resolved: the slot's last 3-channel embed output, the staged copy of a host
-// plane, or the device plane
-static int prep_rgb_input(wm_ctx* ctx, Slot& s, const wm_plane* rgb, PlaneDesc* d)
-{
-    if (rgb->mem == WM_MEM_SLOT_OUT) { *d = s.last_out; return WM_OK; }  // (matched by slot_out_rgb before anything was queued)
-    if (rgb->mem != WM_MEM_HOST) { *d = desc_device(rgb); return WM_OK; }
-    const Staged st = staged_layout(rgb);
-    int rc = ensure(ctx, &s.st_in, &s.st_in_bytes, st.bytes);
-    if (rc != WM_OK) return rc;
-    if ((rc = stage_in(ctx, s, rgb, s.st_in, st)) != WM_OK) return rc;
-    *d = st.d; d->p = s.st_in;
-    return WM_OK;
-}
+// what the slot's last output must be for a WM_MEM_SLOT_OUT input: a 3-channel embed output of the operand's frames and dtype ...
 static int slot_out_rgb(wm_ctx* ctx, const Slot& s, const wm_plane* rgb)
 {
-    if (rgb->mem != WM_MEM_SLOT_OUT) return WM_OK;
     if (s.last_out_frames == 0 || s.last_out.channels != 3 || rgb->frames != s.last_out_frames || rgb->dtype != s.last_out_dtype)
         return fail(ctx, WM_ERR_BAD_ARG, "WM_MEM_SLOT_OUT: no matching 3-channel embed output on this slot (frames / dtype must equal the last wm_embed's)");
     return WM_OK;
 }
-// host outputs of one call side by side in Slot::st_base: `need` bytes each rounded up to 256
-static size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }
-
-int wm_rgb2gray(wm_ctx* ctx, const wm_plane* rgb, const wm_plane* gray_out, const float* weights, int slot)
+// ... or an f32 embed output of the operand's channels and frames
+static int slot_out_f32(wm_ctx* ctx, const Slot& s, const wm_plane* src)
 {
-    if (!ctx) return WM_ERR_BAD_ARG;
-    if (plane_null(rgb) || plane_null(gray_out)) return fail(ctx, WM_ERR_BAD_ARG, "wm_rgb2gray: null plane");
-    int rc;
-    if ((rc = check_shape(ctx, rgb->rows, rgb->cols, "rgb")) != WM_OK || (rc = check_shape(ctx, gray_out->rows, gray_out->cols, "gray_out")) != WM_OK) return rc;
-    if ((rc = check_rgb_plane(ctx, rgb, "rgb", true)) != WM_OK || (rc = check_gray_f32(ctx, gray_out, "gray_out")) != WM_OK) return rc;
-    const int frames = rgb->frames;
-    if (gray_out->frames != frames) return fail(ctx, WM_ERR_BAD_ARG, "gray_out: frame count mismatch");
-    if (!convert_grid_fits(ctx->rows, frames)) return fail(ctx, WM_ERR_BAD_ARG, "wm_rgb2gray: rows or frames beyond the launch grid");
-    // overlap, on the resolved planes: host planes resolve to staging buffers of their own, a WM_MEM_SLOT_OUT input below
-    const bool dev_in = rgb->mem == WM_MEM_DEVICE, dev_out = gray_out->mem == WM_MEM_DEVICE;
-    if (dev_in && dev_out && ranges_overlap(range_of(ctx, desc_device(rgb), frames), range_of(ctx, desc_device(gray_out), frames)))
-        return fail(ctx, WM_ERR_BAD_ARG, "wm_rgb2gray: gray_out overlaps rgb");
-    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
-    Slot& s = slot_of(ctx, slot);
-    float w[3];
-    if ((rc = check_weights(ctx, weights, w)) != WM_OK) return rc;
-    if ((rc = slot_out_rgb(ctx, s, rgb)) != WM_OK) return rc;
-    if (rgb->mem == WM_MEM_SLOT_OUT && dev_out && ranges_overlap(range_of(ctx, s.last_out, frames), range_of(ctx, desc_device(gray_out), frames)))
-        return fail(ctx, WM_ERR_BAD_ARG, "wm_rgb2gray: gray_out overlaps rgb (the slot's last output)");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    PlaneDesc xd, gd;
-    if ((rc = prep_rgb_input(ctx, s, rgb, &xd)) != WM_OK) return rc;
-    Staged st_g{};
-    if (dev_out) gd = desc_device(gray_out);
-    else {
-        st_g = staged_layout(gray_out);
-        if ((rc = ensure(ctx, &s.st_base, &s.st_base_bytes, st_g.bytes)) != WM_OK) return rc;
-        gd = st_g.d; gd.p = s.st_base;
-    }
-    invalidate_handovers(ctx, gd, frames);
-    launch_rgb2gray(s.stream, ctx->rows, ctx->cols, frames, xd, gd, w);
-    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
-    if (!dev_out && (rc = stage_out(ctx, s, gray_out, s.st_base, st_g)) != WM_OK) return rc;
-    return finish_call(ctx, s, slot, 0, 0, false, nullptr, nullptr);
+    if (s.last_out_frames == 0 || s.last_out.channels != src->channels || src->frames != s.last_out_frames || s.last_out_dtype != WM_F32)
+        return fail(ctx, WM_ERR_BAD_ARG, "WM_MEM_SLOT_OUT: no matching f32 embed output on this slot (channels / frames must equal the last wm_embed's)");
+    return WM_OK;
 }
-
-int wm_unpack_rgb8(wm_ctx* ctx, const wm_packed* packed, const wm_plane* rgb_out, const wm_plane* gray_out, const float* weights, int slot)
-{
-    if (!ctx) return WM_ERR_BAD_ARG;
-    if (!packed || !packed->data) return fail(ctx, WM_ERR_BAD_ARG, "wm_unpack_rgb8: null packed buffer");
-    if (!rgb_out && !gray_out) return fail(ctx, WM_ERR_BAD_ARG, "wm_unpack_rgb8: rgb_out and gray_out are both null");
-    if ((rgb_out && !rgb_out->data) || (gray_out && !gray_out->data)) return fail(ctx, WM_ERR_BAD_ARG, "wm_unpack_rgb8: null plane");
-    int rc;
-    if ((rc = check_shape(ctx, packed->rows, packed->cols, "packed")) != WM_OK) return rc;
-    if (rgb_out && (rc = check_shape(ctx, rgb_out->rows, rgb_out->cols, "rgb_out")) != WM_OK) return rc;
-    if (gray_out && (rc = check_shape(ctx, gray_out->rows, gray_out->cols, "gray_out")) != WM_OK) return rc;
-    if ((rc = check_packed(ctx, packed, "packed")) != WM_OK) return rc;
-    if (rgb_out && (rc = check_rgb_plane(ctx, rgb_out, "rgb_out", false)) != WM_OK) return rc;
-    if (gray_out && (rc = check_gray_f32(ctx, gray_out, "gray_out")) != WM_OK) return rc;
-    const int frames = packed->frames;
-    if (rgb_out && rgb_out->frames != frames) return fail(ctx, WM_ERR_BAD_ARG, "rgb_out: frame count mismatch");
-    if (gray_out && gray_out->frames != frames) return fail(ctx, WM_ERR_BAD_ARG, "gray_out: frame count mismatch");
-    if (!convert_grid_fits(ctx->rows, frames)) return fail(ctx, WM_ERR_BAD_ARG, "wm_unpack_rgb8: rows or frames beyond the launch grid");
-    const bool dev_in = packed->mem == WM_MEM_DEVICE, dev_rgb = rgb_out && rgb_out->mem == WM_MEM_DEVICE, dev_gray = gray_out && gray_out->mem == WM_MEM_DEVICE;
-    {
-        const ByteRange none{nullptr, nullptr};
-        const ByteRange rp = dev_in ? range_of(ctx, desc_packed(packed), frames) : none;
-        const ByteRange rr = dev_rgb ? range_of(ctx, desc_device(rgb_out), frames) : none;
-        const ByteRange rg = dev_gray ? range_of(ctx, desc_device(gray_out), frames) : none;
-        if (ranges_overlap(rp, rr) || ranges_overlap(rp, rg) || ranges_overlap(rr, rg)) return fail(ctx, WM_ERR_BAD_ARG, "wm_unpack_rgb8: packed, rgb_out and gray_out must not overlap");
-    }
-    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
-    Slot& s = slot_of(ctx, slot);
-    float w[3];
-    if ((rc = check_weights(ctx, weights, w)) != WM_OK) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    PackedDesc pd;
-    if (dev_in) pd = desc_packed(packed);
-    else {  // a host buffer goes up as rows of 3 * cols bytes
-        size_t bytes;
-        pd = staged_packed(packed, &bytes);
-        if ((rc = ensure(ctx, &s.st_in, &s.st_in_bytes, bytes)) != WM_OK) return rc;
-        pd.p = s.st_in;
-        for (int f = 0; f < frames; ++f)
-            HIPCHK(ctx, hipMemcpy2DAsync((char*)s.st_in + (size_t)f * pd.fstride, pd.pitch, (const char*)packed->data + (size_t)f * (frames > 1 ? packed->frame_stride_bytes : 0),
-                                         packed->pitch_bytes, 3 * (size_t)packed->cols, packed->rows, hipMemcpyHostToDevice, s.stream));
-    }
-    // host outputs: side by side in st_base
-    Staged st_r{}, st_g{};
-    if (rgb_out && !dev_rgb) st_r = staged_layout(rgb_out);
-    if (gray_out && !dev_gray) st_g = staged_layout(gray_out);
-    const size_t off_g = rgb_out && !dev_rgb ? round256(st_r.bytes) : 0;
-    const size_t host_bytes = off_g + (gray_out && !dev_gray ? st_g.bytes : 0);
-    if (host_bytes && (rc = ensure(ctx, &s.st_base, &s.st_base_bytes, host_bytes)) != WM_OK) return rc;
-    PlaneDesc rd{}, gd{};
-    if (rgb_out) { if (dev_rgb) rd = desc_device(rgb_out); else { rd = st_r.d; rd.p = s.st_base; } }
-    if (gray_out) { if (dev_gray) gd = desc_device(gray_out); else { gd = st_g.d; gd.p = (char*)s.st_base + off_g; } }
-    if (rgb_out) invalidate_handovers(ctx, rd, frames);
-    if (gray_out) invalidate_handovers(ctx, gd, frames);
-    launch_unpack_rgb8(s.stream, ctx->rows, ctx->cols, frames, pd, rd, gd, w);
-    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
-    if (rgb_out && !dev_rgb && (rc = stage_out(ctx, s, rgb_out, rd.p, st_r)) != WM_OK) return rc;
-    if (gray_out && !dev_gray && (rc = stage_out(ctx, s, gray_out, gd.p, st_g)) != WM_OK) return rc;
-    return finish_call(ctx, s, slot, 0, 0, false, nullptr, nullptr);
-}
-
-int wm_pack_rgb8(wm_ctx* ctx, const wm_plane* rgb, const wm_packed* packed_out, int slot)
-{
-    if (!ctx) return WM_ERR_BAD_ARG;
-    if (plane_null(rgb) || !packed_out || !packed_out->data) return fail(ctx, WM_ERR_BAD_ARG, "wm_pack_rgb8: null plane or packed buffer");
-    int rc;
-    if ((rc = check_shape(ctx, rgb->rows, rgb->cols, "rgb")) != WM_OK || (rc = check_shape(ctx, packed_out->rows, packed_out->cols, "packed_out")) != WM_OK) return rc;
-    if ((rc = check_rgb_plane(ctx, rgb, "rgb", true)) != WM_OK || (rc = check_packed(ctx, packed_out, "packed_out")) != WM_OK) return rc;
-    const int frames = rgb->frames;
-    if (packed_out->frames != frames) return fail(ctx, WM_ERR_BAD_ARG, "packed_out: frame count mismatch");
-    if (!convert_grid_fits(ctx->rows, frames)) return fail(ctx, WM_ERR_BAD_ARG, "wm_pack_rgb8: rows or frames beyond the launch grid");
-    const bool dev_in = rgb->mem == WM_MEM_DEVICE, dev_out = packed_out->mem == WM_MEM_DEVICE;
-    if (dev_in && dev_out && ranges_overlap(range_of(ctx, desc_device(rgb), frames), range_of(ctx, desc_packed(packed_out), frames)))
-        return fail(ctx, WM_ERR_BAD_ARG, "wm_pack_rgb8: packed_out overlaps rgb");
-    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
-    Slot& s = slot_of(ctx, slot);
-    if ((rc = slot_out_rgb(ctx, s, rgb)) != WM_OK) return rc;
-    if (rgb->mem == WM_MEM_SLOT_OUT && dev_out && ranges_overlap(range_of(ctx, s.last_out, frames), range_of(ctx, desc_packed(packed_out), frames)))
-        return fail(ctx, WM_ERR_BAD_ARG, "wm_pack_rgb8: packed_out overlaps rgb (the slot's last output)");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    PlaneDesc xd;
-    if ((rc = prep_rgb_input(ctx, s, rgb, &xd)) != WM_OK) return rc;
-    PackedDesc pd;
-    if (dev_out) pd = desc_packed(packed_out);
-    else {
-        size_t bytes;
-        pd = staged_packed(packed_out, &bytes);
-        if ((rc = ensure(ctx, &s.st_base, &s.st_base_bytes, bytes)) != WM_OK) return rc;
-        pd.p = s.st_base;
-    }
-    invalidate_handovers_packed(ctx, pd, frames);
-    launch_pack_rgb8(s.stream, ctx->rows, ctx->cols, frames, xd, pd);
-    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
-    if (!dev_out)
-        for (int f = 0; f < frames; ++f)
-            HIPCHK(ctx, hipMemcpy2DAsync((char*)packed_out->data + (size_t)f * (frames > 1 ? packed_out->frame_stride_bytes : 0), packed_out->pitch_bytes,
-                                         (const char*)s.st_base + (size_t)f * pd.fstride, pd.pitch, 3 * (size_t)packed_out->cols, packed_out->rows, hipMemcpyDeviceToHost, s.stream));
-    return finish_call(ctx, s, slot, 0, 0, false, nullptr, nullptr);
-}
-
-// ---- samples of 9 to 16 bits: wm_depth_scale, wm_unpack16, wm_pack16 and the host layers wm_embed16, wm_detect16 (wm.h; kernels in
-// wm_k_convert16.hip).  The two conversions are the pixel-format front once more: the same order of checks (`bits` and msb_aligned
-// where the weights stood), host inputs in Slot::st_in, host outputs in Slot::st_base, no result records.
 int wm_depth_scale(int bits, float* to255, float* from255)
 {
     if (bits < 9 || bits > 16 || !to255 || !from255) return WM_ERR_BAD_ARG;
@@ -2558,109 +2379,175 @@ static int check_depth(wm_ctx* ctx, int bits, int msb_aligned)
     if (bits < 9 || bits > 16) return fail(ctx, WM_ERR_BAD_ARG, "bits=" + std::to_string(bits) + ": must be 9..16");
     return msb_aligned == 0 || msb_aligned == 1 ? WM_OK : fail(ctx, WM_ERR_BAD_ARG, "msb_aligned must be 0 or 1");
 }
-// a device u16 plane, described: four samples of a lane are one 8-byte access when the base is a multiple of 4 bytes and the pitch
-// and the used strides are even
-static PlaneDesc desc_device16(const wm_plane* pl)
+
+// ---- one operand of a conversion call.  The input comes first in a call's list, its outputs follow (at most two).  A packed buffer
+// is carried as the plane its bytes are -- u8, 1 channel, 3 * cols wide, pitch and frame stride in bytes -- so that extents, staging
+// and the copies both ways are the planes' (staged_layout then gives rows of 3 * cols bytes at a pitch rounded up to 4)
+enum ConvKind { OP_RGB, OP_GRAY_F32, OP_U16, OP_F32, OP_PACKED };  // the operand's own rule: conv_check_operand
+typedef int (*SlotOutRule)(wm_ctx*, const Slot&, const wm_plane*);
+struct ConvOp {
+    const char* name;      // the argument's name in messages
+    ConvKind kind;
+    const wm_plane* pl;    // as passed: a planar operand, or
+    const wm_packed* pk;   // a packed one; both null: an output the call leaves out
+    SlotOutRule match;     // an input that may be WM_MEM_SLOT_OUT: what the slot's last output must be (null: a caller's plane only)
+    wm_plane v;            // the operand as a plane
+    PlaneDesc d;           // resolved: what the kernel addresses -- the device plane, the slot's last output, or its place in a staging buffer
+    Staged st;             // a host output's staging layout ...
+    size_t off;            // ... and its offset in Slot::st_base
+    bool present() const { return pl || pk; }
+    bool in(int mem) const { return present() && v.mem == mem; }
+    ByteRange range() const { return range_of(d, v.rows, v.cols, v.frames); }  // (nothing before the operand is resolved)
+};
+static ConvOp conv_plane(const char* name, ConvKind kind, const wm_plane* pl, SlotOutRule match = nullptr)
 {
-    PlaneDesc d;
-    d.p = pl->data; d.pitch = pl->pitch; d.fstride = pl->frames > 1 ? pl->frame_stride : 0;
-    d.cstride = pl->channels > 1 ? pl->channel_stride : 0;
-    d.dtype = WM_U16; d.channels = pl->channels;
-    d.aligned = reinterpret_cast<uintptr_t>(pl->data) % 4 == 0 && d.pitch % 2 == 0 && d.fstride % 2 == 0 && d.cstride % 2 == 0 ? 1 : 0;
+    ConvOp o{};
+    o.name = name; o.kind = kind; o.pl = pl; o.match = match;
+    if (pl) o.v = *pl;
+    return o;
+}
+static ConvOp conv_packed(const char* name, const wm_packed* pk)
+{
+    ConvOp o{};
+    o.name = name; o.kind = OP_PACKED; o.pk = pk;
+    o.v.data = pk->data; o.v.rows = pk->rows; o.v.cols = (int32_t)(3 * (int64_t)pk->cols); o.v.channels = 1; o.v.dtype = WM_U8; o.v.mem = pk->mem;
+    o.v.frames = pk->frames; o.v.pitch = pk->pitch_bytes; o.v.frame_stride = pk->frame_stride_bytes;
+    return o;
+}
+// the descriptor the packed kernels take: a lane's four pixels are three dwords when base, pitch and frame stride are multiples of 4
+static PackedDesc packed_desc(const ConvOp& o)
+{
+    PackedDesc d;
+    d.p = o.d.p; d.pitch = o.d.pitch; d.fstride = o.d.fstride;
+    d.aligned = reinterpret_cast<uintptr_t>(d.p) % 4 == 0 && d.pitch % 4 == 0 && d.fstride % 4 == 0;
     return d;
 }
-// the planes' shared front: what both must satisfy together (channels, frames, the launch grid)
-static int check_pair16(wm_ctx* ctx, const char* who, const wm_plane* a, const wm_plane* b)
+static int conv_check_operand(wm_ctx* ctx, const ConvOp& o)
 {
-    if (a->channels != b->channels) return fail(ctx, WM_ERR_BAD_ARG, std::string(who) + ": channel count mismatch");
-    if (a->frames != b->frames) return fail(ctx, WM_ERR_BAD_ARG, std::string(who) + ": frame count mismatch");
-    if (!convert_grid_fits(ctx->rows, a->frames * a->channels)) return fail(ctx, WM_ERR_BAD_ARG, std::string(who) + ": rows or frames beyond the launch grid");
-    return WM_OK;
+    switch (o.kind) {
+    case OP_RGB: return check_rgb_plane(ctx, o.pl, o.name, o.match != nullptr);
+    case OP_GRAY_F32: return check_gray_f32(ctx, o.pl, o.name);
+    case OP_U16: return check_plane16(ctx, o.pl, o.name);
+    case OP_F32: return check_plane_f32(ctx, o.pl, o.name, o.match != nullptr);
+    default: return check_packed(ctx, o.pk, o.name);
+    }
+}
+static int fail_overlap(wm_ctx* ctx, const char* who, const ConvOp* op, int n, const char* where)
+{
+    if (n == 3) return fail(ctx, WM_ERR_BAD_ARG, std::string(who) + ": " + op[0].name + ", " + op[1].name + " and " + op[2].name + " must not overlap" + where);
+    return fail(ctx, WM_ERR_BAD_ARG, std::string(who) + ": " + op[1].name + " overlaps " + op[0].name + where);
+}
+static size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// ---- the conversions' frame.  The arguments are looked at in wm.h's order: shapes, each operand's own rules, frames between the
+// operands (per_channel, the 16-bit calls: channels too, and the grid's z is frames x channels), the launch grid, overlap of device
+// operands, slot, the scalar argument (scalar_check: weights, or bits / msb_aligned), and last what needs the slot -- a
+// WM_MEM_SLOT_OUT input's matching rule and its overlap with the outputs.  Nothing is staged or launched before all of them have
+// passed.  A host input is staged in Slot::st_in, host outputs side by side in Slot::st_base at multiples of 256 bytes -- never in
+// st_out, which may hold the plane WM_MEM_SLOT_OUT names (the conversions neither read their input from the buffer they write nor
+// change what the name means).  Every output ends the hand-overs whose plane it overwrites.  launch(stream, frames) reads the
+// resolved operands; the calls are plain enqueues and queue no result records
+extern "C++" {  // (a template cannot have C linkage)
+template <class Scalar, class Launch>
+static int convert_call(wm_ctx* ctx, const char* who, bool per_channel, ConvOp* op, int n, int slot, Scalar scalar_check, Launch launch)
+{
+    int rc;
+    for (int i = 0; i < n; ++i)
+        if (op[i].present() && (rc = check_shape(ctx, op[i].v.rows, op[i].pk ? op[i].pk->cols : op[i].v.cols, op[i].name)) != WM_OK) return rc;
+    for (int i = 0; i < n; ++i)
+        if (op[i].present() && (rc = conv_check_operand(ctx, op[i])) != WM_OK) return rc;
+    const int frames = op[0].v.frames, channels = op[0].v.channels;
+    for (int i = 1; i < n && per_channel; ++i)
+        if (op[i].present() && op[i].v.channels != channels) return fail(ctx, WM_ERR_BAD_ARG, std::string(who) + ": channel count mismatch");
+    for (int i = 1; i < n; ++i)
+        if (op[i].present() && op[i].v.frames != frames) return fail(ctx, WM_ERR_BAD_ARG, std::string(per_channel ? who : op[i].name) + ": frame count mismatch");
+    if (!convert_grid_fits(ctx->rows, per_channel ? frames * channels : frames)) return fail(ctx, WM_ERR_BAD_ARG, std::string(who) + ": rows or frames beyond the launch grid");
+    // overlap, on the resolved operands: host operands resolve to staging buffers of their own, a WM_MEM_SLOT_OUT input below
+    for (int i = 0; i < n; ++i)
+        if (op[i].in(WM_MEM_DEVICE)) op[i].d = desc_device(&op[i].v);
+    for (int i = 0; i < n; ++i)
+        for (int j = i + 1; j < n; ++j)
+            if (ranges_overlap(op[i].range(), op[j].range())) return fail_overlap(ctx, who, op, n, "");
+    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
+    if ((rc = scalar_check()) != WM_OK) return rc;
+    if (op[0].in(WM_MEM_SLOT_OUT)) {
+        if ((rc = op[0].match(ctx, s, op[0].pl)) != WM_OK) return rc;
+        op[0].d = s.last_out;
+        for (int j = 1; j < n; ++j)
+            if (ranges_overlap(op[0].range(), op[j].range())) return fail_overlap(ctx, who, op, n, " (the slot's last output)");
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!op[0].in(WM_MEM_SLOT_OUT) && (rc = resolve_plane(ctx, s, &op[0].v, &s.st_in, &s.st_in_bytes, &op[0].d)) != WM_OK) return rc;
+    size_t need = 0;
+    for (int j = 1; j < n; ++j)
+        if (op[j].in(WM_MEM_HOST)) { op[j].st = staged_layout(&op[j].v); op[j].off = round256(need); need = op[j].off + op[j].st.bytes; }
+    if (need && (rc = ensure(ctx, &s.st_base, &s.st_base_bytes, need)) != WM_OK) return rc;
+    for (int j = 1; j < n; ++j) {
+        if (op[j].in(WM_MEM_HOST)) { op[j].d = op[j].st.d; op[j].d.p = (char*)s.st_base + op[j].off; }
+        if (op[j].present()) invalidate_handovers(ctx, op[j].range());
+    }
+    launch(s.stream, frames);
+    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
+    for (int j = 1; j < n; ++j)
+        if (op[j].in(WM_MEM_HOST) && (rc = stage_out(ctx, s, &op[j].v, op[j].d.p, op[j].st)) != WM_OK) return rc;
+    return finish_call(ctx, s, slot, 0, 0, false, nullptr, nullptr);
+}
+}  // extern "C++"
+
+int wm_rgb2gray(wm_ctx* ctx, const wm_plane* rgb, const wm_plane* gray_out, const float* weights, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    if (plane_null(rgb) || plane_null(gray_out)) return fail(ctx, WM_ERR_BAD_ARG, "wm_rgb2gray: null plane");
+    ConvOp op[] = {conv_plane("rgb", OP_RGB, rgb, slot_out_rgb), conv_plane("gray_out", OP_GRAY_F32, gray_out)};
+    float w[3];
+    return convert_call(ctx, "wm_rgb2gray", false, op, 2, slot, [&] { return check_weights(ctx, weights, w); },
+                        [&](hipStream_t st, int frames) { launch_rgb2gray(st, ctx->rows, ctx->cols, frames, op[0].d, op[1].d, w); });
+}
+
+int wm_unpack_rgb8(wm_ctx* ctx, const wm_packed* packed, const wm_plane* rgb_out, const wm_plane* gray_out, const float* weights, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    if (!packed || !packed->data) return fail(ctx, WM_ERR_BAD_ARG, "wm_unpack_rgb8: null packed buffer");
+    if (!rgb_out && !gray_out) return fail(ctx, WM_ERR_BAD_ARG, "wm_unpack_rgb8: rgb_out and gray_out are both null");
+    if ((rgb_out && !rgb_out->data) || (gray_out && !gray_out->data)) return fail(ctx, WM_ERR_BAD_ARG, "wm_unpack_rgb8: null plane");
+    ConvOp op[] = {conv_packed("packed", packed), conv_plane("rgb_out", OP_RGB, rgb_out), conv_plane("gray_out", OP_GRAY_F32, gray_out)};
+    float w[3];
+    return convert_call(ctx, "wm_unpack_rgb8", false, op, 3, slot, [&] { return check_weights(ctx, weights, w); },
+                        [&](hipStream_t st, int frames) { launch_unpack_rgb8(st, ctx->rows, ctx->cols, frames, packed_desc(op[0]), op[1].d, op[2].d, w); });
+}
+
+int wm_pack_rgb8(wm_ctx* ctx, const wm_plane* rgb, const wm_packed* packed_out, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    if (plane_null(rgb) || !packed_out || !packed_out->data) return fail(ctx, WM_ERR_BAD_ARG, "wm_pack_rgb8: null plane or packed buffer");
+    ConvOp op[] = {conv_plane("rgb", OP_RGB, rgb, slot_out_rgb), conv_packed("packed_out", packed_out)};
+    return convert_call(ctx, "wm_pack_rgb8", false, op, 2, slot, [] { return WM_OK; },
+                        [&](hipStream_t st, int frames) { launch_pack_rgb8(st, ctx->rows, ctx->cols, frames, op[0].d, packed_desc(op[1])); });
 }
 
 int wm_unpack16(wm_ctx* ctx, const wm_plane* src16, int bits, int msb_aligned, const wm_plane* out_f32, int slot)
 {
     if (!ctx) return WM_ERR_BAD_ARG;
     if (!src16 || !src16->data || !out_f32 || !out_f32->data) return fail(ctx, WM_ERR_BAD_ARG, "wm_unpack16: null plane");
-    int rc;
-    if ((rc = check_shape(ctx, src16->rows, src16->cols, "src16")) != WM_OK || (rc = check_shape(ctx, out_f32->rows, out_f32->cols, "out_f32")) != WM_OK) return rc;
-    if ((rc = check_plane16(ctx, src16, "src16")) != WM_OK || (rc = check_plane_f32(ctx, out_f32, "out_f32", false)) != WM_OK) return rc;
-    if ((rc = check_pair16(ctx, "wm_unpack16", src16, out_f32)) != WM_OK) return rc;
-    const int frames = src16->frames;
-    const bool dev_in = src16->mem == WM_MEM_DEVICE, dev_out = out_f32->mem == WM_MEM_DEVICE;
-    if (dev_in && dev_out && ranges_overlap(range_of(ctx, desc_device16(src16), frames), range_of(ctx, desc_device(out_f32), frames)))
-        return fail(ctx, WM_ERR_BAD_ARG, "wm_unpack16: out_f32 overlaps src16");
-    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
-    Slot& s = slot_of(ctx, slot);
-    if ((rc = check_depth(ctx, bits, msb_aligned)) != WM_OK) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    PlaneDesc xd, od;
-    if (dev_in) xd = desc_device16(src16);
-    else {
-        const Staged st = staged_layout(src16);
-        if ((rc = ensure(ctx, &s.st_in, &s.st_in_bytes, st.bytes)) != WM_OK) return rc;
-        if ((rc = stage_in(ctx, s, src16, s.st_in, st)) != WM_OK) return rc;
-        xd = st.d; xd.p = s.st_in;
-    }
-    Staged st_o{};
-    if (dev_out) od = desc_device(out_f32);
-    else {
-        st_o = staged_layout(out_f32);
-        if ((rc = ensure(ctx, &s.st_base, &s.st_base_bytes, st_o.bytes)) != WM_OK) return rc;
-        od = st_o.d; od.p = s.st_base;
-    }
-    invalidate_handovers(ctx, od, frames);
-    float k_in, k_out;
-    (void)wm_depth_scale(bits, &k_in, &k_out);
-    launch_unpack16(s.stream, ctx->rows, ctx->cols, frames, xd, od, bits, msb_aligned, k_in);
-    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
-    if (!dev_out && (rc = stage_out(ctx, s, out_f32, s.st_base, st_o)) != WM_OK) return rc;
-    return finish_call(ctx, s, slot, 0, 0, false, nullptr, nullptr);
+    ConvOp op[] = {conv_plane("src16", OP_U16, src16), conv_plane("out_f32", OP_F32, out_f32)};
+    return convert_call(ctx, "wm_unpack16", true, op, 2, slot, [&] { return check_depth(ctx, bits, msb_aligned); }, [&](hipStream_t st, int frames) {
+        float k_in, k_out;
+        (void)wm_depth_scale(bits, &k_in, &k_out);
+        launch_unpack16(st, ctx->rows, ctx->cols, frames, op[0].d, op[1].d, bits, msb_aligned, k_in);
+    });
 }
 
 int wm_pack16(wm_ctx* ctx, const wm_plane* src_f32, const wm_plane* out16, int bits, int msb_aligned, int slot)
 {
     if (!ctx) return WM_ERR_BAD_ARG;
     if (plane_null(src_f32) || !out16 || !out16->data) return fail(ctx, WM_ERR_BAD_ARG, "wm_pack16: null plane");
-    int rc;
-    if ((rc = check_shape(ctx, src_f32->rows, src_f32->cols, "src_f32")) != WM_OK || (rc = check_shape(ctx, out16->rows, out16->cols, "out16")) != WM_OK) return rc;
-    if ((rc = check_plane_f32(ctx, src_f32, "src_f32", true)) != WM_OK || (rc = check_plane16(ctx, out16, "out16")) != WM_OK) return rc;
-    if ((rc = check_pair16(ctx, "wm_pack16", src_f32, out16)) != WM_OK) return rc;
-    const int frames = src_f32->frames;
-    const bool dev_in = src_f32->mem == WM_MEM_DEVICE, dev_out = out16->mem == WM_MEM_DEVICE, slot_in = src_f32->mem == WM_MEM_SLOT_OUT;
-    if (dev_in && dev_out && ranges_overlap(range_of(ctx, desc_device(src_f32), frames), range_of(ctx, desc_device16(out16), frames)))
-        return fail(ctx, WM_ERR_BAD_ARG, "wm_pack16: out16 overlaps src_f32");
-    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
-    Slot& s = slot_of(ctx, slot);
-    if ((rc = check_depth(ctx, bits, msb_aligned)) != WM_OK) return rc;
-    if (slot_in && (s.last_out_frames == 0 || s.last_out.channels != src_f32->channels || frames != s.last_out_frames || s.last_out_dtype != WM_F32))
-        return fail(ctx, WM_ERR_BAD_ARG, "WM_MEM_SLOT_OUT: no matching f32 embed output on this slot (channels / frames must equal the last wm_embed's)");
-    if (slot_in && dev_out && ranges_overlap(range_of(ctx, s.last_out, frames), range_of(ctx, desc_device16(out16), frames)))
-        return fail(ctx, WM_ERR_BAD_ARG, "wm_pack16: out16 overlaps src_f32 (the slot's last output)");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    PlaneDesc xd, od;
-    if (slot_in) xd = s.last_out;
-    else if (dev_in) xd = desc_device(src_f32);
-    else {
-        const Staged st = staged_layout(src_f32);
-        if ((rc = ensure(ctx, &s.st_in, &s.st_in_bytes, st.bytes)) != WM_OK) return rc;
-        if ((rc = stage_in(ctx, s, src_f32, s.st_in, st)) != WM_OK) return rc;
-        xd = st.d; xd.p = s.st_in;
-    }
-    Staged st_o{};
-    if (dev_out) od = desc_device16(out16);
-    else {
-        st_o = staged_layout(out16);
-        if ((rc = ensure(ctx, &s.st_base, &s.st_base_bytes, st_o.bytes)) != WM_OK) return rc;
-        od = st_o.d; od.p = s.st_base;
-    }
-    invalidate_handovers(ctx, od, frames);  // (by the bytes the u16 plane spans)
-    float k_in, k_out;
-    (void)wm_depth_scale(bits, &k_in, &k_out);
-    launch_pack16(s.stream, ctx->rows, ctx->cols, frames, xd, od, bits, msb_aligned, k_out);
-    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
-    if (!dev_out && (rc = stage_out(ctx, s, out16, s.st_base, st_o)) != WM_OK) return rc;
-    return finish_call(ctx, s, slot, 0, 0, false, nullptr, nullptr);
+    ConvOp op[] = {conv_plane("src_f32", OP_F32, src_f32, slot_out_f32), conv_plane("out16", OP_U16, out16)};
+    return convert_call(ctx, "wm_pack16", true, op, 2, slot, [&] { return check_depth(ctx, bits, msb_aligned); }, [&](hipStream_t st, int frames) {
+        float k_in, k_out;
+        (void)wm_depth_scale(bits, &k_in, &k_out);
+        launch_pack16(st, ctx->rows, ctx->cols, frames, op[0].d, op[1].d, bits, msb_aligned, k_out);  // (the u16 output is judged by the bytes it spans)
+    });
 }
 
 // the front of the two host layers: everything they refuse themselves, before anything is queued; then the slot's f32 plane(s),
