@@ -96,14 +96,34 @@ int wm_create_from_file(wm_ctx** out, int device, int rows, int cols, int p, flo
  * the file `wm_genw rows cols seed file` writes (to the last ulp of the device's f64 log / cos) and every GPU of a node
  * fills its own copy without a file, an upload or a broadcast.  wm_w_device() + wm_memcpy_d2h() read it back. */
 int wm_create_generated(wm_ctx** out, int device, int rows, int cols, int p, float psnr, uint32_t seed);
-/* Watermark(const Watermark&) / operator= (Watermark.cpp:30-51): shares W, owns new scratch */
+/* Watermark(const Watermark&) / operator= (Watermark.cpp:30-51): shares W, owns new scratch.  The clone takes EVERY setting of the
+ * source: shape, p, psnr, slots and max_frames, rows per segment, fused mode, wm_set_handover, wm_set_checked_handover and the band.
+ * It does not take the caller's streams (every slot of the clone runs on a stream of its own), queued results, what
+ * WM_MEM_SLOT_OUT names, pending hand-overs, the checked hand-over's counts or profile numbers (profiling starts switched off).
+ * Source and clone are independent afterwards: either may be reinitialised or destroyed without the other noticing. */
 int wm_clone(const wm_ctx* src, wm_ctx** out);
+/* ---- Reconfiguring a context: wm_reinit, wm_reinit_from_file, wm_configure, wm_set_rows_per_segment ------------------------------
+ * All four rebuild every slot, and behave alike.  After the arguments have been checked (a refused call changes nothing) they
+ *   1. wait for all slots and DELIVER what is queued on them, as wm_sync would: strengths, scores, statuses and coefficients reach
+ *      the callers' pointers.  An unsolvable frame is in its status; the call itself still returns WM_OK (as wm_set_stream does),
+ *      and a wm_sync afterwards has nothing left to deliver.  An error (< 0) of the wait is returned and nothing is rebuilt;
+ *   2. start every slot afresh: WM_MEM_SLOT_OUT names nothing until the slot's next embed (WM_ERR_BAD_ARG), no hand-over is pending,
+ *      promised or checked, wm_checked_handover_counts reads (0, 0), and the scratch that grows on demand (staging buffers, key and
+ *      tile records, table arenas, the 16-bit planes) is gone and grows again with the first call that needs it.
+ * KEPT by all four: p, psnr, the number of slots and max_frames (wm_configure: as given), rows per segment (wm_set_rows_per_segment:
+ * as given), fused mode, wm_set_handover, wm_set_checked_handover, profiling (switched on or off, and the numbers recorded so far),
+ * and the caller's stream of every slot that still exists: a slot given a stream with wm_set_stream still runs on it, ordered with
+ * the caller's collectives as before; a slot index beyond a smaller nslots is gone, and its stream with it (WM_ERR_BAD_ARG).
+ * The BAND (wm_band_configure) is kept by wm_configure and wm_set_rows_per_segment and cleared by the two reinits: it describes rows
+ * of the old planes.  After a reinit planes and key banks of the old shape are WM_ERR_BAD_ARG.
+ * Results do not depend on how a context reached its configuration: the same shape, W, p, psnr, slots, max_frames, rows per segment,
+ * fused mode, hand-over settings and band give the same bits (tests/test_gpu_lifecycle.py). */
 /* Watermark::reinitialize(path, rows, cols)  (Watermark.cpp:78-85) */
 int wm_reinit(wm_ctx* ctx, int rows, int cols, const float* w_rowmajor);
 int wm_reinit_from_file(wm_ctx* ctx, int rows, int cols, const char* w_path);
 void wm_destroy(wm_ctx* ctx);
 
-/* number of slots (streams + scratch) and the largest `frames` a call may carry; default 2 x 1 */
+/* number of slots (streams + scratch) and the largest `frames` a call may carry; default 2 x 1.  A reconfiguring call (above) */
 int wm_configure(wm_ctx* ctx, int nslots, int max_frames);
 /* One image per synchronous call (slot = WM_SLOT_SYNC, frames == 1: what makeWatermark / detectWatermark are in the
  * reference, Watermark.cpp:156-172,234-250) runs as ONE launch whose tiles stay in LDS when the shape allows it (p = 3,

@@ -440,6 +440,10 @@ HandOver handover_of(const wm_ctx* ctx, const Slot& s, int stride)
 int alloc_slots(wm_ctx* ctx, int nslots, int max_frames)
 {
     HIPCHK(ctx, hipSetDevice(ctx->device));
+    // a slot that runs on the caller's stream (wm_set_stream) keeps it across the rebuild, as long as its index still exists: the
+    // ordering against the caller's collectives must not end because a rank tunes rps or reinitialises
+    std::vector<hipStream_t> caller_stream;
+    for (auto& s : ctx->slots) caller_stream.push_back(s.stream != s.own ? s.stream : nullptr);
     for (auto& s : ctx->slots) free_slot(s);
     ctx->slots.clear();
     ctx->nslots = nslots; ctx->max_frames = max_frames;
@@ -529,7 +533,9 @@ int alloc_slots(wm_ctx* ctx, int nslots, int max_frames)
             if (!want_stamps) s.fz.dbg &= ~3;  // bits 0, 1 give wrong results (timing experiments): only with the stamps switched on
         }
     }
-    HIPCHK(ctx, hipDeviceSynchronize());
+    HIPCHK(ctx, hipDeviceSynchronize());  // (the scratch is cleared before any stream, the caller's included, can reach it)
+    for (size_t i = 0; i < ctx->slots.size() && i < caller_stream.size(); ++i)
+        if (caller_stream[i]) ctx->slots[i].stream = caller_stream[i];
     if (ctx->handover) {
         const int rc = ho_alloc(ctx);
         if (rc != WM_OK) { ctx->handover = 0; return rc; }
@@ -977,6 +983,21 @@ int do_sync(wm_ctx* ctx, Slot& s)
     return deliver(s);
 }
 
+// in front of a rebuild of the slots (wm_configure, wm_set_rows_per_segment, wm_reinit): every slot's queued results reach the
+// callers' pointers as wm_sync would deliver them, before the records are freed.  An unsolvable frame is in the statuses, not in the
+// return value (as with wm_set_stream); an error is returned and nothing is rebuilt
+int sync_all_slots(wm_ctx* ctx)
+{
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    for (auto& s : ctx->slots) {
+        if (!s.stream) continue;
+        const int rc = do_sync(ctx, s);
+        if (rc < 0) return rc;
+    }
+    HIPCHK(ctx, hipDeviceSynchronize());
+    return WM_OK;
+}
+
 // the back half of a call behind its launches: their check, the records queued for delivery, and the wait of a synchronous call
 int finish_call(wm_ctx* ctx, Slot& s, int slot, int frames, int per_frame, bool keep, float* value_out, int* status_out, float* coef_out = nullptr)
 {
@@ -1027,6 +1048,7 @@ int wm_clone(const wm_ctx* src, wm_ctx** out)
     std::unique_ptr<wm_ctx> ctx(new wm_ctx);
     ctx->device = src->device; ctx->rows = src->rows; ctx->cols = src->cols; ctx->p = src->p; ctx->psnr = src->psnr;
     ctx->sF = src->sF; ctx->w = src->w; ctx->rps_override = src->rps_override; ctx->fused_mode = src->fused_mode;
+    ctx->handover = src->handover; ctx->checked_handover = src->checked_handover;  // (alloc_slots allocates the hand-over arrays)
     ctx->band_lo = src->band_lo; ctx->band_hi = src->band_hi; ctx->band_rows_global = src->band_rows_global;
     int rc = alloc_slots(ctx.get(), src->nslots, src->max_frames);
     if (rc != WM_OK) return rc;
@@ -1039,8 +1061,7 @@ int wm_reinit(wm_ctx* ctx, int rows, int cols, const float* w_rowmajor)
     if (!ctx || !w_rowmajor) return WM_ERR_BAD_ARG;
     int rc = check_params(rows, cols, ctx->p, ctx->psnr);
     if (rc != WM_OK) return fail(ctx, rc, "bad dimensions");
-    for (auto& s : ctx->slots)
-        if (s.stream) (void)hipStreamSynchronize(s.stream);
+    if ((rc = sync_all_slots(ctx)) != WM_OK) return rc;
     // commit the new shape only once the new W is on the device; a band configuration belongs to the old shape
     const int old_rows = ctx->rows, old_cols = ctx->cols;
     ctx->rows = rows; ctx->cols = cols;
@@ -1070,8 +1091,8 @@ void wm_destroy(wm_ctx* ctx)
 int wm_configure(wm_ctx* ctx, int nslots, int max_frames)
 {
     if (!ctx || nslots < 1 || nslots > 64 || max_frames < 1 || max_frames > RES_CAP) return fail(ctx, WM_ERR_BAD_ARG, "wm_configure: bad arguments");
-    (void)hipSetDevice(ctx->device);
-    (void)hipDeviceSynchronize();
+    const int rc = sync_all_slots(ctx);
+    if (rc != WM_OK) return rc;
     return alloc_slots(ctx, nslots, max_frames);
 }
 
@@ -1153,9 +1174,9 @@ int wm_fused_gram(wm_ctx* ctx, double* out44)
 int wm_set_rows_per_segment(wm_ctx* ctx, int rps)
 {
     if (!ctx || rps < 0 || rps > 4096) return fail(ctx, WM_ERR_BAD_ARG, "wm_set_rows_per_segment: bad value");
+    const int rc = sync_all_slots(ctx);
+    if (rc != WM_OK) return rc;
     ctx->rps_override = rps;
-    (void)hipSetDevice(ctx->device);
-    (void)hipDeviceSynchronize();
     return alloc_slots(ctx, ctx->nslots, ctx->max_frames);
 }
 
