@@ -131,6 +131,10 @@ private:
     int device_ = 0;
 };
 
+// What Watermark::quality measures per channel (wm.h wm_quality): the mean squared error, its PSNR against peak 255, the mean SSIM
+// index over the whole windows (NaN below 11 x 11) and the largest absolute difference
+struct Quality { float mse, psnr, ssim, maxAbs; };
+
 }  // namespace wm
 
 // A bank of watermark keys on one device (wm.h wm_keys_*): what Watermark::detectWatermarkKeys scores one image against.
@@ -301,6 +305,20 @@ public:
         const int rc = wm_detect16(ctx, (int)maskType, &py, bits, msbAligned ? 1 : 0, &corr, nullptr, WM_SLOT_SYNC);
         if (rc < 0) fail(rc, "detectWatermark16");
         return corr;
+    }
+    // PSNR and SSIM of `test` (a marked copy) against `ref` (its base), measured on the device (wm.h wm_quality): one entry per
+    // channel.  The images are f32 or u8, independently, with the engine's shape and the same channel count (1 or 3)
+    std::vector<wm::Quality> quality(const wm::Image& ref, const wm::Image& test) const
+    {
+        const wm_plane pr = ref.plane(), pt = test.plane();
+        const size_t ch = (size_t)(ref.channels() > 0 ? ref.channels() : 0);
+        std::vector<float> q(ch * WM_QUALITY_NVALS, 0.0f);
+        const int rc = wm_quality(ctx, &pr, &pt, 0, 0, q.data(), nullptr, WM_SLOT_SYNC);
+        if (rc < 0) fail(rc, "quality");
+        std::vector<wm::Quality> out(ch);
+        for (size_t c = 0; c < ch; ++c)
+            out[c] = wm::Quality{q[3 * c], (float)wm_psnr_from_mse((double)q[3 * c], 255.0), q[3 * c + 1], q[3 * c + 2]};
+        return out;
     }
     // detectWatermark of one grey image against every key of `keys` in one call (wm.h wm_detect_keys): score k is what
     // detectWatermark returns with key k as W (0.0f for every key when the prediction system is not solvable)

@@ -686,6 +686,63 @@ int wm_embed16(wm_ctx* ctx, int mask, const wm_plane* in16, const wm_plane* out1
  * wm_detect(wm_unpack16(img16)) bit for bit.  Grey only; masks, band mode, result records and X as for wm_embed16. */
 int wm_detect16(wm_ctx* ctx, int mask, const wm_plane* img16, int bits, int msb_aligned, float* corr_out, int* status_out, int slot);
 
+/* ---- Quality of a marked copy: PSNR and SSIM against its base, measured on the device ---------------------------------------------
+ * The one quality knob is psnr, and wm_embed scales `a` so that the UNCLAMPED float term a m W has exactly that PSNR.  What a
+ * recipient gets has also been through the clamp to [0, 255], truncation to u8 (wm_pack_rgb8, u8 planes) or rounding to d bits
+ * (wm_pack16), tiles with sign 0 (wm_embed_signs) and K keys with K strengths (wm_embed_keys).  wm_quality measures what a call
+ * actually achieved: the mean squared error, the SSIM index of Wang et al. (2004) and the largest difference of `test` against
+ * `ref`, per (frame, channel) and, in sums_dev, per tile.  Every difference, square, product and sum below is f64.
+ *
+ * d = (double)ref - (double)test per sample (u8 samples convert exactly).
+ * Sums over a tile's pixels: sse = sum d^2;  max|d|;  npix = the tile's pixel count.
+ * SSIM: an 11 x 11 window with weights g[i] g[j], g[i] = exp(-(i - 5)^2 / 4.5) divided by the sum of the eleven values (f64, formed
+ * on the host).  L = 255 (the engine's scale is [0, 255] everywhere), C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2.  Only windows that lie
+ * wholly inside the plane are evaluated -- no padding --, so the window centres are rows 5 .. rows - 6 and columns 5 .. cols - 6.
+ * Per window, with E[.] the weighted mean over the window, x = ref and y = test:
+ *     mx = E[x], my = E[y];  vx = E[x^2] - mx^2, vy = E[y^2] - my^2, cxy = E[x y] - mx my;
+ *     s = ((2 mx my + C1) (2 cxy + C2)) / ((mx^2 + my^2 + C1) (vx + vy + C2))
+ * evaluated separably (rows, then columns) with the taps i and 10 - i added before they are weighted.  A window belongs to the tile
+ * that holds its centre pixel: ssim_sum = sum s, nwin = the tile's window count.
+ * Tile geometry is wm_tiles_shape's, unchanged; tile_rows == tile_cols == 0 means ONE tile per plane (ny = nx = 1); any other tile
+ * shape must pass wm_tiles_shape.
+ *
+ * sums_dev [frames][channels][ny][nx][WM_QUALITY_NSUMS] is a DEVICE f64 array on the context's device and may be NULL:
+ * {sse, npix, ssim_sum, nwin, max|d|} per tile, written on the slot's stream and valid once wm_sync(ctx, slot) has returned.  The
+ * sums ADD over tiles (max for the fifth).  q_out [frames][channels][WM_QUALITY_NVALS] is a HOST f32 array written by wm_sync and may
+ * be NULL (not both): {(float)(sse / npix), (float)(ssim_sum / nwin), (float)max|d|} over the whole plane, the tile sums added in
+ * ascending tile index (max for the third).  PSNR = wm_psnr_from_mse(mse, 255).
+ *   - A plane with rows < 11 or cols < 11 has no window: nwin = 0 and its ssim is 0 / 0 = NaN, the zero rule of this header; its mse
+ *     and max|d| are unaffected.  Planes that hold non-finite samples give unspecified values; the call completes.
+ *   - ref and test are f32 or u8, independently (all four combinations), 1 or 3 planar channels, equal between the two, equal frame
+ *     counts within max_frames, any base address, pitch and strides, WM_MEM_DEVICE or WM_MEM_HOST.  test (only) may be
+ *     WM_MEM_SLOT_OUT: the slot's last embed output, 1 or 3 channels, when its channels, frames and dtype are the plane's (the rule of
+ *     wm_pack_rgb8 and wm_pack16).  The planes may overlap or be the same plane: both are only read.  The context supplies shape,
+ *     device and slots; its W, p and psnr are not used.
+ *   - An ENQUEUE on the slot (WM_SLOT_SYNC: slot 0, waits); it may share a slot with any other call in any order.  It writes no plane
+ *     and changes nothing about the slot: not what WM_MEM_SLOT_OUT names, and it neither leaves nor ends a hand-over, checked or
+ *     promised.  Never takes the fused kernels; refused in band mode.  Its kernels are not in the wm_prof_* list.
+ *   - frames * channels * 3 result records count against the slot's 4096 (WM_ERR_BUSY) when q_out is non-null; none otherwise.
+ *   - Scratch (frames * channels * ceil(rows / rps) * ceil(cols / 4) * 24 bytes of records, rps = the largest divisor of tile_rows in
+ *     8 .. 48, 48 for one tile per plane -- 1.0 to 1.6 MB per 4K plane --, a few per cent more for the folds, and the tile sums when sums_dev
+ *     is NULL) is kept per slot and grown on demand (WM_ERR_ALLOC when it does not fit): the FIRST call on a slot that needs more of
+ *     it than any call before reallocates it, which waits for the whole device, the other slots' streams included.  Later calls only
+ *     enqueue.
+ *   - WM_ERR_BAD_ARG, before any device work, looked at in this order: a null ctx or plane, or q_out and sums_dev both NULL; shapes
+ *     (rows x cols of both planes must be the context's); each plane's own rules; channel counts that differ; frame counts that differ
+ *     (and frames * channels beyond 65535, the launch grid); the tile shape; band mode; the slot; a WM_MEM_SLOT_OUT test plane that
+ *     does not match the slot's last embed output.  Record room is looked at after these.
+ * Bits: a (frame, channel)'s sums do not depend on the batch it arrives in or on repetition (segments follow from tile_rows alone;
+ * every fold adds in a fixed order, no atomics).
+ *
+ * wm_psnr_from_mse: 10 log10(peak^2 / mse).  +inf for mse == 0; NaN for a negative or NaN mse and for peak <= 0 (or NaN).  Pure host
+ * arithmetic; it touches no device. */
+#define WM_QUALITY_NVALS 3  /* per (frame, channel), HOST f32, delivered by wm_sync: {mse, ssim, max|d|} */
+#define WM_QUALITY_NSUMS 5  /* per (frame, channel, tile), DEVICE f64: {sse, npix, ssim_sum, nwin, max|d|} */
+int wm_quality(wm_ctx* ctx, const wm_plane* ref, const wm_plane* test, int tile_rows, int tile_cols,
+               float* q_out /* HOST [frames][channels][3], may be NULL */,
+               double* sums_dev /* DEVICE [frames][channels][ny][nx][5], may be NULL */, int slot);
+double wm_psnr_from_mse(double mse, double peak);
+
 /* Building blocks exposed for parity tests (the reference keeps them private):
  * computeCustomMask / computePredictionErrorMask (Watermark.cpp:96-114,176-218).
  * mask_out / e_out: f32 device planes [rows,cols] (e_out may be NULL; ignored for NVF).

@@ -8,7 +8,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "watermarking-gpu_amd", "csrc")
-files = [a for a in sys.argv[1:] if a.endswith(".hip")] or ["wm_k_gram.hip", "wm_k_embed.hip", "wm_k_detect.hip", "wm_k_fused.hip", "wm_k_detect_keys.hip", "wm_k_embed_keys.hip", "wm_k_detect_offsets.hip", "wm_k_detect_tiles.hip", "wm_k_detect_keys_tiles.hip", "wm_k_bits.hip", "wm_k_embed_signs_multi.hip", "wm_k_convert.hip", "wm_k_convert16.hip", "wm_k_select.hip"]
+files = [a for a in sys.argv[1:] if a.endswith(".hip")] or ["wm_k_gram.hip", "wm_k_embed.hip", "wm_k_detect.hip", "wm_k_fused.hip", "wm_k_detect_keys.hip", "wm_k_embed_keys.hip", "wm_k_detect_offsets.hip", "wm_k_detect_tiles.hip", "wm_k_detect_keys_tiles.hip", "wm_k_bits.hip", "wm_k_embed_signs_multi.hip", "wm_k_convert.hip", "wm_k_convert16.hip", "wm_k_select.hip", "wm_k_quality.hip"]
 flags = [a for a in sys.argv[1:] if a.startswith("-D")]
 only = "--spills-only" in sys.argv
 bad = 0

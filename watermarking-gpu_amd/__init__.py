@@ -110,6 +110,8 @@ ABI = [
     ("wm_pack16", C.c_int, [_ctx_p, _P(wm_plane), _P(wm_plane), C.c_int, C.c_int, C.c_int]),
     ("wm_embed16", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), _P(wm_plane), C.c_int, C.c_int, _P(C.c_float), _P(C.c_int), C.c_int]),
     ("wm_detect16", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), C.c_int, C.c_int, _P(C.c_float), _P(C.c_int), C.c_int]),
+    ("wm_quality", C.c_int, [_ctx_p, _P(wm_plane), _P(wm_plane), C.c_int, C.c_int, _P(C.c_float), C.c_void_p, C.c_int]),
+    ("wm_psnr_from_mse", C.c_double, [C.c_double, C.c_double]),
     ("wm_compute_mask", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), _P(wm_plane), _P(wm_plane), _P(C.c_float), _P(C.c_int), C.c_int]),
     ("wm_gram", C.c_int, [_ctx_p, _P(wm_plane), _P(C.c_double), C.c_int]),
     ("wm_band_configure", C.c_int, [_ctx_p, C.c_int, C.c_int, C.c_longlong]),
@@ -264,6 +266,38 @@ def plane_any(t, channels=1):
         raise RuntimeError(f"bad shape {tuple(shape)} / strides {tuple(strides)} for channels={channels}")
     frames, fstride = (shape[0], strides[0]) if nd == base_nd + 1 else (1, 0)
     return wm_plane(ptr, shape[-2], shape[-1], channels, dt, mem, frames, strides[-2], strides[-3] if channels > 1 else 0, fstride)
+
+
+WM_QUALITY_NVALS, WM_QUALITY_NSUMS = 3, 5
+
+
+def psnr_from_mse(mse, peak=255.0):
+    """wm.h wm_psnr_from_mse: 10 log10(peak^2 / mse); +inf for mse == 0, NaN for a negative or NaN mse or peak <= 0"""
+    return lib().wm_psnr_from_mse(float(mse), float(peak))
+
+
+def plane_u8f32(t, channels=1):
+    """wm_plane view of a float32 or uint8 row-major array for wm_quality: [R,C], [3,R,C] (channels=3) or a batch of either.  A GPU
+    torch tensor is a device plane (plane_of); a numpy array or a CPU torch tensor is a WM_MEM_HOST plane (it must stay alive until
+    the slot is synced)"""
+    if isinstance(t, np.ndarray):
+        if t.dtype not in (np.float32, np.uint8) or any(st % t.itemsize for st in t.strides):
+            raise RuntimeError(f"unsupported numpy array {t.dtype} / strides {t.strides}")
+        dt = WM_F32 if t.dtype == np.float32 else WM_U8
+        shape, strides, ptr = t.shape, [st // t.itemsize for st in t.strides], t.ctypes.data
+    else:
+        import torch
+        if t.is_cuda:
+            return plane_of(t, channels)
+        if t.dtype not in (torch.float32, torch.uint8):
+            raise RuntimeError(f"unsupported dtype {t.dtype}")
+        dt = WM_F32 if t.dtype == torch.float32 else WM_U8
+        shape, strides, ptr = tuple(t.shape), list(t.stride()), t.data_ptr()
+    nd, base_nd = len(shape), 2 if channels == 1 else 3
+    if nd not in (base_nd, base_nd + 1) or strides[-1] != 1 or (channels > 1 and shape[-3] != channels):
+        raise RuntimeError(f"bad shape {tuple(shape)} / strides {tuple(strides)} for channels={channels}")
+    frames, fstride = (shape[0], strides[0]) if nd == base_nd + 1 else (1, 0)
+    return wm_plane(ptr, shape[-2], shape[-1], channels, dt, WM_MEM_HOST, frames, strides[-2], strides[-3] if channels > 1 else 0, fstride)
 
 
 class KeySet:
@@ -851,6 +885,47 @@ class Watermark:
         torch.cuda.current_stream().synchronize()
         self.detect16_async(pimg, bits, maskType, WM_SLOT_SYNC, msbAligned, corr)
         return corr[0] if len(samples.shape) == 2 else list(corr)
+
+    # -- quality of a marked copy (wm.h wm_quality) ---------------------------------------------------------------------------
+    def quality(self, ref, test, tile=None, sums=False, channels=1):
+        """PSNR and SSIM of `test` against `ref`, measured on the device (wm.h wm_quality): (mse, psnr, ssim, maxabs), float64 numpy
+        arrays [frames, channels]; psnr = psnr_from_mse(mse, 255), ssim is NaN for planes below 11 x 11.  ref / test: float32 or uint8
+        arrays -- GPU tensors, CPU tensors or numpy arrays (staged), or wm_planes (test may be a WM_MEM_SLOT_OUT plane) --, [R,C],
+        [3,R,C] with channels=3, or a batch of either.  tile=(tile_rows, tile_cols) chooses the tile grid of the sums (default: one
+        tile per plane); sums=True appends them: float64 [frames, channels, ny, nx, 5] = {sse, npix, ssim_sum, nwin, max|d|}"""
+        import torch
+        pr, pt = self._as_plane_u8f32(ref, channels), self._as_plane_u8f32(test, channels)
+        F, ch = pr.frames, pr.channels
+        tile_rows, tile_cols = tile if tile is not None else (0, 0)
+        ny, nx = self.tiles_shape(self.rows, self.cols, tile_rows, tile_cols) if tile is not None else (1, 1)
+        q = np.zeros((F, ch, WM_QUALITY_NVALS), np.float32)
+        sums_t = torch.empty((F, ch, ny, nx, WM_QUALITY_NSUMS), dtype=torch.float64, device=self._dev()) if sums else None
+        torch.cuda.current_stream().synchronize()
+        self.quality_async(pr, pt, WM_SLOT_SYNC, q, tile_rows, tile_cols, sums_t)
+        mse = q[..., 0].astype(np.float64)
+        psnr = np.array([[psnr_from_mse(v, 255.0) for v in row] for row in mse], np.float64).reshape(F, ch)
+        out = (mse, psnr, q[..., 1].astype(np.float64), q[..., 2].astype(np.float64))
+        return out + (sums_t.cpu().numpy(),) if sums else out
+
+    @staticmethod
+    def _as_plane_u8f32(t, channels):
+        return t if isinstance(t, wm_plane) else plane_u8f32(t, channels)
+
+    def quality_async(self, ref, test, slot, q_out, tile_rows=0, tile_cols=0, sums_t=None, channels=1):
+        """wm_quality enqueued on `slot`: q_out (frames * channels * 3 floats: a ctypes array or a C-contiguous float32 numpy array,
+        may be None) is written by sync(slot); sums_t (a contiguous float64 GPU tensor of frames * channels * ny * nx * 5 elements,
+        may be None) on the slot's stream, valid after sync(slot).  Host planes must stay alive until then"""
+        pr, pt = self._as_plane_u8f32(ref, channels), self._as_plane_u8f32(test, channels)
+        psums = None
+        if sums_t is not None:
+            import torch
+            ny, nx = self.tiles_shape(self.rows, self.cols, tile_rows, tile_cols) if (tile_rows or tile_cols) else (1, 1)
+            n = pr.frames * pr.channels * ny * nx * WM_QUALITY_NSUMS
+            if not (sums_t.is_cuda and sums_t.dtype == torch.float64 and sums_t.is_contiguous() and sums_t.numel() == n):
+                raise RuntimeError(f"sums_t must be a contiguous float64 GPU tensor of {n} elements")
+            psums = C.c_void_p(sums_t.data_ptr())
+        q_out, _ = self._scalars_out(q_out, None)
+        self._chk(lib().wm_quality(self._ctx, C.byref(pr), C.byref(pt), tile_rows, tile_cols, q_out, psums, slot))
 
     # north_star aliases
     embed = makeWatermark

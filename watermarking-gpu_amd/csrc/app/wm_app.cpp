@@ -138,6 +138,20 @@ static int testForImage(const INIReader& inir, const int p, const float psnr, co
         std::snprintf(line, sizeof line, "Correlation [%s]: %.16f\n", r.name, r.correlation);
         cout << line;
     }
+    // optional key [options] report_quality (not in the reference's settings.ini; default false leaves the output as it was): what
+    // the embed actually achieved, measured on the device -- the unquantised marked RGB image against the RGB input, the three
+    // channels pooled as the mean of their mse values and the mean of their ssim values
+    if (inir.GetBoolean("options", "report_quality", false)) {
+        for (const MaskRun& r : runs) {
+            const std::vector<wm::Quality> q = engine.quality(rgbImage, r.marked);
+            double mse = 0.0, ssim = 0.0;
+            for (const wm::Quality& c : q) { mse += (double)c.mse; ssim += (double)c.ssim; }
+            mse /= (double)q.size(); ssim /= (double)q.size();
+            char line[96];
+            std::snprintf(line, sizeof line, "Quality [%s]: PSNR %.4f SSIM %.6f\n", r.name, wm_psnr_from_mse(mse, 255.0), ssim);
+            cout << line;
+        }
+    }
 
     if (inir.GetBoolean("options", "save_watermarked_files_to_disk", false)) {  // main.cpp:229-240 (.as(u8): truncation)
         cout << "\nSaving watermarked files to disk...\n";

@@ -93,6 +93,14 @@ int main(int argc, char** argv)
     for (size_t i = 0; i < yh.size(); ++i) mse += ((double)yh[i] - x[i]) * ((double)yh[i] - x[i]);
     const double psnr = 10.0 * std::log10(255.0 * 255.0 / (mse / (double)yh.size()));
     CHECK(std::fabs(psnr - 40.0) < 0.2, "the embed hits the requested PSNR");
+    {
+        // the same figure from the device (wm_quality): the host loop's mse to f32 rounding, an SSIM in (0.9, 1), and 1 for a copy
+        const std::vector<wm::Quality> q = wm1.quality(gray, y_me), same = wm1.quality(gray, gray);
+        const bool measured = q.size() == 1 && std::fabs((double)q[0].mse - mse / (double)yh.size()) <= 1e-6 * (double)q[0].mse &&
+                              std::fabs((double)q[0].psnr - psnr) < 1e-4 && q[0].ssim > 0.9f && q[0].ssim < 1.0f && q[0].maxAbs > 0.0f;
+        const bool identical = same.size() == 1 && same[0].mse == 0.0f && std::isinf(same[0].psnr) && same[0].ssim == 1.0f && same[0].maxAbs == 0.0f;
+        CHECK(measured && identical, "quality: the device's mse, PSNR and SSIM of the marked image; a copy scores mse 0, SSIM 1");
+    }
 
     // ---- RGB base: the same a*u is added to the three channels (main.cpp:169-190)
     std::vector<float> rgb((size_t)3 * R * C);

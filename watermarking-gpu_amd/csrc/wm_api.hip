@@ -14,6 +14,7 @@
 #include <cstring>
 #include <deque>
 #include <fstream>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <optional>
@@ -172,6 +173,9 @@ struct Slot {
     // dense in staged_layout's form (grown on demand)
     void* x16 = nullptr; size_t x16_bytes = 0;
     void* y16 = nullptr; size_t y16_bytes = 0;
+    // wm_quality: k_quality's records [planes][nsegs][ngroups][3] f64 and the folds' [planes][nsegs][nx][3], then the tile sums [planes][ny * nx][5] f64 of a call that
+    // passes no sums_dev (grown on demand)
+    void* qual_scr = nullptr; size_t qual_scr_bytes = 0;
 };
 
 struct ProfRec { int kid; hipEvent_t a, b; bool first; };  // first: the sweep's first launch (counts the call)
@@ -375,7 +379,7 @@ void free_slot(Slot& s)
     (void)hipFree(s.st_in); (void)hipFree(s.st_base); (void)hipFree(s.st_out); (void)hipFree(s.fz_block); (void)hipFree(s.d_ho); (void)hipFree(s.d_hoseam);
     (void)hipFree(s.d_hodig); (void)hipFree(s.keys_part); (void)hipFree(s.ekeys_part); (void)hipFree(s.tiles_rec); (void)hipFree(s.keys_tiles_rec);
     if (s.tab_host) (void)hipHostFree(s.tab_host);
-    (void)hipFree(s.tab_dev); (void)hipFree(s.bits_scr); (void)hipFree(s.x16); (void)hipFree(s.y16);
+    (void)hipFree(s.tab_dev); (void)hipFree(s.bits_scr); (void)hipFree(s.x16); (void)hipFree(s.y16); (void)hipFree(s.qual_scr);
     s = Slot();
 }
 
@@ -2632,6 +2636,62 @@ int wm_detect16(wm_ctx* ctx, int mask, const wm_plane* img16, int bits, int msb_
     if ((rc = wm_unpack16(ctx, img16, bits, msb_aligned, &X, q)) != WM_OK) return rc;
     if ((rc = wm_detect(ctx, mask, &X, corr_out, status_out, q)) != WM_OK) return rc;
     return slot == WM_SLOT_SYNC ? do_sync(ctx, s) : WM_OK;
+}
+
+// ---- wm_quality: PSNR and SSIM of a marked copy against its base (wm_k_quality.hip).  Both planes are only read: nothing of the slot
+// changes but its staging buffers (a host ref is staged in st_in, a host test in st_base -- never in st_out, which may hold the plane
+// WM_MEM_SLOT_OUT names), its quality scratch and, with q_out, its result records.  The kernels are launched outside any ProfScope
+double wm_psnr_from_mse(double mse, double peak)
+{
+    if (!(mse >= 0.0) || !(peak > 0.0)) return std::numeric_limits<double>::quiet_NaN();
+    if (mse == 0.0) return std::numeric_limits<double>::infinity();
+    return 10.0 * std::log10(peak * peak / mse);
+}
+
+// what the slot's last output must be for a WM_MEM_SLOT_OUT test plane: an embed output of the operand's channels, frames and dtype
+static int slot_out_any(wm_ctx* ctx, const Slot& s, const wm_plane* pl)
+{
+    if (s.last_out_frames == 0 || s.last_out.channels != pl->channels || pl->frames != s.last_out_frames || pl->dtype != s.last_out_dtype)
+        return fail(ctx, WM_ERR_BAD_ARG, "WM_MEM_SLOT_OUT: no matching embed output on this slot (channels / frames / dtype must equal the last wm_embed's)");
+    return WM_OK;
+}
+
+int wm_quality(wm_ctx* ctx, const wm_plane* ref, const wm_plane* test, int tile_rows, int tile_cols, float* q_out, double* sums_dev, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    if (!ref || !ref->data || plane_null(test)) return fail(ctx, WM_ERR_BAD_ARG, "wm_quality: null plane");
+    if (!q_out && !sums_dev) return fail(ctx, WM_ERR_BAD_ARG, "wm_quality: q_out and sums_dev are both null");
+    int rc;
+    if ((rc = check_shape(ctx, ref->rows, ref->cols, "ref")) != WM_OK || (rc = check_shape(ctx, test->rows, test->cols, "test")) != WM_OK) return rc;
+    if ((rc = check_plane(ctx, ref, 0, true, "ref")) != WM_OK || (rc = check_plane(ctx, test, 0, true, "test", true)) != WM_OK) return rc;
+    if (ref->channels != test->channels) return fail(ctx, WM_ERR_BAD_ARG, "wm_quality: channel count mismatch");
+    if (ref->frames != test->frames) return fail(ctx, WM_ERR_BAD_ARG, "wm_quality: frame count mismatch");
+    const int frames = ref->frames, channels = ref->channels, planes = frames * channels;
+    if (!quality_grid_fits(planes)) return fail(ctx, WM_ERR_BAD_ARG, "wm_quality: frames x channels beyond the launch grid");
+    TileShape ts{0, 0, 1, 1};  // tile_rows == tile_cols == 0: one tile per plane
+    if ((tile_rows != 0 || tile_cols != 0) && (rc = tiles_checked(ctx, "wm_quality", tile_rows, tile_cols, &ts)) != WM_OK) return rc;
+    if ((rc = refuse_band(ctx, "wm_quality")) != WM_OK) return rc;
+    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
+    if (test->mem == WM_MEM_SLOT_OUT && (rc = slot_out_any(ctx, s, test)) != WM_OK) return rc;
+    if (q_out && (rc = check_res_room(ctx, s, (long long)planes * WM_QUALITY_NVALS, "channels x 3")) != WM_OK) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    PlaneDesc xd, yd;
+    if ((rc = resolve_plane(ctx, s, ref, &s.st_in, &s.st_in_bytes, &xd)) != WM_OK) return rc;
+    if (test->mem == WM_MEM_SLOT_OUT) yd = s.last_out;
+    else if ((rc = resolve_plane(ctx, s, test, &s.st_base, &s.st_base_bytes, &yd)) != WM_OK) return rc;
+    const QualityGeom q = quality_geom(ctx->rows, ctx->cols, channels, ts.th);
+    const size_t rec_bytes = round256(quality_rec_bytes(q, ts, planes));
+    const size_t sums_bytes = sums_dev ? 0 : (size_t)planes * ts.ny * ts.nx * WM_QUALITY_NSUMS * sizeof(double);
+    if ((rc = ensure(ctx, &s.qual_scr, &s.qual_scr_bytes, rec_bytes + sums_bytes, WM_ERR_ALLOC)) != WM_OK) return rc;
+    double* sums = sums_dev ? sums_dev : (double*)((char*)s.qual_scr + rec_bytes);
+    // the Gaussian of Wang et al.: g[i] = exp(-(i - 5)^2 / 4.5) over the sum of the eleven values, f64, formed here once per call
+    double g[11], gsum = 0.0;
+    for (int i = 0; i < 11; ++i) { g[i] = std::exp(-(double)((i - 5) * (i - 5)) / 4.5); gsum += g[i]; }
+    QualityWeights w;
+    for (int i = 0; i < 6; ++i) w.g[i] = g[i] / gsum;
+    launch_quality(s.stream, q, w, ts, planes, xd, yd, (double*)s.qual_scr, sums, q_out ? s.d_res + s.res_used : nullptr);
+    return finish_call(ctx, s, slot, q_out ? frames : 0, q_out ? channels * WM_QUALITY_NVALS : 0, false, q_out, nullptr);
 }
 
 int wm_gram(wm_ctx* ctx, const wm_plane* img, double* gram_out, int slot)

@@ -336,6 +336,27 @@ void launch_pack_rgb8(hipStream_t s, int rows, int cols, int frames, const Plane
 // k_in / k_out: wm_depth_scale's constants of `bits`
 void launch_unpack16(hipStream_t s, int rows, int cols, int frames, const PlaneDesc& src, const PlaneDesc& out, int bits, int msb_aligned, float k_in);
 void launch_pack16(hipStream_t s, int rows, int cols, int frames, const PlaneDesc& src, const PlaneDesc& out, int bits, int msb_aligned, float k_out);
+// PSNR and SSIM of one plane against another (wm_quality, wm_k_quality.hip).  A plane is one (frame, channel) pair, `planes` =
+// frames x channels of them (the grid's z: quality_grid_fits).  k_quality marches strips of 64 columns in segments of rps rows and
+// leaves rec [planes][nsegs][ngroups][3] f64 = {sse, ssim_sum, max|d|} per column group of 4; k_quality_fold_cols and k_quality_fold add
+// each tile's records in a fixed order (per segment and tile column into part [planes][nsegs][nx][3] behind rec, then per tile) into
+// sums [planes][ny][nx][5] = {sse, npix, ssim_sum, nwin, max|d|}; k_quality_total (res non-null) adds a plane's tiles in ascending
+// index and writes res[plane * 3 ..] = {mse, ssim, max|d|}, status 0.  rec: quality_rec_bytes of scratch.  ts: the tile grid,
+// th = tw = 0 with ny = nx = 1 for one tile per plane.  w: the six distinct weights of the 11-tap Gaussian, g[i] = g[10 - i], formed
+// on the host
+struct QualityGeom {
+    int rows, cols, channels;
+    int rps, nsegs, nstrips;  // segments of rps rows (rps divides the tile height), strips of 64 columns
+    int ngroups;              // column groups of 4
+};
+struct QualityWeights {
+    double g[6];
+};
+QualityGeom quality_geom(int rows, int cols, int channels, int tile_rows);
+size_t quality_rec_bytes(const QualityGeom& q, const TileShape& ts, int planes);
+bool quality_grid_fits(int planes);
+void launch_quality(hipStream_t s, const QualityGeom& q, const QualityWeights& w, const TileShape& ts, int planes, const PlaneDesc& x,
+                    const PlaneDesc& y, double* rec, double* sums, OpResult* res);
 // band mode: solve the 8x8 system from all-reduced Gram totals [frames][44]; writes coef / status like k_gram's tail
 void launch_solve_totals(hipStream_t s, int frames, const double* totals, float* coef, int* status);
 // band mode, device-resident exchange (wm_band_*_dev): glue kernels between the sweeps and the caller's collectives
