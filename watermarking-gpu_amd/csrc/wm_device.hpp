@@ -359,9 +359,11 @@ __device__ __forceinline__ WaveJob make_job(const Geom& g, int block_id)
 }
 __device__ __forceinline__ WaveJob make_job(const Geom& g) { return make_job(g, (int)blockIdx.x); }
 
-// the wave's job and group in a grid of `ngroups` blocks per tile (the key groups of k_stats_keys / k_embed_keys, the copy groups of
-// k_embed_signs_multi): block order of k_detect_keys (the groups of one (tile, frame) block are consecutive logical indices of one
-// XCD; inside a group the order is the sweep's own)
+// the wave's job and group in a grid of `ngroups` blocks per tile: the key groups of k_detect_keys / k_detect_keys_tiles / k_stats_keys /
+// k_embed_keys, the copy groups of k_embed_signs_multi, the offset groups of k_detect_offsets (column groups fastest).  Block order:
+// the groups of one (tile, frame) block are consecutive logical indices of one XCD (xcd_remap), so the tile of x -- and base, and
+// whatever W or key rows neighbouring groups share -- is read from memory once and from that XCD's L2 for the other groups; inside
+// a group the order is the sweep's own (make_job's)
 __device__ __forceinline__ WaveJob keys_job(const Geom& g, int ngroups, int& grp)
 {
     const int nb = (int)gridDim.x / ngroups;

@@ -1,7 +1,8 @@
 // wm_embed_march.hpp -- embed_march, the embed sweep's march over one wave's segment, and WM_EMBED_BODY, the kernel body around it:
 // shared by k_embed (wm_k_embed.hip; plain and with the Gram hand-over) and k_embed_signs (wm_k_bits.hip; the tile's sign in the
-// row step), with the launch loop the two have in common and the per-channel loop around it of the multi-copy embed kernels
-// (k_embed_keys, k_embed_signs_multi)
+// row step), with the launch loop the two have in common; and embed_group_march with WM_EMBED_GROUP_BODY / WM_EMBED_GROUP_MARCH, the
+// same march and body on one channel with the copy-dependent tail repeated for a group of copies: shared by the multi-copy embed
+// kernels k_embed_keys (wm_k_embed_keys.hip) and k_embed_signs_multi (wm_k_embed_signs_multi.hip), with their per-channel launch loop
 #pragma once
 #include "wm_march.hpp"
 
@@ -92,6 +93,46 @@ struct SignWalk {
             nxt = p[min(ty + 1, ny - 1) * nx];
         }
         return cur;
+    }
+};
+
+// SignWalk for the G tables of a copy group (k_embed_signs_multi).  The tile column of a lane is fixed over its march and the tile row
+// is wave-uniform (SignWalk's argument, unchanged), so the walks share ty / next_row -- the scalar bookkeeping runs once per row -- and
+// differ in their table and in cur / nxt.  The tables of a frame's copies lie ny * nx apart: one base, one offset per copy.
+template <int G>
+struct SignWalkGroup {
+    const signed char* p;  // this lane's column of the group's first table
+    int off[G];            // table of copy q from there (wave-uniform)
+    int nx, th, ny;
+    int ty, next_row;      // current tile row; first row of the next one (INT_MAX in the last)
+    float cur[G];
+    int nxt[G];            // raw signs of tile row ty + 1 (converted when it becomes current)
+    __device__ __forceinline__ void start(const signed char* table, const int* off_, int th_, int tw, int ny_, int nx_, int c0, int row)
+    {
+        nx = nx_; th = th_; ny = ny_;
+        p = table + min(c0 / tw, nx - 1);
+        ty = min(row / th, ny - 1);
+#pragma unroll
+        for (int q = 0; q < G; ++q) {
+            off[q] = off_[q];
+            cur[q] = (float)p[off[q] + ty * nx];
+            nxt[q] = p[off[q] + min(ty + 1, ny - 1) * nx];
+        }
+        next_row = ty < ny - 1 ? (ty + 1) * th : 0x7fffffff;
+    }
+    // move to row `row` (rows arrive in ascending order); cur[q] is then the sign of copy q there
+    __device__ __forceinline__ void advance(int row)
+    {
+        if (row >= next_row) {  // wave-uniform
+            ++ty;
+            next_row = ty < ny - 1 ? next_row + th : 0x7fffffff;
+            const int r2 = min(ty + 1, ny - 1) * nx;
+#pragma unroll
+            for (int q = 0; q < G; ++q) {
+                cur[q] = (float)nxt[q];
+                nxt[q] = p[off[q] + r2];
+            }
+        }
     }
 };
 
@@ -282,6 +323,169 @@ __device__ __forceinline__ void embed_march(const TX* __restrict__ xf, long long
     else                                                                                                                                 \
         embed_march<TX, TB, NCH, MASK, PAD, VEC, BX, (MASK != 0), HO, SIGNS>(xf, pitch, W, bptr, optr, base, out, g, j, s_row[j.wave],    \
                                                                              s_out[VEC ? 0 : j.wave], c, a, maxe, pass, horec, hoseam, hodig, sg)
+
+// =================================================================================================
+// embed_group_march: the multi-copy embed (k_embed_keys, k_embed_signs_multi) -- embed_march's plain instance (no hand-over) on ONE
+// channel of the base, with the copy-dependent tail of the row step repeated for a compile-time group of G copies.  The image side --
+// the mask m and the base row b -- is formed once per row.  The copy side is one of two:
+//   SIGNS false (k_embed_keys):        a W stream with PW rows in flight and a strength per copy (W, a: arrays of G):
+//                                      y_q = clamp(fmaf(m W_q, a_q, b), 0, 255)
+//   SIGNS true  (k_embed_signs_multi): one W stream and one strength (W, a: scalars) and a sign table per copy (SignWalkGroup:
+//                                      `table` of the group's first copy, toff[q] from there to copy q's, st for the tile geometry):
+//                                      u = m W once, y_q = clamp(fmaf(u s_q, a, b), 0, 255) -- u s exact, as embed_march's SIGNS
+// G, PW and SIGNS are template parameters, not constants of the function: a generic lambda discards an `if constexpr` branch on the
+// former when the march is instantiated, on the latter only when the lambda is called -- by then it has captured what the branch
+// names, and 31 of the 40 k_embed_keys instances compiled to other code.  The W take and the sign advance stand in front of the mask
+// for SIGNS, u = m W inside the mask loop: the order k_embed_signs_multi was written in, and the one its instances compile the same with.
+// =================================================================================================
+template <typename V, int N>
+__device__ __forceinline__ V copy_of(const V (&v)[N], int q) { return v[q]; }  // copy q's W plane / strength: one per copy ...
+template <typename V>
+__device__ __forceinline__ V copy_of(const V& v, int) { return v; }            // ... or one for all
+
+template <typename T, int MASK, int PAD, bool VEC, bool BX, bool EDGE, int G, int PW, bool SIGNS, typename WT, typename AT>
+__device__ __forceinline__ void embed_group_march(const T* __restrict__ xf, long long pitch, const WT& W, const T* __restrict__ bptr,
+                                                  T* const (&optr)[G], int nk, const PlaneDesc& base, const PlaneDesc& out,
+                                                  const Geom& g, const WaveJob& j, float* lds, float* obuf, const float (&c)[8],
+                                                  const AT& a, float maxe, const signed char* table, const int* toff,
+                                                  const SignTable* st)
+{
+    constexpr int NR = MASK == 0 ? 3 : 2 * PAD + 1;
+    constexpr int HR = MASK == 0 ? 1 : PAD;  // halo rows above/below = halo columns left/right
+    constexpr int RG = VEC && NR == 3 ? WM_RING3 : UNROLL;
+    constexpr int NW = SIGNS ? 1 : G;        // W streams
+    static_assert(UNROLL % PW == 0 && RG % PW == 0, "the W prefetch ring must divide the march group");
+    XMarch<T, 1, HR, NR, VEC, PFX, EDGE, false, RG> xm;
+    PMarch<float, VEC, PW> wm_[NW];
+    PMarch<T, VEC, PFW> bm;               // (BX: the base is the grey input, read from the stencil window)
+    const float inv_maxe = 1.0f / maxe;   // (k_embed's m = |e| / max|e|: one reciprocal per wave, then div_by per pixel)
+    const int nout = j.re - j.rs, n = nout + 2 * HR;
+    const int c0 = j.c0s + 4 * j.lane;
+    const bool own = !EDGE || 4 * j.lane >= j.dup;  // duplicate lanes of a shifted last strip: the previous strip stores these pixels
+    xm.start(xf, pitch, g, j, lds, j.rs - HR, n);
+#pragma unroll
+    for (int q = 0; q < NW; ++q) wm_[q].start(copy_of(W, q), g.cols, g.cols, j, j.rs, nout);
+    if (!BX) bm.start(bptr, base.pitch, g.cols, j, j.rs, nout);
+    SignWalkGroup<G> sw;
+    if constexpr (SIGNS) sw.start(table, toff, st->th, st->tw, st->ny, st->nx, c0, j.rs);
+    march_n<2 * HR, RG>(n, [&](int i, auto qc, auto emit) {
+        constexpr int Q = decltype(qc)::value;
+        xm.template step<Q>(i);
+        if (decltype(emit)::value) {
+            const int o = i - 2 * HR;
+            constexpr int SB = (Q + 4 * UNROLL - 2 * HR) % PFW;
+            constexpr int SW = (Q + 4 * UNROLL - 2 * HR) % PW;
+            // ---- the image side, once per row: the mask of the lane's 4 pixels and the base row
+            float4 w;
+            float m[4], u[4];
+            if constexpr (SIGNS) {
+                w = wm_[0].template take<SW>();
+                sw.advance(j.rs + o);
+            }
+            float pr[4] = {0.f, 0.f, 0.f, 0.f};
+            if (MASK == 0) predict4<4>(xm.template row<Q>(0), xm.template row<Q>(1), xm.template row<Q>(2), c, pr);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (MASK == 0) {
+                    const float* mid = xm.template row<Q>(1);
+                    m[k] = div_by(fabsf(mid[4 + k] - pr[k]), maxe, inv_maxe);
+                } else {
+                    m[k] = nvf_value<PAD, 4, Q>(xm, k);
+                }
+                if constexpr (SIGNS) u[k] = m[k] * f4get(w, k);  // Watermark.cpp:169
+            }
+            float4 b;
+            if (BX) {
+                const float* ctr = xm.template row<Q>(HR);  // the output row itself
+                b = make_float4(ctr[4], ctr[5], ctr[6], ctr[7]);
+            } else {
+                b = bm.template take<SB>();
+            }
+            // ---- the copy side: k_embed's u and y for every copy of the group
+#pragma unroll
+            for (int q = 0; q < G; ++q) {
+                if constexpr (!SIGNS) {
+                    w = wm_[q].template take<SW>();
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) u[k] = m[k] * f4get(w, k);  // Watermark.cpp:169
+                }
+                if (q < nk) {  // (wave-uniform: copies beyond the last store nothing)
+                    const float aq = copy_of(a, q);
+                    float us[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        us[k] = u[k];
+                        if constexpr (SIGNS) us[k] *= sw.cur[q];  // times the tile's sign (exact)
+                    }
+                    float4 y;
+                    y.x = fminf(fmaxf(fmaf(us[0], aq, b.x), 0.0f), 255.0f);
+                    y.y = fminf(fmaxf(fmaf(us[1], aq, b.y), 0.0f), 255.0f);
+                    y.z = fminf(fmaxf(fmaf(us[2], aq, b.z), 0.0f), 255.0f);
+                    y.w = fminf(fmaxf(fmaf(us[3], aq, b.w), 0.0f), 255.0f);
+                    if constexpr (VEC) {
+                        if (own) store4<T, true>(optr[q], out.pitch, j.rs + o, c0, g.cols, y);
+                    } else {
+                        store_row_generic<T>(optr[q], out.pitch, j.rs + o, j.c0s, j.lane, g.cols, y, obuf);
+                    }
+                }
+                if constexpr (!SIGNS) wm_[q].template refill<SW>(o);
+            }
+            if (!BX) bm.template refill<SB>(o);
+            if constexpr (SIGNS) wm_[0].template refill<SW>(o);
+        }
+    });
+}
+
+// WM_EMBED_GROUP_BODY: the body of k_embed_keys and k_embed_signs_multi in front of the march -- WM_EMBED_BODY's lines for a group of G
+// copies: the wave's job and copy group (keys_job), the base and the group's out planes, the unsolvable pass-through of every copy, the
+// coefficients.  It expands inside a kernel with the template parameters T, MASK, PAD, VEC, BX and the arguments x, pitch, fstride, base,
+// out (one channel: PlaneDesc::p at that channel, cstride unused), g, coef, status, and leaves j, frame, k0 (the group's first copy), nk
+// (its copies), kq[] (the copy index of slot q), bptr, optr[] and c behind.  Copy (frame, k) is frame index frame * ncopies + k of `out`;
+// slots beyond the last copy (a short last group) repeat it and store nothing.  A macro for WM_EMBED_BODY's reason.
+#define WM_EMBED_GROUP_BODY(G, ngroups, ncopies)                                                                                          \
+    __shared__ __attribute__((aligned(16))) float s_row[WPB][2 * RowBuf<1>::N];                                                          \
+    __shared__ __attribute__((aligned(16))) float s_out[VEC ? 1 : WPB][VEC ? 4 : STRIP]; /* generic path: store re-layout rows */         \
+    int grp;                                                                                                                             \
+    const WaveJob j = keys_job(g, ngroups, grp);                                                                                         \
+    if (!j.valid) return;                                                                                                                \
+    const int frame = j.frame;                                                                                                           \
+    const int k0 = grp * (G);                                                                                                            \
+    const int nk = min((G), (ncopies) - k0);                                                                                             \
+    const T* bptr = static_cast<const T*>(base.p) + (long long)frame * base.fstride;                                                     \
+    T* optr[G];                                                                                                                          \
+    int kq[G];                                                                                                                           \
+    _Pragma("unroll") for (int q = 0; q < (G); ++q) {                                                                                    \
+        kq[q] = min(k0 + q, (ncopies) - 1);                                                                                              \
+        optr[q] = static_cast<T*>(const_cast<void*>(out.p)) + ((long long)frame * (ncopies) + kq[q]) * out.fstride;                      \
+    }                                                                                                                                    \
+    if (MASK == 0 && status[frame] != 0) {                                                                                               \
+        /* unsolvable: every copy = base bit-exact (Watermark.cpp:164-165) */                                                            \
+        const int c0 = j.c0s + 4 * j.lane;                                                                                               \
+        _Pragma("unroll") for (int q = 0; q < (G); ++q) {                                                                                \
+            if (q >= nk) break;                                                                                                          \
+            for (int r = j.rs; r < j.re; ++r) {                                                                                          \
+                const T* rb = bptr + (long long)r * base.pitch;                                                                          \
+                T* ro = optr[q] + (long long)r * out.pitch;                                                                              \
+                for (int k = 0; k < 4; ++k)                                                                                              \
+                    if (c0 + k < g.cols) ro[c0 + k] = rb[c0 + k];                                                                        \
+            }                                                                                                                            \
+        }                                                                                                                                \
+        return;                                                                                                                          \
+    }                                                                                                                                    \
+    float c[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};                                                                               \
+    if (MASK == 0) {                                                                                                                     \
+        _Pragma("unroll") for (int k = 0; k < 8; ++k) c[k] = coef[frame * 8 + k];                                                        \
+    }                                                                                                                                    \
+    (void)0
+// ... and behind the kernel's own lines (W, a, maxe, xf; table, toff, st as embed_group_march takes them: the sign tables of SIGNS,
+// null without): the choice between the edge and the no-edge instance
+#define WM_EMBED_GROUP_MARCH(G, PW, SIGNS, W, a, maxe, table, toff, st)                                                                      \
+    if (MASK != 0 || strip_on_edge<VEC>(g, j))                                                                                           \
+        embed_group_march<T, MASK, PAD, VEC, BX, true, G, PW, SIGNS>(xf, pitch, W, bptr, optr, nk, base, out, g, j, s_row[j.wave],       \
+                                                                     s_out[VEC ? 0 : j.wave], c, a, maxe, table, toff, st);              \
+    else                                                                                                                                 \
+        embed_group_march<T, MASK, PAD, VEC, BX, (MASK != 0), G, PW, SIGNS>(xf, pitch, W, bptr, optr, nk, base, out, g, j, s_row[j.wave], \
+                                                                            s_out[VEC ? 0 : j.wave], c, a, maxe, table, toff, st)
 
 // ---- launch: what launch_embed (without hand-over) and launch_embed_signs share ----------------------------------------------------
 // the planes of an embed sweep: f(T{}, IC<channels of the base>{}) with T = float or uint8_t, the element type of x, base and out.

@@ -34,12 +34,8 @@ __global__ __launch_bounds__(BLOCK, (PAD == 1 && HC == 1 ? (VEC ? (sizeof(T) == 
     __shared__ __attribute__((aligned(16))) float s_row[WPB][2 * RowBuf<HC>::N];
     __shared__ __attribute__((aligned(16))) float s_u[WPB][2 * KG * RowBuf<1>::N];
     __shared__ double s_red[WPB][2 * KG + 1];
-    // block order: the key groups of one (tile, frame) block are consecutive logical indices of one XCD (xcd_remap), so the
-    // tile of x is read from memory once and from that XCD's L2 for the other groups; inside a group the order is k_detect's
-    const int nb = (int)gridDim.x / ka.ngroups;
-    const int pidx = xcd_remap((int)blockIdx.x, (int)gridDim.x);
-    const int grp = pidx % ka.ngroups;
-    const WaveJob j = make_job(g, xcd_unmap(pidx / ka.ngroups, nb));
+    int grp;
+    const WaveJob j = keys_job(g, ka.ngroups, grp);
     const int frame = j.frame;
     const int k0 = grp * KG;
     float dot[KG], nu[KG], nw = 0.0f;
@@ -183,7 +179,7 @@ int launch_detect_keys(const Sweep& sw, const KeyBank& bank, double* part, int r
     const bool quad = frames >= 4;
     if (ld.nblk > rstride || ld.nstrips * ld.nsegs > rstride || ld.nstrips > KEYS_MAX_STRIPS) return -1;
     KeysArgs ka;
-    ka.W = bank.W; ka.kstride = bank.kstride; ka.nkeys = nkeys; ka.ngroups = (nkeys + KG - 1) / KG; ka.rstride = rstride;
+    ka.W = bank.W; ka.kstride = bank.kstride; ka.nkeys = nkeys; ka.ngroups = group_count(nkeys, KG); ka.rstride = rstride;
     ka.part = part; ka.partw = part + (size_t)frames * nkeys * rstride * 2;
     WM_DISPATCH_T(sw.x.dtype, launch_detect_keys_t<T>(sw, pl, ka));
     launch_keys_fold(sw.s, ka.part, ka.partw, rstride, frames, nkeys, quad ? 1 : 0, ld.nblk, ld.nsegs, ld.nstrips, sw.status, res);

@@ -25,11 +25,8 @@ __global__ __launch_bounds__(BLOCK, (PAD == 1 && HC == 1 ? (VEC ? (sizeof(T) == 
 {
     __shared__ __attribute__((aligned(16))) float s_row[WPB][2 * RowBuf<HC>::N];
     __shared__ __attribute__((aligned(16))) float s_u[WPB][2 * KG * RowBuf<1>::N];
-    // k_detect_keys' block order: the key groups of one (tile, frame) block are consecutive logical indices of one XCD
-    const int nb = (int)gridDim.x / ngroups;
-    const int pidx = xcd_remap((int)blockIdx.x, (int)gridDim.x);
-    const int grp = pidx % ngroups;
-    const WaveJob j = make_job(g, xcd_unmap(pidx / ngroups, nb));
+    int grp;
+    const WaveJob j = keys_job(g, ngroups, grp);
     // wave-uniform exits (the kernel has no block barrier): a surplus wave, or a frame the fold answers from its status alone
     if (!j.valid || status[j.frame] != 0) return;
     const int frame = j.frame;
@@ -108,7 +105,7 @@ __global__ __launch_bounds__(BLOCK) void k_keys_tiles_fold(const float* __restri
 
 size_t keys_tiles_rec_bytes(const TilesPlan& pl, int frames, int nkeys)
 {
-    const size_t ngroups = (size_t)((nkeys + KG - 1) / KG);
+    const size_t ngroups = (size_t)group_count(nkeys, KG);
     return (size_t)frames * ngroups * pl.ld.nsegs * pl.ld.nstrips * KT_NV * WAVE * sizeof(float);
 }
 
@@ -118,7 +115,7 @@ size_t keys_tiles_rec_bytes(const TilesPlan& pl, int frames, int nkeys)
 bool keys_tiles_grids_fit(int rows, int cols, int tile_rows, int frames, int nkeys, int ny, int nx)
 {
     const long long lim = 0x7fffffffLL;
-    const long long ngroups = (nkeys + KG - 1) / KG;
+    const long long ngroups = group_count(nkeys, KG);
     const int rps = std::min(tiles_segment_rows(tile_rows), rows);
     const long long nsegs = (rows + rps - 1) / rps;
     const long long nstrips = std::max((cols + STRIP - 1) / STRIP, overlap_strips(cols) + 1);
@@ -129,7 +126,7 @@ template <typename T>
 static void launch_detect_keys_tiles_t(const Sweep& sw, const TilesPlan& pl, const KeyBank& bank, float* rec)
 {
     const PlaneDesc& x = sw.x;
-    const int ngroups = (bank.nkeys + KG - 1) / KG;
+    const int ngroups = group_count(bank.nkeys, KG);
     // every grid times the key groups
     for_each_detect_launch(pl, sw, [&](auto m, auto p, auto hc, auto vec, const SweepPart& sp) {
         WM_KLAUNCH((k_detect_keys_tiles<T, decltype(m)::value, decltype(p)::value, decltype(hc)::value, decltype(vec)::value>),
@@ -146,7 +143,7 @@ void launch_detect_keys_tiles(const Sweep& sw, const TilesPlan& pl, const KeyBan
 void launch_keys_tiles_fold(hipStream_t s, const TilesPlan& pl, int frames, int nkeys, const float* rec, const int* status, float* map,
                             double* sums, OpResult* res)
 {
-    const int ngroups = (nkeys + KG - 1) / KG;
+    const int ngroups = group_count(nkeys, KG);
     const long long n = (long long)frames * nkeys * pl.tg.ny * pl.tg.nx;
     if (pl.fold_threads == BLOCK) WM_KLAUNCH(k_keys_tiles_fold<BLOCK>, dim3((unsigned)n), dim3(BLOCK), 0, s, rec, pl.tg, frames, nkeys, ngroups, status, map, sums, res);
     else WM_KLAUNCH(k_keys_tiles_fold<WAVE>, dim3((unsigned)((n + WPB - 1) / WPB)), dim3(BLOCK), 0, s, rec, pl.tg, frames, nkeys, ngroups, status, map, sums, res);

@@ -313,13 +313,8 @@ __global__ __launch_bounds__(BLOCK, offsets_min_blocks(PAD, HC, VEC, (int)sizeof
     __shared__ __attribute__((aligned(16))) float s_row[WPB][2 * RowBuf<HC>::N];
     __shared__ __attribute__((aligned(16))) float s_u[WPB][2 * G * RowBuf<1>::N];
     __shared__ double s_red[WPB][2 * G + 1];
-    // block order: the offset groups of one (tile, frame) block are consecutive logical indices of one XCD (xcd_remap), column
-    // groups fastest: the tile of x comes from memory once, and the key rows that neighbouring groups and row offsets share are
-    // that XCD's L2 hits; inside a group the order is k_detect's
-    const int nb = (int)gridDim.x / oa.ngroups;
-    const int pidx = xcd_remap((int)blockIdx.x, (int)gridDim.x);
-    const int grp = pidx % oa.ngroups;
-    const WaveJob j = make_job(g, xcd_unmap(pidx / oa.ngroups, nb));
+    int grp;  // (offset group: iy * ngx + gx, column groups fastest)
+    const WaveJob j = keys_job(g, oa.ngroups, grp);
     const int frame = j.frame;
     const int iy = grp / oa.ngx, gx = grp - iy * oa.ngx;
     // every group is full: a short last group starts further left and recomputes the members below `first`, which it does not store
@@ -380,7 +375,7 @@ static void launch_detect_offsets_t(const Sweep& sw, const DetectPlan& pl, const
     auto columns = [&](int G, int lo, int n, int write_w) {
         OffsArgs a = oa1;
         a.jx_lo = lo; a.nxl = n; a.write_w = write_w;
-        a.ngx = (n + G - 1) / G; a.ngroups = a.ny * a.ngx;
+        a.ngx = group_count(n, G); a.ngroups = a.ny * a.ngx;
         return a;
     };
     // the aligned instance of the 3x3 windows: the shared row when a full group exists.  A remainder of nx % G columns costs a

@@ -9,9 +9,11 @@
 // or one per wave under the quad mapping), one set per key; k_embed_keys_fold folds them per (frame, key) in
 // embed_scalars_frame's (stats_fold's) order, so a_k is wm_embed's with key k as W bit for bit.  k_embed_keys is k_embed's march
 // with the key-dependent half inside the row step: m and the base row are formed / read once, then every key of the group takes
-// its W row and stores its copy of y.  Key groups are a grid axis, as in k_detect_keys: the groups of one tile are consecutive
-// blocks of one XCD, so the re-reads of x and base are L2 hits.
-#include "wm_embed_march.hpp"   // (WM_RING3, the ring length of the 3-row x windows on the aligned path, and the launch loop)
+// its W row and stores its copy of y.  That march (embed_group_march) and the kernel body around it (WM_EMBED_GROUP_BODY) live in
+// wm_embed_march.hpp, shared with k_embed_signs_multi; the kernel here says where W, a and max|e| come from.  Key groups are a grid
+// axis, as in k_detect_keys (keys_job): the groups of one tile are consecutive blocks of one XCD, so the re-reads of x and base are
+// L2 hits.
+#include "wm_embed_march.hpp"   // (WM_RING3, the ring length of the 3-row x windows on the aligned path; the group march, body and launch loop)
 
 #ifndef WM_EMBED_KEYS_G
 #define WM_EMBED_KEYS_G 4   // keys per group (registers vs. x / base re-reads)
@@ -274,125 +276,15 @@ __global__ __launch_bounds__(BLOCK) void k_embed_keys_fold(EKeysArgs ka, int qua
 }
 
 // =================================================================================================
-// k_embed_keys: embed_march (wm_embed_march.hpp) with y = clamp(base + a_k * m * W_k, 0, 255) for every key of the group, on ONE
-// channel of the base (a planar-RGB base is three launches, one per channel: y of a channel depends on that channel's base only)
+// k_embed_keys: the group march (embed_group_march, wm_embed_march.hpp) with a W stream and a strength per key, on ONE channel of the
+// base (a planar-RGB base is three launches, one per channel: y of a channel depends on that channel's base only)
 // =================================================================================================
-template <typename T, int MASK, int PAD, bool VEC, bool BX, bool EDGE>
-__device__ __forceinline__ void embed_keys_march(const T* __restrict__ xf, long long pitch, const float* const (&Wk)[EKG],
-                                                 const T* __restrict__ bptr, T* const (&optr)[EKG], int nk, const PlaneDesc& base,
-                                                 const PlaneDesc& out, const Geom& g, const WaveJob& j, float* lds, float* obuf,
-                                                 const float (&c)[8], const float (&a)[EKG], float maxe)
-{
-    constexpr int NR = MASK == 0 ? 3 : 2 * PAD + 1;
-    constexpr int HR = MASK == 0 ? 1 : PAD;  // halo rows above/below = halo columns left/right
-    constexpr int RG = VEC && NR == 3 ? WM_RING3 : UNROLL;
-    XMarch<T, 1, HR, NR, VEC, PFX, EDGE, false, RG> xm;
-    PMarch<float, VEC, EPFK> wm_[EKG];
-    PMarch<T, VEC, PFW> bm;               // (BX: the base is the grey input, read from the stencil window)
-    const float inv_maxe = 1.0f / maxe;   // (k_embed's m = |e| / max|e|: one reciprocal per wave, then div_by per pixel)
-    const int nout = j.re - j.rs, n = nout + 2 * HR;
-    const int c0 = j.c0s + 4 * j.lane;
-    const bool own = !EDGE || 4 * j.lane >= j.dup;  // duplicate lanes of a shifted last strip: the previous strip stores these pixels
-    xm.start(xf, pitch, g, j, lds, j.rs - HR, n);
-#pragma unroll
-    for (int q = 0; q < EKG; ++q) wm_[q].start(Wk[q], g.cols, g.cols, j, j.rs, nout);
-    if (!BX) bm.start(bptr, base.pitch, g.cols, j, j.rs, nout);
-    march_n<2 * HR, RG>(n, [&](int i, auto qc, auto emit) {
-        constexpr int Q = decltype(qc)::value;
-        xm.template step<Q>(i);
-        if (decltype(emit)::value) {
-            const int o = i - 2 * HR;
-            constexpr int SB = (Q + 4 * UNROLL - 2 * HR) % PFW;
-            constexpr int SW = (Q + 4 * UNROLL - 2 * HR) % EPFK;
-            // ---- the image side, once per row: the mask of the lane's 4 pixels and the base row
-            float m[4];
-            float pr[4] = {0.f, 0.f, 0.f, 0.f};
-            if (MASK == 0) predict4<4>(xm.template row<Q>(0), xm.template row<Q>(1), xm.template row<Q>(2), c, pr);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (MASK == 0) {
-                    const float* mid = xm.template row<Q>(1);
-                    m[k] = div_by(fabsf(mid[4 + k] - pr[k]), maxe, inv_maxe);
-                } else {
-                    m[k] = nvf_value<PAD, 4, Q>(xm, k);
-                }
-            }
-            float4 b;
-            if (BX) {
-                const float* ctr = xm.template row<Q>(HR);  // the output row itself
-                b = make_float4(ctr[4], ctr[5], ctr[6], ctr[7]);
-            } else {
-                b = bm.template take<SB>();
-            }
-            // ---- the key side: k_embed's u and y for every key of the group
-#pragma unroll
-            for (int q = 0; q < EKG; ++q) {
-                const float4 w = wm_[q].template take<SW>();
-                float u[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) u[k] = m[k] * f4get(w, k);  // Watermark.cpp:169
-                if (q < nk) {  // (wave-uniform: keys beyond the bank store nothing)
-                    float4 y;
-                    y.x = fminf(fmaxf(fmaf(u[0], a[q], b.x), 0.0f), 255.0f);
-                    y.y = fminf(fmaxf(fmaf(u[1], a[q], b.y), 0.0f), 255.0f);
-                    y.z = fminf(fmaxf(fmaf(u[2], a[q], b.z), 0.0f), 255.0f);
-                    y.w = fminf(fmaxf(fmaf(u[3], a[q], b.w), 0.0f), 255.0f);
-                    if constexpr (VEC) {
-                        if (own) store4<T, true>(optr[q], out.pitch, j.rs + o, c0, g.cols, y);
-                    } else {
-                        store_row_generic<T>(optr[q], out.pitch, j.rs + o, j.c0s, j.lane, g.cols, y, obuf);
-                    }
-                }
-                wm_[q].template refill<SW>(o);
-            }
-            if (!BX) bm.template refill<SB>(o);
-        }
-    });
-}
-
-// base / out: one channel (PlaneDesc::p at that channel, cstride unused)
 template <typename T, int MASK, int PAD, bool VEC, bool BX>
 __global__ __launch_bounds__(BLOCK) void k_embed_keys(const T* __restrict__ x, long long pitch, long long fstride, EKeysArgs ka,
                                                       PlaneDesc base, PlaneDesc out, Geom g, const float* __restrict__ coef,
                                                       const int* __restrict__ status)
 {
-    __shared__ __attribute__((aligned(16))) float s_row[WPB][2 * RowBuf<1>::N];
-    __shared__ __attribute__((aligned(16))) float s_out[VEC ? 1 : WPB][VEC ? 4 : STRIP];  // generic path: store re-layout rows
-    int grp;
-    const WaveJob j = keys_job(g, ka.ngroups, grp);
-    if (!j.valid) return;
-    const int frame = j.frame;
-    const int k0 = grp * EKG;
-    const int nk = min(EKG, ka.nkeys - k0);
-    // copy (frame, k) is frame index frame * nkeys + k of `out`; keys beyond the bank repeat its last key and store nothing
-    const T* bptr = static_cast<const T*>(base.p) + (long long)frame * base.fstride;
-    T* optr[EKG];
-    int kq[EKG];
-#pragma unroll
-    for (int q = 0; q < EKG; ++q) {
-        kq[q] = min(k0 + q, ka.nkeys - 1);
-        optr[q] = static_cast<T*>(const_cast<void*>(out.p)) + ((long long)frame * ka.nkeys + kq[q]) * out.fstride;
-    }
-    if (MASK == 0 && status[frame] != 0) {
-        // unsolvable: every copy = base bit-exact (Watermark.cpp:164-165)
-        const int c0 = j.c0s + 4 * j.lane;
-#pragma unroll
-        for (int q = 0; q < EKG; ++q) {
-            if (q >= nk) break;
-            for (int r = j.rs; r < j.re; ++r) {
-                const T* rb = bptr + (long long)r * base.pitch;
-                T* ro = optr[q] + (long long)r * out.pitch;
-                for (int k = 0; k < 4; ++k)
-                    if (c0 + k < g.cols) ro[c0 + k] = rb[c0 + k];
-            }
-        }
-        return;
-    }
-    float c[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (MASK == 0) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) c[k] = coef[frame * 8 + k];
-    }
+    WM_EMBED_GROUP_BODY(EKG, ka.ngroups, ka.nkeys);
     const float* Wk[EKG];
     float a[EKG];
 #pragma unroll
@@ -402,17 +294,14 @@ __global__ __launch_bounds__(BLOCK) void k_embed_keys(const T* __restrict__ x, l
     }
     const float maxe = ka.scal[(long long)frame * ka.nkeys + k0].maxe;  // (the same for every key of the frame)
     const T* xf = x + (long long)frame * fstride;
-    if (MASK != 0 || strip_on_edge<VEC>(g, j))
-        embed_keys_march<T, MASK, PAD, VEC, BX, true>(xf, pitch, Wk, bptr, optr, nk, base, out, g, j, s_row[j.wave], s_out[VEC ? 0 : j.wave], c, a, maxe);
-    else
-        embed_keys_march<T, MASK, PAD, VEC, BX, (MASK != 0)>(xf, pitch, Wk, bptr, optr, nk, base, out, g, j, s_row[j.wave], s_out[VEC ? 0 : j.wave], c, a, maxe);
+    WM_EMBED_GROUP_MARCH(EKG, EPFK, false, Wk, a, maxe, nullptr, nullptr, nullptr);  // (no sign tables)
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------
 static EKeysArgs ekeys_args(const float* Wbank, long long kstride, int nkeys, int frames, void* scratch, int rstride)
 {
     EKeysArgs ka;
-    ka.W = Wbank; ka.kstride = kstride; ka.nkeys = nkeys; ka.ngroups = (nkeys + EKG - 1) / EKG; ka.rstride = rstride;
+    ka.W = Wbank; ka.kstride = kstride; ka.nkeys = nkeys; ka.ngroups = group_count(nkeys, EKG); ka.rstride = rstride;
     char* p = static_cast<char*>(scratch);
     ka.pss = reinterpret_cast<double*>(p);
     p += (size_t)frames * nkeys * rstride * sizeof(double);

@@ -93,6 +93,8 @@ struct KeyBank {
     int nkeys;
     int aligned_w;
 };
+// the groups of `per` that n keys / copies / offsets make (the last one may be short): the grid blocks per tile of the group kernels
+inline int group_count(int n, int per) { return (n + per - 1) / per; }
 // The planes an embed sweep reads and writes beside x, and the frames' scalars of the stats sweep (null: the launcher has its own)
 struct EmbedPlanes {
     PlaneDesc base, out;
