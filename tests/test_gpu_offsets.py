@@ -112,6 +112,41 @@ def test_bit_equal_to_detect_keys(wm, torch_cuda, kshape, shape, mask, p, dtype,
     eng.close()
 
 
+# (key shape, image shape, rectangles (oy0, ox0, ny, nx)): with groups of 4, nx = 7 is a full shared group and a three-column
+# remainder that runs as a group moved left, nx = 5 a one-column remainder in a launch of its own
+SHARED_ROW_SHAPES = [((80, 300), (64, 256), [(3, 5, 2, 7), (1, 2, 2, 5)]), ((301, 523), (271, 483), [(3, 5, 2, 7)])]
+SHARED_ROW_CASES = [(ks, s, rs, mk, dt, F) for ks, s, rs in SHARED_ROW_SHAPES for mk in (0, 1) for dt in ("f32", "u8") for F in (1, 5)]
+
+
+@pytest.mark.parametrize("kshape,shape,rects,mask,dtype,F", SHARED_ROW_CASES)
+def test_every_score_bit_equal_to_wm_detect(wm, torch_cuda, kshape, shape, rects, mask, dtype, F):
+    """wm_detect_offsets and wm_detect_keys run one march (group_march), so their equality does not anchor the shared W row to
+    independent code: every score of a rectangle equals, as uint32, wm_detect on the batched sweeps (fused kernels off:
+    detect_march) with that window copied out as W.  p = 3; the aligned overlapped strips (256 columns) and the generic / split
+    ones (483), the record per wave (F = 5) and per block (F = 1), the full, the moved-left and the one-column-tail groups"""
+    torch = torch_cuda
+    (KR, KC), (R, Cc) = kshape, shape
+    keys = wm.KeySet.from_seeds(KR, KC, [4100 + 13 * k for k in range(KBANK)])
+    key = keys.plane(KBANK - 1)
+    xs = torch.from_numpy(frames_of(R, Cc, F, dtype, first=2)).cuda()
+    mt = wm.MASK_TYPE(mask)
+    eng = wm.Watermark(R, Cc, np.zeros((R, Cc), np.float32), 3, 40.0, max_frames=F)
+    one = wm.Watermark(R, Cc, np.zeros((R, Cc), np.float32), 3, 40.0, max_frames=F)
+    for (oy0, ox0, ny, nx) in rects:
+        got = np.asarray(eng.detectOffsets(xs, keys, KBANK - 1, oy0, ox0, ny, nx, mt)).reshape(F, ny, nx)
+        want = np.empty((F, ny, nx), np.float32)
+        for i in range(ny):
+            for j in range(nx):
+                one.reinitialize(window(key, R, Cc, oy0 + i, ox0 + j), R, Cc)
+                one.set_fused(False)
+                want[:, i, j] = np.asarray(one.detectWatermark(xs, mt), np.float32).reshape(F)
+        assert np.isfinite(want).all() and float(np.abs(want).max()) > 1e-4
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), ((oy0, ox0, ny, nx), got, want)
+    one.close()
+    eng.close()
+    keys.close()
+
+
 @pytest.mark.parametrize("kshape,shape", SHAPES[1:4])
 @pytest.mark.parametrize("mask,p", [(0, 3), (1, 3), (1, 7)])
 @pytest.mark.parametrize("dtype", ["f32", "u8"])

@@ -4,8 +4,10 @@
 // Everything on the image side of the detector is independent of the key (Watermark.cpp:221-250): the coefficients c (one
 // Gram sweep + solve, wm_api.hip gram_sweep), e_w = x - c.nbrs(x), the mask m (ME: |e_w|, NVF: nvf(x)) and ||e_w||^2.  Only
 // u_k = m W_k, e_u_k = u_k - c.nbrs(u_k), <e_u_k, e_w> and ||e_u_k||^2 change with the key.  k_detect_keys is k_detect's strip
-// march (wm_k_detect.hip detect_march) with a compile-time group of KG keys inside every row step: x, e_w and m are formed
-// once per row, then every key of the group loads its W row, forms its rolling u window and runs its residual4 chain.  K > KG
+// march (wm_k_detect.hip detect_march) with a compile-time group of KG keys inside every row step (group_march,
+// wm_keys_march.hpp, shared with k_detect_keys_tiles and k_detect_offsets, as are the lines around it and the record tail):
+// x, e_w and m are formed once per row, then every key of the group loads its W row, forms its rolling u window and runs its
+// residual4 chain.  K > KG
 // is a grid axis over key groups (x is marched again per group; the groups of one tile run back to back on one XCD, so those
 // re-reads are L2 hits).  Per key the per-pixel operations, their order and the partial-sum grouping are k_detect's: a key's
 // score is bit-identical to wm_detect's with that key as W (tests/test_gpu_keys.py).
@@ -33,7 +35,6 @@ __global__ __launch_bounds__(BLOCK, (PAD == 1 && HC == 1 ? (VEC ? (sizeof(T) == 
 {
     __shared__ __attribute__((aligned(16))) float s_row[WPB][2 * RowBuf<HC>::N];
     __shared__ __attribute__((aligned(16))) float s_u[WPB][2 * KG * RowBuf<1>::N];
-    __shared__ double s_red[WPB][2 * KG + 1];
     int grp;
     const WaveJob j = keys_job(g, ka.ngroups, grp);
     const int frame = j.frame;
@@ -42,47 +43,16 @@ __global__ __launch_bounds__(BLOCK, (PAD == 1 && HC == 1 ? (VEC ? (sizeof(T) == 
 #pragma unroll
     for (int q = 0; q < KG; ++q) { dot[q] = 0.0f; nu[q] = 0.0f; }
     if (j.valid && status[frame] == 0) {
-        float c[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) c[k] = coef[frame * 8 + k];
-        const T* xf = x + (long long)frame * fstride;
+        WM_GROUP_DETECT_FRAME;
         // keys beyond the bank (a short last group) repeat its last key; their sums are not stored
         const float* Wk[KG];
 #pragma unroll
         for (int q = 0; q < KG; ++q) Wk[q] = ka.W + (long long)min(k0 + q, ka.nkeys - 1) * ka.kstride;
-        constexpr bool V = VEC && HC == 1;
-        if (MASK != 0 || strip_on_edge<V>(g, j)) keys_march<T, MASK, PAD, HC, V, true>(xf, pitch, Wk, g, j, s_row[j.wave], s_u[j.wave], c, dot, nu, nw);
-        else keys_march<T, MASK, PAD, HC, V, (MASK != 0)>(xf, pitch, Wk, g, j, s_row[j.wave], s_u[j.wave], c, dot, nu, nw);
+        WM_GROUP_DETECT_MARCH(KG, false, PFK, Wk, g.cols);
     }
-    double d[2 * KG + 1];
-#pragma unroll
-    for (int q = 0; q < KG; ++q) { d[2 * q] = wave_sum((double)dot[q]); d[2 * q + 1] = wave_sum((double)nu[q]); }
-    d[2 * KG] = wave_sum((double)nw);
-    if (g.quad) {
-        // the waves of this block are 4 frames: one record per wave (k_detect's corr_fold order, folded by k_keys_fold)
-        if (!j.valid || j.lane != 0) return;
-#pragma unroll
-        for (int q = 0; q < KG; ++q) {
-            if (k0 + q >= ka.nkeys) break;
-            double* p = ka.part + (((long long)frame * ka.nkeys + k0 + q) * ka.rstride + j.rec) * 2;
-            p[0] = d[2 * q]; p[1] = d[2 * q + 1];
-        }
-        if (grp == 0) ka.partw[(long long)frame * ka.rstride + j.rec] = d[2 * KG];
-        return;
-    }
-    // the waves of this block are 4 segments of one frame: one record per block, k_detect's ((w0 + w1) + w2) + w3
-    if (j.lane == 0) {
-#pragma unroll
-        for (int v = 0; v < 2 * KG + 1; ++v) s_red[j.wave][v] = d[v];
-    }
-    __syncthreads();
-    const int v = threadIdx.x;
-    if (v < 2 * KG + 1) {
-        const double s = ((s_red[0][v] + s_red[1][v]) + s_red[2][v]) + s_red[3][v];
-        const long long blk = g.pb0 + j.tile;
-        if (v == 2 * KG) { if (grp == 0) ka.partw[(long long)frame * ka.rstride + blk] = s; }
-        else if (k0 + v / 2 < ka.nkeys) ka.part[(((long long)frame * ka.nkeys + k0 + v / 2) * ka.rstride + blk) * 2 + (v & 1)] = s;
-    }
+    // one record per wave (quad) or per block; the group's keys are k0 .. of the bank's nkeys, those below nkeys are stored; key
+    // group 0 records ||e_w||^2
+    WM_GROUP_RECORDS(KG, k0, ka.nkeys, k0, ka.nkeys, ka.rstride, grp == 0, ka.part, ka.partw);
 }
 
 // one block per (frame, key): the records folded in k_detect's order -- corr_finalize_frame's over the blocks, or (quad)

@@ -2,10 +2,10 @@
 // k_detect_keys_tiles + k_keys_tiles_fold
 //
 // wm_detect_keys shares the image side of the detector (c, e_w, m, ||e_w||^2) between the keys of a bank; wm_detect_tiles keeps
-// the positions of the three sums.  k_detect_keys_tiles is k_detect_keys' march (keys_march, wm_keys_march.hpp: the same
-// instances, key groups, block order and fmaf order) on wm_detect_tiles' geometry (tiles_plan: segments whose height divides
-// tile_rows) with k_detect_tiles' end: no wave reduction, no LDS fold, no block barrier -- every lane stores its 2 KG + 1 f32
-// partials into
+// the positions of the three sums.  k_detect_keys_tiles is k_detect_keys' march (group_march with the lines around it,
+// wm_keys_march.hpp: the same instances, key groups, block order and fmaf order) on wm_detect_tiles' geometry (tiles_plan:
+// segments whose height divides tile_rows) with k_detect_tiles' end: no wave reduction, no LDS fold, no block barrier -- every
+// lane stores its 2 KG + 1 f32 partials into
 //     rec [frame][group][segment][strip][2 KG + 1][64 lanes]     {dot_q, nu_q} per key q of the group, then nw
 // with plain vector stores (a lane that owns no pixels stores zeros).  k_keys_tiles_fold then adds the records of each
 // (frame, key, tile) in k_tiles_fold's fixed index order in f64: key k's map and sums are wm_detect_tiles' with key k as W, bit
@@ -34,18 +34,13 @@ __global__ __launch_bounds__(BLOCK, (PAD == 1 && HC == 1 ? (VEC ? (sizeof(T) == 
     float dot[KG], nu[KG], nw = 0.0f;
 #pragma unroll
     for (int q = 0; q < KG; ++q) { dot[q] = 0.0f; nu[q] = 0.0f; }
-    float c[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) c[k] = coef[frame * 8 + k];
-    const T* xf = x + (long long)frame * fstride;
+    WM_GROUP_DETECT_FRAME;
     // keys beyond the bank (a short last group) repeat its last key; the fold never reads their slots
     const float* Wk[KG];
 #pragma unroll
     for (int q = 0; q < KG; ++q) Wk[q] = Wbank + (long long)min(k0 + q, nkeys - 1) * kstride;
-    constexpr bool V = VEC && HC == 1;
-    if (MASK != 0 || strip_on_edge<V>(g, j)) keys_march<T, MASK, PAD, HC, V, true>(xf, pitch, Wk, g, j, s_row[j.wave], s_u[j.wave], c, dot, nu, nw);
-    else keys_march<T, MASK, PAD, HC, V, (MASK != 0)>(xf, pitch, Wk, g, j, s_row[j.wave], s_u[j.wave], c, dot, nu, nw);
-    // every lane of the wave stores (the lanes that own nothing hold zeros: keys_march masks them)
+    WM_GROUP_DETECT_MARCH(KG, false, PFK, Wk, g.cols);
+    // every lane of the wave stores (the lanes that own nothing hold zeros: group_march masks them)
     float* p = rec + ((((long long)frame * ngroups + grp) * g.nrec + j.rec) * KT_NV) * WAVE + j.lane;
 #pragma unroll
     for (int q = 0; q < KG; ++q) { p[(2 * q) * WAVE] = dot[q]; p[(2 * q + 1) * WAVE] = nu[q]; }

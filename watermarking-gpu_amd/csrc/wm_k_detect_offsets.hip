@@ -2,13 +2,14 @@
 // plane that is larger than the image (wm_detect_offsets, wm.h): where in its key does a cropped copy lie?
 //
 // Offset (oy, ox) scores the image against W = key[oy : oy + rows, ox : ox + cols].  The image side is wm_detect_keys' (Gram
-// sweep, solve; e_w, the mask and ||e_w||^2 once per row of the march); the sweep is k_detect_keys' march (wm_k_detect_keys.hip
-// keys_march) whose members are G horizontally adjacent offsets of one row offset instead of KG keys.  The point of the kernel:
+// sweep, solve; e_w, the mask and ||e_w||^2 once per row of the march); the sweep is k_detect_keys' march (group_march,
+// wm_keys_march.hpp: one body for both, as are the lines around it and the record tail WM_GROUP_RECORDS) whose members are G
+// horizontally adjacent offsets of one row offset instead of KG keys.  The point of the kernel:
 // on the aligned path the G members SHARE ONE W ROW STREAM.  A lane's four pixels need, for the offsets ox .. ox + G - 1, the
 // 4 + G - 1 consecutive key values key[oy + r][ox + c .. ox + c + 3 + G - 1]: one 16-byte load and one load of the G - 1 values
 // behind it (the bytes the next lane loads as its own: a vector-cache hit).  Member q takes values q .. q + 3 of them; all that
 // follows -- u = m w, the rolling u window with ITS OWN halos (the replicate border is the window's edge, never the key's next
-// column), residual4, the dot / nu chains and the partial-sum grouping -- is keys_march's per member, so a score is bit for bit
+// column), residual4, the dot / nu chains and the partial-sum grouping -- is the march's per member, so a score is bit for bit
 // wm_detect_keys' on a bank that holds the window copied out (tests/test_gpu_offsets.py).  The records are laid out
 // [frames][ny * nx][rstride][2] and folded by k_keys_fold with nkeys = ny * nx.
 //
@@ -20,22 +21,9 @@
 // its last member's window, which wm_detect_offsets has checked to lie inside the plane.  nx < G runs the G = 1 instance, as do
 // the generic, split-remainder and NVF p > 3 instances: their members would each need a W stream and a halo stream of their
 // own, and at G = 1 they are k_detect's march with a pitch.
-#include "wm_march.hpp"
-
-#ifndef WM_OFFS_G
-#define WM_OFFS_G 4     // offsets per group on the aligned 3x3 path (registers vs. W bytes per offset)
-#endif
-#ifndef WM_PFW_OFFS
-#define WM_PFW_OFFS 2   // W rows in flight per group (must divide UNROLL): a row step does G members' arithmetic, so two rows
-                        // ahead are as far ahead in time as k_detect_keys' two rows per key
-#endif
+#include "wm_keys_march.hpp"
 
 namespace wmk {
-
-constexpr int OG = WM_OFFS_G;
-constexpr int PFO = WM_PFW_OFFS;
-static_assert(OG >= 2 && OG <= 4, "the shared row is one 16-byte load and one load of 1..3 values");
-static_assert(UNROLL % PFO == 0, "the W prefetch ring must divide the march group");
 
 struct OffsArgs {
     const float* key;   // the searched key plane [KR][KC]
@@ -50,250 +38,6 @@ struct OffsArgs {
     double* part;       // [frames][ny * nx][rstride][2]  {<e_u,e_w>, ||e_u||^2}
     double* partw;      // [frames][rstride]              ||e_w||^2 (written by group 0 of the write_w launch)
 };
-
-// the G - 1 key values behind a lane's float4
-template <int N> struct ExtVec;
-template <> struct ExtVec<1> { using type = float; };
-template <> struct ExtVec<2> { using type = float2; };
-template <> struct ExtVec<3> { using type = float3; };
-__device__ __forceinline__ void ext_unpack(float v, float* o) { o[0] = pinned(v); }
-__device__ __forceinline__ void ext_unpack(const float2& v, float* o) { o[0] = pinned(v.x); o[1] = pinned(v.y); }
-__device__ __forceinline__ void ext_unpack(const float3& v, float* o) { o[0] = pinned(v.x); o[1] = pinned(v.y); o[2] = pinned(v.z); }
-
-// PMarch's ring (wm_march.hpp) for the shared W row of a group of G offsets: per row the lane's 4 + G - 1 key values
-template <int G, int PF>
-struct WShare {
-    using Ext = typename ExtVec<G - 1>::type;
-    BufRsrc rs;
-    unsigned pitch_b, off;
-    float4 pa[PF];
-    Ext pb[PF];
-    int r0, last;
-    // base: the key at (row offset, the group's first column offset); lanes beyond the image re-read its last 4 columns
-    __device__ __forceinline__ void start(const float* base, int kc, int cols, const WaveJob& j, int first_row, int count)
-    {
-        rs = make_rsrc(base); pitch_b = (unsigned)kc * 4u;
-        off = (unsigned)min(j.c0s + 4 * j.lane, cols - 4) * 4u;
-        r0 = first_row; last = first_row + count - 1;
-#pragma unroll
-        for (int q = 0; q < PF; ++q) issue(q, min(r0 + q, last));
-    }
-    __device__ __forceinline__ void issue(int slot, int r)
-    {
-        pa[slot] = buf_load<float4>(rs, off, (unsigned)r * pitch_b);
-        pb[slot] = buf_load<Ext>(rs, off + 16u, (unsigned)r * pitch_b);
-    }
-    template <int SLOT>
-    __device__ __forceinline__ void take(float (&v)[4 + G - 1]) const
-    {
-        const float4 a = pinned(pa[SLOT]);
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-        ext_unpack(pb[SLOT], v + 4);
-    }
-    template <int SLOT>
-    __device__ __forceinline__ void refill(int o)
-    {
-        __builtin_amdgcn_sched_barrier(0);
-        issue(SLOT, min(r0 + o + PF, last));
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);  // keep the prefetch where it is written (see XMarch::step)
-    }
-};
-struct WShareNone {};
-
-// keys_march (wm_k_detect_keys.hip) with the G members' W rows taken from the window pitch kc apart: Wg = the key at the
-// group's (row offset, first column offset), member q's window starts q columns further right.  SHARED (aligned path, G > 1):
-// one row stream for the group; else one PMarch (and, LDS path, one halo stream) per member
-template <typename T, int MASK, int PAD, int HC, bool VEC, bool EDGE, int G>
-__device__ __forceinline__ void offsets_march(const T* __restrict__ xf, long long pitch, const float* __restrict__ Wg, int kc,
-                                              const Geom& g, const WaveJob& j, float* lds_x, float* lds_u,
-                                              const float (&c)[8], float (&dot)[G], float (&nu)[G], float& nw)
-{
-    constexpr int HRX = MASK == 0 ? 1 : PAD;
-    constexpr int NR = 2 * HRX + 1;
-    constexpr int O = 4 * HC;
-    constexpr int MID = HRX;
-    constexpr bool HALO1 = VEC && HC == 1 && (MASK == 0 || PAD <= 3);
-    constexpr bool SHARED = VEC && G > 1;
-    static_assert(!SHARED || HALO1, "the shared row serves the overlapped strips: no halo loads");
-    constexpr int NM = SHARED ? 1 : G;  // per-member streams
-    const int R = g.rows, C = g.cols;
-    float nc[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) nc[k] = -c[k];
-    const int t0 = j.rs > 0 ? j.rs - 1 : 0;
-    const int t1 = j.re < R ? j.re : R - 1;
-    const int nu_rows = t1 - t0 + 1;
-    const int n = nu_rows + 2 * HRX;
-    XMarch<T, HC, HALO1 ? HRX : HRX + 1, NR, VEC, PFX, EDGE, HALO1, UNROLL> xm;
-    PMarch<float, VEC, PFO> wm_[NM];
-    typename std::conditional<SHARED, WShare<SHARED ? G : 2, PFO>, WShareNone>::type ws;
-    const int c0 = j.c0s + 4 * j.lane;
-    const bool left_edge = EDGE && j.c0s == 0;
-    const bool has_right = !EDGE || j.c0s + STRIP <= C - 1;
-    xm.start(xf, pitch, g, j, lds_x, t0 - HRX, n);
-    if constexpr (SHARED) ws.start(Wg, kc, C, j, t0, nu_rows);
-    else {
-#pragma unroll
-        for (int q = 0; q < G; ++q) wm_[q].start(Wg + q, kc, C, j, t0, nu_rows);
-    }
-    // (LDS path) the window's column beside the strip, clamped to the WINDOW: its replicate border, not the key's next column
-    const int wh_col = j.lane == WAVE - 1 ? (j.c0s + STRIP < C ? j.c0s + STRIP : C - 1) : (j.c0s > 0 ? j.c0s - 1 : 0);
-    const unsigned wh_off = (unsigned)wh_col * 4u;
-    auto load_wh = [&](int q, int r) -> float {
-        if constexpr (HALO1) return 0.0f;
-        else if constexpr (VEC) return buf_load<float>(wm_[q].ps.rs, wh_off, (unsigned)r * wm_[q].ps.pitch_b);
-        else return Wg[q + wh_col + (long long)r * kc];
-    };
-    float whpre[G][PFO];
-#pragma unroll
-    for (int q = 0; q < G; ++q)
-#pragma unroll
-        for (int s = 0; s < PFO; ++s) whpre[q][s] = load_wh(q, min(t0 + s, t1));
-    float uw[G][3][6];
-    float eww[3][4];
-#pragma unroll
-    for (int q = 0; q < G; ++q)
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int b = 0; b < 6; ++b) uw[q][a][b] = 0.f;
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) eww[a][b] = 0.f;
-    const int last_col_local = C - 1 - j.c0s;
-    const bool own = HALO1 || !EDGE || 4 * j.lane >= j.dup;
-    march_n<2 * HRX, UNROLL>(n, [&](int i, auto qc, auto emit) {
-        constexpr int Q = decltype(qc)::value;
-        xm.template step<Q>(i);
-        if (decltype(emit)::value) {
-            const int o = i - 2 * HRX;
-            const int t = t0 + o;
-            constexpr int SLOT = (Q + 2 * UNROLL - 2 * HRX) % PFO;
-            const float* xup = xm.template row<Q>(MID - 1);
-            const float* xmid = xm.template row<Q>(MID);
-            const float* xdn = xm.template row<Q>(MID + 1);
-            // ---- the image side, once per row: e_w and the mask of the 4 own pixels (and, LDS path, of the strip's halo columns)
-            float* ew = eww[Q % 3];
-            float ewn[4], m[4];
-            residual4<O>(xup, xmid, xdn, nc, ewn);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                ew[k] = ewn[k];
-                m[k] = MASK == 0 ? fabsf(ew[k]) : nvf_value<PAD, O, Q>(xm, k);
-            }
-            float mh = 0.0f;  // (LDS path) lane 0: the mask at column c0s - 1, lane 63: at column c0s + STRIP
-            if constexpr (!HALO1) {
-                if (j.lane == 0 && !left_edge) {
-                    const float eh = residual1<O>(xup, xmid, xdn, -1, nc);
-                    mh = MASK == 0 ? fabsf(eh) : nvf_value<PAD, O, Q>(xm, -1);
-                }
-                if (j.lane == WAVE - 1 && has_right) {
-                    const float eh = residual1<O>(xup, xmid, xdn, 4, nc);
-                    mh = MASK == 0 ? fabsf(eh) : nvf_value<PAD, O, Q>(xm, 4);
-                }
-            }
-            const int r = t - 1;
-            const bool emit_r = r >= j.rs && r < j.re;
-            const bool last_row = j.re == R && t == R - 1;
-            // ---- the key side: the row's 4 + G - 1 key values once (shared row), then k_detect's operations for every member
-            float wv[4 + G - 1];
-            if constexpr (SHARED) ws.template take<SLOT>(wv);
-#pragma unroll
-            for (int q = 0; q < G; ++q) {
-                float wq[4];
-                if constexpr (SHARED) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) wq[k] = wv[q + k];
-                } else {
-                    const float4 w = wm_[q].template take<SLOT>();
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) wq[k] = f4get(w, k);
-                }
-                const float wh = HALO1 ? 0.0f : pinned(whpre[q][SLOT]);
-                float uu[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) uu[k] = m[k] * wq[k];
-                float* un = uw[q][Q % 3];
-                if constexpr (HALO1) {
-                    if constexpr (EDGE) {
-                        un[0] = dpp_from_prev(uu[3], uu[0]);
-                        const float nx = dpp_from_next(uu[0], uu[3]);
-                        un[5] = xm.xs.rsel ? uu[3] : nx;
-                    } else {
-                        un[0] = dpp_from_prev_any(uu[3]);
-                        un[5] = dpp_from_next_any(uu[0]);
-                    }
-                } else {
-#pragma unroll
-                    for (int k = 1; k < 4; ++k)
-                        if (c0 + k >= C) uu[k] = uu[k - 1];
-                    float* urow = lds_u + (2 * q + (Q & 1)) * RowBuf<1>::N;
-                    reinterpret_cast<float4*>(urow)[1 + j.lane] = make_float4(uu[0], uu[1], uu[2], uu[3]);
-                    if (j.lane == 0) urow[3] = left_edge ? uu[0] : mh * wh;
-                    if (j.lane == WAVE - 1 && has_right) urow[4 + STRIP] = mh * wh;
-                    if (!has_right) {
-                        const int lk = last_col_local - 4 * j.lane;
-                        if (lk >= 0 && lk < 4) urow[4 + last_col_local + 1] = uu[lk];
-                    }
-                    wave_lds_fence();
-                    un[0] = urow[3 + 4 * j.lane];
-                    un[5] = urow[8 + 4 * j.lane];
-                }
-                un[1] = uu[0]; un[2] = uu[1]; un[3] = uu[2]; un[4] = uu[3];
-                if (o == 0 && j.rs == 0) {
-#pragma unroll
-                    for (int b = 0; b < 6; ++b) uw[q][(Q + 2) % 3][b] = un[b];
-                }
-                if (emit_r) {
-                    const float* um = uw[q][(Q + 1) % 3];
-                    const float* u0 = uw[q][(Q + 2) % 3];
-                    const float* ewp = eww[(Q + 2) % 3];
-                    float eun[4];
-                    residual4<1>(um, u0, un, nc, eun);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        if (VEC ? own : (c0 + k < C && c0 + k >= j.own_c0)) {
-                            const float eu = eun[k];
-                            dot[q] = fmaf(eu, ewp[k], dot[q]);
-                            nu[q] = fmaf(eu, eu, nu[q]);
-                            if (q == 0) nw = fmaf(ewp[k], ewp[k], nw);
-                        }
-                    }
-                }
-                if (last_row) {
-                    const float* u0 = uw[q][(Q + 2) % 3];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        if (VEC ? own : (c0 + k < C && c0 + k >= j.own_c0)) {
-                            const float eu = residual1<1>(u0, un, un, k, nc);
-                            dot[q] = fmaf(eu, ew[k], dot[q]);
-                            nu[q] = fmaf(eu, eu, nu[q]);
-                            if (q == 0) nw = fmaf(ew[k], ew[k], nw);
-                        }
-                    }
-                }
-                if constexpr (!SHARED) {
-                    wm_[q].template refill<SLOT>(o);
-                    if constexpr (!HALO1) {
-                        __builtin_amdgcn_sched_barrier(0);
-                        whpre[q][SLOT] = load_wh(q, min(t + PFO, t1));
-                        asm volatile("" ::: "memory");
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                }
-            }
-            if constexpr (SHARED) ws.template refill<SLOT>(o);
-        }
-    });
-    if constexpr (HALO1) {
-        const bool mine = j.lane >= j.lo && j.lane <= j.hi;
-#pragma unroll
-        for (int q = 0; q < G; ++q) { dot[q] = mine ? dot[q] : 0.0f; nu[q] = mine ? nu[q] : 0.0f; }
-        nw = mine ? nw : 0.0f;
-    }
-}
 
 // occupancy floor: G = 1 is k_detect_keys' budget with one member less; the shared-row instances hold G u windows
 // (18 VGPRs each) beside the image side's registers
@@ -312,7 +56,6 @@ __global__ __launch_bounds__(BLOCK, offsets_min_blocks(PAD, HC, VEC, (int)sizeof
 {
     __shared__ __attribute__((aligned(16))) float s_row[WPB][2 * RowBuf<HC>::N];
     __shared__ __attribute__((aligned(16))) float s_u[WPB][2 * G * RowBuf<1>::N];
-    __shared__ double s_red[WPB][2 * G + 1];
     int grp;  // (offset group: iy * ngx + gx, column groups fastest)
     const WaveJob j = keys_job(g, oa.ngroups, grp);
     const int frame = j.frame;
@@ -327,44 +70,17 @@ __global__ __launch_bounds__(BLOCK, offsets_min_blocks(PAD, HC, VEC, (int)sizeof
 #pragma unroll
     for (int q = 0; q < G; ++q) { dot[q] = 0.0f; nu[q] = 0.0f; }
     if (j.valid && status[frame] == 0) {
-        float c[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) c[k] = coef[frame * 8 + k];
-        const T* xf = x + (long long)frame * fstride;
+        WM_GROUP_DETECT_FRAME;
+        // member q's window starts q columns right of the group's (row offset, first column offset)
         const float* Wg = oa.key + (long long)(oa.oy0 + iy) * oa.kc + (oa.ox0 + jx0);
-        constexpr bool V = VEC && HC == 1;
-        if (MASK != 0 || strip_on_edge<V>(g, j)) offsets_march<T, MASK, PAD, HC, V, true, G>(xf, pitch, Wg, oa.kc, g, j, s_row[j.wave], s_u[j.wave], c, dot, nu, nw);
-        else offsets_march<T, MASK, PAD, HC, V, (MASK != 0), G>(xf, pitch, Wg, oa.kc, g, j, s_row[j.wave], s_u[j.wave], c, dot, nu, nw);
-    }
-    double d[2 * G + 1];
+        const float* Wm[G];
 #pragma unroll
-    for (int q = 0; q < G; ++q) { d[2 * q] = wave_sum((double)dot[q]); d[2 * q + 1] = wave_sum((double)nu[q]); }
-    d[2 * G] = wave_sum((double)nw);
-    if (g.quad) {
-        // the waves of this block are 4 frames: one record per wave (k_detect's corr_fold order, folded by k_keys_fold)
-        if (!j.valid || j.lane != 0) return;
-#pragma unroll
-        for (int q = 0; q < G; ++q) {
-            if (q < first) continue;
-            double* p = oa.part + (((long long)frame * noff + o0 + q) * oa.rstride + j.rec) * 2;
-            p[0] = d[2 * q]; p[1] = d[2 * q + 1];
-        }
-        if (grp == 0 && oa.write_w) oa.partw[(long long)frame * oa.rstride + j.rec] = d[2 * G];
-        return;
+        for (int q = 0; q < G; ++q) Wm[q] = Wg + q;
+        WM_GROUP_DETECT_MARCH(G, G > 1, PFO, Wm, oa.kc);
     }
-    // the waves of this block are 4 segments of one frame: one record per block, k_detect's ((w0 + w1) + w2) + w3
-    if (j.lane == 0) {
-#pragma unroll
-        for (int v = 0; v < 2 * G + 1; ++v) s_red[j.wave][v] = d[v];
-    }
-    __syncthreads();
-    const int v = threadIdx.x;
-    if (v < 2 * G + 1) {
-        const double s = ((s_red[0][v] + s_red[1][v]) + s_red[2][v]) + s_red[3][v];
-        const long long blk = g.pb0 + j.tile;
-        if (v == 2 * G) { if (grp == 0 && oa.write_w) oa.partw[(long long)frame * oa.rstride + blk] = s; }
-        else if (v / 2 >= first) oa.part[(((long long)frame * noff + o0 + v / 2) * oa.rstride + blk) * 2 + (v & 1)] = s;
-    }
+    // one record per wave (quad) or per block; the group's offsets are o0 .. of the rectangle's noff, those from `first` on are
+    // stored; group 0 of the write_w launch records ||e_w||^2
+    WM_GROUP_RECORDS(G, o0, noff, o0 + first, o0 + G, oa.rstride, grp == 0 && oa.write_w, oa.part, oa.partw);
 }
 
 template <typename T>

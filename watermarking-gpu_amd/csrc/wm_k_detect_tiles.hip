@@ -12,8 +12,7 @@
 
 namespace wmk {
 
-// the same occupancy floors as k_detect's instances (wm_k_detect.hip)
-#define WM_DET_BOUNDS (PAD == 1 && HC == 1 ? (VEC ? WM_DET_WAVES : 3) : 1)
+// the same occupancy floors as k_detect's instances (WM_DET_BOUNDS, wm_detect_march.hpp)
 template <typename T, int MASK, int PAD, int HC, bool VEC>
 __global__ __launch_bounds__(BLOCK, WM_DET_BOUNDS) void k_detect_tiles(const T* __restrict__ x, long long pitch, long long fstride,
                                                                        const float* __restrict__ W, Geom g,
