@@ -4,7 +4,7 @@ import os
 import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from benchlib import ROOT  # (the children take WM_AB_LIB through quick_bench's benchlib.load())
 libs = [os.path.join(ROOT, p) for p in sys.argv[1:] if p.endswith(".so")]
 dt = sys.argv[-1] if sys.argv[-1] in ("f32", "u8") else "f32"
 code = ("import sys, torch; sys.path.insert(0, 'tools'); from quick_bench import run; "

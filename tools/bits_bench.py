@@ -12,68 +12,18 @@ times (wm_prof_*) are printed beside the pair to show what share of the call tha
 profiling names), and the two embeds are also timed by events on the slot's stream (device span: no host share)."""
 import argparse
 import ctypes as C
-import importlib
 import json
-import os
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def round_median_us(fn, iters):
-    ts = []
-    for _ in range(iters):
-        t0 = time.perf_counter()
-        fn()
-        ts.append(time.perf_counter() - t0)
-    return float(np.median(ts)) * 1e6
-
-
-def prof(eng, wm, fn, n):
-    L = wm.lib()
-    L.wm_prof_reset(eng._ctx)
-    L.wm_prof_enable(eng._ctx, 1)
-    for _ in range(n):
-        fn()
-    out = {}
-    for k in range(L.wm_prof_kernel_count()):
-        cnt, ms = C.c_uint64(), C.c_double()
-        L.wm_prof_get(eng._ctx, k, C.byref(cnt), C.byref(ms))
-        if cnt.value:
-            out[L.wm_prof_kernel_name(k).decode()] = round(ms.value * 1e3 / cnt.value, 2)
-    L.wm_prof_enable(eng._ctx, 0)
-    return out
-
-
-def device_span_us(torch, wm, eng, enqueue, n):
-    """median microseconds between two events on slot 0's stream around one enqueued call: what the device spends on it (the
-    table's upload and the launches, the gaps between them included), without the host's share of the call"""
-    st = torch.cuda.ExternalStream(wm.lib().wm_get_stream(eng._ctx, 0))
-    ts = []
-    for _ in range(n):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(st)
-        enqueue()
-        e1.record(st)
-        eng.sync(0)
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1) * 1e3)
-    return round(float(np.median(ts)), 1)
+import benchlib as bl
 
 
 def pair(a, fa, fb, warm=5):
     """the two routes alternate: (median of a, rounds of a, median of b, rounds of b)"""
-    for _ in range(warm):
-        fa()
-        fb()
-    ta, tb = [], []
-    for _ in range(a.rounds):
-        ta.append(round_median_us(fa, a.iters))
-        tb.append(round_median_us(fb, a.iters))
-    return float(np.median(ta)), [round(v, 1) for v in ta], float(np.median(tb)), [round(v, 1) for v in tb]
+    t = bl.alternate({"a": fa, "b": fb}, a.rounds, a.iters, bl.wall_median_us, warm)
+    ta, tb = t["a"], t["b"]
+    return bl.median_of_rounds(ta), [round(v, 1) for v in ta], bl.median_of_rounds(tb), [round(v, 1) for v in tb]
 
 
 def main():
@@ -89,11 +39,9 @@ def main():
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     import torch
-    sys.path.insert(0, ROOT)
-    wm = importlib.import_module("watermarking-gpu_amd")
-    if os.environ.get("WM_AB_LIB"):  # another build of the library (the parent commit's)
-        wm.LIB_PATH = os.environ["WM_AB_LIB"]
-    synth = importlib.import_module("watermarking-gpu_amd.synth")
+    wm, synth = bl.load()
+    kernels_us = lambda eng, fn, n: {k: round(v, 2) for k, v in bl.prof_us_per_launch(eng, fn, n).items()}
+    span = lambda eng, enqueue: round(bl.device_span_us(eng, enqueue, a.iters), 1)
     R, Cc = a.rows, a.cols
     th, tw = (int(v) for v in a.tile.split("x"))
     ny, nx = wm.Watermark.tiles_shape(R, Cc, th, tw)
@@ -118,9 +66,9 @@ def main():
             e_us, e_rounds, s_us, s_rounds = pair(a, emb, sgn)
             r = {"mask": mk.name, "F": F, "embed_us": round(e_us, 1), "embed_us_rounds": e_rounds, "embed_signs_us": round(s_us, 1),
                  "embed_signs_us_rounds": s_rounds, "ratio_signs_over_embed": round(s_us / e_us, 3),
-                 "embed_spread": round((max(e_rounds) - min(e_rounds)) / e_us, 3), "embed_kernels_us": prof(eng, wm, emb, 10),
-                 "embed_device_span_us": device_span_us(torch, wm, eng, lambda: eng.embed_async(pin, pin, pout, mk, 0, av), a.iters),
-                 "embed_signs_device_span_us": device_span_us(torch, wm, eng, lambda: eng.embed_signs_async(pin, pin, pout, th, tw, signs, mk, 0, av), a.iters)}
+                 "embed_spread": round((max(e_rounds) - min(e_rounds)) / e_us, 3), "embed_kernels_us": kernels_us(eng, emb, 10),
+                 "embed_device_span_us": span(eng, lambda: eng.embed_async(pin, pin, pout, mk, 0, av)),
+                 "embed_signs_device_span_us": span(eng, lambda: eng.embed_signs_async(pin, pin, pout, th, tw, signs, mk, 0, av))}
             # the detectors read the marked planes
             mp = torch.empty((F, ny, nx), dtype=torch.float32, device="cuda")
             sm = torch.empty((F, ny, nx, 3), dtype=torch.float64, device="cuda")
@@ -138,15 +86,14 @@ def main():
             r.update(tiles_d2h_us=round(t_us, 1), tiles_d2h_us_rounds=t_rounds, detect_bits_us=round(b_us, 1), detect_bits_us_rounds=b_rounds,
                      ratio_bits_over_tiles_d2h=round(b_us / t_us, 3), min_abs_soft=round(float(np.abs(soft).min()), 4),
                      payload_read_back=bool(np.array_equal(np.packbits(soft > 0, axis=1, bitorder="little"), payload)),
-                     detect_bits_kernels_us=prof(eng, wm, bit, 10))
+                     detect_bits_kernels_us=kernels_us(eng, bit, 10))
             cases.append(r)
             print(json.dumps(r), flush=True)
             eng.close()
     res = {"rows": R, "cols": Cc, "tile": a.tile, "nbits": a.nbits, "iters": a.iters, "rounds": a.rounds, "dtype": "f32", "cases": cases}
     print("BITS_BENCH " + json.dumps(res), flush=True)
     if a.json:
-        with open(a.json, "w") as f:
-            json.dump(res, f, indent=1)
+        bl.write_json(a.json, res)
 
 
 if __name__ == "__main__":

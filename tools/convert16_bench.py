@@ -13,42 +13,11 @@ around --batch calls queued back to back, per call.
      never the fused kernels), ME and NVF.  wm_embed16 minus wm_embed is what the two conversions cost; the two routes must give the
      same bytes."""
 import argparse
-import ctypes as C
-import importlib
 import json
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def device_span_us(torch, wm, eng, enqueue, batch, n, plug=None):
-    """median microseconds per call between two events on slot 0's stream around `batch` calls queued back to back.  plug: queued in
-    front of the first event -- work that keeps the device busy while the host enqueues the timed calls, so that the span is the
-    device's time for them whatever the host's enqueue rate (a guard for calls of under 10 us; the report carries both spans)"""
-    st = torch.cuda.ExternalStream(wm.lib().wm_get_stream(eng._ctx, 0))
-    ts = []
-    for _ in range(n):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        if plug:
-            plug()
-        e0.record(st)
-        for _ in range(batch):
-            enqueue()
-        e1.record(st)
-        eng.sync(0)
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1) * 1e3 / batch)
-    return float(np.median(ts))
-
-
-def membench_us(wm, kind, nbytes, seconds=0.2):
-    us, n = C.c_double(), C.c_int()
-    rc = wm.lib().wm_membench(0, kind, nbytes, seconds, C.byref(us), C.byref(n))
-    assert rc == 0, rc
-    return us.value  # (one copy: `nbytes` read and `nbytes` written)
+import benchlib as bl
 
 
 def main():
@@ -62,9 +31,7 @@ def main():
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     import torch
-    sys.path.insert(0, ROOT)
-    wm = importlib.import_module("watermarking-gpu_amd")
-    synth = importlib.import_module("watermarking-gpu_amd.synth")
+    wm, synth = bl.load()
     R, Cc, bits = a.rows, a.cols, a.bits
     N = R * Cc
     eng = wm.Watermark(R, Cc, synth.synth_watermark(R, Cc), 3, 40.0, nslots=1, max_frames=1)
@@ -81,28 +48,26 @@ def main():
     # (a) the two conversions beside a copy of the same bytes
     conv = {"unpack16": lambda: eng.unpack16_async(pv, bits, pX, 0), "pack16": lambda: eng.pack16_async(pX, pout, bits, 0)}
     moved = 6 * N
-    rounds = {k: [] for k in conv}
-    unplugged = {k: [] for k in conv}
 
     def plug():
         for _ in range(8):
             eng.embed_async(pX, pX, pY, wm.MASK_TYPE.NVF, 0)
-    mb = {1: [], 4: []}
     for fn in conv.values():
         for _ in range(3):
             fn()
     eng.sync(0)
-    for _ in range(a.rounds):
-        for kind in mb:
-            mb[kind].append(membench_us(wm, kind, moved // 2))
-        for k, fn in conv.items():
-            rounds[k].append(device_span_us(torch, wm, eng, fn, a.batch, a.iters, plug))
-            unplugged[k].append(device_span_us(torch, wm, eng, fn, a.batch, a.iters))
-    copy1, copy4 = float(np.median(mb[1])), float(np.median(mb[4]))
+    # every entry takes its own measurement of a round: the two copies (`moved // 2` read and as much written), then per conversion
+    # the plugged span and the unplugged one
+    takes = {kind: (lambda n, kind=kind: bl.membench_us(kind, moved // 2, 0.2)[0]) for kind in (1, 4)}
+    for k, fn in conv.items():
+        takes[k] = lambda n, fn=fn: bl.device_span_us(eng, fn, n, a.batch, plug)
+        takes[k, "unplugged"] = lambda n, fn=fn: bl.device_span_us(eng, fn, n, a.batch)
+    rounds = bl.alternate(takes, a.rounds, a.iters, lambda take, n: take(n))
+    copy1, copy4 = bl.median_of_rounds(rounds[1]), bl.median_of_rounds(rounds[4])
     rates = {}
     for k in conv:
-        us = float(np.median(rounds[k]))
-        rates[k] = {"us": round(us, 2), "us_rounds": [round(t, 2) for t in rounds[k]], "us_unplugged": round(float(np.median(unplugged[k])), 2), "bytes": moved, "GBps": round(moved / us * 1e-3, 1),
+        us = bl.median_of_rounds(rounds[k])
+        rates[k] = {"us": round(us, 2), "us_rounds": [round(t, 2) for t in rounds[k]], "us_unplugged": round(bl.median_of_rounds(rounds[k, "unplugged"]), 2), "bytes": moved, "GBps": round(moved / us * 1e-3, 1),
                     "time_over_copy_kind1": round(us / copy1, 3), "time_over_copy_kind4": round(us / copy4, 3)}
         print(json.dumps({k: rates[k]}), flush=True)
 
@@ -137,13 +102,14 @@ def main():
             for _ in range(3):
                 fn()
         eng.sync(0)
-        t = {k: [] for k in routes}
-        for _ in range(a.rounds):
-            for k, fn in routes.items():
-                if k == "embed16_inplace":
-                    reset_inplace()  # (the frame is marked again and again within a span: the time does not depend on it)
-                t[k].append(device_span_us(torch, wm, eng, fn, a.batch, a.iters))
-        med = {k: float(np.median(ts)) for k, ts in t.items()}
+
+        def span(fn, n):
+            if fn is routes["embed16_inplace"]:
+                reset_inplace()  # (the frame is marked again and again within a span: the time does not depend on it)
+            return bl.device_span_us(eng, fn, n, a.batch)
+
+        t = bl.alternate(routes, a.rounds, a.iters, span)
+        med = {k: bl.median_of_rounds(ts) for k, ts in t.items()}
         r = {"mask": mk.name, "same_bytes_as_three_calls": same}
         for k in routes:
             r[k + "_us"] = round(med[k], 2)
@@ -153,14 +119,12 @@ def main():
         embeds.append(r)
         print(json.dumps(r), flush=True)
     res = {"rows": R, "cols": Cc, "bits": bits, "iters": a.iters, "rounds": a.rounds, "batch": a.batch,
-           "membench_copy_us": {"kind1": round(copy1, 2), "kind4": round(copy4, 2), "kind1_rounds": [round(x, 2) for x in mb[1]],
-                                "kind4_rounds": [round(x, 2) for x in mb[4]], "bytes_read_plus_written": moved},
+           "membench_copy_us": {"kind1": round(copy1, 2), "kind4": round(copy4, 2), "kind1_rounds": [round(x, 2) for x in rounds[1]],
+                                "kind4_rounds": [round(x, 2) for x in rounds[4]], "bytes_read_plus_written": moved},
            "conversions": rates, "embed": embeds}
     print("CONVERT16_BENCH " + json.dumps(res), flush=True)
     if a.json:
-        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
-        with open(a.json, "w") as f:
-            json.dump(res, f, indent=1)
+        bl.write_json(a.json, res)
     eng.close()
 
 

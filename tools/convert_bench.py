@@ -12,47 +12,11 @@ One process, the routes alternating in --rounds rounds (tools/bits_bench.py's sc
      upload it, wm_detect); wall-clock microseconds per image, and their ratio.  Both routes must score the same bits."""
 import argparse
 import ctypes as C
-import importlib
 import json
-import os
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def device_span_us(torch, wm, eng, enqueue, batch, n):
-    """median microseconds per call between two events on slot 0's stream around `batch` calls queued back to back"""
-    st = torch.cuda.ExternalStream(wm.lib().wm_get_stream(eng._ctx, 0))
-    ts = []
-    for _ in range(n):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(st)
-        for _ in range(batch):
-            enqueue()
-        e1.record(st)
-        eng.sync(0)
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1) * 1e3 / batch)
-    return float(np.median(ts))
-
-
-def wall_us(fn, n):
-    ts = []
-    for _ in range(n):
-        t0 = time.perf_counter()
-        fn()
-        ts.append(time.perf_counter() - t0)
-    return float(np.median(ts)) * 1e6
-
-
-def membench_gbs(wm, kind, nbytes, seconds=0.2):
-    us, n = C.c_double(), C.c_int()
-    rc = wm.lib().wm_membench(0, kind, nbytes, seconds, C.byref(us), C.byref(n))
-    assert rc == 0, rc
-    return 2 * nbytes / us.value * 1e-3  # (a copy reads and writes `nbytes`)
+import benchlib as bl
 
 
 def main():
@@ -65,9 +29,7 @@ def main():
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     import torch
-    sys.path.insert(0, ROOT)
-    wm = importlib.import_module("watermarking-gpu_amd")
-    synth = importlib.import_module("watermarking-gpu_amd.synth")
+    wm, synth = bl.load()
     R, Cc = a.rows, a.cols
     N = R * Cc
     eng = wm.Watermark(R, Cc, synth.synth_watermark(R, Cc), 3, 40.0, nslots=1, max_frames=1)
@@ -89,21 +51,18 @@ def main():
         "pack_rgb8_f32": (15 * N, lambda: eng.pack_rgb8_async(planes["rgb_f"], pk_out, 0)),
     }
     copy_bytes = 12 * N  # one planar f32 RGB image
-    rounds = {k: [] for k in conv}
-    mb = {1: [], 4: []}
     for fn in conv.values():
         for _ in range(3):
             fn[1]()
     eng.sync(0)
-    for _ in range(a.rounds):
-        for kind in mb:
-            mb[kind].append(membench_gbs(wm, kind, copy_bytes))
-        for k, (_, fn) in conv.items():
-            rounds[k].append(device_span_us(torch, wm, eng, fn, a.batch, a.iters))
-    copy1, copy4 = float(np.median(mb[1])), float(np.median(mb[4]))
+    # every entry takes its own measurement of a round: the two copies' GB/s (a copy reads and writes `copy_bytes`), then the spans
+    takes = {kind: (lambda n, kind=kind: 2 * copy_bytes / bl.membench_us(kind, copy_bytes, 0.2)[0] * 1e-3) for kind in (1, 4)}
+    takes.update({k: (lambda n, fn=fn: bl.device_span_us(eng, fn, n, a.batch)) for k, (_, fn) in conv.items()})
+    rounds = bl.alternate(takes, a.rounds, a.iters, lambda take, n: take(n))
+    copy1, copy4 = bl.median_of_rounds(rounds[1]), bl.median_of_rounds(rounds[4])
     rates = {}
     for k, (nbytes, _) in conv.items():
-        us = float(np.median(rounds[k]))
+        us = bl.median_of_rounds(rounds[k])
         gbs = nbytes / us * 1e-3
         rates[k] = {"us": round(us, 2), "us_rounds": [round(v, 2) for v in rounds[k]], "bytes": nbytes, "GBps": round(gbs, 1),
                     "of_copy_kind1": round(gbs / copy1, 3), "of_copy_kind4": round(gbs / copy4, 3)}
@@ -136,27 +95,21 @@ def main():
             eng.detect_async(pgy, mk, 0, ch)
             eng.sync(0)
 
-        for _ in range(3):
-            device_route()
-            host_route()
-        td, th = [], []
-        for _ in range(a.rounds):
-            td.append(wall_us(device_route, a.iters))
-            th.append(wall_us(host_route, max(3, a.iters // 4)))
-        d_us, h_us = float(np.median(td)), float(np.median(th))
+        t = bl.alternate({"device": device_route, "host": host_route}, a.rounds, a.iters,
+                         lambda fn, n: bl.wall_median_us(fn, n if fn is device_route else max(3, n // 4)), warm=3)
+        td, th = t["device"], t["host"]
+        d_us, h_us = bl.median_of_rounds(td), bl.median_of_rounds(th)
         r = {"mask": mk.name, "device_route_us": round(d_us, 1), "device_route_us_rounds": [round(v, 1) for v in td], "host_route_us": round(h_us, 1),
              "host_route_us_rounds": [round(v, 1) for v in th], "host_over_device": round(h_us / d_us, 1), "corr_device": cd[0], "corr_host": ch[0],
              "same_bits": bool(np.float32(cd[0]).view(np.uint32) == np.float32(ch[0]).view(np.uint32))}
         proto.append(r)
         print(json.dumps(r), flush=True)
     res = {"rows": R, "cols": Cc, "iters": a.iters, "rounds": a.rounds, "batch": a.batch, "membench_copy_GBps": {"kind1": round(copy1, 1), "kind4": round(copy4, 1),
-           "kind1_rounds": [round(v, 1) for v in mb[1]], "kind4_rounds": [round(v, 1) for v in mb[4]], "bytes_each_way": copy_bytes},
+           "kind1_rounds": [round(v, 1) for v in rounds[1]], "kind4_rounds": [round(v, 1) for v in rounds[4]], "bytes_each_way": copy_bytes},
            "conversions": rates, "protocol": proto}
     print("CONVERT_BENCH " + json.dumps(res), flush=True)
     if a.json:
-        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
-        with open(a.json, "w") as f:
-            json.dump(res, f, indent=1)
+        bl.write_json(a.json, res)
     eng.close()
 
 

@@ -10,33 +10,20 @@ on one stream followed by one wait.  Last, the round trip: wm_embed_keys, then w
 score highest at its own key.  wm_membench kinds 1 (copy) and 2 (read) are printed first as the box's yardsticks."""
 import argparse
 import ctypes as C
-import importlib
 import json
-import os
 import sys
-import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-wm = importlib.import_module("watermarking-gpu_amd")
-if os.environ.get("WM_AB_LIB"):  # another build of the library (the parent commit's)
-    wm.LIB_PATH = os.environ["WM_AB_LIB"]
-synth = importlib.import_module("watermarking-gpu_amd.synth")
+import benchlib as bl
+
+wm, synth = bl.load()
 PEAK = 8.0e12
 
 
-def median_us(fn, iters, warmup=3):
-    for _ in range(warmup):
-        fn()
-    ts = []
-    for _ in range(iters):
-        t0 = time.perf_counter()
-        fn()
-        ts.append(time.perf_counter() - t0)
-    return float(np.median(ts)) * 1e6
+def timed(fn, iters):
+    return bl.wall_median_us(fn, iters, warmup=3)
 
 
 def main():
@@ -54,12 +41,11 @@ def main():
     nb = 1 << 30
     bench = {}
     for kind, name in ((1, "copy"), (2, "read")):
-        mean_us, n = C.c_double(), C.c_int()
-        L.wm_membench(0, kind, nb, C.c_double(0.5), C.byref(mean_us), C.byref(n))
+        mean_us, n = bl.membench_us(kind, nb, 0.5)
         moved = nb * (2 if kind == 1 else 1)
-        bench[name] = moved / (mean_us.value * 1e-6)
-        print(f"wm_membench kind {kind} ({name}, {nb >> 20} MiB): {mean_us.value:.1f} us/launch = {bench[name] / 1e9:.0f} GB/s moved "
-              f"({n.value} launches)", flush=True)
+        bench[name] = moved / (mean_us * 1e-6)
+        print(f"wm_membench kind {kind} ({name}, {nb >> 20} MiB): {mean_us:.1f} us/launch = {bench[name] / 1e9:.0f} GB/s moved "
+              f"({n} launches)", flush=True)
     Ks = [int(v) for v in a.keys.split(",")]
     Kmax = max(Ks)
     seeds = [3000 + 13 * k for k in range(Kmax)]
@@ -83,7 +69,7 @@ def main():
     for K in Ks:
         pout = wm.plane_of(copies[:K], nch)
         aout = np.zeros(K, np.float32)
-        t = median_us(lambda: eng.embed_keys_async(pin, pb, pout, bank[K], mk, wm.WM_SLOT_SYNC, aout), a.iters)
+        t = timed(lambda: eng.embed_keys_async(pin, pb, pout, bank[K], mk, wm.WM_SLOT_SYNC, aout), a.iters)
         if K == 1:
             t1 = t
         marg = (t - t1) / (K - 1) if K > 1 and t1 is not None else None
@@ -103,8 +89,8 @@ def main():
             for e in ctxs[:K]:
                 L.wm_sync(e._ctx, 0)
 
-        ts = median_us(sync_calls, max(3, a.iters // 4))
-        tq = median_us(queued, max(3, a.iters // 4))
+        ts = timed(sync_calls, max(3, a.iters // 4))
+        tq = timed(queued, max(3, a.iters // 4))
         r = {"K": K, "embed_keys_us": round(t, 1), "marginal_us_per_key": round(marg, 2) if marg is not None else None,
              "key_planes": key_planes, "key_planes_estimate_us": round(est_key_us, 2), "marginal_over_estimate": round(marg / est_key_us, 3) if marg is not None else None,
              "alg_bytes": alg, "frac_of_8TBs": round(alg / (t * 1e-6) / PEAK, 3), "K_sync_embed_us": round(ts, 1),
@@ -123,8 +109,8 @@ def main():
         e.close()
     eng.close()
     if a.json:
-        with open(a.json, "w") as f:
-            json.dump({"rows": R, "cols": Cc, "mask": a.mask, "base": a.base, "membench_bytes_per_s": bench, "results": rows, "round_trip": rt}, f, indent=1, allow_nan=False)
+        bl.write_json(a.json, {"rows": R, "cols": Cc, "mask": a.mask, "base": a.base, "membench_bytes_per_s": bench, "results": rows, "round_trip": rt},
+                      allow_nan=False)
     if hits != K:
         sys.exit(1)
 

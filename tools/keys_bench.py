@@ -8,33 +8,19 @@ wm_detect calls (one image: the fused single-launch kernels) and K wm_detect cal
 wm_membench kind 2 (pure read) is printed first as the box's read-rate yardstick."""
 import argparse
 import ctypes as C
-import importlib
 import json
-import os
-import sys
-import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-wm = importlib.import_module("watermarking-gpu_amd")
-if os.environ.get("WM_AB_LIB"):  # development A/B runs: another build of the library (tools/ab.py)
-    wm.LIB_PATH = os.environ["WM_AB_LIB"]
-synth = importlib.import_module("watermarking-gpu_amd.synth")
+import benchlib as bl
+
+wm, synth = bl.load()
 PEAK = 8.0e12
 
 
-def median_us(fn, iters, warmup=3):
-    for _ in range(warmup):
-        fn()
-    ts = []
-    for _ in range(iters):
-        t0 = time.perf_counter()
-        fn()
-        ts.append(time.perf_counter() - t0)
-    return float(np.median(ts)) * 1e6
+def timed(fn, iters):
+    return bl.wall_median_us(fn, iters, warmup=3)
 
 
 def main():
@@ -49,10 +35,9 @@ def main():
     a = ap.parse_args()
     L = wm.lib()
     R, Cc, mk = a.rows, a.cols, wm.MASK_TYPE(a.mask)
-    mean_us, n = C.c_double(), C.c_int()
     nb = 1 << 30
-    L.wm_membench(0, 2, nb, C.c_double(0.5), C.byref(mean_us), C.byref(n))
-    print(f"wm_membench kind 2 (read, {nb >> 20} MiB): {mean_us.value:.1f} us/launch = {nb / mean_us.value / 1e3:.0f} GB/s ({n.value} launches)")
+    mean_us, n = bl.membench_us(2, nb, 0.5)
+    print(f"wm_membench kind 2 (read, {nb >> 20} MiB): {mean_us:.1f} us/launch = {nb / mean_us / 1e3:.0f} GB/s ({n} launches)")
     Ks = [int(v) for v in a.keys.split(",")]
     Fs = [int(v) for v in a.frames.split(",")]
     seeds = [1000 + 17 * k for k in range(max(Ks))]
@@ -73,7 +58,7 @@ def main():
         t1 = None
         for K in Ks:
             out = np.zeros(F * K, np.float32)
-            t = median_us(lambda: eng.detect_keys_async(pimg, bank[K], mk, wm.WM_SLOT_SYNC, out), a.iters)
+            t = timed(lambda: eng.detect_keys_async(pimg, bank[K], mk, wm.WM_SLOT_SYNC, out), a.iters)
             if K == 1:
                 t1 = t
             marg = (t - t1) / (K - 1) if K > 1 and t1 is not None else float("nan")
@@ -90,8 +75,8 @@ def main():
                 for e in ctxs[:K]:
                     L.wm_sync(e._ctx, 0)
 
-            ts = median_us(sync_calls, max(3, a.iters // 4))
-            tq = median_us(queued, max(3, a.iters // 4))
+            ts = timed(sync_calls, max(3, a.iters // 4))
+            tq = timed(queued, max(3, a.iters // 4))
             r = {"K": K, "F": F, "detect_keys_us": round(t, 1), "marginal_us_per_key": round(marg, 2), "alg_bytes": alg,
                  "frac_of_8TBs": round(frac, 3), "K_sync_detect_us": round(ts, 1), "K_queued_detect_us": round(tq, 1),
                  "ratio_vs_queued": round(t / tq, 3)}
@@ -101,8 +86,7 @@ def main():
             e.close()
         eng.close()
     if a.json:
-        with open(a.json, "w") as f:
-            json.dump({"rows": R, "cols": Cc, "mask": a.mask, "membench_read_us": mean_us.value, "results": rows}, f, indent=1)
+        bl.write_json(a.json, {"rows": R, "cols": Cc, "mask": a.mask, "membench_read_us": mean_us, "results": rows})
 
 
 if __name__ == "__main__":

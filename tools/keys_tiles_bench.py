@@ -12,57 +12,37 @@ over --rounds rounds of the median of --iters synchronous calls, in microseconds
 children.  f32 frames.  wm_membench kind 2 (pure read) is printed first as the box's read-rate yardstick.  Without --parent-lib one
 process times what this build has."""
 import argparse
-import ctypes as C
-import importlib
 import json
 import os
 import subprocess
 import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import benchlib as bl
+
+ROOT = bl.ROOT
 TAG = "KEYS_TILES_BENCH "
 
 
-def round_median_us(fn, iters):
-    ts = []
-    for _ in range(iters):
-        t0 = time.perf_counter()
-        fn()
-        ts.append(time.perf_counter() - t0)
-    return float(np.median(ts)) * 1e6
-
-
 def timed(fn, a):
-    for _ in range(3):
-        fn()
-    rounds = [round_median_us(fn, a.iters) for _ in range(a.rounds)]
-    return round(float(np.median(rounds)), 1), [round(v, 1) for v in rounds]
+    rounds = bl.alternate({"fn": fn}, a.rounds, a.iters, bl.wall_median_us, warm=3)["fn"]
+    return round(bl.median_of_rounds(rounds), 1), [round(v, 1) for v in rounds]
 
 
 def child(a):
     import torch
-    sys.path.insert(0, ROOT)
-    wm = importlib.import_module("watermarking-gpu_amd")
-    if os.environ.get("WM_AB_LIB"):  # another build of the library (the parent commit's)
-        wm.LIB_PATH = os.environ["WM_AB_LIB"]
-        _L = C.CDLL(wm.LIB_PATH)   # an older build lacks the entries added since (wm_detect_keys_tiles): bind what it has
-        wm.ABI = [e for e in wm.ABI if hasattr(_L, e[0])]
-    synth = importlib.import_module("watermarking-gpu_amd.synth")
-    L = wm.lib()
-    has_kt = hasattr(L, "wm_detect_keys_tiles")
+    wm, synth = bl.load()
+    has_kt = hasattr(wm.lib(), "wm_detect_keys_tiles")  # (an older build, named by WM_AB_LIB, lacks it)
     R, Cc, mk = a.rows, a.cols, wm.MASK_TYPE(a.mask)
     th, tw = (int(v) for v in a.tile.split("x"))
     ny, nx = wm.Watermark.tiles_shape(R, Cc, th, tw)
     res = {"lib": os.path.basename(wm.LIB_PATH), "has_keys_tiles": has_kt, "cases": []}
     if a.membench:
-        mean_us, n = C.c_double(), C.c_int()
         nb = 1 << 30
-        L.wm_membench(0, 2, nb, C.c_double(0.5), C.byref(mean_us), C.byref(n))
-        res["membench_read_us"] = round(mean_us.value, 1)
-        res["membench_read_gbs"] = round(nb / mean_us.value / 1e3)
+        mean_us, _ = bl.membench_us(2, nb, 0.5)
+        res["membench_read_us"] = round(mean_us, 1)
+        res["membench_read_gbs"] = round(nb / mean_us / 1e3)
     Kmax = max(a.keys)
     seeds = [7100 + k for k in range(Kmax)]
     for F in a.frames:
@@ -125,8 +105,7 @@ def main():
     if a.child or not a.parent_lib:
         res = child(a)
         if a.json and not a.child:
-            with open(a.json, "w") as f:
-                json.dump(dict(meta, run=res), f, indent=1)
+            bl.write_json(a.json, dict(meta, run=res))
         return
     libs = [("parent", os.path.join(ROOT, a.parent_lib) if not os.path.isabs(a.parent_lib) else a.parent_lib), ("this", None)]
     runs = {"parent": [], "this": []}
@@ -161,9 +140,8 @@ def main():
         summary.append(s)
         print(json.dumps(s), flush=True)
     if a.json:
-        with open(a.json, "w") as f:
-            json.dump(dict(meta, reps=a.reps, membench={k: v for k, v in runs["parent"][0].items() if k.startswith("membench")}, summary=summary,
-                           runs=runs), f, indent=1)
+        bl.write_json(a.json, dict(meta, reps=a.reps, membench={k: v for k, v in runs["parent"][0].items() if k.startswith("membench")}, summary=summary,
+                                   runs=runs))
 
 
 if __name__ == "__main__":

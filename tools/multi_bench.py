@@ -14,48 +14,25 @@ slope of B between K = 16 and K = 64 in microseconds per extra copy, beside the 
 (wm_membench kind 0 over rows * cols * 4 bytes, and over the copy's own size for u8): the claim to test is that the slope lies
 closer to that store than to A's time per copy."""
 import argparse
-import ctypes as C
-import importlib
 import json
 import os
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import benchlib as bl
 
 
-def membench_us(wm, kind, nbytes, seconds=0.3):
-    us, n = C.c_double(), C.c_int()
-    rc = wm.lib().wm_membench(0, kind, nbytes, seconds, C.byref(us), C.byref(n))
-    assert rc == wm.WM_OK, rc
-    return round(us.value, 1)
-
-
-def timed(torch, eng, st, route):
-    """(device span, host wall) of one repeat in microseconds"""
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0 = time.perf_counter()
-    e0.record(st)
-    route()
-    e1.record(st)
-    eng.sync(0)
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e3, (time.perf_counter() - t0) * 1e6
-
-
-def rounds_of(torch, eng, st, fa, fb, rounds, iters, warm=2):
+def rounds_of(eng, fa, fb, rounds, iters, warm=2):
+    """{"A" / "B": (device medians of the rounds, wall medians of the rounds)}, device and wall taken from the same repeats"""
     for _ in range(warm):
-        timed(torch, eng, st, fa)
-        timed(torch, eng, st, fb)
-    out = {"A": ([], []), "B": ([], [])}
-    for _ in range(rounds):
-        for name, fn in (("A", fa), ("B", fb)):
-            ts = [timed(torch, eng, st, fn) for _ in range(iters)]
-            out[name][0].append(round(float(np.median([t[0] for t in ts])), 1))
-            out[name][1].append(round(float(np.median([t[1] for t in ts])), 1))
-    return out
+        bl.span_and_wall_us(eng, fa)
+        bl.span_and_wall_us(eng, fb)
+
+    def medians(fn, n):
+        ts = [bl.span_and_wall_us(eng, fn) for _ in range(n)]
+        return round(float(np.median([t[0] for t in ts])), 1), round(float(np.median([t[1] for t in ts])), 1)
+
+    return {name: tuple(zip(*r)) for name, r in bl.alternate({"A": fa, "B": fb}, rounds, iters, medians).items()}
 
 
 def main():
@@ -70,18 +47,14 @@ def main():
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     import torch
-    sys.path.insert(0, ROOT)
-    wm = importlib.import_module("watermarking-gpu_amd")
-    if os.environ.get("WM_AB_LIB"):  # another build of the library
-        wm.LIB_PATH = os.environ["WM_AB_LIB"]
-    synth = importlib.import_module("watermarking-gpu_amd.synth")
+    wm, synth = bl.load()
     R, Cc = a.rows, a.cols
     th, tw = (int(v) for v in a.tile.split("x"))
     ny, nx = wm.Watermark.tiles_shape(R, Cc, th, tw)
     Ks = [int(v) for v in a.copies.split(",")]
     W = synth.synth_watermark(R, Cc)
     xf = synth.synth_frames_torch(R, Cc, 2, "cuda")  # frame 0: the input; frame 1: the grey base of the f32 setup
-    store = {"store_plane_f32_us": membench_us(wm, 0, R * Cc * 4), "store_plane_u8_us": membench_us(wm, 0, R * Cc)}
+    store = {"store_plane_f32_us": round(bl.membench_us(0, R * Cc * 4, 0.3)[0], 1), "store_plane_u8_us": round(bl.membench_us(0, R * Cc, 0.3)[0], 1)}
     print(json.dumps(store), flush=True)
     cases, slopes = [], []
     for mask in (int(v) for v in a.masks.split(",")):
@@ -94,7 +67,6 @@ def main():
             eng = wm.Watermark(R, Cc, W, 3, 40.0, nslots=1, max_frames=1)
             eng.set_fused(False)
             eng.set_checked_handover(False)
-            st = torch.cuda.ExternalStream(wm.lib().wm_get_stream(eng._ctx, 0))
             by_k = {}
             for K in Ks:
                 signs = (2 * np.random.default_rng(K).integers(0, 2, (1, K, ny, nx)) - 1).astype(np.int8)
@@ -120,7 +92,7 @@ def main():
                 eng.sync(0)
                 same = bool(torch.equal(ya, out))
                 del ya
-                r = rounds_of(torch, eng, st, route_a, route_b, a.rounds, a.iters)
+                r = rounds_of(eng, route_a, route_b, a.rounds, a.iters)
                 ua, ub = float(np.median(r["A"][0])), float(np.median(r["B"][0]))
                 c = {"mask": mk.name, "setup": setup, "K": K, "same_bits": same,
                      "A_device_us": round(ua, 1), "A_device_us_rounds": r["A"][0], "A_wall_us": round(float(np.median(r["A"][1])), 1),
@@ -144,8 +116,7 @@ def main():
            "lib": os.environ.get("WM_AB_LIB") and "WM_AB_LIB" or "tree", **store, "cases": cases, "slopes": slopes}
     print("MULTI_BENCH " + json.dumps(res), flush=True)
     if a.json:
-        with open(a.json, "w") as f:
-            json.dump(res, f, indent=1)
+        bl.write_json(a.json, res)
 
 
 if __name__ == "__main__":

@@ -9,31 +9,14 @@ median of the rounds' medians, and their spread), the marginal microseconds per 
 same for the parent route where its bank is at most --max-bank planes, and the bank memory the new call avoids.  wm_membench
 kind 2 (pure read) is printed first as the box's read-rate yardstick."""
 import argparse
-import ctypes as C
-import importlib
 import json
-import os
-import sys
-import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-wm = importlib.import_module("watermarking-gpu_amd")
-if os.environ.get("WM_AB_LIB"):  # development A/B runs: another build of the library (tools/ab.py)
-    wm.LIB_PATH = os.environ["WM_AB_LIB"]
-synth = importlib.import_module("watermarking-gpu_amd.synth")
+import benchlib as bl
 
-
-def round_median_us(fn, iters):
-    ts = []
-    for _ in range(iters):
-        t0 = time.perf_counter()
-        fn()
-        ts.append(time.perf_counter() - t0)
-    return float(np.median(ts)) * 1e6
+wm, synth = bl.load()
 
 
 def main():
@@ -50,10 +33,9 @@ def main():
     a = ap.parse_args()
     L = wm.lib()
     R, Cc, mk = a.rows, a.cols, wm.MASK_TYPE(a.mask)
-    mean_us, n = C.c_double(), C.c_int()
     nb = 1 << 30
-    L.wm_membench(0, 2, nb, C.c_double(0.5), C.byref(mean_us), C.byref(n))
-    print(f"wm_membench kind 2 (read, {nb >> 20} MiB): {mean_us.value:.1f} us/launch = {nb / mean_us.value / 1e3:.0f} GB/s ({n.value} launches)")
+    mean_us, n = bl.membench_us(2, nb, 0.5)
+    print(f"wm_membench kind 2 (read, {nb >> 20} MiB): {mean_us:.1f} us/launch = {nb / mean_us / 1e3:.0f} GB/s ({n} launches)")
     print(f"offsets per group (shared key row): {L.wm_detect_offsets_group()}")
     rects = [(1, 1)] + [tuple(int(v) for v in r.split("x")) for r in a.rects.split(",")]
     Fs = [int(v) for v in a.frames.split(",")]
@@ -85,18 +67,11 @@ def main():
             new = lambda: eng.detect_offsets_async(pimg, keys, 0, oy0, ox0, ny, nx, mk, wm.WM_SLOT_SYNC, out_o)
             bank = banks.get((ny, nx))
             old = (lambda: eng.detect_keys_async(pimg, bank, mk, wm.WM_SLOT_SYNC, out_k)) if bank is not None else None
-            for _ in range(3):
-                new()
-                if old:
-                    old()
-            tn, to = [], []
-            for _ in range(a.rounds):  # the routes alternate
-                tn.append(round_median_us(new, a.iters))
-                if old:
-                    to.append(round_median_us(old, a.iters))
+            t = bl.alternate({"new": new, "old": old}, a.rounds, a.iters, bl.wall_median_us, warm=3)  # the routes alternate
+            tn, to = t["new"], t.get("old", [])
             if old:
                 assert np.array_equal(out_o.view(np.uint32), out_k.view(np.uint32)), "the two routes must give the same bits"
-            t_new, t_old = float(np.median(tn)), (float(np.median(to)) if old else None)
+            t_new, t_old = bl.median_of_rounds(tn), (bl.median_of_rounds(to) if old else None)
             if K == 1:
                 base[F] = (t_new, t_old)
             r = {"ny": ny, "nx": nx, "F": F, "offsets_us": round(t_new, 1), "offsets_us_rounds": [round(v, 1) for v in tn],
@@ -109,9 +84,8 @@ def main():
             print(json.dumps(r), flush=True)
         eng.close()
     if a.json:
-        with open(a.json, "w") as f:
-            json.dump({"rows": R, "cols": Cc, "mask": a.mask, "key_rows": KR, "key_cols": KC, "group": L.wm_detect_offsets_group(),
-                       "membench_read_us": mean_us.value, "iters": a.iters, "rounds": a.rounds, "results": results}, f, indent=1)
+        bl.write_json(a.json, {"rows": R, "cols": Cc, "mask": a.mask, "key_rows": KR, "key_cols": KC, "group": L.wm_detect_offsets_group(),
+                               "membench_read_us": mean_us, "iters": a.iters, "rounds": a.rounds, "results": results})
 
 
 if __name__ == "__main__":

@@ -10,38 +10,11 @@ tiles.  Beside every wm_quality time, from the same rounds:
   - one wm_embed (ME, batched sweeps) of the same frames: in_gray = the first channel of the base, base and out with the call's
     channels -- what checking a copy costs beside making it."""
 import argparse
-import ctypes as C
-import importlib
 import json
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def device_span_us(torch, wm, eng, enqueue, batch, n):
-    """median microseconds per call between two events on slot 0's stream around `batch` calls queued back to back"""
-    st = torch.cuda.ExternalStream(wm.lib().wm_get_stream(eng._ctx, 0))
-    ts = []
-    for _ in range(n):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(st)
-        for _ in range(batch):
-            enqueue()
-        e1.record(st)
-        eng.sync(0)
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1) * 1e3 / batch)
-    return float(np.median(ts))
-
-
-def membench_us(wm, kind, nbytes, seconds=0.15):
-    us, n = C.c_double(), C.c_int()
-    rc = wm.lib().wm_membench(0, kind, nbytes, seconds, C.byref(us), C.byref(n))
-    assert rc == 0, rc
-    return us.value
+import benchlib as bl
 
 
 def main():
@@ -55,9 +28,7 @@ def main():
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     import torch
-    sys.path.insert(0, ROOT)
-    wm = importlib.import_module("watermarking-gpu_amd")
-    synth = importlib.import_module("watermarking-gpu_amd.synth")
+    wm, synth = bl.load()
     R, Cc = a.rows, a.cols
     Fmax = max(a.frames)
     eng = wm.Watermark(R, Cc, synth.synth_watermark(R, Cc), 3, 40.0, nslots=1, max_frames=Fmax)
@@ -88,16 +59,11 @@ def main():
                         for _ in range(2):
                             fn()
                     eng.sync(0)
-                    t = {k: [] for k in routes}
-                    mb = {2: [], 5: []}
-                    for _ in range(a.rounds):
-                        for k in mb:
-                            mb[k].append(membench_us(wm, k, nbytes))
-                        for k, fn in routes.items():
-                            t[k].append(device_span_us(torch, wm, eng, fn, a.batch, a.iters))
-                    us = float(np.median(t["quality"]))
-                    emb = float(np.median(t["embed"]))
-                    r2, r5 = float(np.median(mb[2])), float(np.median(mb[5]))
+                    # every entry takes its own measurement of a round: the two reads of `nbytes`, then the two spans
+                    takes = {k: (lambda n, k=k: bl.membench_us(k, nbytes, 0.15)[0]) for k in (2, 5)}
+                    takes.update({k: (lambda n, fn=fn: bl.device_span_us(eng, fn, n, a.batch)) for k, fn in routes.items()})
+                    t = bl.alternate(takes, a.rounds, a.iters, lambda take, n: take(n))
+                    us, emb, r2, r5 = (bl.median_of_rounds(t[k]) for k in ("quality", "embed", 2, 5))
                     r = {"frames": F, "dtype": kind, "channels": ch, "tile": list(tile), "quality_us": round(us, 2), "quality_us_rounds": [round(v, 2) for v in t["quality"]],
                          "us_per_plane_pair": round(us / (F * ch), 2), "bytes_read": nbytes, "GBps": round(nbytes / us * 1e-3, 1),
                          "read_kind2_us": round(r2, 2), "read_kind5_us": round(r5, 2), "time_over_read_kind2": round(us / r2, 2), "time_over_read_kind5": round(us / r5, 2),
@@ -108,9 +74,7 @@ def main():
     res = {"rows": R, "cols": Cc, "iters": a.iters, "rounds": a.rounds, "batch": a.batch, "results": results}
     print("QUALITY_BENCH " + json.dumps(res), flush=True)
     if a.json:
-        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
-        with open(a.json, "w") as f:
-            json.dump(res, f, indent=1)
+        bl.write_json(a.json, res)
     eng.close()
 
 

@@ -1,6 +1,5 @@
 """ad-hoc timing helper for development runs on the GPU box (not part of the test suite)"""
 import ctypes as C
-import importlib
 import os
 import sys
 import time
@@ -8,14 +7,9 @@ import time
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-wm = importlib.import_module("watermarking-gpu_amd")
-if os.environ.get("WM_AB_LIB"):  # development A/B runs: another build of the library (tools/ab.py)
-    wm.LIB_PATH = os.environ["WM_AB_LIB"]
-    _L = C.CDLL(wm.LIB_PATH)   # an older build may lack entries added since: bind what it has
-    wm.ABI = [e for e in wm.ABI if hasattr(_L, e[0])]
-synth = importlib.import_module("watermarking-gpu_amd.synth")
+import benchlib as bl
+
+wm, synth = bl.load()  # (WM_AB_LIB, set by tools/ab.py: another build of the library)
 
 
 def fake_frames(rows, cols, F, dtype=torch.float32):

@@ -22,24 +22,14 @@ per-key contexts of (b) write.  The per-sweep split of (c) - (a) comes from a ke
 not in the wm_prof_* list."""
 import argparse
 import csv
-import ctypes as C
-import importlib
 import json
-import os
 import re
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import benchlib as bl
+
 SWEEPS = (("stats", ("k_me_stats", "k_nvf_stats")), ("embed", ("k_embed",)), ("detect", ("k_detect",)), ("gram", ("k_gram",)))
-
-
-def membench_us(wm, kind, nbytes, seconds=0.1):
-    us, n = C.c_double(), C.c_int()
-    rc = wm.lib().wm_membench(0, kind, nbytes, seconds, C.byref(us), C.byref(n))
-    assert rc == 0, rc
-    return us.value
 
 
 def from_trace(path):
@@ -91,9 +81,7 @@ def main():
 
     def write(res):
         if a.json:
-            os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
-            with open(a.json, "w") as f:
-                json.dump(res, f, indent=1)
+            bl.write_json(a.json, res)
 
     if a.from_trace:
         res = {"per_sweep_from_kernel_trace": from_trace(a.from_trace)}
@@ -101,9 +89,7 @@ def main():
         return write(res)
 
     import torch
-    sys.path.insert(0, ROOT)
-    wm = importlib.import_module("watermarking-gpu_amd")
-    synth = importlib.import_module("watermarking-gpu_amd.synth")
+    wm, synth = bl.load()
     R, Cc, F = a.rows, a.cols, a.frames
     plane_bytes = R * Cc * 4
     seeds = [3000 + 7 * k for k in range(F)]
@@ -191,7 +177,7 @@ def main():
         t = {op: {leg: [] for leg in legs} for op in ("embed", "detect")}
         for _ in range(a.rounds):
             for kind in mb:
-                mb[kind].append(membench_us(wm, kind, (F - 1) * plane_bytes))
+                mb[kind].append(bl.membench_us(kind, (F - 1) * plane_bytes, 0.1)[0])
             for leg in legs:
                 t["embed"][leg].append(span_us(embed, leg, a.iters))
                 t["detect"][leg].append(span_us(detect, leg, a.iters))

@@ -11,63 +11,34 @@ the two builds --reps times (tools/ab.py's scheme), each child timing what its b
 medians over the children.  wm_membench kind 2 (pure read) is printed first as the box's read-rate yardstick."""
 import argparse
 import ctypes as C
-import importlib
 import json
 import os
 import subprocess
 import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import benchlib as bl
+
+ROOT = bl.ROOT
 
 
-def round_median_us(fn, iters):
-    ts = []
-    for _ in range(iters):
-        t0 = time.perf_counter()
-        fn()
-        ts.append(time.perf_counter() - t0)
-    return float(np.median(ts)) * 1e6
-
-
-def prof(eng, wm, fn, n):
-    L = wm.lib()
-    L.wm_prof_reset(eng._ctx)
-    L.wm_prof_enable(eng._ctx, 1)
-    for _ in range(n):
-        fn()
-    out = {}
-    for k in range(L.wm_prof_kernel_count()):
-        cnt, ms = C.c_uint64(), C.c_double()
-        L.wm_prof_get(eng._ctx, k, C.byref(cnt), C.byref(ms))
-        if cnt.value:
-            out[L.wm_prof_kernel_name(k).decode()] = round(ms.value * 1e3 / cnt.value, 2)
-    L.wm_prof_enable(eng._ctx, 0)
-    return out
+def kernels_us(eng, fn, n):
+    return {k: round(v, 2) for k, v in bl.prof_us_per_launch(eng, fn, n).items()}
 
 
 def child(a):
     import torch
-    sys.path.insert(0, ROOT)
-    wm = importlib.import_module("watermarking-gpu_amd")
-    if os.environ.get("WM_AB_LIB"):  # another build of the library (the parent commit's)
-        wm.LIB_PATH = os.environ["WM_AB_LIB"]
-        _L = C.CDLL(wm.LIB_PATH)   # an older build lacks the entries added since (wm_detect_tiles): bind what it has
-        wm.ABI = [e for e in wm.ABI if hasattr(_L, e[0])]
-    synth = importlib.import_module("watermarking-gpu_amd.synth")
-    L = wm.lib()
-    has_tiles = hasattr(L, "wm_detect_tiles")
+    wm, synth = bl.load()
+    has_tiles = hasattr(wm.lib(), "wm_detect_tiles")  # (an older build, named by WM_AB_LIB, lacks it)
     R, Cc, mk = a.rows, a.cols, wm.MASK_TYPE(a.mask)
     th, tw = (int(v) for v in a.tile.split("x"))
     res = {"lib": os.path.basename(wm.LIB_PATH), "has_tiles": has_tiles, "cases": []}
     if a.membench:
-        mean_us, n = C.c_double(), C.c_int()
         nb = 1 << 30
-        L.wm_membench(0, 2, nb, C.c_double(0.5), C.byref(mean_us), C.byref(n))
-        res["membench_read_us"] = round(mean_us.value, 1)
-        res["membench_read_gbs"] = round(nb / mean_us.value / 1e3)
+        mean_us, _ = bl.membench_us(2, nb, 0.5)
+        res["membench_read_us"] = round(mean_us, 1)
+        res["membench_read_gbs"] = round(nb / mean_us / 1e3)
     W = synth.synth_watermark(R, Cc)
     for case in a.cases.split(","):
         dt, F = case.split(":")
@@ -85,20 +56,13 @@ def child(a):
             sm = torch.empty((F, ny, nx, 3), dtype=torch.float64, device="cuda")
             til = lambda: eng.detect_tiles_async(pimg, th, tw, mk, wm.WM_SLOT_SYNC, mp, sm)
         torch.cuda.synchronize()
-        for _ in range(5):
-            det()
-            if til:
-                til()
-        td, tt = [], []
-        for _ in range(a.rounds):  # the two calls alternate
-            td.append(round_median_us(det, a.iters))
-            if til:
-                tt.append(round_median_us(til, a.iters))
+        t = bl.alternate({"det": det, "til": til}, a.rounds, a.iters, bl.wall_median_us, warm=5)  # the two calls alternate
+        td, tt = t["det"], t.get("til")
         r = {"dtype": dt, "F": F, "detect_us": round(float(np.median(td)), 1), "detect_us_rounds": [round(v, 1) for v in td],
-             "detect_kernels_us": prof(eng, wm, det, 10)}
+             "detect_kernels_us": kernels_us(eng, det, 10)}
         if til:
             r.update(tiles_us=round(float(np.median(tt)), 1), tiles_us_rounds=[round(v, 1) for v in tt],
-                     ratio_tiles_over_detect=round(float(np.median(tt)) / float(np.median(td)), 3), tiles_kernels_us=prof(eng, wm, til, 10))
+                     ratio_tiles_over_detect=round(float(np.median(tt)) / float(np.median(td)), 3), tiles_kernels_us=kernels_us(eng, til, 10))
         res["cases"].append(r)
         eng.close()
     print("TILES_BENCH " + json.dumps(res), flush=True)
@@ -123,8 +87,7 @@ def main():
     if a.child or not a.parent_lib:
         res = child(a)
         if a.json and not a.child:
-            with open(a.json, "w") as f:
-                json.dump({"rows": a.rows, "cols": a.cols, "tile": a.tile, "mask": a.mask, "iters": a.iters, "rounds": a.rounds, "run": res}, f, indent=1)
+            bl.write_json(a.json, {"rows": a.rows, "cols": a.cols, "tile": a.tile, "mask": a.mask, "iters": a.iters, "rounds": a.rounds, "run": res})
         return
     # alternating child processes: the parent build (its wm_detect is the yardstick), then this build
     libs = [("parent", os.path.join(ROOT, a.parent_lib) if not os.path.isabs(a.parent_lib) else a.parent_lib), ("this", None)]
@@ -159,9 +122,8 @@ def main():
         summary.append(s)
         print(json.dumps(s), flush=True)
     if a.json:
-        with open(a.json, "w") as f:
-            json.dump({"rows": a.rows, "cols": a.cols, "tile": a.tile, "mask": a.mask, "iters": a.iters, "rounds": a.rounds, "reps": a.reps,
-                       "membench": {k: v for k, v in runs["parent"][0].items() if k.startswith("membench")}, "summary": summary, "runs": runs}, f, indent=1)
+        bl.write_json(a.json, {"rows": a.rows, "cols": a.cols, "tile": a.tile, "mask": a.mask, "iters": a.iters, "rounds": a.rounds, "reps": a.reps,
+                               "membench": {k: v for k, v in runs["parent"][0].items() if k.startswith("membench")}, "summary": summary, "runs": runs})
 
 
 if __name__ == "__main__":
