@@ -766,6 +766,11 @@ int wm_gram(wm_ctx* ctx, const wm_plane* img, double* gram_out, int slot);
  *   embed : wm_gram (44 sums) -> SUM -> wm_band_solve -> wm_band_stats ({max|e|, sum}) -> MAX, SUM -> wm_band_embed
  *   detect: halo rows of y from the neighbour bands -> wm_gram -> SUM -> wm_band_solve
  *           -> wm_band_detect_sums ({<e_u,e_w>, |e_u|^2, |e_w|^2}) -> SUM -> corr = (float)dot / (float)(sqrt(nw) * sqrt(nu))
+ * The halo rule bounds the split as well: the rows below a band's owned rows are its lower neighbours' owned rows, so the band
+ * that holds the image's bottom border owns at least p/2 + 1 >= 2 rows (the top band likewise).  The Gram sweep relies on it: it
+ * sums the window rows R-2, R-1 and R of the image in the band with own_hi == rows, and every band above stops at R-3.  A split
+ * whose last band is the image's last row alone is therefore refused -- at the band above, which would hold one row below its own
+ * ("an interior side needs 2 halo rows").
  * All five calls are synchronous.  own_hi == 0 switches band mode off.  In band mode wm_embed / wm_detect see only the
  * band and are not meaningful. */
 int wm_band_configure(wm_ctx* ctx, int own_lo, int own_hi, long long rows_global);

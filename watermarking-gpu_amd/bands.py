@@ -48,6 +48,19 @@ def band_with_halo(rows, rank, world, halo=HALO):
     return g0, g1, r0 - g0, r1 - g0
 
 
+def check_split(rows, world, p):
+    """refuses a split in which some rank owns fewer rows than the halo (pure: no GPU, no engine).  exchange_halos sends the
+    first and the last `halo` OWNED rows of a band; a band that owns fewer would send rows of its own halo, which are stale after
+    an embed.  It also keeps band_with_halo inside wm_band_configure's halo rule, which wants the halo's rows on every interior
+    side: the rows below the last band's neighbour (above the first band's) are the last (first) band's owned rows"""
+    halo = halo_rows(p)
+    if world < 1 or rows < 1:
+        raise ValueError(f"bad split: rows = {rows}, world = {world}")
+    if world > 1 and rows // world < halo:
+        raise ValueError(f"rows = {rows} over world = {world} ranks leaves a rank {rows // world} rows, fewer than the {halo} halo rows "
+                         f"of p = {p}: use at most {rows // halo} ranks")
+
+
 def _allreduce(values, op, device):
     t = torch.tensor(values, dtype=torch.float64, device=device)
     if dist.is_initialized() and dist.get_world_size() > 1:
@@ -62,6 +75,7 @@ class BandedWatermark:
     coll_device: where the tiny collective tensors live ("cuda" for nccl, "cpu" for gloo)."""
 
     def __init__(self, rows, cols, W, p, psnr, rank, world, device=0, coll_device=None):
+        check_split(rows, world, p)
         wm = importlib.import_module(__package__)
         self.wm = wm
         self.rows, self.cols, self.rank, self.world = rows, cols, rank, world
