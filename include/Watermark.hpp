@@ -137,6 +137,10 @@ struct Quality { float mse, psnr, ssim, maxAbs; };
 
 }  // namespace wm
 
+// What Watermark::locate finds per frame (wm.h wm_locate): the offset of the crop in its key, the map value there (the detector's
+// <e_u, e_w> against that window) and its distance from the rest of the map in standard deviations (NaN: no such measure)
+struct WmLocation { int oy, ox; float peak, z; };
+
 // A bank of watermark keys on one device (wm.h wm_keys_*): what Watermark::detectWatermarkKeys scores one image against.
 // Owns its device planes; movable, not copyable.  Errors throw std::runtime_error like the Watermark methods.
 class WatermarkKeys {
@@ -342,6 +346,19 @@ public:
         const int rc = wm_detect_offsets(ctx, (int)maskType, &pimg, keys.handle(), k, oy0, ox0, ny, nx, corr.data(), nullptr, WM_SLOT_SYNC);
         if (rc < 0) fail(rc, "detectOffsets");
         return corr;
+    }
+    // where does a cropped copy lie in its key, without a hint?  One grey image (or a batch: one entry per frame) cross-correlated
+    // with key k of `keys` over EVERY admissible offset by FFT (wm.h wm_locate).  An unsolvable frame gives {0, 0, 0, 0};
+    // detectOffsets with ny = nx = 1 at the offset found gives the score
+    std::vector<WmLocation> locate(const wm::Image& watermarkedImage, const WatermarkKeys& keys, int k, MASK_TYPE maskType) const
+    {
+        const wm_plane pimg = watermarkedImage.plane();
+        std::vector<float> v((size_t)pimg.frames * WM_LOCATE_NVALS, 0.0f);
+        const int rc = wm_locate(ctx, (int)maskType, &pimg, keys.handle(), k, v.data(), nullptr, nullptr, WM_SLOT_SYNC);
+        if (rc < 0) fail(rc, "locate");
+        std::vector<WmLocation> out((size_t)pimg.frames);
+        for (size_t f = 0; f < out.size(); ++f) out[f] = WmLocation{(int)v[4 * f], (int)v[4 * f + 1], v[4 * f + 2], v[4 * f + 3]};
+        return out;
     }
     // where in the frame is the mark?  detectWatermark of one grey image against this engine's W with the correlation's three sums
     // kept per tile of tileRows x tileCols pixels (wm.h wm_detect_tiles; the last tile of each axis takes the remainder): score

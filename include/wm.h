@@ -297,6 +297,53 @@ int wm_detect_offsets_group(void);  /* G: horizontally adjacent offsets that sha
 int wm_detect_offsets(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* keys, int k, int oy0, int ox0, int ny, int nx,
                       float* corr_out, int* status_out, int slot);
 
+/* ---- Crop search without a hint: every admissible offset at once, by FFT -----------------------------------------------------
+ * wm_detect_offsets searches a rectangle of offsets the caller suspects, at most 4096 per call.  wm_locate names the offset among
+ * ALL of them.  With the frame's coefficients c solved, the detector's numerator is linear in W:
+ *     <e_u, e_w>(oy, ox) = sum_q h(q) key[q + (oy, ox)],     h = m * F^T e_w,
+ * e_w the frame's prediction error, m its mask (ME: |e_w|, without the 1 / max|e| -- the scale of wm_detect_tiles' sums_dev[0]; NVF:
+ * the mask of window p) and F^T the exact adjoint of the replicate-border prediction-error stencil.  That is ONE 2-D cross-correlation
+ * of the image-side plane h with key plane k: three 2-D transforms (the key's once per call) give it for every offset.
+ * wm_locate_shape (pure host arithmetic): ny = key_rows - rows + 1, nx = key_cols - cols + 1 admissible offsets per axis; pr, pc: the
+ * padded transform, the smallest powers of two >= max(key_rows, 64) and >= max(key_cols, 64).  WM_ERR_BAD_ARG for a null pointer,
+ * rows or cols < 1, a key smaller than the image, pr or pc above 8192 (a row of 8192 complex f32 fills the 64 KiB of LDS a
+ * workgroup transforms it in).  No wrap-around of the circular correlation reaches an admissible offset: q + o < key_rows <= pr.
+ * wm_locate takes wm_detect_offsets' inputs (the context supplies the image shape, p and the device, not its W; f32 / u8, any pitch
+ * and width, WM_MEM_HOST, batches up to max_frames, ME with p = 3 -- WM_ERR_BAD_P otherwise --, NVF with p = 3..9) and refuses in
+ * its order: null ctx, mask, null img / keys or loc_out and map_dev both NULL, k, the bank (device, at least as large),
+ * wm_locate_shape, band mode, slot, plane, record room.  The image side is wm_detect_keys' (Gram sweep and solve); per frame it
+ * then forms h, correlates, writes map[i][j] = sum_q h(q) key[q + (i, j)] for the ny x nx offsets into map_dev [frames][ny][nx]
+ * (DEVICE f32, may be NULL) and folds the map into loc_out[frame][4] (HOST, may be NULL, delivered by wm_sync):
+ *     oy, ox   the argmax (ties: the smallest i * nx + j), as floats (exact below 2^24)
+ *     peak     map[oy][ox]: the detector's <e_u, e_w> against the window at (oy, ox), to the f32 transform's rounding
+ *     z        (float)((peak - mu) / sigma), mu and sigma the f64 mean and population standard deviation of the map over the
+ *              offsets OUTSIDE the 3 x 3 block around the argmax (the prediction filter smears the peak over its neighbours);
+ *              NaN when fewer than two offsets lie outside that block or sigma = 0 (a zero key, a flat frame, key == image)
+ * status_out[frames] (may be NULL).  An unsolvable frame has status WM_UNSOLVABLE, {0, 0, 0, 0} and a zero map.  A marked crop
+ * reaches z of 20-60, an unmarked one stays below 5; wm_detect_offsets with ny = nx = 1 at (oy, ox) then gives
+ * the score.  A payload-marked copy (wm_embed_bits) has tiles of both signs whose contributions cancel in a whole-frame map.
+ * An ENQUEUE on the slot like wm_detect_offsets; frames * 4 records count against the slot's 4096 (WM_ERR_BUSY).  Never takes the
+ * fused kernels, leaves no hand-over, ends none, does not change what WM_MEM_SLOT_OUT names; its kernels are not in the wm_prof_*
+ * list.  A frame's map and numbers do not depend on the batch or on repetition.  Scratch per slot: three pr x pc complex f32 planes
+ * and the frame's e (and m) planes -- 384 MB for a 4K key, 1.5 GB at 8192 x 8192 -- grown on demand (WM_ERR_ALLOC when it does not
+ * fit; the first growing call waits for the device) and released by the reconfiguring calls.
+ * HAZARD: the bank stays alive and unmodified until wm_sync of this slot, as for wm_detect_keys.
+ * wm_fft2: the transform on its own, a synchronous building block for parity tests.  In place over data_dev [pr][pc] interleaved
+ * complex f32 on `device`, exp(-2 pi i ..) forward and exp(+2 pi i ..) inverse, neither normalised (inverse(forward(x)) = pr pc x);
+ * pr and pc powers of two in 64 .. 8192, anything else WM_ERR_BAD_ARG. */
+#define WM_LOCATE_NVALS 4   /* per frame, HOST f32, delivered by wm_sync: {oy, ox, peak, z} */
+int wm_locate_shape(int rows, int cols, int key_rows, int key_cols, int* ny, int* nx, int* pr, int* pc);
+int wm_locate(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* keys, int k,
+              float* loc_out /* HOST [frames][4], by wm_sync */, float* map_dev /* DEVICE [frames][ny][nx] f32, may be NULL */,
+              int* status_out, int slot);
+int wm_fft2(int device, float* data_dev /* [pr][pc] interleaved complex f32, in place */, int pr, int pc, int inverse);
+/* Yardstick of the transform (tools/locate_bench.py): the seven passes one frame of wm_locate makes over a pr x pc plane -- rows of pc,
+ * transpose, rows of pr, the spectrum product, rows of pr (inverse), transpose, rows of pc (inverse) -- each launched `iters` times
+ * back to back between two events; us_out[7]: mean microseconds per launch.  A row or transpose pass reads and writes the plane once
+ * (pr pc 8 bytes each way: wm_membench kind 4 on that many bytes is the copy to hold it against), the product reads two planes. */
+#define WM_FFT_BENCH_PASSES 7
+int wm_fft_bench(int device, int pr, int pc, int iters, double* us_out /* [WM_FFT_BENCH_PASSES] */);
+
 /* ---- Tile map: where in the frame is the mark? -------------------------------------------------------------------------------
  * wm_detect answers with one correlation for the whole plane.  A copy with a logo pasted over it, a picture-in-picture or a
  * spliced region only lets that score sag.  The detector is local, though: after the one solve per frame, e_w, u = m W and e_u

@@ -8,7 +8,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "watermarking-gpu_amd", "csrc")
-files = [a for a in sys.argv[1:] if a.endswith(".hip")] or ["wm_k_gram.hip", "wm_k_embed.hip", "wm_k_detect.hip", "wm_k_fused.hip", "wm_k_detect_keys.hip", "wm_k_embed_keys.hip", "wm_k_detect_offsets.hip", "wm_k_detect_tiles.hip", "wm_k_detect_keys_tiles.hip", "wm_k_bits.hip", "wm_k_embed_signs_multi.hip", "wm_k_convert.hip", "wm_k_convert16.hip", "wm_k_select.hip", "wm_k_quality.hip"]
+files = [a for a in sys.argv[1:] if a.endswith(".hip")] or ["wm_k_gram.hip", "wm_k_embed.hip", "wm_k_detect.hip", "wm_k_fused.hip", "wm_k_detect_keys.hip", "wm_k_embed_keys.hip", "wm_k_detect_offsets.hip", "wm_k_detect_tiles.hip", "wm_k_detect_keys_tiles.hip", "wm_k_bits.hip", "wm_k_embed_signs_multi.hip", "wm_k_convert.hip", "wm_k_convert16.hip", "wm_k_select.hip", "wm_k_quality.hip", "wm_k_locate.hip", "wm_k_fft.hip"]
 flags = [a for a in sys.argv[1:] if a.startswith("-D")]
 only = "--spills-only" in sys.argv
 bad = 0
@@ -31,7 +31,7 @@ for f in files:
                 cur[key] = int(m.group(1))
     for r in recs:
         dem = subprocess.run(["c++filt", r["name"]], capture_output=True, text=True).stdout.strip()
-        short = dem.split("(")[0].replace("void wmk::", "")
+        short = dem.replace("(anonymous namespace)::", "").split("(")[0].replace("void wmk::", "")
         spills = r.get("vspill", 0) > 0 or r.get("scratch", 0) > 0
         # (k_fused_pair's 128-row instances: 4-8 VGPRs stored and reloaded ONCE per wave around the statistics hand-off -- the
         # opt-in one-launch pair, WM_FUSED_PAIR=1; reported, not counted)

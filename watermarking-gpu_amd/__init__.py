@@ -84,6 +84,10 @@ ABI = [
     ("wm_detect_offsets_group", C.c_int, []),
     ("wm_detect_offsets", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_float), _P(C.c_int),
                                    C.c_int]),
+    ("wm_locate_shape", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_int), _P(C.c_int), _P(C.c_int), _P(C.c_int)]),
+    ("wm_locate", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), C.c_void_p, C.c_int, _P(C.c_float), C.c_void_p, _P(C.c_int), C.c_int]),
+    ("wm_fft2", C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    ("wm_fft_bench", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_double)]),
     ("wm_tiles_shape", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_int), _P(C.c_int)]),
     ("wm_detect_tiles", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), C.c_int, C.c_int, C.c_void_p, C.c_void_p, _P(C.c_int), C.c_int]),
     ("wm_detect_keys_tiles", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _P(C.c_int), C.c_int]),
@@ -269,6 +273,42 @@ def plane_any(t, channels=1):
 
 
 WM_QUALITY_NVALS, WM_QUALITY_NSUMS = 3, 5
+WM_LOCATE_NVALS = 4
+
+
+def locate_shape(rows, cols, key_rows, key_cols):
+    """(ny, nx, pr, pc) of wm_locate_shape: the admissible offsets per axis of a rows x cols image in a key_rows x key_cols key plane and
+    the padded power-of-two transform.  Raises for a key smaller than the image or a transform above 8192 per axis"""
+    v = [C.c_int() for _ in range(4)]
+    rc = lib().wm_locate_shape(rows, cols, key_rows, key_cols, *[C.byref(x) for x in v])
+    if rc != WM_OK:
+        _raise(rc)
+    return tuple(x.value for x in v)
+
+
+FFT_BENCH_PASSES = ("rows_pc", "transpose", "rows_pr", "product", "rows_pr_inverse", "transpose_back", "rows_pc_inverse")
+
+
+def fft_bench(pr, pc, iters=20, device=0):
+    """wm.h wm_fft_bench: {pass: mean microseconds per launch} of the seven passes one frame of wm_locate makes over a pr x pc plane"""
+    us = (C.c_double * len(FFT_BENCH_PASSES))()
+    rc = lib().wm_fft_bench(device, pr, pc, iters, us)
+    if rc != WM_OK:
+        _raise(rc)
+    return dict(zip(FFT_BENCH_PASSES, us))
+
+
+def fft2(t, inverse=False):
+    """wm.h wm_fft2, a building block for parity tests: the 2-D transform of a contiguous float32 GPU tensor [pr, pc, 2] (interleaved
+    complex) IN PLACE, exp(-2 pi i ..) forward, exp(+2 pi i ..) inverse, neither normalised; pr, pc powers of two in 64 .. 8192"""
+    import torch
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 3 and t.shape[2] == 2):
+        raise RuntimeError("fft2 takes a contiguous float32 GPU tensor [pr, pc, 2]")
+    torch.cuda.current_stream().synchronize()
+    rc = lib().wm_fft2(t.device.index or 0, C.c_void_p(t.data_ptr()), t.shape[0], t.shape[1], 1 if inverse else 0)
+    if rc != WM_OK:
+        _raise(rc)
+    return t
 
 
 def psnr_from_mse(mse, peak=255.0):
@@ -591,6 +631,25 @@ class Watermark:
         self._chk(lib().wm_detect_offsets(self._ctx, int(maskType), C.byref(pimg), keys.handle, k, oy0, ox0, ny, nx,
                                           corr.ctypes.data_as(_P(C.c_float)), None, WM_SLOT_SYNC))
         return corr[0] if image.dim() == 2 else corr
+
+    def locate(self, image, keys, k, maskType=MASK_TYPE.ME, want_map=False):
+        """where does a cropped copy lie in its key, without a hint?  The cross-correlation of the frame's image-side plane with key
+        `k` of the KeySet over EVERY admissible offset, by FFT (wm.h wm_locate): a float32 numpy array [frames, 4] ([4] for one grey
+        frame) = (oy, ox, peak, z) -- the argmax, the map value there (the detector's <e_u, e_w> against that window) and its
+        distance from the rest of the map in standard deviations; zeros for an unsolvable frame.  want_map=True: (loc, map) with map a
+        float32 GPU tensor [frames, ny, nx] ([ny, nx])"""
+        import torch
+        pimg = plane_of(image, 1)
+        frames = pimg.frames
+        ny, nx, _, _ = locate_shape(self.rows, self.cols, keys.rows, keys.cols)
+        loc = np.zeros((frames, WM_LOCATE_NVALS), np.float32)
+        map_t = torch.empty((frames, ny, nx), dtype=torch.float32, device=image.device) if want_map else None
+        torch.cuda.current_stream().synchronize()
+        self.locate_async(image, keys, k, maskType, WM_SLOT_SYNC, loc, map_t)
+        one = image.dim() == 2
+        if want_map:
+            return (loc[0], map_t[0]) if one else (loc, map_t)
+        return loc[0] if one else loc
 
     @staticmethod
     def tiles_shape(rows, cols, tile_rows, tile_cols):
@@ -962,6 +1021,21 @@ class Watermark:
         corr_out, status_out = self._scalars_out(corr_out, status_out)
         self._chk(lib().wm_detect_offsets(self._ctx, int(maskType), C.byref(pimg), _keys_handle(keys),
                                           k, oy0, ox0, ny, nx, corr_out, status_out, slot))
+
+    def locate_async(self, image, keys, k, maskType, slot, loc_out, map_t=None, status_out=None):
+        """wm_locate enqueued on `slot`: loc_out (frames * 4 floats: a ctypes array or a C-contiguous float32 numpy array, may be None
+        when map_t is given) and status_out (frames ints, may be None) are written by sync(slot); map_t (a contiguous float32 GPU
+        tensor of frames * ny * nx elements, may be None) is written on the slot's stream.  `keys` must stay alive and unmodified until
+        then"""
+        import torch
+        pimg = self._as_plane(image, 1)
+        loc_out, status_out = self._scalars_out(loc_out, status_out)
+        pmap = None
+        if map_t is not None:
+            if not (map_t.is_cuda and map_t.dtype == torch.float32 and map_t.is_contiguous()):
+                raise RuntimeError("map_t must be a contiguous float32 GPU tensor")
+            pmap = C.c_void_p(map_t.data_ptr())
+        self._chk(lib().wm_locate(self._ctx, int(maskType), C.byref(pimg), _keys_handle(keys), k, loc_out, pmap, status_out, slot))
 
     def detect_tiles_async(self, image, tile_rows, tile_cols, maskType, slot, map_t, sums_t=None, status=None):
         """wm_detect_tiles enqueued on `slot`: map_t (a contiguous float32 GPU tensor of frames * ny * nx elements) and sums_t

@@ -176,6 +176,10 @@ struct Slot {
     // wm_quality: k_quality's records [planes][nsegs][ngroups][3] f64 and the folds' [planes][nsegs][nx][3], then the tile sums [planes][ny * nx][5] f64 of a call that
     // passes no sums_dev (grown on demand)
     void* qual_scr = nullptr; size_t qual_scr_bytes = 0;
+    // wm_locate: three [pr][pc] complex f32 planes, the frame's e and m planes, the two twiddle tables and the peak records (LocScratch;
+    // grown on demand).  loc_pr x loc_pc: the transform its layout and tables are for
+    void* loc_scr = nullptr; size_t loc_scr_bytes = 0;
+    int loc_pr = 0, loc_pc = 0;
 };
 
 struct ProfRec { int kid; hipEvent_t a, b; bool first; };  // first: the sweep's first launch (counts the call)
@@ -379,7 +383,7 @@ void free_slot(Slot& s)
     (void)hipFree(s.st_in); (void)hipFree(s.st_base); (void)hipFree(s.st_out); (void)hipFree(s.fz_block); (void)hipFree(s.d_ho); (void)hipFree(s.d_hoseam);
     (void)hipFree(s.d_hodig); (void)hipFree(s.keys_part); (void)hipFree(s.ekeys_part); (void)hipFree(s.tiles_rec); (void)hipFree(s.keys_tiles_rec);
     if (s.tab_host) (void)hipHostFree(s.tab_host);
-    (void)hipFree(s.tab_dev); (void)hipFree(s.bits_scr); (void)hipFree(s.x16); (void)hipFree(s.y16); (void)hipFree(s.qual_scr);
+    (void)hipFree(s.tab_dev); (void)hipFree(s.bits_scr); (void)hipFree(s.x16); (void)hipFree(s.y16); (void)hipFree(s.qual_scr); (void)hipFree(s.loc_scr);
     s = Slot();
 }
 
@@ -1826,6 +1830,189 @@ int wm_detect_offsets(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys*
                        });
 }
 
+// ---- wm_locate: the offset of a crop anywhere in its key, by FFT (wm_k_locate.hip, wm_k_fft.hip) ---------------------------------
+static size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }
+static int pow2_at_least(int n)
+{
+    int p = 1 << FFT_LOG_MIN;
+    while (p < n) p <<= 1;
+    return p;
+}
+
+int wm_locate_shape(int rows, int cols, int key_rows, int key_cols, int* ny, int* nx, int* pr, int* pc)
+{
+    if (!ny || !nx || !pr || !pc) return WM_ERR_BAD_ARG;
+    constexpr int PMAX = 1 << FFT_LOG_MAX;
+    if (rows < 1 || cols < 1 || key_rows < rows || key_cols < cols || key_rows > PMAX || key_cols > PMAX) return WM_ERR_BAD_ARG;
+    *ny = key_rows - rows + 1; *nx = key_cols - cols + 1;
+    *pr = pow2_at_least(key_rows); *pc = pow2_at_least(key_cols);
+    return WM_OK;
+}
+
+namespace {
+// the slot's wm_locate scratch as one allocation: planes a (h, its spectrum, the map), b (transposes), w (the key's spectrum,
+// transposed), then e, m, the tables and the peak records
+struct LocScratch {
+    float *a, *b, *w, *e, *m, *tw_r, *tw_c;
+    void* part;
+    size_t bytes;
+};
+LocScratch loc_layout(void* base, int rows, int cols, int pr, int pc, int ny, int nx)
+{
+    const size_t plane = (size_t)pr * pc * 2 * sizeof(float), img = round256((size_t)rows * cols * sizeof(float));
+    char* p = (char*)base;
+    LocScratch L;
+    L.a = (float*)p; p += plane;
+    L.b = (float*)p; p += plane;
+    L.w = (float*)p; p += plane;
+    L.e = (float*)p; p += img;
+    L.m = (float*)p; p += img;
+    L.tw_r = (float*)p; p += round256((size_t)pr * 2 * sizeof(float));
+    L.tw_c = (float*)p; p += round256((size_t)pc * 2 * sizeof(float));
+    L.part = p; p += round256(locate_part_bytes(ny, nx));
+    L.bytes = (size_t)(p - (char*)base);
+    return L;
+}
+
+// forward 2-D transform of the [pr][pc] plane `a`; the spectrum lands TRANSPOSED ([pc][pr]) in `t`
+void fft2_forward_t(hipStream_t st, float* a, float* t, int pr, int pc, const float* tw_r, const float* tw_c)
+{
+    launch_fft_rows(st, a, pr, pc, tw_c, false);
+    launch_fft_transpose(st, a, t, pr, pc);
+    launch_fft_rows(st, t, pc, pr, tw_r, false);
+}
+// inverse 2-D transform of a transposed spectrum `t` ([pc][pr]); the plane lands in `a` ([pr][pc])
+void fft2_inverse_t(hipStream_t st, float* t, float* a, int pr, int pc, const float* tw_r, const float* tw_c)
+{
+    launch_fft_rows(st, t, pc, pr, tw_r, true);
+    launch_fft_transpose(st, t, a, pc, pr);
+    launch_fft_rows(st, a, pr, pc, tw_c, true);
+}
+}  // namespace
+
+int wm_locate(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* keys, int k, float* loc_out, float* map_dev, int* status_out, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    int rc = check_mask(ctx, mask);
+    if (rc != WM_OK) return rc;
+    if (!img || !keys || (!loc_out && !map_dev)) return fail(ctx, WM_ERR_BAD_ARG, "wm_locate: null img or keys, or loc_out and map_dev both null");
+    if (k < 0 || k >= keys->nkeys) return fail(ctx, WM_ERR_BAD_ARG, "wm_locate: key " + std::to_string(k) + " of a bank of " + std::to_string(keys->nkeys));
+    if ((rc = check_bank(ctx, keys, "wm_locate", false)) != WM_OK) return rc;
+    int ny, nx, pr, pc;
+    if (wm_locate_shape(ctx->rows, ctx->cols, keys->rows, keys->cols, &ny, &nx, &pr, &pc) != WM_OK)
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_locate: a " + std::to_string(keys->rows) + "x" + std::to_string(keys->cols) + " key plane needs a transform above " +
+                                             std::to_string(1 << FFT_LOG_MAX) + " per axis");
+    if ((rc = refuse_band(ctx, "wm_locate")) != WM_OK) return rc;
+    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
+    Sweep sw;
+    if ((rc = open_input(ctx, s, img, "image", mask, WM_LOCATE_NVALS, "4 location records", &sw)) != WM_OK) return rc;
+    const int frames = img->frames;
+    // scratch and tables: a new transform shape moves the layout under the calls still queued on the slot, so it waits for them
+    const size_t need = loc_layout(nullptr, ctx->rows, ctx->cols, pr, pc, ny, nx).bytes;
+    const bool reshape = s.loc_pr != pr || s.loc_pc != pc || s.loc_scr_bytes < need;
+    if (reshape) {
+        HIPCHK(ctx, hipStreamSynchronize(s.stream));
+        s.loc_pr = s.loc_pc = 0;
+        if ((rc = ensure(ctx, &s.loc_scr, &s.loc_scr_bytes, need, WM_ERR_ALLOC)) != WM_OK) return rc;
+    }
+    const LocScratch L = loc_layout(s.loc_scr, ctx->rows, ctx->cols, pr, pc, ny, nx);
+    if (reshape) {
+        std::vector<float> tw((size_t)2 * std::max(pr, pc));
+        fft_twiddles(pr, tw.data());
+        HIPCHK(ctx, hipMemcpy(L.tw_r, tw.data(), (size_t)pr * 2 * sizeof(float), hipMemcpyHostToDevice));
+        fft_twiddles(pc, tw.data());
+        HIPCHK(ctx, hipMemcpy(L.tw_c, tw.data(), (size_t)pc * 2 * sizeof(float), hipMemcpyHostToDevice));
+        s.loc_pr = pr; s.loc_pc = pc;
+    }
+    // the image side is wm_detect_keys': the Gram sweep and the solve
+    if ((rc = gram_sweep(ctx, s, sw, img)) != WM_OK) return rc;
+    // the key's spectrum, once per call (transposed, in L.w)
+    launch_locate_key(s.stream, keys->d + (size_t)k * keys->rows * keys->cols, keys->rows, keys->cols, L.b, pr, pc);
+    fft2_forward_t(s.stream, L.b, L.w, pr, pc, L.tw_r, L.tw_c);
+    // the frames one after the other: e (and m), h, its spectrum, conj(H) Wf, back, the map and its four numbers
+    for (int f = 0; f < frames; ++f) {
+        launch_locate_e(sw, f, L.e, L.m);
+        launch_locate_h(sw, f, L.e, L.m, L.a, pr, pc);
+        fft2_forward_t(s.stream, L.a, L.b, pr, pc, L.tw_r, L.tw_c);
+        launch_locate_mul(s.stream, L.b, L.w, (size_t)pr * pc);
+        fft2_inverse_t(s.stream, L.b, L.a, pr, pc, L.tw_r, L.tw_c);
+        launch_locate_peak(s.stream, L.a, pr, pc, ny, nx, s.d_status + f, map_dev ? map_dev + (size_t)f * ny * nx : nullptr, L.part,
+                           s.d_res + s.res_used + WM_LOCATE_NVALS * f);
+    }
+    return finish_call(ctx, s, slot, frames, WM_LOCATE_NVALS, false, loc_out, status_out);
+}
+
+int wm_fft2(int device, float* data_dev, int pr, int pc, int inverse)
+{
+    if (!data_dev || fft_log2(pr) < 0 || fft_log2(pc) < 0) return WM_ERR_BAD_ARG;
+    int rc = choose_device(&device);
+    if (rc != WM_OK) return rc;
+    const size_t plane = (size_t)pr * pc * 2 * sizeof(float);
+    float* scr = nullptr;
+    if (hipMalloc((void**)&scr, plane + (size_t)(pr + pc) * 2 * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return WM_ERR_ALLOC; }
+    float* tw_r = scr + (size_t)pr * pc * 2;
+    float* tw_c = tw_r + (size_t)pr * 2;
+    std::vector<float> tw((size_t)2 * (pr + pc));
+    fft_twiddles(pr, tw.data());
+    fft_twiddles(pc, tw.data() + (size_t)2 * pr);
+    bool ok = hipMemcpy(tw_r, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        // rows, transpose, rows (the columns), transpose back
+        launch_fft_rows(nullptr, data_dev, pr, pc, tw_c, inverse != 0);
+        launch_fft_transpose(nullptr, data_dev, scr, pr, pc);
+        launch_fft_rows(nullptr, scr, pc, pr, tw_r, inverse != 0);
+        launch_fft_transpose(nullptr, scr, data_dev, pc, pr);
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    }
+    (void)hipFree(scr);
+    return ok ? WM_OK : WM_ERR_RUNTIME;
+}
+
+// the seven passes of one forward + product + inverse transform of wm_locate, each launched `iters` times back to back between two
+// events on the null stream: mean microseconds per launch (tools/locate_bench.py holds them against wm_membench's copy)
+int wm_fft_bench(int device, int pr, int pc, int iters, double* us_out)
+{
+    if (!us_out || iters < 1 || fft_log2(pr) < 0 || fft_log2(pc) < 0) return WM_ERR_BAD_ARG;
+    int rc = choose_device(&device);
+    if (rc != WM_OK) return rc;
+    const size_t plane = (size_t)pr * pc * 2 * sizeof(float);
+    float* scr = nullptr;
+    if (hipMalloc((void**)&scr, 2 * plane + (size_t)(pr + pc) * 2 * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return WM_ERR_ALLOC; }
+    float* a = scr;
+    float* b = scr + (size_t)pr * pc * 2;
+    float* tw_r = b + (size_t)pr * pc * 2;
+    float* tw_c = tw_r + (size_t)pr * 2;
+    std::vector<float> tw((size_t)2 * (pr + pc));
+    fft_twiddles(pr, tw.data());
+    fft_twiddles(pc, tw.data() + (size_t)2 * pr);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    bool ok = hipMemset(scr, 0, 2 * plane) == hipSuccess && hipMemcpy(tw_r, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
+              hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
+    for (int pass = 0; ok && pass < WM_FFT_BENCH_PASSES; ++pass) {
+        for (int i = -1; i < iters; ++i) {  // (one untimed launch in front)
+            if (i == 0) ok = ok && hipEventRecord(e0, nullptr) == hipSuccess;
+            switch (pass) {
+            case 0: launch_fft_rows(nullptr, a, pr, pc, tw_c, false); break;
+            case 1: launch_fft_transpose(nullptr, a, b, pr, pc); break;
+            case 2: launch_fft_rows(nullptr, b, pc, pr, tw_r, false); break;
+            case 3: launch_locate_mul(nullptr, b, a, (size_t)pr * pc); break;
+            case 4: launch_fft_rows(nullptr, b, pc, pr, tw_r, true); break;
+            case 5: launch_fft_transpose(nullptr, b, a, pc, pr); break;
+            default: launch_fft_rows(nullptr, a, pr, pc, tw_c, true); break;
+            }
+        }
+        float ms = 0.f;
+        ok = ok && hipEventRecord(e1, nullptr) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess &&
+             hipGetLastError() == hipSuccess;
+        us_out[pass] = (double)ms * 1e3 / iters;
+    }
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    (void)hipFree(scr);
+    return ok ? WM_OK : WM_ERR_RUNTIME;
+}
+
 // tiles per axis of wm_detect_tiles: the last tile of each axis takes the remainder (pure host arithmetic)
 int wm_tiles_shape(int rows, int cols, int tile_rows, int tile_cols, int* ny, int* nx)
 {
@@ -2462,7 +2649,6 @@ static int fail_overlap(wm_ctx* ctx, const char* who, const ConvOp* op, int n, c
     if (n == 3) return fail(ctx, WM_ERR_BAD_ARG, std::string(who) + ": " + op[0].name + ", " + op[1].name + " and " + op[2].name + " must not overlap" + where);
     return fail(ctx, WM_ERR_BAD_ARG, std::string(who) + ": " + op[1].name + " overlaps " + op[0].name + where);
 }
-static size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 // ---- the conversions' frame.  The arguments are looked at in wm.h's order: shapes, each operand's own rules, frames between the
 // operands (per_channel, the 16-bit calls: channels too, and the grid's z is frames x channels), the launch grid, overlap of device

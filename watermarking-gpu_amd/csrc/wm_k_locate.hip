@@ -1,0 +1,242 @@
+// wm_k_locate.hip -- the image and key side of wm_locate around the transform of wm_k_fft.hip: k_locate_e (the frame's prediction
+// error and NVF mask), k_locate_h (h = m * F^T e_w, the exact adjoint of the replicate-border stencil, laid into a zeroed complex
+// plane), k_locate_key (the key plane laid out the same way), k_locate_peak and k_locate_fold (the map and its four numbers).
+//
+// With c solved, the detector's numerator is linear in W: <e_u, e_w>(oy, ox) = sum_q h(q) W(q + (oy, ox)), one 2-D cross-correlation
+// of h with the key plane.  Every workgroup works on its own pixels or its own chunk of the map; the fold
+// runs in a fixed order in f64, without atomics: a frame's map and numbers do not depend on the batch or on repetition.
+#include "wm_march.hpp"
+
+namespace wmk {
+
+namespace {
+
+constexpr int LB = 256;          // threads per workgroup
+constexpr int LTX = 64, LTY = 4; // ... as 64 columns x 4 rows of pixels
+constexpr int PEAK_PER = 16;     // map values per thread of k_locate_peak: a workgroup folds 4096 consecutive values
+
+__device__ __forceinline__ int clampi(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
+
+// k_locate_e: e = x - sum_k c_k x(clamp(p + d_k)) with the detector's rounding sequence (residual1: the chain starts at the centre
+// and runs over the negated coefficients), and under NVF the mask of the window 2 PAD + 1 (nvf_from_sums over row-major taps, as
+// nvf_value forms it).  One pixel per lane, replicate borders by clamped indices; x of any type, pitch and frame stride.
+// e, m: dense [rows][cols] f32 planes of ONE frame (m unused under ME).  An unsolvable frame is skipped: k_locate_h writes zeros
+template <typename T, int MASK, int PAD>
+__global__ __launch_bounds__(LB) void k_locate_e(const T* __restrict__ x, long long pitch, int rows, int cols, const float* __restrict__ coef,
+                                                 const int* __restrict__ status, float* __restrict__ e, float* __restrict__ m)
+{
+    if (status[0] != 0) return;
+    const int c = blockIdx.x * LTX + threadIdx.x % LTX, r = blockIdx.y * LTY + threadIdx.x / LTX;
+    if (r >= rows || c >= cols) return;
+    float nc[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) nc[k] = -coef[k];
+    float win[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b)
+            win[a][b] = Elem<T>::cvt1(x[(long long)clampi(r + a - 1, rows) * pitch + clampi(c + b - 1, cols)]);
+    e[(size_t)r * cols + c] = residual1<1>(win[0], win[1], win[2], 0, nc);
+    if (MASK == 1) {
+        float sum = 0.0f, sumsq = 0.0f;
+#pragma unroll
+        for (int a = -PAD; a <= PAD; ++a)
+#pragma unroll
+            for (int b = -PAD; b <= PAD; ++b) {
+                const float v = PAD == 1 ? win[a + 1][b + 1] : Elem<T>::cvt1(x[(long long)clampi(r + a, rows) * pitch + clampi(c + b, cols)]);
+                if (a == -PAD && b == -PAD) { sum = v; sumsq = v * v; }
+                else { sum += v; sumsq = fmaf(v, v, sumsq); }
+            }
+        m[(size_t)r * cols + c] = nvf_from_sums<PAD>(sum, sumsq);
+    }
+}
+
+// the pixels p of one axis with clamp(p + d) == q: q - d when it is in range, and the border pixel once more when q is that
+// border and d points outwards.  Returns their count (0 .. 2)
+__device__ __forceinline__ int adjoint_set(int q, int d, int n, int (&out)[2])
+{
+    int cnt = 0;
+    const int p = q - d;
+    if (p >= 0 && p < n) out[cnt++] = p;
+    if (d == -1 && q == 0) out[cnt++] = 0;
+    if (d == 1 && q == n - 1) out[cnt++] = n - 1;
+    return cnt;
+}
+
+// k_locate_h: g(q) = e(q) - sum_k c_k sum_{p : clamp(p + d_k) = q} e(p), h = m g with m = |e| (ME) or the NVF plane, written as
+// (h, 0) into the [pr][pc] complex plane; every element outside the image, and the whole plane of an unsolvable frame, is (0, 0)
+template <int MASK>
+__global__ __launch_bounds__(LB) void k_locate_h(const float* __restrict__ e, const float* __restrict__ m, int rows, int cols,
+                                                 const float* __restrict__ coef, const int* __restrict__ status, float2* __restrict__ plane, int pc)
+{
+    const int c = blockIdx.x * LTX + threadIdx.x % LTX, r = blockIdx.y * LTY + threadIdx.x / LTX;  // (the grid covers pr x pc exactly)
+    float h = 0.0f;
+    if (r < rows && c < cols && status[0] == 0) {
+        const float ec = e[(size_t)r * cols + c];
+        float g = ec;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int t = k < 4 ? k : k + 1;  // the 3x3 taps in row-major order without the centre
+            const int dr = t / 3 - 1, dc = t % 3 - 1;
+            int pr_[2], pc_[2];
+            const int nr = adjoint_set(r, dr, rows, pr_), ncn = adjoint_set(c, dc, cols, pc_);
+            float s = 0.0f;
+            for (int a = 0; a < nr; ++a)
+                for (int b = 0; b < ncn; ++b) s += e[(size_t)pr_[a] * cols + pc_[b]];
+            g = fmaf(-coef[k], s, g);
+        }
+        h = (MASK == 0 ? fabsf(ec) : m[(size_t)r * cols + c]) * g;
+    }
+    plane[(size_t)r * pc + c] = make_float2(h, 0.0f);
+}
+
+// k_locate_key: the key plane [key_rows][key_cols] as the real part of a zeroed [pr][pc] complex plane
+__global__ __launch_bounds__(LB) void k_locate_key(const float* __restrict__ key, int key_rows, int key_cols, float2* __restrict__ plane, int pc)
+{
+    const int c = blockIdx.x * LTX + threadIdx.x % LTX, r = blockIdx.y * LTY + threadIdx.x / LTX;
+    const float v = r < key_rows && c < key_cols ? key[(size_t)r * key_cols + c] : 0.0f;
+    plane[(size_t)r * pc + c] = make_float2(v, 0.0f);
+}
+
+// one block's or one frame's fold: argmax (ties to the smallest index), sum and sum of squares in f64
+struct PeakRec {
+    double sum, sumsq;
+    long long idx;
+    float val;
+    int pad;
+};
+__device__ __forceinline__ bool peak_better(float v, long long i, float bv, long long bi) { return v > bv || (v == bv && i < bi); }
+
+// a workgroup's 256 records folded pairwise in a fixed tree; the result is in s_rec[0]
+__device__ __forceinline__ void peak_tree(PeakRec* s_rec, int t)
+{
+    for (int half = LB / 2; half > 0; half >>= 1) {
+        __syncthreads();
+        if (t < half) {
+            const PeakRec o = s_rec[t + half];
+            PeakRec me = s_rec[t];
+            me.sum += o.sum; me.sumsq += o.sumsq;
+            if (o.idx >= 0 && (me.idx < 0 || peak_better(o.val, o.idx, me.val, me.idx))) { me.val = o.val; me.idx = o.idx; }
+            s_rec[t] = me;
+        }
+    }
+    __syncthreads();
+}
+
+// k_locate_peak: map value i * nx + j = Re plane[i][j] * scale over the ny x nx admissible offsets (scale = 1 / (pr pc): the
+// transforms are not normalised), stored to map when it is given; workgroup b folds values [4096 b, 4096 (b + 1)) into part[b].
+// An unsolvable frame's map is zero
+__global__ __launch_bounds__(LB) void k_locate_peak(const float2* __restrict__ plane, int pc, int ny, int nx, float scale,
+                                                    const int* __restrict__ status, float* __restrict__ map, PeakRec* __restrict__ part)
+{
+    __shared__ PeakRec s_rec[LB];
+    const int t = threadIdx.x;
+    const long long n = (long long)ny * nx;
+    const long long i0 = (long long)blockIdx.x * (LB * PEAK_PER);
+    const bool dead = status[0] != 0;
+    PeakRec me{0.0, 0.0, -1, 0.0f, 0};
+#pragma unroll 4
+    for (int k = 0; k < PEAK_PER; ++k) {
+        const long long i = i0 + t + (long long)k * LB;
+        if (i >= n) break;
+        const int oy = (int)(i / nx), ox = (int)(i % nx);
+        const float v = dead ? 0.0f : plane[(size_t)oy * pc + ox].x * scale;
+        if (map) map[i] = v;
+        me.sum += (double)v; me.sumsq += (double)v * (double)v;
+        if (me.idx < 0 || peak_better(v, i, me.val, me.idx)) { me.val = v; me.idx = i; }
+    }
+    s_rec[t] = me;
+    peak_tree(s_rec, t);
+    if (t == 0) part[blockIdx.x] = s_rec[0];
+}
+
+// k_locate_fold: one workgroup folds the nblk records of a frame (thread t takes t, t + 256, ... in ascending order, then the tree),
+// takes the values of the 3 x 3 block around the argmax out of the sums, and writes the frame's four records
+// {oy, ox, peak, z}: z = (peak - mu) / sigma over the offsets outside that block (population sigma, f64), NaN when fewer than two
+// offsets lie outside it or sigma is 0.  An unsolvable frame: status 1 and zeros
+__global__ __launch_bounds__(LB) void k_locate_fold(const PeakRec* __restrict__ part, int nblk, const float2* __restrict__ plane, int pc, int ny,
+                                                    int nx, float scale, const int* __restrict__ status, OpResult* __restrict__ res)
+{
+    __shared__ PeakRec s_rec[LB];
+    const int t = threadIdx.x;
+    PeakRec me{0.0, 0.0, -1, 0.0f, 0};
+    for (int b = t; b < nblk; b += LB) {
+        const PeakRec o = part[b];
+        me.sum += o.sum; me.sumsq += o.sumsq;
+        if (o.idx >= 0 && (me.idx < 0 || peak_better(o.val, o.idx, me.val, me.idx))) { me.val = o.val; me.idx = o.idx; }
+    }
+    s_rec[t] = me;
+    peak_tree(s_rec, t);
+    if (t != 0) return;
+    const int st = status[0];
+    if (st != 0) {
+        for (int k = 0; k < 4; ++k) res[k] = OpResult{st, 0.0f};
+        return;
+    }
+    const PeakRec tot = s_rec[0];
+    const int oy = (int)(tot.idx / nx), ox = (int)(tot.idx % nx);
+    double sum = tot.sum, sumsq = tot.sumsq;
+    long long cnt = (long long)ny * nx;
+    for (int i = max(oy - 1, 0); i <= min(oy + 1, ny - 1); ++i)
+        for (int j = max(ox - 1, 0); j <= min(ox + 1, nx - 1); ++j) {
+            const double v = (double)(plane[(size_t)i * pc + j].x * scale);
+            sum -= v; sumsq -= v * v; --cnt;
+        }
+    float z = __builtin_nanf("");
+    if (cnt >= 2) {
+        const double mu = sum / (double)cnt;
+        const double var = sumsq / (double)cnt - mu * mu;
+        if (var > 0.0) z = (float)(((double)tot.val - mu) / sqrt(var));
+    }
+    res[0] = OpResult{0, (float)oy};
+    res[1] = OpResult{0, (float)ox};
+    res[2] = OpResult{0, tot.val};
+    res[3] = OpResult{0, z};
+}
+
+}  // namespace
+
+size_t locate_part_bytes(int ny, int nx)
+{
+    const long long n = (long long)ny * nx;
+    return (size_t)((n + LB * PEAK_PER - 1) / (LB * PEAK_PER)) * sizeof(PeakRec);
+}
+
+void launch_locate_e(const Sweep& sw, int frame, float* e, float* m)
+{
+    const PlaneDesc& x = sw.x;
+    const int rows = sw.lg.rows, cols = sw.lg.cols;
+    const dim3 grid((cols + LTX - 1) / LTX, (rows + LTY - 1) / LTY);
+    WM_DISPATCH_T(x.dtype, for_mask_pad(sw.mask, sw.pad, [&](auto mk, auto p) {
+        WM_KLAUNCH((k_locate_e<T, decltype(mk)::value, decltype(p)::value>), grid, dim3(LB), 0, sw.s, (const T*)x.p + (long long)frame * x.fstride,
+                   x.pitch, rows, cols, sw.coef + 8 * frame, sw.status + frame, e, m);
+    }));
+}
+
+void launch_locate_h(const Sweep& sw, int frame, const float* e, const float* m, float* plane, int pr, int pc)
+{
+    const dim3 grid(pc / LTX, pr / LTY);
+    if (sw.mask == 0)
+        WM_KLAUNCH(k_locate_h<0>, grid, dim3(LB), 0, sw.s, e, m, sw.lg.rows, sw.lg.cols, sw.coef + 8 * frame, sw.status + frame,
+                   reinterpret_cast<float2*>(plane), pc);
+    else
+        WM_KLAUNCH(k_locate_h<1>, grid, dim3(LB), 0, sw.s, e, m, sw.lg.rows, sw.lg.cols, sw.coef + 8 * frame, sw.status + frame,
+                   reinterpret_cast<float2*>(plane), pc);
+}
+
+void launch_locate_key(hipStream_t s, const float* key, int key_rows, int key_cols, float* plane, int pr, int pc)
+{
+    WM_KLAUNCH(k_locate_key, dim3(pc / LTX, pr / LTY), dim3(LB), 0, s, key, key_rows, key_cols, reinterpret_cast<float2*>(plane), pc);
+}
+
+void launch_locate_peak(hipStream_t s, const float* plane, int pr, int pc, int ny, int nx, const int* status, float* map, void* part, OpResult* res)
+{
+    const float scale = 1.0f / ((float)pr * (float)pc);  // (a power of two: the scaling is exact)
+    const int nblk = (int)(locate_part_bytes(ny, nx) / sizeof(PeakRec));
+    const float2* pl = reinterpret_cast<const float2*>(plane);
+    WM_KLAUNCH(k_locate_peak, dim3(nblk), dim3(LB), 0, s, pl, pc, ny, nx, scale, status, map, static_cast<PeakRec*>(part));
+    WM_KLAUNCH(k_locate_fold, dim3(1), dim3(LB), 0, s, static_cast<const PeakRec*>(part), nblk, pl, pc, ny, nx, scale, status, res);
+}
+
+}  // namespace wmk

@@ -359,6 +359,27 @@ size_t quality_rec_bytes(const QualityGeom& q, const TileShape& ts, int planes);
 bool quality_grid_fits(int planes);
 void launch_quality(hipStream_t s, const QualityGeom& q, const QualityWeights& w, const TileShape& ts, int planes, const PlaneDesc& x,
                     const PlaneDesc& y, double* rec, double* sums, OpResult* res);
+// the 2-D complex f32 transform (wm_fft2 / wm_locate, wm_k_fft.hip).  launch_fft_rows: every row of a dense [nrows][P] interleaved
+// complex plane in place, P = 2^6 .. 2^13, nrows a multiple of 64, exp(-2 pi i ..) forward and exp(+2 pi i ..) inverse, neither
+// normalised; tw: [P] complex, fft_twiddles' table of that length on the device.  launch_fft_transpose: dst [ncols][nrows] =
+// src^T, both sides multiples of 64, out of place.  launch_locate_mul: a = conj(a) * b over n complex elements (n even)
+constexpr int FFT_LOG_MIN = 6, FFT_LOG_MAX = 13;
+int fft_log2(int n);                   // log2 of a length the row transform takes, -1 for any other n
+void fft_twiddles(int P, float* out);  // [P][2] = exp(-2 pi i t / P), formed in f64 (host)
+void launch_fft_rows(hipStream_t s, float* data, int nrows, int P, const float* tw, bool inverse);
+void launch_fft_transpose(hipStream_t s, const float* src, float* dst, int nrows, int ncols);
+void launch_locate_mul(hipStream_t s, float* a, const float* b, size_t n);
+// where a crop sits in its key (wm_locate, wm_k_locate.hip), one frame per launch.  launch_locate_e: the frame's prediction error e
+// (and, under NVF, mask m) as dense [rows][cols] f32 planes, from sw.x with the solve sw.coef / sw.status of that frame.
+// launch_locate_h: h = m * (adjoint of the stencil) e as the real part of the zeroed [pr][pc] complex plane; launch_locate_key: one
+// key plane laid out the same way.  launch_locate_peak: the admissible ny x nx real parts of `plane` times 1 / (pr pc) into map
+// (may be null), and the frame's four records res[0 .. 4) = {oy, ox, peak, z}; part: locate_part_bytes of scratch; status: the frame's
+size_t locate_part_bytes(int ny, int nx);
+void launch_locate_e(const Sweep& sw, int frame, float* e, float* m);
+void launch_locate_h(const Sweep& sw, int frame, const float* e, const float* m, float* plane, int pr, int pc);
+void launch_locate_key(hipStream_t s, const float* key, int key_rows, int key_cols, float* plane, int pr, int pc);
+void launch_locate_peak(hipStream_t s, const float* plane, int pr, int pc, int ny, int nx, const int* status, float* map, void* part,
+                        OpResult* res);
 // band mode: solve the 8x8 system from all-reduced Gram totals [frames][44]; writes coef / status like k_gram's tail
 void launch_solve_totals(hipStream_t s, int frames, const double* totals, float* coef, int* status);
 // band mode, device-resident exchange (wm_band_*_dev): glue kernels between the sweeps and the caller's collectives
