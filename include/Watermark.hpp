@@ -360,6 +360,26 @@ public:
         for (size_t f = 0; f < out.size(); ++f) out[f] = WmLocation{(int)v[4 * f], (int)v[4 * f + 1], v[4 * f + 2], v[4 * f + 3]};
         return out;
     }
+    // locate for a cropped copy that carries a PAYLOAD (wm.h wm_locate_bits): tileBit holds one entry per tileRows x tileCols tile of
+    // the KEY plane (-1: no bit).  Returns per frame the location on the energy map; soft [frame * nbits + b] > 0 reads bit b as set
+    // (NaN: a bit without a tile)
+    std::vector<WmLocation> locateBits(const wm::Image& watermarkedImage, const WatermarkKeys& keys, int k, int tileRows, int tileCols,
+                                       const std::vector<int32_t>& tileBit, int nbits, MASK_TYPE maskType, std::vector<float>& soft) const
+    {
+        const wm_plane pimg = watermarkedImage.plane();
+        std::vector<float> v((size_t)pimg.frames * WM_LOCATE_BITS_NVALS, 0.0f);
+        soft.assign((size_t)pimg.frames * (size_t)(nbits > 0 ? nbits : 0), 0.0f);
+        int ty = 0, tx = 0;  // (a table shorter than the key plane's tile grid must not reach the library)
+        if (wm_tiles_shape(wm_keys_rows(keys.handle()), wm_keys_cols(keys.handle()), tileRows, tileCols, &ty, &tx) == WM_OK &&
+            tileBit.size() != (size_t)ty * (size_t)tx)
+            fail(WM_ERR_BAD_ARG, "locateBits: tileBit must hold one entry per tile of the key plane");
+        const int rc = wm_locate_bits(ctx, (int)maskType, &pimg, keys.handle(), k, tileRows, tileCols, tileBit.data(), nbits, v.data(), soft.data(),
+                                      nullptr, nullptr, nullptr, WM_SLOT_SYNC);
+        if (rc < 0) fail(rc, "locateBits");
+        std::vector<WmLocation> out((size_t)pimg.frames);
+        for (size_t f = 0; f < out.size(); ++f) out[f] = WmLocation{(int)v[4 * f], (int)v[4 * f + 1], v[4 * f + 2], v[4 * f + 3]};
+        return out;
+    }
     // where in the frame is the mark?  detectWatermark of one grey image against this engine's W with the correlation's three sums
     // kept per tile of tileRows x tileCols pixels (wm.h wm_detect_tiles; the last tile of each axis takes the remainder): score
     // [i * nx + j] is tile (i, j)'s, NaN for a tile without energy, 0 everywhere when the system is not solvable.  ny / nx, if

@@ -321,7 +321,8 @@ int wm_detect_offsets(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys*
  *              NaN when fewer than two offsets lie outside that block or sigma = 0 (a zero key, a flat frame, key == image)
  * status_out[frames] (may be NULL).  An unsolvable frame has status WM_UNSOLVABLE, {0, 0, 0, 0} and a zero map.  A marked crop
  * reaches z of 20-60, an unmarked one stays below 5; wm_detect_offsets with ny = nx = 1 at (oy, ox) then gives
- * the score.  A payload-marked copy (wm_embed_bits) has tiles of both signs whose contributions cancel in a whole-frame map.
+ * the score.  A payload-marked copy (wm_embed_bits) has tiles of both signs whose contributions cancel in a whole-frame map:
+ * wm_locate_bits below finds and reads such a copy.
  * An ENQUEUE on the slot like wm_detect_offsets; frames * 4 records count against the slot's 4096 (WM_ERR_BUSY).  Never takes the
  * fused kernels, leaves no hand-over, ends none, does not change what WM_MEM_SLOT_OUT names; its kernels are not in the wm_prof_*
  * list.  A frame's map and numbers do not depend on the batch or on repetition.  Scratch per slot: three pr x pc complex f32 planes
@@ -343,6 +344,58 @@ int wm_fft2(int device, float* data_dev /* [pr][pc] interleaved complex f32, in 
  * (pr pc 8 bytes each way: wm_membench kind 4 on that many bytes is the copy to hold it against), the product reads two planes. */
 #define WM_FFT_BENCH_PASSES 7
 int wm_fft_bench(int device, int pr, int pc, int iters, double* us_out /* [WM_FFT_BENCH_PASSES] */);
+
+/* ---- A payload-marked crop: found without a hint, and read ---------------------------------------------------------------------
+ * wm_embed_bits marks tile t with +W or -W by the bit it carries, so in wm_locate's whole-key map the tiles cancel.  Tile signs are a
+ * property of KEY coordinates: with key_b = key * [tile_bit[tile(p)] == b], the key masked to the tiles of bit b, the marked crop's
+ * numerator at offset o is sum_b s_b map_b(o), map_b(o) = sum_q h(q) key_b[q + o] -- wm_locate's correlation with another key plane.
+ * The energy E(o) = sum_b map_b(o)^2 does not see the signs s_b; the sign of map_b at E's argmax is bit b.  h is real, so two bits
+ * ride in one complex transform: correlating h with key_b + i key_b' gives map_b + i map_b' (for an odd nbits the last bit rides alone).
+ * Geometry: the tiles are wm_tiles_shape(key_rows, key_cols, tile_rows, tile_cols) over the KEY plane, where wm_embed_bits put them on a
+ * context of the key's shape; tile_bit [ty * tx] is wm_bits_layout's table or the caller's own, -1: the tile belongs to no bit.  Offsets
+ * and the transform are wm_locate_shape's; h is wm_locate's (the same Gram sweep, solve and kernels).
+ * wm_locate_bits takes wm_locate's inputs and refuses in its order -- null ctx, mask, a null img / keys / tile_bit / loc_out / soft_out,
+ * k, the bank, wm_locate_shape, band mode, slot, plane, record room (frames * (4 + nbits) records against the slot's 4096,
+ * WM_ERR_BUSY) --, then a tile shape wm_tiles_shape refuses on the key's shape, nbits outside 1 .. 4096 and a tile_bit entry outside
+ * -1 .. nbits - 1; all of it before any device work.  tile_bit is read before the call returns.  Outputs, valid after wm_sync:
+ *     loc_out[frame][4]       wm_locate's {oy, ox, peak, z} taken on E: the argmax o* (ties: the smallest index), E there, and z against
+ *                             the offsets outside the 3 x 3 block around o* (f64), NaN by wm_locate's rule
+ *     soft_out[frame][nbits]  (float)((map_b(o*) - mu_b) / sigma_b), mu_b and sigma_b the f64 mean and population standard deviation
+ *                             of map_b over the offsets outside that same block: the bit is soft > 0, |soft| is in standard deviations
+ *                             of the bit's own unmarked level.  NaN where sigma_b = 0 (a bit without a tile, a zero key) or fewer
+ *                             than two offsets lie outside the block.  A bit without a pixel in the window reads about 0:
+ *                             wm_locate_bits_cover names those bits
+ *     energy_dev              DEVICE [frames][ny][nx] f32, may be NULL: E, added in f32 in ascending pair order (the first pair stores)
+ *     maps_dev                DEVICE [frames][nbits][ny][nx] f32, may be NULL: the maps; peak == energy_dev[oy][ox] bit for bit
+ * An unsolvable frame: status WM_UNSOLVABLE, {0, 0, 0, 0}, soft zero, zero maps and a zero E.  A frame's numbers, E and maps do not
+ * depend on the batch or on repetition.  A marked crop reaches z of 140-680 on E and an unmarked one stays below 10 (DESIGN.md section
+ * 25); a plainly marked copy (all signs +1) is found as well.
+ * An ENQUEUE on the slot; never takes the fused kernels, leaves no hand-over, ends none, does not change what WM_MEM_SLOT_OUT names; its
+ * kernels are not in the wm_prof_* list.  Scratch per slot, grown on demand (WM_ERR_ALLOC when it does not fit; a call whose shapes
+ * differ from the one before waits for the slot's stream) and released by the reconfiguring calls:
+ *     bytes = (frames + 3) * pr * pc * 8  +  2 * rows * cols * 4  +  [energy_dev NULL] frames * ny * nx * 4
+ *             +  [maps_dev NULL] frames * nbits * ny * nx * 4  +  frames * (ceil(nbits / 2) + 1) * ceil(ny * nx / 4096) * 32  +  tables
+ * -- about 700 MB for a 4K key (4096 x 4096 transform), a 1600 x 3000 crop, 64 bits and one frame.
+ * HAZARD: the bank stays alive and unmodified until wm_sync of this slot, as for wm_locate.
+ * wm_locate_bits_cover (pure host arithmetic): pixels_out[b] = the pixels of the rows x cols window at (oy, ox) whose key tile carries
+ * bit b.  WM_ERR_BAD_ARG for what wm_locate_shape or wm_tiles_shape refuse, an offset outside 0 .. ny - 1, 0 .. nx - 1, a null
+ * pointer, nbits outside 1 .. 4096 or a tile_bit entry outside -1 .. nbits - 1. */
+#define WM_LOCATE_BITS_NVALS 4   /* {oy, ox, peak, z} of the energy map, then nbits soft values */
+int wm_locate_bits(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* keys, int k,
+                   int tile_rows, int tile_cols, const int32_t* tile_bit /* HOST [ty*tx] over the KEY plane, -1 .. nbits-1 */, int nbits,
+                   float* loc_out  /* HOST [frames][4], by wm_sync */,
+                   float* soft_out /* HOST [frames][nbits], by wm_sync */,
+                   float* energy_dev /* DEVICE [frames][ny][nx] f32, may be NULL */,
+                   float* maps_dev   /* DEVICE [frames][nbits][ny][nx] f32, may be NULL */,
+                   int* status_out, int slot);
+int wm_locate_bits_cover(int rows, int cols, int key_rows, int key_cols, int tile_rows, int tile_cols,
+                         const int32_t* tile_bit, int nbits, int oy, int ox, int64_t* pixels_out /* [nbits] */);
+/* Yardstick (tools/locate_bits_bench.py), beside wm_fft_bench and timed the same way: the three passes wm_locate_bits adds to the
+ * seven of a transform -- the key-pair plane (128 x 128 tiles over a pr x pc key: one plane written), the three-operand product (two
+ * planes read, one written), the accumulate pass of a later pair over ny x nx offsets (8 bytes read, 4 read and 12 written per
+ * offset).  pr, pc: powers of two in 128 .. 8192, ny <= pr, nx <= pc; anything else WM_ERR_BAD_ARG. */
+#define WM_LOCATE_BITS_BENCH_PASSES 3
+int wm_locate_bits_bench(int device, int pr, int pc, int ny, int nx, int iters, double* us_out /* [WM_LOCATE_BITS_BENCH_PASSES] */);
 
 /* ---- Tile map: where in the frame is the mark? -------------------------------------------------------------------------------
  * wm_detect answers with one correlation for the whole plane.  A copy with a logo pasted over it, a picture-in-picture or a

@@ -86,6 +86,10 @@ ABI = [
                                    C.c_int]),
     ("wm_locate_shape", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_int), _P(C.c_int), _P(C.c_int), _P(C.c_int)]),
     ("wm_locate", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), C.c_void_p, C.c_int, _P(C.c_float), C.c_void_p, _P(C.c_int), C.c_int]),
+    ("wm_locate_bits", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, _P(C.c_float),
+                                 _P(C.c_float), C.c_void_p, C.c_void_p, _P(C.c_int), C.c_int]),
+    ("wm_locate_bits_cover", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, _P(C.c_int64)]),
+    ("wm_locate_bits_bench", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_double)]),
     ("wm_fft2", C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     ("wm_fft_bench", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_double)]),
     ("wm_tiles_shape", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_int), _P(C.c_int)]),
@@ -286,6 +290,24 @@ def locate_shape(rows, cols, key_rows, key_cols):
     return tuple(x.value for x in v)
 
 
+WM_LOCATE_BITS_NVALS = 4
+
+
+def locate_bits_cover(rows, cols, key_rows, key_cols, tile_rows, tile_cols, tile_bit, nbits, oy, ox):
+    """wm.h wm_locate_bits_cover: an int64 numpy array [nbits], the pixels of the rows x cols window at (oy, ox) of the key plane whose
+    key tile carries bit b (tile_bit: int32 [ty * tx] over the KEY plane).  Raises for what the library refuses"""
+    tb = np.ascontiguousarray(tile_bit, np.int32).reshape(-1)
+    px = np.zeros(max(nbits, 1), np.int64)
+    ny, nx = C.c_int(), C.c_int()
+    if lib().wm_tiles_shape(key_rows, key_cols, tile_rows, tile_cols, C.byref(ny), C.byref(nx)) != WM_OK or tb.size != ny.value * nx.value:
+        raise RuntimeError("locate_bits_cover: bad tile shape, or tile_bit is not the table of the key plane's tiles")
+    rc = lib().wm_locate_bits_cover(rows, cols, key_rows, key_cols, tile_rows, tile_cols, tb.ctypes.data_as(C.c_void_p), nbits, oy, ox,
+                                    px.ctypes.data_as(_P(C.c_int64)))
+    if rc != WM_OK:
+        _raise(rc)
+    return px[:nbits]
+
+
 FFT_BENCH_PASSES = ("rows_pc", "transpose", "rows_pr", "product", "rows_pr_inverse", "transpose_back", "rows_pc_inverse")
 
 
@@ -296,6 +318,18 @@ def fft_bench(pr, pc, iters=20, device=0):
     if rc != WM_OK:
         _raise(rc)
     return dict(zip(FFT_BENCH_PASSES, us))
+
+
+LOCATE_BITS_BENCH_PASSES = ("key_pair", "product3", "accumulate")
+
+
+def locate_bits_bench(pr, pc, ny, nx, iters=20, device=0):
+    """wm.h wm_locate_bits_bench: {pass: mean microseconds per launch} of the three passes wm_locate_bits adds to a transform's seven"""
+    us = (C.c_double * len(LOCATE_BITS_BENCH_PASSES))()
+    rc = lib().wm_locate_bits_bench(device, pr, pc, ny, nx, iters, us)
+    if rc != WM_OK:
+        _raise(rc)
+    return dict(zip(LOCATE_BITS_BENCH_PASSES, us))
 
 
 def fft2(t, inverse=False):
@@ -650,6 +684,30 @@ class Watermark:
         if want_map:
             return (loc[0], map_t[0]) if one else (loc, map_t)
         return loc[0] if one else loc
+
+    def locate_bits(self, image, keys, k, tile_rows, tile_cols, tile_bit, nbits, maskType=MASK_TYPE.ME, want_energy=False, want_maps=False):
+        """finds a cropped, PAYLOAD-marked copy in key `k` of the KeySet and reads its bits (wm.h wm_locate_bits): the tiles (tile_rows x
+        tile_cols, tile_bit int32 [ty * tx], -1: no bit) lie on the KEY plane.  Returns (loc, soft[, energy][, maps]): loc a float32
+        numpy array [frames, 4] ([4] for one grey frame) = (oy, ox, peak, z) of the energy map sum_b map_b^2, soft float32 [frames,
+        nbits] ([nbits]) with bit b = soft > 0 (NaN: a bit without a tile; about 0: no pixel of the bit in the window, see
+        locate_bits_cover); energy a float32 GPU tensor [frames, ny, nx], maps [frames, nbits, ny, nx].  Zeros for an unsolvable frame"""
+        import torch
+        pimg = plane_of(image, 1)
+        frames = pimg.frames
+        ny, nx, _, _ = locate_shape(self.rows, self.cols, keys.rows, keys.cols)
+        loc = np.zeros((frames, WM_LOCATE_BITS_NVALS), np.float32)
+        soft = np.zeros((frames, max(nbits, 0)), np.float32)
+        en_t = torch.empty((frames, ny, nx), dtype=torch.float32, device=image.device) if want_energy else None
+        maps_t = torch.empty((frames, max(nbits, 0), ny, nx), dtype=torch.float32, device=image.device) if want_maps else None
+        torch.cuda.current_stream().synchronize()
+        self.locate_bits_async(image, keys, k, tile_rows, tile_cols, tile_bit, nbits, maskType, WM_SLOT_SYNC, loc, soft, en_t, maps_t)
+        one = image.dim() == 2
+        out = [loc[0] if one else loc, soft[0] if one else soft]
+        if want_energy:
+            out.append(en_t[0] if one else en_t)
+        if want_maps:
+            out.append(maps_t[0] if one else maps_t)
+        return tuple(out)
 
     @staticmethod
     def tiles_shape(rows, cols, tile_rows, tile_cols):
@@ -1036,6 +1094,30 @@ class Watermark:
                 raise RuntimeError("map_t must be a contiguous float32 GPU tensor")
             pmap = C.c_void_p(map_t.data_ptr())
         self._chk(lib().wm_locate(self._ctx, int(maskType), C.byref(pimg), _keys_handle(keys), k, loc_out, pmap, status_out, slot))
+
+    def locate_bits_async(self, image, keys, k, tile_rows, tile_cols, tile_bit, nbits, maskType, slot, loc_out, soft_out, energy_t=None,
+                          maps_t=None, status_out=None):
+        """wm_locate_bits enqueued on `slot`: tile_bit (int32, one entry per tile of the KEY plane) is read before the call returns;
+        loc_out (frames * 4 floats), soft_out (frames * nbits floats) and status_out (frames ints, may be None) are written by
+        sync(slot); energy_t (frames * ny * nx) and maps_t (frames * nbits * ny * nx), contiguous float32 GPU tensors that may be
+        None, on the slot's stream.  `keys` must stay alive and unmodified until then"""
+        import torch
+        pimg = self._as_plane(image, 1)
+        tb = np.ascontiguousarray(tile_bit, np.int32).reshape(-1) if tile_bit is not None else None
+        if tb is not None and keys is not None:
+            tny, tnx = C.c_int(), C.c_int()
+            if lib().wm_tiles_shape(keys.rows, keys.cols, tile_rows, tile_cols, C.byref(tny), C.byref(tnx)) == WM_OK and tb.size != tny.value * tnx.value:
+                raise RuntimeError(f"tile_bit must hold {tny.value * tnx.value} entries, got {tb.size}")
+        loc_out, status_out = self._scalars_out(loc_out, status_out)
+        soft_out, _ = self._scalars_out(soft_out, None)
+        ptrs = []
+        for t in (energy_t, maps_t):
+            if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                raise RuntimeError("energy_t and maps_t must be contiguous float32 GPU tensors")
+            ptrs.append(C.c_void_p(t.data_ptr()) if t is not None else None)
+        self._chk(lib().wm_locate_bits(self._ctx, int(maskType), C.byref(pimg), _keys_handle(keys), k, tile_rows, tile_cols,
+                                       tb.ctypes.data_as(C.c_void_p) if tb is not None else None, nbits, loc_out, soft_out, ptrs[0], ptrs[1],
+                                       status_out, slot))
 
     def detect_tiles_async(self, image, tile_rows, tile_cols, maskType, slot, map_t, sums_t=None, status=None):
         """wm_detect_tiles enqueued on `slot`: map_t (a contiguous float32 GPU tensor of frames * ny * nx elements) and sums_t

@@ -180,6 +180,10 @@ struct Slot {
     // grown on demand).  loc_pr x loc_pc: the transform its layout and tables are for
     void* loc_scr = nullptr; size_t loc_scr_bytes = 0;
     int loc_pr = 0, loc_pc = 0;
+    // wm_locate_bits: frames + 3 complex planes, the e and m planes, the tables, the energy map and the per-bit maps of a call that
+    // passes none, and the block records (LocBitsScratch; grown on demand).  locb_key: the shapes its layout and tables are for
+    void* locb_scr = nullptr; size_t locb_scr_bytes = 0;
+    long long locb_key[6] = {0, 0, 0, 0, 0, 0};
 };
 
 struct ProfRec { int kid; hipEvent_t a, b; bool first; };  // first: the sweep's first launch (counts the call)
@@ -384,6 +388,7 @@ void free_slot(Slot& s)
     (void)hipFree(s.d_hodig); (void)hipFree(s.keys_part); (void)hipFree(s.ekeys_part); (void)hipFree(s.tiles_rec); (void)hipFree(s.keys_tiles_rec);
     if (s.tab_host) (void)hipHostFree(s.tab_host);
     (void)hipFree(s.tab_dev); (void)hipFree(s.bits_scr); (void)hipFree(s.x16); (void)hipFree(s.y16); (void)hipFree(s.qual_scr); (void)hipFree(s.loc_scr);
+    (void)hipFree(s.locb_scr);
     s = Slot();
 }
 
@@ -2239,6 +2244,209 @@ int wm_detect_bits(wm_ctx* ctx, int mask, const wm_plane* img, int tile_rows, in
     { ProfScope ps(ctx, K_TILES_FOLD, s.stream); launch_tiles_fold(s.stream, pl, frames, (const float*)s.tiles_rec, s.d_status, map, sums, tres); }
     launch_bits_fold(s.stream, frames, nbits, T, sums, (const int*)td, (const int*)td + nbits + 1, s.d_status, s.d_res + s.res_used);
     return finish_call(ctx, s, slot, frames, nbits, false, soft_out, status_out);
+}
+
+// ---- wm_locate_bits: a payload-marked crop found and read without a hint ---------------------------------
+namespace {
+// the slot's wm_locate_bits scratch as one allocation: the tables, the frames' spectra hs [frames] (transposed), planes a (work: h,
+// the key pair, the inverse), kw (the pair's spectrum, transposed) and p (the product), e and m, the energy map and the per-bit maps
+// (null when the caller passes its own), the bits' block records [frames][pairs][blocks] and the energy's [frames][blocks]
+struct LocBitsScratch {
+    float *tw_r, *tw_c, *hs, *a, *kw, *p, *e, *m, *energy, *maps;
+    char *part, *epart;
+    size_t plane_floats, part_stride, epart_stride, bytes;
+};
+LocBitsScratch locb_layout(void* base, int rows, int cols, int pr, int pc, int ny, int nx, int frames, int nbits, bool own_energy, bool own_maps)
+{
+    const size_t plane = (size_t)pr * pc * 2 * sizeof(float), img = round256((size_t)rows * cols * sizeof(float));
+    const size_t n = (size_t)ny * nx;
+    char* p = (char*)base;
+    LocBitsScratch L;
+    L.plane_floats = (size_t)pr * pc * 2;
+    L.tw_r = (float*)p; p += round256((size_t)pr * 2 * sizeof(float));
+    L.tw_c = (float*)p; p += round256((size_t)pc * 2 * sizeof(float));
+    L.hs = (float*)p; p += plane * frames;
+    L.a = (float*)p; p += plane;
+    L.kw = (float*)p; p += plane;
+    L.p = (float*)p; p += plane;
+    L.e = (float*)p; p += img;
+    L.m = (float*)p; p += img;
+    L.energy = own_energy ? (float*)p : nullptr; p += own_energy ? round256(n * frames * sizeof(float)) : 0;
+    L.maps = own_maps ? (float*)p : nullptr; p += own_maps ? round256(n * frames * nbits * sizeof(float)) : 0;
+    L.part_stride = locate_bits_part_bytes(ny, nx) * (size_t)((nbits + 1) / 2);
+    L.part = p; p += round256(L.part_stride * frames);
+    L.epart_stride = locate_part_bytes(ny, nx);
+    L.epart = p; p += round256(L.epart_stride * frames);
+    L.bytes = (size_t)(p - (char*)base);
+    return L;
+}
+}  // namespace
+
+int wm_locate_bits_cover(int rows, int cols, int key_rows, int key_cols, int tile_rows, int tile_cols, const int32_t* tile_bit, int nbits, int oy,
+                         int ox, int64_t* pixels_out)
+{
+    int ny, nx, pr, pc, tny, tnx;
+    if (!tile_bit || !pixels_out || nbits < 1 || nbits > 4096) return WM_ERR_BAD_ARG;
+    if (wm_locate_shape(rows, cols, key_rows, key_cols, &ny, &nx, &pr, &pc) != WM_OK) return WM_ERR_BAD_ARG;
+    if (wm_tiles_shape(key_rows, key_cols, tile_rows, tile_cols, &tny, &tnx) != WM_OK) return WM_ERR_BAD_ARG;
+    if (oy < 0 || oy >= ny || ox < 0 || ox >= nx) return WM_ERR_BAD_ARG;
+    for (int t = 0; t < tny * tnx; ++t)
+        if (tile_bit[t] < -1 || tile_bit[t] >= nbits) return WM_ERR_BAD_ARG;
+    std::fill(pixels_out, pixels_out + nbits, (int64_t)0);
+    for (int ty = 0; ty < tny; ++ty) {
+        // the tile's rows [r0, r1) of the key plane (the last tile takes the remainder) cut with the window's [oy, oy + rows)
+        const int r0 = ty * tile_rows, r1 = ty == tny - 1 ? key_rows : r0 + tile_rows;
+        const int64_t hr = std::min(r1, oy + rows) - std::max(r0, oy);
+        if (hr <= 0) continue;
+        for (int tx = 0; tx < tnx; ++tx) {
+            const int c0 = tx * tile_cols, c1 = tx == tnx - 1 ? key_cols : c0 + tile_cols;
+            const int64_t wc = std::min(c1, ox + cols) - std::max(c0, ox);
+            const int b = tile_bit[ty * tnx + tx];
+            if (wc > 0 && b >= 0) pixels_out[b] += hr * wc;
+        }
+    }
+    return WM_OK;
+}
+
+// wm_locate with the key masked to the tiles of one payload bit at a time, two bits per complex transform: the frames' spectra are
+// kept, every pair's key plane is transformed once per call, and per (pair, frame) there are a product, an inverse transform and the
+// accumulate pass; behind the last pair the folds.  None of its kernels runs inside a ProfScope
+int wm_locate_bits(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* keys, int k, int tile_rows, int tile_cols, const int32_t* tile_bit,
+                   int nbits, float* loc_out, float* soft_out, float* energy_dev, float* maps_dev, int* status_out, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    int rc = check_mask(ctx, mask);
+    if (rc != WM_OK) return rc;
+    if (!img || !keys || !tile_bit || !loc_out || !soft_out)
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_locate_bits: null img, keys, tile_bit, loc_out or soft_out");
+    if (k < 0 || k >= keys->nkeys) return fail(ctx, WM_ERR_BAD_ARG, "wm_locate_bits: key " + std::to_string(k) + " of a bank of " + std::to_string(keys->nkeys));
+    if ((rc = check_bank(ctx, keys, "wm_locate_bits", false)) != WM_OK) return rc;
+    int ny, nx, pr, pc;
+    if (wm_locate_shape(ctx->rows, ctx->cols, keys->rows, keys->cols, &ny, &nx, &pr, &pc) != WM_OK)
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_locate_bits: a " + std::to_string(keys->rows) + "x" + std::to_string(keys->cols) +
+                                             " key plane needs a transform above " + std::to_string(1 << FFT_LOG_MAX) + " per axis");
+    if ((rc = refuse_band(ctx, "wm_locate_bits")) != WM_OK) return rc;
+    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
+    // (open_input checks the plane and the record room again: both have to be known HERE, in front of the table's checks and of any device work)
+    if ((rc = check_plane(ctx, img, 0, false, "image", true)) != WM_OK) return rc;
+    const int frames = img->frames;
+    const long long per_frame = WM_LOCATE_BITS_NVALS + (long long)std::max(nbits, 0);
+    if ((rc = check_res_room(ctx, s, frames * per_frame, "(4 + bits)")) != WM_OK) return rc;
+    TileShape ts;
+    ts.th = tile_rows; ts.tw = tile_cols;
+    if (wm_tiles_shape(keys->rows, keys->cols, tile_rows, tile_cols, &ts.ny, &ts.nx) != WM_OK)
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_locate_bits: tile shape " + std::to_string(tile_rows) + "x" + std::to_string(tile_cols) +
+                                             " (rows: a multiple of 8, >= 32; columns: a multiple of 4, >= 32)");
+    const int T = ts.ny * ts.nx;
+    if ((rc = tile_bits_checked(ctx, "wm_locate_bits", tile_bit, T, nbits)) != WM_OK) return rc;
+    Sweep sw;
+    if ((rc = open_input(ctx, s, img, "image", mask, per_frame, "(4 + bits)", &sw)) != WM_OK) return rc;
+
+    // scratch and tables: another layout moves the planes under the calls still queued on the slot, so it waits for them
+    const long long key_now[6] = {((long long)pr << 32) | pc, ((long long)ny << 32) | nx, frames, nbits, energy_dev ? 0 : 1, maps_dev ? 0 : 1};
+    const size_t need = locb_layout(nullptr, ctx->rows, ctx->cols, pr, pc, ny, nx, frames, nbits, !energy_dev, !maps_dev).bytes;
+    const bool reshape = !std::equal(key_now, key_now + 6, s.locb_key) || s.locb_scr_bytes < need;
+    if (reshape) {
+        HIPCHK(ctx, hipStreamSynchronize(s.stream));
+        std::fill(s.locb_key, s.locb_key + 6, 0LL);
+        if ((rc = ensure(ctx, &s.locb_scr, &s.locb_scr_bytes, need, WM_ERR_ALLOC)) != WM_OK) return rc;
+    }
+    const LocBitsScratch L = locb_layout(s.locb_scr, ctx->rows, ctx->cols, pr, pc, ny, nx, frames, nbits, !energy_dev, !maps_dev);
+    if (reshape) {
+        std::vector<float> tw((size_t)2 * std::max(pr, pc));
+        fft_twiddles(pr, tw.data());
+        HIPCHK(ctx, hipMemcpy(L.tw_r, tw.data(), (size_t)pr * 2 * sizeof(float), hipMemcpyHostToDevice));
+        fft_twiddles(pc, tw.data());
+        HIPCHK(ctx, hipMemcpy(L.tw_c, tw.data(), (size_t)pc * 2 * sizeof(float), hipMemcpyHostToDevice));
+        std::copy(key_now, key_now + 6, s.locb_key);
+    }
+    // the call's own copy of the table (the caller's array is free when this function returns), and which bits have a tile at all
+    void *th = nullptr, *td = nullptr;
+    if ((rc = table_room(ctx, s, (size_t)T * sizeof(int), &th, &td)) != WM_OK) return rc;
+    std::memcpy(th, tile_bit, (size_t)T * sizeof(int));
+    std::vector<char> has((size_t)nbits + 1, 0);
+    for (int t = 0; t < T; ++t)
+        if (tile_bit[t] >= 0) has[(size_t)tile_bit[t]] = 1;
+    if ((rc = table_upload(ctx, s, th, td, (size_t)T * sizeof(int))) != WM_OK) return rc;
+
+    const size_t n = (size_t)ny * nx, npl = (size_t)pr * pc;
+    float* energy = energy_dev ? energy_dev : L.energy;
+    float* maps = maps_dev ? maps_dev : L.maps;
+    OpResult* res = s.d_res + s.res_used;
+    // the image side is wm_locate's: the Gram sweep and the solve, then every frame's e (and m), h and its spectrum, kept
+    if ((rc = gram_sweep(ctx, s, sw, img)) != WM_OK) return rc;
+    for (int f = 0; f < frames; ++f) {
+        launch_locate_e(sw, f, L.e, L.m);
+        launch_locate_h(sw, f, L.e, L.m, L.a, pr, pc);
+        fft2_forward_t(s.stream, L.a, L.hs + f * L.plane_floats, pr, pc, L.tw_r, L.tw_c);
+    }
+    // pair-major: the pair's key plane and its spectrum once per call, then per frame the product, the way back and the accumulate pass
+    const float* key = keys->d + (size_t)k * keys->rows * keys->cols;
+    const int npairs = (nbits + 1) / 2;
+    const size_t blk_bytes = locate_bits_part_bytes(ny, nx);
+    for (int pi = 0; pi < npairs; ++pi) {
+        const int b0 = 2 * pi, b1 = b0 + 1 < nbits ? b0 + 1 : -2;
+        launch_locate_key_pair(s.stream, key, keys->rows, keys->cols, (const int*)td, ts, b0, b1, L.a, pr, pc);
+        fft2_forward_t(s.stream, L.a, L.kw, pr, pc, L.tw_r, L.tw_c);
+        for (int f = 0; f < frames; ++f) {
+            launch_locate_mul3(s.stream, L.hs + f * L.plane_floats, L.kw, L.p, npl);
+            fft2_inverse_t(s.stream, L.p, L.a, pr, pc, L.tw_r, L.tw_c);
+            float* mf = maps + (size_t)f * nbits * n;
+            launch_locate_bits_acc(s.stream, L.a, pr, pc, ny, nx, s.d_status + f, pi == 0, has[(size_t)b0] != 0, b1 >= 0 && has[(size_t)b1] != 0,
+                                   mf + (size_t)b0 * n, b1 >= 0 ? mf + (size_t)b1 * n : nullptr, energy + (size_t)f * n,
+                                   L.part + (size_t)f * L.part_stride + (size_t)pi * blk_bytes,
+                                   pi == npairs - 1 ? L.epart + (size_t)f * L.epart_stride : nullptr);
+        }
+    }
+    // the records: [frames][4] of the energy map, then [frames][nbits] soft values
+    for (int f = 0; f < frames; ++f)
+        launch_locate_bits_fold(s.stream, L.epart + (size_t)f * L.epart_stride, L.part + (size_t)f * L.part_stride, ny, nx, nbits, energy + (size_t)f * n,
+                                maps + (size_t)f * nbits * n, s.d_status + f, res + WM_LOCATE_BITS_NVALS * f,
+                                res + WM_LOCATE_BITS_NVALS * frames + (size_t)f * nbits);
+    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
+    push_pending(s, frames, WM_LOCATE_BITS_NVALS, false, loc_out, status_out, nullptr);
+    return finish_call(ctx, s, slot, frames, nbits, false, soft_out, nullptr);
+}
+
+// the three passes wm_locate_bits adds to wm_fft_bench's seven, timed the same way: the key-pair plane (128 x 128 tiles over a key
+// of the transform's size), the three-operand product, and the accumulate pass of a later pair over ny x nx offsets
+int wm_locate_bits_bench(int device, int pr, int pc, int ny, int nx, int iters, double* us_out)
+{
+    if (!us_out || iters < 1 || fft_log2(pr) < 0 || fft_log2(pc) < 0 || pr < 128 || pc < 128 || ny < 1 || ny > pr || nx < 1 || nx > pc) return WM_ERR_BAD_ARG;
+    int rc = choose_device(&device);
+    if (rc != WM_OK) return rc;
+    const size_t plane = (size_t)pr * pc * 2 * sizeof(float), n = round256((size_t)ny * nx * sizeof(float));
+    const TileShape ts{128, 128, pr / 128, pc / 128};
+    const size_t tab = round256((size_t)ts.ny * ts.nx * sizeof(int)), part = round256(locate_bits_part_bytes(ny, nx));
+    char* scr = nullptr;
+    const size_t total = 3 * plane + 3 * n + 2 * part + tab + 256;
+    if (hipMalloc((void**)&scr, total) != hipSuccess) { (void)hipGetLastError(); return WM_ERR_ALLOC; }
+    float *a = (float*)scr, *b = (float*)(scr + plane), *c = (float*)(scr + 2 * plane);
+    float *m0 = (float*)(scr + 3 * plane), *m1 = (float*)(scr + 3 * plane + n), *en = (float*)(scr + 3 * plane + 2 * n);
+    char* p0 = scr + 3 * plane + 3 * n;
+    int* table = (int*)(p0 + 2 * part);
+    int* status = (int*)(p0 + 2 * part + tab);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    bool ok = hipMemset(scr, 0, total) == hipSuccess && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
+    for (int pass = 0; ok && pass < WM_LOCATE_BITS_BENCH_PASSES; ++pass) {
+        for (int i = -1; i < iters; ++i) {  // (one untimed launch in front)
+            if (i == 0) ok = ok && hipEventRecord(e0, nullptr) == hipSuccess;
+            switch (pass) {
+            case 0: launch_locate_key_pair(nullptr, a, pr, pc, table, ts, 0, 1, b, pr, pc); break;
+            case 1: launch_locate_mul3(nullptr, a, b, c, (size_t)pr * pc); break;
+            default: launch_locate_bits_acc(nullptr, c, pr, pc, ny, nx, status, false, true, true, m0, m1, en, p0, p0 + part); break;
+            }
+        }
+        float ms = 0.f;
+        ok = ok && hipEventRecord(e1, nullptr) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess &&
+             hipGetLastError() == hipSuccess;
+        us_out[pass] = (double)ms * 1e3 / iters;
+    }
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    (void)hipFree(scr);
+    return ok ? WM_OK : WM_ERR_RUNTIME;
 }
 
 // makeWatermark of every frame with every key of the bank: wm_embed's input and base handling, one record per (frame, key)

@@ -1,5 +1,5 @@
 // wm_k_fft.hip -- the 2-D complex f32 transform behind wm_locate and wm_fft2: k_fft_rows (batched power-of-two rows through LDS),
-// k_fft_transpose (tiled LDS transpose) and k_locate_mul (the spectrum product).
+// k_fft_transpose (tiled LDS transpose), k_locate_mul (the spectrum product) and k_locate_mul3 (the product into a third plane).
 //
 // A 2-D transform of a [pr][pc] plane is: rows of length pc, transpose, rows of length pr -- the spectrum then lies TRANSPOSED
 // ([pc][pr]); wm_locate multiplies and starts the inverse in that layout, so a forward and an inverse transform need one transpose
@@ -136,6 +136,15 @@ __global__ __launch_bounds__(FFT_BLOCK) void k_locate_mul(float4* __restrict__ a
     a[i] = make_float4(h.x * w.x + h.y * w.y, h.x * w.y - h.y * w.x, h.z * w.z + h.w * w.w, h.z * w.w - h.w * w.z);
 }
 
+// k_locate_mul3: out = conj(h) * k per element, h and k kept (wm_locate_bits multiplies one frame's spectrum with every key pair's)
+__global__ __launch_bounds__(FFT_BLOCK) void k_locate_mul3(const float4* __restrict__ hs, const float4* __restrict__ ks, float4* __restrict__ out, size_t n2)
+{
+    const size_t i = (size_t)blockIdx.x * FFT_BLOCK + threadIdx.x;
+    if (i >= n2) return;
+    const float4 h = hs[i], w = ks[i];
+    out[i] = make_float4(h.x * w.x + h.y * w.y, h.x * w.y - h.y * w.x, h.z * w.z + h.w * w.w, h.z * w.w - h.w * w.z);
+}
+
 template <int LOGP>
 void launch_rows_p(hipStream_t s, float2* data, int nrows, const float2* tw, bool inverse)
 {
@@ -191,6 +200,13 @@ void launch_locate_mul(hipStream_t s, float* a, const float* b, size_t n)
     const size_t n2 = n / 2;
     WM_KLAUNCH(k_locate_mul, dim3((unsigned)((n2 + FFT_BLOCK - 1) / FFT_BLOCK)), dim3(FFT_BLOCK), 0, s, reinterpret_cast<float4*>(a),
                reinterpret_cast<const float4*>(b), n2);
+}
+
+void launch_locate_mul3(hipStream_t s, const float* h, const float* k, float* out, size_t n)
+{
+    const size_t n2 = n / 2;
+    WM_KLAUNCH(k_locate_mul3, dim3((unsigned)((n2 + FFT_BLOCK - 1) / FFT_BLOCK)), dim3(FFT_BLOCK), 0, s, reinterpret_cast<const float4*>(h),
+               reinterpret_cast<const float4*>(k), reinterpret_cast<float4*>(out), n2);
 }
 
 }  // namespace wmk

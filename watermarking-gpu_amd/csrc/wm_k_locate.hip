@@ -1,6 +1,8 @@
 // wm_k_locate.hip -- the image and key side of wm_locate around the transform of wm_k_fft.hip: k_locate_e (the frame's prediction
 // error and NVF mask), k_locate_h (h = m * F^T e_w, the exact adjoint of the replicate-border stencil, laid into a zeroed complex
-// plane), k_locate_key (the key plane laid out the same way), k_locate_peak and k_locate_fold (the map and its four numbers).
+// plane), k_locate_key (the key plane laid out the same way), k_locate_peak and k_locate_fold (the map and its four numbers); and
+// of wm_locate_bits: k_locate_key_pair (the key masked to the tiles of two payload bits, one per half of a complex plane),
+// k_locate_bits_acc (the two maps, the energy map and their block folds) and k_locate_bits_fold (the records).
 //
 // With c solved, the detector's numerator is linear in W: <e_u, e_w>(oy, ox) = sum_q h(q) W(q + (oy, ox)), one 2-D cross-correlation
 // of h with the key plane.  Every workgroup works on its own pixels or its own chunk of the map; the fold
@@ -195,7 +197,211 @@ __global__ __launch_bounds__(LB) void k_locate_fold(const PeakRec* __restrict__ 
     res[3] = OpResult{0, z};
 }
 
+// ---- wm_locate_bits: one map per payload bit, two bits per transform -----------------------------------
+
+// k_locate_key_pair: plane[r][c] = (key [tb(tile) == b0], key [tb(tile) == b1]) over the key, (0, 0) outside it.  The tiles lie on
+// the KEY plane by the rule of wm_tiles_shape: tile (min(r / th, tny - 1), min(c / tw, tnx - 1)), the last one of an axis takes the
+// remainder.  b1 = -2 (no entry of the table is below -1): the odd last bit rides alone
+__global__ __launch_bounds__(LB) void k_locate_key_pair(const float* __restrict__ key, int key_rows, int key_cols, const int* __restrict__ tb, int th,
+                                                        int tw, int tny, int tnx, int b0, int b1, float2* __restrict__ plane, int pc)
+{
+    const int c = blockIdx.x * LTX + threadIdx.x % LTX, r = blockIdx.y * LTY + threadIdx.x / LTX;  // (the grid covers pr x pc exactly)
+    float2 v = make_float2(0.0f, 0.0f);
+    if (r < key_rows && c < key_cols) {
+        const int bit = tb[min(r / th, tny - 1) * tnx + min(c / tw, tnx - 1)];
+        const float w = key[(size_t)r * key_cols + c];
+        v = make_float2(bit == b0 ? w : 0.0f, bit == b1 ? w : 0.0f);
+    }
+    plane[(size_t)r * pc + c] = v;
+}
+
+// one block's sums of the two maps of a pair: sum and sum of squares in f64
+struct BitsRec {
+    double s0, q0, s1, q1;
+};
+__device__ __forceinline__ void bits_tree(BitsRec* s_b, int t)
+{
+    for (int half = LB / 2; half > 0; half >>= 1) {
+        __syncthreads();
+        if (t < half) {
+            const BitsRec o = s_b[t + half];
+            BitsRec me = s_b[t];
+            me.s0 += o.s0; me.q0 += o.q0; me.s1 += o.s1; me.q1 += o.q1;
+            s_b[t] = me;
+        }
+    }
+    __syncthreads();
+}
+
+// k_locate_bits_acc: the ny x nx admissible offsets of the pair's inverse plane times 1 / (pr pc): the real parts are bit b0's map,
+// the imaginary parts bit b1's.  Stores both maps, E = re^2 + im^2 for the first pair and E += re^2 + im^2 for the later ones (f32,
+// in the order of the pairs: E's bits do not depend on the batch), and folds each map's sum and sum of squares over the workgroup's
+// 4096 consecutive values into part[block].  use0 / use1 = 0: the bit has no tile (or, use1, the odd last pair has no second bit):
+// its map is exactly zero, not the rounding residue of its partner.  epart (the last pair only): the block's fold of the finished E,
+// as k_locate_peak folds a map.  An unsolvable frame's maps and E are zero
+template <bool FIRST>
+__global__ __launch_bounds__(LB) void k_locate_bits_acc(const float2* __restrict__ plane, int pc, int ny, int nx, float scale, const int* __restrict__ status,
+                                                        int use0, int use1, float* __restrict__ map0, float* __restrict__ map1, float* __restrict__ E,
+                                                        BitsRec* __restrict__ part, PeakRec* __restrict__ epart)
+{
+    __shared__ BitsRec s_b[LB];
+    __shared__ PeakRec s_rec[LB];
+    const int t = threadIdx.x;
+    const long long n = (long long)ny * nx;
+    const long long i0 = (long long)blockIdx.x * (LB * PEAK_PER);
+    const bool dead = status[0] != 0;
+    BitsRec me{0.0, 0.0, 0.0, 0.0};
+    PeakRec pk{0.0, 0.0, -1, 0.0f, 0};
+#pragma unroll 4
+    for (int k = 0; k < PEAK_PER; ++k) {
+        const long long i = i0 + t + (long long)k * LB;
+        if (i >= n) break;
+        const int oy = (int)(i / nx), ox = (int)(i % nx);
+        const float2 v = dead ? make_float2(0.0f, 0.0f) : plane[(size_t)oy * pc + ox];
+        const float re = use0 ? v.x * scale : 0.0f, im = use1 ? v.y * scale : 0.0f;
+        map0[i] = re;
+        if (map1) map1[i] = im;
+        const float e2 = fmaf(im, im, re * re);
+        const float e = FIRST ? e2 : E[i] + e2;
+        E[i] = e;
+        me.s0 += (double)re; me.q0 += (double)re * (double)re;
+        me.s1 += (double)im; me.q1 += (double)im * (double)im;
+        if (epart) {
+            pk.sum += (double)e; pk.sumsq += (double)e * (double)e;
+            if (pk.idx < 0 || peak_better(e, i, pk.val, pk.idx)) { pk.val = e; pk.idx = i; }
+        }
+    }
+    s_b[t] = me;
+    bits_tree(s_b, t);
+    if (t == 0) part[blockIdx.x] = s_b[0];
+    if (epart) {  // (the same in every lane: a kernel argument)
+        s_rec[t] = pk;
+        peak_tree(s_rec, t);
+        if (t == 0) epart[blockIdx.x] = s_rec[0];
+    }
+}
+
+// k_locate_bits_fold: workgroup 0 writes the frame's four records of E by k_locate_fold's rule, workgroup 1 + b the soft value of bit
+// b.  Every workgroup folds E's nblk block records itself, in k_locate_fold's order (thread t takes t, t + 256, ... ascending, then
+// the tree): all agree on the argmax o* without waiting for each other.  Bit b: its block records folded the same way, the values of
+// the 3 x 3 block around o* taken out of the sums -- re-read from the stored map, so they are the map's bits --, and
+// soft = (map_b(o*) - mu_b) / sigma_b in f64; NaN when fewer than two offsets lie outside the block or sigma_b is 0.
+// part: [pairs][nblk], maps: [nbits][ny nx].  An unsolvable frame: its status and zeros
+__global__ __launch_bounds__(LB) void k_locate_bits_fold(const PeakRec* __restrict__ epart, const BitsRec* __restrict__ part, int nblk,
+                                                         const float* __restrict__ E, const float* __restrict__ maps, int ny, int nx,
+                                                         const int* __restrict__ status, OpResult* __restrict__ loc, OpResult* __restrict__ soft)
+{
+    __shared__ PeakRec s_rec[LB];
+    __shared__ double s_sum[LB], s_sq[LB];
+    const int t = threadIdx.x;
+    PeakRec me{0.0, 0.0, -1, 0.0f, 0};
+    for (int b = t; b < nblk; b += LB) {
+        const PeakRec o = epart[b];
+        me.sum += o.sum; me.sumsq += o.sumsq;
+        if (o.idx >= 0 && (me.idx < 0 || peak_better(o.val, o.idx, me.val, me.idx))) { me.val = o.val; me.idx = o.idx; }
+    }
+    s_rec[t] = me;
+    peak_tree(s_rec, t);
+    const PeakRec tot = s_rec[0];
+    const int st = status[0];
+    const int oy = (int)(tot.idx / nx), ox = (int)(tot.idx % nx);
+    const int i_lo = max(oy - 1, 0), i_hi = min(oy + 1, ny - 1), j_lo = max(ox - 1, 0), j_hi = min(ox + 1, nx - 1);
+    const long long n = (long long)ny * nx;
+    if (blockIdx.x == 0) {
+        if (t != 0) return;
+        if (st != 0) {
+            for (int k = 0; k < 4; ++k) loc[k] = OpResult{st, 0.0f};
+            return;
+        }
+        double sum = tot.sum, sumsq = tot.sumsq;
+        long long cnt = n;
+        for (int i = i_lo; i <= i_hi; ++i)
+            for (int j = j_lo; j <= j_hi; ++j) {
+                const double v = (double)E[(size_t)i * nx + j];
+                sum -= v; sumsq -= v * v; --cnt;
+            }
+        float z = __builtin_nanf("");
+        if (cnt >= 2) {
+            const double mu = sum / (double)cnt;
+            const double var = sumsq / (double)cnt - mu * mu;
+            if (var > 0.0) z = (float)(((double)tot.val - mu) / sqrt(var));
+        }
+        loc[0] = OpResult{0, (float)oy};
+        loc[1] = OpResult{0, (float)ox};
+        loc[2] = OpResult{0, tot.val};
+        loc[3] = OpResult{0, z};
+        return;
+    }
+    const int bit = (int)blockIdx.x - 1;
+    const BitsRec* __restrict__ pp = part + (size_t)(bit / 2) * nblk;
+    double sum = 0.0, sumsq = 0.0;
+    for (int b = t; b < nblk; b += LB) {
+        const BitsRec o = pp[b];
+        sum += bit % 2 ? o.s1 : o.s0; sumsq += bit % 2 ? o.q1 : o.q0;
+    }
+    s_sum[t] = sum; s_sq[t] = sumsq;
+    for (int half = LB / 2; half > 0; half >>= 1) {
+        __syncthreads();
+        if (t < half) { s_sum[t] += s_sum[t + half]; s_sq[t] += s_sq[t + half]; }
+    }
+    if (t != 0) return;
+    if (st != 0) {
+        soft[bit] = OpResult{st, 0.0f};
+        return;
+    }
+    const float* __restrict__ mp = maps + (size_t)bit * n;
+    sum = s_sum[0]; sumsq = s_sq[0];
+    long long cnt = n;
+    for (int i = i_lo; i <= i_hi; ++i)
+        for (int j = j_lo; j <= j_hi; ++j) {
+            const double v = (double)mp[(size_t)i * nx + j];
+            sum -= v; sumsq -= v * v; --cnt;
+        }
+    float z = __builtin_nanf("");
+    if (cnt >= 2) {
+        const double mu = sum / (double)cnt;
+        const double var = sumsq / (double)cnt - mu * mu;
+        if (var > 0.0) z = (float)(((double)mp[tot.idx] - mu) / sqrt(var));
+    }
+    soft[bit] = OpResult{0, z};
+}
+
 }  // namespace
+
+size_t locate_bits_part_bytes(int ny, int nx)
+{
+    const long long n = (long long)ny * nx;
+    return (size_t)((n + LB * PEAK_PER - 1) / (LB * PEAK_PER)) * sizeof(BitsRec);
+}
+
+void launch_locate_key_pair(hipStream_t s, const float* key, int key_rows, int key_cols, const int* tile_bit, const TileShape& ts, int b0, int b1,
+                            float* plane, int pr, int pc)
+{
+    WM_KLAUNCH(k_locate_key_pair, dim3(pc / LTX, pr / LTY), dim3(LB), 0, s, key, key_rows, key_cols, tile_bit, ts.th, ts.tw, ts.ny, ts.nx, b0, b1,
+               reinterpret_cast<float2*>(plane), pc);
+}
+
+void launch_locate_bits_acc(hipStream_t s, const float* plane, int pr, int pc, int ny, int nx, const int* status, bool first, bool use0, bool use1,
+                            float* map0, float* map1, float* energy, void* part, void* epart)
+{
+    const float scale = 1.0f / ((float)pr * (float)pc);  // (a power of two: the scaling is exact)
+    const int nblk = (int)(locate_bits_part_bytes(ny, nx) / sizeof(BitsRec));
+    const float2* pl = reinterpret_cast<const float2*>(plane);
+    if (first)
+        WM_KLAUNCH(k_locate_bits_acc<true>, dim3(nblk), dim3(LB), 0, s, pl, pc, ny, nx, scale, status, use0 ? 1 : 0, use1 ? 1 : 0, map0, map1, energy,
+                   static_cast<BitsRec*>(part), static_cast<PeakRec*>(epart));
+    else
+        WM_KLAUNCH(k_locate_bits_acc<false>, dim3(nblk), dim3(LB), 0, s, pl, pc, ny, nx, scale, status, use0 ? 1 : 0, use1 ? 1 : 0, map0, map1, energy,
+                   static_cast<BitsRec*>(part), static_cast<PeakRec*>(epart));
+}
+
+void launch_locate_bits_fold(hipStream_t s, const void* epart, const void* part, int ny, int nx, int nbits, const float* energy, const float* maps,
+                             const int* status, OpResult* loc, OpResult* soft)
+{
+    const int nblk = (int)(locate_bits_part_bytes(ny, nx) / sizeof(BitsRec));
+    WM_KLAUNCH(k_locate_bits_fold, dim3(1 + nbits), dim3(LB), 0, s, static_cast<const PeakRec*>(epart), static_cast<const BitsRec*>(part), nblk, energy,
+               maps, ny, nx, status, loc, soft);
+}
 
 size_t locate_part_bytes(int ny, int nx)
 {

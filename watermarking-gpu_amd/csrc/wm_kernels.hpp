@@ -380,6 +380,21 @@ void launch_locate_h(const Sweep& sw, int frame, const float* e, const float* m,
 void launch_locate_key(hipStream_t s, const float* key, int key_rows, int key_cols, float* plane, int pr, int pc);
 void launch_locate_peak(hipStream_t s, const float* plane, int pr, int pc, int ny, int nx, const int* status, float* map, void* part,
                         OpResult* res);
+// a payload-marked crop (wm_locate_bits): two bits per transform.  launch_locate_mul3: out = conj(h) * k over n complex elements (n
+// even), h and k kept.  launch_locate_key_pair: the key masked to the tiles of bit b0 (real part) and of bit b1 (imaginary part; -2:
+// none) as a zeroed [pr][pc] complex plane; tile_bit: the DEVICE table over the tiles ts of the KEY plane.  launch_locate_bits_acc:
+// the pair's inverse plane into the two maps (map1 null: no second bit; use0 / use1 false: a bit without a tile, whose map is exactly
+// zero) and into energy (first: stored, else added); part: one frame's and pair's block records (locate_bits_part_bytes), epart: the
+// frame's fold of the finished energy map (locate_part_bytes; the last pair only, else null).  launch_locate_bits_fold: the frame's
+// four records of the energy map into loc[0 .. 4) and its soft values into soft[0 .. nbits); part: [pairs][blocks], maps: [nbits][ny nx]
+size_t locate_bits_part_bytes(int ny, int nx);
+void launch_locate_mul3(hipStream_t s, const float* h, const float* k, float* out, size_t n);
+void launch_locate_key_pair(hipStream_t s, const float* key, int key_rows, int key_cols, const int* tile_bit, const TileShape& ts, int b0, int b1,
+                            float* plane, int pr, int pc);
+void launch_locate_bits_acc(hipStream_t s, const float* plane, int pr, int pc, int ny, int nx, const int* status, bool first, bool use0, bool use1,
+                            float* map0, float* map1, float* energy, void* part, void* epart);
+void launch_locate_bits_fold(hipStream_t s, const void* epart, const void* part, int ny, int nx, int nbits, const float* energy, const float* maps,
+                             const int* status, OpResult* loc, OpResult* soft);
 // band mode: solve the 8x8 system from all-reduced Gram totals [frames][44]; writes coef / status like k_gram's tail
 void launch_solve_totals(hipStream_t s, int frames, const double* totals, float* coef, int* status);
 // band mode, device-resident exchange (wm_band_*_dev): glue kernels between the sweeps and the caller's collectives
