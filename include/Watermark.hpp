@@ -360,6 +360,20 @@ public:
         for (size_t f = 0; f < out.size(); ++f) out[f] = WmLocation{(int)v[4 * f], (int)v[4 * f + 1], v[4 * f + 2], v[4 * f + 3]};
         return out;
     }
+    // whose key is in a cropped copy, and where?  locate of every frame against keys k0 .. k0 + nk - 1 of `keys` in one call, two keys
+    // per transform (wm.h wm_locate_keys).  Frame-major: entry [frame * nk + j] is key k0 + j's; wm_locate_keys_rank names the owner
+    // of a frame from the z of its nk entries.  A key plane that is all zero gives {0, 0, 0, NaN}, an unsolvable frame {0, 0, 0, 0}
+    std::vector<WmLocation> locateKeys(const wm::Image& watermarkedImage, const WatermarkKeys& keys, int k0, int nk, MASK_TYPE maskType) const
+    {
+        const wm_plane pimg = watermarkedImage.plane();
+        const size_t n = (size_t)pimg.frames * (size_t)(nk > 0 ? nk : 0);
+        std::vector<float> v(n * WM_LOCATE_KEYS_NVALS + 1, 0.0f);  // (never an empty buffer: nk < 1 is the library's to refuse)
+        const int rc = wm_locate_keys(ctx, (int)maskType, &pimg, keys.handle(), k0, nk, v.data(), nullptr, nullptr, WM_SLOT_SYNC);
+        if (rc < 0) fail(rc, "locateKeys");
+        std::vector<WmLocation> out(n);
+        for (size_t i = 0; i < n; ++i) out[i] = WmLocation{(int)v[4 * i], (int)v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]};
+        return out;
+    }
     // locate for a cropped copy that carries a PAYLOAD (wm.h wm_locate_bits): tileBit holds one entry per tileRows x tileCols tile of
     // the KEY plane (-1: no bit).  Returns per frame the location on the energy map; soft [frame * nbits + b] > 0 reads bit b as set
     // (NaN: a bit without a tile)

@@ -397,6 +397,54 @@ int wm_locate_bits_cover(int rows, int cols, int key_rows, int key_cols, int til
 #define WM_LOCATE_BITS_BENCH_PASSES 3
 int wm_locate_bits_bench(int device, int pr, int pc, int ny, int nx, int iters, double* us_out /* [WM_LOCATE_BITS_BENCH_PASSES] */);
 
+/* ---- A crop against a bank of keys: whose key, and where -------------------------------------------------------------------------
+ * wm_embed_keys hands every recipient a copy marked with their own key; such a copy comes back cropped.  wm_locate_keys is wm_locate of
+ * every frame against keys k0 .. k0 + nk - 1 of the bank in one call.  Nothing on the image side depends on the key: the Gram sweep,
+ * the solve, h and its spectrum are formed once per frame.  h and the keys are real, so two keys ride in one complex transform:
+ * correlating h with key_a + i key_b gives map_a + i map_b.  Keys k0 + 2i and k0 + 2i + 1 form pair i; for an odd nk the last key rides
+ * alone with a zero imaginary half.  Per frame that is one forward transform, and per pair of keys and frame one forward (shared by
+ * the frames) and one inverse transform.
+ * Inputs and geometry are wm_locate's: the context supplies the image shape, p and the device, not its W; planes of f32 or u8, any
+ * pitch and width, WM_MEM_HOST included, in batches up to max_frames; ME needs p = 3 (WM_ERR_BAD_P), NVF takes p = 3 .. 9;
+ * wm_locate_shape gives ny, nx, pr and pc.  It refuses in wm_locate's order -- null ctx, mask, a null img or keys or loc_out and
+ * maps_dev both NULL, the key range (k0 < 0, nk < 1, k0 + nk > nkeys), the bank, wm_locate_shape, band mode, slot, plane, record room
+ * (frames * nk * 4 records against the slot's 4096, WM_ERR_BUSY) --, all of it before any device work.  Outputs, valid after wm_sync:
+ *     loc_out[frame][j][4]    wm_locate's {oy, ox, peak, z} of key k0 + j, by its rule: the argmax (ties: the smallest index), the map
+ *                             value there, z in f64 against the offsets outside the 3 x 3 block around it, NaN by wm_locate's
+ *                             conditions.  The nine values are formed again as the map pass formed them: they are the map's bits
+ *     maps_dev                DEVICE [frames][nk][ny][nx] f32, may be NULL: the maps; maps_dev[f][j][oy][ox] == peak bit for bit
+ *     status_out[frames]      may be NULL
+ * An unsolvable frame: status WM_UNSOLVABLE, {0, 0, 0, 0} for every key and zero maps.  A key plane that is all zero (a new bank's
+ * planes are) gives an exact zero map and {0, 0, 0, NaN}, as wm_locate gives for it: the device notes per key whether its plane holds
+ * a value other than 0, and a half of a pair without one is written as zero, not as the f32 residue of its partner.
+ * A (frame, key)'s map and numbers do not depend on the batch or on repetition.  They DO depend, in the last bits, on the key's
+ * partner in the pair and hence on k0 and nk, and they agree with wm_locate's for that key to the transform's rounding (1e-4 sigma_W
+ * is the tested bound of either against the f64 model), not bit for bit.  wm_locate_keys_rank names the owner; the owner's key
+ * reaches z of 20-80 at the true offset and every other key stays below 6.
+ * An ENQUEUE on the slot (WM_SLOT_SYNC: slot 0, and waits); never takes the fused kernels, leaves no hand-over, ends none, does not
+ * change what WM_MEM_SLOT_OUT names; its kernels are not in the wm_prof_* list.  Scratch per slot, an allocation of its own beside
+ * wm_locate's and wm_locate_bits', grown on demand (WM_ERR_ALLOC when it does not fit; a call whose shapes or frame count differ from
+ * the one before waits for the slot's stream) and released by the reconfiguring calls:
+ *     bytes = (frames + 3) * pr * pc * 8  +  2 * rows * cols * 4  +  2 * ceil(ny * nx / 4096) * 32  +  1025 * 4  +  tables
+ * -- about 575 MB for a 4K key (4096 x 4096 transform), a 1600 x 3000 crop and one frame, whatever nk.  There is no map storage when
+ * maps_dev is NULL: the records of a pair are folded from the inverse plane before the next pair overwrites it.
+ * HAZARD: the bank stays alive and unmodified until wm_sync of this slot, as for wm_locate.
+ * wm_locate_keys_rank (pure host arithmetic) reads one frame's [nk][4] records: best = the index of the largest z (NaN is ignored,
+ * ties: the smallest index), z_best that z, z_next the largest z among the other keys (NaN when there is none); best = -1 and both
+ * NaN when every z is NaN.  WM_ERR_BAD_ARG for a null pointer or nk < 1. */
+#define WM_LOCATE_KEYS_NVALS 4   /* per (frame, key), HOST f32, by wm_sync: {oy, ox, peak, z} */
+int wm_locate_keys(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* keys, int k0, int nk,
+                   float* loc_out  /* HOST [frames][nk][4], by wm_sync */,
+                   float* maps_dev /* DEVICE [frames][nk][ny][nx] f32, may be NULL */,
+                   int* status_out /* [frames], may be NULL */, int slot);
+int wm_locate_keys_rank(const float* loc /* [nk][4] of one frame */, int nk, int* best, float* z_best, float* z_next);
+/* Yardstick (tools/locate_keys_bench.py), beside wm_fft_bench and wm_locate_bits_bench and timed the same way: the two passes
+ * wm_locate_keys adds to them -- the key-pair plane (two pr x pc keys read, one plane written) and the map pass of a pair over
+ * ny x nx offsets (8 bytes read and 8 written per offset).  pr, pc: powers of two in 128 .. 8192, ny <= pr, nx <= pc; anything else
+ * WM_ERR_BAD_ARG. */
+#define WM_LOCATE_KEYS_BENCH_PASSES 2
+int wm_locate_keys_bench(int device, int pr, int pc, int ny, int nx, int iters, double* us_out /* [WM_LOCATE_KEYS_BENCH_PASSES] */);
+
 /* ---- Tile map: where in the frame is the mark? -------------------------------------------------------------------------------
  * wm_detect answers with one correlation for the whole plane.  A copy with a logo pasted over it, a picture-in-picture or a
  * spliced region only lets that score sag.  The detector is local, though: after the one solve per frame, e_w, u = m W and e_u

@@ -90,6 +90,9 @@ ABI = [
                                  _P(C.c_float), C.c_void_p, C.c_void_p, _P(C.c_int), C.c_int]),
     ("wm_locate_bits_cover", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, _P(C.c_int64)]),
     ("wm_locate_bits_bench", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_double)]),
+    ("wm_locate_keys", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), C.c_void_p, C.c_int, C.c_int, _P(C.c_float), C.c_void_p, _P(C.c_int), C.c_int]),
+    ("wm_locate_keys_rank", C.c_int, [_P(C.c_float), C.c_int, _P(C.c_int), _P(C.c_float), _P(C.c_float)]),
+    ("wm_locate_keys_bench", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_double)]),
     ("wm_fft2", C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     ("wm_fft_bench", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_double)]),
     ("wm_tiles_shape", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_int), _P(C.c_int)]),
@@ -330,6 +333,34 @@ def locate_bits_bench(pr, pc, ny, nx, iters=20, device=0):
     if rc != WM_OK:
         _raise(rc)
     return dict(zip(LOCATE_BITS_BENCH_PASSES, us))
+
+
+WM_LOCATE_KEYS_NVALS = 4
+LOCATE_KEYS_BENCH_PASSES = ("keys_pair", "keys_peak")
+
+
+def locate_keys_rank(loc):
+    """wm.h wm_locate_keys_rank on one frame's records [nk, 4] of Watermark.locateKeys: (best, z_best, z_next) -- the index of the key
+    with the largest z (NaN is ignored, ties: the smallest index; -1 when every z is NaN), that z, and the largest z among the others
+    (NaN when there is none)"""
+    a = np.ascontiguousarray(loc, np.float32)
+    if a.ndim != 2 or a.shape[1] != WM_LOCATE_KEYS_NVALS:
+        raise RuntimeError("locate_keys_rank: loc must be one frame's [nk, 4] records")
+    best, zb, zn = C.c_int(), C.c_float(), C.c_float()
+    rc = lib().wm_locate_keys_rank(a.ctypes.data_as(_P(C.c_float)), a.shape[0], C.byref(best), C.byref(zb), C.byref(zn))
+    if rc != WM_OK:
+        _raise(rc)
+    return best.value, zb.value, zn.value
+
+
+def locate_keys_bench(pr, pc, ny, nx, iters=20, device=0):
+    """wm.h wm_locate_keys_bench: {pass: mean microseconds per launch} of the two passes wm_locate_keys adds to a transform's seven
+    and wm_locate_bits_bench's product"""
+    us = (C.c_double * len(LOCATE_KEYS_BENCH_PASSES))()
+    rc = lib().wm_locate_keys_bench(device, pr, pc, ny, nx, iters, us)
+    if rc != WM_OK:
+        _raise(rc)
+    return dict(zip(LOCATE_KEYS_BENCH_PASSES, us))
 
 
 def fft2(t, inverse=False):
@@ -683,6 +714,24 @@ class Watermark:
         one = image.dim() == 2
         if want_map:
             return (loc[0], map_t[0]) if one else (loc, map_t)
+        return loc[0] if one else loc
+
+    def locateKeys(self, image, keys, k0, nk, maskType=MASK_TYPE.ME, want_maps=False):
+        """whose key is in a cropped copy, and where?  locate() of every frame against keys k0 .. k0 + nk - 1 of the KeySet in one call,
+        two keys per transform (wm.h wm_locate_keys): a float32 numpy array [frames, nk, 4] ([nk, 4] for one grey frame) = (oy, ox,
+        peak, z) per key; locate_keys_rank names the owner.  Zeros for an unsolvable frame, (0, 0, 0, NaN) for a key plane that is all
+        zero.  want_maps=True: (loc, maps) with maps a float32 GPU tensor [frames, nk, ny, nx] ([nk, ny, nx])"""
+        import torch
+        pimg = plane_of(image, 1)
+        frames = pimg.frames
+        ny, nx, _, _ = locate_shape(self.rows, self.cols, keys.rows, keys.cols)
+        loc = np.zeros((frames, max(nk, 0), WM_LOCATE_KEYS_NVALS), np.float32)
+        maps_t = torch.empty((frames, max(nk, 0), ny, nx), dtype=torch.float32, device=image.device) if want_maps else None
+        torch.cuda.current_stream().synchronize()
+        self.locate_keys_async(image, keys, k0, nk, maskType, WM_SLOT_SYNC, loc, maps_t)
+        one = image.dim() == 2
+        if want_maps:
+            return (loc[0], maps_t[0]) if one else (loc, maps_t)
         return loc[0] if one else loc
 
     def locate_bits(self, image, keys, k, tile_rows, tile_cols, tile_bit, nbits, maskType=MASK_TYPE.ME, want_energy=False, want_maps=False):
@@ -1094,6 +1143,21 @@ class Watermark:
                 raise RuntimeError("map_t must be a contiguous float32 GPU tensor")
             pmap = C.c_void_p(map_t.data_ptr())
         self._chk(lib().wm_locate(self._ctx, int(maskType), C.byref(pimg), _keys_handle(keys), k, loc_out, pmap, status_out, slot))
+
+    def locate_keys_async(self, image, keys, k0, nk, maskType, slot, loc_out, maps_t=None, status_out=None):
+        """wm_locate_keys enqueued on `slot`: loc_out (frames * nk * 4 floats: a ctypes array or a C-contiguous float32 numpy array, may
+        be None when maps_t is given) and status_out (frames ints, may be None) are written by sync(slot); maps_t (a contiguous float32
+        GPU tensor of frames * nk * ny * nx elements, may be None) is written on the slot's stream.  `keys` must stay alive and
+        unmodified until then"""
+        import torch
+        pimg = self._as_plane(image, 1)
+        loc_out, status_out = self._scalars_out(loc_out, status_out)
+        pmaps = None
+        if maps_t is not None:
+            if not (maps_t.is_cuda and maps_t.dtype == torch.float32 and maps_t.is_contiguous()):
+                raise RuntimeError("maps_t must be a contiguous float32 GPU tensor")
+            pmaps = C.c_void_p(maps_t.data_ptr())
+        self._chk(lib().wm_locate_keys(self._ctx, int(maskType), C.byref(pimg), _keys_handle(keys), k0, nk, loc_out, pmaps, status_out, slot))
 
     def locate_bits_async(self, image, keys, k, tile_rows, tile_cols, tile_bit, nbits, maskType, slot, loc_out, soft_out, energy_t=None,
                           maps_t=None, status_out=None):

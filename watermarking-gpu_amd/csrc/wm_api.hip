@@ -184,6 +184,10 @@ struct Slot {
     // passes none, and the block records (LocBitsScratch; grown on demand).  locb_key: the shapes its layout and tables are for
     void* locb_scr = nullptr; size_t locb_scr_bytes = 0;
     long long locb_key[6] = {0, 0, 0, 0, 0, 0};
+    // wm_locate_keys: frames + 3 complex planes, the e and m planes, the tables, the block records of one pair and the per-key
+    // non-zero flags (LocKeysScratch; its own allocation, grown on demand).  lock_key: the shapes its layout and tables are for
+    void* lock_scr = nullptr; size_t lock_scr_bytes = 0;
+    long long lock_key[3] = {0, 0, 0};
 };
 
 struct ProfRec { int kid; hipEvent_t a, b; bool first; };  // first: the sweep's first launch (counts the call)
@@ -388,7 +392,7 @@ void free_slot(Slot& s)
     (void)hipFree(s.d_hodig); (void)hipFree(s.keys_part); (void)hipFree(s.ekeys_part); (void)hipFree(s.tiles_rec); (void)hipFree(s.keys_tiles_rec);
     if (s.tab_host) (void)hipHostFree(s.tab_host);
     (void)hipFree(s.tab_dev); (void)hipFree(s.bits_scr); (void)hipFree(s.x16); (void)hipFree(s.y16); (void)hipFree(s.qual_scr); (void)hipFree(s.loc_scr);
-    (void)hipFree(s.locb_scr);
+    (void)hipFree(s.locb_scr); (void)hipFree(s.lock_scr);
     s = Slot();
 }
 
@@ -2437,6 +2441,170 @@ int wm_locate_bits_bench(int device, int pr, int pc, int ny, int nx, int iters, 
             case 1: launch_locate_mul3(nullptr, a, b, c, (size_t)pr * pc); break;
             default: launch_locate_bits_acc(nullptr, c, pr, pc, ny, nx, status, false, true, true, m0, m1, en, p0, p0 + part); break;
             }
+        }
+        float ms = 0.f;
+        ok = ok && hipEventRecord(e1, nullptr) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess &&
+             hipGetLastError() == hipSuccess;
+        us_out[pass] = (double)ms * 1e3 / iters;
+    }
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    (void)hipFree(scr);
+    return ok ? WM_OK : WM_ERR_RUNTIME;
+}
+
+// ---- wm_locate_keys: whose key is in a crop, and where ----------------------------------------------------
+namespace {
+constexpr int LOCK_MAX_KEYS = RES_CAP / WM_LOCATE_KEYS_NVALS;  // (more keys than this never pass the record-room check)
+// the slot's wm_locate_keys scratch as one allocation: the tables, the frames' spectra hs [frames] (transposed), planes a (work: h,
+// the key pair, the inverse), kw (the pair's spectrum, transposed) and p (the product), e and m, the block records of the two halves
+// of one (pair, frame) -- its fold runs before the next one's map pass -- and the per-key non-zero flags
+struct LocKeysScratch {
+    float *tw_r, *tw_c, *hs, *a, *kw, *p, *e, *m;
+    char* part;
+    int* nz;
+    size_t plane_floats, bytes;
+};
+LocKeysScratch lock_layout(void* base, int rows, int cols, int pr, int pc, int ny, int nx, int frames)
+{
+    const size_t plane = (size_t)pr * pc * 2 * sizeof(float), img = round256((size_t)rows * cols * sizeof(float));
+    char* p = (char*)base;
+    LocKeysScratch L;
+    L.plane_floats = (size_t)pr * pc * 2;
+    L.tw_r = (float*)p; p += round256((size_t)pr * 2 * sizeof(float));
+    L.tw_c = (float*)p; p += round256((size_t)pc * 2 * sizeof(float));
+    L.hs = (float*)p; p += plane * frames;
+    L.a = (float*)p; p += plane;
+    L.kw = (float*)p; p += plane;
+    L.p = (float*)p; p += plane;
+    L.e = (float*)p; p += img;
+    L.m = (float*)p; p += img;
+    L.part = p; p += round256(2 * locate_part_bytes(ny, nx));
+    L.nz = (int*)p; p += round256((size_t)(LOCK_MAX_KEYS + 1) * sizeof(int));  // (+ 1: the flag of the odd last key's missing partner)
+    L.bytes = (size_t)(p - (char*)base);
+    return L;
+}
+}  // namespace
+
+// wm_locate of every frame against keys k0 .. k0 + nk - 1, two keys per complex transform: the frames' spectra are kept, every
+// pair's plane is transformed once per call, and per (pair, frame) there are a product, an inverse transform, the map pass and the
+// fold of its records.  None of its kernels runs inside a ProfScope
+int wm_locate_keys(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* keys, int k0, int nk, float* loc_out, float* maps_dev, int* status_out,
+                   int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    int rc = check_mask(ctx, mask);
+    if (rc != WM_OK) return rc;
+    if (!img || !keys || (!loc_out && !maps_dev)) return fail(ctx, WM_ERR_BAD_ARG, "wm_locate_keys: null img or keys, or loc_out and maps_dev both null");
+    if (k0 < 0 || nk < 1 || (long long)k0 + nk > keys->nkeys)
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_locate_keys: keys " + std::to_string(k0) + " .. " + std::to_string((long long)k0 + nk - 1) + " of a bank of " +
+                                             std::to_string(keys->nkeys));
+    if ((rc = check_bank(ctx, keys, "wm_locate_keys", false)) != WM_OK) return rc;
+    int ny, nx, pr, pc;
+    if (wm_locate_shape(ctx->rows, ctx->cols, keys->rows, keys->cols, &ny, &nx, &pr, &pc) != WM_OK)
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_locate_keys: a " + std::to_string(keys->rows) + "x" + std::to_string(keys->cols) +
+                                             " key plane needs a transform above " + std::to_string(1 << FFT_LOG_MAX) + " per axis");
+    if ((rc = refuse_band(ctx, "wm_locate_keys")) != WM_OK) return rc;
+    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
+    // (open_input checks the plane and the record room again: the room has to be known before per_frame is narrowed to an int)
+    if ((rc = check_plane(ctx, img, 0, false, "image", true)) != WM_OK) return rc;
+    const int frames = img->frames;
+    const long long per_frame = (long long)WM_LOCATE_KEYS_NVALS * nk;
+    if ((rc = check_res_room(ctx, s, frames * per_frame, "(4 x keys)")) != WM_OK) return rc;
+    Sweep sw;
+    if ((rc = open_input(ctx, s, img, "image", mask, (int)per_frame, "(4 x keys)", &sw)) != WM_OK) return rc;
+
+    // scratch and tables: another layout moves the planes under the calls still queued on the slot, so it waits for them
+    const long long key_now[3] = {((long long)pr << 32) | pc, ((long long)ny << 32) | nx, frames};
+    const size_t need = lock_layout(nullptr, ctx->rows, ctx->cols, pr, pc, ny, nx, frames).bytes;
+    const bool reshape = !std::equal(key_now, key_now + 3, s.lock_key) || s.lock_scr_bytes < need;
+    if (reshape) {
+        HIPCHK(ctx, hipStreamSynchronize(s.stream));
+        std::fill(s.lock_key, s.lock_key + 3, 0LL);
+        if ((rc = ensure(ctx, &s.lock_scr, &s.lock_scr_bytes, need, WM_ERR_ALLOC)) != WM_OK) return rc;
+    }
+    const LocKeysScratch L = lock_layout(s.lock_scr, ctx->rows, ctx->cols, pr, pc, ny, nx, frames);
+    if (reshape) {
+        std::vector<float> tw((size_t)2 * std::max(pr, pc));
+        fft_twiddles(pr, tw.data());
+        HIPCHK(ctx, hipMemcpy(L.tw_r, tw.data(), (size_t)pr * 2 * sizeof(float), hipMemcpyHostToDevice));
+        fft_twiddles(pc, tw.data());
+        HIPCHK(ctx, hipMemcpy(L.tw_c, tw.data(), (size_t)pc * 2 * sizeof(float), hipMemcpyHostToDevice));
+        std::copy(key_now, key_now + 3, s.lock_key);
+    }
+    const size_t n = (size_t)ny * nx, npl = (size_t)pr * pc, key_elems = (size_t)keys->rows * keys->cols;
+    OpResult* res = s.d_res + s.res_used;
+    HIPCHK(ctx, hipMemsetAsync(L.nz, 0, (size_t)(nk + 1) * sizeof(int), s.stream));
+    // the image side is wm_locate's: the Gram sweep and the solve, then every frame's e (and m), h and its spectrum, kept
+    if ((rc = gram_sweep(ctx, s, sw, img)) != WM_OK) return rc;
+    for (int f = 0; f < frames; ++f) {
+        launch_locate_e(sw, f, L.e, L.m);
+        launch_locate_h(sw, f, L.e, L.m, L.a, pr, pc);
+        fft2_forward_t(s.stream, L.a, L.hs + f * L.plane_floats, pr, pc, L.tw_r, L.tw_c);
+    }
+    // pair-major: the pair's plane and its spectrum once per call, then per frame the product, the way back, the maps and the records
+    for (int j = 0; j < nk; j += 2) {
+        const bool pair = j + 1 < nk;
+        const float* ka = keys->d + (size_t)(k0 + j) * key_elems;
+        launch_locate_keys_pair(s.stream, ka, pair ? ka + key_elems : nullptr, keys->rows, keys->cols, L.a, pr, pc, L.nz + j);
+        fft2_forward_t(s.stream, L.a, L.kw, pr, pc, L.tw_r, L.tw_c);
+        for (int f = 0; f < frames; ++f) {
+            launch_locate_mul3(s.stream, L.hs + f * L.plane_floats, L.kw, L.p, npl);
+            fft2_inverse_t(s.stream, L.p, L.a, pr, pc, L.tw_r, L.tw_c);
+            float* mf = maps_dev ? maps_dev + ((size_t)f * nk + j) * n : nullptr;
+            launch_locate_keys_peak(s.stream, L.a, pr, pc, ny, nx, s.d_status + f, L.nz + j, pair, mf, mf && pair ? mf + n : nullptr, L.part,
+                                    res + ((size_t)f * nk + j) * WM_LOCATE_KEYS_NVALS);
+        }
+    }
+    return finish_call(ctx, s, slot, frames, (int)per_frame, false, loc_out, status_out);
+}
+
+int wm_locate_keys_rank(const float* loc, int nk, int* best, float* z_best, float* z_next)
+{
+    if (!loc || !best || !z_best || !z_next || nk < 1) return WM_ERR_BAD_ARG;
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    int b = -1;
+    for (int j = 0; j < nk; ++j) {
+        const float z = loc[(size_t)j * WM_LOCATE_KEYS_NVALS + 3];
+        if (z == z && (b < 0 || z > loc[(size_t)b * WM_LOCATE_KEYS_NVALS + 3])) b = j;  // (NaN is ignored; ties: the smallest index)
+    }
+    float next = nan;
+    for (int j = 0; j < nk; ++j) {
+        const float z = loc[(size_t)j * WM_LOCATE_KEYS_NVALS + 3];
+        if (j != b && z == z && !(next >= z)) next = z;
+    }
+    *best = b;
+    *z_best = b < 0 ? nan : loc[(size_t)b * WM_LOCATE_KEYS_NVALS + 3];
+    *z_next = next;
+    return WM_OK;
+}
+
+// the two passes wm_locate_keys adds to wm_fft_bench's seven and wm_locate_bits_bench's product, timed the same way: the key-pair
+// plane (two keys of the transform's size) and the map pass of a pair over ny x nx offsets, both maps stored
+int wm_locate_keys_bench(int device, int pr, int pc, int ny, int nx, int iters, double* us_out)
+{
+    if (!us_out || iters < 1 || fft_log2(pr) < 0 || fft_log2(pc) < 0 || pr < 128 || pc < 128 || ny < 1 || ny > pr || nx < 1 || nx > pc) return WM_ERR_BAD_ARG;
+    int rc = choose_device(&device);
+    if (rc != WM_OK) return rc;
+    const size_t plane = (size_t)pr * pc * 2 * sizeof(float), n = round256((size_t)ny * nx * sizeof(float));
+    const size_t part = round256(2 * locate_part_bytes(ny, nx));
+    char* scr = nullptr;
+    const size_t total = 2 * plane + 2 * n + part + 256;
+    if (hipMalloc((void**)&scr, total) != hipSuccess) { (void)hipGetLastError(); return WM_ERR_ALLOC; }
+    // (plane a doubles as the two keys, pr x pc f32 each; its zeros leave the flags clear, which costs the map pass nothing less)
+    float *a = (float*)scr, *b = (float*)(scr + plane);
+    float *m0 = (float*)(scr + 2 * plane), *m1 = (float*)(scr + 2 * plane + n);
+    char* p0 = scr + 2 * plane + 2 * n;
+    int* nz = (int*)(p0 + part);
+    int* status = nz + 2;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    bool ok = hipMemset(scr, 0, total) == hipSuccess && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
+    for (int pass = 0; ok && pass < WM_LOCATE_KEYS_BENCH_PASSES; ++pass) {
+        for (int i = -1; i < iters; ++i) {  // (one untimed launch in front)
+            if (i == 0) ok = ok && hipEventRecord(e0, nullptr) == hipSuccess;
+            if (pass == 0) launch_locate_keys_pair(nullptr, a, a + (size_t)pr * pc, pr, pc, b, pr, pc, nz);
+            else launch_locate_keys_peak(nullptr, b, pr, pc, ny, nx, status, nz, true, m0, m1, p0, nullptr);
         }
         float ms = 0.f;
         ok = ok && hipEventRecord(e1, nullptr) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess &&

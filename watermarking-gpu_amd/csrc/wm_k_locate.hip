@@ -2,7 +2,9 @@
 // error and NVF mask), k_locate_h (h = m * F^T e_w, the exact adjoint of the replicate-border stencil, laid into a zeroed complex
 // plane), k_locate_key (the key plane laid out the same way), k_locate_peak and k_locate_fold (the map and its four numbers); and
 // of wm_locate_bits: k_locate_key_pair (the key masked to the tiles of two payload bits, one per half of a complex plane),
-// k_locate_bits_acc (the two maps, the energy map and their block folds) and k_locate_bits_fold (the records).
+// k_locate_bits_acc (the two maps, the energy map and their block folds) and k_locate_bits_fold (the records); and of wm_locate_keys:
+// k_locate_keys_pair (two keys of a bank, one per half of a complex plane, and a flag per key that is not all zero),
+// k_locate_keys_peak (the two maps and their block folds) and k_locate_keys_fold (the records of the two keys).
 //
 // With c solved, the detector's numerator is linear in W: <e_u, e_w>(oy, ox) = sum_q h(q) W(q + (oy, ox)), one 2-D cross-correlation
 // of h with the key plane.  Every workgroup works on its own pixels or its own chunk of the map; the fold
@@ -126,6 +128,19 @@ __device__ __forceinline__ void peak_tree(PeakRec* s_rec, int t)
     __syncthreads();
 }
 
+// z of a peak against the offsets that remain in (sum, sumsq, cnt) once the 3 x 3 block around it is taken out: (val - mu) / sigma in
+// f64 (population sigma), NaN when fewer than two offsets remain or they do not vary
+__device__ __forceinline__ float peak_z(double sum, double sumsq, long long cnt, float val)
+{
+    float z = __builtin_nanf("");
+    if (cnt >= 2) {
+        const double mu = sum / (double)cnt;
+        const double var = sumsq / (double)cnt - mu * mu;
+        if (var > 0.0) z = (float)(((double)val - mu) / sqrt(var));
+    }
+    return z;
+}
+
 // k_locate_peak: map value i * nx + j = Re plane[i][j] * scale over the ny x nx admissible offsets (scale = 1 / (pr pc): the
 // transforms are not normalised), stored to map when it is given; workgroup b folds values [4096 b, 4096 (b + 1)) into part[b].
 // An unsolvable frame's map is zero
@@ -185,16 +200,10 @@ __global__ __launch_bounds__(LB) void k_locate_fold(const PeakRec* __restrict__ 
             const double v = (double)(plane[(size_t)i * pc + j].x * scale);
             sum -= v; sumsq -= v * v; --cnt;
         }
-    float z = __builtin_nanf("");
-    if (cnt >= 2) {
-        const double mu = sum / (double)cnt;
-        const double var = sumsq / (double)cnt - mu * mu;
-        if (var > 0.0) z = (float)(((double)tot.val - mu) / sqrt(var));
-    }
     res[0] = OpResult{0, (float)oy};
     res[1] = OpResult{0, (float)ox};
     res[2] = OpResult{0, tot.val};
-    res[3] = OpResult{0, z};
+    res[3] = OpResult{0, peak_z(sum, sumsq, cnt, tot.val)};
 }
 
 // ---- wm_locate_bits: one map per payload bit, two bits per transform -----------------------------------
@@ -366,6 +375,112 @@ __global__ __launch_bounds__(LB) void k_locate_bits_fold(const PeakRec* __restri
     soft[bit] = OpResult{0, z};
 }
 
+// ---- wm_locate_keys: one map per key of a bank, two keys per transform ---------------------------------
+
+// k_locate_keys_pair: plane[r][c] = (keyA[r][c], keyB[r][c]) over the key, (0, 0) outside it; keyB null: the odd last key rides alone.
+// nz[0] / nz[1] (cleared on the stream at the start of the call) is set to 1 by every workgroup that saw a value of key A / key B
+// other than 0: the workgroups store the same value, a later kernel on the stream reads it
+__global__ __launch_bounds__(LB) void k_locate_keys_pair(const float* __restrict__ keyA, const float* __restrict__ keyB, int key_rows, int key_cols,
+                                                         float2* __restrict__ plane, int pc, int* __restrict__ nz)
+{
+    const int c = blockIdx.x * LTX + threadIdx.x % LTX, r = blockIdx.y * LTY + threadIdx.x / LTX;  // (the grid covers pr x pc exactly)
+    float2 v = make_float2(0.0f, 0.0f);
+    if (r < key_rows && c < key_cols) {
+        const size_t i = (size_t)r * key_cols + c;
+        v = make_float2(keyA[i], keyB ? keyB[i] : 0.0f);
+    }
+    plane[(size_t)r * pc + c] = v;
+    const int anyA = __syncthreads_or(v.x != 0.0f), anyB = __syncthreads_or(v.y != 0.0f);
+    if (threadIdx.x == 0) {
+        if (anyA) nz[0] = 1;
+        if (anyB) nz[1] = 1;
+    }
+}
+
+// the value of one half of the pair's inverse plane at an offset: the product with 1 / (pr pc), or exactly zero for a half that
+// carries no key (its flag is clear, or the odd last key has no partner) -- not the rounding residue of the other half
+__device__ __forceinline__ float keys_half(const float2 v, int half, float scale, bool use) { return use ? (half ? v.y : v.x) * scale : 0.0f; }
+
+// k_locate_keys_peak: the ny x nx admissible offsets of the pair's inverse plane times 1 / (pr pc): the real parts are key A's map,
+// the imaginary parts key B's (mapA / mapB null: not stored; partB null: no key B).  Workgroup b folds values [4096 b, 4096 (b + 1))
+// of each map into partA[b] / partB[b] as k_locate_peak does.  An unsolvable frame's maps are zero
+__global__ __launch_bounds__(LB) void k_locate_keys_peak(const float2* __restrict__ plane, int pc, int ny, int nx, float scale, const int* __restrict__ status,
+                                                         const int* __restrict__ nz, float* __restrict__ mapA, float* __restrict__ mapB,
+                                                         PeakRec* __restrict__ partA, PeakRec* __restrict__ partB)
+{
+    __shared__ PeakRec s_a[LB];
+    __shared__ PeakRec s_b[LB];
+    const int t = threadIdx.x;
+    const long long n = (long long)ny * nx;
+    const long long i0 = (long long)blockIdx.x * (LB * PEAK_PER);
+    const bool dead = status[0] != 0;
+    const bool useA = nz[0] != 0, useB = partB && nz[1] != 0;
+    PeakRec a{0.0, 0.0, -1, 0.0f, 0}, b{0.0, 0.0, -1, 0.0f, 0};
+#pragma unroll 4
+    for (int k = 0; k < PEAK_PER; ++k) {
+        const long long i = i0 + t + (long long)k * LB;
+        if (i >= n) break;
+        const int oy = (int)(i / nx), ox = (int)(i % nx);
+        const float2 v = dead ? make_float2(0.0f, 0.0f) : plane[(size_t)oy * pc + ox];
+        const float re = keys_half(v, 0, scale, useA), im = keys_half(v, 1, scale, useB);
+        if (mapA) mapA[i] = re;
+        if (mapB) mapB[i] = im;
+        a.sum += (double)re; a.sumsq += (double)re * (double)re;
+        if (a.idx < 0 || peak_better(re, i, a.val, a.idx)) { a.val = re; a.idx = i; }
+        b.sum += (double)im; b.sumsq += (double)im * (double)im;
+        if (b.idx < 0 || peak_better(im, i, b.val, b.idx)) { b.val = im; b.idx = i; }
+    }
+    s_a[t] = a;
+    peak_tree(s_a, t);
+    if (t == 0) partA[blockIdx.x] = s_a[0];
+    if (partB) {  // (the same in every lane: a kernel argument)
+        s_b[t] = b;
+        peak_tree(s_b, t);
+        if (t == 0) partB[blockIdx.x] = s_b[0];
+    }
+}
+
+// k_locate_keys_fold: workgroup 0 writes key A's four records, workgroup 1 key B's (grid 1: no key B), each by k_locate_fold's rule
+// on its own block records (part + half * nblk) and its own half of the plane: the values of the 3 x 3 block around the argmax are
+// formed as k_locate_keys_peak formed them, so they are the map's bits.  res: key A's records, key B's follow
+__global__ __launch_bounds__(LB) void k_locate_keys_fold(const PeakRec* __restrict__ part, int nblk, const float2* __restrict__ plane, int pc, int ny,
+                                                         int nx, float scale, const int* __restrict__ status, const int* __restrict__ nz,
+                                                         OpResult* __restrict__ res)
+{
+    __shared__ PeakRec s_rec[LB];
+    const int t = threadIdx.x, half = (int)blockIdx.x;
+    part += (size_t)half * nblk;
+    res += 4 * half;
+    PeakRec me{0.0, 0.0, -1, 0.0f, 0};
+    for (int b = t; b < nblk; b += LB) {
+        const PeakRec o = part[b];
+        me.sum += o.sum; me.sumsq += o.sumsq;
+        if (o.idx >= 0 && (me.idx < 0 || peak_better(o.val, o.idx, me.val, me.idx))) { me.val = o.val; me.idx = o.idx; }
+    }
+    s_rec[t] = me;
+    peak_tree(s_rec, t);
+    if (t != 0) return;
+    const int st = status[0];
+    if (st != 0) {
+        for (int k = 0; k < 4; ++k) res[k] = OpResult{st, 0.0f};
+        return;
+    }
+    const bool use = nz[half] != 0;
+    const PeakRec tot = s_rec[0];
+    const int oy = (int)(tot.idx / nx), ox = (int)(tot.idx % nx);
+    double sum = tot.sum, sumsq = tot.sumsq;
+    long long cnt = (long long)ny * nx;
+    for (int i = max(oy - 1, 0); i <= min(oy + 1, ny - 1); ++i)
+        for (int j = max(ox - 1, 0); j <= min(ox + 1, nx - 1); ++j) {
+            const double v = (double)keys_half(plane[(size_t)i * pc + j], half, scale, use);
+            sum -= v; sumsq -= v * v; --cnt;
+        }
+    res[0] = OpResult{0, (float)oy};
+    res[1] = OpResult{0, (float)ox};
+    res[2] = OpResult{0, tot.val};
+    res[3] = OpResult{0, peak_z(sum, sumsq, cnt, tot.val)};
+}
+
 }  // namespace
 
 size_t locate_bits_part_bytes(int ny, int nx)
@@ -401,6 +516,22 @@ void launch_locate_bits_fold(hipStream_t s, const void* epart, const void* part,
     const int nblk = (int)(locate_bits_part_bytes(ny, nx) / sizeof(BitsRec));
     WM_KLAUNCH(k_locate_bits_fold, dim3(1 + nbits), dim3(LB), 0, s, static_cast<const PeakRec*>(epart), static_cast<const BitsRec*>(part), nblk, energy,
                maps, ny, nx, status, loc, soft);
+}
+
+void launch_locate_keys_pair(hipStream_t s, const float* key_a, const float* key_b, int key_rows, int key_cols, float* plane, int pr, int pc, int* nz)
+{
+    WM_KLAUNCH(k_locate_keys_pair, dim3(pc / LTX, pr / LTY), dim3(LB), 0, s, key_a, key_b, key_rows, key_cols, reinterpret_cast<float2*>(plane), pc, nz);
+}
+
+void launch_locate_keys_peak(hipStream_t s, const float* plane, int pr, int pc, int ny, int nx, const int* status, const int* nz, bool pair, float* map_a,
+                             float* map_b, void* part, OpResult* res)
+{
+    const float scale = 1.0f / ((float)pr * (float)pc);  // (a power of two: the scaling is exact)
+    const int nblk = (int)(locate_part_bytes(ny, nx) / sizeof(PeakRec));
+    const float2* pl = reinterpret_cast<const float2*>(plane);
+    PeakRec* pa = static_cast<PeakRec*>(part);
+    WM_KLAUNCH(k_locate_keys_peak, dim3(nblk), dim3(LB), 0, s, pl, pc, ny, nx, scale, status, nz, map_a, pair ? map_b : nullptr, pa, pair ? pa + nblk : nullptr);
+    if (res) WM_KLAUNCH(k_locate_keys_fold, dim3(pair ? 2 : 1), dim3(LB), 0, s, pa, nblk, pl, pc, ny, nx, scale, status, nz, res);
 }
 
 size_t locate_part_bytes(int ny, int nx)

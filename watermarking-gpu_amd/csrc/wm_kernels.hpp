@@ -395,6 +395,14 @@ void launch_locate_bits_acc(hipStream_t s, const float* plane, int pr, int pc, i
                             float* map0, float* map1, float* energy, void* part, void* epart);
 void launch_locate_bits_fold(hipStream_t s, const void* epart, const void* part, int ny, int nx, int nbits, const float* energy, const float* maps,
                              const int* status, OpResult* loc, OpResult* soft);
+// a crop against a bank of keys (wm_locate_keys): two keys per transform.  launch_locate_keys_pair: key_a (real part) and key_b
+// (imaginary part; null: none) as a zeroed [pr][pc] complex plane; nz[0] / nz[1], DEVICE ints cleared on the stream beforehand, are
+// set to 1 when key_a / key_b holds a value other than 0.  launch_locate_keys_peak: the pair's inverse plane into map_a and map_b
+// (either may be null; pair false: no key_b), a half whose nz is clear as exact zero, and the frame's four records of key_a into
+// res[0 .. 4), of key_b into res[4 .. 8) (res null: the map pass alone); part: 2 * locate_part_bytes of scratch; status: the frame's
+void launch_locate_keys_pair(hipStream_t s, const float* key_a, const float* key_b, int key_rows, int key_cols, float* plane, int pr, int pc, int* nz);
+void launch_locate_keys_peak(hipStream_t s, const float* plane, int pr, int pc, int ny, int nx, const int* status, const int* nz, bool pair, float* map_a,
+                             float* map_b, void* part, OpResult* res);
 // band mode: solve the 8x8 system from all-reduced Gram totals [frames][44]; writes coef / status like k_gram's tail
 void launch_solve_totals(hipStream_t s, int frames, const double* totals, float* coef, int* status);
 // band mode, device-resident exchange (wm_band_*_dev): glue kernels between the sweeps and the caller's collectives
