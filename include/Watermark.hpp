@@ -394,6 +394,53 @@ public:
         for (size_t f = 0; f < out.size(); ++f) out[f] = WmLocation{(int)v[4 * f], (int)v[4 * f + 1], v[4 * f + 2], v[4 * f + 3]};
         return out;
     }
+    // a clip's frames pooled on the image side (wm.h wm_clip_pool): poolDev, a dense DEVICE f32 [rows][cols] plane of the caller's,
+    // becomes fmaf(w_f, h_f, pool) over the solvable frames of `clip` in ascending order, from zero unless `accumulate`; weights:
+    // empty (all 1) or one per frame.  Returns the frames' statuses; a clip longer than max_frames is pooled in several calls
+    std::vector<int> poolClip(const wm::Image& clip, MASK_TYPE maskType, float* poolDev, bool accumulate = false,
+                              const std::vector<float>& weights = {}) const
+    {
+        const wm_plane pimg = clip.plane();
+        if (!weights.empty() && weights.size() != (size_t)pimg.frames) fail(WM_ERR_BAD_ARG, "poolClip: weights must hold one entry per frame");
+        std::vector<int> status((size_t)pimg.frames, 0);
+        const int rc = wm_clip_pool(ctx, (int)maskType, &pimg, weights.empty() ? nullptr : weights.data(), poolDev, accumulate ? 1 : 0, status.data(),
+                                    WM_SLOT_SYNC);
+        if (rc < 0) fail(rc, "poolClip");
+        return status;
+    }
+    // locate, locateKeys and locateBits of a pooled clip (wm.h wm_locate_pooled, wm_locate_keys_pooled, wm_locate_bits_pooled): one
+    // transform tail for the whole clip.  A pool without a solvable frame gives {0, 0, 0, NaN}
+    WmLocation locatePooled(const float* poolDev, const WatermarkKeys& keys, int k) const
+    {
+        float v[WM_LOCATE_NVALS] = {0.0f, 0.0f, 0.0f, 0.0f};
+        const int rc = wm_locate_pooled(ctx, poolDev, keys.handle(), k, v, nullptr, WM_SLOT_SYNC);
+        if (rc < 0) fail(rc, "locatePooled");
+        return WmLocation{(int)v[0], (int)v[1], v[2], v[3]};
+    }
+    std::vector<WmLocation> locateKeysPooled(const float* poolDev, const WatermarkKeys& keys, int k0, int nk) const
+    {
+        const size_t n = (size_t)(nk > 0 ? nk : 0);
+        std::vector<float> v(n * WM_LOCATE_KEYS_NVALS + 1, 0.0f);  // (never an empty buffer: nk < 1 is the library's to refuse)
+        const int rc = wm_locate_keys_pooled(ctx, poolDev, keys.handle(), k0, nk, v.data(), nullptr, WM_SLOT_SYNC);
+        if (rc < 0) fail(rc, "locateKeysPooled");
+        std::vector<WmLocation> out(n);
+        for (size_t i = 0; i < n; ++i) out[i] = WmLocation{(int)v[4 * i], (int)v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]};
+        return out;
+    }
+    WmLocation locateBitsPooled(const float* poolDev, const WatermarkKeys& keys, int k, int tileRows, int tileCols, const std::vector<int32_t>& tileBit,
+                                int nbits, std::vector<float>& soft) const
+    {
+        float v[WM_LOCATE_BITS_NVALS] = {0.0f, 0.0f, 0.0f, 0.0f};
+        soft.assign((size_t)(nbits > 0 ? nbits : 0), 0.0f);
+        int ty = 0, tx = 0;  // (a table shorter than the key plane's tile grid must not reach the library)
+        if (wm_tiles_shape(wm_keys_rows(keys.handle()), wm_keys_cols(keys.handle()), tileRows, tileCols, &ty, &tx) == WM_OK &&
+            tileBit.size() != (size_t)ty * (size_t)tx)
+            fail(WM_ERR_BAD_ARG, "locateBitsPooled: tileBit must hold one entry per tile of the key plane");
+        const int rc = wm_locate_bits_pooled(ctx, poolDev, keys.handle(), k, tileRows, tileCols, tileBit.data(), nbits, v, soft.data(), nullptr, nullptr,
+                                             WM_SLOT_SYNC);
+        if (rc < 0) fail(rc, "locateBitsPooled");
+        return WmLocation{(int)v[0], (int)v[1], v[2], v[3]};
+    }
     // where in the frame is the mark?  detectWatermark of one grey image against this engine's W with the correlation's three sums
     // kept per tile of tileRows x tileCols pixels (wm.h wm_detect_tiles; the last tile of each axis takes the remainder): score
     // [i * nx + j] is tile (i, j)'s, NaN for a tile without energy, 0 everywhere when the system is not solvable.  ny / nx, if

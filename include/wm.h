@@ -445,6 +445,57 @@ int wm_locate_keys_rank(const float* loc /* [nk][4] of one frame */, int nk, int
 #define WM_LOCATE_KEYS_BENCH_PASSES 2
 int wm_locate_keys_bench(int device, int pr, int pc, int ny, int nx, int iters, double* us_out /* [WM_LOCATE_KEYS_BENCH_PASSES] */);
 
+/* ---- A clip's frames pooled into one crop search ----------------------------------------------------------------------------------
+ * What is traced in practice is a clip: many frames, one crop rectangle, one key, one payload.  The map is linear in the image-side
+ * plane, map(o) = sum_q h(q) key[q + o], so the pooled map of a clip is the map of the pooled h:
+ *     sum_f w_f map_f = correlate(sum_f w_f h_f, key),
+ * and the same holds per payload bit and per key of a bank.  A clip of F frames costs F image-sized passes and ONE transform tail.  On
+ * small crops and weak marks, where no single frame reaches a decision, the pooled clip does.
+ * The pooled plane belongs to the CALLER: a dense DEVICE f32 [rows][cols] plane of the context's shape and on its device.  The slot
+ * keeps no state of a clip, so a clip longer than max_frames is pooled in several calls.
+ * wm_clip_pool takes wm_locate's image side (f32 / u8, any pitch and width, WM_MEM_HOST, batches up to max_frames, ME with p = 3 --
+ * WM_ERR_BAD_P otherwise --, NVF with p = 3..9) and refuses in its order, all before any device work: null ctx, mask, null img or
+ * pool_dev, band mode, slot, plane, record room (frames records, WM_ERR_BUSY), then a weight that is not finite (WM_ERR_BAD_ARG).
+ * It runs the Gram sweep and the solve as wm_locate does and then ONE kernel over the batch:
+ *     pool(q) = fmaf(w_f, h_f(q), pool(q))   for f ascending,
+ * from 0.0f when accumulate == 0 and from the plane's content otherwise; h_f is wm_locate's h of that frame bit for bit.  weights:
+ * HOST [frames], read before the call returns, NULL: all 1.  A frame whose status is not 0 (WM_UNSOLVABLE) is skipped: it makes no
+ * fmaf and changes nothing; status_out[frames] (may be NULL) is delivered by wm_sync.  The pool's bits depend only on the frames,
+ * their order and the weights: not on how the clip was cut into calls, on the batch size, on pitch or memory kind, or on repetition.
+ * pool_dev must not overlap the image or any plane a queued call still uses.
+ * An ENQUEUE on the slot with wm_locate's side-effect rules: never takes the fused kernels, leaves no hand-over, ends none, does not
+ * change what WM_MEM_SLOT_OUT names; its kernel is not in the wm_prof_* list.  No scratch beyond the frames' weights in the slot's
+ * table arena.
+ * wm_locate_pooled, wm_locate_bits_pooled and wm_locate_keys_pooled are the tails of wm_locate, wm_locate_bits and wm_locate_keys with
+ * ONE frame and pool_dev in the place of h: the same launches on the same scratch.  The context supplies the shape, the device and
+ * the slots; neither its p nor a mask matters to them.  Refusal order (without mask and plane), record room (4, 4 + nbits, 4 * nk
+ * records), records, scratch rules (a pooled call is a call of one frame), the zero-key rule and the bank HAZARD are those of the
+ * call each is the tail of; there is no status_out: a pool has no solve.  A pool that is all zero (no solvable frame) gives a zero
+ * map and {0, 0, 0, NaN}.  For a clip of ONE frame with weights NULL and accumulate == 0 the pooled calls' maps and numbers equal the
+ * per-frame calls' as floats (a -0 of h becomes +0).  A pooled clip of 8 frames at PSNR 52 on a 64 x 256 crop reaches z of 20-23
+ * where its frames reach 5-10, and an unmarked clip stays below 5. */
+int wm_clip_pool(wm_ctx* ctx, int mask, const wm_plane* img,
+                 const float* weights /* HOST [frames], NULL: all 1; read before return */,
+                 float* pool_dev /* DEVICE [rows][cols] f32 */, int accumulate,
+                 int* status_out /* [frames], may be NULL */, int slot);
+int wm_locate_pooled(wm_ctx* ctx, const float* pool_dev, const wm_keys* keys, int k,
+                     float* loc_out /* HOST [4], by wm_sync */, float* map_dev /* DEVICE [ny][nx] f32, may be NULL */, int slot);
+int wm_locate_bits_pooled(wm_ctx* ctx, const float* pool_dev, const wm_keys* keys, int k,
+                          int tile_rows, int tile_cols, const int32_t* tile_bit /* HOST [ty*tx] over the KEY plane */, int nbits,
+                          float* loc_out /* HOST [4], by wm_sync */, float* soft_out /* HOST [nbits], by wm_sync */,
+                          float* energy_dev /* DEVICE [ny][nx] f32, may be NULL */,
+                          float* maps_dev /* DEVICE [nbits][ny][nx] f32, may be NULL */, int slot);
+int wm_locate_keys_pooled(wm_ctx* ctx, const float* pool_dev, const wm_keys* keys, int k0, int nk,
+                          float* loc_out /* HOST [nk][4], by wm_sync */, float* maps_dev /* DEVICE [nk][ny][nx] f32, may be NULL */,
+                          int slot);
+/* Yardstick (tools/locate_clip_bench.py), timed as wm_fft_bench is: the pool kernel of wm_clip_pool over `frames` dense f32 frames of
+ * rows x cols made up on the spot (mask and p as for wm_clip_pool), by its two routes -- us_out[0]: x and e tiles in LDS, the route
+ * wm_clip_pool takes; us_out[1]: a direct gather of the 5 x 5 window from cache, one pixel per lane, taken by no call.  equal_out: 1
+ * when the two pools have equal bits.  frames 1 .. 1024; anything else WM_ERR_BAD_ARG. */
+#define WM_CLIP_POOL_BENCH_ROUTES 2
+int wm_clip_pool_bench(int device, int rows, int cols, int frames, int mask, int p, int iters,
+                       double* us_out /* [WM_CLIP_POOL_BENCH_ROUTES] */, int* equal_out);
+
 /* ---- Tile map: where in the frame is the mark? -------------------------------------------------------------------------------
  * wm_detect answers with one correlation for the whole plane.  A copy with a logo pasted over it, a picture-in-picture or a
  * spliced region only lets that score sag.  The detector is local, though: after the one solve per frame, e_w, u = m W and e_u

@@ -93,6 +93,12 @@ ABI = [
     ("wm_locate_keys", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), C.c_void_p, C.c_int, C.c_int, _P(C.c_float), C.c_void_p, _P(C.c_int), C.c_int]),
     ("wm_locate_keys_rank", C.c_int, [_P(C.c_float), C.c_int, _P(C.c_int), _P(C.c_float), _P(C.c_float)]),
     ("wm_locate_keys_bench", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_double)]),
+    ("wm_clip_pool", C.c_int, [_ctx_p, C.c_int, _P(wm_plane), _P(C.c_float), C.c_void_p, C.c_int, _P(C.c_int), C.c_int]),
+    ("wm_locate_pooled", C.c_int, [_ctx_p, C.c_void_p, C.c_void_p, C.c_int, _P(C.c_float), C.c_void_p, C.c_int]),
+    ("wm_locate_bits_pooled", C.c_int, [_ctx_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, _P(C.c_float), _P(C.c_float),
+                                        C.c_void_p, C.c_void_p, C.c_int]),
+    ("wm_locate_keys_pooled", C.c_int, [_ctx_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, _P(C.c_float), C.c_void_p, C.c_int]),
+    ("wm_clip_pool_bench", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_double), _P(C.c_int)]),
     ("wm_fft2", C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     ("wm_fft_bench", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_double)]),
     ("wm_tiles_shape", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_int), _P(C.c_int)]),
@@ -339,6 +345,16 @@ WM_LOCATE_KEYS_NVALS = 4
 LOCATE_KEYS_BENCH_PASSES = ("keys_pair", "keys_peak")
 
 
+def clip_pool_bench(rows, cols, frames, mask=0, p=3, iters=20, device=0):
+    """wm.h wm_clip_pool_bench: ({"lds_tile": us, "gather": us} per launch of the pool kernel's two routes, whether their pools have
+    equal bits)"""
+    us, eq = (C.c_double * 2)(), C.c_int()
+    rc = lib().wm_clip_pool_bench(device, rows, cols, frames, int(mask), p, iters, us, C.byref(eq))
+    if rc != WM_OK:
+        _raise(rc)
+    return {"lds_tile": us[0], "gather": us[1]}, bool(eq.value)
+
+
 def locate_keys_rank(loc):
     """wm.h wm_locate_keys_rank on one frame's records [nk, 4] of Watermark.locateKeys: (best, z_best, z_next) -- the index of the key
     with the largest z (NaN is ignored, ties: the smallest index; -1 when every z is NaN), that z, and the largest z among the others
@@ -525,6 +541,7 @@ class Watermark:
         if rc != WM_OK:
             self._ctx = _ctx_p()
             _raise(rc)
+        self._max_frames = 1  # (wm_create's; configure keeps it current: what locateClip cuts a clip by)
         if (nslots, max_frames) != (2, 1):
             self.configure(nslots, max_frames)
 
@@ -543,6 +560,7 @@ class Watermark:
         if rc != WM_OK:
             self._ctx = _ctx_p()
             _raise(rc)
+        self._max_frames = 1  # (wm_create's; configure keeps it current: what locateClip cuts a clip by)
         if (nslots, max_frames) != (2, 1):
             self.configure(nslots, max_frames)
         return self
@@ -574,6 +592,7 @@ class Watermark:
         rc = lib().wm_clone(self._ctx, C.byref(other._ctx))
         if rc != WM_OK:
             _raise(rc, self._ctx)
+        other._max_frames = self._max_frames  # (wm_clone carries the configuration over)
         return other
 
     def reinitialize(self, randomMatrixPath, rows, cols):
@@ -592,6 +611,7 @@ class Watermark:
         rc = lib().wm_configure(self._ctx, nslots, max_frames)
         if rc != WM_OK:
             _raise(rc, self._ctx)
+        self._max_frames = max_frames
 
     def set_fused(self, on):
         """one-frame synchronous calls as ONE launch with LDS-resident tiles (wm.h wm_set_fused); on by default"""
@@ -757,6 +777,73 @@ class Watermark:
         if want_maps:
             out.append(maps_t[0] if one else maps_t)
         return tuple(out)
+
+    # -- a clip's frames pooled into one crop search (wm.h wm_clip_pool, wm_locate_*_pooled) --
+    def poolClip(self, frames, maskType=MASK_TYPE.ME, weights=None, pool=None, accumulate=False):
+        """the frames of a clip pooled on the image side (wm.h wm_clip_pool): pool = fmaf(w_f, h_f, pool) over the solvable frames in
+        ascending order, from zero unless `accumulate`.  frames: [F, rows, cols] (or one [rows, cols] frame), F <= max_frames;
+        weights: F floats or None (all 1); pool: a contiguous float32 GPU tensor [rows, cols] or None (a new one).  Returns
+        (pool, status) with status an int32 numpy array [F]: an unsolvable frame is skipped and named there"""
+        import torch
+        pimg = plane_of(frames, 1)
+        if pool is None:
+            if accumulate:
+                raise RuntimeError("poolClip: accumulate needs a pool")
+            pool = torch.empty((self.rows, self.cols), dtype=torch.float32, device=frames.device)
+        st = np.zeros(pimg.frames, np.int32)
+        torch.cuda.current_stream().synchronize()
+        self.pool_clip_async(frames, maskType, WM_SLOT_SYNC, pool, weights, accumulate, st)
+        return pool, st
+
+    def locatePooled(self, pool, keys, k, want_map=False):
+        """locate() of a pooled clip (wm.h wm_locate_pooled): a float32 numpy array [4] = (oy, ox, peak, z); want_map=True: (loc, map)
+        with map a float32 GPU tensor [ny, nx]"""
+        import torch
+        ny, nx, _, _ = locate_shape(self.rows, self.cols, keys.rows, keys.cols)
+        loc = np.zeros(WM_LOCATE_NVALS, np.float32)
+        map_t = torch.empty((ny, nx), dtype=torch.float32, device=pool.device) if want_map else None
+        torch.cuda.current_stream().synchronize()
+        self.locate_pooled_async(pool, keys, k, WM_SLOT_SYNC, loc, map_t)
+        return (loc, map_t) if want_map else loc
+
+    def locateBitsPooled(self, pool, keys, k, tile_rows, tile_cols, tile_bit, nbits, want_energy=False, want_maps=False):
+        """locate_bits() of a pooled clip (wm.h wm_locate_bits_pooled): (loc [4], soft [nbits][, energy [ny, nx]][, maps [nbits, ny, nx]])"""
+        import torch
+        ny, nx, _, _ = locate_shape(self.rows, self.cols, keys.rows, keys.cols)
+        loc = np.zeros(WM_LOCATE_BITS_NVALS, np.float32)
+        soft = np.zeros(max(nbits, 0), np.float32)
+        en_t = torch.empty((ny, nx), dtype=torch.float32, device=pool.device) if want_energy else None
+        maps_t = torch.empty((max(nbits, 0), ny, nx), dtype=torch.float32, device=pool.device) if want_maps else None
+        torch.cuda.current_stream().synchronize()
+        self.locate_bits_pooled_async(pool, keys, k, tile_rows, tile_cols, tile_bit, nbits, WM_SLOT_SYNC, loc, soft, en_t, maps_t)
+        return (loc, soft) + ((en_t,) if want_energy else ()) + ((maps_t,) if want_maps else ())
+
+    def locateKeysPooled(self, pool, keys, k0, nk, want_maps=False):
+        """locateKeys() of a pooled clip (wm.h wm_locate_keys_pooled): a float32 numpy array [nk, 4]; want_maps=True: (loc, maps) with
+        maps a float32 GPU tensor [nk, ny, nx].  locate_keys_rank names the owner"""
+        import torch
+        ny, nx, _, _ = locate_shape(self.rows, self.cols, keys.rows, keys.cols)
+        loc = np.zeros((max(nk, 0), WM_LOCATE_KEYS_NVALS), np.float32)
+        maps_t = torch.empty((max(nk, 0), ny, nx), dtype=torch.float32, device=pool.device) if want_maps else None
+        torch.cuda.current_stream().synchronize()
+        self.locate_keys_pooled_async(pool, keys, k0, nk, WM_SLOT_SYNC, loc, maps_t)
+        return (loc, maps_t) if want_maps else loc
+
+    def locateClip(self, frames, keys, k, maskType=MASK_TYPE.ME, weights=None, want_map=False):
+        """where does a cropped CLIP lie in key `k`?  frames [F, rows, cols] of any F: pooled in chunks of max_frames (poolClip), then one locatePooled.  Returns (loc [4], status [F]) or, with
+        want_map=True, (loc, status, map)"""
+        F, chunk = frames.shape[0], self._max_frames
+        w = None if weights is None else np.ascontiguousarray(weights, np.float32).reshape(-1)
+        if w is not None and w.size != F:
+            raise RuntimeError(f"weights must hold {F} entries, got {w.size}")
+        pool, status = None, []
+        for f0 in range(0, F, chunk):
+            f1 = min(F, f0 + chunk)
+            pool, st = self.poolClip(frames[f0:f1], maskType, None if w is None else w[f0:f1], pool, accumulate=f0 > 0)
+            status.append(st)
+        out = self.locatePooled(pool, keys, k, want_map)
+        status = np.concatenate(status)
+        return (out[0], status, out[1]) if want_map else (out, status)
 
     @staticmethod
     def tiles_shape(rows, cols, tile_rows, tile_cols):
@@ -1182,6 +1269,58 @@ class Watermark:
         self._chk(lib().wm_locate_bits(self._ctx, int(maskType), C.byref(pimg), _keys_handle(keys), k, tile_rows, tile_cols,
                                        tb.ctypes.data_as(C.c_void_p) if tb is not None else None, nbits, loc_out, soft_out, ptrs[0], ptrs[1],
                                        status_out, slot))
+
+    @staticmethod
+    def _f32_gpu(t, what, n=None):
+        """a contiguous float32 GPU tensor (of n elements) as a pointer; None passes through"""
+        import torch
+        if t is None:
+            return None
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and (n is None or t.numel() == n)):
+            raise RuntimeError(f"{what} must be a contiguous float32 GPU tensor" + (f" of {n} elements" if n is not None else ""))
+        return C.c_void_p(t.data_ptr())
+
+    def pool_clip_async(self, frames, maskType, slot, pool_t, weights=None, accumulate=False, status_out=None):
+        """wm_clip_pool enqueued on `slot`: pool_t (a contiguous float32 GPU tensor of rows * cols elements) is written on the slot's
+        stream; weights (frames floats, may be None) is read before the call returns; status_out (frames ints, may be None) is
+        written by sync(slot)"""
+        pimg = self._as_plane(frames, 1)
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+            if w.size != pimg.frames:
+                raise RuntimeError(f"weights must hold {pimg.frames} entries, got {w.size}")
+        _, status_out = self._scalars_out(None, status_out)
+        self._chk(lib().wm_clip_pool(self._ctx, int(maskType), C.byref(pimg), w.ctypes.data_as(_P(C.c_float)) if w is not None else None,
+                                     self._f32_gpu(pool_t, "pool_t", self.rows * self.cols), 1 if accumulate else 0, status_out, slot))
+
+    def locate_pooled_async(self, pool_t, keys, k, slot, loc_out, map_t=None):
+        """wm_locate_pooled enqueued on `slot`: loc_out (4 floats, may be None when map_t is given) is written by sync(slot), map_t
+        (ny * nx, may be None) on the slot's stream.  `keys` and pool_t must stay alive and unmodified until then"""
+        loc_out, _ = self._scalars_out(loc_out, None)
+        self._chk(lib().wm_locate_pooled(self._ctx, self._f32_gpu(pool_t, "pool_t", self.rows * self.cols), _keys_handle(keys), k, loc_out,
+                                         self._f32_gpu(map_t, "map_t"), slot))
+
+    def locate_bits_pooled_async(self, pool_t, keys, k, tile_rows, tile_cols, tile_bit, nbits, slot, loc_out, soft_out, energy_t=None, maps_t=None):
+        """wm_locate_bits_pooled enqueued on `slot`: tile_bit is read before the call returns; loc_out (4 floats) and soft_out (nbits
+        floats) are written by sync(slot), energy_t (ny * nx) and maps_t (nbits * ny * nx), which may be None, on the slot's stream"""
+        tb = np.ascontiguousarray(tile_bit, np.int32).reshape(-1) if tile_bit is not None else None
+        if tb is not None and keys is not None:
+            tny, tnx = C.c_int(), C.c_int()
+            if lib().wm_tiles_shape(keys.rows, keys.cols, tile_rows, tile_cols, C.byref(tny), C.byref(tnx)) == WM_OK and tb.size != tny.value * tnx.value:
+                raise RuntimeError(f"tile_bit must hold {tny.value * tnx.value} entries, got {tb.size}")
+        loc_out, _ = self._scalars_out(loc_out, None)
+        soft_out, _ = self._scalars_out(soft_out, None)
+        self._chk(lib().wm_locate_bits_pooled(self._ctx, self._f32_gpu(pool_t, "pool_t", self.rows * self.cols), _keys_handle(keys), k, tile_rows,
+                                              tile_cols, tb.ctypes.data_as(C.c_void_p) if tb is not None else None, nbits, loc_out, soft_out,
+                                              self._f32_gpu(energy_t, "energy_t"), self._f32_gpu(maps_t, "maps_t"), slot))
+
+    def locate_keys_pooled_async(self, pool_t, keys, k0, nk, slot, loc_out, maps_t=None):
+        """wm_locate_keys_pooled enqueued on `slot`: loc_out (nk * 4 floats, may be None when maps_t is given) is written by
+        sync(slot), maps_t (nk * ny * nx, may be None) on the slot's stream"""
+        loc_out, _ = self._scalars_out(loc_out, None)
+        self._chk(lib().wm_locate_keys_pooled(self._ctx, self._f32_gpu(pool_t, "pool_t", self.rows * self.cols), _keys_handle(keys), k0, nk, loc_out,
+                                              self._f32_gpu(maps_t, "maps_t"), slot))
 
     def detect_tiles_async(self, image, tile_rows, tile_cols, maskType, slot, map_t, sums_t=None, status=None):
         """wm_detect_tiles enqueued on `slot`: map_t (a contiguous float32 GPU tensor of frames * ny * nx elements) and sums_t

@@ -1899,6 +1899,58 @@ void fft2_inverse_t(hipStream_t st, float* t, float* a, int pr, int pc, const fl
 }
 }  // namespace
 
+namespace {
+// the slot's wm_locate scratch for a transform shape, its tables filled: a new shape moves the layout under the calls still queued on
+// the slot, so it waits for them
+int loc_scratch(wm_ctx* ctx, Slot& s, int pr, int pc, int ny, int nx, LocScratch* L)
+{
+    int rc;
+    const size_t need = loc_layout(nullptr, ctx->rows, ctx->cols, pr, pc, ny, nx).bytes;
+    const bool reshape = s.loc_pr != pr || s.loc_pc != pc || s.loc_scr_bytes < need;
+    if (reshape) {
+        HIPCHK(ctx, hipStreamSynchronize(s.stream));
+        s.loc_pr = s.loc_pc = 0;
+        if ((rc = ensure(ctx, &s.loc_scr, &s.loc_scr_bytes, need, WM_ERR_ALLOC)) != WM_OK) return rc;
+    }
+    *L = loc_layout(s.loc_scr, ctx->rows, ctx->cols, pr, pc, ny, nx);
+    if (reshape) {
+        std::vector<float> tw((size_t)2 * std::max(pr, pc));
+        fft_twiddles(pr, tw.data());
+        HIPCHK(ctx, hipMemcpy(L->tw_r, tw.data(), (size_t)pr * 2 * sizeof(float), hipMemcpyHostToDevice));
+        fft_twiddles(pc, tw.data());
+        HIPCHK(ctx, hipMemcpy(L->tw_c, tw.data(), (size_t)pc * 2 * sizeof(float), hipMemcpyHostToDevice));
+        s.loc_pr = pr; s.loc_pc = pc;
+    }
+    return WM_OK;
+}
+// the key's spectrum, once per call (transposed, in L.w)
+void locate_key_spectrum(Slot& s, const LocScratch& L, const wm_keys* keys, int k, int pr, int pc)
+{
+    launch_locate_key(s.stream, keys->d + (size_t)k * keys->rows * keys->cols, keys->rows, keys->cols, L.b, pr, pc);
+    fft2_forward_t(s.stream, L.b, L.w, pr, pc, L.tw_r, L.tw_c);
+}
+// wm_locate's tail of one image-side plane h laid into L.a: its spectrum, conj(H) Wf, back, the map and its four numbers
+void locate_tail(Slot& s, const LocScratch& L, int pr, int pc, int ny, int nx, const int* status, float* map, OpResult* res)
+{
+    fft2_forward_t(s.stream, L.a, L.b, pr, pc, L.tw_r, L.tw_c);
+    launch_locate_mul(s.stream, L.b, L.w, (size_t)pr * pc);
+    fft2_inverse_t(s.stream, L.b, L.a, pr, pc, L.tw_r, L.tw_c);
+    launch_locate_peak(s.stream, L.a, pr, pc, ny, nx, status, map, L.part, res);
+}
+// a DEVICE int that holds 0 for the call's kernels: the status of a pooled plane, which has no solve of its own (the slot's
+// table arena, as the tile tables).  A call takes table room ONCE: a second request may move the arenas under the first pointer
+int zero_status(wm_ctx* ctx, Slot& s, const int** status)
+{
+    void *th = nullptr, *td = nullptr;
+    int rc = table_room(ctx, s, sizeof(int), &th, &td);
+    if (rc != WM_OK) return rc;
+    *(int*)th = 0;
+    if ((rc = table_upload(ctx, s, th, td, sizeof(int))) != WM_OK) return rc;
+    *status = (const int*)td;
+    return WM_OK;
+}
+}  // namespace
+
 int wm_locate(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* keys, int k, float* loc_out, float* map_dev, int* status_out, int slot)
 {
     if (!ctx) return WM_ERR_BAD_ARG;
@@ -1917,39 +1969,127 @@ int wm_locate(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* keys, i
     Sweep sw;
     if ((rc = open_input(ctx, s, img, "image", mask, WM_LOCATE_NVALS, "4 location records", &sw)) != WM_OK) return rc;
     const int frames = img->frames;
-    // scratch and tables: a new transform shape moves the layout under the calls still queued on the slot, so it waits for them
-    const size_t need = loc_layout(nullptr, ctx->rows, ctx->cols, pr, pc, ny, nx).bytes;
-    const bool reshape = s.loc_pr != pr || s.loc_pc != pc || s.loc_scr_bytes < need;
-    if (reshape) {
-        HIPCHK(ctx, hipStreamSynchronize(s.stream));
-        s.loc_pr = s.loc_pc = 0;
-        if ((rc = ensure(ctx, &s.loc_scr, &s.loc_scr_bytes, need, WM_ERR_ALLOC)) != WM_OK) return rc;
-    }
-    const LocScratch L = loc_layout(s.loc_scr, ctx->rows, ctx->cols, pr, pc, ny, nx);
-    if (reshape) {
-        std::vector<float> tw((size_t)2 * std::max(pr, pc));
-        fft_twiddles(pr, tw.data());
-        HIPCHK(ctx, hipMemcpy(L.tw_r, tw.data(), (size_t)pr * 2 * sizeof(float), hipMemcpyHostToDevice));
-        fft_twiddles(pc, tw.data());
-        HIPCHK(ctx, hipMemcpy(L.tw_c, tw.data(), (size_t)pc * 2 * sizeof(float), hipMemcpyHostToDevice));
-        s.loc_pr = pr; s.loc_pc = pc;
-    }
+    LocScratch L;
+    if ((rc = loc_scratch(ctx, s, pr, pc, ny, nx, &L)) != WM_OK) return rc;
     // the image side is wm_detect_keys': the Gram sweep and the solve
     if ((rc = gram_sweep(ctx, s, sw, img)) != WM_OK) return rc;
-    // the key's spectrum, once per call (transposed, in L.w)
-    launch_locate_key(s.stream, keys->d + (size_t)k * keys->rows * keys->cols, keys->rows, keys->cols, L.b, pr, pc);
-    fft2_forward_t(s.stream, L.b, L.w, pr, pc, L.tw_r, L.tw_c);
-    // the frames one after the other: e (and m), h, its spectrum, conj(H) Wf, back, the map and its four numbers
+    locate_key_spectrum(s, L, keys, k, pr, pc);
+    // the frames one after the other: e (and m), h, then the tail
     for (int f = 0; f < frames; ++f) {
         launch_locate_e(sw, f, L.e, L.m);
         launch_locate_h(sw, f, L.e, L.m, L.a, pr, pc);
-        fft2_forward_t(s.stream, L.a, L.b, pr, pc, L.tw_r, L.tw_c);
-        launch_locate_mul(s.stream, L.b, L.w, (size_t)pr * pc);
-        fft2_inverse_t(s.stream, L.b, L.a, pr, pc, L.tw_r, L.tw_c);
-        launch_locate_peak(s.stream, L.a, pr, pc, ny, nx, s.d_status + f, map_dev ? map_dev + (size_t)f * ny * nx : nullptr, L.part,
-                           s.d_res + s.res_used + WM_LOCATE_NVALS * f);
+        locate_tail(s, L, pr, pc, ny, nx, s.d_status + f, map_dev ? map_dev + (size_t)f * ny * nx : nullptr, s.d_res + s.res_used + WM_LOCATE_NVALS * f);
     }
     return finish_call(ctx, s, slot, frames, WM_LOCATE_NVALS, false, loc_out, status_out);
+}
+
+// wm_locate's tail on a caller's pooled image-side plane (wm_clip_pool) in the place of one frame's h
+int wm_locate_pooled(wm_ctx* ctx, const float* pool_dev, const wm_keys* keys, int k, float* loc_out, float* map_dev, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    int rc;
+    if (!pool_dev || !keys || (!loc_out && !map_dev))
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_locate_pooled: null pool_dev or keys, or loc_out and map_dev both null");
+    if (k < 0 || k >= keys->nkeys)
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_locate_pooled: key " + std::to_string(k) + " of a bank of " + std::to_string(keys->nkeys));
+    if ((rc = check_bank(ctx, keys, "wm_locate_pooled", false)) != WM_OK) return rc;
+    int ny, nx, pr, pc;
+    if (wm_locate_shape(ctx->rows, ctx->cols, keys->rows, keys->cols, &ny, &nx, &pr, &pc) != WM_OK)
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_locate_pooled: a " + std::to_string(keys->rows) + "x" + std::to_string(keys->cols) +
+                                             " key plane needs a transform above " + std::to_string(1 << FFT_LOG_MAX) + " per axis");
+    if ((rc = refuse_band(ctx, "wm_locate_pooled")) != WM_OK) return rc;
+    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
+    if ((rc = check_res_room(ctx, s, WM_LOCATE_NVALS, "4 location records")) != WM_OK) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    LocScratch L;
+    if ((rc = loc_scratch(ctx, s, pr, pc, ny, nx, &L)) != WM_OK) return rc;
+    const int* status = nullptr;
+    if ((rc = zero_status(ctx, s, &status)) != WM_OK) return rc;
+    locate_key_spectrum(s, L, keys, k, pr, pc);
+    launch_locate_key(s.stream, pool_dev, ctx->rows, ctx->cols, L.a, pr, pc);  // (the pool in the place of h: a dense real plane)
+    locate_tail(s, L, pr, pc, ny, nx, status, map_dev, s.d_res + s.res_used);
+    return finish_call(ctx, s, slot, 1, WM_LOCATE_NVALS, false, loc_out, nullptr);
+}
+
+// the frames of a clip pooled on the image side: wm_locate's Gram sweep and solve, then ONE launch of k_clip_pool
+int wm_clip_pool(wm_ctx* ctx, int mask, const wm_plane* img, const float* weights, float* pool_dev, int accumulate, int* status_out, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    int rc = check_mask(ctx, mask);
+    if (rc != WM_OK) return rc;
+    if (!img || !pool_dev) return fail(ctx, WM_ERR_BAD_ARG, "wm_clip_pool: null img or pool_dev");
+    if ((rc = refuse_band(ctx, "wm_clip_pool")) != WM_OK) return rc;
+    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
+    // (open_input checks the plane and the record room again: the frame count has to be known HERE, in front of the weights' check)
+    if ((rc = check_plane(ctx, img, 0, false, "image", true)) != WM_OK) return rc;
+    const int frames = img->frames;
+    if ((rc = check_res_room(ctx, s, frames)) != WM_OK) return rc;
+    for (int f = 0; weights && f < frames; ++f)
+        if (!std::isfinite(weights[f])) return fail(ctx, WM_ERR_BAD_ARG, "wm_clip_pool: weights[" + std::to_string(f) + "] is not finite");
+    Sweep sw;
+    if ((rc = open_input(ctx, s, img, "image", mask, 1, nullptr, &sw)) != WM_OK) return rc;
+    // the call's own copy of the weights (the caller's array is free when this function returns)
+    void *th = nullptr, *td = nullptr;
+    if ((rc = table_room(ctx, s, (size_t)frames * sizeof(float), &th, &td)) != WM_OK) return rc;
+    for (int f = 0; f < frames; ++f) ((float*)th)[f] = weights ? weights[f] : 1.0f;
+    if ((rc = table_upload(ctx, s, th, td, (size_t)frames * sizeof(float))) != WM_OK) return rc;
+    if ((rc = gram_sweep(ctx, s, sw, img)) != WM_OK) return rc;
+    launch_clip_pool(sw, (const float*)td, pool_dev, accumulate != 0, s.d_res + s.res_used);
+    return finish_call(ctx, s, slot, frames, 1, false, nullptr, status_out);
+}
+
+// k_clip_pool (x and e tiles in LDS) and k_clip_pool_gather (a direct gather from cache), each launched `iters` times back to back
+// between two events on the null stream over `frames` dense f32 frames of rows x cols: mean microseconds per launch, and whether the
+// two pools have equal bits (tools/locate_clip_bench.py holds them against wm_membench's copy)
+int wm_clip_pool_bench(int device, int rows, int cols, int frames, int mask, int p, int iters, double* us_out, int* equal_out)
+{
+    if (!us_out || !equal_out || iters < 1 || rows < 1 || cols < 1 || rows > 32768 || cols > 32768 || frames < 1 || frames > 1024 ||
+        (mask != WM_MASK_ME && mask != WM_MASK_NVF) || p < 3 || p > 9 || p % 2 == 0 || (mask == WM_MASK_ME && p != 3))
+        return WM_ERR_BAD_ARG;
+    int rc = choose_device(&device);
+    if (rc != WM_OK) return rc;
+    const size_t n = (size_t)rows * cols, img = round256(n * sizeof(float)), small = round256((size_t)frames * 8 * sizeof(float));
+    const size_t total = (size_t)frames * img + 2 * img + 4 * small;
+    char* scr = nullptr;
+    if (hipMalloc((void**)&scr, total) != hipSuccess) { (void)hipGetLastError(); return WM_ERR_ALLOC; }
+    float* pool[2] = {(float*)(scr + (size_t)frames * img), (float*)(scr + (size_t)frames * img + img)};
+    char* tail = scr + (size_t)frames * img + 2 * img;
+    float* coef = (float*)tail; int* status = (int*)(tail + small); float* weights = (float*)(tail + 2 * small); OpResult* res = (OpResult*)(tail + 3 * small);
+    // frames that differ: a hash of the index in 0 .. 255, as 8-bit pixels; coefficients 1/8 (a plain mean of the neighbours)
+    std::vector<float> hx((size_t)frames * (img / sizeof(float)), 0.0f), hc((size_t)frames * 8, 0.125f), hw((size_t)frames, 1.0f);
+    for (size_t i = 0; i < hx.size(); ++i) hx[i] = (float)(((i * 2654435761ull) >> 13) & 255);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    bool ok = hipMemset(scr, 0, total) == hipSuccess && hipMemcpy(scr, hx.data(), hx.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(coef, hc.data(), hc.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(weights, hw.data(), hw.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
+              hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
+    Sweep sw{};
+    sw.s = nullptr; sw.lg.rows = rows; sw.lg.cols = cols; sw.frames = frames; sw.mask = mask; sw.pad = p / 2;
+    sw.x = PlaneDesc{scr, cols, (long long)(img / sizeof(float)), 0, WM_F32, 1, 0};
+    sw.coef = coef; sw.status = status;
+    for (int route = 0; ok && route < WM_CLIP_POOL_BENCH_ROUTES; ++route) {
+        for (int i = -1; i < iters; ++i) {  // (one untimed launch in front)
+            if (i == 0) ok = ok && hipEventRecord(e0, nullptr) == hipSuccess;
+            if (route == 0) launch_clip_pool(sw, weights, pool[0], false, res);
+            else launch_clip_pool_gather(sw, weights, pool[1], false, res);
+        }
+        float ms = 0.f;
+        ok = ok && hipEventRecord(e1, nullptr) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess &&
+             hipGetLastError() == hipSuccess;
+        us_out[route] = (double)ms * 1e3 / iters;
+    }
+    if (ok) {
+        std::vector<float> a(n), b(n);
+        ok = hipMemcpy(a.data(), pool[0], n * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess &&
+             hipMemcpy(b.data(), pool[1], n * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess;
+        *equal_out = ok && std::memcmp(a.data(), b.data(), n * sizeof(float)) == 0 ? 1 : 0;
+    }
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    (void)hipFree(scr);
+    return ok ? WM_OK : WM_ERR_RUNTIME;
 }
 
 int wm_fft2(int device, float* data_dev, int pr, int pc, int inverse)
@@ -2312,6 +2452,120 @@ int wm_locate_bits_cover(int rows, int cols, int key_rows, int key_cols, int til
     return WM_OK;
 }
 
+namespace {
+// what wm_locate_bits and wm_locate_bits_pooled share in front of their image side: the geometry, the refusals from the key on
+// (`plane`: the image plane of wm_locate_bits, null for the pooled call, which has one frame and no plane to check)
+struct LocBitsCall { int ny, nx, pr, pc, frames; TileShape ts; long long per_frame; };
+int locate_bits_front(wm_ctx* ctx, const std::string& who, const wm_plane* plane, const wm_keys* keys, int k, int tile_rows, int tile_cols,
+                      const int32_t* tile_bit, int nbits, int slot, LocBitsCall* c)
+{
+    int rc;
+    if (k < 0 || k >= keys->nkeys) return fail(ctx, WM_ERR_BAD_ARG, who + ": key " + std::to_string(k) + " of a bank of " + std::to_string(keys->nkeys));
+    if ((rc = check_bank(ctx, keys, who.c_str(), false)) != WM_OK) return rc;
+    if (wm_locate_shape(ctx->rows, ctx->cols, keys->rows, keys->cols, &c->ny, &c->nx, &c->pr, &c->pc) != WM_OK)
+        return fail(ctx, WM_ERR_BAD_ARG, who + ": a " + std::to_string(keys->rows) + "x" + std::to_string(keys->cols) +
+                                             " key plane needs a transform above " + std::to_string(1 << FFT_LOG_MAX) + " per axis");
+    if ((rc = refuse_band(ctx, who.c_str())) != WM_OK) return rc;
+    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
+    // (open_input checks the plane and the record room again: both have to be known HERE, in front of the table's checks and of any device work)
+    if (plane && (rc = check_plane(ctx, plane, 0, false, "image", true)) != WM_OK) return rc;
+    c->frames = plane ? plane->frames : 1;
+    c->per_frame = WM_LOCATE_BITS_NVALS + (long long)std::max(nbits, 0);
+    if ((rc = check_res_room(ctx, s, c->frames * c->per_frame, "(4 + bits)")) != WM_OK) return rc;
+    c->ts.th = tile_rows; c->ts.tw = tile_cols;
+    if (wm_tiles_shape(keys->rows, keys->cols, tile_rows, tile_cols, &c->ts.ny, &c->ts.nx) != WM_OK)
+        return fail(ctx, WM_ERR_BAD_ARG, who + ": tile shape " + std::to_string(tile_rows) + "x" + std::to_string(tile_cols) +
+                                             " (rows: a multiple of 8, >= 32; columns: a multiple of 4, >= 32)");
+    return tile_bits_checked(ctx, who.c_str(), tile_bit, (long long)c->ts.ny * c->ts.nx, nbits);
+}
+
+// the slot's wm_locate_bits scratch for the call's shapes, its tables filled: another layout moves the planes under the calls still
+// queued on the slot, so it waits for them
+int locb_scratch(wm_ctx* ctx, Slot& s, const LocBitsCall& c, int nbits, bool own_energy, bool own_maps, LocBitsScratch* L)
+{
+    int rc;
+    const int pr = c.pr, pc = c.pc;
+    const long long key_now[6] = {((long long)pr << 32) | pc, ((long long)c.ny << 32) | c.nx, c.frames, nbits, own_energy ? 1 : 0, own_maps ? 1 : 0};
+    const size_t need = locb_layout(nullptr, ctx->rows, ctx->cols, pr, pc, c.ny, c.nx, c.frames, nbits, own_energy, own_maps).bytes;
+    const bool reshape = !std::equal(key_now, key_now + 6, s.locb_key) || s.locb_scr_bytes < need;
+    if (reshape) {
+        HIPCHK(ctx, hipStreamSynchronize(s.stream));
+        std::fill(s.locb_key, s.locb_key + 6, 0LL);
+        if ((rc = ensure(ctx, &s.locb_scr, &s.locb_scr_bytes, need, WM_ERR_ALLOC)) != WM_OK) return rc;
+    }
+    *L = locb_layout(s.locb_scr, ctx->rows, ctx->cols, pr, pc, c.ny, c.nx, c.frames, nbits, own_energy, own_maps);
+    if (reshape) {
+        std::vector<float> tw((size_t)2 * std::max(pr, pc));
+        fft_twiddles(pr, tw.data());
+        HIPCHK(ctx, hipMemcpy(L->tw_r, tw.data(), (size_t)pr * 2 * sizeof(float), hipMemcpyHostToDevice));
+        fft_twiddles(pc, tw.data());
+        HIPCHK(ctx, hipMemcpy(L->tw_c, tw.data(), (size_t)pc * 2 * sizeof(float), hipMemcpyHostToDevice));
+        std::copy(key_now, key_now + 6, s.locb_key);
+    }
+    return WM_OK;
+}
+
+// the call's own copy of the table (the caller's array is free when the call returns), and which bits have a tile at all.
+// zero_dev (may be null): a DEVICE int that holds 0 behind the table, zero_status' word -- taken in the SAME request as the table: a
+// second table_room may move the arenas and free the block the first pointer lies in
+int locate_bits_table(wm_ctx* ctx, Slot& s, const int32_t* tile_bit, int T, int nbits, const int** table_dev, std::vector<char>* has,
+                      const int** zero_dev = nullptr)
+{
+    int rc;
+    void *th = nullptr, *td = nullptr;
+    const size_t bytes = ((size_t)T + (zero_dev ? 1 : 0)) * sizeof(int);
+    if ((rc = table_room(ctx, s, bytes, &th, &td)) != WM_OK) return rc;
+    std::memcpy(th, tile_bit, (size_t)T * sizeof(int));
+    if (zero_dev) { ((int*)th)[T] = 0; *zero_dev = (const int*)td + T; }
+    has->assign((size_t)nbits + 1, 0);
+    for (int t = 0; t < T; ++t)
+        if (tile_bit[t] >= 0) (*has)[(size_t)tile_bit[t]] = 1;
+    if ((rc = table_upload(ctx, s, th, td, bytes)) != WM_OK) return rc;
+    *table_dev = (const int*)td;
+    return WM_OK;
+}
+
+// wm_locate_bits' tail behind the frames' spectra in L.hs.  Pair-major: the pair's key plane and its spectrum once per call, then
+// per frame the product, the way back and the accumulate pass; behind the last pair the folds and the records: [frames][4] of the
+// energy map, then [frames][nbits] soft values.  status: the frames' DEVICE status words
+int locate_bits_tail(wm_ctx* ctx, Slot& s, int slot, const LocBitsCall& c, const LocBitsScratch& L, const wm_keys* keys, int k, const int* table_dev,
+                     const std::vector<char>& has, int nbits, const int* status, float* energy_dev, float* maps_dev, float* loc_out, float* soft_out,
+                     int* status_out)
+{
+    int rc;
+    const int pr = c.pr, pc = c.pc, ny = c.ny, nx = c.nx, frames = c.frames;
+    const size_t n = (size_t)ny * nx, npl = (size_t)pr * pc;
+    float* energy = energy_dev ? energy_dev : L.energy;
+    float* maps = maps_dev ? maps_dev : L.maps;
+    OpResult* res = s.d_res + s.res_used;
+    const float* key = keys->d + (size_t)k * keys->rows * keys->cols;
+    const int npairs = (nbits + 1) / 2;
+    const size_t blk_bytes = locate_bits_part_bytes(ny, nx);
+    for (int pi = 0; pi < npairs; ++pi) {
+        const int b0 = 2 * pi, b1 = b0 + 1 < nbits ? b0 + 1 : -2;
+        launch_locate_key_pair(s.stream, key, keys->rows, keys->cols, table_dev, c.ts, b0, b1, L.a, pr, pc);
+        fft2_forward_t(s.stream, L.a, L.kw, pr, pc, L.tw_r, L.tw_c);
+        for (int f = 0; f < frames; ++f) {
+            launch_locate_mul3(s.stream, L.hs + f * L.plane_floats, L.kw, L.p, npl);
+            fft2_inverse_t(s.stream, L.p, L.a, pr, pc, L.tw_r, L.tw_c);
+            float* mf = maps + (size_t)f * nbits * n;
+            launch_locate_bits_acc(s.stream, L.a, pr, pc, ny, nx, status + f, pi == 0, has[(size_t)b0] != 0, b1 >= 0 && has[(size_t)b1] != 0,
+                                   mf + (size_t)b0 * n, b1 >= 0 ? mf + (size_t)b1 * n : nullptr, energy + (size_t)f * n,
+                                   L.part + (size_t)f * L.part_stride + (size_t)pi * blk_bytes,
+                                   pi == npairs - 1 ? L.epart + (size_t)f * L.epart_stride : nullptr);
+        }
+    }
+    for (int f = 0; f < frames; ++f)
+        launch_locate_bits_fold(s.stream, L.epart + (size_t)f * L.epart_stride, L.part + (size_t)f * L.part_stride, ny, nx, nbits, energy + (size_t)f * n,
+                                maps + (size_t)f * nbits * n, status + f, res + WM_LOCATE_BITS_NVALS * f,
+                                res + WM_LOCATE_BITS_NVALS * frames + (size_t)f * nbits);
+    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
+    push_pending(s, frames, WM_LOCATE_BITS_NVALS, false, loc_out, status_out, nullptr);
+    return finish_call(ctx, s, slot, frames, nbits, false, soft_out, nullptr);
+}
+}  // namespace
+
 // wm_locate with the key masked to the tiles of one payload bit at a time, two bits per complex transform: the frames' spectra are
 // kept, every pair's key plane is transformed once per call, and per (pair, frame) there are a product, an inverse transform and the
 // accumulate pass; behind the last pair the folds.  None of its kernels runs inside a ProfScope
@@ -2323,94 +2577,47 @@ int wm_locate_bits(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* ke
     if (rc != WM_OK) return rc;
     if (!img || !keys || !tile_bit || !loc_out || !soft_out)
         return fail(ctx, WM_ERR_BAD_ARG, "wm_locate_bits: null img, keys, tile_bit, loc_out or soft_out");
-    if (k < 0 || k >= keys->nkeys) return fail(ctx, WM_ERR_BAD_ARG, "wm_locate_bits: key " + std::to_string(k) + " of a bank of " + std::to_string(keys->nkeys));
-    if ((rc = check_bank(ctx, keys, "wm_locate_bits", false)) != WM_OK) return rc;
-    int ny, nx, pr, pc;
-    if (wm_locate_shape(ctx->rows, ctx->cols, keys->rows, keys->cols, &ny, &nx, &pr, &pc) != WM_OK)
-        return fail(ctx, WM_ERR_BAD_ARG, "wm_locate_bits: a " + std::to_string(keys->rows) + "x" + std::to_string(keys->cols) +
-                                             " key plane needs a transform above " + std::to_string(1 << FFT_LOG_MAX) + " per axis");
-    if ((rc = refuse_band(ctx, "wm_locate_bits")) != WM_OK) return rc;
-    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    LocBitsCall c;
+    if ((rc = locate_bits_front(ctx, "wm_locate_bits", img, keys, k, tile_rows, tile_cols, tile_bit, nbits, slot, &c)) != WM_OK) return rc;
     Slot& s = slot_of(ctx, slot);
-    // (open_input checks the plane and the record room again: both have to be known HERE, in front of the table's checks and of any device work)
-    if ((rc = check_plane(ctx, img, 0, false, "image", true)) != WM_OK) return rc;
-    const int frames = img->frames;
-    const long long per_frame = WM_LOCATE_BITS_NVALS + (long long)std::max(nbits, 0);
-    if ((rc = check_res_room(ctx, s, frames * per_frame, "(4 + bits)")) != WM_OK) return rc;
-    TileShape ts;
-    ts.th = tile_rows; ts.tw = tile_cols;
-    if (wm_tiles_shape(keys->rows, keys->cols, tile_rows, tile_cols, &ts.ny, &ts.nx) != WM_OK)
-        return fail(ctx, WM_ERR_BAD_ARG, "wm_locate_bits: tile shape " + std::to_string(tile_rows) + "x" + std::to_string(tile_cols) +
-                                             " (rows: a multiple of 8, >= 32; columns: a multiple of 4, >= 32)");
-    const int T = ts.ny * ts.nx;
-    if ((rc = tile_bits_checked(ctx, "wm_locate_bits", tile_bit, T, nbits)) != WM_OK) return rc;
     Sweep sw;
-    if ((rc = open_input(ctx, s, img, "image", mask, per_frame, "(4 + bits)", &sw)) != WM_OK) return rc;
-
-    // scratch and tables: another layout moves the planes under the calls still queued on the slot, so it waits for them
-    const long long key_now[6] = {((long long)pr << 32) | pc, ((long long)ny << 32) | nx, frames, nbits, energy_dev ? 0 : 1, maps_dev ? 0 : 1};
-    const size_t need = locb_layout(nullptr, ctx->rows, ctx->cols, pr, pc, ny, nx, frames, nbits, !energy_dev, !maps_dev).bytes;
-    const bool reshape = !std::equal(key_now, key_now + 6, s.locb_key) || s.locb_scr_bytes < need;
-    if (reshape) {
-        HIPCHK(ctx, hipStreamSynchronize(s.stream));
-        std::fill(s.locb_key, s.locb_key + 6, 0LL);
-        if ((rc = ensure(ctx, &s.locb_scr, &s.locb_scr_bytes, need, WM_ERR_ALLOC)) != WM_OK) return rc;
-    }
-    const LocBitsScratch L = locb_layout(s.locb_scr, ctx->rows, ctx->cols, pr, pc, ny, nx, frames, nbits, !energy_dev, !maps_dev);
-    if (reshape) {
-        std::vector<float> tw((size_t)2 * std::max(pr, pc));
-        fft_twiddles(pr, tw.data());
-        HIPCHK(ctx, hipMemcpy(L.tw_r, tw.data(), (size_t)pr * 2 * sizeof(float), hipMemcpyHostToDevice));
-        fft_twiddles(pc, tw.data());
-        HIPCHK(ctx, hipMemcpy(L.tw_c, tw.data(), (size_t)pc * 2 * sizeof(float), hipMemcpyHostToDevice));
-        std::copy(key_now, key_now + 6, s.locb_key);
-    }
-    // the call's own copy of the table (the caller's array is free when this function returns), and which bits have a tile at all
-    void *th = nullptr, *td = nullptr;
-    if ((rc = table_room(ctx, s, (size_t)T * sizeof(int), &th, &td)) != WM_OK) return rc;
-    std::memcpy(th, tile_bit, (size_t)T * sizeof(int));
-    std::vector<char> has((size_t)nbits + 1, 0);
-    for (int t = 0; t < T; ++t)
-        if (tile_bit[t] >= 0) has[(size_t)tile_bit[t]] = 1;
-    if ((rc = table_upload(ctx, s, th, td, (size_t)T * sizeof(int))) != WM_OK) return rc;
-
-    const size_t n = (size_t)ny * nx, npl = (size_t)pr * pc;
-    float* energy = energy_dev ? energy_dev : L.energy;
-    float* maps = maps_dev ? maps_dev : L.maps;
-    OpResult* res = s.d_res + s.res_used;
+    if ((rc = open_input(ctx, s, img, "image", mask, c.per_frame, "(4 + bits)", &sw)) != WM_OK) return rc;
+    LocBitsScratch L;
+    if ((rc = locb_scratch(ctx, s, c, nbits, !energy_dev, !maps_dev, &L)) != WM_OK) return rc;
+    const int* table_dev = nullptr;
+    std::vector<char> has;
+    if ((rc = locate_bits_table(ctx, s, tile_bit, c.ts.ny * c.ts.nx, nbits, &table_dev, &has)) != WM_OK) return rc;
     // the image side is wm_locate's: the Gram sweep and the solve, then every frame's e (and m), h and its spectrum, kept
     if ((rc = gram_sweep(ctx, s, sw, img)) != WM_OK) return rc;
-    for (int f = 0; f < frames; ++f) {
+    for (int f = 0; f < c.frames; ++f) {
         launch_locate_e(sw, f, L.e, L.m);
-        launch_locate_h(sw, f, L.e, L.m, L.a, pr, pc);
-        fft2_forward_t(s.stream, L.a, L.hs + f * L.plane_floats, pr, pc, L.tw_r, L.tw_c);
+        launch_locate_h(sw, f, L.e, L.m, L.a, c.pr, c.pc);
+        fft2_forward_t(s.stream, L.a, L.hs + f * L.plane_floats, c.pr, c.pc, L.tw_r, L.tw_c);
     }
-    // pair-major: the pair's key plane and its spectrum once per call, then per frame the product, the way back and the accumulate pass
-    const float* key = keys->d + (size_t)k * keys->rows * keys->cols;
-    const int npairs = (nbits + 1) / 2;
-    const size_t blk_bytes = locate_bits_part_bytes(ny, nx);
-    for (int pi = 0; pi < npairs; ++pi) {
-        const int b0 = 2 * pi, b1 = b0 + 1 < nbits ? b0 + 1 : -2;
-        launch_locate_key_pair(s.stream, key, keys->rows, keys->cols, (const int*)td, ts, b0, b1, L.a, pr, pc);
-        fft2_forward_t(s.stream, L.a, L.kw, pr, pc, L.tw_r, L.tw_c);
-        for (int f = 0; f < frames; ++f) {
-            launch_locate_mul3(s.stream, L.hs + f * L.plane_floats, L.kw, L.p, npl);
-            fft2_inverse_t(s.stream, L.p, L.a, pr, pc, L.tw_r, L.tw_c);
-            float* mf = maps + (size_t)f * nbits * n;
-            launch_locate_bits_acc(s.stream, L.a, pr, pc, ny, nx, s.d_status + f, pi == 0, has[(size_t)b0] != 0, b1 >= 0 && has[(size_t)b1] != 0,
-                                   mf + (size_t)b0 * n, b1 >= 0 ? mf + (size_t)b1 * n : nullptr, energy + (size_t)f * n,
-                                   L.part + (size_t)f * L.part_stride + (size_t)pi * blk_bytes,
-                                   pi == npairs - 1 ? L.epart + (size_t)f * L.epart_stride : nullptr);
-        }
-    }
-    // the records: [frames][4] of the energy map, then [frames][nbits] soft values
-    for (int f = 0; f < frames; ++f)
-        launch_locate_bits_fold(s.stream, L.epart + (size_t)f * L.epart_stride, L.part + (size_t)f * L.part_stride, ny, nx, nbits, energy + (size_t)f * n,
-                                maps + (size_t)f * nbits * n, s.d_status + f, res + WM_LOCATE_BITS_NVALS * f,
-                                res + WM_LOCATE_BITS_NVALS * frames + (size_t)f * nbits);
-    if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
-    push_pending(s, frames, WM_LOCATE_BITS_NVALS, false, loc_out, status_out, nullptr);
-    return finish_call(ctx, s, slot, frames, nbits, false, soft_out, nullptr);
+    return locate_bits_tail(ctx, s, slot, c, L, keys, k, table_dev, has, nbits, s.d_status, energy_dev, maps_dev, loc_out, soft_out, status_out);
+}
+
+// wm_locate_bits' tail on a caller's pooled image-side plane (wm_clip_pool) in the place of one frame's h
+int wm_locate_bits_pooled(wm_ctx* ctx, const float* pool_dev, const wm_keys* keys, int k, int tile_rows, int tile_cols, const int32_t* tile_bit,
+                          int nbits, float* loc_out, float* soft_out, float* energy_dev, float* maps_dev, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    int rc;
+    if (!pool_dev || !keys || !tile_bit || !loc_out || !soft_out)
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_locate_bits_pooled: null pool_dev, keys, tile_bit, loc_out or soft_out");
+    LocBitsCall c;
+    if ((rc = locate_bits_front(ctx, "wm_locate_bits_pooled", nullptr, keys, k, tile_rows, tile_cols, tile_bit, nbits, slot, &c)) != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    LocBitsScratch L;
+    if ((rc = locb_scratch(ctx, s, c, nbits, !energy_dev, !maps_dev, &L)) != WM_OK) return rc;
+    const int* table_dev = nullptr;
+    std::vector<char> has;
+    const int* status = nullptr;  // (ONE request of table room for the table and the zero word)
+    if ((rc = locate_bits_table(ctx, s, tile_bit, c.ts.ny * c.ts.nx, nbits, &table_dev, &has, &status)) != WM_OK) return rc;
+    launch_locate_key(s.stream, pool_dev, ctx->rows, ctx->cols, L.a, c.pr, c.pc);  // (the pool in the place of h: a dense real plane)
+    fft2_forward_t(s.stream, L.a, L.hs, c.pr, c.pc, L.tw_r, L.tw_c);
+    return locate_bits_tail(ctx, s, slot, c, L, keys, k, table_dev, has, nbits, status, energy_dev, maps_dev, loc_out, soft_out, nullptr);
 }
 
 // the three passes wm_locate_bits adds to wm_fft_bench's seven, timed the same way: the key-pair plane (128 x 128 tiles over a key
@@ -2486,6 +2693,82 @@ LocKeysScratch lock_layout(void* base, int rows, int cols, int pr, int pc, int n
 }
 }  // namespace
 
+namespace {
+// what wm_locate_keys and wm_locate_keys_pooled share in front of their image side: the geometry, the refusals from the key range
+// on (`plane`: the image plane of wm_locate_keys, null for the pooled call, which has one frame and no plane to check)
+struct LocKeysCall { int ny, nx, pr, pc, frames; long long per_frame; };
+int locate_keys_front(wm_ctx* ctx, const std::string& who, const wm_plane* plane, const wm_keys* keys, int k0, int nk, int slot, LocKeysCall* c)
+{
+    int rc;
+    if (k0 < 0 || nk < 1 || (long long)k0 + nk > keys->nkeys)
+        return fail(ctx, WM_ERR_BAD_ARG, who + ": keys " + std::to_string(k0) + " .. " + std::to_string((long long)k0 + nk - 1) + " of a bank of " +
+                                             std::to_string(keys->nkeys));
+    if ((rc = check_bank(ctx, keys, who.c_str(), false)) != WM_OK) return rc;
+    if (wm_locate_shape(ctx->rows, ctx->cols, keys->rows, keys->cols, &c->ny, &c->nx, &c->pr, &c->pc) != WM_OK)
+        return fail(ctx, WM_ERR_BAD_ARG, who + ": a " + std::to_string(keys->rows) + "x" + std::to_string(keys->cols) +
+                                             " key plane needs a transform above " + std::to_string(1 << FFT_LOG_MAX) + " per axis");
+    if ((rc = refuse_band(ctx, who.c_str())) != WM_OK) return rc;
+    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
+    // (open_input checks the plane and the record room again: the room has to be known before per_frame is narrowed to an int)
+    if (plane && (rc = check_plane(ctx, plane, 0, false, "image", true)) != WM_OK) return rc;
+    c->frames = plane ? plane->frames : 1;
+    c->per_frame = (long long)WM_LOCATE_KEYS_NVALS * nk;
+    return check_res_room(ctx, s, c->frames * c->per_frame, "(4 x keys)");
+}
+
+// the slot's wm_locate_keys scratch for the call's shapes, its tables filled: another layout moves the planes under the calls still
+// queued on the slot, so it waits for them
+int lock_scratch(wm_ctx* ctx, Slot& s, const LocKeysCall& c, LocKeysScratch* L)
+{
+    int rc;
+    const int pr = c.pr, pc = c.pc;
+    const long long key_now[3] = {((long long)pr << 32) | pc, ((long long)c.ny << 32) | c.nx, c.frames};
+    const size_t need = lock_layout(nullptr, ctx->rows, ctx->cols, pr, pc, c.ny, c.nx, c.frames).bytes;
+    const bool reshape = !std::equal(key_now, key_now + 3, s.lock_key) || s.lock_scr_bytes < need;
+    if (reshape) {
+        HIPCHK(ctx, hipStreamSynchronize(s.stream));
+        std::fill(s.lock_key, s.lock_key + 3, 0LL);
+        if ((rc = ensure(ctx, &s.lock_scr, &s.lock_scr_bytes, need, WM_ERR_ALLOC)) != WM_OK) return rc;
+    }
+    *L = lock_layout(s.lock_scr, ctx->rows, ctx->cols, pr, pc, c.ny, c.nx, c.frames);
+    if (reshape) {
+        std::vector<float> tw((size_t)2 * std::max(pr, pc));
+        fft_twiddles(pr, tw.data());
+        HIPCHK(ctx, hipMemcpy(L->tw_r, tw.data(), (size_t)pr * 2 * sizeof(float), hipMemcpyHostToDevice));
+        fft_twiddles(pc, tw.data());
+        HIPCHK(ctx, hipMemcpy(L->tw_c, tw.data(), (size_t)pc * 2 * sizeof(float), hipMemcpyHostToDevice));
+        std::copy(key_now, key_now + 3, s.lock_key);
+    }
+    return WM_OK;
+}
+
+// wm_locate_keys' tail behind the frames' spectra in L.hs (L.nz cleared on the stream beforehand).  Pair-major: the pair's plane and
+// its spectrum once per call, then per frame the product, the way back, the maps and the records.  status: the frames' DEVICE
+// status words
+int locate_keys_tail(wm_ctx* ctx, Slot& s, int slot, const LocKeysCall& c, const LocKeysScratch& L, const wm_keys* keys, int k0, int nk,
+                     const int* status, float* loc_out, float* maps_dev, int* status_out)
+{
+    const int pr = c.pr, pc = c.pc, ny = c.ny, nx = c.nx, frames = c.frames;
+    const size_t n = (size_t)ny * nx, npl = (size_t)pr * pc, key_elems = (size_t)keys->rows * keys->cols;
+    OpResult* res = s.d_res + s.res_used;
+    for (int j = 0; j < nk; j += 2) {
+        const bool pair = j + 1 < nk;
+        const float* ka = keys->d + (size_t)(k0 + j) * key_elems;
+        launch_locate_keys_pair(s.stream, ka, pair ? ka + key_elems : nullptr, keys->rows, keys->cols, L.a, pr, pc, L.nz + j);
+        fft2_forward_t(s.stream, L.a, L.kw, pr, pc, L.tw_r, L.tw_c);
+        for (int f = 0; f < frames; ++f) {
+            launch_locate_mul3(s.stream, L.hs + f * L.plane_floats, L.kw, L.p, npl);
+            fft2_inverse_t(s.stream, L.p, L.a, pr, pc, L.tw_r, L.tw_c);
+            float* mf = maps_dev ? maps_dev + ((size_t)f * nk + j) * n : nullptr;
+            launch_locate_keys_peak(s.stream, L.a, pr, pc, ny, nx, status + f, L.nz + j, pair, mf, mf && pair ? mf + n : nullptr, L.part,
+                                    res + ((size_t)f * nk + j) * WM_LOCATE_KEYS_NVALS);
+        }
+    }
+    return finish_call(ctx, s, slot, frames, (int)c.per_frame, false, loc_out, status_out);
+}
+}  // namespace
+
 // wm_locate of every frame against keys k0 .. k0 + nk - 1, two keys per complex transform: the frames' spectra are kept, every
 // pair's plane is transformed once per call, and per (pair, frame) there are a product, an inverse transform, the map pass and the
 // fold of its records.  None of its kernels runs inside a ProfScope
@@ -2496,68 +2779,43 @@ int wm_locate_keys(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* ke
     int rc = check_mask(ctx, mask);
     if (rc != WM_OK) return rc;
     if (!img || !keys || (!loc_out && !maps_dev)) return fail(ctx, WM_ERR_BAD_ARG, "wm_locate_keys: null img or keys, or loc_out and maps_dev both null");
-    if (k0 < 0 || nk < 1 || (long long)k0 + nk > keys->nkeys)
-        return fail(ctx, WM_ERR_BAD_ARG, "wm_locate_keys: keys " + std::to_string(k0) + " .. " + std::to_string((long long)k0 + nk - 1) + " of a bank of " +
-                                             std::to_string(keys->nkeys));
-    if ((rc = check_bank(ctx, keys, "wm_locate_keys", false)) != WM_OK) return rc;
-    int ny, nx, pr, pc;
-    if (wm_locate_shape(ctx->rows, ctx->cols, keys->rows, keys->cols, &ny, &nx, &pr, &pc) != WM_OK)
-        return fail(ctx, WM_ERR_BAD_ARG, "wm_locate_keys: a " + std::to_string(keys->rows) + "x" + std::to_string(keys->cols) +
-                                             " key plane needs a transform above " + std::to_string(1 << FFT_LOG_MAX) + " per axis");
-    if ((rc = refuse_band(ctx, "wm_locate_keys")) != WM_OK) return rc;
-    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    LocKeysCall c;
+    if ((rc = locate_keys_front(ctx, "wm_locate_keys", img, keys, k0, nk, slot, &c)) != WM_OK) return rc;
     Slot& s = slot_of(ctx, slot);
-    // (open_input checks the plane and the record room again: the room has to be known before per_frame is narrowed to an int)
-    if ((rc = check_plane(ctx, img, 0, false, "image", true)) != WM_OK) return rc;
-    const int frames = img->frames;
-    const long long per_frame = (long long)WM_LOCATE_KEYS_NVALS * nk;
-    if ((rc = check_res_room(ctx, s, frames * per_frame, "(4 x keys)")) != WM_OK) return rc;
     Sweep sw;
-    if ((rc = open_input(ctx, s, img, "image", mask, (int)per_frame, "(4 x keys)", &sw)) != WM_OK) return rc;
-
-    // scratch and tables: another layout moves the planes under the calls still queued on the slot, so it waits for them
-    const long long key_now[3] = {((long long)pr << 32) | pc, ((long long)ny << 32) | nx, frames};
-    const size_t need = lock_layout(nullptr, ctx->rows, ctx->cols, pr, pc, ny, nx, frames).bytes;
-    const bool reshape = !std::equal(key_now, key_now + 3, s.lock_key) || s.lock_scr_bytes < need;
-    if (reshape) {
-        HIPCHK(ctx, hipStreamSynchronize(s.stream));
-        std::fill(s.lock_key, s.lock_key + 3, 0LL);
-        if ((rc = ensure(ctx, &s.lock_scr, &s.lock_scr_bytes, need, WM_ERR_ALLOC)) != WM_OK) return rc;
-    }
-    const LocKeysScratch L = lock_layout(s.lock_scr, ctx->rows, ctx->cols, pr, pc, ny, nx, frames);
-    if (reshape) {
-        std::vector<float> tw((size_t)2 * std::max(pr, pc));
-        fft_twiddles(pr, tw.data());
-        HIPCHK(ctx, hipMemcpy(L.tw_r, tw.data(), (size_t)pr * 2 * sizeof(float), hipMemcpyHostToDevice));
-        fft_twiddles(pc, tw.data());
-        HIPCHK(ctx, hipMemcpy(L.tw_c, tw.data(), (size_t)pc * 2 * sizeof(float), hipMemcpyHostToDevice));
-        std::copy(key_now, key_now + 3, s.lock_key);
-    }
-    const size_t n = (size_t)ny * nx, npl = (size_t)pr * pc, key_elems = (size_t)keys->rows * keys->cols;
-    OpResult* res = s.d_res + s.res_used;
+    if ((rc = open_input(ctx, s, img, "image", mask, (int)c.per_frame, "(4 x keys)", &sw)) != WM_OK) return rc;
+    LocKeysScratch L;
+    if ((rc = lock_scratch(ctx, s, c, &L)) != WM_OK) return rc;
     HIPCHK(ctx, hipMemsetAsync(L.nz, 0, (size_t)(nk + 1) * sizeof(int), s.stream));
     // the image side is wm_locate's: the Gram sweep and the solve, then every frame's e (and m), h and its spectrum, kept
     if ((rc = gram_sweep(ctx, s, sw, img)) != WM_OK) return rc;
-    for (int f = 0; f < frames; ++f) {
+    for (int f = 0; f < c.frames; ++f) {
         launch_locate_e(sw, f, L.e, L.m);
-        launch_locate_h(sw, f, L.e, L.m, L.a, pr, pc);
-        fft2_forward_t(s.stream, L.a, L.hs + f * L.plane_floats, pr, pc, L.tw_r, L.tw_c);
+        launch_locate_h(sw, f, L.e, L.m, L.a, c.pr, c.pc);
+        fft2_forward_t(s.stream, L.a, L.hs + f * L.plane_floats, c.pr, c.pc, L.tw_r, L.tw_c);
     }
-    // pair-major: the pair's plane and its spectrum once per call, then per frame the product, the way back, the maps and the records
-    for (int j = 0; j < nk; j += 2) {
-        const bool pair = j + 1 < nk;
-        const float* ka = keys->d + (size_t)(k0 + j) * key_elems;
-        launch_locate_keys_pair(s.stream, ka, pair ? ka + key_elems : nullptr, keys->rows, keys->cols, L.a, pr, pc, L.nz + j);
-        fft2_forward_t(s.stream, L.a, L.kw, pr, pc, L.tw_r, L.tw_c);
-        for (int f = 0; f < frames; ++f) {
-            launch_locate_mul3(s.stream, L.hs + f * L.plane_floats, L.kw, L.p, npl);
-            fft2_inverse_t(s.stream, L.p, L.a, pr, pc, L.tw_r, L.tw_c);
-            float* mf = maps_dev ? maps_dev + ((size_t)f * nk + j) * n : nullptr;
-            launch_locate_keys_peak(s.stream, L.a, pr, pc, ny, nx, s.d_status + f, L.nz + j, pair, mf, mf && pair ? mf + n : nullptr, L.part,
-                                    res + ((size_t)f * nk + j) * WM_LOCATE_KEYS_NVALS);
-        }
-    }
-    return finish_call(ctx, s, slot, frames, (int)per_frame, false, loc_out, status_out);
+    return locate_keys_tail(ctx, s, slot, c, L, keys, k0, nk, s.d_status, loc_out, maps_dev, status_out);
+}
+
+// wm_locate_keys' tail on a caller's pooled image-side plane (wm_clip_pool) in the place of one frame's h
+int wm_locate_keys_pooled(wm_ctx* ctx, const float* pool_dev, const wm_keys* keys, int k0, int nk, float* loc_out, float* maps_dev, int slot)
+{
+    if (!ctx) return WM_ERR_BAD_ARG;
+    int rc;
+    if (!pool_dev || !keys || (!loc_out && !maps_dev))
+        return fail(ctx, WM_ERR_BAD_ARG, "wm_locate_keys_pooled: null pool_dev or keys, or loc_out and maps_dev both null");
+    LocKeysCall c;
+    if ((rc = locate_keys_front(ctx, "wm_locate_keys_pooled", nullptr, keys, k0, nk, slot, &c)) != WM_OK) return rc;
+    Slot& s = slot_of(ctx, slot);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    LocKeysScratch L;
+    if ((rc = lock_scratch(ctx, s, c, &L)) != WM_OK) return rc;
+    HIPCHK(ctx, hipMemsetAsync(L.nz, 0, (size_t)(nk + 1) * sizeof(int), s.stream));
+    const int* status = nullptr;
+    if ((rc = zero_status(ctx, s, &status)) != WM_OK) return rc;
+    launch_locate_key(s.stream, pool_dev, ctx->rows, ctx->cols, L.a, c.pr, c.pc);  // (the pool in the place of h: a dense real plane)
+    fft2_forward_t(s.stream, L.a, L.hs, c.pr, c.pc, L.tw_r, L.tw_c);
+    return locate_keys_tail(ctx, s, slot, c, L, keys, k0, nk, status, loc_out, maps_dev, nullptr);
 }
 
 int wm_locate_keys_rank(const float* loc, int nk, int* best, float* z_best, float* z_next)

@@ -4,7 +4,8 @@
 // of wm_locate_bits: k_locate_key_pair (the key masked to the tiles of two payload bits, one per half of a complex plane),
 // k_locate_bits_acc (the two maps, the energy map and their block folds) and k_locate_bits_fold (the records); and of wm_locate_keys:
 // k_locate_keys_pair (two keys of a bank, one per half of a complex plane, and a flag per key that is not all zero),
-// k_locate_keys_peak (the two maps and their block folds) and k_locate_keys_fold (the records of the two keys).
+// k_locate_keys_peak (the two maps and their block folds) and k_locate_keys_fold (the records of the two keys); and of
+// wm_clip_pool: k_clip_pool (the frames of a clip pooled into one image-side plane, h formed by k_locate_e's and k_locate_h's helpers).
 //
 // With c solved, the detector's numerator is linear in W: <e_u, e_w>(oy, ox) = sum_q h(q) W(q + (oy, ox)), one 2-D cross-correlation
 // of h with the key plane.  Every workgroup works on its own pixels or its own chunk of the map; the fold
@@ -21,9 +22,75 @@ constexpr int PEAK_PER = 16;     // map values per thread of k_locate_peak: a wo
 
 __device__ __forceinline__ int clampi(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
 
+// ---- the arithmetic of one pixel of the image side, shared by k_locate_e / k_locate_h and k_clip_pool: the kernels differ in where
+// the taps come from (global memory or an LDS tile), never in the sequence of operations, so their e, m and h agree bit for bit
+
+// the NVF value of the window 2 PAD + 1 around a pixel: nvf_from_sums over row-major taps, as nvf_value forms it (the first tap
+// starts both chains).  at(a, b): the pixel value at row offset a, column offset b
+template <int PAD, typename At>
+__device__ __forceinline__ float locate_nvf(At&& at)
+{
+    float sum = 0.0f, sumsq = 0.0f;
+#pragma unroll
+    for (int a = -PAD; a <= PAD; ++a)
+#pragma unroll
+        for (int b = -PAD; b <= PAD; ++b) {
+            const float v = at(a, b);
+            if (a == -PAD && b == -PAD) { sum = v; sumsq = v * v; }
+            else { sum += v; sumsq = fmaf(v, v, sumsq); }
+        }
+    return nvf_from_sums<PAD>(sum, sumsq);
+}
+
+// the pixels p of one axis with clamp(p + d) == q: q - d when it is in range, and the border pixel once more when q is that
+// border and d points outwards.  Returns their count (0 .. 2)
+__device__ __forceinline__ int adjoint_set(int q, int d, int n, int (&out)[2])
+{
+    int cnt = 0;
+    const int p = q - d;
+    if (p >= 0 && p < n) out[cnt++] = p;
+    if (d == -1 && q == 0) out[cnt++] = 0;
+    if (d == 1 && q == n - 1) out[cnt++] = n - 1;
+    return cnt;
+}
+
+// g(q) = e(q) - sum_k c_k sum_{p : clamp(p + d_k) = q} e(p) at q = (r, c): the exact adjoint of the replicate-border stencil.
+// ec = e(q); e_at(pr, pc): e at image coordinates
+template <typename EAt>
+__device__ __forceinline__ float locate_g(float ec, int r, int c, int rows, int cols, const float* __restrict__ coef, EAt&& e_at)
+{
+    float g = ec;
+    if (r >= 1 && r < rows - 1 && c >= 1 && c < cols - 1) {
+        // off the border every set is the one pixel q - d_k: the same operations as below (0.0f + e included), without the sets
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int t = k < 4 ? k : k + 1;
+            const float s = 0.0f + e_at(r - (t / 3 - 1), c - (t % 3 - 1));
+            g = fmaf(-coef[k], s, g);
+        }
+        return g;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int t = k < 4 ? k : k + 1;  // the 3x3 taps in row-major order without the centre
+        const int dr = t / 3 - 1, dc = t % 3 - 1;
+        int pr_[2], pc_[2];
+        const int nr = adjoint_set(r, dr, rows, pr_), ncn = adjoint_set(c, dc, cols, pc_);
+        float s = 0.0f;
+        for (int a = 0; a < nr; ++a)
+            for (int b = 0; b < ncn; ++b) s += e_at(pr_[a], pc_[b]);
+        g = fmaf(-coef[k], s, g);
+    }
+    return g;
+}
+
+// h = m g with m = |e| (ME) or the NVF value
+template <int MASK>
+__device__ __forceinline__ float locate_h_value(float ec, float m, float g) { return (MASK == 0 ? fabsf(ec) : m) * g; }
+
 // k_locate_e: e = x - sum_k c_k x(clamp(p + d_k)) with the detector's rounding sequence (residual1: the chain starts at the centre
-// and runs over the negated coefficients), and under NVF the mask of the window 2 PAD + 1 (nvf_from_sums over row-major taps, as
-// nvf_value forms it).  One pixel per lane, replicate borders by clamped indices; x of any type, pitch and frame stride.
+// and runs over the negated coefficients), and under NVF the mask of the window 2 PAD + 1 (locate_nvf).  One pixel per lane,
+// replicate borders by clamped indices; x of any type, pitch and frame stride.
 // e, m: dense [rows][cols] f32 planes of ONE frame (m unused under ME).  An unsolvable frame is skipped: k_locate_h writes zeros
 template <typename T, int MASK, int PAD>
 __global__ __launch_bounds__(LB) void k_locate_e(const T* __restrict__ x, long long pitch, int rows, int cols, const float* __restrict__ coef,
@@ -42,30 +109,10 @@ __global__ __launch_bounds__(LB) void k_locate_e(const T* __restrict__ x, long l
         for (int b = 0; b < 3; ++b)
             win[a][b] = Elem<T>::cvt1(x[(long long)clampi(r + a - 1, rows) * pitch + clampi(c + b - 1, cols)]);
     e[(size_t)r * cols + c] = residual1<1>(win[0], win[1], win[2], 0, nc);
-    if (MASK == 1) {
-        float sum = 0.0f, sumsq = 0.0f;
-#pragma unroll
-        for (int a = -PAD; a <= PAD; ++a)
-#pragma unroll
-            for (int b = -PAD; b <= PAD; ++b) {
-                const float v = PAD == 1 ? win[a + 1][b + 1] : Elem<T>::cvt1(x[(long long)clampi(r + a, rows) * pitch + clampi(c + b, cols)]);
-                if (a == -PAD && b == -PAD) { sum = v; sumsq = v * v; }
-                else { sum += v; sumsq = fmaf(v, v, sumsq); }
-            }
-        m[(size_t)r * cols + c] = nvf_from_sums<PAD>(sum, sumsq);
-    }
-}
-
-// the pixels p of one axis with clamp(p + d) == q: q - d when it is in range, and the border pixel once more when q is that
-// border and d points outwards.  Returns their count (0 .. 2)
-__device__ __forceinline__ int adjoint_set(int q, int d, int n, int (&out)[2])
-{
-    int cnt = 0;
-    const int p = q - d;
-    if (p >= 0 && p < n) out[cnt++] = p;
-    if (d == -1 && q == 0) out[cnt++] = 0;
-    if (d == 1 && q == n - 1) out[cnt++] = n - 1;
-    return cnt;
+    if (MASK == 1)
+        m[(size_t)r * cols + c] = locate_nvf<PAD>([&](int a, int b) {
+            return PAD == 1 ? win[a + 1][b + 1] : Elem<T>::cvt1(x[(long long)clampi(r + a, rows) * pitch + clampi(c + b, cols)]);
+        });
 }
 
 // k_locate_h: g(q) = e(q) - sum_k c_k sum_{p : clamp(p + d_k) = q} e(p), h = m g with m = |e| (ME) or the NVF plane, written as
@@ -78,21 +125,133 @@ __global__ __launch_bounds__(LB) void k_locate_h(const float* __restrict__ e, co
     float h = 0.0f;
     if (r < rows && c < cols && status[0] == 0) {
         const float ec = e[(size_t)r * cols + c];
-        float g = ec;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int t = k < 4 ? k : k + 1;  // the 3x3 taps in row-major order without the centre
-            const int dr = t / 3 - 1, dc = t % 3 - 1;
-            int pr_[2], pc_[2];
-            const int nr = adjoint_set(r, dr, rows, pr_), ncn = adjoint_set(c, dc, cols, pc_);
-            float s = 0.0f;
-            for (int a = 0; a < nr; ++a)
-                for (int b = 0; b < ncn; ++b) s += e[(size_t)pr_[a] * cols + pc_[b]];
-            g = fmaf(-coef[k], s, g);
-        }
-        h = (MASK == 0 ? fabsf(ec) : m[(size_t)r * cols + c]) * g;
+        const float g = locate_g(ec, r, c, rows, cols, coef, [&](int pr_, int pc_) { return e[(size_t)pr_ * cols + pc_]; });
+        h = locate_h_value<MASK>(ec, MASK == 0 ? 0.0f : m[(size_t)r * cols + c], g);
     }
     plane[(size_t)r * pc + c] = make_float2(h, 0.0f);
+}
+
+// ---- wm_clip_pool: the frames of a clip pooled on the image side ----------------------------------------
+
+constexpr int CTX = 64, CTY = 16;        // k_clip_pool: a workgroup's tile of output pixels, 64 columns x 16 rows
+constexpr int CPER = CTY / (LB / CTX);   // ... 4 pixels per lane: column t % 64, rows t / 64 + 4 k
+
+// k_clip_pool: pool(q) = fmaf(w_f, h_f(q), pool(q)) over the solvable frames f ascending, from 0.0f (accumulate == 0) or from the
+// plane's content; h_f is k_locate_e's and k_locate_h's, through the same helpers.  A workgroup owns a CTX x CTY tile and loops
+// over the frames: x with a halo of H = max(2, PAD) (indices clamped to the image) into LDS, e on the tile plus one pixel of halo
+// once per pixel into LDS, then per output pixel g, m, h and one fmaf into a register.  The pool is read and written once per
+// call.  Workgroup (0, 0) also writes the frames' status records.  x of any type, pitch and frame stride
+template <typename T, int MASK, int PAD>
+__global__ __launch_bounds__(LB) void k_clip_pool(const T* __restrict__ x, long long pitch, long long fstride, int frames, int rows, int cols,
+                                                  const float* __restrict__ coef, const int* __restrict__ status, const float* __restrict__ weights,
+                                                  float* __restrict__ pool, int accumulate, OpResult* __restrict__ res)
+{
+    constexpr int H = PAD > 2 ? PAD : 2;
+    constexpr int XW = CTX + 2 * H, XH = CTY + 2 * H, EW = CTX + 2, EH = CTY + 2;
+    __shared__ float s_x[XH * XW];
+    __shared__ float s_e[EH * EW];
+    const int t = threadIdx.x, tx = t % CTX, ty = t / CTX;
+    const int c0 = blockIdx.x * CTX, r0 = blockIdx.y * CTY;
+    const int c = c0 + tx;
+    if (blockIdx.x == 0 && blockIdx.y == 0)
+        for (int f = t; f < frames; f += LB) res[f] = OpResult{status[f], 0.0f};
+    float acc[CPER];
+#pragma unroll
+    for (int k = 0; k < CPER; ++k) {
+        const int r = r0 + ty + k * (LB / CTX);
+        acc[k] = accumulate && r < rows && c < cols ? pool[(size_t)r * cols + c] : 0.0f;
+    }
+    for (int f = 0; f < frames; ++f) {
+        if (status[f] != 0) continue;  // (the same in every lane)
+        const T* __restrict__ xf = x + (long long)f * fstride;
+        const float* __restrict__ cf = coef + 8 * f;
+        const float w = weights[f];
+        for (int i = t; i < XH * XW; i += LB) {
+            const int lr = i / XW, lc = i % XW;
+            s_x[i] = Elem<T>::cvt1(xf[(long long)clampi(r0 - H + lr, rows) * pitch + clampi(c0 - H + lc, cols)]);
+        }
+        __syncthreads();
+        float nc[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) nc[k] = -cf[k];
+        for (int i = t; i < EH * EW; i += LB) {
+            const int lr = i / EW, lc = i % EW;
+            const int r = r0 - 1 + lr, cc = c0 - 1 + lc;
+            float e = 0.0f;  // (a halo pixel outside the image: no adjoint set names it)
+            if (r >= 0 && r < rows && cc >= 0 && cc < cols) {
+                const float* up = s_x + (lr + H - 2) * XW + (lc + H - 2);  // the window's top left tap: x at (r - 1, cc - 1)
+                e = residual1<1>(up, up + XW, up + 2 * XW, 0, nc);
+            }
+            s_e[i] = e;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < CPER; ++k) {
+            // (the row is the same in every lane of a wave; pinned to a vector register, or the row conditions of the four pixels
+            // overfill the scalar registers)
+            const int lr = (int)pinned((uint32_t)(ty + k * (LB / CTX))), r = r0 + lr;
+            if (r < rows && c < cols) {
+                const float ec = s_e[(lr + 1) * EW + tx + 1];
+                const float g = locate_g(ec, r, c, rows, cols, cf, [&](int pr_, int pc_) { return s_e[(pr_ - r0 + 1) * EW + (pc_ - c0 + 1)]; });
+                float m = 0.0f;
+                if (MASK == 1) m = locate_nvf<PAD>([&](int a, int b) { return s_x[(lr + H + a) * XW + tx + H + b]; });
+                acc[k] = fmaf(w, locate_h_value<MASK>(ec, m, g), acc[k]);
+            }
+        }
+        if (MASK == 1) __syncthreads();  // (the next frame's x replaces the windows the NVF values read)
+    }
+#pragma unroll
+    for (int k = 0; k < CPER; ++k) {
+        const int r = r0 + ty + k * (LB / CTX);
+        if (r < rows && c < cols) pool[(size_t)r * cols + c] = acc[k];
+    }
+}
+
+// k_clip_pool_gather: k_clip_pool's result bit for bit without the LDS tiles -- one pixel per lane; per frame the 5 x 5 window of x
+// (a window of 2 PAD + 1 beside it under NVF p > 5) is gathered from cache with clamped indices and the nine e values around the
+// pixel are formed in registers.  The yardstick k_clip_pool's tiles are held against (wm_clip_pool_bench); no call takes it
+__device__ __forceinline__ float pick3(float a, float b, float c, int i) { return i == 0 ? a : (i == 1 ? b : c); }
+template <typename T, int MASK, int PAD>
+__global__ __launch_bounds__(LB) void k_clip_pool_gather(const T* __restrict__ x, long long pitch, long long fstride, int frames, int rows, int cols,
+                                                         const float* __restrict__ coef, const int* __restrict__ status,
+                                                         const float* __restrict__ weights, float* __restrict__ pool, int accumulate,
+                                                         OpResult* __restrict__ res)
+{
+    const int c = blockIdx.x * LTX + threadIdx.x % LTX, r = blockIdx.y * LTY + threadIdx.x / LTX;
+    if (blockIdx.x == 0 && blockIdx.y == 0)
+        for (int f = threadIdx.x; f < frames; f += LB) res[f] = OpResult{status[f], 0.0f};
+    if (r >= rows || c >= cols) return;
+    float acc = accumulate ? pool[(size_t)r * cols + c] : 0.0f;
+    for (int f = 0; f < frames; ++f) {
+        if (status[f] != 0) continue;
+        const T* __restrict__ xf = x + (long long)f * fstride;
+        const float* __restrict__ cf = coef + 8 * f;
+        float nc[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) nc[k] = -cf[k];
+        float win[5][5];
+#pragma unroll
+        for (int a = 0; a < 5; ++a)
+#pragma unroll
+            for (int b = 0; b < 5; ++b) win[a][b] = Elem<T>::cvt1(xf[(long long)clampi(r + a - 2, rows) * pitch + clampi(c + b - 2, cols)]);
+        float ee[3][3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int b = 0; b < 3; ++b) ee[a][b] = residual1<1>(win[a] + b, win[a + 1] + b, win[a + 2] + b, 0, nc);
+        const float ec = ee[1][1];
+        const float g = locate_g(ec, r, c, rows, cols, cf, [&](int pr_, int pc_) {
+            const int j = pc_ - c + 1;
+            return pick3(pick3(ee[0][0], ee[0][1], ee[0][2], j), pick3(ee[1][0], ee[1][1], ee[1][2], j), pick3(ee[2][0], ee[2][1], ee[2][2], j), pr_ - r + 1);
+        });
+        float m = 0.0f;
+        if (MASK == 1)
+            m = locate_nvf<PAD>([&](int a, int b) {
+                return PAD <= 2 ? win[a + 2][b + 2] : Elem<T>::cvt1(xf[(long long)clampi(r + a, rows) * pitch + clampi(c + b, cols)]);
+            });
+        acc = fmaf(weights[f], locate_h_value<MASK>(ec, m, g), acc);
+    }
+    pool[(size_t)r * cols + c] = acc;
 }
 
 // k_locate_key: the key plane [key_rows][key_cols] as the real part of a zeroed [pr][pc] complex plane
@@ -560,6 +719,28 @@ void launch_locate_h(const Sweep& sw, int frame, const float* e, const float* m,
     else
         WM_KLAUNCH(k_locate_h<1>, grid, dim3(LB), 0, sw.s, e, m, sw.lg.rows, sw.lg.cols, sw.coef + 8 * frame, sw.status + frame,
                    reinterpret_cast<float2*>(plane), pc);
+}
+
+void launch_clip_pool(const Sweep& sw, const float* weights, float* pool, bool accumulate, OpResult* res)
+{
+    const PlaneDesc& x = sw.x;
+    const int rows = sw.lg.rows, cols = sw.lg.cols;
+    const dim3 grid((cols + CTX - 1) / CTX, (rows + CTY - 1) / CTY);
+    WM_DISPATCH_T(x.dtype, for_mask_pad(sw.mask, sw.pad, [&](auto mk, auto p) {
+        WM_KLAUNCH((k_clip_pool<T, decltype(mk)::value, decltype(p)::value>), grid, dim3(LB), 0, sw.s, (const T*)x.p, x.pitch, x.fstride, sw.frames, rows,
+                   cols, sw.coef, sw.status, weights, pool, accumulate ? 1 : 0, res);
+    }));
+}
+
+void launch_clip_pool_gather(const Sweep& sw, const float* weights, float* pool, bool accumulate, OpResult* res)
+{
+    const PlaneDesc& x = sw.x;
+    const int rows = sw.lg.rows, cols = sw.lg.cols;
+    const dim3 grid((cols + LTX - 1) / LTX, (rows + LTY - 1) / LTY);
+    WM_DISPATCH_T(x.dtype, for_mask_pad(sw.mask, sw.pad, [&](auto mk, auto p) {
+        WM_KLAUNCH((k_clip_pool_gather<T, decltype(mk)::value, decltype(p)::value>), grid, dim3(LB), 0, sw.s, (const T*)x.p, x.pitch, x.fstride, sw.frames,
+                   rows, cols, sw.coef, sw.status, weights, pool, accumulate ? 1 : 0, res);
+    }));
 }
 
 void launch_locate_key(hipStream_t s, const float* key, int key_rows, int key_cols, float* plane, int pr, int pc)

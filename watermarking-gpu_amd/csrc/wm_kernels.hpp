@@ -403,6 +403,12 @@ void launch_locate_bits_fold(hipStream_t s, const void* epart, const void* part,
 void launch_locate_keys_pair(hipStream_t s, const float* key_a, const float* key_b, int key_rows, int key_cols, float* plane, int pr, int pc, int* nz);
 void launch_locate_keys_peak(hipStream_t s, const float* plane, int pr, int pc, int ny, int nx, const int* status, const int* nz, bool pair, float* map_a,
                              float* map_b, void* part, OpResult* res);
+// the frames of a clip pooled on the image side (wm_clip_pool), one launch per call: pool = fmaf(w_f, h_f, pool) over the solvable
+// frames of sw in ascending order, h_f being launch_locate_e's and launch_locate_h's bit for bit; pool: a dense DEVICE
+// [rows][cols] f32 plane, started from 0.0f unless accumulate; weights: DEVICE [frames]; res[0 .. frames): the frames' status records
+void launch_clip_pool(const Sweep& sw, const float* weights, float* pool, bool accumulate, OpResult* res);
+// ... the same result by a direct gather from cache, one pixel per lane and no LDS: wm_clip_pool_bench's yardstick, taken by no call
+void launch_clip_pool_gather(const Sweep& sw, const float* weights, float* pool, bool accumulate, OpResult* res);
 // band mode: solve the 8x8 system from all-reduced Gram totals [frames][44]; writes coef / status like k_gram's tail
 void launch_solve_totals(hipStream_t s, int frames, const double* totals, float* coef, int* status);
 // band mode, device-resident exchange (wm_band_*_dev): glue kernels between the sweeps and the caller's collectives
