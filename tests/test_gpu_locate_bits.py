@@ -193,6 +193,29 @@ def test_maps_against_wm_locate(wm, torch_cuda, mask):
     bank.close()
 
 
+@pytest.mark.parametrize("mask", [0, 1])
+def test_one_bit_on_every_tile_is_wm_locate_bit_for_bit(wm, torch_cuda, mask):
+    """one payload bit whose table takes every tile masks nothing: its map is wm_locate's map of the key bit for bit -- the lay pass,
+    the transforms and the map value are the same code --, and the energy map is that map squared in f32 (the missing second bit of
+    the pair adds an exact zero)"""
+    torch = torch_cuda
+    name = "120x330_8"
+    cs = CASES[name]
+    mt = wm.MASK_TYPE(mask)
+    keys = wm.KeySet(cs.kshape[0], cs.kshape[1], 2)
+    keys.set(1, TL.key_of(cs.kshape))
+    xt = torch.from_numpy(frames_of(wm, torch, name, mask, 3, "f32")).cuda()
+    eng = wm.Watermark(cs.shape[0], cs.shape[1], np.zeros(cs.shape, np.float32), 3, 40.0, max_frames=F)
+    every = np.zeros(cs.ny * cs.nx, np.int32)
+    _, _, en, mp = eng.locate_bits(xt, keys, 1, cs.tile[0], cs.tile[1], every, 1, mt, want_energy=True, want_maps=True)
+    whole = eng.locate(xt, keys, 1, mt, want_map=True)[1]
+    assert mp.shape[:2] == (F, 1) and float(whole.abs().max()) > 0.0
+    assert torch.equal(mp[:, 0].view(torch.int32), whole.view(torch.int32))
+    assert torch.equal(en.view(torch.int32), (mp[:, 0] * mp[:, 0]).view(torch.int32))
+    eng.close()
+    keys.close()
+
+
 def test_layouts_and_host_plane(wm, torch_cuda):
     """a pitched batch (tests/layouts.py) and a host plane give the dense device plane's bits, f32 and u8"""
     torch = torch_cuda

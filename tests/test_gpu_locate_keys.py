@@ -161,6 +161,42 @@ def test_against_wm_locate_and_another_partner(wm, torch_cuda, mask):
     keys.close()
 
 
+# 1037 x 1045 offsets make 265 block records: the one shape here where a thread of the record fold takes more than one
+MANY_RECORDS = ((1100, 1300), (64, 256), (500, 600))
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+@pytest.mark.parametrize("mask", [0, 1])
+@pytest.mark.parametrize("kshape,shape,at", [LK.CASES[0], LK.CASES[2], MANY_RECORDS])
+def test_one_key_is_wm_locate_bit_for_bit(wm, torch_cuda, kshape, shape, at, mask):
+    """a range of ONE key is wm_locate of that key: locateKeys(x, keys, k, 1) gives locate(x, keys, k)'s records and map bit for bit,
+    for every key of the bank and the three frames (two owners, one unmarked), and locateKeysPooled(pool, keys, k, 1) gives
+    locatePooled(pool, keys, k)'s -- the map pass, the record fold and the z rule are the same code"""
+    torch = torch_cuda
+    mt = wm.MASK_TYPE(mask)
+    xt = torch.from_numpy(LK.frames_of(kshape, shape, at, mask)).cuda()
+    keys = keyset(wm, LK.bank_of(kshape))
+    eng = engine(wm, shape, max_frames=F)
+    pool, status = eng.poolClip(xt, mt)
+    assert not status.any()
+    for k in range(NK):
+        loc, m = eng.locate(xt, keys, k, mt, want_map=True)
+        lock, mk = eng.locateKeys(xt, keys, k, 1, mt, want_maps=True)
+        assert lock.shape == (F, 1, 4) and np.array_equal(bits(lock[:, 0]), bits(loc)), (k, loc, lock)
+        assert torch.equal(mk[:, 0].view(torch.int32), m.view(torch.int32)), k
+        if k == LK.OWNER[0]:
+            assert (int(loc[0][0]), int(loc[0][1])) == at  # (the inputs mean something: frame 0's owner is found)
+        locp, mp = eng.locatePooled(pool, keys, k, want_map=True)
+        lockp, mkp = eng.locateKeysPooled(pool, keys, k, 1, want_maps=True)
+        assert np.array_equal(bits(lockp[0]), bits(locp)), (k, locp, lockp)
+        assert torch.equal(mkp[0].view(torch.int32), mp.view(torch.int32)), k
+    eng.close()
+    keys.close()
+
+
 def is_zero_record(rec):
     return list(rec[:3]) == [0, 0, 0] and np.isnan(rec[3])
 

@@ -1221,30 +1221,20 @@ class Watermark:
         when map_t is given) and status_out (frames ints, may be None) are written by sync(slot); map_t (a contiguous float32 GPU
         tensor of frames * ny * nx elements, may be None) is written on the slot's stream.  `keys` must stay alive and unmodified until
         then"""
-        import torch
         pimg = self._as_plane(image, 1)
         loc_out, status_out = self._scalars_out(loc_out, status_out)
-        pmap = None
-        if map_t is not None:
-            if not (map_t.is_cuda and map_t.dtype == torch.float32 and map_t.is_contiguous()):
-                raise RuntimeError("map_t must be a contiguous float32 GPU tensor")
-            pmap = C.c_void_p(map_t.data_ptr())
-        self._chk(lib().wm_locate(self._ctx, int(maskType), C.byref(pimg), _keys_handle(keys), k, loc_out, pmap, status_out, slot))
+        self._chk(lib().wm_locate(self._ctx, int(maskType), C.byref(pimg), _keys_handle(keys), k, loc_out, self._f32_gpu(map_t, "map_t"), status_out,
+                                  slot))
 
     def locate_keys_async(self, image, keys, k0, nk, maskType, slot, loc_out, maps_t=None, status_out=None):
         """wm_locate_keys enqueued on `slot`: loc_out (frames * nk * 4 floats: a ctypes array or a C-contiguous float32 numpy array, may
         be None when maps_t is given) and status_out (frames ints, may be None) are written by sync(slot); maps_t (a contiguous float32
         GPU tensor of frames * nk * ny * nx elements, may be None) is written on the slot's stream.  `keys` must stay alive and
         unmodified until then"""
-        import torch
         pimg = self._as_plane(image, 1)
         loc_out, status_out = self._scalars_out(loc_out, status_out)
-        pmaps = None
-        if maps_t is not None:
-            if not (maps_t.is_cuda and maps_t.dtype == torch.float32 and maps_t.is_contiguous()):
-                raise RuntimeError("maps_t must be a contiguous float32 GPU tensor")
-            pmaps = C.c_void_p(maps_t.data_ptr())
-        self._chk(lib().wm_locate_keys(self._ctx, int(maskType), C.byref(pimg), _keys_handle(keys), k0, nk, loc_out, pmaps, status_out, slot))
+        self._chk(lib().wm_locate_keys(self._ctx, int(maskType), C.byref(pimg), _keys_handle(keys), k0, nk, loc_out, self._f32_gpu(maps_t, "maps_t"),
+                                       status_out, slot))
 
     def locate_bits_async(self, image, keys, k, tile_rows, tile_cols, tile_bit, nbits, maskType, slot, loc_out, soft_out, energy_t=None,
                           maps_t=None, status_out=None):
@@ -1252,23 +1242,24 @@ class Watermark:
         loc_out (frames * 4 floats), soft_out (frames * nbits floats) and status_out (frames ints, may be None) are written by
         sync(slot); energy_t (frames * ny * nx) and maps_t (frames * nbits * ny * nx), contiguous float32 GPU tensors that may be
         None, on the slot's stream.  `keys` must stay alive and unmodified until then"""
-        import torch
         pimg = self._as_plane(image, 1)
+        tb = self._key_tile_table(keys, tile_rows, tile_cols, tile_bit)
+        loc_out, status_out = self._scalars_out(loc_out, status_out)
+        soft_out, _ = self._scalars_out(soft_out, None)
+        self._chk(lib().wm_locate_bits(self._ctx, int(maskType), C.byref(pimg), _keys_handle(keys), k, tile_rows, tile_cols,
+                                       tb.ctypes.data_as(C.c_void_p) if tb is not None else None, nbits, loc_out, soft_out,
+                                       self._f32_gpu(energy_t, "energy_t"), self._f32_gpu(maps_t, "maps_t"), status_out, slot))
+
+    @staticmethod
+    def _key_tile_table(keys, tile_rows, tile_cols, tile_bit):
+        """tile_bit as a flat int32 array with one entry per tile of the KEY plane (a tile shape the library refuses, and None, pass
+        through to its own refusal)"""
         tb = np.ascontiguousarray(tile_bit, np.int32).reshape(-1) if tile_bit is not None else None
         if tb is not None and keys is not None:
             tny, tnx = C.c_int(), C.c_int()
             if lib().wm_tiles_shape(keys.rows, keys.cols, tile_rows, tile_cols, C.byref(tny), C.byref(tnx)) == WM_OK and tb.size != tny.value * tnx.value:
                 raise RuntimeError(f"tile_bit must hold {tny.value * tnx.value} entries, got {tb.size}")
-        loc_out, status_out = self._scalars_out(loc_out, status_out)
-        soft_out, _ = self._scalars_out(soft_out, None)
-        ptrs = []
-        for t in (energy_t, maps_t):
-            if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-                raise RuntimeError("energy_t and maps_t must be contiguous float32 GPU tensors")
-            ptrs.append(C.c_void_p(t.data_ptr()) if t is not None else None)
-        self._chk(lib().wm_locate_bits(self._ctx, int(maskType), C.byref(pimg), _keys_handle(keys), k, tile_rows, tile_cols,
-                                       tb.ctypes.data_as(C.c_void_p) if tb is not None else None, nbits, loc_out, soft_out, ptrs[0], ptrs[1],
-                                       status_out, slot))
+        return tb
 
     @staticmethod
     def _f32_gpu(t, what, n=None):
@@ -1304,11 +1295,7 @@ class Watermark:
     def locate_bits_pooled_async(self, pool_t, keys, k, tile_rows, tile_cols, tile_bit, nbits, slot, loc_out, soft_out, energy_t=None, maps_t=None):
         """wm_locate_bits_pooled enqueued on `slot`: tile_bit is read before the call returns; loc_out (4 floats) and soft_out (nbits
         floats) are written by sync(slot), energy_t (ny * nx) and maps_t (nbits * ny * nx), which may be None, on the slot's stream"""
-        tb = np.ascontiguousarray(tile_bit, np.int32).reshape(-1) if tile_bit is not None else None
-        if tb is not None and keys is not None:
-            tny, tnx = C.c_int(), C.c_int()
-            if lib().wm_tiles_shape(keys.rows, keys.cols, tile_rows, tile_cols, C.byref(tny), C.byref(tnx)) == WM_OK and tb.size != tny.value * tnx.value:
-                raise RuntimeError(f"tile_bit must hold {tny.value * tnx.value} entries, got {tb.size}")
+        tb = self._key_tile_table(keys, tile_rows, tile_cols, tile_bit)
         loc_out, _ = self._scalars_out(loc_out, None)
         soft_out, _ = self._scalars_out(soft_out, None)
         self._chk(lib().wm_locate_bits_pooled(self._ctx, self._f32_gpu(pool_t, "pool_t", self.rows * self.cols), _keys_handle(keys), k, tile_rows,

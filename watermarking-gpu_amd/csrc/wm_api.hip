@@ -14,6 +14,7 @@
 #include <cstring>
 #include <deque>
 #include <fstream>
+#include <functional>
 #include <limits>
 #include <memory>
 #include <mutex>
@@ -99,6 +100,28 @@ struct Pending {
     float* coef_out;  // host destination for 8*frames coefficients (mask-only ops)
 };
 
+// the scratch of one call of the locate family inside one allocation (loc_layout): the twiddle tables of the [pr][pc] transform, the
+// frames' spectra hs [kept] (transposed; null: the call keeps none), planes a (work: h, its spectrum's way back, the map), kw (the
+// key side's spectrum, transposed) and p (the product; the plane a key is laid into), the frame's e and m, and what only some calls
+// have (null: not in this layout): the energy map and the per-bit maps of a wm_locate_bits call that passes none, the block records
+// (wm_locate: one map's; wm_locate_keys: the two halves' of one (pair, frame), whose fold runs before the next one's map pass;
+// wm_locate_bits: the bits' [frames][pairs][blocks]), the energy's block records [frames][blocks], the per-key non-zero flags.
+// Every member is 8 bytes wide or one of a pair of ints: two layouts are compared as bytes
+struct LocScratch {
+    int pr, pc;
+    float *tw_r, *tw_c, *hs, *a, *kw, *p, *e, *m, *energy, *maps;
+    char *part, *epart;
+    int* nz;
+    size_t plane_floats;
+};
+// one allocation of that scratch; at: the layout on a null base that its tables were last filled for (loc_scratch)
+struct LocAlloc {
+    void* p = nullptr;
+    size_t bytes = 0;
+    LocScratch at{};
+};
+enum { LOC_PLAIN, LOC_BITS, LOC_KEYS, LOC_KINDS };  // wm_locate, wm_locate_bits, wm_locate_keys, each with its pooled call
+
 struct Slot {
     hipStream_t own = nullptr, stream = nullptr;
     void* arena = nullptr;  // the one device allocation behind the scratch arrays below (alloc_slots)
@@ -176,18 +199,9 @@ struct Slot {
     // wm_quality: k_quality's records [planes][nsegs][ngroups][3] f64 and the folds' [planes][nsegs][nx][3], then the tile sums [planes][ny * nx][5] f64 of a call that
     // passes no sums_dev (grown on demand)
     void* qual_scr = nullptr; size_t qual_scr_bytes = 0;
-    // wm_locate: three [pr][pc] complex f32 planes, the frame's e and m planes, the two twiddle tables and the peak records (LocScratch;
-    // grown on demand).  loc_pr x loc_pc: the transform its layout and tables are for
-    void* loc_scr = nullptr; size_t loc_scr_bytes = 0;
-    int loc_pr = 0, loc_pc = 0;
-    // wm_locate_bits: frames + 3 complex planes, the e and m planes, the tables, the energy map and the per-bit maps of a call that
-    // passes none, and the block records (LocBitsScratch; grown on demand).  locb_key: the shapes its layout and tables are for
-    void* locb_scr = nullptr; size_t locb_scr_bytes = 0;
-    long long locb_key[6] = {0, 0, 0, 0, 0, 0};
-    // wm_locate_keys: frames + 3 complex planes, the e and m planes, the tables, the block records of one pair and the per-key
-    // non-zero flags (LocKeysScratch; its own allocation, grown on demand).  lock_key: the shapes its layout and tables are for
-    void* lock_scr = nullptr; size_t lock_scr_bytes = 0;
-    long long lock_key[3] = {0, 0, 0};
+    // the locate family's scratch (LocScratch; grown on demand), one allocation per call kind: calls of different kinds alternate
+    // on a slot without moving each other's layout, which would make every one of them wait for the stream
+    LocAlloc loc[LOC_KINDS];
 };
 
 struct ProfRec { int kid; hipEvent_t a, b; bool first; };  // first: the sweep's first launch (counts the call)
@@ -391,8 +405,8 @@ void free_slot(Slot& s)
     (void)hipFree(s.st_in); (void)hipFree(s.st_base); (void)hipFree(s.st_out); (void)hipFree(s.fz_block); (void)hipFree(s.d_ho); (void)hipFree(s.d_hoseam);
     (void)hipFree(s.d_hodig); (void)hipFree(s.keys_part); (void)hipFree(s.ekeys_part); (void)hipFree(s.tiles_rec); (void)hipFree(s.keys_tiles_rec);
     if (s.tab_host) (void)hipHostFree(s.tab_host);
-    (void)hipFree(s.tab_dev); (void)hipFree(s.bits_scr); (void)hipFree(s.x16); (void)hipFree(s.y16); (void)hipFree(s.qual_scr); (void)hipFree(s.loc_scr);
-    (void)hipFree(s.locb_scr); (void)hipFree(s.lock_scr);
+    (void)hipFree(s.tab_dev); (void)hipFree(s.bits_scr); (void)hipFree(s.x16); (void)hipFree(s.y16); (void)hipFree(s.qual_scr);
+    for (LocAlloc& al : s.loc) (void)hipFree(al.p);
     s = Slot();
 }
 
@@ -1859,95 +1873,185 @@ int wm_locate_shape(int rows, int cols, int key_rows, int key_cols, int* ny, int
 }
 
 namespace {
-// the slot's wm_locate scratch as one allocation: planes a (h, its spectrum, the map), b (transposes), w (the key's spectrum,
-// transposed), then e, m, the tables and the peak records
-struct LocScratch {
-    float *a, *b, *w, *e, *m, *tw_r, *tw_c;
-    void* part;
-    size_t bytes;
+// what a call of the locate family asks of its scratch: the transform and offset shape, the frames' spectra it keeps (0: wm_locate,
+// which finishes a frame before it starts the next), the bytes of its block records, and the bytes of the areas that only some calls
+// have (0: none): the energy's per-frame records, the energy map and the per-bit maps of a wm_locate_bits call that passes none, the
+// non-zero flags of wm_locate_keys
+struct LocShape {
+    int pr, pc, ny, nx, kept;
+    size_t part, epart, energy, maps, nz;
 };
-LocScratch loc_layout(void* base, int rows, int cols, int pr, int pc, int ny, int nx)
+// LocScratch over one allocation at `base`; returns its bytes.  base null: the areas' offsets, what loc_scratch compares
+size_t loc_layout(void* base, int rows, int cols, const LocShape& sh, LocScratch* L)
 {
-    const size_t plane = (size_t)pr * pc * 2 * sizeof(float), img = round256((size_t)rows * cols * sizeof(float));
+    const size_t plane = (size_t)sh.pr * sh.pc * 2 * sizeof(float), img = round256((size_t)rows * cols * sizeof(float));
     char* p = (char*)base;
-    LocScratch L;
-    L.a = (float*)p; p += plane;
-    L.b = (float*)p; p += plane;
-    L.w = (float*)p; p += plane;
-    L.e = (float*)p; p += img;
-    L.m = (float*)p; p += img;
-    L.tw_r = (float*)p; p += round256((size_t)pr * 2 * sizeof(float));
-    L.tw_c = (float*)p; p += round256((size_t)pc * 2 * sizeof(float));
-    L.part = p; p += round256(locate_part_bytes(ny, nx));
-    L.bytes = (size_t)(p - (char*)base);
-    return L;
+    const auto take = [&p](size_t bytes) { char* q = bytes ? p : nullptr; p += round256(bytes); return q; };
+    L->pr = sh.pr; L->pc = sh.pc;
+    L->plane_floats = (size_t)sh.pr * sh.pc * 2;
+    L->tw_r = (float*)take((size_t)(sh.pr + sh.pc) * 2 * sizeof(float));
+    L->tw_c = L->tw_r + (size_t)2 * sh.pr;
+    L->hs = (float*)take(plane * sh.kept);
+    L->a = (float*)take(plane);
+    L->kw = (float*)take(plane);
+    L->p = (float*)take(plane);
+    L->e = (float*)take(img);
+    L->m = (float*)take(img);
+    L->energy = (float*)take(sh.energy);
+    L->maps = (float*)take(sh.maps);
+    L->part = take(sh.part);
+    L->epart = take(sh.epart);
+    L->nz = (int*)take(sh.nz);
+    return (size_t)(p - (char*)base);
 }
 
 // forward 2-D transform of the [pr][pc] plane `a`; the spectrum lands TRANSPOSED ([pc][pr]) in `t`
-void fft2_forward_t(hipStream_t st, float* a, float* t, int pr, int pc, const float* tw_r, const float* tw_c)
+void fft2_forward_t(hipStream_t st, const LocScratch& L, float* a, float* t)
 {
-    launch_fft_rows(st, a, pr, pc, tw_c, false);
-    launch_fft_transpose(st, a, t, pr, pc);
-    launch_fft_rows(st, t, pc, pr, tw_r, false);
+    launch_fft_rows(st, a, L.pr, L.pc, L.tw_c, false);
+    launch_fft_transpose(st, a, t, L.pr, L.pc);
+    launch_fft_rows(st, t, L.pc, L.pr, L.tw_r, false);
 }
 // inverse 2-D transform of a transposed spectrum `t` ([pc][pr]); the plane lands in `a` ([pr][pc])
-void fft2_inverse_t(hipStream_t st, float* t, float* a, int pr, int pc, const float* tw_r, const float* tw_c)
+void fft2_inverse_t(hipStream_t st, const LocScratch& L, float* t, float* a)
 {
-    launch_fft_rows(st, t, pc, pr, tw_r, true);
-    launch_fft_transpose(st, t, a, pc, pr);
-    launch_fft_rows(st, a, pr, pc, tw_c, true);
+    launch_fft_rows(st, t, L.pc, L.pr, L.tw_r, true);
+    launch_fft_transpose(st, t, a, L.pc, L.pr);
+    launch_fft_rows(st, a, L.pr, L.pc, L.tw_c, true);
 }
-}  // namespace
 
-namespace {
-// the slot's wm_locate scratch for a transform shape, its tables filled: a new shape moves the layout under the calls still queued on
-// the slot, so it waits for them
-int loc_scratch(wm_ctx* ctx, Slot& s, int pr, int pc, int ny, int nx, LocScratch* L)
+// the slot's scratch of one call kind for a call's shape, its tables filled.  THE RESHAPE RULE: the calls still queued on the slot
+// hold the pointers of the layout they were given and read its tables, and the tables are filled by a blocking copy.  So whenever
+// the transform shape or the offset of any area differs from the layout the allocation was last filled for, or the allocation has
+// to grow, the call first waits for the slot's stream, then moves the layout and fills the tables again; in every other case it
+// takes the allocation as it is and waits for nothing.  (The size of the LAST area moves no pointer: a wm_locate call whose key has
+// another number of offsets under the same transform does not wait)
+int loc_scratch(wm_ctx* ctx, Slot& s, int kind, const LocShape& sh, LocScratch* L)
 {
     int rc;
-    const size_t need = loc_layout(nullptr, ctx->rows, ctx->cols, pr, pc, ny, nx).bytes;
-    const bool reshape = s.loc_pr != pr || s.loc_pc != pc || s.loc_scr_bytes < need;
+    LocAlloc& al = s.loc[kind];
+    LocScratch at{};
+    const size_t need = loc_layout(nullptr, ctx->rows, ctx->cols, sh, &at);
+    const bool reshape = std::memcmp(&at, &al.at, sizeof at) != 0 || al.bytes < need;
     if (reshape) {
         HIPCHK(ctx, hipStreamSynchronize(s.stream));
-        s.loc_pr = s.loc_pc = 0;
-        if ((rc = ensure(ctx, &s.loc_scr, &s.loc_scr_bytes, need, WM_ERR_ALLOC)) != WM_OK) return rc;
+        al.at = LocScratch{};
+        if ((rc = ensure(ctx, &al.p, &al.bytes, need, WM_ERR_ALLOC)) != WM_OK) return rc;
     }
-    *L = loc_layout(s.loc_scr, ctx->rows, ctx->cols, pr, pc, ny, nx);
+    loc_layout(al.p, ctx->rows, ctx->cols, sh, L);
     if (reshape) {
-        std::vector<float> tw((size_t)2 * std::max(pr, pc));
-        fft_twiddles(pr, tw.data());
-        HIPCHK(ctx, hipMemcpy(L->tw_r, tw.data(), (size_t)pr * 2 * sizeof(float), hipMemcpyHostToDevice));
-        fft_twiddles(pc, tw.data());
-        HIPCHK(ctx, hipMemcpy(L->tw_c, tw.data(), (size_t)pc * 2 * sizeof(float), hipMemcpyHostToDevice));
-        s.loc_pr = pr; s.loc_pc = pc;
+        HIPCHK(ctx, fft_twiddles_upload(L->tw_r, sh.pr, sh.pc));
+        al.at = at;
     }
     return WM_OK;
 }
-// the key's spectrum, once per call (transposed, in L.w)
-void locate_key_spectrum(Slot& s, const LocScratch& L, const wm_keys* keys, int k, int pr, int pc)
+
+// the call's own copy of `count` host ints in the slot's table arena (the caller's array is free when the call returns; count 0: no
+// table), and behind it, where `zero` is asked for, a DEVICE int that holds 0 for the call's kernels: the status of a pooled plane,
+// which has no solve of its own.  Both in ONE request, for a call takes table room once: a second request may move the arenas and
+// free the block the first pointer lies in
+int call_ints(wm_ctx* ctx, Slot& s, const int32_t* src, int count, const int** dev, const int** zero)
 {
-    launch_locate_key(s.stream, keys->d + (size_t)k * keys->rows * keys->cols, keys->rows, keys->cols, L.b, pr, pc);
-    fft2_forward_t(s.stream, L.b, L.w, pr, pc, L.tw_r, L.tw_c);
-}
-// wm_locate's tail of one image-side plane h laid into L.a: its spectrum, conj(H) Wf, back, the map and its four numbers
-void locate_tail(Slot& s, const LocScratch& L, int pr, int pc, int ny, int nx, const int* status, float* map, OpResult* res)
-{
-    fft2_forward_t(s.stream, L.a, L.b, pr, pc, L.tw_r, L.tw_c);
-    launch_locate_mul(s.stream, L.b, L.w, (size_t)pr * pc);
-    fft2_inverse_t(s.stream, L.b, L.a, pr, pc, L.tw_r, L.tw_c);
-    launch_locate_peak(s.stream, L.a, pr, pc, ny, nx, status, map, L.part, res);
-}
-// a DEVICE int that holds 0 for the call's kernels: the status of a pooled plane, which has no solve of its own (the slot's
-// table arena, as the tile tables).  A call takes table room ONCE: a second request may move the arenas under the first pointer
-int zero_status(wm_ctx* ctx, Slot& s, const int** status)
-{
+    int rc;
     void *th = nullptr, *td = nullptr;
-    int rc = table_room(ctx, s, sizeof(int), &th, &td);
-    if (rc != WM_OK) return rc;
-    *(int*)th = 0;
-    if ((rc = table_upload(ctx, s, th, td, sizeof(int))) != WM_OK) return rc;
-    *status = (const int*)td;
+    const size_t bytes = ((size_t)count + (zero ? 1 : 0)) * sizeof(int);
+    if ((rc = table_room(ctx, s, bytes, &th, &td)) != WM_OK) return rc;
+    if (count) std::memcpy(th, src, (size_t)count * sizeof(int));
+    if (zero) { ((int*)th)[count] = 0; *zero = (const int*)td + count; }
+    if ((rc = table_upload(ctx, s, th, td, bytes)) != WM_OK) return rc;
+    *dev = (const int*)td;
     return WM_OK;
+}
+
+// what the six calls of the family share in front of their image side: the geometry, and the refusals from the key range on.  Keys
+// k0 .. k0 + nk - 1 of the bank (`range`: the call takes a range, and says so); plane: the image plane, null for a pooled call,
+// which has one frame and no plane to check; per_frame, noun: the call's records per frame, as check_res_room words them
+struct LocCall { int ny, nx, pr, pc, frames; };
+int locate_front(wm_ctx* ctx, const std::string& who, const wm_plane* plane, const wm_keys* keys, int k0, int nk, bool range, long long per_frame,
+                 const char* noun, int slot, LocCall* c)
+{
+    int rc;
+    if (k0 < 0 || nk < 1 || (long long)k0 + nk > keys->nkeys)
+        return fail(ctx, WM_ERR_BAD_ARG, who + (range ? ": keys " + std::to_string(k0) + " .. " + std::to_string((long long)k0 + nk - 1) : ": key " + std::to_string(k0)) +
+                                             " of a bank of " + std::to_string(keys->nkeys));
+    if ((rc = check_bank(ctx, keys, who.c_str(), false)) != WM_OK) return rc;
+    if (wm_locate_shape(ctx->rows, ctx->cols, keys->rows, keys->cols, &c->ny, &c->nx, &c->pr, &c->pc) != WM_OK)
+        return fail(ctx, WM_ERR_BAD_ARG, who + ": a " + std::to_string(keys->rows) + "x" + std::to_string(keys->cols) +
+                                             " key plane needs a transform above " + std::to_string(1 << FFT_LOG_MAX) + " per axis");
+    if ((rc = refuse_band(ctx, who.c_str())) != WM_OK) return rc;
+    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    // (open_input checks the plane and the record room again: both have to be known HERE, in front of a call's own checks, of
+    // per_frame narrowed to an int, and of any device work)
+    if (plane && (rc = check_plane(ctx, plane, 0, false, "image", true)) != WM_OK) return rc;
+    c->frames = plane ? plane->frames : 1;
+    return check_res_room(ctx, slot_of(ctx, slot), c->frames * per_frame, noun);
+}
+
+// the image side of wm_locate, wm_locate_bits and wm_locate_keys: the Gram sweep and the solve (wm_detect_keys'), then the frames
+// one after the other: e (and m), h laid into L.a and, in a call that keeps the spectra, its forward transform into L.hs[f];
+// then(f): what the call does with frame f at once
+int locate_image_side(wm_ctx* ctx, Slot& s, const Sweep& sw, const wm_plane* img, const LocScratch& L, const std::function<void(int)>& then)
+{
+    const int rc = gram_sweep(ctx, s, sw, img);
+    if (rc != WM_OK) return rc;
+    for (int f = 0; f < sw.frames; ++f) {
+        launch_locate_e(sw, f, L.e, L.m);
+        launch_locate_h(sw, f, L.e, L.m, L.a, L.pr, L.pc);
+        if (L.hs) fft2_forward_t(s.stream, L, L.a, L.hs + f * L.plane_floats);
+        then(f);
+    }
+    return WM_OK;
+}
+// the image side of the pooled calls: a caller's pooled plane (wm_clip_pool) in the place of one frame's h -- a dense real plane, as
+// a key is --, and its spectrum where the call keeps one.  table (count ints; null, 0: none): the call's table; *status: the zero word
+int locate_pooled_side(wm_ctx* ctx, Slot& s, int kind, const LocShape& sh, const float* pool_dev, const int32_t* table, int count, LocScratch* L,
+                       const int** table_dev, const int** status)
+{
+    int rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if ((rc = loc_scratch(ctx, s, kind, sh, L)) != WM_OK) return rc;
+    if ((rc = call_ints(ctx, s, table, count, table_dev, status)) != WM_OK) return rc;
+    launch_locate_lay(s.stream, pool_dev, ctx->rows, ctx->cols, L->a, L->pr, L->pc);
+    if (L->hs) fft2_forward_t(s.stream, *L, L->a, L->hs);
+    return WM_OK;
+}
+
+// the device benches' clock: pass p is launch(p) once untimed, then `iters` times back to back between two events on the null
+// stream; us_out[p]: its mean microseconds per launch
+bool bench_passes(int passes, int iters, double* us_out, const std::function<void(int)>& launch)
+{
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    bool ok = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
+    for (int p = 0; ok && p < passes; ++p) {
+        for (int i = -1; i < iters; ++i) {  // (one untimed launch in front)
+            if (i == 0) ok = ok && hipEventRecord(e0, nullptr) == hipSuccess;
+            launch(p);
+        }
+        float ms = 0.f;
+        ok = ok && hipEventRecord(e1, nullptr) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess &&
+             hipGetLastError() == hipSuccess;
+        us_out[p] = (double)ms * 1e3 / iters;
+    }
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    return ok;
+}
+
+// wm_locate's scratch: three planes and the block records of one map
+LocShape locate_shape_of(const LocCall& c) { return LocShape{c.pr, c.pc, c.ny, c.nx, 0, locate_part_bytes(c.ny, c.nx), 0, 0, 0, 0}; }
+// the key's spectrum, once per call (transposed, in L.kw; L.p is the plane it is laid into)
+void locate_key_spectrum(Slot& s, const LocScratch& L, const wm_keys* keys, int k)
+{
+    launch_locate_lay(s.stream, keys->d + (size_t)k * keys->rows * keys->cols, keys->rows, keys->cols, L.p, L.pr, L.pc);
+    fft2_forward_t(s.stream, L, L.p, L.kw);
+}
+// wm_locate's tail of one image-side plane h laid into L.a: its spectrum, conj(H) Wf in place, back, the map and its four numbers
+void locate_tail(Slot& s, const LocScratch& L, const LocCall& c, const int* status, float* map, OpResult* res)
+{
+    fft2_forward_t(s.stream, L, L.a, L.p);
+    launch_locate_mul(s.stream, L.p, L.kw, (size_t)L.pr * L.pc);
+    fft2_inverse_t(s.stream, L, L.p, L.a);
+    launch_locate_map(s.stream, L.a, L.pr, L.pc, c.ny, c.nx, status, nullptr, false, map, nullptr, L.part, res);
 }
 }  // namespace
 
@@ -1957,30 +2061,21 @@ int wm_locate(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* keys, i
     int rc = check_mask(ctx, mask);
     if (rc != WM_OK) return rc;
     if (!img || !keys || (!loc_out && !map_dev)) return fail(ctx, WM_ERR_BAD_ARG, "wm_locate: null img or keys, or loc_out and map_dev both null");
-    if (k < 0 || k >= keys->nkeys) return fail(ctx, WM_ERR_BAD_ARG, "wm_locate: key " + std::to_string(k) + " of a bank of " + std::to_string(keys->nkeys));
-    if ((rc = check_bank(ctx, keys, "wm_locate", false)) != WM_OK) return rc;
-    int ny, nx, pr, pc;
-    if (wm_locate_shape(ctx->rows, ctx->cols, keys->rows, keys->cols, &ny, &nx, &pr, &pc) != WM_OK)
-        return fail(ctx, WM_ERR_BAD_ARG, "wm_locate: a " + std::to_string(keys->rows) + "x" + std::to_string(keys->cols) + " key plane needs a transform above " +
-                                             std::to_string(1 << FFT_LOG_MAX) + " per axis");
-    if ((rc = refuse_band(ctx, "wm_locate")) != WM_OK) return rc;
-    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    LocCall c;
+    if ((rc = locate_front(ctx, "wm_locate", img, keys, k, 1, false, WM_LOCATE_NVALS, "4 location records", slot, &c)) != WM_OK) return rc;
     Slot& s = slot_of(ctx, slot);
     Sweep sw;
     if ((rc = open_input(ctx, s, img, "image", mask, WM_LOCATE_NVALS, "4 location records", &sw)) != WM_OK) return rc;
-    const int frames = img->frames;
     LocScratch L;
-    if ((rc = loc_scratch(ctx, s, pr, pc, ny, nx, &L)) != WM_OK) return rc;
-    // the image side is wm_detect_keys': the Gram sweep and the solve
-    if ((rc = gram_sweep(ctx, s, sw, img)) != WM_OK) return rc;
-    locate_key_spectrum(s, L, keys, k, pr, pc);
-    // the frames one after the other: e (and m), h, then the tail
-    for (int f = 0; f < frames; ++f) {
-        launch_locate_e(sw, f, L.e, L.m);
-        launch_locate_h(sw, f, L.e, L.m, L.a, pr, pc);
-        locate_tail(s, L, pr, pc, ny, nx, s.d_status + f, map_dev ? map_dev + (size_t)f * ny * nx : nullptr, s.d_res + s.res_used + WM_LOCATE_NVALS * f);
-    }
-    return finish_call(ctx, s, slot, frames, WM_LOCATE_NVALS, false, loc_out, status_out);
+    if ((rc = loc_scratch(ctx, s, LOC_PLAIN, locate_shape_of(c), &L)) != WM_OK) return rc;
+    locate_key_spectrum(s, L, keys, k);
+    // frame-major: a frame's tail runs before the next frame's h takes L.a
+    const size_t n = (size_t)c.ny * c.nx;
+    rc = locate_image_side(ctx, s, sw, img, L, [&](int f) {
+        locate_tail(s, L, c, s.d_status + f, map_dev ? map_dev + f * n : nullptr, s.d_res + s.res_used + WM_LOCATE_NVALS * f);
+    });
+    if (rc != WM_OK) return rc;
+    return finish_call(ctx, s, slot, c.frames, WM_LOCATE_NVALS, false, loc_out, status_out);
 }
 
 // wm_locate's tail on a caller's pooled image-side plane (wm_clip_pool) in the place of one frame's h
@@ -1990,27 +2085,17 @@ int wm_locate_pooled(wm_ctx* ctx, const float* pool_dev, const wm_keys* keys, in
     int rc;
     if (!pool_dev || !keys || (!loc_out && !map_dev))
         return fail(ctx, WM_ERR_BAD_ARG, "wm_locate_pooled: null pool_dev or keys, or loc_out and map_dev both null");
-    if (k < 0 || k >= keys->nkeys)
-        return fail(ctx, WM_ERR_BAD_ARG, "wm_locate_pooled: key " + std::to_string(k) + " of a bank of " + std::to_string(keys->nkeys));
-    if ((rc = check_bank(ctx, keys, "wm_locate_pooled", false)) != WM_OK) return rc;
-    int ny, nx, pr, pc;
-    if (wm_locate_shape(ctx->rows, ctx->cols, keys->rows, keys->cols, &ny, &nx, &pr, &pc) != WM_OK)
-        return fail(ctx, WM_ERR_BAD_ARG, "wm_locate_pooled: a " + std::to_string(keys->rows) + "x" + std::to_string(keys->cols) +
-                                             " key plane needs a transform above " + std::to_string(1 << FFT_LOG_MAX) + " per axis");
-    if ((rc = refuse_band(ctx, "wm_locate_pooled")) != WM_OK) return rc;
-    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
+    LocCall c;
+    if ((rc = locate_front(ctx, "wm_locate_pooled", nullptr, keys, k, 1, false, WM_LOCATE_NVALS, "4 location records", slot, &c)) != WM_OK) return rc;
     Slot& s = slot_of(ctx, slot);
-    if ((rc = check_res_room(ctx, s, WM_LOCATE_NVALS, "4 location records")) != WM_OK) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
     LocScratch L;
-    if ((rc = loc_scratch(ctx, s, pr, pc, ny, nx, &L)) != WM_OK) return rc;
-    const int* status = nullptr;
-    if ((rc = zero_status(ctx, s, &status)) != WM_OK) return rc;
-    locate_key_spectrum(s, L, keys, k, pr, pc);
-    launch_locate_key(s.stream, pool_dev, ctx->rows, ctx->cols, L.a, pr, pc);  // (the pool in the place of h: a dense real plane)
-    locate_tail(s, L, pr, pc, ny, nx, status, map_dev, s.d_res + s.res_used);
+    const int *none = nullptr, *status = nullptr;
+    if ((rc = locate_pooled_side(ctx, s, LOC_PLAIN, locate_shape_of(c), pool_dev, nullptr, 0, &L, &none, &status)) != WM_OK) return rc;
+    locate_key_spectrum(s, L, keys, k);
+    locate_tail(s, L, c, status, map_dev, s.d_res + s.res_used);
     return finish_call(ctx, s, slot, 1, WM_LOCATE_NVALS, false, loc_out, nullptr);
 }
+
 
 // the frames of a clip pooled on the image side: wm_locate's Gram sweep and solve, then ONE launch of k_clip_pool
 int wm_clip_pool(wm_ctx* ctx, int mask, const wm_plane* img, const float* weights, float* pool_dev, int accumulate, int* status_out, int slot)
@@ -2060,34 +2145,23 @@ int wm_clip_pool_bench(int device, int rows, int cols, int frames, int mask, int
     // frames that differ: a hash of the index in 0 .. 255, as 8-bit pixels; coefficients 1/8 (a plain mean of the neighbours)
     std::vector<float> hx((size_t)frames * (img / sizeof(float)), 0.0f), hc((size_t)frames * 8, 0.125f), hw((size_t)frames, 1.0f);
     for (size_t i = 0; i < hx.size(); ++i) hx[i] = (float)(((i * 2654435761ull) >> 13) & 255);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
     bool ok = hipMemset(scr, 0, total) == hipSuccess && hipMemcpy(scr, hx.data(), hx.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(coef, hc.data(), hc.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(weights, hw.data(), hw.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
-              hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
+              hipMemcpy(weights, hw.data(), hw.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
     Sweep sw{};
     sw.s = nullptr; sw.lg.rows = rows; sw.lg.cols = cols; sw.frames = frames; sw.mask = mask; sw.pad = p / 2;
     sw.x = PlaneDesc{scr, cols, (long long)(img / sizeof(float)), 0, WM_F32, 1, 0};
     sw.coef = coef; sw.status = status;
-    for (int route = 0; ok && route < WM_CLIP_POOL_BENCH_ROUTES; ++route) {
-        for (int i = -1; i < iters; ++i) {  // (one untimed launch in front)
-            if (i == 0) ok = ok && hipEventRecord(e0, nullptr) == hipSuccess;
-            if (route == 0) launch_clip_pool(sw, weights, pool[0], false, res);
-            else launch_clip_pool_gather(sw, weights, pool[1], false, res);
-        }
-        float ms = 0.f;
-        ok = ok && hipEventRecord(e1, nullptr) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess &&
-             hipGetLastError() == hipSuccess;
-        us_out[route] = (double)ms * 1e3 / iters;
-    }
+    ok = ok && bench_passes(WM_CLIP_POOL_BENCH_ROUTES, iters, us_out, [&](int route) {
+             if (route == 0) launch_clip_pool(sw, weights, pool[0], false, res);
+             else launch_clip_pool_gather(sw, weights, pool[1], false, res);
+         });
     if (ok) {
         std::vector<float> a(n), b(n);
         ok = hipMemcpy(a.data(), pool[0], n * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess &&
              hipMemcpy(b.data(), pool[1], n * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess;
         *equal_out = ok && std::memcmp(a.data(), b.data(), n * sizeof(float)) == 0 ? 1 : 0;
     }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
     (void)hipFree(scr);
     return ok ? WM_OK : WM_ERR_RUNTIME;
 }
@@ -2102,10 +2176,7 @@ int wm_fft2(int device, float* data_dev, int pr, int pc, int inverse)
     if (hipMalloc((void**)&scr, plane + (size_t)(pr + pc) * 2 * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return WM_ERR_ALLOC; }
     float* tw_r = scr + (size_t)pr * pc * 2;
     float* tw_c = tw_r + (size_t)pr * 2;
-    std::vector<float> tw((size_t)2 * (pr + pc));
-    fft_twiddles(pr, tw.data());
-    fft_twiddles(pc, tw.data() + (size_t)2 * pr);
-    bool ok = hipMemcpy(tw_r, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
+    bool ok = fft_twiddles_upload(tw_r, pr, pc) == hipSuccess;
     if (ok) {
         // rows, transpose, rows (the columns), transpose back
         launch_fft_rows(nullptr, data_dev, pr, pc, tw_c, inverse != 0);
@@ -2132,32 +2203,18 @@ int wm_fft_bench(int device, int pr, int pc, int iters, double* us_out)
     float* b = scr + (size_t)pr * pc * 2;
     float* tw_r = b + (size_t)pr * pc * 2;
     float* tw_c = tw_r + (size_t)pr * 2;
-    std::vector<float> tw((size_t)2 * (pr + pc));
-    fft_twiddles(pr, tw.data());
-    fft_twiddles(pc, tw.data() + (size_t)2 * pr);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    bool ok = hipMemset(scr, 0, 2 * plane) == hipSuccess && hipMemcpy(tw_r, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
-              hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
-    for (int pass = 0; ok && pass < WM_FFT_BENCH_PASSES; ++pass) {
-        for (int i = -1; i < iters; ++i) {  // (one untimed launch in front)
-            if (i == 0) ok = ok && hipEventRecord(e0, nullptr) == hipSuccess;
-            switch (pass) {
-            case 0: launch_fft_rows(nullptr, a, pr, pc, tw_c, false); break;
-            case 1: launch_fft_transpose(nullptr, a, b, pr, pc); break;
-            case 2: launch_fft_rows(nullptr, b, pc, pr, tw_r, false); break;
-            case 3: launch_locate_mul(nullptr, b, a, (size_t)pr * pc); break;
-            case 4: launch_fft_rows(nullptr, b, pc, pr, tw_r, true); break;
-            case 5: launch_fft_transpose(nullptr, b, a, pc, pr); break;
-            default: launch_fft_rows(nullptr, a, pr, pc, tw_c, true); break;
-            }
-        }
-        float ms = 0.f;
-        ok = ok && hipEventRecord(e1, nullptr) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess &&
-             hipGetLastError() == hipSuccess;
-        us_out[pass] = (double)ms * 1e3 / iters;
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
+    const bool ok = hipMemset(scr, 0, 2 * plane) == hipSuccess && fft_twiddles_upload(tw_r, pr, pc) == hipSuccess &&
+                    bench_passes(WM_FFT_BENCH_PASSES, iters, us_out, [&](int pass) {
+                        switch (pass) {
+                        case 0: launch_fft_rows(nullptr, a, pr, pc, tw_c, false); break;
+                        case 1: launch_fft_transpose(nullptr, a, b, pr, pc); break;
+                        case 2: launch_fft_rows(nullptr, b, pc, pr, tw_r, false); break;
+                        case 3: launch_locate_mul(nullptr, b, a, (size_t)pr * pc); break;
+                        case 4: launch_fft_rows(nullptr, b, pc, pr, tw_r, true); break;
+                        case 5: launch_fft_transpose(nullptr, b, a, pc, pr); break;
+                        default: launch_fft_rows(nullptr, a, pr, pc, tw_c, true); break;
+                        }
+                    });
     (void)hipFree(scr);
     return ok ? WM_OK : WM_ERR_RUNTIME;
 }
@@ -2391,41 +2448,6 @@ int wm_detect_bits(wm_ctx* ctx, int mask, const wm_plane* img, int tile_rows, in
 }
 
 // ---- wm_locate_bits: a payload-marked crop found and read without a hint ---------------------------------
-namespace {
-// the slot's wm_locate_bits scratch as one allocation: the tables, the frames' spectra hs [frames] (transposed), planes a (work: h,
-// the key pair, the inverse), kw (the pair's spectrum, transposed) and p (the product), e and m, the energy map and the per-bit maps
-// (null when the caller passes its own), the bits' block records [frames][pairs][blocks] and the energy's [frames][blocks]
-struct LocBitsScratch {
-    float *tw_r, *tw_c, *hs, *a, *kw, *p, *e, *m, *energy, *maps;
-    char *part, *epart;
-    size_t plane_floats, part_stride, epart_stride, bytes;
-};
-LocBitsScratch locb_layout(void* base, int rows, int cols, int pr, int pc, int ny, int nx, int frames, int nbits, bool own_energy, bool own_maps)
-{
-    const size_t plane = (size_t)pr * pc * 2 * sizeof(float), img = round256((size_t)rows * cols * sizeof(float));
-    const size_t n = (size_t)ny * nx;
-    char* p = (char*)base;
-    LocBitsScratch L;
-    L.plane_floats = (size_t)pr * pc * 2;
-    L.tw_r = (float*)p; p += round256((size_t)pr * 2 * sizeof(float));
-    L.tw_c = (float*)p; p += round256((size_t)pc * 2 * sizeof(float));
-    L.hs = (float*)p; p += plane * frames;
-    L.a = (float*)p; p += plane;
-    L.kw = (float*)p; p += plane;
-    L.p = (float*)p; p += plane;
-    L.e = (float*)p; p += img;
-    L.m = (float*)p; p += img;
-    L.energy = own_energy ? (float*)p : nullptr; p += own_energy ? round256(n * frames * sizeof(float)) : 0;
-    L.maps = own_maps ? (float*)p : nullptr; p += own_maps ? round256(n * frames * nbits * sizeof(float)) : 0;
-    L.part_stride = locate_bits_part_bytes(ny, nx) * (size_t)((nbits + 1) / 2);
-    L.part = p; p += round256(L.part_stride * frames);
-    L.epart_stride = locate_part_bytes(ny, nx);
-    L.epart = p; p += round256(L.epart_stride * frames);
-    L.bytes = (size_t)(p - (char*)base);
-    return L;
-}
-}  // namespace
-
 int wm_locate_bits_cover(int rows, int cols, int key_rows, int key_cols, int tile_rows, int tile_cols, const int32_t* tile_bit, int nbits, int oy,
                          int ox, int64_t* pixels_out)
 {
@@ -2453,111 +2475,64 @@ int wm_locate_bits_cover(int rows, int cols, int key_rows, int key_cols, int til
 }
 
 namespace {
-// what wm_locate_bits and wm_locate_bits_pooled share in front of their image side: the geometry, the refusals from the key on
-// (`plane`: the image plane of wm_locate_bits, null for the pooled call, which has one frame and no plane to check)
-struct LocBitsCall { int ny, nx, pr, pc, frames; TileShape ts; long long per_frame; };
-int locate_bits_front(wm_ctx* ctx, const std::string& who, const wm_plane* plane, const wm_keys* keys, int k, int tile_rows, int tile_cols,
-                      const int32_t* tile_bit, int nbits, int slot, LocBitsCall* c)
+// what wm_locate_bits and wm_locate_bits_pooled check behind the family's front: the tile grid of the KEY plane and the table over
+// it; has: which bits have a tile at all
+struct LocBitsCall { LocCall c; TileShape ts; std::vector<char> has; };
+int locate_bits_checks(wm_ctx* ctx, const std::string& who, const wm_plane* plane, const wm_keys* keys, int k, int tile_rows, int tile_cols,
+                       const int32_t* tile_bit, int nbits, int slot, LocBitsCall* b)
 {
-    int rc;
-    if (k < 0 || k >= keys->nkeys) return fail(ctx, WM_ERR_BAD_ARG, who + ": key " + std::to_string(k) + " of a bank of " + std::to_string(keys->nkeys));
-    if ((rc = check_bank(ctx, keys, who.c_str(), false)) != WM_OK) return rc;
-    if (wm_locate_shape(ctx->rows, ctx->cols, keys->rows, keys->cols, &c->ny, &c->nx, &c->pr, &c->pc) != WM_OK)
-        return fail(ctx, WM_ERR_BAD_ARG, who + ": a " + std::to_string(keys->rows) + "x" + std::to_string(keys->cols) +
-                                             " key plane needs a transform above " + std::to_string(1 << FFT_LOG_MAX) + " per axis");
-    if ((rc = refuse_band(ctx, who.c_str())) != WM_OK) return rc;
-    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
-    Slot& s = slot_of(ctx, slot);
-    // (open_input checks the plane and the record room again: both have to be known HERE, in front of the table's checks and of any device work)
-    if (plane && (rc = check_plane(ctx, plane, 0, false, "image", true)) != WM_OK) return rc;
-    c->frames = plane ? plane->frames : 1;
-    c->per_frame = WM_LOCATE_BITS_NVALS + (long long)std::max(nbits, 0);
-    if ((rc = check_res_room(ctx, s, c->frames * c->per_frame, "(4 + bits)")) != WM_OK) return rc;
-    c->ts.th = tile_rows; c->ts.tw = tile_cols;
-    if (wm_tiles_shape(keys->rows, keys->cols, tile_rows, tile_cols, &c->ts.ny, &c->ts.nx) != WM_OK)
+    int rc = locate_front(ctx, who, plane, keys, k, 1, false, WM_LOCATE_BITS_NVALS + (long long)std::max(nbits, 0), "(4 + bits)", slot, &b->c);
+    if (rc != WM_OK) return rc;
+    b->ts.th = tile_rows; b->ts.tw = tile_cols;
+    if (wm_tiles_shape(keys->rows, keys->cols, tile_rows, tile_cols, &b->ts.ny, &b->ts.nx) != WM_OK)
         return fail(ctx, WM_ERR_BAD_ARG, who + ": tile shape " + std::to_string(tile_rows) + "x" + std::to_string(tile_cols) +
                                              " (rows: a multiple of 8, >= 32; columns: a multiple of 4, >= 32)");
-    return tile_bits_checked(ctx, who.c_str(), tile_bit, (long long)c->ts.ny * c->ts.nx, nbits);
-}
-
-// the slot's wm_locate_bits scratch for the call's shapes, its tables filled: another layout moves the planes under the calls still
-// queued on the slot, so it waits for them
-int locb_scratch(wm_ctx* ctx, Slot& s, const LocBitsCall& c, int nbits, bool own_energy, bool own_maps, LocBitsScratch* L)
-{
-    int rc;
-    const int pr = c.pr, pc = c.pc;
-    const long long key_now[6] = {((long long)pr << 32) | pc, ((long long)c.ny << 32) | c.nx, c.frames, nbits, own_energy ? 1 : 0, own_maps ? 1 : 0};
-    const size_t need = locb_layout(nullptr, ctx->rows, ctx->cols, pr, pc, c.ny, c.nx, c.frames, nbits, own_energy, own_maps).bytes;
-    const bool reshape = !std::equal(key_now, key_now + 6, s.locb_key) || s.locb_scr_bytes < need;
-    if (reshape) {
-        HIPCHK(ctx, hipStreamSynchronize(s.stream));
-        std::fill(s.locb_key, s.locb_key + 6, 0LL);
-        if ((rc = ensure(ctx, &s.locb_scr, &s.locb_scr_bytes, need, WM_ERR_ALLOC)) != WM_OK) return rc;
-    }
-    *L = locb_layout(s.locb_scr, ctx->rows, ctx->cols, pr, pc, c.ny, c.nx, c.frames, nbits, own_energy, own_maps);
-    if (reshape) {
-        std::vector<float> tw((size_t)2 * std::max(pr, pc));
-        fft_twiddles(pr, tw.data());
-        HIPCHK(ctx, hipMemcpy(L->tw_r, tw.data(), (size_t)pr * 2 * sizeof(float), hipMemcpyHostToDevice));
-        fft_twiddles(pc, tw.data());
-        HIPCHK(ctx, hipMemcpy(L->tw_c, tw.data(), (size_t)pc * 2 * sizeof(float), hipMemcpyHostToDevice));
-        std::copy(key_now, key_now + 6, s.locb_key);
-    }
-    return WM_OK;
-}
-
-// the call's own copy of the table (the caller's array is free when the call returns), and which bits have a tile at all.
-// zero_dev (may be null): a DEVICE int that holds 0 behind the table, zero_status' word -- taken in the SAME request as the table: a
-// second table_room may move the arenas and free the block the first pointer lies in
-int locate_bits_table(wm_ctx* ctx, Slot& s, const int32_t* tile_bit, int T, int nbits, const int** table_dev, std::vector<char>* has,
-                      const int** zero_dev = nullptr)
-{
-    int rc;
-    void *th = nullptr, *td = nullptr;
-    const size_t bytes = ((size_t)T + (zero_dev ? 1 : 0)) * sizeof(int);
-    if ((rc = table_room(ctx, s, bytes, &th, &td)) != WM_OK) return rc;
-    std::memcpy(th, tile_bit, (size_t)T * sizeof(int));
-    if (zero_dev) { ((int*)th)[T] = 0; *zero_dev = (const int*)td + T; }
-    has->assign((size_t)nbits + 1, 0);
+    const int T = b->ts.ny * b->ts.nx;
+    if ((rc = tile_bits_checked(ctx, who.c_str(), tile_bit, T, nbits)) != WM_OK) return rc;
+    b->has.assign((size_t)nbits + 1, 0);
     for (int t = 0; t < T; ++t)
-        if (tile_bit[t] >= 0) (*has)[(size_t)tile_bit[t]] = 1;
-    if ((rc = table_upload(ctx, s, th, td, bytes)) != WM_OK) return rc;
-    *table_dev = (const int*)td;
+        if (tile_bit[t] >= 0) b->has[(size_t)tile_bit[t]] = 1;
     return WM_OK;
+}
+// wm_locate_bits' scratch: the frames' spectra and three planes, the bits' block records [frames][pairs][blocks], the energy's
+// [frames][blocks], and the energy map and the per-bit maps where the caller passes none
+LocShape locate_bits_shape(const LocCall& c, int nbits, bool own_energy, bool own_maps)
+{
+    const size_t n = (size_t)c.ny * c.nx, F = (size_t)c.frames;
+    return LocShape{c.pr, c.pc, c.ny, c.nx, c.frames, locate_bits_part_bytes(c.ny, c.nx) * (size_t)((nbits + 1) / 2) * F, locate_part_bytes(c.ny, c.nx) * F,
+                    own_energy ? n * F * sizeof(float) : 0, own_maps ? n * F * nbits * sizeof(float) : 0, 0};
 }
 
 // wm_locate_bits' tail behind the frames' spectra in L.hs.  Pair-major: the pair's key plane and its spectrum once per call, then
 // per frame the product, the way back and the accumulate pass; behind the last pair the folds and the records: [frames][4] of the
 // energy map, then [frames][nbits] soft values.  status: the frames' DEVICE status words
-int locate_bits_tail(wm_ctx* ctx, Slot& s, int slot, const LocBitsCall& c, const LocBitsScratch& L, const wm_keys* keys, int k, const int* table_dev,
-                     const std::vector<char>& has, int nbits, const int* status, float* energy_dev, float* maps_dev, float* loc_out, float* soft_out,
-                     int* status_out)
+int locate_bits_tail(wm_ctx* ctx, Slot& s, int slot, const LocBitsCall& b, const LocScratch& L, const wm_keys* keys, int k, const int* table_dev, int nbits,
+                     const int* status, float* energy_dev, float* maps_dev, float* loc_out, float* soft_out, int* status_out)
 {
     int rc;
-    const int pr = c.pr, pc = c.pc, ny = c.ny, nx = c.nx, frames = c.frames;
+    const int pr = L.pr, pc = L.pc, ny = b.c.ny, nx = b.c.nx, frames = b.c.frames;
     const size_t n = (size_t)ny * nx, npl = (size_t)pr * pc;
     float* energy = energy_dev ? energy_dev : L.energy;
     float* maps = maps_dev ? maps_dev : L.maps;
     OpResult* res = s.d_res + s.res_used;
     const float* key = keys->d + (size_t)k * keys->rows * keys->cols;
     const int npairs = (nbits + 1) / 2;
-    const size_t blk_bytes = locate_bits_part_bytes(ny, nx);
+    const size_t blk_bytes = locate_bits_part_bytes(ny, nx), part_stride = blk_bytes * npairs, epart_stride = locate_part_bytes(ny, nx);
     for (int pi = 0; pi < npairs; ++pi) {
         const int b0 = 2 * pi, b1 = b0 + 1 < nbits ? b0 + 1 : -2;
-        launch_locate_key_pair(s.stream, key, keys->rows, keys->cols, table_dev, c.ts, b0, b1, L.a, pr, pc);
-        fft2_forward_t(s.stream, L.a, L.kw, pr, pc, L.tw_r, L.tw_c);
+        launch_locate_lay_bits(s.stream, key, keys->rows, keys->cols, table_dev, b.ts, b0, b1, L.a, pr, pc);
+        fft2_forward_t(s.stream, L, L.a, L.kw);
         for (int f = 0; f < frames; ++f) {
             launch_locate_mul3(s.stream, L.hs + f * L.plane_floats, L.kw, L.p, npl);
-            fft2_inverse_t(s.stream, L.p, L.a, pr, pc, L.tw_r, L.tw_c);
+            fft2_inverse_t(s.stream, L, L.p, L.a);
             float* mf = maps + (size_t)f * nbits * n;
-            launch_locate_bits_acc(s.stream, L.a, pr, pc, ny, nx, status + f, pi == 0, has[(size_t)b0] != 0, b1 >= 0 && has[(size_t)b1] != 0,
+            launch_locate_bits_acc(s.stream, L.a, pr, pc, ny, nx, status + f, pi == 0, b.has[(size_t)b0] != 0, b1 >= 0 && b.has[(size_t)b1] != 0,
                                    mf + (size_t)b0 * n, b1 >= 0 ? mf + (size_t)b1 * n : nullptr, energy + (size_t)f * n,
-                                   L.part + (size_t)f * L.part_stride + (size_t)pi * blk_bytes,
-                                   pi == npairs - 1 ? L.epart + (size_t)f * L.epart_stride : nullptr);
+                                   L.part + (size_t)f * part_stride + (size_t)pi * blk_bytes, pi == npairs - 1 ? L.epart + (size_t)f * epart_stride : nullptr);
         }
     }
     for (int f = 0; f < frames; ++f)
-        launch_locate_bits_fold(s.stream, L.epart + (size_t)f * L.epart_stride, L.part + (size_t)f * L.part_stride, ny, nx, nbits, energy + (size_t)f * n,
+        launch_locate_bits_fold(s.stream, L.epart + (size_t)f * epart_stride, L.part + (size_t)f * part_stride, ny, nx, nbits, energy + (size_t)f * n,
                                 maps + (size_t)f * nbits * n, status + f, res + WM_LOCATE_BITS_NVALS * f,
                                 res + WM_LOCATE_BITS_NVALS * frames + (size_t)f * nbits);
     if ((rc = launch_check(ctx, s)) != WM_OK) return rc;
@@ -2577,24 +2552,17 @@ int wm_locate_bits(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* ke
     if (rc != WM_OK) return rc;
     if (!img || !keys || !tile_bit || !loc_out || !soft_out)
         return fail(ctx, WM_ERR_BAD_ARG, "wm_locate_bits: null img, keys, tile_bit, loc_out or soft_out");
-    LocBitsCall c;
-    if ((rc = locate_bits_front(ctx, "wm_locate_bits", img, keys, k, tile_rows, tile_cols, tile_bit, nbits, slot, &c)) != WM_OK) return rc;
+    LocBitsCall b;
+    if ((rc = locate_bits_checks(ctx, "wm_locate_bits", img, keys, k, tile_rows, tile_cols, tile_bit, nbits, slot, &b)) != WM_OK) return rc;
     Slot& s = slot_of(ctx, slot);
     Sweep sw;
-    if ((rc = open_input(ctx, s, img, "image", mask, c.per_frame, "(4 + bits)", &sw)) != WM_OK) return rc;
-    LocBitsScratch L;
-    if ((rc = locb_scratch(ctx, s, c, nbits, !energy_dev, !maps_dev, &L)) != WM_OK) return rc;
+    if ((rc = open_input(ctx, s, img, "image", mask, WM_LOCATE_BITS_NVALS + nbits, "(4 + bits)", &sw)) != WM_OK) return rc;
+    LocScratch L;
+    if ((rc = loc_scratch(ctx, s, LOC_BITS, locate_bits_shape(b.c, nbits, !energy_dev, !maps_dev), &L)) != WM_OK) return rc;
     const int* table_dev = nullptr;
-    std::vector<char> has;
-    if ((rc = locate_bits_table(ctx, s, tile_bit, c.ts.ny * c.ts.nx, nbits, &table_dev, &has)) != WM_OK) return rc;
-    // the image side is wm_locate's: the Gram sweep and the solve, then every frame's e (and m), h and its spectrum, kept
-    if ((rc = gram_sweep(ctx, s, sw, img)) != WM_OK) return rc;
-    for (int f = 0; f < c.frames; ++f) {
-        launch_locate_e(sw, f, L.e, L.m);
-        launch_locate_h(sw, f, L.e, L.m, L.a, c.pr, c.pc);
-        fft2_forward_t(s.stream, L.a, L.hs + f * L.plane_floats, c.pr, c.pc, L.tw_r, L.tw_c);
-    }
-    return locate_bits_tail(ctx, s, slot, c, L, keys, k, table_dev, has, nbits, s.d_status, energy_dev, maps_dev, loc_out, soft_out, status_out);
+    if ((rc = call_ints(ctx, s, tile_bit, b.ts.ny * b.ts.nx, &table_dev, nullptr)) != WM_OK) return rc;
+    if ((rc = locate_image_side(ctx, s, sw, img, L, [](int) {})) != WM_OK) return rc;
+    return locate_bits_tail(ctx, s, slot, b, L, keys, k, table_dev, nbits, s.d_status, energy_dev, maps_dev, loc_out, soft_out, status_out);
 }
 
 // wm_locate_bits' tail on a caller's pooled image-side plane (wm_clip_pool) in the place of one frame's h
@@ -2605,20 +2573,17 @@ int wm_locate_bits_pooled(wm_ctx* ctx, const float* pool_dev, const wm_keys* key
     int rc;
     if (!pool_dev || !keys || !tile_bit || !loc_out || !soft_out)
         return fail(ctx, WM_ERR_BAD_ARG, "wm_locate_bits_pooled: null pool_dev, keys, tile_bit, loc_out or soft_out");
-    LocBitsCall c;
-    if ((rc = locate_bits_front(ctx, "wm_locate_bits_pooled", nullptr, keys, k, tile_rows, tile_cols, tile_bit, nbits, slot, &c)) != WM_OK) return rc;
+    LocBitsCall b;
+    if ((rc = locate_bits_checks(ctx, "wm_locate_bits_pooled", nullptr, keys, k, tile_rows, tile_cols, tile_bit, nbits, slot, &b)) != WM_OK) return rc;
     Slot& s = slot_of(ctx, slot);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    LocBitsScratch L;
-    if ((rc = locb_scratch(ctx, s, c, nbits, !energy_dev, !maps_dev, &L)) != WM_OK) return rc;
-    const int* table_dev = nullptr;
-    std::vector<char> has;
-    const int* status = nullptr;  // (ONE request of table room for the table and the zero word)
-    if ((rc = locate_bits_table(ctx, s, tile_bit, c.ts.ny * c.ts.nx, nbits, &table_dev, &has, &status)) != WM_OK) return rc;
-    launch_locate_key(s.stream, pool_dev, ctx->rows, ctx->cols, L.a, c.pr, c.pc);  // (the pool in the place of h: a dense real plane)
-    fft2_forward_t(s.stream, L.a, L.hs, c.pr, c.pc, L.tw_r, L.tw_c);
-    return locate_bits_tail(ctx, s, slot, c, L, keys, k, table_dev, has, nbits, status, energy_dev, maps_dev, loc_out, soft_out, nullptr);
+    LocScratch L;
+    const int *table_dev = nullptr, *status = nullptr;
+    if ((rc = locate_pooled_side(ctx, s, LOC_BITS, locate_bits_shape(b.c, nbits, !energy_dev, !maps_dev), pool_dev, tile_bit, b.ts.ny * b.ts.nx, &L, &table_dev,
+                                 &status)) != WM_OK)
+        return rc;
+    return locate_bits_tail(ctx, s, slot, b, L, keys, k, table_dev, nbits, status, energy_dev, maps_dev, loc_out, soft_out, nullptr);
 }
+
 
 // the three passes wm_locate_bits adds to wm_fft_bench's seven, timed the same way: the key-pair plane (128 x 128 tiles over a key
 // of the transform's size), the three-operand product, and the accumulate pass of a later pair over ny x nx offsets
@@ -2638,24 +2603,13 @@ int wm_locate_bits_bench(int device, int pr, int pc, int ny, int nx, int iters, 
     char* p0 = scr + 3 * plane + 3 * n;
     int* table = (int*)(p0 + 2 * part);
     int* status = (int*)(p0 + 2 * part + tab);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    bool ok = hipMemset(scr, 0, total) == hipSuccess && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
-    for (int pass = 0; ok && pass < WM_LOCATE_BITS_BENCH_PASSES; ++pass) {
-        for (int i = -1; i < iters; ++i) {  // (one untimed launch in front)
-            if (i == 0) ok = ok && hipEventRecord(e0, nullptr) == hipSuccess;
-            switch (pass) {
-            case 0: launch_locate_key_pair(nullptr, a, pr, pc, table, ts, 0, 1, b, pr, pc); break;
-            case 1: launch_locate_mul3(nullptr, a, b, c, (size_t)pr * pc); break;
-            default: launch_locate_bits_acc(nullptr, c, pr, pc, ny, nx, status, false, true, true, m0, m1, en, p0, p0 + part); break;
-            }
+    const bool ok = hipMemset(scr, 0, total) == hipSuccess && bench_passes(WM_LOCATE_BITS_BENCH_PASSES, iters, us_out, [&](int pass) {
+        switch (pass) {
+        case 0: launch_locate_lay_bits(nullptr, a, pr, pc, table, ts, 0, 1, b, pr, pc); break;
+        case 1: launch_locate_mul3(nullptr, a, b, c, (size_t)pr * pc); break;
+        default: launch_locate_bits_acc(nullptr, c, pr, pc, ny, nx, status, false, true, true, m0, m1, en, p0, p0 + part); break;
         }
-        float ms = 0.f;
-        ok = ok && hipEventRecord(e1, nullptr) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess &&
-             hipGetLastError() == hipSuccess;
-        us_out[pass] = (double)ms * 1e3 / iters;
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
+    });
     (void)hipFree(scr);
     return ok ? WM_OK : WM_ERR_RUNTIME;
 }
@@ -2663,109 +2617,36 @@ int wm_locate_bits_bench(int device, int pr, int pc, int ny, int nx, int iters, 
 // ---- wm_locate_keys: whose key is in a crop, and where ----------------------------------------------------
 namespace {
 constexpr int LOCK_MAX_KEYS = RES_CAP / WM_LOCATE_KEYS_NVALS;  // (more keys than this never pass the record-room check)
-// the slot's wm_locate_keys scratch as one allocation: the tables, the frames' spectra hs [frames] (transposed), planes a (work: h,
-// the key pair, the inverse), kw (the pair's spectrum, transposed) and p (the product), e and m, the block records of the two halves
-// of one (pair, frame) -- its fold runs before the next one's map pass -- and the per-key non-zero flags
-struct LocKeysScratch {
-    float *tw_r, *tw_c, *hs, *a, *kw, *p, *e, *m;
-    char* part;
-    int* nz;
-    size_t plane_floats, bytes;
-};
-LocKeysScratch lock_layout(void* base, int rows, int cols, int pr, int pc, int ny, int nx, int frames)
+// wm_locate_keys' scratch: the frames' spectra and three planes, the block records of the two halves of one (pair, frame), and the
+// per-key non-zero flags (+ 1: the flag of the odd last key's missing partner)
+LocShape locate_keys_shape(const LocCall& c)
 {
-    const size_t plane = (size_t)pr * pc * 2 * sizeof(float), img = round256((size_t)rows * cols * sizeof(float));
-    char* p = (char*)base;
-    LocKeysScratch L;
-    L.plane_floats = (size_t)pr * pc * 2;
-    L.tw_r = (float*)p; p += round256((size_t)pr * 2 * sizeof(float));
-    L.tw_c = (float*)p; p += round256((size_t)pc * 2 * sizeof(float));
-    L.hs = (float*)p; p += plane * frames;
-    L.a = (float*)p; p += plane;
-    L.kw = (float*)p; p += plane;
-    L.p = (float*)p; p += plane;
-    L.e = (float*)p; p += img;
-    L.m = (float*)p; p += img;
-    L.part = p; p += round256(2 * locate_part_bytes(ny, nx));
-    L.nz = (int*)p; p += round256((size_t)(LOCK_MAX_KEYS + 1) * sizeof(int));  // (+ 1: the flag of the odd last key's missing partner)
-    L.bytes = (size_t)(p - (char*)base);
-    return L;
-}
-}  // namespace
-
-namespace {
-// what wm_locate_keys and wm_locate_keys_pooled share in front of their image side: the geometry, the refusals from the key range
-// on (`plane`: the image plane of wm_locate_keys, null for the pooled call, which has one frame and no plane to check)
-struct LocKeysCall { int ny, nx, pr, pc, frames; long long per_frame; };
-int locate_keys_front(wm_ctx* ctx, const std::string& who, const wm_plane* plane, const wm_keys* keys, int k0, int nk, int slot, LocKeysCall* c)
-{
-    int rc;
-    if (k0 < 0 || nk < 1 || (long long)k0 + nk > keys->nkeys)
-        return fail(ctx, WM_ERR_BAD_ARG, who + ": keys " + std::to_string(k0) + " .. " + std::to_string((long long)k0 + nk - 1) + " of a bank of " +
-                                             std::to_string(keys->nkeys));
-    if ((rc = check_bank(ctx, keys, who.c_str(), false)) != WM_OK) return rc;
-    if (wm_locate_shape(ctx->rows, ctx->cols, keys->rows, keys->cols, &c->ny, &c->nx, &c->pr, &c->pc) != WM_OK)
-        return fail(ctx, WM_ERR_BAD_ARG, who + ": a " + std::to_string(keys->rows) + "x" + std::to_string(keys->cols) +
-                                             " key plane needs a transform above " + std::to_string(1 << FFT_LOG_MAX) + " per axis");
-    if ((rc = refuse_band(ctx, who.c_str())) != WM_OK) return rc;
-    if ((rc = check_slot(ctx, slot)) != WM_OK) return rc;
-    Slot& s = slot_of(ctx, slot);
-    // (open_input checks the plane and the record room again: the room has to be known before per_frame is narrowed to an int)
-    if (plane && (rc = check_plane(ctx, plane, 0, false, "image", true)) != WM_OK) return rc;
-    c->frames = plane ? plane->frames : 1;
-    c->per_frame = (long long)WM_LOCATE_KEYS_NVALS * nk;
-    return check_res_room(ctx, s, c->frames * c->per_frame, "(4 x keys)");
+    return LocShape{c.pr, c.pc, c.ny, c.nx, c.frames, 2 * locate_part_bytes(c.ny, c.nx), 0, 0, 0, (size_t)(LOCK_MAX_KEYS + 1) * sizeof(int)};
 }
 
-// the slot's wm_locate_keys scratch for the call's shapes, its tables filled: another layout moves the planes under the calls still
-// queued on the slot, so it waits for them
-int lock_scratch(wm_ctx* ctx, Slot& s, const LocKeysCall& c, LocKeysScratch* L)
+// wm_locate_keys' tail behind the frames' spectra in L.hs.  Pair-major: the pair's plane and its spectrum once per call, then per
+// frame the product, the way back, the maps and the records.  status: the frames' DEVICE status words
+int locate_keys_tail(wm_ctx* ctx, Slot& s, int slot, const LocCall& c, const LocScratch& L, const wm_keys* keys, int k0, int nk, const int* status,
+                     float* loc_out, float* maps_dev, int* status_out)
 {
-    int rc;
-    const int pr = c.pr, pc = c.pc;
-    const long long key_now[3] = {((long long)pr << 32) | pc, ((long long)c.ny << 32) | c.nx, c.frames};
-    const size_t need = lock_layout(nullptr, ctx->rows, ctx->cols, pr, pc, c.ny, c.nx, c.frames).bytes;
-    const bool reshape = !std::equal(key_now, key_now + 3, s.lock_key) || s.lock_scr_bytes < need;
-    if (reshape) {
-        HIPCHK(ctx, hipStreamSynchronize(s.stream));
-        std::fill(s.lock_key, s.lock_key + 3, 0LL);
-        if ((rc = ensure(ctx, &s.lock_scr, &s.lock_scr_bytes, need, WM_ERR_ALLOC)) != WM_OK) return rc;
-    }
-    *L = lock_layout(s.lock_scr, ctx->rows, ctx->cols, pr, pc, c.ny, c.nx, c.frames);
-    if (reshape) {
-        std::vector<float> tw((size_t)2 * std::max(pr, pc));
-        fft_twiddles(pr, tw.data());
-        HIPCHK(ctx, hipMemcpy(L->tw_r, tw.data(), (size_t)pr * 2 * sizeof(float), hipMemcpyHostToDevice));
-        fft_twiddles(pc, tw.data());
-        HIPCHK(ctx, hipMemcpy(L->tw_c, tw.data(), (size_t)pc * 2 * sizeof(float), hipMemcpyHostToDevice));
-        std::copy(key_now, key_now + 3, s.lock_key);
-    }
-    return WM_OK;
-}
-
-// wm_locate_keys' tail behind the frames' spectra in L.hs (L.nz cleared on the stream beforehand).  Pair-major: the pair's plane and
-// its spectrum once per call, then per frame the product, the way back, the maps and the records.  status: the frames' DEVICE
-// status words
-int locate_keys_tail(wm_ctx* ctx, Slot& s, int slot, const LocKeysCall& c, const LocKeysScratch& L, const wm_keys* keys, int k0, int nk,
-                     const int* status, float* loc_out, float* maps_dev, int* status_out)
-{
-    const int pr = c.pr, pc = c.pc, ny = c.ny, nx = c.nx, frames = c.frames;
-    const size_t n = (size_t)ny * nx, npl = (size_t)pr * pc, key_elems = (size_t)keys->rows * keys->cols;
+    const int pr = L.pr, pc = L.pc, frames = c.frames;
+    const size_t n = (size_t)c.ny * c.nx, npl = (size_t)pr * pc, key_elems = (size_t)keys->rows * keys->cols;
     OpResult* res = s.d_res + s.res_used;
+    HIPCHK(ctx, hipMemsetAsync(L.nz, 0, (size_t)(nk + 1) * sizeof(int), s.stream));
     for (int j = 0; j < nk; j += 2) {
         const bool pair = j + 1 < nk;
         const float* ka = keys->d + (size_t)(k0 + j) * key_elems;
-        launch_locate_keys_pair(s.stream, ka, pair ? ka + key_elems : nullptr, keys->rows, keys->cols, L.a, pr, pc, L.nz + j);
-        fft2_forward_t(s.stream, L.a, L.kw, pr, pc, L.tw_r, L.tw_c);
+        launch_locate_lay_keys(s.stream, ka, pair ? ka + key_elems : nullptr, keys->rows, keys->cols, L.a, pr, pc, L.nz + j);
+        fft2_forward_t(s.stream, L, L.a, L.kw);
         for (int f = 0; f < frames; ++f) {
             launch_locate_mul3(s.stream, L.hs + f * L.plane_floats, L.kw, L.p, npl);
-            fft2_inverse_t(s.stream, L.p, L.a, pr, pc, L.tw_r, L.tw_c);
+            fft2_inverse_t(s.stream, L, L.p, L.a);
             float* mf = maps_dev ? maps_dev + ((size_t)f * nk + j) * n : nullptr;
-            launch_locate_keys_peak(s.stream, L.a, pr, pc, ny, nx, status + f, L.nz + j, pair, mf, mf && pair ? mf + n : nullptr, L.part,
-                                    res + ((size_t)f * nk + j) * WM_LOCATE_KEYS_NVALS);
+            launch_locate_map(s.stream, L.a, pr, pc, c.ny, c.nx, status + f, L.nz + j, pair, mf, mf && pair ? mf + n : nullptr, L.part,
+                              res + ((size_t)f * nk + j) * WM_LOCATE_KEYS_NVALS);
         }
     }
-    return finish_call(ctx, s, slot, frames, (int)c.per_frame, false, loc_out, status_out);
+    return finish_call(ctx, s, slot, frames, WM_LOCATE_KEYS_NVALS * nk, false, loc_out, status_out);
 }
 }  // namespace
 
@@ -2779,21 +2660,14 @@ int wm_locate_keys(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys* ke
     int rc = check_mask(ctx, mask);
     if (rc != WM_OK) return rc;
     if (!img || !keys || (!loc_out && !maps_dev)) return fail(ctx, WM_ERR_BAD_ARG, "wm_locate_keys: null img or keys, or loc_out and maps_dev both null");
-    LocKeysCall c;
-    if ((rc = locate_keys_front(ctx, "wm_locate_keys", img, keys, k0, nk, slot, &c)) != WM_OK) return rc;
+    LocCall c;
+    if ((rc = locate_front(ctx, "wm_locate_keys", img, keys, k0, nk, true, (long long)WM_LOCATE_KEYS_NVALS * nk, "(4 x keys)", slot, &c)) != WM_OK) return rc;
     Slot& s = slot_of(ctx, slot);
     Sweep sw;
-    if ((rc = open_input(ctx, s, img, "image", mask, (int)c.per_frame, "(4 x keys)", &sw)) != WM_OK) return rc;
-    LocKeysScratch L;
-    if ((rc = lock_scratch(ctx, s, c, &L)) != WM_OK) return rc;
-    HIPCHK(ctx, hipMemsetAsync(L.nz, 0, (size_t)(nk + 1) * sizeof(int), s.stream));
-    // the image side is wm_locate's: the Gram sweep and the solve, then every frame's e (and m), h and its spectrum, kept
-    if ((rc = gram_sweep(ctx, s, sw, img)) != WM_OK) return rc;
-    for (int f = 0; f < c.frames; ++f) {
-        launch_locate_e(sw, f, L.e, L.m);
-        launch_locate_h(sw, f, L.e, L.m, L.a, c.pr, c.pc);
-        fft2_forward_t(s.stream, L.a, L.hs + f * L.plane_floats, c.pr, c.pc, L.tw_r, L.tw_c);
-    }
+    if ((rc = open_input(ctx, s, img, "image", mask, WM_LOCATE_KEYS_NVALS * nk, "(4 x keys)", &sw)) != WM_OK) return rc;
+    LocScratch L;
+    if ((rc = loc_scratch(ctx, s, LOC_KEYS, locate_keys_shape(c), &L)) != WM_OK) return rc;
+    if ((rc = locate_image_side(ctx, s, sw, img, L, [](int) {})) != WM_OK) return rc;
     return locate_keys_tail(ctx, s, slot, c, L, keys, k0, nk, s.d_status, loc_out, maps_dev, status_out);
 }
 
@@ -2804,19 +2678,16 @@ int wm_locate_keys_pooled(wm_ctx* ctx, const float* pool_dev, const wm_keys* key
     int rc;
     if (!pool_dev || !keys || (!loc_out && !maps_dev))
         return fail(ctx, WM_ERR_BAD_ARG, "wm_locate_keys_pooled: null pool_dev or keys, or loc_out and maps_dev both null");
-    LocKeysCall c;
-    if ((rc = locate_keys_front(ctx, "wm_locate_keys_pooled", nullptr, keys, k0, nk, slot, &c)) != WM_OK) return rc;
+    LocCall c;
+    if ((rc = locate_front(ctx, "wm_locate_keys_pooled", nullptr, keys, k0, nk, true, (long long)WM_LOCATE_KEYS_NVALS * nk, "(4 x keys)", slot, &c)) != WM_OK)
+        return rc;
     Slot& s = slot_of(ctx, slot);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    LocKeysScratch L;
-    if ((rc = lock_scratch(ctx, s, c, &L)) != WM_OK) return rc;
-    HIPCHK(ctx, hipMemsetAsync(L.nz, 0, (size_t)(nk + 1) * sizeof(int), s.stream));
-    const int* status = nullptr;
-    if ((rc = zero_status(ctx, s, &status)) != WM_OK) return rc;
-    launch_locate_key(s.stream, pool_dev, ctx->rows, ctx->cols, L.a, c.pr, c.pc);  // (the pool in the place of h: a dense real plane)
-    fft2_forward_t(s.stream, L.a, L.hs, c.pr, c.pc, L.tw_r, L.tw_c);
+    LocScratch L;
+    const int *none = nullptr, *status = nullptr;
+    if ((rc = locate_pooled_side(ctx, s, LOC_KEYS, locate_keys_shape(c), pool_dev, nullptr, 0, &L, &none, &status)) != WM_OK) return rc;
     return locate_keys_tail(ctx, s, slot, c, L, keys, k0, nk, status, loc_out, maps_dev, nullptr);
 }
+
 
 int wm_locate_keys_rank(const float* loc, int nk, int* best, float* z_best, float* z_next)
 {
@@ -2856,21 +2727,10 @@ int wm_locate_keys_bench(int device, int pr, int pc, int ny, int nx, int iters, 
     char* p0 = scr + 2 * plane + 2 * n;
     int* nz = (int*)(p0 + part);
     int* status = nz + 2;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    bool ok = hipMemset(scr, 0, total) == hipSuccess && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
-    for (int pass = 0; ok && pass < WM_LOCATE_KEYS_BENCH_PASSES; ++pass) {
-        for (int i = -1; i < iters; ++i) {  // (one untimed launch in front)
-            if (i == 0) ok = ok && hipEventRecord(e0, nullptr) == hipSuccess;
-            if (pass == 0) launch_locate_keys_pair(nullptr, a, a + (size_t)pr * pc, pr, pc, b, pr, pc, nz);
-            else launch_locate_keys_peak(nullptr, b, pr, pc, ny, nx, status, nz, true, m0, m1, p0, nullptr);
-        }
-        float ms = 0.f;
-        ok = ok && hipEventRecord(e1, nullptr) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess &&
-             hipGetLastError() == hipSuccess;
-        us_out[pass] = (double)ms * 1e3 / iters;
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
+    const bool ok = hipMemset(scr, 0, total) == hipSuccess && bench_passes(WM_LOCATE_KEYS_BENCH_PASSES, iters, us_out, [&](int pass) {
+        if (pass == 0) launch_locate_lay_keys(nullptr, a, a + (size_t)pr * pc, pr, pc, b, pr, pc, nz);
+        else launch_locate_map(nullptr, b, pr, pc, ny, nx, status, nz, true, m0, m1, p0, nullptr);
+    });
     (void)hipFree(scr);
     return ok ? WM_OK : WM_ERR_RUNTIME;
 }

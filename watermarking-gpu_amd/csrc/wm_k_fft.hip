@@ -5,6 +5,7 @@
 // ([pc][pr]); wm_locate multiplies and starts the inverse in that layout, so a forward and an inverse transform need one transpose
 // each.  Every workgroup works on its own rows or tile: no waits between workgroups, no atomics, a fixed order of operations.
 #include "wm_kernels.hpp"
+#include <vector>
 
 namespace wmk {
 
@@ -170,6 +171,14 @@ void fft_twiddles(int P, float* out)
         out[2 * t] = (float)cos(step * t);
         out[2 * t + 1] = (float)sin(step * t);
     }
+}
+
+hipError_t fft_twiddles_upload(float* tw_dev, int pr, int pc)
+{
+    std::vector<float> tw((size_t)2 * (pr + pc));
+    fft_twiddles(pr, tw.data());
+    fft_twiddles(pc, tw.data() + (size_t)2 * pr);
+    return hipMemcpy(tw_dev, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice);
 }
 
 void launch_fft_rows(hipStream_t s, float* data, int nrows, int P, const float* tw, bool inverse)

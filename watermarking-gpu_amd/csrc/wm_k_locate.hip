@@ -1,11 +1,12 @@
-// wm_k_locate.hip -- the image and key side of wm_locate around the transform of wm_k_fft.hip: k_locate_e (the frame's prediction
-// error and NVF mask), k_locate_h (h = m * F^T e_w, the exact adjoint of the replicate-border stencil, laid into a zeroed complex
-// plane), k_locate_key (the key plane laid out the same way), k_locate_peak and k_locate_fold (the map and its four numbers); and
-// of wm_locate_bits: k_locate_key_pair (the key masked to the tiles of two payload bits, one per half of a complex plane),
-// k_locate_bits_acc (the two maps, the energy map and their block folds) and k_locate_bits_fold (the records); and of wm_locate_keys:
-// k_locate_keys_pair (two keys of a bank, one per half of a complex plane, and a flag per key that is not all zero),
-// k_locate_keys_peak (the two maps and their block folds) and k_locate_keys_fold (the records of the two keys); and of
-// wm_clip_pool: k_clip_pool (the frames of a clip pooled into one image-side plane, h formed by k_locate_e's and k_locate_h's helpers).
+// wm_k_locate.hip -- the image and key side of the locate family around the transform of wm_k_fft.hip.  Image side: k_locate_e (the
+// frame's prediction error and NVF mask), k_locate_h (h = m * F^T e_w, the exact adjoint of the replicate-border stencil, laid into
+// a zeroed complex plane) and, for wm_clip_pool, k_clip_pool (the frames of a clip pooled into one image-side plane, h formed by
+// k_locate_e's and k_locate_h's helpers).  Key side: k_locate_lay, one kernel body over three sources -- a dense real plane (a key of
+// wm_locate, or a pool), a key masked to the tiles of two payload bits (wm_locate_bits), two keys of a bank with a flag per key that
+// is not all zero (wm_locate_keys) --, one source per half of a complex plane.  Behind the inverse transform: k_locate_map (one map,
+// or the two of a pair, and their block folds) and k_locate_records (a map's four numbers) for wm_locate and wm_locate_keys;
+// k_locate_bits_acc (the two maps, the energy map and their block folds) and k_locate_bits_fold (the records) for wm_locate_bits.
+// All of them fold through the same pieces: peak_take, peak_tree, peak_fold, peak_z_around, peak_records.
 //
 // With c solved, the detector's numerator is linear in W: <e_u, e_w>(oy, ox) = sum_q h(q) W(q + (oy, ox)), one 2-D cross-correlation
 // of h with the key plane.  Every workgroup works on its own pixels or its own chunk of the map; the fold
@@ -18,7 +19,7 @@ namespace {
 
 constexpr int LB = 256;          // threads per workgroup
 constexpr int LTX = 64, LTY = 4; // ... as 64 columns x 4 rows of pixels
-constexpr int PEAK_PER = 16;     // map values per thread of k_locate_peak: a workgroup folds 4096 consecutive values
+constexpr int PEAK_PER = 16;     // map values per thread of k_locate_map: a workgroup folds 4096 consecutive values
 
 __device__ __forceinline__ int clampi(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
 
@@ -254,13 +255,60 @@ __global__ __launch_bounds__(LB) void k_clip_pool_gather(const T* __restrict__ x
     pool[(size_t)r * cols + c] = acc;
 }
 
-// k_locate_key: the key plane [key_rows][key_cols] as the real part of a zeroed [pr][pc] complex plane
-__global__ __launch_bounds__(LB) void k_locate_key(const float* __restrict__ key, int key_rows, int key_cols, float2* __restrict__ plane, int pc)
+// ---- k_locate_lay: a real source laid into a zeroed [pr][pc] complex plane, (0, 0) outside the source's rows x cols.  The source is
+// a functor: src(r, c, i), i = r * cols + c, gives the plane's element of source pixel (r, c); FLAGS: the kernel also raises src.nz.
+// Its members arrive as plain kernel arguments and it is put together in the kernel: pointers that come inside a struct argument
+// are addressed as flat ones, which costs registers
+
+// one dense real plane as the real part: a key of wm_locate, or a pooled image side in the place of h
+struct LayPlane {
+    static constexpr bool FLAGS = false;
+    const float* key;
+    __device__ __forceinline__ float2 operator()(int, int, size_t i) const { return make_float2(key[i], 0.0f); }
+};
+// wm_locate_bits: (key [tb(tile) == b0], key [tb(tile) == b1]).  The tiles lie on the KEY plane by the rule of wm_tiles_shape: tile
+// (min(r / th, tny - 1), min(c / tw, tnx - 1)), the last one of an axis takes the remainder.  b1 = -2 (no entry of the table is below
+// -1): the odd last bit rides alone
+struct LayBits {
+    static constexpr bool FLAGS = false;
+    const float* key;
+    const int* tb;
+    int th, tw, tny, tnx, b0, b1;
+    __device__ __forceinline__ float2 operator()(int r, int c, size_t i) const
+    {
+        const int bit = tb[min(r / th, tny - 1) * tnx + min(c / tw, tnx - 1)];
+        const float w = key[i];
+        return make_float2(bit == b0 ? w : 0.0f, bit == b1 ? w : 0.0f);
+    }
+};
+// wm_locate_keys: (keyA, keyB); keyB null: the odd last key rides alone.  nz[0] / nz[1] (cleared on the stream at the start of the
+// call) is set to 1 by every workgroup that saw a value of key A / key B other than 0: the workgroups store the same value, a later
+// kernel on the stream reads it
+struct LayKeys {
+    static constexpr bool FLAGS = true;
+    const float *keyA, *keyB;
+    int* nz;
+    __device__ __forceinline__ float2 operator()(int, int, size_t i) const { return make_float2(keyA[i], keyB ? keyB[i] : 0.0f); }
+};
+
+template <typename Src, typename... A>
+__global__ __launch_bounds__(LB) void k_locate_lay(int rows, int cols, float2* __restrict__ plane, int pc, A... a)
 {
-    const int c = blockIdx.x * LTX + threadIdx.x % LTX, r = blockIdx.y * LTY + threadIdx.x / LTX;
-    const float v = r < key_rows && c < key_cols ? key[(size_t)r * key_cols + c] : 0.0f;
-    plane[(size_t)r * pc + c] = make_float2(v, 0.0f);
+    const Src src{a...};
+    const int c = blockIdx.x * LTX + threadIdx.x % LTX, r = blockIdx.y * LTY + threadIdx.x / LTX;  // (the grid covers pr x pc exactly)
+    float2 v = make_float2(0.0f, 0.0f);
+    if (r < rows && c < cols) v = src(r, c, (size_t)r * cols + c);
+    plane[(size_t)r * pc + c] = v;
+    if constexpr (Src::FLAGS) {
+        const int anyA = __syncthreads_or(v.x != 0.0f), anyB = __syncthreads_or(v.y != 0.0f);
+        if (threadIdx.x == 0) {
+            if (anyA) src.nz[0] = 1;
+            if (anyB) src.nz[1] = 1;
+        }
+    }
 }
+
+// ---- the fold of a map: records, their tree, the z rule ---------------------------------------------------------------------------
 
 // one block's or one frame's fold: argmax (ties to the smallest index), sum and sum of squares in f64
 struct PeakRec {
@@ -270,6 +318,15 @@ struct PeakRec {
     int pad;
 };
 __device__ __forceinline__ bool peak_better(float v, long long i, float bv, long long bi) { return v > bv || (v == bv && i < bi); }
+// map value v at index i as a record of its own, and the record of nothing (idx -1)
+__device__ __forceinline__ PeakRec peak_of(float v, long long i) { return PeakRec{(double)v, (double)v * (double)v, i, v, 0}; }
+__device__ __forceinline__ PeakRec peak_none() { return PeakRec{0.0, 0.0, -1, 0.0f, 0}; }
+// record o taken into the running record me
+__device__ __forceinline__ void peak_take(PeakRec& me, const PeakRec& o)
+{
+    me.sum += o.sum; me.sumsq += o.sumsq;
+    if (o.idx >= 0 && (me.idx < 0 || peak_better(o.val, o.idx, me.val, me.idx))) { me.val = o.val; me.idx = o.idx; }
+}
 
 // a workgroup's 256 records folded pairwise in a fixed tree; the result is in s_rec[0]
 __device__ __forceinline__ void peak_tree(PeakRec* s_rec, int t)
@@ -277,14 +334,20 @@ __device__ __forceinline__ void peak_tree(PeakRec* s_rec, int t)
     for (int half = LB / 2; half > 0; half >>= 1) {
         __syncthreads();
         if (t < half) {
-            const PeakRec o = s_rec[t + half];
             PeakRec me = s_rec[t];
-            me.sum += o.sum; me.sumsq += o.sumsq;
-            if (o.idx >= 0 && (me.idx < 0 || peak_better(o.val, o.idx, me.val, me.idx))) { me.val = o.val; me.idx = o.idx; }
+            peak_take(me, s_rec[t + half]);
             s_rec[t] = me;
         }
     }
     __syncthreads();
+}
+// a workgroup's fold of the nblk block records of one map: thread t takes t, t + 256, ... in ascending order, then the tree
+__device__ __forceinline__ void peak_fold(const PeakRec* __restrict__ part, int nblk, PeakRec* s_rec, int t)
+{
+    PeakRec me = peak_none();
+    for (int b = t; b < nblk; b += LB) peak_take(me, part[b]);
+    s_rec[t] = me;
+    peak_tree(s_rec, t);
 }
 
 // z of a peak against the offsets that remain in (sum, sumsq, cnt) once the 3 x 3 block around it is taken out: (val - mu) / sigma in
@@ -299,89 +362,100 @@ __device__ __forceinline__ float peak_z(double sum, double sumsq, long long cnt,
     }
     return z;
 }
-
-// k_locate_peak: map value i * nx + j = Re plane[i][j] * scale over the ny x nx admissible offsets (scale = 1 / (pr pc): the
-// transforms are not normalised), stored to map when it is given; workgroup b folds values [4096 b, 4096 (b + 1)) into part[b].
-// An unsolvable frame's map is zero
-__global__ __launch_bounds__(LB) void k_locate_peak(const float2* __restrict__ plane, int pc, int ny, int nx, float scale,
-                                                    const int* __restrict__ status, float* __restrict__ map, PeakRec* __restrict__ part)
+// ... with (sum, sumsq) still over all ny x nx offsets: the values at(i, j) of the 3 x 3 block around (oy, ox) are taken out first
+template <typename At>
+__device__ __forceinline__ float peak_z_around(double sum, double sumsq, int oy, int ox, int ny, int nx, float val, At&& at)
 {
-    __shared__ PeakRec s_rec[LB];
+    long long cnt = (long long)ny * nx;
+    for (int i = max(oy - 1, 0); i <= min(oy + 1, ny - 1); ++i)
+        for (int j = max(ox - 1, 0); j <= min(ox + 1, nx - 1); ++j) {
+            const double v = (double)at(i, j);
+            sum -= v; sumsq -= v * v; --cnt;
+        }
+    return peak_z(sum, sumsq, cnt, val);
+}
+// the four records {oy, ox, peak, z} of a map; an unsolvable frame (st != 0): its status and zeros
+__device__ __forceinline__ void peak_records(OpResult* __restrict__ res, int st, int oy, int ox, float val, float z)
+{
+    res[0] = OpResult{st, st ? 0.0f : (float)oy};
+    res[1] = OpResult{st, st ? 0.0f : (float)ox};
+    res[2] = OpResult{st, st ? 0.0f : val};
+    res[3] = OpResult{st, st ? 0.0f : z};
+}
+
+// the value of one half of a complex plane at an offset: the product with 1 / (pr pc), or exactly zero for a half that carries no
+// key (its flag is clear, or the odd last key has no partner) -- not the rounding residue of the other half
+__device__ __forceinline__ float keys_half(const float2 v, int half, float scale, bool use) { return use ? (half ? v.y : v.x) * scale : 0.0f; }
+
+// k_locate_map: the ny x nx admissible offsets of an inverse plane times scale = 1 / (pr pc) (the transforms are not normalised): the
+// real parts are key A's map and, under PAIR, the imaginary parts key B's (mapA / mapB null: not stored).  Workgroup b folds values
+// [4096 b, 4096 (b + 1)) of each map into partA[b] / partB[b].  nz: the pair's flags (k_locate_lay), null: key A is in use (wm_locate).
+// Without PAIR there is no second half: no load, no record, no LDS for it.  An unsolvable frame's maps are zero
+template <bool PAIR>
+__global__ __launch_bounds__(LB) void k_locate_map(const float2* __restrict__ plane, int pc, int ny, int nx, float scale, const int* __restrict__ status,
+                                                   const int* __restrict__ nz, float* __restrict__ mapA, float* __restrict__ mapB,
+                                                   PeakRec* __restrict__ partA, PeakRec* __restrict__ partB)
+{
+    __shared__ PeakRec s_rec[PAIR ? 2 : 1][LB];
     const int t = threadIdx.x;
     const long long n = (long long)ny * nx;
     const long long i0 = (long long)blockIdx.x * (LB * PEAK_PER);
     const bool dead = status[0] != 0;
-    PeakRec me{0.0, 0.0, -1, 0.0f, 0};
+    const bool useA = !nz || nz[0] != 0, useB = PAIR && nz[1] != 0;
+    PeakRec a = peak_none(), b = peak_none();
 #pragma unroll 4
     for (int k = 0; k < PEAK_PER; ++k) {
         const long long i = i0 + t + (long long)k * LB;
         if (i >= n) break;
         const int oy = (int)(i / nx), ox = (int)(i % nx);
-        const float v = dead ? 0.0f : plane[(size_t)oy * pc + ox].x * scale;
-        if (map) map[i] = v;
-        me.sum += (double)v; me.sumsq += (double)v * (double)v;
-        if (me.idx < 0 || peak_better(v, i, me.val, me.idx)) { me.val = v; me.idx = i; }
+        float2 v = make_float2(0.0f, 0.0f);
+        if (!dead) {
+            if (PAIR) v = plane[(size_t)oy * pc + ox];
+            else v.x = plane[(size_t)oy * pc + ox].x;
+        }
+        const float re = keys_half(v, 0, scale, useA);
+        if (mapA) mapA[i] = re;
+        peak_take(a, peak_of(re, i));
+        if (PAIR) {
+            const float im = keys_half(v, 1, scale, useB);
+            if (mapB) mapB[i] = im;
+            peak_take(b, peak_of(im, i));
+        }
     }
-    s_rec[t] = me;
-    peak_tree(s_rec, t);
-    if (t == 0) part[blockIdx.x] = s_rec[0];
+    s_rec[0][t] = a;
+    peak_tree(s_rec[0], t);
+    if (t == 0) partA[blockIdx.x] = s_rec[0][0];
+    if constexpr (PAIR) {
+        s_rec[1][t] = b;
+        peak_tree(s_rec[1], t);
+        if (t == 0) partB[blockIdx.x] = s_rec[1][0];
+    }
 }
 
-// k_locate_fold: one workgroup folds the nblk records of a frame (thread t takes t, t + 256, ... in ascending order, then the tree),
-// takes the values of the 3 x 3 block around the argmax out of the sums, and writes the frame's four records
-// {oy, ox, peak, z}: z = (peak - mu) / sigma over the offsets outside that block (population sigma, f64), NaN when fewer than two
-// offsets lie outside it or sigma is 0.  An unsolvable frame: status 1 and zeros
-__global__ __launch_bounds__(LB) void k_locate_fold(const PeakRec* __restrict__ part, int nblk, const float2* __restrict__ plane, int pc, int ny,
-                                                    int nx, float scale, const int* __restrict__ status, OpResult* __restrict__ res)
+// k_locate_records: workgroup h folds the nblk block records of half h of a (pair, frame) (part + h * nblk; grid 1: key A alone),
+// takes the values of the 3 x 3 block around the argmax out of the sums -- formed as k_locate_map formed them, so they are the map's
+// bits -- and writes the half's four records {oy, ox, peak, z} to res + 4 h: z = (peak - mu) / sigma over the offsets outside that
+// block (peak_z).  nz as in k_locate_map
+__global__ __launch_bounds__(LB) void k_locate_records(const PeakRec* __restrict__ part, int nblk, const float2* __restrict__ plane, int pc, int ny,
+                                                       int nx, float scale, const int* __restrict__ status, const int* __restrict__ nz,
+                                                       OpResult* __restrict__ res)
 {
     __shared__ PeakRec s_rec[LB];
-    const int t = threadIdx.x;
-    PeakRec me{0.0, 0.0, -1, 0.0f, 0};
-    for (int b = t; b < nblk; b += LB) {
-        const PeakRec o = part[b];
-        me.sum += o.sum; me.sumsq += o.sumsq;
-        if (o.idx >= 0 && (me.idx < 0 || peak_better(o.val, o.idx, me.val, me.idx))) { me.val = o.val; me.idx = o.idx; }
-    }
-    s_rec[t] = me;
-    peak_tree(s_rec, t);
+    const int t = threadIdx.x, half = (int)blockIdx.x;
+    peak_fold(part + (size_t)half * nblk, nblk, s_rec, t);
     if (t != 0) return;
     const int st = status[0];
-    if (st != 0) {
-        for (int k = 0; k < 4; ++k) res[k] = OpResult{st, 0.0f};
-        return;
-    }
+    const bool use = !nz || nz[half] != 0;
     const PeakRec tot = s_rec[0];
     const int oy = (int)(tot.idx / nx), ox = (int)(tot.idx % nx);
-    double sum = tot.sum, sumsq = tot.sumsq;
-    long long cnt = (long long)ny * nx;
-    for (int i = max(oy - 1, 0); i <= min(oy + 1, ny - 1); ++i)
-        for (int j = max(ox - 1, 0); j <= min(ox + 1, nx - 1); ++j) {
-            const double v = (double)(plane[(size_t)i * pc + j].x * scale);
-            sum -= v; sumsq -= v * v; --cnt;
-        }
-    res[0] = OpResult{0, (float)oy};
-    res[1] = OpResult{0, (float)ox};
-    res[2] = OpResult{0, tot.val};
-    res[3] = OpResult{0, peak_z(sum, sumsq, cnt, tot.val)};
+    float z = 0.0f;
+    if (st == 0)
+        z = peak_z_around(tot.sum, tot.sumsq, oy, ox, ny, nx, tot.val,
+                          [&](int i, int j) { return keys_half(plane[(size_t)i * pc + j], half, scale, use); });
+    peak_records(res + 4 * half, st, oy, ox, tot.val, z);
 }
 
 // ---- wm_locate_bits: one map per payload bit, two bits per transform -----------------------------------
-
-// k_locate_key_pair: plane[r][c] = (key [tb(tile) == b0], key [tb(tile) == b1]) over the key, (0, 0) outside it.  The tiles lie on
-// the KEY plane by the rule of wm_tiles_shape: tile (min(r / th, tny - 1), min(c / tw, tnx - 1)), the last one of an axis takes the
-// remainder.  b1 = -2 (no entry of the table is below -1): the odd last bit rides alone
-__global__ __launch_bounds__(LB) void k_locate_key_pair(const float* __restrict__ key, int key_rows, int key_cols, const int* __restrict__ tb, int th,
-                                                        int tw, int tny, int tnx, int b0, int b1, float2* __restrict__ plane, int pc)
-{
-    const int c = blockIdx.x * LTX + threadIdx.x % LTX, r = blockIdx.y * LTY + threadIdx.x / LTX;  // (the grid covers pr x pc exactly)
-    float2 v = make_float2(0.0f, 0.0f);
-    if (r < key_rows && c < key_cols) {
-        const int bit = tb[min(r / th, tny - 1) * tnx + min(c / tw, tnx - 1)];
-        const float w = key[(size_t)r * key_cols + c];
-        v = make_float2(bit == b0 ? w : 0.0f, bit == b1 ? w : 0.0f);
-    }
-    plane[(size_t)r * pc + c] = v;
-}
 
 // one block's sums of the two maps of a pair: sum and sum of squares in f64
 struct BitsRec {
@@ -406,7 +480,7 @@ __device__ __forceinline__ void bits_tree(BitsRec* s_b, int t)
 // in the order of the pairs: E's bits do not depend on the batch), and folds each map's sum and sum of squares over the workgroup's
 // 4096 consecutive values into part[block].  use0 / use1 = 0: the bit has no tile (or, use1, the odd last pair has no second bit):
 // its map is exactly zero, not the rounding residue of its partner.  epart (the last pair only): the block's fold of the finished E,
-// as k_locate_peak folds a map.  An unsolvable frame's maps and E are zero
+// as k_locate_map folds a map.  An unsolvable frame's maps and E are zero
 template <bool FIRST>
 __global__ __launch_bounds__(LB) void k_locate_bits_acc(const float2* __restrict__ plane, int pc, int ny, int nx, float scale, const int* __restrict__ status,
                                                         int use0, int use1, float* __restrict__ map0, float* __restrict__ map1, float* __restrict__ E,
@@ -419,14 +493,14 @@ __global__ __launch_bounds__(LB) void k_locate_bits_acc(const float2* __restrict
     const long long i0 = (long long)blockIdx.x * (LB * PEAK_PER);
     const bool dead = status[0] != 0;
     BitsRec me{0.0, 0.0, 0.0, 0.0};
-    PeakRec pk{0.0, 0.0, -1, 0.0f, 0};
+    PeakRec pk = peak_none();
 #pragma unroll 4
     for (int k = 0; k < PEAK_PER; ++k) {
         const long long i = i0 + t + (long long)k * LB;
         if (i >= n) break;
         const int oy = (int)(i / nx), ox = (int)(i % nx);
         const float2 v = dead ? make_float2(0.0f, 0.0f) : plane[(size_t)oy * pc + ox];
-        const float re = use0 ? v.x * scale : 0.0f, im = use1 ? v.y * scale : 0.0f;
+        const float re = keys_half(v, 0, scale, use0), im = keys_half(v, 1, scale, use1);
         map0[i] = re;
         if (map1) map1[i] = im;
         const float e2 = fmaf(im, im, re * re);
@@ -434,10 +508,7 @@ __global__ __launch_bounds__(LB) void k_locate_bits_acc(const float2* __restrict
         E[i] = e;
         me.s0 += (double)re; me.q0 += (double)re * (double)re;
         me.s1 += (double)im; me.q1 += (double)im * (double)im;
-        if (epart) {
-            pk.sum += (double)e; pk.sumsq += (double)e * (double)e;
-            if (pk.idx < 0 || peak_better(e, i, pk.val, pk.idx)) { pk.val = e; pk.idx = i; }
-        }
+        if (epart) peak_take(pk, peak_of(e, i));
     }
     s_b[t] = me;
     bits_tree(s_b, t);
@@ -449,11 +520,10 @@ __global__ __launch_bounds__(LB) void k_locate_bits_acc(const float2* __restrict
     }
 }
 
-// k_locate_bits_fold: workgroup 0 writes the frame's four records of E by k_locate_fold's rule, workgroup 1 + b the soft value of bit
-// b.  Every workgroup folds E's nblk block records itself, in k_locate_fold's order (thread t takes t, t + 256, ... ascending, then
-// the tree): all agree on the argmax o* without waiting for each other.  Bit b: its block records folded the same way, the values of
-// the 3 x 3 block around o* taken out of the sums -- re-read from the stored map, so they are the map's bits --, and
-// soft = (map_b(o*) - mu_b) / sigma_b in f64; NaN when fewer than two offsets lie outside the block or sigma_b is 0.
+// k_locate_bits_fold: workgroup 0 writes the frame's four records of E by k_locate_records' rule, workgroup 1 + b the soft value of
+// bit b.  Every workgroup folds E's nblk block records itself (peak_fold): all agree on the argmax o* without waiting for each
+// other.  Bit b: its block records folded in the same order, the values of the 3 x 3 block around o* taken out of the sums --
+// re-read from the stored map, so they are the map's bits --, and soft = (map_b(o*) - mu_b) / sigma_b by peak_z.
 // part: [pairs][nblk], maps: [nbits][ny nx].  An unsolvable frame: its status and zeros
 __global__ __launch_bounds__(LB) void k_locate_bits_fold(const PeakRec* __restrict__ epart, const BitsRec* __restrict__ part, int nblk,
                                                          const float* __restrict__ E, const float* __restrict__ maps, int ny, int nx,
@@ -462,42 +532,15 @@ __global__ __launch_bounds__(LB) void k_locate_bits_fold(const PeakRec* __restri
     __shared__ PeakRec s_rec[LB];
     __shared__ double s_sum[LB], s_sq[LB];
     const int t = threadIdx.x;
-    PeakRec me{0.0, 0.0, -1, 0.0f, 0};
-    for (int b = t; b < nblk; b += LB) {
-        const PeakRec o = epart[b];
-        me.sum += o.sum; me.sumsq += o.sumsq;
-        if (o.idx >= 0 && (me.idx < 0 || peak_better(o.val, o.idx, me.val, me.idx))) { me.val = o.val; me.idx = o.idx; }
-    }
-    s_rec[t] = me;
-    peak_tree(s_rec, t);
+    peak_fold(epart, nblk, s_rec, t);
     const PeakRec tot = s_rec[0];
     const int st = status[0];
     const int oy = (int)(tot.idx / nx), ox = (int)(tot.idx % nx);
-    const int i_lo = max(oy - 1, 0), i_hi = min(oy + 1, ny - 1), j_lo = max(ox - 1, 0), j_hi = min(ox + 1, nx - 1);
-    const long long n = (long long)ny * nx;
     if (blockIdx.x == 0) {
         if (t != 0) return;
-        if (st != 0) {
-            for (int k = 0; k < 4; ++k) loc[k] = OpResult{st, 0.0f};
-            return;
-        }
-        double sum = tot.sum, sumsq = tot.sumsq;
-        long long cnt = n;
-        for (int i = i_lo; i <= i_hi; ++i)
-            for (int j = j_lo; j <= j_hi; ++j) {
-                const double v = (double)E[(size_t)i * nx + j];
-                sum -= v; sumsq -= v * v; --cnt;
-            }
-        float z = __builtin_nanf("");
-        if (cnt >= 2) {
-            const double mu = sum / (double)cnt;
-            const double var = sumsq / (double)cnt - mu * mu;
-            if (var > 0.0) z = (float)(((double)tot.val - mu) / sqrt(var));
-        }
-        loc[0] = OpResult{0, (float)oy};
-        loc[1] = OpResult{0, (float)ox};
-        loc[2] = OpResult{0, tot.val};
-        loc[3] = OpResult{0, z};
+        float z = 0.0f;
+        if (st == 0) z = peak_z_around(tot.sum, tot.sumsq, oy, ox, ny, nx, tot.val, [&](int i, int j) { return E[(size_t)i * nx + j]; });
+        peak_records(loc, st, oy, ox, tot.val, z);
         return;
     }
     const int bit = (int)blockIdx.x - 1;
@@ -517,149 +560,60 @@ __global__ __launch_bounds__(LB) void k_locate_bits_fold(const PeakRec* __restri
         soft[bit] = OpResult{st, 0.0f};
         return;
     }
-    const float* __restrict__ mp = maps + (size_t)bit * n;
-    sum = s_sum[0]; sumsq = s_sq[0];
-    long long cnt = n;
-    for (int i = i_lo; i <= i_hi; ++i)
-        for (int j = j_lo; j <= j_hi; ++j) {
-            const double v = (double)mp[(size_t)i * nx + j];
-            sum -= v; sumsq -= v * v; --cnt;
-        }
-    float z = __builtin_nanf("");
-    if (cnt >= 2) {
-        const double mu = sum / (double)cnt;
-        const double var = sumsq / (double)cnt - mu * mu;
-        if (var > 0.0) z = (float)(((double)mp[tot.idx] - mu) / sqrt(var));
-    }
-    soft[bit] = OpResult{0, z};
+    const float* __restrict__ mp = maps + (size_t)bit * ((size_t)ny * nx);
+    soft[bit] = OpResult{0, peak_z_around(s_sum[0], s_sq[0], oy, ox, ny, nx, mp[tot.idx], [&](int i, int j) { return mp[(size_t)i * nx + j]; })};
 }
 
-// ---- wm_locate_keys: one map per key of a bank, two keys per transform ---------------------------------
+// the block records of a map of ny x nx offsets, and the scale of an unnormalised forward + inverse transform pair
+int locate_nblk(int ny, int nx) { return (int)(((long long)ny * nx + LB * PEAK_PER - 1) / (LB * PEAK_PER)); }
+float locate_scale(int pr, int pc) { return 1.0f / ((float)pr * (float)pc); }  // (a power of two: the scaling is exact)
 
-// k_locate_keys_pair: plane[r][c] = (keyA[r][c], keyB[r][c]) over the key, (0, 0) outside it; keyB null: the odd last key rides alone.
-// nz[0] / nz[1] (cleared on the stream at the start of the call) is set to 1 by every workgroup that saw a value of key A / key B
-// other than 0: the workgroups store the same value, a later kernel on the stream reads it
-__global__ __launch_bounds__(LB) void k_locate_keys_pair(const float* __restrict__ keyA, const float* __restrict__ keyB, int key_rows, int key_cols,
-                                                         float2* __restrict__ plane, int pc, int* __restrict__ nz)
+using LayF = const float* __restrict__;
+using LayI = const int* __restrict__;
+template <typename Src, typename... A>
+void launch_lay(hipStream_t s, int rows, int cols, float* plane, int pr, int pc, A... a)
 {
-    const int c = blockIdx.x * LTX + threadIdx.x % LTX, r = blockIdx.y * LTY + threadIdx.x / LTX;  // (the grid covers pr x pc exactly)
-    float2 v = make_float2(0.0f, 0.0f);
-    if (r < key_rows && c < key_cols) {
-        const size_t i = (size_t)r * key_cols + c;
-        v = make_float2(keyA[i], keyB ? keyB[i] : 0.0f);
-    }
-    plane[(size_t)r * pc + c] = v;
-    const int anyA = __syncthreads_or(v.x != 0.0f), anyB = __syncthreads_or(v.y != 0.0f);
-    if (threadIdx.x == 0) {
-        if (anyA) nz[0] = 1;
-        if (anyB) nz[1] = 1;
-    }
-}
-
-// the value of one half of the pair's inverse plane at an offset: the product with 1 / (pr pc), or exactly zero for a half that
-// carries no key (its flag is clear, or the odd last key has no partner) -- not the rounding residue of the other half
-__device__ __forceinline__ float keys_half(const float2 v, int half, float scale, bool use) { return use ? (half ? v.y : v.x) * scale : 0.0f; }
-
-// k_locate_keys_peak: the ny x nx admissible offsets of the pair's inverse plane times 1 / (pr pc): the real parts are key A's map,
-// the imaginary parts key B's (mapA / mapB null: not stored; partB null: no key B).  Workgroup b folds values [4096 b, 4096 (b + 1))
-// of each map into partA[b] / partB[b] as k_locate_peak does.  An unsolvable frame's maps are zero
-__global__ __launch_bounds__(LB) void k_locate_keys_peak(const float2* __restrict__ plane, int pc, int ny, int nx, float scale, const int* __restrict__ status,
-                                                         const int* __restrict__ nz, float* __restrict__ mapA, float* __restrict__ mapB,
-                                                         PeakRec* __restrict__ partA, PeakRec* __restrict__ partB)
-{
-    __shared__ PeakRec s_a[LB];
-    __shared__ PeakRec s_b[LB];
-    const int t = threadIdx.x;
-    const long long n = (long long)ny * nx;
-    const long long i0 = (long long)blockIdx.x * (LB * PEAK_PER);
-    const bool dead = status[0] != 0;
-    const bool useA = nz[0] != 0, useB = partB && nz[1] != 0;
-    PeakRec a{0.0, 0.0, -1, 0.0f, 0}, b{0.0, 0.0, -1, 0.0f, 0};
-#pragma unroll 4
-    for (int k = 0; k < PEAK_PER; ++k) {
-        const long long i = i0 + t + (long long)k * LB;
-        if (i >= n) break;
-        const int oy = (int)(i / nx), ox = (int)(i % nx);
-        const float2 v = dead ? make_float2(0.0f, 0.0f) : plane[(size_t)oy * pc + ox];
-        const float re = keys_half(v, 0, scale, useA), im = keys_half(v, 1, scale, useB);
-        if (mapA) mapA[i] = re;
-        if (mapB) mapB[i] = im;
-        a.sum += (double)re; a.sumsq += (double)re * (double)re;
-        if (a.idx < 0 || peak_better(re, i, a.val, a.idx)) { a.val = re; a.idx = i; }
-        b.sum += (double)im; b.sumsq += (double)im * (double)im;
-        if (b.idx < 0 || peak_better(im, i, b.val, b.idx)) { b.val = im; b.idx = i; }
-    }
-    s_a[t] = a;
-    peak_tree(s_a, t);
-    if (t == 0) partA[blockIdx.x] = s_a[0];
-    if (partB) {  // (the same in every lane: a kernel argument)
-        s_b[t] = b;
-        peak_tree(s_b, t);
-        if (t == 0) partB[blockIdx.x] = s_b[0];
-    }
-}
-
-// k_locate_keys_fold: workgroup 0 writes key A's four records, workgroup 1 key B's (grid 1: no key B), each by k_locate_fold's rule
-// on its own block records (part + half * nblk) and its own half of the plane: the values of the 3 x 3 block around the argmax are
-// formed as k_locate_keys_peak formed them, so they are the map's bits.  res: key A's records, key B's follow
-__global__ __launch_bounds__(LB) void k_locate_keys_fold(const PeakRec* __restrict__ part, int nblk, const float2* __restrict__ plane, int pc, int ny,
-                                                         int nx, float scale, const int* __restrict__ status, const int* __restrict__ nz,
-                                                         OpResult* __restrict__ res)
-{
-    __shared__ PeakRec s_rec[LB];
-    const int t = threadIdx.x, half = (int)blockIdx.x;
-    part += (size_t)half * nblk;
-    res += 4 * half;
-    PeakRec me{0.0, 0.0, -1, 0.0f, 0};
-    for (int b = t; b < nblk; b += LB) {
-        const PeakRec o = part[b];
-        me.sum += o.sum; me.sumsq += o.sumsq;
-        if (o.idx >= 0 && (me.idx < 0 || peak_better(o.val, o.idx, me.val, me.idx))) { me.val = o.val; me.idx = o.idx; }
-    }
-    s_rec[t] = me;
-    peak_tree(s_rec, t);
-    if (t != 0) return;
-    const int st = status[0];
-    if (st != 0) {
-        for (int k = 0; k < 4; ++k) res[k] = OpResult{st, 0.0f};
-        return;
-    }
-    const bool use = nz[half] != 0;
-    const PeakRec tot = s_rec[0];
-    const int oy = (int)(tot.idx / nx), ox = (int)(tot.idx % nx);
-    double sum = tot.sum, sumsq = tot.sumsq;
-    long long cnt = (long long)ny * nx;
-    for (int i = max(oy - 1, 0); i <= min(oy + 1, ny - 1); ++i)
-        for (int j = max(ox - 1, 0); j <= min(ox + 1, nx - 1); ++j) {
-            const double v = (double)keys_half(plane[(size_t)i * pc + j], half, scale, use);
-            sum -= v; sumsq -= v * v; --cnt;
-        }
-    res[0] = OpResult{0, (float)oy};
-    res[1] = OpResult{0, (float)ox};
-    res[2] = OpResult{0, tot.val};
-    res[3] = OpResult{0, peak_z(sum, sumsq, cnt, tot.val)};
+    WM_KLAUNCH((k_locate_lay<Src, A...>), dim3(pc / LTX, pr / LTY), dim3(LB), 0, s, rows, cols, reinterpret_cast<float2*>(plane), pc, a...);
 }
 
 }  // namespace
 
-size_t locate_bits_part_bytes(int ny, int nx)
+size_t locate_part_bytes(int ny, int nx) { return (size_t)locate_nblk(ny, nx) * sizeof(PeakRec); }
+size_t locate_bits_part_bytes(int ny, int nx) { return (size_t)locate_nblk(ny, nx) * sizeof(BitsRec); }
+
+void launch_locate_lay(hipStream_t s, const float* src, int rows, int cols, float* plane, int pr, int pc)
 {
-    const long long n = (long long)ny * nx;
-    return (size_t)((n + LB * PEAK_PER - 1) / (LB * PEAK_PER)) * sizeof(BitsRec);
+    launch_lay<LayPlane, LayF>(s, rows, cols, plane, pr, pc, src);
 }
 
-void launch_locate_key_pair(hipStream_t s, const float* key, int key_rows, int key_cols, const int* tile_bit, const TileShape& ts, int b0, int b1,
+void launch_locate_lay_bits(hipStream_t s, const float* key, int key_rows, int key_cols, const int* tile_bit, const TileShape& ts, int b0, int b1,
                             float* plane, int pr, int pc)
 {
-    WM_KLAUNCH(k_locate_key_pair, dim3(pc / LTX, pr / LTY), dim3(LB), 0, s, key, key_rows, key_cols, tile_bit, ts.th, ts.tw, ts.ny, ts.nx, b0, b1,
-               reinterpret_cast<float2*>(plane), pc);
+    launch_lay<LayBits, LayF, LayI, int, int, int, int, int, int>(s, key_rows, key_cols, plane, pr, pc, key, tile_bit, ts.th, ts.tw, ts.ny, ts.nx, b0, b1);
+}
+
+void launch_locate_lay_keys(hipStream_t s, const float* key_a, const float* key_b, int key_rows, int key_cols, float* plane, int pr, int pc, int* nz)
+{
+    launch_lay<LayKeys, LayF, LayF, int*>(s, key_rows, key_cols, plane, pr, pc, key_a, key_b, nz);
+}
+
+void launch_locate_map(hipStream_t s, const float* plane, int pr, int pc, int ny, int nx, const int* status, const int* nz, bool pair, float* map_a,
+                       float* map_b, void* part, OpResult* res)
+{
+    const float scale = locate_scale(pr, pc);
+    const int nblk = locate_nblk(ny, nx);
+    const float2* pl = reinterpret_cast<const float2*>(plane);
+    PeakRec* pa = static_cast<PeakRec*>(part);
+    if (pair) WM_KLAUNCH(k_locate_map<true>, dim3(nblk), dim3(LB), 0, s, pl, pc, ny, nx, scale, status, nz, map_a, map_b, pa, pa + nblk);
+    else WM_KLAUNCH(k_locate_map<false>, dim3(nblk), dim3(LB), 0, s, pl, pc, ny, nx, scale, status, nz, map_a, nullptr, pa, nullptr);
+    if (res) WM_KLAUNCH(k_locate_records, dim3(pair ? 2 : 1), dim3(LB), 0, s, pa, nblk, pl, pc, ny, nx, scale, status, nz, res);
 }
 
 void launch_locate_bits_acc(hipStream_t s, const float* plane, int pr, int pc, int ny, int nx, const int* status, bool first, bool use0, bool use1,
                             float* map0, float* map1, float* energy, void* part, void* epart)
 {
-    const float scale = 1.0f / ((float)pr * (float)pc);  // (a power of two: the scaling is exact)
-    const int nblk = (int)(locate_bits_part_bytes(ny, nx) / sizeof(BitsRec));
+    const float scale = locate_scale(pr, pc);
+    const int nblk = locate_nblk(ny, nx);
     const float2* pl = reinterpret_cast<const float2*>(plane);
     if (first)
         WM_KLAUNCH(k_locate_bits_acc<true>, dim3(nblk), dim3(LB), 0, s, pl, pc, ny, nx, scale, status, use0 ? 1 : 0, use1 ? 1 : 0, map0, map1, energy,
@@ -672,31 +626,8 @@ void launch_locate_bits_acc(hipStream_t s, const float* plane, int pr, int pc, i
 void launch_locate_bits_fold(hipStream_t s, const void* epart, const void* part, int ny, int nx, int nbits, const float* energy, const float* maps,
                              const int* status, OpResult* loc, OpResult* soft)
 {
-    const int nblk = (int)(locate_bits_part_bytes(ny, nx) / sizeof(BitsRec));
-    WM_KLAUNCH(k_locate_bits_fold, dim3(1 + nbits), dim3(LB), 0, s, static_cast<const PeakRec*>(epart), static_cast<const BitsRec*>(part), nblk, energy,
-               maps, ny, nx, status, loc, soft);
-}
-
-void launch_locate_keys_pair(hipStream_t s, const float* key_a, const float* key_b, int key_rows, int key_cols, float* plane, int pr, int pc, int* nz)
-{
-    WM_KLAUNCH(k_locate_keys_pair, dim3(pc / LTX, pr / LTY), dim3(LB), 0, s, key_a, key_b, key_rows, key_cols, reinterpret_cast<float2*>(plane), pc, nz);
-}
-
-void launch_locate_keys_peak(hipStream_t s, const float* plane, int pr, int pc, int ny, int nx, const int* status, const int* nz, bool pair, float* map_a,
-                             float* map_b, void* part, OpResult* res)
-{
-    const float scale = 1.0f / ((float)pr * (float)pc);  // (a power of two: the scaling is exact)
-    const int nblk = (int)(locate_part_bytes(ny, nx) / sizeof(PeakRec));
-    const float2* pl = reinterpret_cast<const float2*>(plane);
-    PeakRec* pa = static_cast<PeakRec*>(part);
-    WM_KLAUNCH(k_locate_keys_peak, dim3(nblk), dim3(LB), 0, s, pl, pc, ny, nx, scale, status, nz, map_a, pair ? map_b : nullptr, pa, pair ? pa + nblk : nullptr);
-    if (res) WM_KLAUNCH(k_locate_keys_fold, dim3(pair ? 2 : 1), dim3(LB), 0, s, pa, nblk, pl, pc, ny, nx, scale, status, nz, res);
-}
-
-size_t locate_part_bytes(int ny, int nx)
-{
-    const long long n = (long long)ny * nx;
-    return (size_t)((n + LB * PEAK_PER - 1) / (LB * PEAK_PER)) * sizeof(PeakRec);
+    WM_KLAUNCH(k_locate_bits_fold, dim3(1 + nbits), dim3(LB), 0, s, static_cast<const PeakRec*>(epart), static_cast<const BitsRec*>(part),
+               locate_nblk(ny, nx), energy, maps, ny, nx, status, loc, soft);
 }
 
 void launch_locate_e(const Sweep& sw, int frame, float* e, float* m)
@@ -741,20 +672,6 @@ void launch_clip_pool_gather(const Sweep& sw, const float* weights, float* pool,
         WM_KLAUNCH((k_clip_pool_gather<T, decltype(mk)::value, decltype(p)::value>), grid, dim3(LB), 0, sw.s, (const T*)x.p, x.pitch, x.fstride, sw.frames,
                    rows, cols, sw.coef, sw.status, weights, pool, accumulate ? 1 : 0, res);
     }));
-}
-
-void launch_locate_key(hipStream_t s, const float* key, int key_rows, int key_cols, float* plane, int pr, int pc)
-{
-    WM_KLAUNCH(k_locate_key, dim3(pc / LTX, pr / LTY), dim3(LB), 0, s, key, key_rows, key_cols, reinterpret_cast<float2*>(plane), pc);
-}
-
-void launch_locate_peak(hipStream_t s, const float* plane, int pr, int pc, int ny, int nx, const int* status, float* map, void* part, OpResult* res)
-{
-    const float scale = 1.0f / ((float)pr * (float)pc);  // (a power of two: the scaling is exact)
-    const int nblk = (int)(locate_part_bytes(ny, nx) / sizeof(PeakRec));
-    const float2* pl = reinterpret_cast<const float2*>(plane);
-    WM_KLAUNCH(k_locate_peak, dim3(nblk), dim3(LB), 0, s, pl, pc, ny, nx, scale, status, map, static_cast<PeakRec*>(part));
-    WM_KLAUNCH(k_locate_fold, dim3(1), dim3(LB), 0, s, static_cast<const PeakRec*>(part), nblk, pl, pc, ny, nx, scale, status, res);
 }
 
 }  // namespace wmk

@@ -366,43 +366,44 @@ void launch_quality(hipStream_t s, const QualityGeom& q, const QualityWeights& w
 constexpr int FFT_LOG_MIN = 6, FFT_LOG_MAX = 13;
 int fft_log2(int n);                   // log2 of a length the row transform takes, -1 for any other n
 void fft_twiddles(int P, float* out);  // [P][2] = exp(-2 pi i t / P), formed in f64 (host)
+// the tables of a [pr][pc] transform on the device (a blocking copy): tw_dev [pr] complex for the columns, then [pc] complex for the rows
+hipError_t fft_twiddles_upload(float* tw_dev, int pr, int pc);
 void launch_fft_rows(hipStream_t s, float* data, int nrows, int P, const float* tw, bool inverse);
 void launch_fft_transpose(hipStream_t s, const float* src, float* dst, int nrows, int ncols);
 void launch_locate_mul(hipStream_t s, float* a, const float* b, size_t n);
-// where a crop sits in its key (wm_locate, wm_k_locate.hip), one frame per launch.  launch_locate_e: the frame's prediction error e
-// (and, under NVF, mask m) as dense [rows][cols] f32 planes, from sw.x with the solve sw.coef / sw.status of that frame.
-// launch_locate_h: h = m * (adjoint of the stencil) e as the real part of the zeroed [pr][pc] complex plane; launch_locate_key: one
-// key plane laid out the same way.  launch_locate_peak: the admissible ny x nx real parts of `plane` times 1 / (pr pc) into map
-// (may be null), and the frame's four records res[0 .. 4) = {oy, ox, peak, z}; part: locate_part_bytes of scratch; status: the frame's
+// where a crop sits in its key (the locate family, wm_k_locate.hip), one frame per launch.  launch_locate_e: the frame's prediction
+// error e (and, under NVF, mask m) as dense [rows][cols] f32 planes, from sw.x with the solve sw.coef / sw.status of that frame.
+// launch_locate_h: h = m * (adjoint of the stencil) e as the real part of the zeroed [pr][pc] complex plane.
+// The key side, a source laid into a zeroed [pr][pc] complex plane: launch_locate_lay, one dense real [rows][cols] plane (a key, or a
+// pooled image side in the place of h) as the real part; launch_locate_lay_bits, the key masked to the tiles of bit b0 (real part) and
+// of bit b1 (imaginary part; -2: none), tile_bit: the DEVICE table over the tiles ts of the KEY plane; launch_locate_lay_keys, key_a
+// (real part) and key_b (imaginary part; null: none), and nz[0] / nz[1], DEVICE ints cleared on the stream beforehand, set to 1 when
+// key_a / key_b holds a value other than 0.
+// launch_locate_map: the admissible ny x nx values of the inverse plane times 1 / (pr pc) into map_a (real parts) and, with pair,
+// map_b (imaginary parts; either may be null), a half whose nz is clear as exact zero (nz null: no flags, key A in use), and the
+// frame's four records {oy, ox, peak, z} of key A into res[0 .. 4), of key B into res[4 .. 8) (res null: the map pass alone); part:
+// locate_part_bytes of scratch per half; status: the frame's
 size_t locate_part_bytes(int ny, int nx);
 void launch_locate_e(const Sweep& sw, int frame, float* e, float* m);
 void launch_locate_h(const Sweep& sw, int frame, const float* e, const float* m, float* plane, int pr, int pc);
-void launch_locate_key(hipStream_t s, const float* key, int key_rows, int key_cols, float* plane, int pr, int pc);
-void launch_locate_peak(hipStream_t s, const float* plane, int pr, int pc, int ny, int nx, const int* status, float* map, void* part,
-                        OpResult* res);
+void launch_locate_lay(hipStream_t s, const float* src, int rows, int cols, float* plane, int pr, int pc);
+void launch_locate_lay_bits(hipStream_t s, const float* key, int key_rows, int key_cols, const int* tile_bit, const TileShape& ts, int b0, int b1,
+                            float* plane, int pr, int pc);
+void launch_locate_lay_keys(hipStream_t s, const float* key_a, const float* key_b, int key_rows, int key_cols, float* plane, int pr, int pc, int* nz);
+void launch_locate_map(hipStream_t s, const float* plane, int pr, int pc, int ny, int nx, const int* status, const int* nz, bool pair, float* map_a,
+                       float* map_b, void* part, OpResult* res);
 // a payload-marked crop (wm_locate_bits): two bits per transform.  launch_locate_mul3: out = conj(h) * k over n complex elements (n
-// even), h and k kept.  launch_locate_key_pair: the key masked to the tiles of bit b0 (real part) and of bit b1 (imaginary part; -2:
-// none) as a zeroed [pr][pc] complex plane; tile_bit: the DEVICE table over the tiles ts of the KEY plane.  launch_locate_bits_acc:
-// the pair's inverse plane into the two maps (map1 null: no second bit; use0 / use1 false: a bit without a tile, whose map is exactly
-// zero) and into energy (first: stored, else added); part: one frame's and pair's block records (locate_bits_part_bytes), epart: the
-// frame's fold of the finished energy map (locate_part_bytes; the last pair only, else null).  launch_locate_bits_fold: the frame's
-// four records of the energy map into loc[0 .. 4) and its soft values into soft[0 .. nbits); part: [pairs][blocks], maps: [nbits][ny nx]
+// even), h and k kept.  launch_locate_bits_acc: the pair's inverse plane into the two maps (map1 null: no second bit; use0 / use1
+// false: a bit without a tile, whose map is exactly zero) and into energy (first: stored, else added); part: one frame's and pair's
+// block records (locate_bits_part_bytes), epart: the frame's fold of the finished energy map (locate_part_bytes; the last pair only,
+// else null).  launch_locate_bits_fold: the frame's four records of the energy map into loc[0 .. 4) and its soft values into
+// soft[0 .. nbits); part: [pairs][blocks], maps: [nbits][ny nx]
 size_t locate_bits_part_bytes(int ny, int nx);
 void launch_locate_mul3(hipStream_t s, const float* h, const float* k, float* out, size_t n);
-void launch_locate_key_pair(hipStream_t s, const float* key, int key_rows, int key_cols, const int* tile_bit, const TileShape& ts, int b0, int b1,
-                            float* plane, int pr, int pc);
 void launch_locate_bits_acc(hipStream_t s, const float* plane, int pr, int pc, int ny, int nx, const int* status, bool first, bool use0, bool use1,
                             float* map0, float* map1, float* energy, void* part, void* epart);
 void launch_locate_bits_fold(hipStream_t s, const void* epart, const void* part, int ny, int nx, int nbits, const float* energy, const float* maps,
                              const int* status, OpResult* loc, OpResult* soft);
-// a crop against a bank of keys (wm_locate_keys): two keys per transform.  launch_locate_keys_pair: key_a (real part) and key_b
-// (imaginary part; null: none) as a zeroed [pr][pc] complex plane; nz[0] / nz[1], DEVICE ints cleared on the stream beforehand, are
-// set to 1 when key_a / key_b holds a value other than 0.  launch_locate_keys_peak: the pair's inverse plane into map_a and map_b
-// (either may be null; pair false: no key_b), a half whose nz is clear as exact zero, and the frame's four records of key_a into
-// res[0 .. 4), of key_b into res[4 .. 8) (res null: the map pass alone); part: 2 * locate_part_bytes of scratch; status: the frame's
-void launch_locate_keys_pair(hipStream_t s, const float* key_a, const float* key_b, int key_rows, int key_cols, float* plane, int pr, int pc, int* nz);
-void launch_locate_keys_peak(hipStream_t s, const float* plane, int pr, int pc, int ny, int nx, const int* status, const int* nz, bool pair, float* map_a,
-                             float* map_b, void* part, OpResult* res);
 // the frames of a clip pooled on the image side (wm_clip_pool), one launch per call: pool = fmaf(w_f, h_f, pool) over the solvable
 // frames of sw in ascending order, h_f being launch_locate_e's and launch_locate_h's bit for bit; pool: a dense DEVICE
 // [rows][cols] f32 plane, started from 0.0f unless accumulate; weights: DEVICE [frames]; res[0 .. frames): the frames' status records
