@@ -318,8 +318,9 @@ int wm_detect_offsets(wm_ctx* ctx, int mask, const wm_plane* img, const wm_keys*
  *     peak     map[oy][ox]: the detector's <e_u, e_w> against the window at (oy, ox), to the f32 transform's rounding
  *     z        (float)((peak - mu) / sigma), mu and sigma the f64 mean and population standard deviation of the map over the
  *              offsets OUTSIDE the 3 x 3 block around the argmax (the prediction filter smears the peak over its neighbours);
- *              NaN when fewer than two offsets lie outside that block or sigma = 0 (a zero key, a flat frame, key == image)
- * status_out[frames] (may be NULL).  An unsolvable frame has status WM_UNSOLVABLE, {0, 0, 0, 0} and a zero map.  A marked crop
+ *              NaN when fewer than two offsets lie outside that block or sigma = 0 (a zero key, key == image)
+ * status_out[frames] (may be NULL).  An unsolvable frame -- a flat frame is one -- has status WM_UNSOLVABLE, {0, 0, 0, 0} (z = 0, not
+ * NaN) and a zero map.  A marked crop
  * reaches z of 20-60, an unmarked one stays below 5; wm_detect_offsets with ny = nx = 1 at (oy, ox) then gives
  * the score.  A payload-marked copy (wm_embed_bits) has tiles of both signs whose contributions cancel in a whole-frame map:
  * wm_locate_bits below finds and reads such a copy.

@@ -404,6 +404,91 @@ int wmo_nvf_mask(const float* x, int rows, int cols, int p, float* m)
     return WMO_OK;
 }
 
+/* the pixels p of one axis with clamp(p + d) == q, in the order the locate kernels' adjoint_set lists them: q - d when it is in
+ * range, then the border pixel once more when q is that border and d points outwards.  Returns their count (0 .. 2) */
+static int locate_adjoint_set(int q, int d, int n, int out[2])
+{
+    int cnt = 0;
+    const int p = q - d;
+    if (p >= 0 && p < n) out[cnt++] = p;
+    if (d == -1 && q == 0) out[cnt++] = 0;
+    if (d == 1 && q == n - 1) out[cnt++] = n - 1;
+    return cnt;
+}
+
+/*
+ * The image side of the crop search (wm_locate, wm_clip_pool; no counterpart in the reference), one frame, in f32 with the
+ * DEVICE's operation sequence (wm_k_locate.hip locate_g / locate_h_value, wm_device.hpp residual1), so that a one-frame
+ * wm_clip_pool can be held against it float for float:
+ *   e  the chain starts at the centre pixel and runs over the NEGATED coefficients, eight fmaf in the tap order up-left, up,
+ *      up-right, left, right, down-left, down, down-right, replicate borders.  NOT wmo_error_sequence: that one forms the
+ *      prediction from 0 and subtracts once (x - chain), which rounds differently by a few ulp of the pixel value
+ *   g  starts at e(q); for k = 0..7 in row-major tap order s = 0.0f + the e of every pixel p with clamp(p + d_k) == q (rows of the
+ *      set outside, columns inside, each in locate_adjoint_set's order), then g = fmaf(-c_k, s, g): the exact adjoint of the
+ *      replicate-border stencil
+ *   m  |e| under ME, wmo_nvf_mask of window p under NVF
+ *   h  m * g, one rounding
+ * e, g, m, h: [rows][cols], each may be NULL.
+ */
+int wmo_locate_h(const float* x, int rows, int cols, const float c[8], int mask, int p, float* e_out, float* g_out, float* m_out,
+                 float* h_out)
+{
+    if (mask != WMO_MASK_ME && mask != WMO_MASK_NVF) return WMO_BAD_ARG;
+    if (mask == WMO_MASK_NVF && p != 3 && p != 5 && p != 7 && p != 9) return WMO_BAD_ARG;
+    const size_t n = (size_t)rows * cols;
+    float* e = (float*)malloc(n * sizeof(float));
+    float* m = (float*)malloc(n * sizeof(float));
+    if (!e || !m) { free(e); free(m); return WMO_BAD_ARG; }
+    float nc[8];
+    for (int k = 0; k < 8; k++) nc[k] = -c[k];
+#pragma omp parallel for schedule(static)
+    for (int r = 0; r < rows; r++) {
+        const float* up = x + (size_t)clampi(r - 1, 0, rows - 1) * cols;
+        const float* mid = x + (size_t)r * cols;
+        const float* dn = x + (size_t)clampi(r + 1, 0, rows - 1) * cols;
+        for (int cc = 0; cc < cols; cc++) {
+            const int cm = cc > 0 ? cc - 1 : 0;
+            const int cp = cc < cols - 1 ? cc + 1 : cols - 1;
+            float d = fmaf(nc[0], up[cm], mid[cc]);
+            d = fmaf(nc[1], up[cc], d);
+            d = fmaf(nc[2], up[cp], d);
+            d = fmaf(nc[3], mid[cm], d);
+            d = fmaf(nc[4], mid[cp], d);
+            d = fmaf(nc[5], dn[cm], d);
+            d = fmaf(nc[6], dn[cc], d);
+            d = fmaf(nc[7], dn[cp], d);
+            e[(size_t)r * cols + cc] = d;
+        }
+    }
+    if (mask == WMO_MASK_NVF) wmo_nvf_mask(x, rows, cols, p, m);
+    else
+        for (size_t i = 0; i < n; i++) m[i] = fabsf(e[i]);
+#pragma omp parallel for schedule(static)
+    for (int r = 0; r < rows; r++) {
+        for (int cc = 0; cc < cols; cc++) {
+            const size_t q = (size_t)r * cols + cc;
+            float g = e[q];
+            for (int k = 0; k < 8; k++) {
+                const int t = k < 4 ? k : k + 1; /* the 3x3 taps in row-major order without the centre */
+                const int dr = t / 3 - 1, dc = t % 3 - 1;
+                int pr[2], pc[2];
+                const int nr = locate_adjoint_set(r, dr, rows, pr), ncn = locate_adjoint_set(cc, dc, cols, pc);
+                float s = 0.0f;
+                for (int a = 0; a < nr; a++)
+                    for (int b = 0; b < ncn; b++) s += e[(size_t)pr[a] * cols + pc[b]];
+                g = fmaf(-c[k], s, g);
+            }
+            if (g_out) g_out[q] = g;
+            if (h_out) h_out[q] = m[q] * g;
+        }
+    }
+    if (e_out) memcpy(e_out, e, n * sizeof(float));
+    if (m_out) memcpy(m_out, m, n * sizeof(float));
+    free(e);
+    free(m);
+    return WMO_OK;
+}
+
 /*
  * computePredictionErrorMask (Watermark.cpp:176-218): coefficients, error sequence and
  * (optionally) m = |e| / max|e|.  e, m may be NULL.  Returns WMO_UNSOLVABLE for a

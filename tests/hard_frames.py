@@ -16,8 +16,12 @@ Families:
   impulse      a low-contrast frame with one pixel at 0 or 255 at a structural spot (corner, strip / segment / tile / band
                seam, shifted last strip): max|e| sits at that pixel, so a reduction that drops it changes the whole mask
   zero-energy  frames and W for which u = m W vanishes: ||u|| = 0, a = +inf
+  hard crops   the families above as crops for the crop search (wm_locate, wm_clip_pool and their siblings): a frame of the key's
+               shape marked at psnr 40, cropped at a known offset and paired with its unmarked twin, at three geometries that hold
+               every tile edge of the pool kernel; impulse crops with the pixel on every corner, edge and tile seam
 
-Only numpy and synth (the package's generator) are used: these frames are built the same way on every machine.
+Only numpy and synth (the package's generator) are used, and np_restatement to mark the hard crops: these frames are built the
+same way on every machine.
 """
 import numpy as np
 
@@ -223,3 +227,135 @@ def zero_w(rows, cols):
 
 def watermark(rows, cols):
     return synth_watermark(rows, cols)
+
+
+# ---- hard crops for the crop search (wm_locate, wm_clip_pool and their siblings) ------------------------------------------------
+# (key shape, crop shape, true offset): between them every tile edge of k_clip_pool's 64 x 16 tiles occurs -- whole tiles, one
+# column and one row past a tile edge, and a last tile of two columns and one row
+LOCATE_GEOMS = (((120, 330), (64, 256), (20, 31)), ((140, 330), (65, 257), (75, 73)), ((100, 200), (33, 66), (5, 7)))
+LOCATE_CONFIGS = ((0, 3), (1, 3), (1, 5), (1, 9))  # (mask, p): ME, and NVF at three windows (9: the gather path above window 3)
+LOCATE_PSNR = 40.0  # ... of the marking; 30 for the 33 x 66 crop (locate_psnr)
+LOCATE_BAR = 12  # rows / columns a bar reaches into the crop
+# family -> (findable at psnr 40, has a u8 variant).  binary: the clamp takes the mark away (every pixel sits at 0 or 255), so a
+# search cannot find it: parity only
+LOCATE_FAMILIES = {"texture": (True, True), "clipped": (True, True), "letterbox": (True, True), "pillar": (True, True),
+                   "binary": (False, True), "near_singular": (True, False), "low_contrast": (True, False)}
+# the figures of the restatement of h (oracle wmo_locate_h) against the f64 model, measured by tests/test_locate_model.py, which
+# asserts that no case exceeds them: (largest |dh| / max|h|, largest map difference in sigma_W) per family.  The GPU tests build
+# their second map bound and the pool bound of test_gpu_locate_clip.py from them
+RESTATEMENT_FIGURES = {"texture": (8e-7, 3e-6), "clipped": (5e-7, 2e-6), "letterbox": (7e-7, 4e-6), "pillar": (9e-7, 3e-6),
+                       "binary": (4e-7, 2e-6), "near_singular": (1.9e-5, 5.6e-5), "low_contrast": (3.3e-6, 1.6e-5),
+                       "impulse": (8e-7, 1.1e-5)}
+_crops = {}
+
+
+def locate_psnr(shape):
+    """psnr 40; 30 for the crop of 33 x 66: z grows with the square root of the crop's area, and at psnr 40 its 2178 pixels leave
+    even plain texture below z = 10 (9.6; clipped 5.1), so that no frame index or bar width could make its cases findable"""
+    return LOCATE_PSNR if shape[0] * shape[1] >= 64 * 256 else 30.0
+
+
+def locate_key(kshape):
+    """the key of a shape (tests/locate_clip_model.py key_of)"""
+    return synth_watermark(*kshape, seed=9100 + 7 * kshape[0] + kshape[1])
+
+
+def locate_base(family, kshape, shape, at, frame=0):
+    """the unmarked f32 frame of the key's shape of one family; the bars end LOCATE_BAR rows / columns inside the crop at `at`.
+    near_singular on the 33 x 66 crop has +-1 pixels at a density of 0.1, not 0.03: under ME the mark itself is most of such a
+    frame's prediction error, z does not grow with the strength, and at 0.03 the small crop stays at z = 8 (pivot ratio 1e-5; at
+    0.1 z = 15.6, pivot ratio 3e-5: still three orders from an ordinary frame)"""
+    kr, kc = kshape
+    if family == "texture":
+        return synth_frame(kr, kc, frame=10 + frame)
+    if family == "clipped":
+        return clipped(kr, kc, frame=frame)
+    if family == "letterbox":
+        x = synth_frame(kr, kc, frame=frame).astype(np.float32)
+        x[:at[0] + LOCATE_BAR] = 16.0
+        return x
+    if family == "pillar":
+        x = synth_frame(kr, kc, frame=frame).astype(np.float32)
+        x[:, :at[1] + LOCATE_BAR] = 0.0
+        return x
+    if family == "binary":
+        return binary(kr, kc, seed=frame)
+    if family == "near_singular":
+        return near_singular(kr, kc, density=0.03 if shape[0] * shape[1] >= 64 * 256 else 0.1, seed=frame)
+    if family == "low_contrast":
+        return low_contrast(kr, kc, frame=frame)
+    raise ValueError(family)
+
+
+def locate_crops(kshape, shape, at, mask, p):
+    """{name: (marked crop, unmarked twin)}: every family's frame of the key's shape marked with np_restatement.embed (the shape's
+    key, window p, locate_psnr) and cropped at `at`, beside the same crop of the unmarked frame.  name is the family (f32 crops) or
+    family + '_u8' (both floored to uint8)"""
+    import np_restatement as NP  # (the marking only; the frames themselves are numpy and synth)
+    tag = (kshape, shape, at, mask, p)
+    if tag not in _crops:
+        (r, c), (oy, ox) = shape, at
+        key = locate_key(kshape)
+        out = {}
+        for family, (_, has_u8) in LOCATE_FAMILIES.items():
+            x = locate_base(family, kshape, shape, at)
+            y = NP.embed(x, x, key, p, locate_psnr(shape), "ME" if mask == 0 else "NVF")[0]
+            cy, cx = (np.ascontiguousarray(v[oy:oy + r, ox:ox + c], np.float32) for v in (y, x))
+            out[family] = (cy, cx)
+            if has_u8:
+                out[family + "_u8"] = (np.floor(cy).astype(np.uint8), np.floor(cx).astype(np.uint8))
+        if len(_crops) >= 4:
+            _crops.clear()
+        _crops[tag] = out
+    return _crops[tag]
+
+
+def locate_family(name):
+    return name[:-3] if name.endswith("_u8") else name
+
+
+def locate_bar_zero(name, shape, p, marked):
+    """boolean [R, C]: the crop's pixels whose NVF window of p lies in bar pixels that the marking left alone (the marking moves
+    the bar pixels whose own window reaches the picture), or None for a family without a bar"""
+    pad = p // 2
+    k = LOCATE_BAR - pad - (pad if marked else 0)
+    z = np.zeros(shape, bool)
+    if locate_family(name) == "letterbox":
+        z[:max(k, 0)] = True
+    elif locate_family(name) == "pillar":
+        z[:, :max(k, 0)] = True
+    else:
+        return None
+    return z
+
+
+def locate_impulse_spots(shape):
+    """named crop coordinates where the image side of the crop search can go wrong: the corners, the middle of every edge, (1, 1),
+    the seams of k_clip_pool's 64 x 16 tiles and of k_locate_e's 64 x 4 blocks, the first pixel of the last partial tile -- each
+    one that exists in the shape, each position once"""
+    R, C = shape
+    rm, cm = R // 2, C // 2
+    cand = [("corner_tl", (0, 0)), ("corner_tr", (0, C - 1)), ("corner_bl", (R - 1, 0)), ("corner_br", (R - 1, C - 1)),
+            ("top", (0, cm)), ("bottom", (R - 1, cm)), ("left", (rm, 0)), ("right", (rm, C - 1)), ("r1_c1", (1, 1))]
+    cand += [(f"seam_r{a}_c{b}", (a, b)) for (a, b) in ((15, 63), (15, 64), (16, 63), (16, 64), (3, 64), (4, 63))]
+    if R % 16 or C % 64:
+        cand.append(("last_tile", ((R - 1) // 16 * 16, (C - 1) // 64 * 64)))
+    out, seen = {}, set()
+    for name, (a, b) in cand:
+        if a < R and b < C and (a, b) not in seen:
+            seen.add((a, b))
+            out[name] = (a, b)
+    return out
+
+
+def locate_impulses(kshape, shape, at, dtype=np.float32):
+    """(frames [F, R, C], [(name, r, c)]): the low-contrast crop with one pixel at 255 or 0 per frame (impulse)"""
+    (r, c), (oy, ox) = shape, at
+    base = low_contrast(*kshape)[oy:oy + r, ox:ox + c]
+    xs, items = [], []
+    for f, (name, (a, b)) in enumerate(locate_impulse_spots(shape).items()):
+        x = base.copy()
+        x[a, b] = 255.0 if f % 2 == 0 else 0.0
+        xs.append(_u8(x) if dtype == np.uint8 else x)
+        items.append((name, a, b))
+    return np.stack(xs), items

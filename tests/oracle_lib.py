@@ -48,6 +48,7 @@ def lib():
         L.wmo_error_sequence.argtypes = [fp, C.c_int, C.c_int, fp, fp]
         L.wmo_error_sequence.restype = None
         L.wmo_nvf_mask.argtypes = [fp, C.c_int, C.c_int, C.c_int, fp]
+        L.wmo_locate_h.argtypes = [fp, C.c_int, C.c_int, fp, C.c_int, C.c_int, fp, fp, fp, fp]
         L.wmo_me_mask.argtypes = [fp, C.c_int, C.c_int, fp, fp, fp, fp, op]
         L.wmo_embed.argtypes = [fp, fp, C.c_int, fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, fp, fp, fp, op]
         L.wmo_detect.argtypes = [fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, fp, op]
@@ -143,6 +144,18 @@ def nvf_mask(x, p=3):
     if st != 0:
         raise ValueError("bad p")
     return m
+
+
+def locate_h(x, c, mask=MASK_ME, p=3):
+    """one frame's image side of the crop search in f32 with the device's operation sequence (wm_oracle.c wmo_locate_h):
+    returns (e, g, m, h), h = m g"""
+    x = _c32(x)
+    c = _c32(c)
+    e, g, m, h = (np.empty_like(x) for _ in range(4))
+    st = lib().wmo_locate_h(_f(x), x.shape[0], x.shape[1], _f(c), int(mask), p, _f(e), _f(g), _f(m), _f(h))
+    if st != 0:
+        raise ValueError("bad mask or p")
+    return e, g, m, h
 
 
 def me_mask(x, **kw):

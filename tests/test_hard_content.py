@@ -277,3 +277,77 @@ def test_non_integer_flat_frame_is_not_zero_energy():
     yn, an = NP.embed(x, x, W, mask="NVF")
     assert a == pytest.approx(an, rel=1e-5)
     np.testing.assert_allclose(y, yn, rtol=0, atol=2e-3)
+
+
+# ---- hard crops of the crop search ----------------------------------------------------------------------------------------
+Z_FOUND, Z_NOISE = 10.0, 6.0
+
+
+@pytest.mark.parametrize("mask,p", H.LOCATE_CONFIGS)
+@pytest.mark.parametrize("kshape,shape,at", H.LOCATE_GEOMS)
+def test_locate_crops_self_check(kshape, shape, at, mask, p):
+    """the facts the GPU tests of the crop search lean on, with the f64 model and np_restatement's coefficients: every marked crop
+    but `binary` has its argmax at the true offset with z >= 10, every unmarked crop z <= 6, and the marked `binary` crop z <= 6 --
+    the clamp takes the mark away, which is why it is a parity-only family.  Measured over the three geometries, marked z (ME /
+    NVF) and the largest unmarked z: texture 18-28 / 22-26, 4.7; clipped 11.5-14.5 / 10.6-13.6, 4.3; letterbox 13-33 / 17-34, 4.2;
+    pillar 15-30 / 21-27, 4.4; near_singular 16-24 / 40-113, 4.3; low_contrast 25-59 / 40-91, 4.3; binary 3.4-4.0 / 3.5-3.7, 4.0"""
+    import locate_model as M
+    key = H.locate_key(kshape)
+    crops = H.locate_crops(kshape, shape, at, mask, p)
+    assert {H.locate_family(n) for n in crops} == set(H.LOCATE_FAMILIES)
+    for name, (marked, plain) in crops.items():
+        findable, has_u8 = H.LOCATE_FAMILIES[H.locate_family(name)]
+        assert marked.shape == shape and plain.shape == shape and marked.dtype == plain.dtype
+        assert marked.dtype == (np.uint8 if name.endswith("_u8") else np.float32) and (has_u8 or not name.endswith("_u8"))
+        xm, xp = marked.astype(np.float32), plain.astype(np.float32)
+        _, (oy, ox, _, z) = M.locate(xm, key, NP.coefficients(xm), mask, p)
+        _, (_, _, _, zu) = M.locate(xp, key, NP.coefficients(xp), mask, p)
+        print(f"{kshape}->{shape}@{at} mask {mask} p {p} {name}: marked ({oy}, {ox}) z {z:.1f}; unmarked z {zu:.2f}")
+        if findable:
+            assert (oy, ox) == at and z >= Z_FOUND, name
+        else:
+            assert z <= Z_NOISE, name
+        assert zu <= Z_NOISE, name
+        fam = H.locate_family(name)
+        if fam == "clipped":
+            assert ((xp == 0) | (xp == 255)).mean() >= 0.1 and ((xm == 0) | (xm == 255)).mean() >= 0.1
+        if fam == "binary":
+            assert set(np.unique(xp)) == {0.0, 255.0} and ((xm == 0) | (xm == 255)).mean() >= 0.4
+        if fam in ("letterbox", "pillar"):
+            bar = xp[:H.LOCATE_BAR] if fam == "letterbox" else xp[:, :H.LOCATE_BAR]
+            rest = xp[H.LOCATE_BAR:] if fam == "letterbox" else xp[:, H.LOCATE_BAR:]
+            level = 16.0 if fam == "letterbox" else 0.0
+            assert (bar == level).all() and (rest != level).mean() > 0.9
+            # under NVF the mask is exactly 0 where the GPU tests expect a pool of exactly 0 (an ME mark moves the whole bar)
+            for mk, x in ((True, xm), (False, xp)) if mask == 1 else ((False, xp),):
+                zero = H.locate_bar_zero(name, shape, p, mk)
+                assert zero.sum() > 0 and (O.nvf_mask(x, p)[zero] == 0).all()
+        if fam == "near_singular":
+            ratio = H.pivot_ratio(O.gram(xp)[0])
+            assert 1e-10 <= ratio <= 1e-4
+
+
+@pytest.mark.parametrize("kshape,shape,at", H.LOCATE_GEOMS)
+def test_locate_impulse_self_check(kshape, shape, at):
+    """every impulse crop is solvable and, under every (mask, p), has its largest |h| within one pixel of the planted pixel; the
+    spots cover the corners, the edges, k_clip_pool's tile seams and the last partial tile where the shape has them"""
+    import locate_model as M
+    spots = H.locate_impulse_spots(shape)
+    assert {"corner_tl", "corner_tr", "corner_bl", "corner_br", "top", "bottom", "left", "right", "r1_c1"} <= set(spots)
+    if shape[0] > 16 and shape[1] > 64:
+        assert {"seam_r15_c63", "seam_r15_c64", "seam_r16_c63", "seam_r16_c64", "seam_r3_c64", "seam_r4_c63"} <= set(spots)
+    if shape == (33, 66):
+        assert spots["last_tile"] == (32, 64)
+    assert len(set(spots.values())) == len(spots)
+    for dtype in (np.float32, np.uint8):
+        xs, items = H.locate_impulses(kshape, shape, at, dtype)
+        assert xs.dtype == dtype and len(xs) == len(spots)
+        for x, (name, r, c) in zip(xs, items):
+            x = x.astype(np.float32)
+            assert x[r, c] in (0.0, 255.0)
+            cf = NP.coefficients(x)
+            assert H.pivot_ratio(O.gram(x)[0]) >= 1e-6
+            for mask, p in H.LOCATE_CONFIGS:
+                h = np.abs(M.h_plane(x, cf, mask, p))
+                rr, cc = np.unravel_index(int(np.argmax(h)), h.shape)
+                assert max(abs(rr - r), abs(cc - c)) <= 1, (name, mask, p, (rr, cc))

@@ -6,8 +6,10 @@ map, while an unmarked crop's map has no such peak."""
 import numpy as np
 import pytest
 
+import hard_frames as H
 import locate_model as M
 import np_restatement as R
+import oracle_lib as O
 from synth import synth_frame, synth_watermark
 
 # (key shape, crop shape, true offset, floored to 8 bits)
@@ -65,6 +67,85 @@ def test_argmax_is_the_true_offset(kshape, shape, at, floored, mask):
     for (i, j) in ((0, 0), at, (mp.shape[0] - 1, mp.shape[1] - 1)):
         direct = float(np.sum(h * W[i:i + shape[0], j:j + shape[1]]))
         assert abs(mp[i, j] - direct) <= 1e-9 * np.sqrt(np.sum(h * h) * np.sum(W.astype(np.float64) ** 2))
+
+
+U32 = 2.0 ** -24  # half an ulp of 1 in f32: the relative error of one rounding
+RESTATED_MAP_BOUND = 8.3e-5  # of sigma_W: 1.5 x the largest measured figure (test_restated_h_against_the_f64_model)
+
+
+def restated_h_bound(c, e, g, m, h, mask):
+    """how far the f32 restatement of h may lie from the f64 model, from the roundings it makes (u = 2^-24 per rounding):
+      e  eight fmaf whose partial results stay below 255 (1 + sum |c|):                    de <= 8 u 255 (1 + sum |c|)
+      g  the model's g of the restated e is linear in e with gain A4 = 1 + 4 sum |c| (a corner's adjoint sets hold four pixels);
+         the set sums (three additions of values below 4 max|e|) and eight fmaf whose partial results stay below A4 max|e|:
+                                                                                             dg <= A4 de + 20 u A4 max|e|
+      m  ME: |e|, dm = de; NVF: the two f32 restatements of the mask agree to 1e-6 (test_oracle.py)
+      h  one product:                                                     dh <= max m dg + max|g| dm + u max|h| + dm dg"""
+    a = float(np.abs(np.asarray(c, np.float64)).sum())
+    de = 8 * U32 * 255.0 * (1 + a)
+    a4 = 1 + 4 * a
+    dg = a4 * de + 20 * U32 * a4 * float(np.abs(e).max())
+    dm = de if mask == 0 else 1e-6
+    return float(np.abs(m).max()) * dg + float(np.abs(g).max()) * dm + U32 * float(np.abs(h).max()) + dm * dg
+
+
+def restated_case(x, key, mask, p):
+    """(|dh| / max|h|, its bound / max|h|, map difference / sigma_W) of one crop: the oracle's f32 restatement of h with the device's
+    operation sequence against locate_model.h_plane, both with np_restatement's coefficients"""
+    x = np.asarray(x, np.float32)
+    c = R.coefficients(x)
+    e, g, m, h = O.locate_h(x, c, mask, p)
+    want = M.h_plane(x, c, mask, p)
+    hmax = float(np.abs(want).max())
+    err = float(np.abs(h.astype(np.float64) - want).max())
+    bound = restated_h_bound(c, e, g, m, h, mask)
+    assert err <= bound, (err, bound)
+    sw = M.sigma_w(x, key, c, mask, p)
+    dmap = float(np.abs(M.correlate(h.astype(np.float64), key) - M.correlate(want, key)).max()) / sw
+    return err / hmax, bound / hmax, dmap
+
+
+@pytest.mark.parametrize("mask,p", H.LOCATE_CONFIGS)
+@pytest.mark.parametrize("kshape,shape,at", H.LOCATE_GEOMS)
+def test_restated_h_against_the_f64_model(kshape, shape, at, mask, p):
+    """wmo_locate_h (f32, the device's operation sequence) against h_plane (f64) per pixel on every hard crop family: within the
+    bound that follows from its roundings (restated_h_bound), and the maps of the two within RESTATED_MAP_BOUND.  Measured over
+    the three geometries and four (mask, p), marked and unmarked, |dh| / max|h| and the map difference in sigma_W:
+      texture 7.8e-7 / 2.6e-6, clipped 4.8e-7 / 1.9e-6, letterbox 6.9e-7 / 3.2e-6, pillar 8.1e-7 / 2.7e-6, binary 3.1e-7 / 1.4e-6,
+      near_singular 1.8e-5 / 5.5e-5, low_contrast 3.2e-6 / 1.5e-5, impulse 7.1e-7 / 1.0e-5
+    (hard_frames.RESTATEMENT_FIGURES holds them rounded up; no case may exceed its family's figure).  The near-singular map
+    figure, 5.5e-5, lies above the 4.3e-5 of the numpy emulation the bound of 6e-5 was first drawn from (that one ran one geometry
+    at p = 3), so the bound is 1.5 x the measured figure: 8.3e-5 sigma_W"""
+    key = H.locate_key(kshape)
+    worst = {}
+
+    def take(family, x):
+        rel, bnd, dmap = restated_case(x, key, mask, p)
+        w = worst.setdefault(family, [0.0, 0.0, 0.0])
+        w[0], w[1], w[2] = max(w[0], rel), max(w[1], bnd), max(w[2], dmap)
+
+    for name, (marked, plain) in H.locate_crops(kshape, shape, at, mask, p).items():
+        take(H.locate_family(name), marked)
+        take(H.locate_family(name), plain)
+    for x in H.locate_impulses(kshape, shape, at)[0]:
+        take("impulse", x)
+    for family, (rel, bnd, dmap) in worst.items():
+        fig = H.RESTATEMENT_FIGURES[family]
+        print(f"{kshape}->{shape}@{at} mask {mask} p {p} {family}: |dh| {rel:.2e} of max|h| (bound {bnd:.2e}, figure {fig[0]:.1e}); maps {dmap:.2e} sigma_W "
+              f"(figure {fig[1]:.1e})")
+        assert dmap <= RESTATED_MAP_BOUND and fig[1] <= RESTATED_MAP_BOUND
+        assert rel <= fig[0] and dmap <= fig[1]
+
+
+def test_restated_h_is_not_the_oracle_error_sequence():
+    """wmo_locate_h's e (the chain from the centre pixel) and wmo_error_sequence (x - the chain from 0) differ in some pixels by a
+    few ulp: the reason the restatement forms its own e"""
+    kshape, shape, at = H.LOCATE_GEOMS[0]
+    x = H.locate_crops(kshape, shape, at, 0, 3)["texture"][0]
+    c = R.coefficients(x)
+    e = O.locate_h(x, c, 0, 3)[0]
+    d = np.abs(e - O.error_sequence(x, c))
+    assert 0 < d.max() <= 8 * 2.0 ** -23 * 255.0 and (d > 0).mean() > 0.01
 
 
 def test_adjoint_is_the_transpose_of_the_stencil():
